@@ -24,7 +24,13 @@ the timed loop).  `value` = dcf of all ranks / wall time of the K timed steps.
 (geometry.host_descriptor_ms, outside the step) and its 66 MB re-uploaded every step.  ("state": "stats
 out"; --xi-out times the same step with the full responses downloaded too.)
 
-Also on the JSON line:
+A plain run (`bench.py --gpus 1 --steps K --warmup W`) sets up, primes and warms up, times the K steps and
+prints the line; the only check it makes is that no timed step flagged a NaN.  --dump-outputs DIR also writes
+what the last timed step returned (std, niter, flags, strips_per_design; Xi with --xi-out; the gathered
+std_all with N > 1) as DIR/<name>.npy in float64.  The inputs depend only on the arguments, so two builds can be
+compared output for output.
+
+With --full (and filtered by --legs / --no-extra-legs / --no-cpu-baseline), also on the JSON line:
   kernel_resident   the fused kernel alone on the whole batch with inputs and outputs
                     resident in HBM (what round 1 reported as `value`), only with --resident
                     (kept out of the default run so that the rocprofv3 average of
@@ -33,6 +39,7 @@ Also on the JSON line:
                     region: algorithmic bytes (SURVEY.md 8d A_min) / summed HIP-event
                     durations vs HBM peak;  roofline_fp64_valu the same with the
                     algorithmic FLOPs vs the fp64 vector peak (the kernel is VALU-bound);
+  isolated_call     the same step as one blocking call; the timed batch solved again alone must give the same bits;
   parity            every design of the timed batch against the CPU oracle (RAO
                     group-relative error, iteration counts), the first 64 against the
                     live reference's own solveDynamics (tests/golden/c3_variants.npz);
@@ -58,6 +65,9 @@ Also on the JSON line:
   c2_dropin / c4_farm / c5_qtf   BASELINE.json's configs[1], [3], [4] at their specified sizes (bench_legs.py),
                     each against its committed live-reference golden and with the roofline of its own kernel;
   flex_sweep        a batch of units with flexible members (150 reduced DOFs) against the drop-in and its golden.
+
+With N > 1 and --full the line also carries single_rank_same_invocation / scaling_efficiency and
+strong_same_invocation (see below).
 
 Multi-GPU: one process per GPU; designs are block-partitioned over ranks, no
 collective while solving; the statistics are gathered onto rank 0 INSIDE the
@@ -89,6 +99,33 @@ if ROOT not in sys.path:
 HBM_PEAK_GBS = 8000.0          # MI355X_MICROARCH.md: 8 TB/s spec
 FP64_VALU_PEAK_TF = 78.6       # MI355X vector fp64 peak
 FP64_FMA_SUSTAINED_TF = 50.8      # measured: profiles/r02_valu_mfma_probe.jsonl (probe fma64)
+DUMP_BUDGET_BYTES = 64 << 20      # --dump-outputs: what the files may hold in all
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: every array of ``arrays`` (name -> array whose first axis is the design) as dirname/<name>.npy in
+    float64 (complex arrays as <name>_re / <name>_im).  Where the whole would pass DUMP_BUDGET_BYTES, every array keeps
+    the same fixed sample of designs (default_rng(0), sorted) and design_index.npy names them."""
+    out = {}
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        if np.iscomplexobj(a):
+            out[name + "_re"], out[name + "_im"] = a.real.astype(np.float64), a.imag.astype(np.float64)
+        else:
+            out[name] = a.astype(np.float64)
+    n = {a.shape[0] for a in out.values()}
+    assert len(n) == 1, "dump_outputs: the arrays must share their first (design) axis"
+    n = n.pop()
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_BUDGET_BYTES:
+        keep = max(1, int(DUMP_BUDGET_BYTES // (total / n + 8)))
+        idx = np.sort(np.random.default_rng(0).choice(n, size=keep, replace=False))
+        out = {name: a[idx] for name, a in out.items()}
+        out["design_index"] = idx.astype(np.float64)
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(a))
+    return sorted(out)
 
 
 def scale_rows(lo, hi):
@@ -657,6 +694,8 @@ def main_sharded_leg(args, world, rank, local, rehearsal):
             q = b["q"]
             herm = bool(np.allclose(q[0], np.conj(np.transpose(q[0], (1, 0, 2))), atol=1e-6 * np.abs(q[0]).max()))
             assert herm and np.all(np.isfinite(q.view(float))), "reduced QTF is not Hermitian / finite"
+            if args.dump_outputs:
+                dump_outputs(args.dump_outputs, {"qtf": q})
             k_max = float(np.max(allt[:, 0]))
             out = {"metric": "QTF difference-frequency pairs/sec (whole node)", "unit": "pairs/s", "value": b["pairs"] / dt,
                    "n_gpus": world, "steps": max(args.steps, 2), "warmup": 1, "ms_per_step": b["wall_ms"], "higher_is_better": True,
@@ -699,21 +738,30 @@ def main():
     ap.add_argument("--resident", action="store_true", help="also time the fused kernel alone, whole batch resident in HBM")
     ap.add_argument("--no-stream", action="store_true", help="time isolated blocking calls (raftx_sweep_stats) instead of streaming the "
                                                              "steps through the library's slots (raftx_sweep_prepare / _launch / _wait)")
-    ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the oracle leg (cpu_baseline and the all-design check)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the oracle leg (cpu_baseline and the all-design check)")
     ap.add_argument("--depth", type=int, default=0, help="batches in flight when the steps are streamed: 2 = submit(i+1), wait(i) (default); 4 = prepare(i+3), launch(i+2), wait(i) "
                                                       "(default with --xi-out: the download of a batch takes longer than its kernels); "
                                                       "3 = prepare(i+2), launch(i+1), wait(i): the next batch's tables are generated in the drain "
                                                       "of the running fused kernel -- measured on one box over 300 steps: 3.73 against 3.71 ms per step "
                                                       "(the gap between fused kernels shrinks 0.35 -> 0.2 ms, the kernels sharing the drain slow each "
                                                       "other by as much), so it is not the default")
-    ap.add_argument("--no-extra-legs", action="store_true", help="skip the legs outside the headline (xi-out, featured sweeps)")
-    ap.add_argument("--legs", default="xi,featured,configs,hostdesc,traffic,launchsize,shard", help="which legs outside the headline run (comma list of xi, featured, configs, hostdesc, launchsize, shard, "
+    ap.add_argument("--no-extra-legs", action="store_true", help="--full: skip the legs outside the headline (xi-out, featured sweeps)")
+    ap.add_argument("--legs", default="xi,featured,configs,hostdesc,traffic,launchsize,shard", help="--full: which legs outside the headline run (comma list of xi, featured, configs, hostdesc, launchsize, shard, "
                                                                             "traffic = the FETCH_SIZE / WRITE_SIZE passes of roofline.traffic, two child runs under rocprofv3)")
     ap.add_argument("--profile", action="store_true", help="for runs under rocprofv3: whole-batch launches only (--chunks 1), no isolated / "
                                                             "extra / oracle legs -- ONE population of k_solve_dynamics launches in the trace")
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline as well: the isolated-call and determinism checks, "
+                                                         "parity against the reference and the CPU oracle, the CPU baselines, the legs of --legs, "
+                                                         "and with N > 1 the single-rank and strong-scaling lines.  Without it a run sets up, "
+                                                         "warms up, times the K steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (float64; a fixed, "
+                         "seeded sample of the designs where the whole would pass %d MB)" % (DUMP_BUDGET_BYTES >> 20))
     args = ap.parse_args()
     if args.profile:
         args.chunks, args.no_extra_legs, args.no_cpu_baseline = 1, True, True
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
     # NumPy's BLAS pool on at most eight threads for the life of this process (it only ever lowers the count): the pool's GPU
     # boxes give a process 16 CPUs by cgroup quota behind 256 logical ones, and OpenBLAS's idle-spinning threads spend that
     # quota -- the whole process, the thread that feeds the GPU included, is then throttled (raft_amd/hostblas.py)
@@ -751,6 +799,8 @@ def main():
         local = int(os.environ["RAFTX_BENCH_DEVICE"])
 
     if args.workload != "c3":
+        if args.dump_outputs and args.workload == "c4":
+            ap.error("--dump-outputs: the c4 workload does not hand its responses back to bench.py (c3 and c5 do)")
         return main_sharded_leg(args, world, rank, local, rehearsal)
 
     from raft_amd import backend
@@ -870,7 +920,7 @@ def main():
     # N > 1: the single-rank yardstick of THIS invocation -- rank 0 alone runs the same K steps (no exchange step) while the
     # other ranks wait at the barrier, so that the N-rank value can be set against N x one rank on the same box and build
     single_rank = None
-    if comm is not None:
+    if comm is not None and args.full:
         barrier()
         if rank == 0:
             solo["on"] = True
@@ -883,7 +933,7 @@ def main():
     # N > 1, weak scaling (the contract line): ALSO the literal shape of BASELINE configs[2] in the same invocation -- ONE sweep of
     # --designs cut into N contiguous shards, streamed and gathered like the timed steps
     strong_same = None
-    if comm is not None and not strong and args.designs >= world:
+    if comm is not None and args.full and not strong and args.designs >= world:
         sb_ = [shard_bounds(args.designs, r_, world) for r_ in range(world)]
         cnt_ = np.array([hi_ - lo_ for lo_, hi_ in sb_], dtype=np.int64)
         sw_st, _, _ = make_sweep(ctx, int(cnt_[rank]), rank, pinned=not args.pageable, rows=sb_[rank], variants=variants)
@@ -921,10 +971,18 @@ def main():
     barrier()
     elapsed = time.perf_counter() - t0
     r = res[-1]
+    if args.dump_outputs and rank == 0:                   # what the last timed step handed back, before anything reuses its buffers
+        if comm is not None:
+            last = {"std_all": r["std_all"]}              # rank 0's share of the exchange: six std columns + iteration count
+        else:
+            last = {"std": r["std"], "niter": r["niter"], "flags": r["flags"], "strips_per_design": np.diff(r["strip_off"])}
+            if r.get("Xi") is not None:                   # --xi-out: this rank's responses (a seeded sample of them)
+                last["Xi"] = r["Xi"]
+        dump_outputs(args.dump_outputs, last)
     tims = [x["timing_ms"] for x in res]
     host_params_ms = 1e3 * float(np.mean(host_params_s)) if host_params_s else None
     isolated = None
-    if stream_steps and rank == 0 and not args.profile:   # the same step as an isolated blocking call (outside the timed region)
+    if stream_steps and rank == 0 and args.full and not args.profile:   # the same step as an isolated blocking call (outside the timed region)
         t1 = time.perf_counter()
         for _ in range(5):                                # (no gather here: only this rank runs it)
             fresh_candidates()
@@ -941,12 +999,14 @@ def main():
     A_steps = float(np.mean([algorithmic_bytes(x["strip_off"], nw) for x in res]))
     flops_steps = float(np.mean([algorithmic_flops(x["strip_off"], nw, x["niter"]) for x in res]))
     mean_iter_timed = float(np.mean([np.mean(x["niter"]) for x in res]))
-    if comm is not None and rank == 0:
+    if comm is not None and rank == 0 and args.full:
         assert r["std_all"].shape == (int(counts_all.sum()), 7) and np.array_equal(r["std_all"][:nD, :6], r["std"].reshape(nD, 6))
 
-    # ---- outside the timed region: determinism of a timed batch, then parity on the STANDARD batch (rows whose first 64
-    # designs the live reference solved), one more crossing with the responses downloaded
-    if variants:
+    # ---- outside the timed region (--full, or --resident, which solves the standard batch again): determinism of a timed
+    # batch, then parity on the STANDARD batch (rows whose first 64 designs the live reference solved), one more crossing
+    # with the responses downloaded.  A plain run checks only the timed steps' own NaN flags.
+    checks = args.full or args.resident
+    if variants and checks:
         distinct = len({x["std"].tobytes() for x in res})
         assert distinct == len(res), "timed steps were meant to solve distinct candidates (%d distinct of %d)" % (distinct, len(res))
         b_last = first_timed_batch + len(res) - 1             # the last timed step's candidates, once more, alone
@@ -957,16 +1017,19 @@ def main():
         sw.set_params(G_.volturnus_params(scale_rows(*shard[rank])))
     # (--profile: no download -- a crossing that downloads its responses is cut into slabs of one residency round, ten more
     # launches of the same kernel name in the rocprofv3 statistics; the parity of the responses is the default run's business)
-    chk = sw.run_crossing(ctx, n_chunk=args.chunks, n_worker=args.workers, want_Xi=not args.profile)
-    if not variants:
-        for x in res:                                     # every timed step re-solved the same batch: the same bits
-            assert np.array_equal(x["std"].view(np.uint64), r["std"].view(np.uint64)) and np.array_equal(x["niter"], r["niter"])
-        assert np.array_equal(chk["std"].view(np.uint64), r["std"].view(np.uint64)) and np.array_equal(chk["niter"], r["niter"]), \
-            "two crossings of the same batch differ"
+    if checks:
+        chk = sw.run_crossing(ctx, n_chunk=args.chunks, n_worker=args.workers, want_Xi=not args.profile)
+        if not variants:
+            for x in res:                                 # every timed step re-solved the same batch: the same bits
+                assert np.array_equal(x["std"].view(np.uint64), r["std"].view(np.uint64)) and np.array_equal(x["niter"], r["niter"])
+            assert np.array_equal(chk["std"].view(np.uint64), r["std"].view(np.uint64)) and np.array_equal(chk["niter"], r["niter"]), \
+                "two crossings of the same batch differ"
+        nan += int(np.count_nonzero(chk["flags"] & 2))
+        Xi = chk["Xi"]
+    else:
+        chk, Xi = r, None
     off = chk["strip_off"]
     niter = chk["niter"]
-    nan += int(np.count_nonzero(chk["flags"] & 2))
-    Xi = chk["Xi"]
     parity = {"nan_flags": nan}
     if rank == 0 and Xi is not None:                      # the first 64 designs are the live reference's own variants
         errs, mism = [], 0
@@ -980,7 +1043,7 @@ def main():
     assert nan == 0, "NaN flags in the timed batch"
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         os.sched_setaffinity(0, cpus_at_start)
         cpu, ores, gen_chk = oracle_run(sw, ctx)
         parity["generator_vs_oracle_all_designs"] = gen_chk
@@ -1016,7 +1079,7 @@ def main():
     B = types.SimpleNamespace(ctx=ctx, sw=sw, nD=nD, nw=nw, args=args, Xi=Xi, chk=chk, variants=variants, rank=rank, shard=shard,
                               make_sweep=make_sweep, run_streamed=run_streamed, algorithmic_flops=algorithmic_flops, scale_rows=scale_rows,
                               G_=G_)                     # what the legs in bench_legs.py read of this run
-    if rank == 0 and world == 1 and not args.no_extra_legs and not args.xi_out and "xi" in args.legs:
+    if rank == 0 and world == 1 and args.full and not args.no_extra_legs and not args.xi_out and "xi" in args.legs:
         xi_leg = guarded("xi_out", lambda: bench_legs.xi_out(B))
         if "error" in xi_leg:                             # a crossing may still be in flight: drain before the next leg
             try:
@@ -1034,18 +1097,18 @@ def main():
                                     "ns_per_pair_iteration": 1e6 * float(np.mean(ks)) / float(np.sum(niter))}}
         f_.update(featured_legs(ctx, nD, sw, float(np.mean(ks)), float(np.sum(niter))))
         return f_
-    if rank == 0 and world == 1 and not args.no_extra_legs and not args.xi_out and "featured" in args.legs:
+    if rank == 0 and world == 1 and args.full and not args.no_extra_legs and not args.xi_out and "featured" in args.legs:
         featured = guarded("featured_sweeps", run_featured)
     # ---- the rounds-1-4 form of the step on the same box, for comparison: ONE batch expanded by NumPy outside the step and its
     # 66 MB of descriptors re-uploaded (DMA) every step -- no device-side expansion, but a host that can feed only 1 / 14 ms
     hostdesc = None
 
-    if variants and rank == 0 and world == 1 and not args.no_extra_legs and not args.xi_out and "hostdesc" in args.legs:
+    if variants and rank == 0 and world == 1 and args.full and not args.no_extra_legs and not args.xi_out and "hostdesc" in args.legs:
         hostdesc = guarded("host_descriptors_same_box", lambda: bench_legs.host_descriptors(B))
 
     # ---- BASELINE configs[1], [3], [4] at their specified sizes, each against its live-reference golden (N = 1)
     cfg_legs = {}
-    if rank == 0 and world == 1 and not args.no_extra_legs and "configs" in args.legs:
+    if rank == 0 and world == 1 and args.full and not args.no_extra_legs and "configs" in args.legs:
         import bench_legs
         cfg_legs["c2_dropin"] = guarded("c2_dropin", lambda: bench_legs.c2_dropin(ctx))
         cfg_legs["c4_farm"] = guarded("c4_farm", lambda: bench_legs.c4_farm(ctx, farms=1000))
@@ -1057,7 +1120,7 @@ def main():
     # (914 of 1 024 slots busy on average; DESIGN.md 3.1, profiles/r05_launch_size_scaling.json); these two figures say what the
     # kernel does when a launch is long enough for that not to matter.
     launch_size = None
-    if rank == 0 and world == 1 and not args.no_extra_legs and "launchsize" in args.legs:
+    if rank == 0 and world == 1 and args.full and not args.no_extra_legs and "launchsize" in args.legs:
         launch_size = guarded("launch_size", lambda: bench_legs.launch_size(B))
 
     # ---- the shard of BASELINE configs[2]'s strong-scaling shape on ONE GPU: 10 000 designs over 8 ranks = 1 250 per rank
@@ -1065,12 +1128,12 @@ def main():
     # strong-scaling run does, so its ms_per_step against this run's 10 000-design step IS the projected 8-GPU speed-up
     # (no collective while solving; the gather moves 56 B per design).
     shard_leg = None
-    if rank == 0 and world == 1 and not args.no_extra_legs and stream_steps and "shard" in args.legs and nD >= 8:
+    if rank == 0 and world == 1 and args.full and not args.no_extra_legs and stream_steps and "shard" in args.legs and nD >= 8:
         shard_leg = guarded("shard_1250", lambda: bench_legs.shard_1250(B, 1e3 * elapsed / args.steps))
 
     # ---- roofline.traffic: measured in THIS run where rocprofv3 is at hand (N = 1), else the committed profile's figure
     traffic_bytes, traffic_prov = measured_traffic(nD), traffic_provenance()
-    if rank == 0 and world == 1 and not args.no_extra_legs and not args.profile and "traffic" in args.legs:
+    if rank == 0 and world == 1 and args.full and not args.no_extra_legs and not args.profile and "traffic" in args.legs:
         tb, tp = live_traffic(nD)
         if tb is not None:
             traffic_bytes, traffic_prov = tb, tp
@@ -1195,7 +1258,7 @@ def main():
     out.update(cfg_legs)
     # ---- the CPU baseline (rank 0, N = 1): the UNMODIFIED reference on this host's cores when this host has it (build
     # container: /root/reference; GPU box: oracle/_ref/raft_reference.zip), the vectorised C port beside it
-    ref_here = reference_on_this_host() if (rank == 0 and world == 1 and not args.no_cpu_baseline) else None
+    ref_here = reference_on_this_host() if (rank == 0 and world == 1 and args.full and not args.no_cpu_baseline) else None
     if ref_here is not None and "error" not in ref_here:
         nw_ = nw
         out["cpu_baseline"] = {
@@ -1227,7 +1290,7 @@ def main():
         out["host_cpu_budget"] = dict(_CPU_BUDGET, note="logical CPUs this container sees vs the CPUs' worth of run time it gets (one busy "
                                       "loop per logical CPU for 1 s, CPU time / wall time): the CPU legs use the latter as their worker / thread count")
     ref_path = os.path.join(ROOT, "profiles", "reference_cpu_timing.json")
-    if os.path.exists(ref_path):      # the same measurement made in the BUILD container (8 cores), for comparison
+    if args.full and os.path.exists(ref_path):      # the same measurement made in the BUILD container (8 cores), for comparison
         with open(ref_path) as f:
             rt = json.load(f)
         out["reference_numpy_build_container"] = {"dcf_per_s_one_core": rt.get("single", rt).get("dcf_per_s_one_core", rt.get("dcf_per_s_per_core")),

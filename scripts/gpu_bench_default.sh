@@ -6,7 +6,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$R/gpurun_out/$TAG
 mkdir -p $OUT
 cd $R
-( timeout 900 python bench.py "${@:2}" 2>$OUT/bench.err | tail -1 ) > $OUT/bench.json
+( timeout 900 python bench.py --full "${@:2}" 2>$OUT/bench.err | tail -1 ) > $OUT/bench.json
 python - <<PY
 import json
 d = json.load(open("$OUT/bench.json"))

@@ -10,7 +10,7 @@ cd $R
 export TMPDIR=/tmp
 ( timeout 900 python -m pytest tests -m gpu -x -q 2>&1 | tail -15 ) > $OUT/pytest_gpu.log
 ( timeout 300 python -c 'import __graft_entry__ as g; g.smoke()' 2>&1 | tail -5 ) > $OUT/smoke.log
-( timeout 600 python bench.py --resident 2>$OUT/bench.err | tail -1 ) > $OUT/bench.json
+( timeout 600 python bench.py --full --resident 2>$OUT/bench.err | tail -1 ) > $OUT/bench.json
 # counter passes: one launch of the fused kernel per step (--chunks 1), so that per-launch counters are per-step counters
 BENCH="python $R/bench.py --steps 5 --warmup 1 --profile"
 cd /tmp

@@ -6,6 +6,7 @@ import ctypes
 import os
 import re
 import socket
+import time
 
 import numpy as np
 import pytest
@@ -53,11 +54,12 @@ def test_product_does_not_import_torch():
 
 def test_product_fails_loudly_without_a_gpu():
     """No CPU fallback: on a host without an MI355X the device library refuses to create a context."""
-    import torch
-    if torch.cuda.is_available():
-        pytest.skip("a GPU is visible")
     from raft_amd import backend
     from raft_amd._abi import RaftxError
+    # asked of the product library, not of torch: torch brings its own HIP runtime, and once that one has opened the device
+    # in this process the library's runtime finds none -- every GPU test later in the same session would skip
+    if backend.hip_library().device_count() > 0:
+        pytest.skip("a GPU is visible")
     with pytest.raises(RaftxError):
         backend.hip_library().context(0)
     assert backend.hip_library().device_count() == 0          # what bench.py's rank launcher checks --gpus against
@@ -133,14 +135,37 @@ def _rank_main(rank, world, port, n, out_path, kind):
         comm.close()
 
 
+def _spawn(fn, args, nprocs, timeout=600):
+    """torch.multiprocessing.spawn's contract -- fn(rank, *args) in nprocs fresh processes, a failing rank stops the others,
+    every rank must exit 0 -- without importing torch into the test process: torch brings its own HIP runtime and RCCL
+    (SONAME librccl.so.1), and once they are loaded here the product library's RCCL binding would find torch's copy."""
+    import multiprocessing
+    mpc = multiprocessing.get_context("spawn")
+    procs = [mpc.Process(target=fn, args=(r,) + tuple(args)) for r in range(nprocs)]
+    for p in procs:
+        p.start()
+    deadline = time.time() + timeout
+    try:
+        while any(p.is_alive() for p in procs) and time.time() < deadline:
+            if any(p.exitcode not in (None, 0) for p in procs):
+                break
+            time.sleep(0.05)
+    finally:
+        for p in procs:
+            if p.is_alive():
+                p.terminate()
+            p.join()
+    codes = [p.exitcode for p in procs]
+    assert codes == [0] * nprocs, "rank processes exited with %r" % codes
+
+
 @pytest.mark.parametrize("kind", TRANSPORTS)
 def test_two_rank_sweep_matches_single_process(tmp_path, oracle_lib, kind):
     """world_size 2: broadcast of the case tables, design sharding, gather of responses and of statistics to rank 0 --
     bitwise identical to the single-process run, and equal to the live-reference vectors."""
-    import torch.multiprocessing as mp
     n, world = 7, 2                      # odd count: ragged shards (4 + 3)
     out = str(tmp_path / "gathered.npz")
-    mp.spawn(_rank_main, args=(world, _free_port(), n, out, kind), nprocs=world, join=True)
+    _spawn(_rank_main, (world, _free_port(), n, out, kind), world)
     got = np.load(out)
     s, fx = _c3_sweep(n)
     ctx = oracle_lib.context(0)
@@ -191,10 +216,9 @@ def _geom_rank_main(rank, world, port, n, out_path, kind):
 def test_two_rank_geometry_sweep(tmp_path, oracle_lib, kind):
     """Designs given as member descriptions shard by design like packed ones: every rank generates its own block
     (no collective on the data path), rank 0 gathers; equal to the packed-table sweep and to the live reference."""
-    import torch.multiprocessing as mp
     n, world = 5, 2
     out = str(tmp_path / "geom_gathered.npz")
-    mp.spawn(_geom_rank_main, args=(world, _free_port(), n, out, kind), nprocs=world, join=True)
+    _spawn(_geom_rank_main, (world, _free_port(), n, out, kind), world)
     got = np.load(out)
     s, fx = _geometry_sweep(n)
     assert s.take(1, 4).tables.n_design == 3 and s.take(1, 4).tables.station_off[0] == 0
@@ -245,10 +269,9 @@ def test_two_rank_variant_sweep(tmp_path, oracle_lib, kind):
     """Designs given as PARAMETERS of an edit program (VariantSweep) shard by design like the others: every rank expands
     and generates its own block (params[lo:hi], no collective on the data path), rank 0 gathers; bit-identical to the
     sweep fed with the host-expanded member descriptions."""
-    import torch.multiprocessing as mp
     n, world = 5, 2
     out = str(tmp_path / "variant_gathered.npz")
-    mp.spawn(_variant_rank_main, args=(world, _free_port(), n, out, kind), nprocs=world, join=True)
+    _spawn(_variant_rank_main, (world, _free_port(), n, out, kind), world)
     got = np.load(out)
     s, g = _variant_sweep(n)
     assert s.take(1, 4).n_design == 3 and np.array_equal(s.take(1, 4).params, s.params[1:4])
@@ -313,9 +336,8 @@ def _qtf_rows_rank_main(rank, world, port, out_path, kind):
 @pytest.mark.parametrize("kind", TRANSPORTS)
 def test_two_rank_qtf_rows_of_one_matrix(tmp_path, kind):
     """ONE QTF split by interleaved rows over two ranks and summed onto rank 0."""
-    import torch.multiprocessing as mp
     out = str(tmp_path / "qrows.npy")
-    mp.spawn(_qtf_rows_rank_main, args=(2, _free_port(), out, kind), nprocs=2, join=True)
+    _spawn(_qtf_rows_rank_main, (2, _free_port(), out, kind), 2)
     got = np.load(out)
     tabs, Xi, beta, w2, k2, f = _qtf_sets()
     ref = _numpy_qtf(tabs[:1], Xi[:1], beta[:1], w2, k2, f.depth, f.rho_water, f.g, np.array([f.M_struc]), None)
@@ -344,10 +366,9 @@ def _farm_rank_main(rank, world, port, out_path, kind):
 def test_two_rank_farm_cases(tmp_path, kind):
     """ONE 4-unit farm, its sea states block-partitioned over two ranks and gathered along the case axis
     (SURVEY.md 8e, C4): equal to the live reference's coupled responses."""
-    import torch.multiprocessing as mp
     from tests.util import load_model_fixture, group_rel_err
     out = str(tmp_path / "farm.npz")
-    mp.spawn(_farm_rank_main, args=(2, _free_port(), out, kind), nprocs=2, join=True)
+    _spawn(_farm_rank_main, (2, _free_port(), out, kind), 2)
     got = np.load(out)
     fx, _ = load_model_fixture("c4_farm.npz")
     assert got["Xi"].shape[:2] == (1, 3) and got["niter"].shape == (4, 3)
@@ -390,9 +411,8 @@ def _flex_rank_main(rank, world, port, n_unit, out_path, kind):
 def test_two_rank_flexible_units(tmp_path, oracle_lib, kind, n_unit):
     """Units with flexible members block-partitioned over two ranks (2 + 1; 1 + 0: a rank without units still takes part in
     the gather), every rank running the whole fixed point of its units: identical to the single-process batch."""
-    import torch.multiprocessing as mp
     out = str(tmp_path / "flex.npz")
-    mp.spawn(_flex_rank_main, args=(2, _free_port(), n_unit, out, kind), nprocs=2, join=True)
+    _spawn(_flex_rank_main, (2, _free_port(), n_unit, out, kind), 2)
     got = np.load(out)
     ctx = oracle_lib.context(0)
     ref = _flex_units(n_unit).run(ctx)
@@ -407,9 +427,8 @@ def test_two_rank_flexible_units(tmp_path, oracle_lib, kind, n_unit):
 @pytest.mark.parametrize("kind", TRANSPORTS)
 def test_two_rank_qtf_sets(tmp_path, kind):
     """QTF sets sharded over two ranks (2 + 1) and gathered: identical to the single-process batch."""
-    import torch.multiprocessing as mp
     out = str(tmp_path / "q.npy")
-    mp.spawn(_qtf_rank_main, args=(2, _free_port(), out, kind), nprocs=2, join=True)
+    _spawn(_qtf_rank_main, (2, _free_port(), out, kind), 2)
     got = np.load(out)
     tabs, Xi, beta, w2, k2, f = _qtf_sets()
     ref = _numpy_qtf(tabs, Xi, beta, w2, k2, f.depth, f.rho_water, f.g, np.array([f.M_struc] * 3), None)
@@ -435,7 +454,6 @@ def test_sharded_statistics_resume_from_shard_files(tmp_path, oracle_lib, monkey
     """run_stats_sharded(checkpoint_dir=...): shards are written as they finish; a second run loads what is there and
     solves only what is missing (one shard file deleted, one replaced by a file of another partition); two ranks then
     complete the same directory.  Every variant returns the bits of the plain run."""
-    import torch.multiprocessing as mp
     n = 9
     s, _ = _c3_sweep(n)
     ctx = oracle_lib.context(0)
@@ -459,7 +477,7 @@ def test_sharded_statistics_resume_from_shard_files(tmp_path, oracle_lib, monkey
     monkeypatch.undo()
     # two ranks, two shards each, over the same directory (same 4-shard partition: everything is already there)
     out = str(tmp_path / "two_rank.npz")
-    mp.spawn(_ckpt_rank_main, args=(2, _free_port(), n, ckpt, out, "host"), nprocs=2, join=True)
+    _spawn(_ckpt_rank_main, (2, _free_port(), n, ckpt, out, "host"), 2)
     got = np.load(out)
     assert np.array_equal(got["std"].view(np.uint64), ref["std"].view(np.uint64)) and np.array_equal(got["niter"], ref["niter"])
 

@@ -53,7 +53,7 @@ def test_two_ranks_on_one_gpu_through_bench_itself():
     ranks on one device, the exchange steps take the host transport and the line says so): two ranks are started, the
     statistics of both are gathered inside the timed steps, rank 0 prints ONE line that says n_gpus = 2 and carries the
     per-rank / gather / single-rank keys."""
-    r = _bench(["--gpus", "2", "--steps", "3", "--warmup", "1", "--designs", "512", "--no-cpu-baseline"], RAFTX_BENCH_DEVICE="0")
+    r = _bench(["--gpus", "2", "--steps", "3", "--warmup", "1", "--designs", "512", "--no-cpu-baseline", "--full"], RAFTX_BENCH_DEVICE="0")
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1 and r.stdout.strip().splitlines()[-1] == lines[0], r.stdout[-500:]     # the JSON line is the LAST line
@@ -73,7 +73,8 @@ def test_two_ranks_on_one_gpu_through_bench_itself():
 def test_single_gpu_line_carries_the_numbers_a_reader_needs():
     """beside `value` the line has the step-level roofline fraction, SURVEY 8d's literal step (responses
     downloaded) as a top-level key, and the 1/8 shard of the sweep (what one rank of an 8-GPU strong-scaling run does)."""
-    r = _bench(["--steps", "4", "--warmup", "1", "--designs", "2048", "--no-cpu-baseline", "--legs", "xi,shard"], RAFTX_BENCH_XI_STEPS="6")
+    r = _bench(["--steps", "4", "--warmup", "1", "--designs", "2048", "--no-cpu-baseline", "--legs", "xi,shard", "--full"],
+               RAFTX_BENCH_XI_STEPS="6")
     assert r.returncode == 0, r.stderr[-2000:]
     out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
     rf = out["roofline"]
@@ -101,8 +102,8 @@ def test_strong_scaling_mode_cuts_one_sweep_into_ragged_shards():
     """--scaling strong: ONE sweep of --designs cut into N contiguous shards (1001 over 3 ranks = 334 + 334 + 333),
     gathered with ragged counts inside the timed steps; the line says "strong", names the shards and carries every rank's
     descriptor-expansion time."""
-    r = _bench(["--gpus", "3", "--scaling", "strong", "--designs", "1001", "--steps", "3", "--warmup", "1", "--no-cpu-baseline"],
-               RAFTX_BENCH_DEVICE="0")
+    r = _bench(["--gpus", "3", "--scaling", "strong", "--designs", "1001", "--steps", "3", "--warmup", "1", "--no-cpu-baseline",
+                "--full"], RAFTX_BENCH_DEVICE="0")
     assert r.returncode == 0, r.stderr[-2000:]
     out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
     assert out["n_gpus"] == 3 and out["scaling"] == "strong"
@@ -110,3 +111,52 @@ def test_strong_scaling_mode_cuts_one_sweep_into_ragged_shards():
     assert abs(out["value"] - 1001 * out["config"]["nw"] / (out["ms_per_step"] * 1e-3)) < 1e-6 * out["value"]
     assert len(out["host_descriptor_ms_per_rank"]["all"]) == 3
     assert out["parity"]["niter_mismatches_vs_reference"] == 0
+
+
+def test_dump_outputs_writes_float64_within_its_budget(tmp_path, monkeypatch):
+    """--dump-outputs: float64 files, complex arrays split in two, and where the whole would pass the budget the same
+    seeded sample of designs in every file (named by design_index.npy), identical from call to call."""
+    import numpy as np
+    if ROOT not in sys.path:
+        sys.path.insert(0, ROOT)
+    import bench
+    std = np.arange(40 * 6, dtype=np.float64).reshape(40, 1, 6)
+    niter = np.arange(40, dtype=np.int32).reshape(40, 1)
+    Xi = (np.arange(40 * 12) * (1 + 2j)).reshape(40, 1, 1, 6, 2)
+    assert bench.dump_outputs(str(tmp_path / "a"), {"std": std, "niter": niter, "Xi": Xi}) == ["Xi_im", "Xi_re", "niter", "std"]
+    got = {n: np.load(str(tmp_path / "a" / (n + ".npy"))) for n in ("std", "niter", "Xi_re", "Xi_im")}
+    assert all(a.dtype == np.float64 for a in got.values())
+    assert np.array_equal(got["std"], std) and np.array_equal(got["niter"], niter) and np.array_equal(got["Xi_im"], Xi.imag)
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 10 * 7 * 8)             # room for about a quarter of the designs
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), {"std": std, "niter": niter})
+    idx = np.load(str(tmp_path / "b" / "design_index.npy")).astype(int)
+    assert 0 < len(idx) < 40 and np.all(np.diff(idx) > 0)
+    for n in ("std", "niter", "design_index"):
+        b, c = np.load(str(tmp_path / "b" / (n + ".npy"))), np.load(str(tmp_path / "c" / (n + ".npy")))
+        assert np.array_equal(b, c)
+    assert np.array_equal(np.load(str(tmp_path / "b" / "std.npy")), std[idx])
+    assert sum(os.path.getsize(str(p)) for p in (tmp_path / "b").iterdir()) < 10 * 7 * 8 + 3 * 256        # + .npy headers
+
+
+@pytest.mark.gpu
+def test_plain_run_is_the_headline_alone_and_its_outputs_repeat(tmp_path):
+    """A plain run times exactly --steps steps and carries none of the --full legs; --dump-outputs writes the last timed
+    step's statistics, and a second run with the same arguments writes the same bits."""
+    import numpy as np
+    outs = []
+    for d in ("one", "two"):
+        r = _bench(["--gpus", "1", "--steps", "3", "--warmup", "1", "--designs", "512", "--dump-outputs", str(tmp_path / d)])
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1 and r.stdout.strip().splitlines()[-1] == lines[0], r.stdout[-500:]
+        outs.append(json.loads(lines[0]))
+    for out in outs:
+        assert out["steps"] == 3 and out["ms_per_step"] > 0 and out["unit"] == "dcf solves/s" and out["dtype"] == "f64"
+        assert abs(out["value"] - 512 * out["config"]["nw"] / (out["ms_per_step"] * 1e-3)) < 1e-6 * out["value"]
+        assert not {"cpu_baseline", "xi_out", "isolated_call", "featured_sweeps", "shard_1250", "c2_dropin"} & set(out)
+    std = np.load(str(tmp_path / "one" / "std.npy"))
+    assert std.shape == (512, 1, 6) and std.dtype == np.float64 and np.all(np.isfinite(std)) and np.all(std > 0)
+    for n in ("std", "niter", "flags", "strips_per_design"):
+        a, b = np.load(str(tmp_path / "one" / (n + ".npy"))), np.load(str(tmp_path / "two" / (n + ".npy")))
+        assert a.dtype == np.float64 and np.array_equal(a, b), n

@@ -429,8 +429,14 @@ def test_installed_calcHydroExcitation_full_dof_and_member_list(patch):
 # every platform deck of the reference tree that the reference itself can build and solve here (MoorPy / CCBlade stubbed,
 # mooring replaced by the injected stiffness of SURVEY 8d): rigid units, farms, internal-QTF decks, the flexible decks
 def _platform_decks():
-    if not rh.tree_available():
-        return []
+    """The committed list of the tree's platform decks (tests/golden/reference_platform_decks.json): the test ids do not
+    depend on whether the tree is present where the suite is collected."""
+    import json
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_platform_decks.json")) as f:
+        return json.load(f)["decks"]
+
+
+def _platform_decks_in_tree():
     import glob
     out = []
     for sub in ("designs", "examples", "tests/test_data"):
@@ -438,6 +444,11 @@ def _platform_decks():
             if isinstance(rh.load_design(path), dict) and "platform" in rh.load_design(path):
                 out.append(os.path.relpath(path, rh.REFERENCE_ROOT))
     return out
+
+
+def test_committed_deck_list_is_the_trees():
+    """Every platform deck of the reference tree, and nothing else, is in the committed list the next test runs over."""
+    assert _platform_decks() == _platform_decks_in_tree()
 
 
 @pytest.mark.parametrize("deck", _platform_decks())
