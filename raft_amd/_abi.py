@@ -38,6 +38,9 @@ EXPORTS = (
     "raftx_strip_kinematics", "raftx_strip_drag", "raftx_response_stats",
 )
 WANT_BDRAG, WANT_FWAVE, WANT_Z = 1, 2, 4
+# include/raftx_modal.h: implemented by the device library only (the oracle has no eigen solver), bound when present
+MODAL_EXPORTS = ("raftx_modal_batch", "raftx_modal_resident", "raftx_sweep_modal")
+MODAL_SMALL_DIAG, MODAL_NONPOSITIVE, MODAL_COMPLEX, MODAL_SINGULAR_M, MODAL_NO_CONVERGENCE = 1, 2, 4, 8, 16
 
 
 class RaftxError(RuntimeError):
@@ -132,6 +135,14 @@ class RaftxLib:
             L.raftx_flex_start.restype = C.c_int
         L.raftx_debug_flex_gemm.argtypes = [_vp, C.c_int, C.c_int, _vp, _vp, _vp]
         L.raftx_debug_flex_gemm.restype = C.c_int
+        self.has_modal = all(hasattr(L, s) for s in MODAL_EXPORTS)
+        if self.has_modal:
+            L.raftx_modal_batch.argtypes = [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp]
+            L.raftx_modal_batch.restype = C.c_int
+            L.raftx_modal_resident.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _vp]
+            L.raftx_modal_resident.restype = C.c_int
+            L.raftx_sweep_modal.argtypes = [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp]
+            L.raftx_sweep_modal.restype = C.c_int
         L.raftx_device_locality.argtypes = [C.c_int, C.c_char_p, C.c_int, C.POINTER(C.c_int)]
         L.raftx_device_locality.restype = C.c_int
         L.raftx_host_alloc.argtypes = [_vp, C.c_size_t, C.POINTER(_vp)]
@@ -573,6 +584,57 @@ class Context:
         cm = np.empty((int(n_cm_rows), 2, self._nw_designs), dtype=np.complex128) if n_cm_rows else None
         self._check(self.rlib.lib.raftx_fetch_strips(self._h, _ptr(strips), _ptr(cm)), "raftx_fetch_strips")
         return strips, cm
+
+    # ------------------------------------------------------------- eigen analysis (include/raftx_modal.h)
+    def _modal_lib(self, what):
+        if not self.rlib.has_modal:
+            raise RaftxError("%s: %s does not implement include/raftx_modal.h (the device library does)" % (what, self.rlib.path))
+        return self.rlib.lib
+
+    @staticmethod
+    def _modal_out(n, want_props=False):
+        return dict(fn=np.empty((n, 6)), modes=np.empty((n, 6, 6)), flags=np.empty(n, dtype=np.int32),
+                    props=np.empty((n, 12)) if want_props else None)
+
+    def modal_batch(self, M, C_):
+        """Natural frequencies [Hz] and modes of n rigid 6-DOF systems (raftx_modal_batch): M, C [n,6,6] summed
+        M_tot / C_tot in; dict(fn [n,6], modes [n,6,6] (column j: mode of fn[j]), flags [n] (MODAL_*), props None)."""
+        L = self._modal_lib("modal_batch")
+        M = _f64(M)
+        n = M.shape[0] if M.ndim == 3 else 0
+        M = _f64(M, (n, 6, 6), "M")
+        C_ = _f64(C_, (n, 6, 6), "C")
+        out = self._modal_out(n)
+        self._check(L.raftx_modal_batch(self._h, n, _ptr(M), _ptr(C_), _ptr(out["fn"]), _ptr(out["modes"]), _ptr(out["flags"])),
+                    "raftx_modal_batch")
+        return out
+
+    def modal_resident(self, dM=None, dC=None, want_props=False):
+        """The same on the resident design set (raftx_modal_resident): M0 + dM, C0 + dC after the statics add-up; props
+        [nD,12] (raftx_fetch_statics' record) when asked for."""
+        L = self._modal_lib("modal_resident")
+        n = self.nDesign
+        dM = None if dM is None else _f64(dM, (n, 6, 6), "dM")
+        dC = None if dC is None else _f64(dC, (n, 6, 6), "dC")
+        out = self._modal_out(n, want_props)
+        self._check(L.raftx_modal_resident(self._h, _ptr(dM), _ptr(dC), _ptr(out["fn"]), _ptr(out["modes"]), _ptr(out["flags"]),
+                                           _ptr(out["props"])), "raftx_modal_resident")
+        return out
+
+    def sweep_modal(self, handle, dM=None, dC=None, want_props=False):
+        """Ask for the eigen analysis of a PREPARED, not yet launched crossing (raftx_sweep_modal); ``sweep_wait`` then
+        also returns fn, modes, modal_flags and props (None unless asked for).  Returns the handle."""
+        L = self._modal_lib("sweep_modal")
+        out = handle["out"]
+        n = out["niter"].shape[0]
+        dM = None if dM is None else _f64(dM, (n, 6, 6), "dM")
+        dC = None if dC is None else _f64(dC, (n, 6, 6), "dC")
+        res = self._modal_out(n, want_props)
+        self._check(L.raftx_sweep_modal(self._h, int(handle["slot"]), _ptr(dM), _ptr(dC), _ptr(res["fn"]), _ptr(res["modes"]),
+                                        _ptr(res["flags"]), _ptr(res["props"])), "raftx_sweep_modal")
+        handle["modal_inputs"] = (dM, dC)                 # alive until the crossing has been waited for
+        out["fn"], out["modes"], out["modal_flags"], out["props"] = res["fn"], res["modes"], res["flags"], res["props"]
+        return handle
 
     def fetch_statics(self):
         """dict(A_morison, C_hydro, M_struc, C_struc [nD,6,6]; W_hydro, W_struc [nD,6]; props [nD,12])."""

@@ -41,6 +41,7 @@
 #include <vector>
 
 #include "../../include/raftx.h"
+#include "../../include/raftx_modal.h"
 
 // roctx ranges around the phases of the host side: named spans for `rocprofv3 --marker-trace`.
 // librocprofiler-sdk-roctx is bound at run time on first use; without it (or outside a profiler) the ranges cost a branch.
@@ -80,6 +81,7 @@ struct RangeScope {
 #include "raftx_fusedgen.h"
 #include "raftx_dense.h"
 #include "raftx_flex.h"
+#include "raftx_modal.h"
 
 // Coupled array solve (raft_model.py:1164-1236): Xi = Z_sys^-1 F for every (system, bin).  One wavefront per
 // (system, bin), NBIN (1, 2 or 4: what fits LDS) consecutive bins per workgroup so that the loads of one matrix entry
@@ -811,6 +813,8 @@ struct raftx_ctx {
     size_t pin_n;
     double *pinRes;                      // page-locked landing area of a block's statistics (sweep crossing)
     size_t pinRes_n;
+    double *pinModal = nullptr;          // page-locked landing area of a block's eigen analysis (raftx_sweep_modal)
+    size_t pinModal_n = 0;
     hipStream_t sCopy, sPrep, sD2H, sGen; // internal streams of raftx_sweep_stats (created on first use)
     hipStream_t sSlab[2] = {nullptr, nullptr}; // with sGen: the streams the slabs of a crossing with responses out go to (SlabPlan)
     hipStream_t sD2Hlow = nullptr;        // bulk download of the responses: a stream of its own priority class, created when first needed
@@ -918,6 +922,13 @@ struct SweepSlot {
     size_t nSlabEv = 0;
     bool slab = false;                   // this crossing's fused launches were cut into slabs (SlabPlan)
     std::vector<double> tlb;             // RAFTX_SWEEP_DEBUG: host time per block of raftx_sweep_launch (upload enqueued | totals seen | enqueued)
+    struct {                             // raftx_sweep_modal: eigen analysis of the crossing's designs
+        bool on = false;
+        const double *dM = nullptr, *dC = nullptr;   // device copies [nDesign,36] (in S.allocs), or null
+        double *fn = nullptr, *modes = nullptr, *props = nullptr;   // the caller's outputs, filled by raftx_sweep_wait
+        int32_t *flags = nullptr;
+        hipEvent_t evUp = nullptr;       // the copies of dM / dC have landed (sCopy)
+    } modal;
 };
 
 #define MAX_NW 2048
@@ -1082,11 +1093,13 @@ extern "C" void raftx_ctx_destroy(raftx_ctx *c) {
     for (int sl = 0; sl < RAFTX_NSLOT; sl++) {
         free_list(c, c->slots[sl].allocs);
         if (c->slots[sl].evXi) (void)hipEventDestroy(c->slots[sl].evXi);
+        if (c->slots[sl].modal.evUp) (void)hipEventDestroy(c->slots[sl].modal.evUp);
     }
     delete[] c->slots;
     c->pool.trim();
     if (c->pin) (void)hipHostFree(c->pin);
     if (c->pinRes) (void)hipHostFree(c->pinRes);
+    if (c->pinModal) (void)hipHostFree(c->pinModal);
     for (hipEvent_t e : {c->evZ, c->ev0, c->ev1, c->evUp, c->evTot, c->evG0, c->evG1, c->evG2, c->evG3, c->evS0, c->evS1, c->evDone,
                          c->evMem, c->evRed})
         (void)hipEventDestroy(e);
@@ -3316,6 +3329,7 @@ static int sweep_prepare_impl(raftx_ctx *c, int slot, int nDesign, const int64_t
     S.tl[0] = since();
     // the slot's previous crossing has been waited for: its tables and offset arrays are free
     free_list(c, S.allocs);
+    S.modal.on = false;
     auto fail_drain = [&](int rc) {
         (void)hipDeviceSynchronize();
         for (raftx_ctx *sub : blk)
@@ -3529,6 +3543,43 @@ static hipStream_t slot_stream(raftx_ctx *c, int slot) {
     return (n_streams > 1 && c->sMainB && (slot & 1)) ? c->sMainB : c->stream;
 }
 
+// The eigen analysis of one block of a crossing (raftx_sweep_modal) on stream st, which is behind whatever wrote the
+// block's summed M0 / C0 (k_geom_addup, k_geom_design with the add-up folded in, or the generating fused kernel): one
+// system per lane, the results written straight into the block's page-locked landing area
+// [fn n*6 | modes n*36 | props n*SP_N | flags n int32], which raftx_sweep_wait copies out.
+static hipError_t modal_block(raftx_ctx *sub, SweepSlot &S, int lo, int n, hipStream_t st) {
+    const size_t need = (size_t)n * (42 + RAFTX_SP_N) + ((size_t)n + 1) / 2;
+    if (!sub->pinModal || sub->pinModal_n < need) {
+        if (sub->pinModal) (void)hipHostFree(sub->pinModal);
+        sub->pinModal = nullptr;
+        sub->pinModal_n = 0;
+        void *p_ = nullptr;
+        const hipError_t e = hipHostMalloc(&p_, need * sizeof(double), hipHostMallocDefault);
+        if (e != hipSuccess) return e;
+        sub->pinModal = reinterpret_cast<double *>(p_);
+        sub->pinModal_n = need;
+    }
+    if (n == 0) return hipSuccess;
+    if (S.modal.evUp) {
+        const hipError_t e = hipStreamWaitEvent(st, S.modal.evUp, 0);
+        if (e != hipSuccess) return e;
+    }
+    double *pm = sub->pinModal;
+    ModalArgs A;
+    A.n = n;
+    A.M = sub->T.M0;
+    A.C = sub->T.C0;
+    A.dM = S.modal.dM ? S.modal.dM + (size_t)lo * 36 : nullptr;
+    A.dC = S.modal.dC ? S.modal.dC + (size_t)lo * 36 : nullptr;
+    A.props_in = S.modal.props ? sub->g_props : nullptr;
+    A.props_out = pm + (size_t)n * 42;
+    A.fn = pm;
+    A.modes = pm + (size_t)n * 6;
+    A.flags = reinterpret_cast<int32_t *>(pm + (size_t)n * (42 + RAFTX_SP_N));
+    hipLaunchKernelGGL(k_modal, dim3((unsigned)(((size_t)n + MODAL_BS - 1) / MODAL_BS)), dim3(MODAL_BS), 0, st, A);
+    return hipGetLastError();
+}
+
 extern "C" int raftx_sweep_launch(raftx_ctx *c, int slot) {
     RangeScope range_("raftx_sweep_launch: generation + fused fixed point + statistics (enqueue)");
     if (!c) return -1;
@@ -3629,6 +3680,7 @@ extern "C" int raftx_sweep_launch(raftx_ctx *c, int slot) {
                                (const int *)sub->rFl, reinterpret_cast<int *>(sub->pinRes + npair * 6));
         }
         if (e == hipSuccess) e = hipEventRecord(sub->evS1, sS);
+        if (e == hipSuccess && S.modal.on) e = modal_block(sub, S, lo, bnd[b + 1] - lo, sS);
         if (e == hipSuccess) e = hipEventRecord(sub->evDone, sS);
         if (e == hipSuccess && Xi && !slab_mode) {
             const size_t p0 = (size_t)lo * nCase;
@@ -3820,6 +3872,7 @@ extern "C" int raftx_sweep_cancel(raftx_ctx *c, int slot) {
             sub->job.active = false;
         }
     S.prepared = false;
+    S.modal.on = false;
     slot_release_cases(c, S);
     HIPCHK(c, e);
     return 0;
@@ -3880,7 +3933,16 @@ extern "C" int raftx_sweep_wait(raftx_ctx *c, int slot, double *timing_ms) {
         memcpy(S.sd + p0 * 6, sub->pinRes, npair * 6 * sizeof(double));
         memcpy(S.niter + p0, sub->pinRes + npair * 6, npair * sizeof(int));
         memcpy(S.flags + p0, reinterpret_cast<int *>(sub->pinRes + npair * 6) + npair, npair * sizeof(int));
+        if (S.modal.on) {
+            const double *pm = sub->pinModal;
+            memcpy(S.modal.fn + (size_t)lo * 6, pm, (size_t)n * 6 * sizeof(double));
+            memcpy(S.modal.modes + (size_t)lo * 36, pm + (size_t)n * 6, (size_t)n * 36 * sizeof(double));
+            if (S.modal.props)
+                memcpy(S.modal.props + (size_t)lo * RAFTX_SP_N, pm + (size_t)n * 42, (size_t)n * RAFTX_SP_N * sizeof(double));
+            memcpy(S.modal.flags + lo, pm + (size_t)n * (42 + RAFTX_SP_N), (size_t)n * sizeof(int32_t));
+        }
     }
+    S.modal.on = false;
     const double wall = since();
     if (dbg_host)
         fprintf(stderr, "[raftx_sweep slot %d] host ms since submit: pre %.3f | phase-1 enqueued %.3f | phase-2 enqueued %.3f | ctx stream "
@@ -3915,6 +3977,86 @@ extern "C" int raftx_sweep_generation(raftx_ctx *c, int slot, int *blocks_fused,
         }
     if (blocks_fused) *blocks_fused = nf;
     if (blocks) *blocks = nb;
+    return 0;
+}
+
+// ---- eigen analysis of rigid 6-DOF systems (include/raftx_modal.h, raftx_modal.h)
+static int modal_launch(raftx_ctx *c, int n, const double *M, const double *C, const double *dM, const double *dC,
+                        const double *props_in, double *fn, double *modes, int32_t *flags, double *props) {
+    Scratch sc(c);
+    double *dfn = sc.alloc<double>((size_t)n * 6), *dmo = sc.alloc<double>((size_t)n * 36);
+    int32_t *dfl = sc.alloc<int32_t>((size_t)n);
+    double *dpr = props_in ? sc.alloc<double>((size_t)n * RAFTX_SP_N) : nullptr;
+    if (!dfn || !dmo || !dfl || (props_in && !dpr)) FAIL(c, "modal: device allocation failed");
+    ModalArgs A;
+    A.n = n; A.M = M; A.C = C; A.dM = dM; A.dC = dC;
+    A.props_in = props_in; A.props_out = dpr;
+    A.fn = dfn; A.modes = dmo; A.flags = dfl;
+    HIPCHK(c, hipEventRecord(c->ev0, c->stream));
+    hipLaunchKernelGGL(k_modal, dim3((unsigned)(((size_t)n + MODAL_BS - 1) / MODAL_BS)), dim3(MODAL_BS), 0, c->stream, A);
+    if (finish_timed(c)) return -2;
+    D2H(c, fn, dfn, (size_t)n * 6 * sizeof(double));
+    D2H(c, modes, dmo, (size_t)n * 36 * sizeof(double));
+    D2H(c, flags, dfl, (size_t)n * sizeof(int32_t));
+    if (props) D2H(c, props, dpr, (size_t)n * RAFTX_SP_N * sizeof(double));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+extern "C" int raftx_modal_batch(raftx_ctx *c, int n, const double *M, const double *C, double *fn, double *modes,
+                                 int32_t *flags) {
+    if (!c) return -1;
+    if (n < 0 || (n > 0 && (!M || !C || !fn || !modes || !flags))) FAIL(c, "modal_batch: bad arguments");
+    if (n == 0) return 0;
+    HIPCHK(c, hipSetDevice(c->device));
+    Scratch sc(c);
+    double *dM = sc.alloc<double>((size_t)n * 36), *dC = sc.alloc<double>((size_t)n * 36);
+    if (!dM || !dC) FAIL(c, "modal_batch: device allocation failed");
+    H2D(c, dM, M, (size_t)n * 36 * sizeof(double));
+    H2D(c, dC, C, (size_t)n * 36 * sizeof(double));
+    return modal_launch(c, n, dM, dC, nullptr, nullptr, nullptr, fn, modes, flags, nullptr);
+}
+
+extern "C" int raftx_modal_resident(raftx_ctx *c, const double *dM, const double *dC, double *fn, double *modes,
+                                    int32_t *flags, double *props) {
+    if (!c) return -1;
+    if (!c->have_designs) FAIL(c, "modal_resident: no design set on this ctx (raftx_upload_designs / raftx_build_designs)");
+    if (!fn || !modes || !flags) FAIL(c, "modal_resident: bad arguments");
+    const int n = c->T.nDesign;
+    if (props && (c->g_n != n || !c->g_props))
+        FAIL(c, "modal_resident: props are generated by raftx_build_designs only (the resident set was uploaded)");
+    if (n == 0) return 0;
+    HIPCHK(c, hipSetDevice(c->device));
+    Scratch sc(c);
+    double *ddM = dM ? sc.alloc<double>((size_t)n * 36) : nullptr, *ddC = dC ? sc.alloc<double>((size_t)n * 36) : nullptr;
+    if ((dM && !ddM) || (dC && !ddC)) FAIL(c, "modal_resident: device allocation failed");
+    if (dM) H2D(c, ddM, dM, (size_t)n * 36 * sizeof(double));
+    if (dC) H2D(c, ddC, dC, (size_t)n * 36 * sizeof(double));
+    return modal_launch(c, n, c->T.M0, c->T.C0, ddM, ddC, props ? c->g_props : nullptr, fn, modes, flags, props);
+}
+
+extern "C" int raftx_sweep_modal(raftx_ctx *c, int slot, const double *dM, const double *dC, double *fn, double *modes,
+                                 int32_t *flags, double *props) {
+    if (!c) return -1;
+    if (slot < 0 || slot >= RAFTX_NSLOT) FAIL(c, "sweep_modal: slot must be 0 .. %d", RAFTX_NSLOT - 1);
+    SweepSlot &S = c->slots[slot];
+    if (S.busy) FAIL(c, "sweep_modal: slot %d has been launched (call it between raftx_sweep_prepare and raftx_sweep_launch)", slot);
+    if (!S.prepared) FAIL(c, "sweep_modal: nothing prepared on slot %d (raftx_sweep_prepare first)", slot);
+    if (!fn || !modes || !flags) FAIL(c, "sweep_modal: bad arguments");
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t n = S.bnd.empty() ? 0 : (size_t)S.bnd.back();
+    const double *ddM = nullptr, *ddC = nullptr;
+    if (upload_on(c, c->sCopy, S.allocs, dM, dM ? n * 36 : 0, &ddM) || upload_on(c, c->sCopy, S.allocs, dC, dC ? n * 36 : 0, &ddC))
+        return -2;
+    if (!S.modal.evUp) HIPCHK(c, hipEventCreateWithFlags(&S.modal.evUp, hipEventDisableTiming));
+    HIPCHK(c, hipEventRecord(S.modal.evUp, c->sCopy));
+    S.modal.dM = ddM;
+    S.modal.dC = ddC;
+    S.modal.fn = fn;
+    S.modal.modes = modes;
+    S.modal.flags = flags;
+    S.modal.props = props;
+    S.modal.on = true;
     return 0;
 }
 

@@ -113,6 +113,83 @@ class Engine:
             self._ctx = backend.default_context()
         return self._ctx
 
+    # ------------------------------------------------------------------ eigen analysis (include/raftx_modal.h)
+    @staticmethod
+    def _eigen_unit(fowt, what):
+        if int(getattr(fowt, "nDOF", 6)) != 6:
+            raise UnsupportedFOWT("%s: units with %d reduced DOFs are not covered (rigid 6-DOF units only)" % (what, fowt.nDOF))
+
+    def _eigen(self, M_tot, C_tot, display, outPath, writer, mode_header):
+        """raft_fowt.py:1664-1729 / raft_model.py:472-540 after the assembly: viability message, one raftx_modal_batch
+        call, the reference's errors, outPath / display."""
+        message = ''
+        for i in range(6):
+            if M_tot[i, i] < 1.0:
+                message += f'Diagonal entry {i} of system mass matrix is less than 1 ({M_tot[i,i]}). '
+            if C_tot[i, i] < 1.0:
+                message += f'Diagonal entry {i} of system stiffness matrix is less than 1 ({C_tot[i,i]}). '
+        if len(message) > 0:
+            raise RuntimeError('System matrices computed by RAFT have one or more small or negative diagonals: ' + message)
+        from ._abi import MODAL_NONPOSITIVE, MODAL_COMPLEX, MODAL_SINGULAR_M, MODAL_NO_CONVERGENCE
+        r = self.ctx.modal_batch(M_tot[None], C_tot[None])
+        fl = int(r["flags"][0])
+        if fl & (MODAL_COMPLEX | MODAL_SINGULAR_M | MODAL_NO_CONVERGENCE):
+            raise UnsupportedFOWT("solveEigen: the eigen problem has %s (device flags %d)" % (
+                "a complex eigenvalue pair" if fl & MODAL_COMPLEX else
+                "a singular mass matrix" if fl & MODAL_SINGULAR_M else "no convergence of the QR iteration", fl))
+        if fl & MODAL_NONPOSITIVE:
+            raise RuntimeError("Error: zero or negative system eigenvalues detected.")
+        fns, modes = r["fn"][0].copy(), r["modes"][0].copy()
+        if isinstance(outPath, str) and writer is not None:
+            writer(outPath, fns, modes)
+        if display > 0:
+            print("")
+            print("--------- Natural frequencies and mode shapes -------------")
+            print(mode_header)
+            print("Fn (Hz)" + "".join([f"{fn:10.4f}" for fn in fns[:6]]))
+            print("")
+            for i in range(6):
+                print(f"DOF {i+1}  " + "".join([f"{modes[i,j]:10.4f}" for j in range(6)]))
+            print("-----------------------------------------------------------")
+        return fns, modes
+
+    def fowt_solveEigen(self, fowt, display=0, outPath=None):
+        """FOWT.solveEigen (raft_fowt.py:1646-1729, with getStiffness :1627-1644): natural frequencies [Hz] and modes of
+        one rigid unit.  Modes have unit 2-norm with their largest component positive (the reference's sign is LAPACK's)."""
+        self._eigen_unit(fowt, "FOWT.solveEigen")
+        M_tot = fowt.M_struc + fowt.A_hydro_morison + fowt.A_BEM[:, :, 0]
+        C_tot = np.zeros([fowt.nDOF, fowt.nDOF])
+        C_tot += fowt.C_moor
+        C_tot[5, 5] += fowt.yawstiff
+        if getattr(fowt, "body", None):
+            C_tot += fowt.body.getStiffness()
+        C_tot += fowt.C_struc + fowt.C_hydro + fowt.C_elast
+        return self._eigen(np.asarray(M_tot, dtype=float), C_tot, display, outPath, getattr(fowt, "write_modes_json", None),
+                           "Mode        1         2         3         4         5         6")
+
+    def solveEigen(self, model, display=0, outPath=None):
+        """Model.solveEigen (raft_model.py:436-547) for one rigid unit without an array mooring system; sets
+        model.results['eigen'].  Arrays and units with more than 6 DOFs raise UnsupportedFOWT."""
+        fowts = list(model.fowtList)
+        if len(fowts) != 1 or getattr(model, "ms", None):
+            raise UnsupportedFOWT("Model.solveEigen: arrays (%d units%s) are not covered" % (
+                len(fowts), ", array mooring system" if getattr(model, "ms", None) else ""))
+        fowt = fowts[0]
+        self._eigen_unit(fowt, "Model.solveEigen")
+        M_tot = np.zeros([6, 6])
+        C_tot = np.zeros([6, 6])
+        M_tot[0:6, 0:6] += fowt.M_struc + fowt.A_hydro_morison + fowt.A_BEM[:, :, 0]
+        C_tot[0:6, 0:6] += fowt.C_struc + fowt.C_hydro + fowt.C_moor + fowt.C_elast
+        C_tot[5, 5] += fowt.yawstiff
+        fns, modes = self._eigen(M_tot, C_tot, display, outPath, getattr(model, "write_modes_json", None),
+                                 "Mode   " + "".join([f"{i+10:3d}" for i in range(6)]))
+        if not hasattr(model, "results") or model.results is None:
+            model.results = {}
+        model.results['eigen'] = {}
+        model.results['eigen']['frequencies'] = fns
+        model.results['eigen']['modes'] = modes
+        return fns, modes
+
     # ------------------------------------------------------------------ per-member side effects (SURVEY.md 8b), on request
     @staticmethod
     def _scatter(table, members, arrays, heading_axis):
@@ -1380,11 +1457,21 @@ def solveDynamics(model, case, tol=0.01, conv_plot=0, RAO_plot=0, display=0):
                                          RAO_plot=RAO_plot, display=display)
 
 
-def install(raft_module=None, outputs=False, materialise_members=None):
+def solveEigen(model, display=0, outPath=None):
+    return _default_engine.solveEigen(model, display=display, outPath=outPath)
+
+
+def fowt_solveEigen(fowt, display=0, outPath=None):
+    return _default_engine.fowt_solveEigen(fowt, display=display, outPath=outPath)
+
+
+def install(raft_module=None, outputs=False, materialise_members=None, eigen=False):
     """Monkey-patch a loaded reference package so that Model.analyzeCases & co
     run the hot path on the GPU.  Returns the originals for un-patching.
     outputs=True also routes FOWT.saveTurbineOutputs (statistics of the resident responses; rigid single units
     without MoorPy / controller outputs -- anything else raises UnsupportedFOWT, never a silent fallback).
+    eigen=True also routes Model.solveEigen and FOWT.solveEigen (rigid single units; arrays and units with more than 6
+    DOFs raise UnsupportedFOWT).
     materialise_members=True / False: switch the default engine's per-member side effects (mem.u, ud, pDyn,
     F_hydro_iner, Bmat, F_exc_drag: Engine.materialise_members) on / off; None leaves the engine as it is."""
     if materialise_members is not None:
@@ -1407,6 +1494,11 @@ def install(raft_module=None, outputs=False, materialise_members=None):
     if outputs:
         saved["saveTurbineOutputs"] = raft_fowt.FOWT.saveTurbineOutputs
         raft_fowt.FOWT.saveTurbineOutputs = saveTurbineOutputs
+    if eigen:
+        saved["Model.solveEigen"] = raft_model.Model.solveEigen
+        saved["FOWT.solveEigen"] = raft_fowt.FOWT.solveEigen
+        raft_model.Model.solveEigen = solveEigen
+        raft_fowt.FOWT.solveEigen = fowt_solveEigen
     return saved
 
 
@@ -1420,3 +1512,6 @@ def uninstall(saved):
     raft_fowt.FOWT.calcHydroForce_2ndOrd = saved['calcHydroForce_2ndOrd']
     if 'saveTurbineOutputs' in saved:
         raft_fowt.FOWT.saveTurbineOutputs = saved['saveTurbineOutputs']
+    if 'Model.solveEigen' in saved:
+        raft_model.Model.solveEigen = saved['Model.solveEigen']
+        raft_fowt.FOWT.solveEigen = saved['FOWT.solveEigen']

@@ -23,6 +23,13 @@ from ._abi import NFIELD
 WAVE_RHO, WAVE_G = 1025.0, 9.81        # hard-wired defaults of Member.calcHydroExcitation (raft_member.py:1940)
 
 
+def periods(fn):
+    """Natural periods [s] from natural frequencies [Hz], as omdao_raft.py:859 exports them (NaN stays NaN)."""
+    fn = np.asarray(fn, dtype=np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return 1.0 / fn
+
+
 def shard_bounds(n, rank, world):
     """Contiguous block partition of range(n): the first n % world ranks get one extra item."""
     if world < 1 or not (0 <= rank < world):
@@ -159,6 +166,13 @@ class Sweep:
         ctx.solve_dynamics_device(self.nIter, self.tol, self.XiStart)
         return ctx.last_kernel_ms()
 
+    def run_modal(self, ctx, dM=None, dC=None, want_props=False):
+        """Natural frequencies and modes of the designs resident on ``ctx`` (after ``upload``; raftx_modal_resident):
+        M0 + dM, C0 + dC after the device's add-up.  dM / dC [nD,6,6] carry what the eigen problem has and the
+        dynamics' matrices may not (A_BEM[:,:,0], yawstiff on [5,5]).  dict(fn [nD,6] Hz, modes [nD,6,6], flags [nD],
+        props [nD,12] or None); ``periods(fn)`` gives the periods."""
+        return ctx.modal_resident(dM, dC, want_props=want_props)
+
     def run_stats(self, ctx, want_psd=False):
         """Solve and return only the response statistics (std [nD,nC,6], optional PSD) + niter/flags:
         ~60 B per (design, case) cross the bus instead of 19 KB (raft_fowt.py:2310-2357)."""
@@ -286,10 +300,14 @@ class GeometrySweep(Sweep):
                                             None if self.pose is None else self.pose[lo:hi], self.add_mask,
                                             None if self.MBw is None else self.MBw[lo:hi], self.rho, self.g), lo, hi)
 
-    def run_crossing(self, ctx, n_chunk=0, n_worker=0, want_Xi=False, Xi_out=None):
+    def run_crossing(self, ctx, n_chunk=0, n_worker=0, want_Xi=False, Xi_out=None, modal=False, dM=None, dC=None, want_props=False):
         """The whole boundary crossing in ONE library call (raftx_sweep_stats): descriptors in, motion statistics +
         iteration counts (+ responses) out, with upload / generation / solve / download of consecutive design blocks
-        overlapped on the library's internal streams.  Nothing stays resident on ``ctx``."""
+        overlapped on the library's internal streams.  Nothing stays resident on ``ctx``.  modal=True: the streamed
+        form on slot 0 with the eigen analysis of every design (see ``prepare_crossing``)."""
+        if modal:
+            return self.wait_crossing(ctx, self.submit_crossing(ctx, 0, n_chunk=n_chunk, want_Xi=want_Xi, Xi_out=Xi_out, modal=True,
+                                                                dM=dM, dC=dC, want_props=want_props))
         self._crossing_supported()
         t = self.tables
         r = ctx.sweep_stats(t, self.M0, self.B0, self.C0, self.w, self.k, self.depth, self.zeta, self.beta, self.nIter,
@@ -298,13 +316,27 @@ class GeometrySweep(Sweep):
         self.off = r["strip_off"]
         return r
 
-    def prepare_crossing(self, ctx, slot, n_chunk=0, want_Xi=False, Xi_out=None):
+    def prepare_crossing(self, ctx, slot, n_chunk=0, want_Xi=False, Xi_out=None, modal=False, dM=None, dC=None, want_props=False):
         """First stage of the streamed form of ``run_crossing`` for back-to-back batches: enqueue this batch's descriptor
-        upload and member pass on ``slot`` (0 .. 3) and return a handle (raftx_sweep_prepare)."""
+        upload and member pass on ``slot`` (0 .. 3) and return a handle (raftx_sweep_prepare).  modal=True: the batch's
+        eigen analysis rides along (raftx_sweep_modal on M_extra + device terms + dM, C_extra + device terms + dC) and
+        ``wait_crossing`` also returns fn, modes, modal_flags and props (``want_props``)."""
         self._crossing_supported()
-        return ctx.sweep_prepare(slot, self.tables, self.M0, self.B0, self.C0, self.w, self.k, self.depth, self.zeta, self.beta,
+        return self._with_modal(ctx, ctx.sweep_prepare(slot, self.tables, self.M0, self.B0, self.C0, self.w, self.k, self.depth, self.zeta, self.beta,
                                  self.nIter, self.tol, self.XiStart, pose=self.pose, rho=self.rho, g=self.g, add_mask=self.add_mask,
-                                 n_chunk=n_chunk, want_Xi=want_Xi, Xi_out=Xi_out)
+                                 n_chunk=n_chunk, want_Xi=want_Xi, Xi_out=Xi_out), modal, dM, dC, want_props)
+
+    @staticmethod
+    def _with_modal(ctx, handle, modal, dM, dC, want_props):
+        if not modal:
+            if dM is not None or dC is not None or want_props:
+                raise ValueError("dM / dC / want_props belong to modal=True")
+            return handle
+        try:
+            return ctx.sweep_modal(handle, dM, dC, want_props=want_props)
+        except Exception:
+            ctx.sweep_cancel(handle)
+            raise
 
     def launch_crossing(self, ctx, handle):
         """Second stage: table generation, fused fixed point and statistics of a prepared batch (raftx_sweep_launch).  With
@@ -312,9 +344,10 @@ class GeometrySweep(Sweep):
         consecutive batches follow each other without a gap."""
         return ctx.sweep_launch(handle)
 
-    def submit_crossing(self, ctx, slot, n_chunk=0, want_Xi=False, Xi_out=None):
+    def submit_crossing(self, ctx, slot, n_chunk=0, want_Xi=False, Xi_out=None, modal=False, dM=None, dC=None, want_props=False):
         """prepare + launch in one call (raftx_sweep_submit); ``wait_crossing`` collects the results."""
-        return self.launch_crossing(ctx, self.prepare_crossing(ctx, slot, n_chunk=n_chunk, want_Xi=want_Xi, Xi_out=Xi_out))
+        return self.launch_crossing(ctx, self.prepare_crossing(ctx, slot, n_chunk=n_chunk, want_Xi=want_Xi, Xi_out=Xi_out,
+                                                               modal=modal, dM=dM, dC=dC, want_props=want_props))
 
     def _crossing_supported(self):
         """raftx_sweep_stats / raftx_sweep_submit carry neither frequency-dependent matrices nor potential-flow excitation
@@ -680,16 +713,19 @@ class VariantSweep(GeometrySweep):
                            self.add_mask, self.rho, self.g)
         return self._take_bem(sub, lo, hi)
 
-    def prepare_crossing(self, ctx, slot, n_chunk=0, want_Xi=False, Xi_out=None):
+    def prepare_crossing(self, ctx, slot, n_chunk=0, want_Xi=False, Xi_out=None, modal=False, dM=None, dC=None, want_props=False):
         self._crossing_supported()
         self._install(ctx)
-        return ctx.sweep_prepare_variants(slot, self.params, self.M0, self.B0, self.C0, self.w, self.k, self.depth, self.zeta, self.beta,
+        return self._with_modal(ctx, ctx.sweep_prepare_variants(slot, self.params, self.M0, self.B0, self.C0, self.w, self.k, self.depth, self.zeta, self.beta,
                                           self.nIter, self.tol, self.XiStart, pose=self.pose, rho=self.rho, g=self.g,
-                                          add_mask=self.add_mask, n_chunk=n_chunk, want_Xi=want_Xi, Xi_out=Xi_out)
+                                          add_mask=self.add_mask, n_chunk=n_chunk, want_Xi=want_Xi, Xi_out=Xi_out),
+                                modal, dM, dC, want_props)
 
-    def run_crossing(self, ctx, n_chunk=0, n_worker=0, want_Xi=False, Xi_out=None, slot=0):
+    def run_crossing(self, ctx, n_chunk=0, n_worker=0, want_Xi=False, Xi_out=None, slot=0, modal=False, dM=None, dC=None,
+                     want_props=False):
         """One isolated crossing: prepare + launch + wait on ``slot``."""
-        return self.wait_crossing(ctx, self.submit_crossing(ctx, slot, n_chunk=n_chunk, want_Xi=want_Xi, Xi_out=Xi_out))
+        return self.wait_crossing(ctx, self.submit_crossing(ctx, slot, n_chunk=n_chunk, want_Xi=want_Xi, Xi_out=Xi_out, modal=modal,
+                                                            dM=dM, dC=dC, want_props=want_props))
 
     def upload(self, ctx):
         self.tables = self.expanded_tables(ctx)
