@@ -510,9 +510,9 @@ int raftx_sweep_submit(raftx_ctx *ctx, int slot, int nDesign, const int64_t *mem
 int raftx_sweep_wait(raftx_ctx *ctx, int slot, double *timing_ms);
 /* Where on the device's clock the fused fixed point of the crossing LAST WAITED FOR on `slot` ran: start of its first
  * launch and end of its last one, in ms since the first crossing of this ctx was launched.  Crossings of consecutive
- * slots run on alternating streams and their fused kernels overlap (the drain of batch i is the ramp of batch i+1), so
- * the busy time of k_solve_dynamics over a stream of batches is the UNION of these spans, not the sum of the per-batch
- * durations of timing_ms[2] (bench.py: roofline.kernel_ms_per_step).  The CPU oracle returns zeros.
+ * slots share one compute stream, so their fused kernels follow each other and do not overlap: the busy time of
+ * k_solve_dynamics over a stream of batches is the UNION of these spans, which on one stream equals their sum
+ * (bench.py: roofline.kernel_ms_per_step).  The CPU oracle returns zeros.
  * (the loop the kernel fuses: raft/raft_model.py:1052-1142) */
 int raftx_sweep_solve_span(raftx_ctx *ctx, int slot, double *start_ms, double *end_ms);
 /* Where the strip tables of the crossing LAST LAUNCHED on `slot` were generated: *blocks_fused = the number of its blocks

@@ -743,7 +743,6 @@ struct BuildJob {
     double *M0d = nullptr, *C0d = nullptr;
     const double *B0d = nullptr, *MBwd = nullptr;
     bool active = false;
-    bool reduce_late = false;
     hipStream_t reduce_stream = nullptr; // side stream the member -> platform reductions were launched on (evRed), or null
     // phase 2 left the tables of the designs to the fused kernel that solves them (raftx_fusedgen.h): nothing has been
     // written yet; solve_enqueue launches the generating form, or k_geom_design + k_geom_addup if it cannot
@@ -817,11 +816,8 @@ struct raftx_ctx {
     size_t pinModal_n = 0;
     hipStream_t sCopy, sPrep, sD2H, sGen; // internal streams of raftx_sweep_stats (created on first use)
     hipStream_t sSlab[2] = {nullptr, nullptr}; // with sGen: the streams the slabs of a crossing with responses out go to (SlabPlan)
-    hipStream_t sD2Hlow = nullptr;        // bulk download of the responses: a stream of its own priority class, created when first needed
+    hipStream_t sD2Hhigh = nullptr;       // bulk download of the responses: a stream of the highest priority class, created when first needed
     hipEvent_t evEpoch = nullptr;         // zero of raftx_sweep_solve_span: recorded when the first crossing of the ctx is launched
-    hipStream_t sMainB = nullptr;         // second compute stream of the sweep crossings (odd slots), created when first needed
-    hipStream_t sExp = nullptr;           // k_geom_expand of a block (variants): a HIGH-priority stream of its own, created when first needed
-    hipEvent_t evExp = nullptr;
     CaseSet csets[RAFTX_NSLOT + 1];      // sea-state tables of the sweep crossings: one per crossing in flight + one being replaced
     unsigned long long cset_clock = 0;
     char err[512];
@@ -874,7 +870,6 @@ struct raftx_ctx {
     int g_n;
     size_t g_nStrips, g_nRows;
     double *g_abi, *g_A, *g_Ch, *g_Wh, *g_props, *g_Ms, *g_Cs, *g_Ws;
-    hipStream_t sStat = nullptr;         // RAFTX_STATS_STREAM=1: the statistics kernels of sweep crossings
     bool last_gen_fused = false;         // the last fused launch generated its designs' tables itself (raftx_fusedgen.h)
     cplx *g_cm;
     void *comm;                          // ncclComm_t of raftx_comm_init (RCCL), or null
@@ -1010,20 +1005,9 @@ extern "C" int raftx_ctx_create(int device_id, raftx_ctx **out) {
     c->pinRes = nullptr;
     c->pinRes_n = 0;
     c->sCopy = c->sPrep = c->sD2H = c->sGen = nullptr;
-    // RAFTX_CTX_PRIORITY=high (tuning): the ctx stream -- the fused fixed points, table generation, statistics -- in the
-    // highest priority class, so that the dispatcher serves its grids before the preparation kernels of the batches behind.
-    // Measured and NOT the default (gpurun_out/r05_ctxprio, same box, K = 40, two repeats): 3.27 against 3.07 ms per step with
-    // three batches in flight, 3.21 against 3.13 with two, 3.29 against 3.08 with host-made descriptors -- the member pass of
-    // the next batch then cannot use the running kernel's drain and lands behind it.
-    bool ok;
-    {
-        static const char *prio = getenv("RAFTX_CTX_PRIORITY");
-        int least = 0, greatest = 0;
-        if (prio && !strcmp(prio, "high") && hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess && least != greatest)
-            ok = hipStreamCreateWithPriority(&c->stream, hipStreamNonBlocking, greatest) == hipSuccess;
-        else
-            ok = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) == hipSuccess;
-    }
+    // the ctx stream -- the fused fixed points, table generation, statistics -- is of the default priority class (a high one
+    // lost: profiles/MEASUREMENT_HISTORY.md, "Closed scheduling experiments of the crossing")
+    bool ok = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) == hipSuccess;
     c->sAux = nullptr;
     for (hipEvent_t *e : {&c->evZ, &c->ev0, &c->ev1, &c->evUp, &c->evTot, &c->evG0, &c->evG1, &c->evG2, &c->evG3, &c->evS0,
                           &c->evS1, &c->evDone, &c->evMem, &c->evRed})
@@ -1104,9 +1088,8 @@ extern "C" void raftx_ctx_destroy(raftx_ctx *c) {
                          c->evMem, c->evRed})
         (void)hipEventDestroy(e);
     if (c->sAux) (void)hipStreamDestroy(c->sAux);
-    if (c->evExp) (void)hipEventDestroy(c->evExp);
     if (c->evEpoch) (void)hipEventDestroy(c->evEpoch);
-    for (hipStream_t st : {c->sCopy, c->sPrep, c->sD2H, c->sGen, c->sD2Hlow, c->sSlab[0], c->sSlab[1], c->sExp, c->sMainB, c->sStat})
+    for (hipStream_t st : {c->sCopy, c->sPrep, c->sD2H, c->sGen, c->sD2Hhigh, c->sSlab[0], c->sSlab[1]})
         if (st) (void)hipStreamDestroy(st);
     if (c->owns_stream) (void)hipStreamDestroy(c->stream);
     delete c;
@@ -1351,30 +1334,10 @@ static int build_phase1(raftx_ctx *c, hipStream_t sCopy, hipStream_t sPrep, int 
     HIPCHK(c, hipEventRecord(c->evUp, sCopy));
     HIPCHK(c, hipStreamWaitEvent(sPrep, c->evUp, 0));
     if (var && nDesign > 0) {
-        // The expansion is 0.09 ms of chip time.  On the preparation stream, beside the fused kernel of the batch before --
-        // whose waves own every register of every CU -- its workgroups are handed out a few at a time over that whole
-        // kernel.  RAFTX_EXPAND_STREAM=1 puts it on a HIGH-priority stream of its own (the dispatcher then takes its
-        // workgroups first as slots free up; the member pass waits for it by event).  Same box, K = 40
-        // (gpurun_out/r05_prio): own stream 3.12 ms per step with the fused kernel at 2.81 ms, preparation stream 3.14 /
-        // 2.785, host-made descriptors uploaded by DMA 3.075 / 2.76 -- the 0.09 ms of stores land inside the running fused
-        // kernel either way; the default keeps that kernel least disturbed.
-        static const bool own_stream = getenv("RAFTX_EXPAND_STREAM") && atoi(getenv("RAFTX_EXPAND_STREAM"));
-        if (own_stream && sPrep != c->stream) {
-            if (!c->sExp) {
-                int least = 0, greatest = 0;
-                if (hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess && least != greatest)
-                    HIPCHK(c, hipStreamCreateWithPriority(&c->sExp, hipStreamNonBlocking, greatest));
-                else
-                    HIPCHK(c, hipStreamCreateWithFlags(&c->sExp, hipStreamNonBlocking));
-                HIPCHK(c, hipEventCreateWithFlags(&c->evExp, hipEventDisableTiming));
-            }
-            HIPCHK(c, hipStreamWaitEvent(c->sExp, c->evUp, 0));
-            launch_expand(E, c->sExp);
-            HIPCHK(c, hipEventRecord(c->evExp, c->sExp));
-            HIPCHK(c, hipStreamWaitEvent(sPrep, c->evExp, 0));
-        } else {
-            launch_expand(E, sPrep);
-        }
+        // the expansion (0.09 ms of chip time) on the preparation stream, ahead of the member pass: its stores land inside the
+        // running fused kernel of the batch before (a high-priority stream of its own gained nothing: profiles/MEASUREMENT_HISTORY.md,
+        // "Closed scheduling experiments of the crossing")
+        launch_expand(E, sPrep);
     }
     // device-side scratch; on a pooled block a memset on sPrep is ordered before the kernels that use it
     int *errd = nullptr;
@@ -1419,8 +1382,7 @@ static int build_phase1(raftx_ctx *c, hipStream_t sCopy, hipStream_t sPrep, int 
     if (nMember > 0) {
         // member kernels on a (member position, design) grid when that wastes few threads: wavefronts of like members
         const int64_t maxMem = J.maxMem;
-        static const bool flat_members = getenv("RAFTX_GEOM_FLAT_MEMBERS") != nullptr;
-        A.mgrid = (!flat_members && nDesign >= 64 && maxMem * nDesign <= nMember + nMember / 4) ? (int)maxMem : 0;
+        A.mgrid = (nDesign >= 64 && maxMem * nDesign <= nMember + nMember / 4) ? (int)maxMem : 0;
         const int64_t nThread = A.mgrid > 0 ? (int64_t)A.mgrid * nDesign : nMember;
         hipLaunchKernelGGL(k_geom_member, dim3((unsigned)((nThread + 127) / 128)), dim3(128), 0, sPrep, A);
         if (add_mask & RAFTX_TRIM_BALLAST) {              // heave trim: density correction, then the inertia again
@@ -1435,9 +1397,7 @@ static int build_phase1(raftx_ctx *c, hipStream_t sCopy, hipStream_t sPrep, int 
         dev_alloc(c, c->design_allocs, (size_t)nDesign * 6, &A.Ws) || dev_alloc(c, c->design_allocs, (size_t)nDesign * RAFTX_SP_N, &A.props))
         return -2;
     J.reduce_stream = nullptr;
-    static const bool reduce_late = getenv("RAFTX_REDUCE_PHASE2") != nullptr;      // tuning: on the ctx stream, before the design kernel
-    J.reduce_late = reduce_late;
-    const bool side = nDesign > 0 && !reduce_late && sPrep != c->stream;          // crossings: a stream of its own per block context
+    const bool side = nDesign > 0 && sPrep != c->stream;          // crossings: a stream of its own per block context
     if (side) HIPCHK(c, hipEventRecord(c->evMem, sPrep));
     // the scan first: streams share hardware queues, and a reduction submitted ahead of it on the same queue would sit on
     // the path to the totals (the host waits for them before it can size and launch the generation)
@@ -1446,7 +1406,7 @@ static int build_phase1(raftx_ctx *c, hipStream_t sCopy, hipStream_t sPrep, int 
         HIPCHK(c, hipEventRecord(c->evG3, sPrep));
         HIPCHK(c, hipEventRecord(c->evTot, sPrep));
     }
-    if (nDesign > 0 && !reduce_late) {
+    if (nDesign > 0) {
         hipStream_t sRed = sPrep;
         if (side) {
             if (!c->sAux) HIPCHK(c, hipStreamCreateWithFlags(&c->sAux, hipStreamNonBlocking));
@@ -1535,10 +1495,8 @@ static int build_phase2(raftx_ctx *c, int64_t *stripOffsets, hipStream_t sGen = 
         // the ctx stream (where the fused kernel goes) behind everything the generation reads: scans, reductions
         HIPCHK(c, hipStreamWaitEvent(c->stream, c->evTot, 0));
         if (J.reduce_stream) HIPCHK(c, hipStreamWaitEvent(c->stream, c->evRed, 0));
-        if (J.reduce_late) hipLaunchKernelGGL(k_geom_reduce, dim3((unsigned)(((size_t)nDesign * 3 + 63) / 64)), dim3(64), 0, c->stream, A);
         J.gen_deferred = true;
     } else if (nDesign > 0) {
-        if (J.reduce_late) hipLaunchKernelGGL(k_geom_reduce, dim3((unsigned)(((size_t)nDesign * 3 + 63) / 64)), dim3(64), 0, sGen, A);
         // A sweep crossing in flight behind others (its member pass and reductions ran a step ago): the generation adds its
         // design's matrices up itself -- one kernel and one launch gap less on the path between two fused kernels (same
         // additions in the same order: bit-identical).  RAFTX_ADDUP_KERNEL=1 keeps k_geom_addup.
@@ -1626,7 +1584,7 @@ extern "C" int raftx_fetch_strips(raftx_ctx *c, double *strips, raftx_c128 *cm) 
     if (!c->g_n || !c->have_designs) FAIL(c, "fetch_strips: no raftx_build_designs call on this ctx");
     HIPCHK(c, hipSetDevice(c->device));
     if (strips && c->g_nStrips && !c->g_abi)
-        FAIL(c, "fetch_strips: the tables of this batch were generated inside the fused kernel of a sweep crossing (no ABI copy of the strip records)");
+        FAIL(c, "fetch_strips: the tables of this batch were generated by a sweep crossing, which keeps no ABI copy of the strip records");
     if (strips && c->g_nStrips)
         HIPCHK(c, hipMemcpyAsync(strips, c->g_abi, c->g_nStrips * NF * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     if (cm && c->g_nRows)
@@ -3180,14 +3138,9 @@ static int block_ctx(raftx_ctx *c, int slot, size_t i, raftx_ctx **out) {
 // block sizes: RAFTX_SWEEP_SPLIT="f0,f1,..." (fractions, tuning) | nChunk equal blocks | default: ONE block when the other slot
 // has a crossing in flight (streamed batches: that crossing's kernels hide this one's upload), otherwise a small first block
 // whose kernels hide the descriptor upload of the rest (every further block costs a partial last residency round of the
-// fused kernel plus the fixed latencies of the generation kernels: two blocks measured best)
-static std::vector<int> sweep_bounds(int nDesign, long pairs, int nChunk, bool pipelined, bool with_xi = false, int nCase = 1) {
-    // RAFTX_XI_SLABS=1: round 4's first form for a crossing that downloads its responses with nothing else in flight -- four
-    // BLOCKS, 20 / 30 / 30 / 20 %, each block's download under the next block's kernels (6.2-6.4 ms against 7.5 for two
-    // blocks downloaded whole).  Superseded by slabs of the fused launch inside the two blocks (SlabPlan, raftx_sweep_launch:
-    // 5.7 ms on the box where this form took 6.95); kept for A/B runs.
-    static const bool xi_slabs = getenv("RAFTX_XI_SLABS") && atoi(getenv("RAFTX_XI_SLABS"));     // round 4's first form: blocks as slabs
-    (void)nCase;
+// fused kernel plus the fixed latencies of the generation kernels: two blocks measured best, also for a crossing that
+// downloads its responses -- profiles/MEASUREMENT_HISTORY.md, "Closed scheduling experiments of the crossing")
+static std::vector<int> sweep_bounds(int nDesign, long pairs, int nChunk, bool pipelined) {
     std::vector<double> fr;
     static const char *env = getenv("RAFTX_SWEEP_SPLIT");
     if (env && nChunk <= 0) {
@@ -3204,7 +3157,6 @@ static std::vector<int> sweep_bounds(int nDesign, long pairs, int nChunk, bool p
     if (fr.empty()) {
         if (nChunk > 0) fr.assign((size_t)nChunk, 1.0);
         else if (pipelined) fr = {1.0};              // the crossing in the other slot hides this one's upload: one launch, no extra tail
-        else if (with_xi && xi_slabs && pairs >= 4096) fr = {0.2, 0.3, 0.3, 0.2};
         else if (pairs >= 3072) fr = {0.2, 0.8};     // measured on MI355X at 10 k pairs (profiles/r02_crossing_splits.txt)
         else fr = {1.0};
     }
@@ -3235,6 +3187,18 @@ static void slot_release_cases(raftx_ctx *c, SweepSlot &S) {
     S.cset = -1;
 }
 
+// a crossing failed while it was being enqueued: drains the device, retires the jobs of its blocks, unpins its sea states
+static int sweep_fail_drain(raftx_ctx *c, SweepSlot &S, int rc) {
+    (void)hipDeviceSynchronize();
+    for (raftx_ctx *sub : S.blk)
+        if (sub) {
+            free_list(sub, sub->job.tmp);
+            sub->job.active = false;
+        }
+    slot_release_cases(c, S);
+    return rc;
+}
+
 static int sweep_prepare_impl(raftx_ctx *c, int slot, int nDesign, const int64_t *memberOff, const double *members,
                               const int64_t *stationOff, const double *stations, const int64_t *capOff,
                               const double *caps, const double *pose, double rho, double g, int add_mask,
@@ -3259,7 +3223,8 @@ static int sweep_prepare_impl(raftx_ctx *c, int slot, int nDesign, const int64_t
     S.t0 = std::chrono::steady_clock::now();
     auto since = [&]() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - S.t0).count(); };
     if (!c->sCopy) {
-        // All four are ordinary streams.  Measured (scripts/ubench/queue_probe2.hip, scripts/gpu_prep.sh): a HIGH-priority
+        // All four are ordinary streams (the generation stream in a high priority class lost: profiles/MEASUREMENT_HISTORY.md,
+        // "Closed scheduling experiments of the crossing").  Measured (scripts/ubench/queue_probe2.hip, scripts/gpu_prep.sh): a HIGH-priority
         // preparation stream whose hardware queue happens to sit apart from the busy one does get the next batch's member
         // pass onto the chip early -- and the step gets SLOWER (4.21 vs 4.02 ms): its 184-VGPR waves break up the
         // 2 x 256-VGPR residency of the fused kernel's workgroups, and the earlier generation / fused kernel of the next
@@ -3268,18 +3233,7 @@ static int sweep_prepare_impl(raftx_ctx *c, int slot, int nDesign, const int64_t
         HIPCHK(c, hipStreamCreateWithFlags(&c->sCopy, hipStreamNonBlocking));
         HIPCHK(c, hipStreamCreateWithFlags(&c->sPrep, hipStreamNonBlocking));
         HIPCHK(c, hipStreamCreateWithFlags(&c->sD2H, hipStreamNonBlocking));
-        {
-            // RAFTX_GEN_PRIORITY=high (tuning): the generation stream in the highest priority class -- the tables of batch
-            // i+1 are what the next fused kernel waits for, the member pass of batch i+2 beside them is not.  Measured and NOT
-            // the default: the generation then runs INSIDE the running fused kernel and lengthens it (2.93 against 2.71 ms;
-            // step 3.13-3.15 against 3.05-3.07, profiles/r06_experiments/gap_design_staging_priority_ab.txt)
-            static const char *gp = getenv("RAFTX_GEN_PRIORITY");
-            int least = 0, greatest = 0;
-            if (gp && !strcmp(gp, "high") && hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess && least != greatest)
-                HIPCHK(c, hipStreamCreateWithPriority(&c->sGen, hipStreamNonBlocking, greatest));
-            else
-                HIPCHK(c, hipStreamCreateWithFlags(&c->sGen, hipStreamNonBlocking));
-        }
+        HIPCHK(c, hipStreamCreateWithFlags(&c->sGen, hipStreamNonBlocking));
     }
     if (!S.evXi) HIPCHK(c, hipEventCreate(&S.evXi));
     // sea-state tables: sets resident on the parent, shared by the blocks of every slot that was prepared with the same
@@ -3317,7 +3271,7 @@ static int sweep_prepare_impl(raftx_ctx *c, int slot, int nDesign, const int64_t
         S.cset = hit;
     }
     const DevTables &CT = c->csets[S.cset].T;
-    S.bnd = sweep_bounds(nDesign, (long)nDesign * nCase, nChunk, others_in_flight(c, slot), Xi != nullptr, nCase);
+    S.bnd = sweep_bounds(nDesign, (long)nDesign * nCase, nChunk, others_in_flight(c, slot));
     const std::vector<int> &bnd = S.bnd;
     const size_t nB = bnd.size() - 1;
     S.dw = nw > 1 ? w[1] - w[0] : w[0];
@@ -3330,16 +3284,6 @@ static int sweep_prepare_impl(raftx_ctx *c, int slot, int nDesign, const int64_t
     // the slot's previous crossing has been waited for: its tables and offset arrays are free
     free_list(c, S.allocs);
     S.modal.on = false;
-    auto fail_drain = [&](int rc) {
-        (void)hipDeviceSynchronize();
-        for (raftx_ctx *sub : blk)
-            if (sub) {
-                free_list(sub, sub->job.tmp);
-                sub->job.active = false;
-            }
-        slot_release_cases(c, S);
-        return rc;
-    };
     // ---- the batch's offset arrays: one upload, shared by the blocks
     DevOffsets dOff{nullptr, nullptr, nullptr};
     {
@@ -3351,7 +3295,7 @@ static int sweep_prepare_impl(raftx_ctx *c, int slot, int nDesign, const int64_t
         int rc = upload_on(c, c->sCopy, S.allocs, memberOff, (size_t)nDesign + 1, &dOff.memberOff);
         rc |= upload_on(c, c->sCopy, S.allocs, stationOff, (size_t)nMemberAll + 1, &dOff.stationOff);
         if (capOff) rc |= upload_on(c, c->sCopy, S.allocs, capOff, (size_t)nMemberAll + 1, &dOff.capOff);
-        if (rc) return fail_drain(-2);
+        if (rc) return sweep_fail_drain(c, S, -2);
     }
     // ---- phase 1: H2D on sCopy, member pass + scans on sPrep.  Every block here -- except for an isolated crossing cut into
     // slabs (responses wanted, nothing else in flight): there only the first two; raftx_sweep_launch enqueues the others one
@@ -3361,7 +3305,7 @@ static int sweep_prepare_impl(raftx_ctx *c, int slot, int nDesign, const int64_t
             var ? *var : VariantSrc{nullptr, nullptr}};
     const size_t nFirst = (Xi && nB > 2 && !others_in_flight(c, slot)) ? 2 : nB;
     for (size_t b = 0; b < nB; b++)
-        if (block_ctx(c, slot, b, &blk[b])) return fail_drain(-1);
+        if (block_ctx(c, slot, b, &blk[b])) return sweep_fail_drain(c, S, -1);
     for (size_t b = 0; b < nFirst; b++) {
         raftx_ctx *sub = blk[b];
         const int lo = bnd[b], n = bnd[b + 1] - lo;
@@ -3369,7 +3313,7 @@ static int sweep_prepare_impl(raftx_ctx *c, int slot, int nDesign, const int64_t
                                     rho, g, nw, k, add_mask, M0, B0, C0, nullptr, Fz_moor, &S.p1.dOff, CT.k, var);
         if (rc) {
             snprintf(c->err, sizeof(c->err), "sweep_stats (block %zu): %s", b, sub->err);
-            return fail_drain(rc);
+            return sweep_fail_drain(c, S, rc);
         }
     }
     S.next_p1 = nFirst;
@@ -3529,20 +3473,6 @@ extern "C" int raftx_sweep_prepare_variants(raftx_ctx *c, int slot, int nDesign,
                               stripOffsets, &var);
 }
 
-// The compute stream of a crossing: the ctx stream -- or, RAFTX_SWEEP_STREAMS=2, one of two that crossings of consecutive slots
-// alternate between, so that their persistent grids can be on the chip together.  Measured in round 6 and NOT the default
-// (profiles/r06_experiments/): the fused grids of consecutive 10 000-design batches do not overlap in practice, because what
-// lies between them is the chain member pass -> host -> table generation of the NEXT batch, whose kernels cannot get onto a
-// chip that a persistent grid fills and so run in its drain whatever the streams (3.06-3.09 ms per step on one stream or
-// two, 4 or 12 hardware queues, pipeline depth 3; depth 4: 3.13-3.3); leaving 32-128 workgroup places of the grid free for
-// them does not help either -- a 256-thread block needs room on all four SIMDs of a CU, and a CU with three of its four
-// pairs still has two SIMDs full (3.14-3.35 ms).  The 1 250-design shard gains 8 % of kernel time and nothing per step.
-static hipStream_t slot_stream(raftx_ctx *c, int slot) {
-    static const int n_streams = getenv("RAFTX_SWEEP_STREAMS") ? std::max(1, std::min(2, atoi(getenv("RAFTX_SWEEP_STREAMS")))) : 1;
-    if (n_streams > 1 && !c->sMainB) (void)hipStreamCreateWithFlags(&c->sMainB, hipStreamNonBlocking);
-    return (n_streams > 1 && c->sMainB && (slot & 1)) ? c->sMainB : c->stream;
-}
-
 // The eigen analysis of one block of a crossing (raftx_sweep_modal) on stream st, which is behind whatever wrote the
 // block's summed M0 / C0 (k_geom_addup, k_geom_design with the add-up folded in, or the generating fused kernel): one
 // system per lane, the results written straight into the block's page-locked landing area
@@ -3580,6 +3510,80 @@ static hipError_t modal_block(raftx_ctx *sub, SweepSlot &S, int lo, int n, hipSt
     return hipGetLastError();
 }
 
+// The stream the responses of a crossing are downloaded on: one of the HIGHEST priority class, created when first needed (so
+// late, it does not move the other streams' hardware queues).  A priority class has hardware queues of its own and the highest
+// is served at once: the copy never sits in a queue with the next batch's kernels (ordinary stream) nor starts a step late
+// (lowest class): profiles/MEASUREMENT_HISTORY.md, "Closed scheduling experiments of the crossing".  A device with one class,
+// or a failed creation: the ordinary download stream.
+static hipStream_t download_stream(raftx_ctx *c) {
+    if (!c->sD2Hhigh) {
+        int least = 0, greatest = 0;
+        if (hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess && least != greatest)
+            (void)hipStreamCreateWithPriority(&c->sD2Hhigh, hipStreamNonBlocking, greatest);
+    }
+    return c->sD2Hhigh ? c->sD2Hhigh : c->sD2H;
+}
+
+// Statistics, iteration counts and flags of block b go straight into its page-locked landing area (the kernels store there:
+// no small D2H copy that could queue on the DMA engine behind a bulk download), on the ctx stream behind the block's fused
+// launch; behind them, on the download stream, the block's responses unless they leave slab by slab.
+static int enqueue_stats(raftx_ctx *c, SweepSlot &S, size_t b, hipStream_t sDown) {
+    raftx_ctx *sub = S.blk[b];
+    const int lo = S.bnd[b], nCase = S.nCase, nHead = S.nHead, nw = S.nw;
+    const size_t npair = (size_t)(S.bnd[b + 1] - lo) * nCase;
+    hipError_t e = hipEventRecord(sub->evS0, c->stream);
+    if (npair) {
+        hipLaunchKernelGGL(k_motion_stats, dim3((unsigned)npair), dim3(nw > 128 ? 256 : (nw > 64 ? 128 : 64)), 0, c->stream,
+                           (int)npair, nHead, nw, 1.0 / S.dw, sub->rXi, sub->pinRes, (double *)nullptr, (const int *)sub->rNi,
+                           (const int *)sub->rFl, reinterpret_cast<int *>(sub->pinRes + npair * 6));
+    }
+    if (e == hipSuccess) e = hipEventRecord(sub->evS1, c->stream);
+    if (e == hipSuccess && S.modal.on) e = modal_block(sub, S, lo, S.bnd[b + 1] - lo, c->stream);
+    if (e == hipSuccess) e = hipEventRecord(sub->evDone, c->stream);
+    if (e == hipSuccess && S.Xi && !S.slab) {
+        e = hipStreamWaitEvent(sDown, sub->evDone, 0);
+        if (e == hipSuccess && sub->r_nx)
+            e = hipMemcpyAsync(S.Xi + (size_t)lo * nCase * nHead * 6 * nw, sub->rXi, sub->r_nx * sizeof(cplx), hipMemcpyDeviceToHost, sDown);
+    }
+    if (e != hipSuccess) {
+        snprintf(sub->err, sizeof(sub->err), "statistics / download of the block: %s", hipGetErrorString(e));
+        return -2;
+    }
+    return 0;
+}
+
+// Responses wanted and nothing else in flight: the launch of block b is cut into slabs of the pair list on the slab
+// stream(s), each followed by its own download (SlabPlan).  The download (3.5 ms for 192 MB) is longer than the solve, so
+// the call ends one slab's download after the last slab when the first download starts early and the copy engine is then
+// never left waiting.  Measured (profiles/DESIGN_HISTORY_r01-r05.md, 10 000 pairs, one box, median of six calls): whole
+// blocks 7.7 ms; slabs of 512 / 768 / 1024 / 1536 pairs on one slab stream 7.9 / 6.2 / 5.7 / 6.1 -- one residency round per
+// slab (256 CUs x 4 pairs) -- and no better on two or three streams (6.0-6.3).  RAFTX_XI_SLAB_PAIRS: pairs per slab (0: whole
+// blocks); RAFTX_XI_SLAB_STREAMS: 1 .. 3.
+static void slab_plan_block(SlabPlan &plan, SweepSlot &S, size_t b, size_t slab_pairs, hipStream_t sDown) {
+    raftx_ctx *sub = S.blk[b];
+    const size_t npair = (size_t)(S.bnd[b + 1] - S.bnd[b]) * S.nCase;
+    plan.bnd.clear();
+    for (size_t p = 0; p < npair; p += slab_pairs) plan.bnd.push_back(p);
+    if (plan.bnd.size() > 1 && npair - plan.bnd.back() < slab_pairs / 2) plan.bnd.pop_back();   // no sliver at the end
+    plan.bnd.push_back(npair);
+    size_t *kslab = &S.nSlabEv;
+    S.nSlabEv = 0;
+    const size_t per = (size_t)S.nHead * 6 * S.nw;
+    raftx_c128 *out = S.Xi + (size_t)S.bnd[b] * S.nCase * per;
+    plan.after = [=](size_t q0, size_t q1, hipStream_t s) -> int {
+        if (q1 <= q0) return 0;
+        while (sub->evSlab.size() <= *kslab) {
+            hipEvent_t e = nullptr;
+            if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) return -2;
+            sub->evSlab.push_back(e);
+        }
+        hipEvent_t e = sub->evSlab[(*kslab)++];
+        if (hipEventRecord(e, s) != hipSuccess || hipStreamWaitEvent(sDown, e, 0) != hipSuccess) return -2;
+        return hipMemcpyAsync(out + q0 * per, sub->rXi + q0 * per, (q1 - q0) * per * sizeof(cplx), hipMemcpyDeviceToHost, sDown) ==
+                       hipSuccess ? 0 : -2;
+    };
+}
+
 extern "C" int raftx_sweep_launch(raftx_ctx *c, int slot) {
     RangeScope range_("raftx_sweep_launch: generation + fused fixed point + statistics (enqueue)");
     if (!c) return -1;
@@ -3589,63 +3593,26 @@ extern "C" int raftx_sweep_launch(raftx_ctx *c, int slot) {
     if (S.cset < 0 || c->csets[S.cset].T.nCase != S.nCase || c->csets[S.cset].T.nHead != S.nHead || c->csets[S.cset].T.nw != S.nw)
         FAIL(c, "sweep_launch: slot %d has lost its sea-state tables (internal error)", slot);
     HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t sM = slot_stream(c, slot);
-    const bool two_streams = c->sMainB != nullptr;
-    for (raftx_ctx *sub : S.blk)
-        if (sub) sub->stream = sM;
     if (!c->evEpoch) {
         HIPCHK(c, hipEventCreate(&c->evEpoch));
-        HIPCHK(c, hipEventRecord(c->evEpoch, sM));
+        HIPCHK(c, hipEventRecord(c->evEpoch, c->stream));
     }
     auto since = [&]() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - S.t0).count(); };
     const std::vector<int> &bnd = S.bnd;
     const size_t nB = bnd.size() - 1;
     std::vector<raftx_ctx *> &blk = S.blk;
-    const int nCase = S.nCase, nHead = S.nHead, nw = S.nw, nIter = S.nIter;
-    const double tol = S.tol, XiStart = S.XiStart, dw = S.dw;
-    raftx_c128 *Xi = S.Xi;
+    const int nCase = S.nCase;
     S.prepared = false;
-    auto fail_drain = [&](int rc) {
-        (void)hipDeviceSynchronize();
-        for (raftx_ctx *sub : blk)
-            if (sub) {
-                free_list(sub, sub->job.tmp);
-                sub->job.active = false;
-            }
-        slot_release_cases(c, S);
-        return rc;
-    };
-    // ---- full responses, if asked for: every block's download is enqueued right behind the block's kernels, on a stream of
-    // its own (enqueued after ALL blocks -- as until round 4 -- the first download of an isolated call could not start before
-    // the host had seen the member pass of the LAST block, i.e. before every descriptor had been uploaded: 1.6 ms late)
-    hipStream_t sDown = nullptr;
-    if (Xi) {
-        // The bulk download goes to a stream of its own PRIORITY CLASS, created when first needed: priority classes have
-        // hardware queues of their own, whereas the ordinary streams of this library share four, and a hardware queue is in
-        // order -- the generation and the fused kernel of batch i+1 used to queue behind the 3.4 ms copy of batch i whenever
-        // the two streams landed on one queue (round 3: 7.0 ms per step instead of 4.6-5.0).  Created late, it does not move the
-        // other streams' queues (the plain step is sensitive to those: +5 % with the generation stream one queue further).
-        // Which class: round 3 took the LOWEST, and the copy / kernel timeline of round 4 (profiles/r04_xi_timeline.txt)
-        // shows what that costs -- the command processor does not look at a low-priority queue while a 10 000-workgroup grid
-        // of the ordinary class is being handed out, so the download of batch i only STARTED 0.26 ms before the end of batch
-        // i+1's fused kernel, a whole step late, and then ran beside nothing.  The HIGHEST class is served at once: the copy
-        // is a barrier packet and an SDMA transfer, no compute, and starts when the batch's statistics kernel has finished.
-        // RAFTX_D2H_PRIORITY = high (default) | low | 0 (the ordinary download stream).
-        static const char *d2h_env = getenv("RAFTX_D2H_PRIORITY");
-        static const bool d2h_own = !(d2h_env && !strcmp(d2h_env, "0"));
-        static const bool d2h_low = d2h_own && d2h_env && !strcmp(d2h_env, "low");
-        if (d2h_own && !c->sD2Hlow) {
-            int least = 0, greatest = 0;
-            if (hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess && least != greatest)
-                (void)hipStreamCreateWithPriority(&c->sD2Hlow, hipStreamNonBlocking, d2h_low ? least : greatest);
-        }
-        sDown = (d2h_own && c->sD2Hlow) ? c->sD2Hlow : c->sD2H;
-    }
-    // ---- phase 2 + fixed point + statistics of every block, in order, on the ctx stream
+    // ---- full responses, if asked for: every block's download is enqueued right behind the block's kernels (after ALL blocks,
+    // the first download of an isolated call waited for the host to see the member pass of the LAST block: 1.6 ms late)
+    hipStream_t sDown = S.Xi ? download_stream(c) : nullptr;
+    // ---- phase 2 + fixed point + statistics of every block, in order, on the ctx stream (the scheduling variants that lost --
+    // a second compute stream among them: profiles/MEASUREMENT_HISTORY.md, "Closed scheduling experiments of the crossing")
     int rc_all = 0;
     static const long slab_pairs = getenv("RAFTX_XI_SLAB_PAIRS") ? atol(getenv("RAFTX_XI_SLAB_PAIRS")) : 1024;
     static const int slab_streams = getenv("RAFTX_XI_SLAB_STREAMS") ? std::min(3, std::max(1, atoi(getenv("RAFTX_XI_SLAB_STREAMS")))) : 1;
-    const bool slab_mode = Xi && sDown && slab_pairs > 0 && !others_in_flight(c, slot);
+    const bool pipelined = others_in_flight(c, slot);
+    const bool slab_mode = S.Xi && sDown && slab_pairs > 0 && !pipelined;
     SlabPlan plan;
     S.slab = slab_mode;
     if (slab_mode) {
@@ -3655,116 +3622,36 @@ extern "C" int raftx_sweep_launch(raftx_ctx *c, int slot) {
             plan.alts.push_back(*ss[i]);
         }
     }
-    // statistics, iteration counts and flags of a block go straight into its page-locked landing area (the kernels store
-    // there: no small D2H copy that could queue on the DMA engine behind a bulk download); behind them, on the download
-    // stream, the block's responses unless they leave slab by slab
-    // RAFTX_STATS_STREAM=1: the statistics of a batch on a stream of their own behind its fused kernel, so that the next
-    // batch's fused kernel (same main stream) does not wait for them
-    const char *ss_ = getenv("RAFTX_STATS_STREAM");
-    const bool stats_side = ss_ && atoi(ss_);
-    if (stats_side && !c->sStat) HIPCHK(c, hipStreamCreateWithFlags(&c->sStat, hipStreamNonBlocking));
-    auto enqueue_stats = [&](size_t b) -> int {
-        raftx_ctx *sub = blk[b];
-        const int lo = bnd[b];
-        const size_t npair = (size_t)(bnd[b + 1] - lo) * nCase;
-        hipStream_t sS = sM;
-        hipError_t e = hipSuccess;
-        if (stats_side && c->sStat && !slab_mode) {
-            sS = c->sStat;
-            e = hipStreamWaitEvent(sS, sub->ev1, 0);                   // the end of the block's fused launch (solve_enqueue)
-        }
-        if (e == hipSuccess) e = hipEventRecord(sub->evS0, sS);
-        if (npair) {
-            hipLaunchKernelGGL(k_motion_stats, dim3((unsigned)npair), dim3(nw > 128 ? 256 : (nw > 64 ? 128 : 64)), 0, sS,
-                               (int)npair, nHead, nw, 1.0 / dw, sub->rXi, sub->pinRes, (double *)nullptr, (const int *)sub->rNi,
-                               (const int *)sub->rFl, reinterpret_cast<int *>(sub->pinRes + npair * 6));
-        }
-        if (e == hipSuccess) e = hipEventRecord(sub->evS1, sS);
-        if (e == hipSuccess && S.modal.on) e = modal_block(sub, S, lo, bnd[b + 1] - lo, sS);
-        if (e == hipSuccess) e = hipEventRecord(sub->evDone, sS);
-        if (e == hipSuccess && Xi && !slab_mode) {
-            const size_t p0 = (size_t)lo * nCase;
-            e = hipStreamWaitEvent(sDown, sub->evDone, 0);
-            if (e == hipSuccess && sub->r_nx)
-                e = hipMemcpyAsync(Xi + p0 * nHead * 6 * nw, sub->rXi, sub->r_nx * sizeof(cplx), hipMemcpyDeviceToHost, sDown);
-        }
-        if (e != hipSuccess) {
-            snprintf(sub->err, sizeof(sub->err), "statistics / download of the block: %s", hipGetErrorString(e));
-            return -2;
-        }
-        return 0;
-    };
+    S.tlb.clear();
     for (size_t b = 0; b < nB && !rc_all; b++) {
         raftx_ctx *sub = blk[b];
-        const int lo = bnd[b], n = bnd[b + 1] - lo;
-        const size_t npair = (size_t)n * nCase;
-        // measured (profiles/r02_crossing_splits.txt): generating a block's tables beside the fused kernel of the block
-        // before it gains nothing (the block's descriptor upload is what it waits for) and inflates the kernel's timed
-        // duration, so the default keeps everything on the ctx stream; RAFTX_SWEEP_GEN_OVERLAP=1 turns the overlap on
-        // A crossing launched while another one is solving generates its tables on a stream of its own: its member pass
-        // ran a step earlier (raftx_sweep_prepare), so the tables can be built in the drain of the running fused kernel
-        // and this crossing's fused kernel follows it without a gap.  RAFTX_SWEEP_GEN_OVERLAP=0 keeps the generation on
-        // the ctx stream.
-        static const bool gen_overlap = !(getenv("RAFTX_SWEEP_GEN_OVERLAP") && !atoi(getenv("RAFTX_SWEEP_GEN_OVERLAP")));
-        const bool pipelined = others_in_flight(c, slot);
         int rc = 0;
-        if (b == 0) S.tlb.clear();
         if (S.next_p1 < nB && S.next_p1 <= b + 1) {                     // deferred phase 1: keep one block's upload ahead
             const size_t bn = S.next_p1++;
-            const int rc1 = build_phase1(blk[bn], c->sCopy, c->sPrep, bnd[bn], bnd[bn + 1] - bnd[bn], S.p1.memberOff, S.p1.members,
-                                         S.p1.stationOff, S.p1.stations, S.p1.capOff, S.p1.caps, S.p1.pose, S.p1.rho, S.p1.g, nw, S.p1.k,
-                                         S.p1.add_mask, S.p1.M0, S.p1.B0, S.p1.C0, nullptr, S.p1.Fz_moor, &S.p1.dOff,
-                                         c->csets[S.cset].T.k, &S.p1.var);
-            if (rc1) {
-                snprintf(sub->err, sizeof(sub->err), "%s", blk[bn]->err);
-                rc = rc1;
-            }
+            rc = build_phase1(blk[bn], c->sCopy, c->sPrep, bnd[bn], bnd[bn + 1] - bnd[bn], S.p1.memberOff, S.p1.members,
+                              S.p1.stationOff, S.p1.stations, S.p1.capOff, S.p1.caps, S.p1.pose, S.p1.rho, S.p1.g, S.nw, S.p1.k,
+                              S.p1.add_mask, S.p1.M0, S.p1.B0, S.p1.C0, nullptr, S.p1.Fz_moor, &S.p1.dOff, c->csets[S.cset].T.k,
+                              &S.p1.var);
+            if (rc) snprintf(sub->err, sizeof(sub->err), "%s", blk[bn]->err);
         }
-        // RAFTX_GEN_EARLY=1 (tuning): no such wait -- behind a PERSISTENT grid the generation cannot start before the first
-        // workgroups of that grid leave anyway
-        static const bool gen_early = getenv("RAFTX_GEN_EARLY") && atoi(getenv("RAFTX_GEN_EARLY"));
-        if (b == 0 && pipelined && gen_overlap && !two_streams && !gen_early) {
-            // When does the generation run?  Enqueued now, beside a fused kernel that has only just started, it would be
-            // dispatched at once and take LDS from that kernel for its whole run (measured: +0.25 ms on the kernel).  A
-            // small kernel queued BEHIND a running big grid is dispatched when that grid has been handed out -- which is
-            // when the member pass of the batch prepared last gets onto the chip: the generation waits for that batch's
-            // first kernel and so runs in the drain, beside that member pass.
+        // A crossing launched while another one is solving generates its tables on the generation stream: its member pass ran
+        // a step earlier (raftx_sweep_prepare), so the tables can be built in the drain of the running fused kernel.  (The
+        // blocks of an isolated crossing wait for their descriptor upload: everything on the ctx stream,
+        // profiles/r02_crossing_splits.txt.)  Enqueued now, beside a fused kernel that has only just started, the generation
+        // would be dispatched at once and take LDS from that kernel for its whole run (measured: +0.25 ms on the kernel).  A
+        // small kernel queued BEHIND a running big grid is dispatched when that grid has been handed out -- which is when
+        // the member pass of the batch prepared last gets onto the chip: the generation waits for that batch's first
+        // kernel and so runs in the drain, beside that member pass.
+        if (b == 0 && pipelined) {
             for (int sl = 0; sl < RAFTX_NSLOT && !rc; sl++)
                 if (sl != slot && c->slots[sl].prepared && !c->slots[sl].blk.empty() && c->slots[sl].blk[0])
                     if (hipStreamWaitEvent(c->sGen, c->slots[sl].blk[0]->evZ, 0) != hipSuccess) rc = -2;
         }
-        // slabs of a crossing that downloads its responses (sweep_bounds): RAFTX_XI_GEN_OVERLAP=1 generates the tables of slab
-        // b + 1 on the side stream while slab b solves -- measured with five slabs: 6.71 against 6.74 ms, so it stays off (the
-        // fused kernel's HIP-event time then is that launch alone)
-        static const bool xi_gen_overlap = getenv("RAFTX_XI_GEN_OVERLAP") && atoi(getenv("RAFTX_XI_GEN_OVERLAP"));
-        const bool gen_side = (pipelined && gen_overlap) || (b > 0 && Xi != nullptr && nB > 2 && xi_gen_overlap);
         S.tlb.push_back(since());
         // (a crossing: no ABI copy of the strip records; with RAFTX_FUSED_GEN=1 the tables are left to the fused kernel itself,
         // raftx_fusedgen.h -- build_phase2 / solve_enqueue decide)
-        if (!rc) rc = build_phase2(sub, nullptr, gen_side ? c->sGen : nullptr, 1 | ((nCase == 1 && !slab_mode) ? 2 : 0) | (pipelined ? 4 : 0));
+        if (!rc) rc = build_phase2(sub, nullptr, pipelined ? c->sGen : nullptr, 1 | ((nCase == 1 && !slab_mode) ? 2 : 0) | (pipelined ? 4 : 0));
         S.tlb.push_back(since());
-        // (with the generation inside the fused kernel nothing of this batch runs in the drain any more: the fused kernel
-        // follows the one before it at once, and the next batch's member pass takes the places the drain frees beside it;
-        // RAFTX_FUSED_WAIT_MEMBER=1 keeps the wait)
-        const char *fw_ = getenv("RAFTX_FUSED_WAIT_MEMBER");
-        const bool fused_wait_member = fw_ && atoi(fw_);
-        // Round 6: that wait is OFF by default (RAFTX_MEMBER_WAIT=1 restores it).  With the persistent grid the member pass
-        // queued behind this batch gets onto the chip in the drain of the fused kernel before it either way, and what has
-        // not finished then runs beside this kernel's first workgroups; same box, alternating, three batches in flight:
-        // 3.033-3.043 ms per step without the wait against 3.045-3.062 with it, no difference with two batches in flight
-        // (profiles/r06_experiments/gap_design_staging_priority_ab.txt).
-        static const bool no_member_wait = !(getenv("RAFTX_MEMBER_WAIT") && atoi(getenv("RAFTX_MEMBER_WAIT")));
-        if (!rc && b == 0 && pipelined && gen_overlap && !two_streams && !no_member_wait && (!sub->job.gen_deferred || fused_wait_member)) {
-            // Small kernels are not dispatched while a big grid is being handed out: whatever of the NEXT batch's member pass
-            // has not finished when this batch's fused kernel starts would wait for the whole kernel and stall that batch's
-            // launch a step later.  So this fused kernel starts only when the member passes already queued (the batches
-            // prepared but not yet launched) are done as well -- they run beside this batch's table generation, in the
-            // drain of the fused kernel before.
-            for (int sl = 0; sl < RAFTX_NSLOT && !rc; sl++)
-                if (sl != slot && c->slots[sl].prepared)
-                    for (raftx_ctx *o : c->slots[sl].blk)
-                        if (o && hipStreamWaitEvent(sM, o->evTot, 0) != hipSuccess) rc = -2;
-        }
         if (!rc) {                                                      // the sea states this crossing was prepared with
             DevTables &T = sub->T;
             const DevTables &P = c->csets[S.cset].T;
@@ -3772,49 +3659,19 @@ extern "C" int raftx_sweep_launch(raftx_ctx *c, int slot) {
             T.w = P.w; T.k = P.k; T.csh = P.csh; T.cch = P.cch; T.zeta = P.zeta; T.beta = P.beta;
             T.depth = P.depth; T.rho = P.rho; T.g = P.g;
             sub->have_cases = true;
-            // Responses wanted and nothing else in flight: the block's launch is cut into slabs of the pair list on the slab
-            // stream(s), each followed by its own download (SlabPlan).  The download (3.5 ms for 192 MB) is longer than the
-            // solve, so the call ends one slab's download after the last slab when the first download starts early and the
-            // copy engine is then never left waiting.  Measured (scripts/gpu_r4_slab.sh, 10 000 pairs, one box, median of six
-            // calls): whole blocks 7.7 ms; four blocks as slabs (round 4's first form) 6.95; slabs of 512 / 768 / 1024 / 1536
-            // pairs on one slab stream 7.9 / 6.2 / 5.7 / 6.1 -- one residency round per slab (256 CUs x 4 pairs) -- and no
-            // better on two or three streams (6.0-6.3).  RAFTX_XI_SLAB_PAIRS: pairs per slab (0: whole blocks);
-            // RAFTX_XI_SLAB_STREAMS: 1 .. 3.
-            if (slab_mode) {
-                plan.bnd.clear();
-                for (size_t p = 0; p < npair; p += (size_t)slab_pairs) plan.bnd.push_back(p);
-                if (plan.bnd.size() > 1 && npair - plan.bnd.back() < (size_t)slab_pairs / 2) plan.bnd.pop_back();   // no sliver at the end
-                plan.bnd.push_back(npair);
-                size_t *kslab = &S.nSlabEv;
-                S.nSlabEv = 0;
-                plan.after = [=](size_t q0, size_t q1, hipStream_t s) -> int {
-                    if (q1 <= q0) return 0;
-                    while (sub->evSlab.size() <= *kslab) {
-                        hipEvent_t e = nullptr;
-                        if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) return -2;
-                        sub->evSlab.push_back(e);
-                    }
-                    hipEvent_t e = sub->evSlab[(*kslab)++];
-                    const size_t per = (size_t)nHead * 6 * nw;
-                    if (hipEventRecord(e, s) != hipSuccess || hipStreamWaitEvent(sDown, e, 0) != hipSuccess) return -2;
-                    return hipMemcpyAsync(Xi + ((size_t)lo * nCase + q0) * per, sub->rXi + q0 * per, (q1 - q0) * per * sizeof(cplx),
-                                          hipMemcpyDeviceToHost, sDown) == hipSuccess ? 0 : -2;
-                };
-            }
-            if (!rc) rc = solve_enqueue(sub, nIter, tol, XiStart, nullptr, 0, slab_mode ? &plan : nullptr);
+            if (slab_mode) slab_plan_block(plan, S, b, (size_t)slab_pairs, sDown);
+            rc = solve_enqueue(sub, S.nIter, S.tol, S.XiStart, nullptr, 0, slab_mode ? &plan : nullptr);
         }
-        if (!rc) {
-            const size_t need = npair * 7 + 2;                          // std [npair,6] | niter, flags [npair] int32 each
-            if (!sub->pinRes || sub->pinRes_n < need) {
-                if (sub->pinRes) (void)hipHostFree(sub->pinRes);
-                sub->pinRes = nullptr;
-                void *p_ = nullptr;
-                if (hipHostMalloc(&p_, need * sizeof(double), hipHostMallocDefault) != hipSuccess) rc = -2;
-                sub->pinRes = reinterpret_cast<double *>(p_);
-                sub->pinRes_n = need;
-            }
+        const size_t need = (size_t)(bnd[b + 1] - bnd[b]) * nCase * 7 + 2;   // std [npair,6] | niter, flags [npair] int32 each
+        if (!rc && (!sub->pinRes || sub->pinRes_n < need)) {
+            if (sub->pinRes) (void)hipHostFree(sub->pinRes);
+            sub->pinRes = nullptr;
+            void *p_ = nullptr;
+            if (hipHostMalloc(&p_, need * sizeof(double), hipHostMallocDefault) != hipSuccess) rc = -2;
+            sub->pinRes = reinterpret_cast<double *>(p_);
+            sub->pinRes_n = need;
         }
-        if (!rc && !slab_mode) rc = enqueue_stats(b);                   // (slab mode: after the join, below)
+        if (!rc && !slab_mode) rc = enqueue_stats(c, S, b, sDown);      // (slab mode: after the join, below)
         S.tlb.push_back(since());
         if (rc) {
             snprintf(c->err, sizeof(c->err), "sweep_stats (block %zu): %s", b, sub->err);
@@ -3823,15 +3680,15 @@ extern "C" int raftx_sweep_launch(raftx_ctx *c, int slot) {
     }
     if (!rc_all && slab_mode) {                                         // the statistics read what the slabs wrote: behind all of them
         if (!blk[0]->evJoin && hipEventCreateWithFlags(&blk[0]->evJoin, hipEventDisableTiming) != hipSuccess) rc_all = -2;
-        if (!rc_all) rc_all = slab_join(blk[0], sM, plan.alts);
-        if (!rc_all && hipEventRecord(blk[nB - 1]->ev1, sM) != hipSuccess) rc_all = -2;
+        if (!rc_all) rc_all = slab_join(blk[0], c->stream, plan.alts);
+        if (!rc_all && hipEventRecord(blk[nB - 1]->ev1, c->stream) != hipSuccess) rc_all = -2;
         for (size_t b = 0; b < nB && !rc_all; b++) {
-            rc_all = enqueue_stats(b);
+            rc_all = enqueue_stats(c, S, b, sDown);
             if (rc_all) snprintf(c->err, sizeof(c->err), "sweep_stats (block %zu): %s", b, blk[b]->err);
         }
     }
-    if (!rc_all && Xi && hipEventRecord(S.evXi, sDown) != hipSuccess) rc_all = -2;
-    if (rc_all) return fail_drain(rc_all);
+    if (!rc_all && S.Xi && hipEventRecord(S.evXi, sDown) != hipSuccess) rc_all = -2;
+    if (rc_all) return sweep_fail_drain(c, S, rc_all);
     S.tl[2] = since();
     S.busy = true;
     return 0;

@@ -2307,7 +2307,7 @@ struct XlStore<true> {
 // The global XiLast scratch is indexed by a SLOT the workgroup holds while it runs, not by its pair: 2 048 regions of 12 nw
 // doubles (39 MB at 200 bins) whatever the batch size, instead of 19.2 KB per pair (192 MB for 10 000 pairs, 3.8 GB for the
 // 200 000-pair launches).  A slot is re-used by the workgroups that follow each other on the same XCD -- 128 resident ones x
-// 19.2 KB = 2.4 MB of the XCD's 4 MB L2.  Measured (round 5, same box, alternating: scripts/gpu_r5_slots_ab.sh): kernel 2.791-
+// 19.2 KB = 2.4 MB of the XCD's 4 MB L2.  Measured (round 5, same box, alternating: profiles/r05_slot_scratch_ab.json): kernel 2.791-
 // 2.800 ms against 2.800-2.809 with the per-pair slab; the L2 <-> fabric traffic does NOT change (FETCH_SIZE 1.323 GB,
 // WRITE_SIZE 1.451 GB per launch either way, gpurun_out/r05_slots): the stores of a kernel are written through to the fabric
 // whether or not the line stays in the L2 -- 1.451 GB is exactly the XiLast (113 KB), F_lin (19 KB) and Xi (19 KB) stores of
