@@ -1681,20 +1681,7 @@ struct Shape {
 #define RAFTX_MINB128 2          // waves per SIMD the default 200-bin shape is compiled for (tuning builds override)
 #endif
 #define SHAPES(X) X(1, 64, 1) X(2, 64, 1) X(4, 64, 1) X(2, 128, RAFTX_MINB128) X(1, 256, 2) X(2, 256, 2) X(2, 512, 1) X(3, 512, 1) X(4, 512, 1)
-// MAXT template value of the kernel instantiated for a shape
-static int shape_maxt(Shape sh) {
-#define X(NB_, MT_, MB_) if (sh.nb == NB_ && sh.threads == MT_) return MT_;
-    SHAPES(X)
-#undef X
-    return 0;
-}
-// waves per SIMD the kernel of a shape is compiled for
-static int shape_minb(Shape sh) {
-#define X(NB_, MT_, MB_) if (sh.nb == NB_ && sh.threads == MT_) return MB_;
-    SHAPES(X)
-#undef X
-    return 1;
-}
+// (NB, MAXT, MINB) of every instantiated kernel: MAXT is the shape's threads, MINB the waves per SIMD it is compiled for
 static bool shape_ok(Shape sh, int nw) {
 #define X(NB_, MT_, MB_) if (sh.nb == NB_ && sh.threads == MT_) return (long)NB_ * MT_ >= nw;
     SHAPES(X)
@@ -1715,23 +1702,41 @@ static Shape pick_shape(int nw) {
     return {nb < 2 ? 2 : nb, 512};
 }
 
-template <typename K>
-static int prep_lds(raftx_ctx *c, K kernel, size_t bytes) {
+static int prep_lds(raftx_ctx *c, const void *kernel, size_t bytes) {
     if (bytes > LDS_LIMIT)
         FAIL(c, "a design has %d submerged strips / nw=%d: %zu B of LDS needed, 160 KiB available", c->maxS, c->T.nw, bytes);
     if (bytes > 64 * 1024)
-        HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      (int)bytes));
+        HIPCHK(c, hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
     return 0;
 }
+#define NO_KERNEL(c, sh) FAIL(c, "no kernel for shape %d x %d", (sh).nb, (sh).threads)
 
-// expands BODY(NB, MAXT, MINB) for the shape sh
-#define DISPATCH_SHAPE(sh, BODY)                                                     \
-    do {                                                                             \
-        bool hit_ = false;                                                           \
-        SHAPES(DISPATCH_ONE_)                                                        \
-        if (!hit_) FAIL(c, "no kernel for shape %d x %d", (sh).nb, (sh).threads);    \
-    } while (0)
+// Device buffers the ctx keeps outside the pool and regrows on demand.  Drains what may still use the old block (the ctx
+// stream, or the whole device), frees it and allocates room for want_n elements (at least one); on failure the pointer
+// is null and the size zero.  WHEN a buffer grows is its caller's rule.
+enum Drain { DRAIN_STREAM, DRAIN_DEVICE };
+template <typename Tp>
+static int grow_device(raftx_ctx *c, Tp **ptr, size_t *have_n, size_t want_n, Drain drain = DRAIN_STREAM) {
+    HIPCHK(c, drain == DRAIN_DEVICE ? hipDeviceSynchronize() : hipStreamSynchronize(c->stream));
+    if (*ptr) (void)hipFree(*ptr);
+    *ptr = nullptr;
+    *have_n = 0;
+    void *p_ = nullptr;
+    HIPCHK(c, hipMalloc(&p_, (want_n ? want_n : 1) * sizeof(Tp)));
+    *ptr = reinterpret_cast<Tp *>(p_);
+    *have_n = want_n;
+    return 0;
+}
+// allocated and zeroed (in the order of the ctx stream) the first time only
+template <typename Tp>
+static int zeroed_once(raftx_ctx *c, Tp **ptr, size_t n) {
+    if (*ptr) return 0;
+    void *p_ = nullptr;
+    HIPCHK(c, hipMalloc(&p_, n * sizeof(Tp)));
+    *ptr = reinterpret_cast<Tp *>(p_);
+    HIPCHK(c, hipMemsetAsync(*ptr, 0, n * sizeof(Tp), c->stream));
+    return 0;
+}
 
 static int check_ready(raftx_ctx *c) {
     if (!c) return -1;
@@ -1774,6 +1779,14 @@ static int finish_timed(raftx_ctx *c) {
     return 0;
 }
 
+// the instantiated kernel of a shape (nullptr: none)
+typedef void (*excitation_fn)(DevTables, cplx *);
+static excitation_fn excitation_kernel(Shape sh) {
+#define X(NB_, MT_, MB_) if (sh.nb == NB_ && sh.threads == MT_) return k_excitation<NB_, MT_, MB_>;
+    SHAPES(X)
+#undef X
+    return nullptr;
+}
 extern "C" int raftx_excitation(raftx_ctx *c, raftx_c128 *F_iner) {
     if (check_ready(c)) return -1;
     if (!F_iner) FAIL(c, "excitation: F_iner is NULL");
@@ -1786,37 +1799,35 @@ extern "C" int raftx_excitation(raftx_ctx *c, raftx_c128 *F_iner) {
     if (n && !dF) FAIL(c, "excitation: device allocation failed");
     const Shape sh = pick_shape(T.nw);
     HIPCHK(c, hipEventRecord(c->ev0, c->stream));
-#define DISPATCH_ONE_(NB_, MT_, MB_)                                                                                  \
-    if (!hit_ && sh.nb == NB_ && sh.threads == MT_) {                                                                 \
-        hit_ = true;                                                                                                  \
-        hipLaunchKernelGGL((k_excitation<NB_, MT_, MB_>), dim3((unsigned)(npair * T.nHead)), dim3(sh.threads), 0,     \
-                           c->stream, T, dF);                                                                         \
+    if (npair) {
+        excitation_fn kernel = excitation_kernel(sh);
+        if (!kernel) NO_KERNEL(c, sh);
+        hipLaunchKernelGGL(kernel, dim3((unsigned)(npair * T.nHead)), dim3(sh.threads), 0, c->stream, T, dF);
     }
-    if (npair) DISPATCH_SHAPE(sh, _);
-#undef DISPATCH_ONE_
     if (finish_timed(c)) return -2;
     if (n) D2H(c, F_iner, dF, n * sizeof(cplx));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return 0;
 }
 
+typedef void (*linearize_fn)(DevTables, const cplx *, double *, cplx *);
+static linearize_fn linearize_kernel(Shape sh) {
+#define X(NB_, MT_, MB_) if (sh.nb == NB_ && sh.threads == MT_) return k_linearize<NB_, MT_, MB_>;
+    SHAPES(X)
+#undef X
+    return nullptr;
+}
 // one drag linearisation on device arrays (enqueued on the ctx stream between ev0 and the caller's ev1)
 static int linearize_enqueue(raftx_ctx *c, const cplx *dXi, double *dB, cplx *dF, bool timed = true) {
     const DevTables &T = c->T;
     const size_t npair = (size_t)T.nDesign * T.nCase;
     const Shape sh = pick_shape(T.nw);
-    const size_t lds = lds_bytes(c->maxS, 0, sh.threads / 64, stage_policy(sh.nb, shape_maxt(sh)));
-#define DISPATCH_ONE_(NB_, MT_, MB_)                                                                                  \
-    if (!hit_ && sh.nb == NB_ && sh.threads == MT_) {                                                                 \
-        hit_ = true;                                                                                                  \
-        if (prep_lds(c, k_linearize<NB_, MT_, MB_>, lds)) return -1;                                                  \
-        if (timed) HIPCHK(c, hipEventRecord(c->ev0, c->stream));                                                      \
-        if (npair)                                                                                                    \
-            hipLaunchKernelGGL((k_linearize<NB_, MT_, MB_>), dim3(grid_for_pairs(npair)), dim3(sh.threads), lds,      \
-                               c->stream, T, dXi, dB, dF);                                                            \
-    }
-    DISPATCH_SHAPE(sh, _);
-#undef DISPATCH_ONE_
+    const size_t lds = lds_bytes(c->maxS, 0, sh.threads / 64, stage_policy(sh.nb, sh.threads));
+    linearize_fn kernel = linearize_kernel(sh);
+    if (!kernel) NO_KERNEL(c, sh);
+    if (prep_lds(c, reinterpret_cast<const void *>(kernel), lds)) return -1;
+    if (timed) HIPCHK(c, hipEventRecord(c->ev0, c->stream));
+    if (npair) hipLaunchKernelGGL(kernel, dim3(grid_for_pairs(npair)), dim3(sh.threads), lds, c->stream, T, dXi, dB, dF);
     return 0;
 }
 extern "C" int raftx_linearize(raftx_ctx *c, const raftx_c128 *Xi, double *B_drag, raftx_c128 *F_drag) {
@@ -1936,7 +1947,6 @@ static int ensure_results(raftx_ctx *c, int want_mask, bool need_fe) {
     return 0;
 }
 
-// enqueues the fused fixed point on the ctx stream between ev0 and ev1; does not wait for it
 // A fused-kernel launch cut into SLABS of the pair list (a crossing that downloads its responses: slab k's download runs
 // while the slabs behind it solve).  The slabs go round-robin to the streams `alts`, none to the ctx stream: pairs are
 // independent, and a grid queued on another stream is handed out as soon as the grids before it are exhausted -- the
@@ -1985,13 +1995,7 @@ static int launch_persistent(raftx_ctx *c, kp_fn kernel, const DevTables &T, con
         HIPCHK(c, hipGetDeviceProperties(&pr, c->device));
         c->nCU = pr.multiProcessorCount > 0 ? pr.multiProcessorCount : 256;
     }
-    if (!c->kpCtr) {
-        void *p_ = nullptr;
-        const size_t bytes = (size_t)KP_RING * 9 * KP_CTR_STRIDE * sizeof(unsigned);
-        HIPCHK(c, hipMalloc(&p_, bytes));
-        c->kpCtr = reinterpret_cast<unsigned *>(p_);
-        HIPCHK(c, hipMemsetAsync(c->kpCtr, 0, bytes, c->stream));         // once: every launch leaves its set zeroed (kp_leave)
-    }
+    if (zeroed_once(c, &c->kpCtr, (size_t)KP_RING * 9 * KP_CTR_STRIDE)) return -2;   // once: every launch leaves its set zeroed (kp_leave)
     if (lds > 64 * 1024)
         HIPCHK(c, hipFuncSetAttribute(gen ? reinterpret_cast<const void *>(raftx_kpg_f0) : reinterpret_cast<const void *>(kernel),
                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -2014,14 +2018,245 @@ static int launch_persistent(raftx_ctx *c, kp_fn kernel, const DevTables &T, con
     return 0;
 }
 
-static int solve_enqueue(raftx_ctx *c, int nIter, double tol, double XiStart, const raftx_c128 *F_extra, int want_mask,
-                         SlabPlan *plan = nullptr) {
+// ---- the fused fixed point: kernel table, launch plan, scratch that grows, launch forms
+// The instantiations of k_solve_dynamics<NB, FLAGS, MAXT, MINB>: for every shape the full-featured <NB, KF_ALL, MAXT, 1>
+// (trades occupancy for registers) and the lean <NB, 0, MAXT, MINB>; the 200-bin shape has a lean kernel per feature set
+// of this list as well (smallest first: a call takes the first one that covers what it needs).
+#define RAFTX_LEAN128(X) X(0) X(KF_FDEP) X(KF_MCF) X(KF_MULTI) X(KF_FDEP | KF_EXTRA) X(KF_FDEP | KF_MCF) X(KF_FDEP | KF_MULTI) \
+    X(KF_MCF | KF_MULTI) X(KF_FDEP | KF_EXTRA | KF_MULTI) X(KF_FDEP | KF_MCF | KF_MULTI) X(KF_OUTF) X(KF_OUTF | KF_MULTI)
+struct SolveKernel {
+    void (*fn)(DevTables, SolveArgs);
+    int minb;                            // waves per SIMD it is compiled for
+    kp_fn kp;                            // its persistent twin raftx_kp_f<FLAGS> (nullptr: none)
+};
+// the kernel of (shape, lean flags or KF_ALL); false: not instantiated
+static bool solve_kernel(Shape sh, int flags, SolveKernel *out) {
+#define ENTRY_(NB_, FL_, MT_, MB_)                                                                                      \
+    {                                                                                                                   \
+        *out = {k_solve_dynamics<NB_, FL_, MT_, MB_>, MB_,                                                              \
+                (NB_ == 2 && MT_ == 128 && MB_ == RAFTX_KP_MINB) ? kp_kernel(FL_) : nullptr};                           \
+        return true;                                                                                                    \
+    }
+#define LEAN_(F) if (flags == (F)) ENTRY_(2, (F), 128, RAFTX_MINB128)
+#define X(NB_, MT_, MB_)                                                                                                \
+    if (sh.nb == NB_ && sh.threads == MT_) {                                                                            \
+        if (flags == KF_ALL) ENTRY_(NB_, KF_ALL, MT_, 1)                                                                \
+        if constexpr (NB_ == 2 && MT_ == 128) { RAFTX_LEAN128(LEAN_) }                                                  \
+        else if (flags == 0) ENTRY_(NB_, 0, MT_, MB_)                                                                   \
+        return false;                                                                                                   \
+    }
+    SHAPES(X)
+#undef X
+#undef LEAN_
+#undef ENTRY_
+    return false;
+}
+
+// what one call of solve_enqueue launches with (make_plan)
+struct LaunchPlan {
+    Shape sh;
+    int nw;
+    bool xlg;                            // XiLast in a global scratch slab (raftx_kernels.h XlStore)
+    bool rc_shape;                       // the shape whose spare LDS is a run-start cache (RC of k_solve_dynamics)
+    int lean;                            // flags of the lean specialisation that runs; -1: the full-featured kernel
+    SolveKernel k;                       // k.kp is null unless a launch of the whole batch goes out in the persistent form
+    int wg_per_cu;                       // pairs per CU the LDS is budgeted for
+    bool persist;
+    // dynamic LDS of a workgroup whose largest design has S strips, with rc_n slots of run-start cache
+    size_t lds(int S, int rc_n) const {
+        return lds_bytes(S, xlg ? 0 : nw, sh.threads / 64, stage_policy(sh.nb, sh.threads), park_policy(sh.nb, sh.threads), rc_n,
+                         rc_shape ? nw : 0);
+    }
+    // Workgroups a CU can hold by registers (the shape's waves per SIMD); LDS beyond what that residency needs goes to
+    // the run-start cache (raftx_kernels.h Kin): as many 16-byte-per-bin slots as fit without costing a resident pair.
+    int rc_slots(int S) const {
+        if (!rc_shape) return 0;
+        static const char *env = getenv("RAFTX_RC_SLOTS");                 // tuning: cap (0 = no cache)
+        const int cap = env ? atoi(env) : 24;
+        const size_t base = lds(S, 0);
+        const size_t budget = LDS_LIMIT / (size_t)wg_per_cu - (persist ? KP_STASH * sizeof(double) : 0);
+        if (budget <= base) return 0;
+        return (int)std::min<size_t>((size_t)cap, (budget - base) / (16 * (size_t)xl_row(nw)));
+    }
+};
+static int make_plan(raftx_ctx *c, SolveArgs *A, LaunchPlan *lp) {
+    const DevTables &T = c->T;
+    // the lean specialisation (no optional inputs / outputs) is the sweep path
+    int need = (T.MBw ? KF_FDEP : 0) | (A->Z ? KF_OUTZ : 0) | (A->F_wave ? KF_OUTF : 0) | (A->F_extra ? KF_EXTRA : 0) |
+               (T.cm ? KF_MCF : 0) | (T.nHead > 1 ? KF_MULTI : 0);
+    if (c->have_xl0 || c->want_xlout) need |= KF_XLIO;
+    const Shape sh = lp->sh = pick_shape(T.nw);
+    lp->nw = T.nw;
+    lp->xlg = xl_global(sh.nb, sh.threads);
+    lp->rc_shape = sh.threads == 128 && sh.nb == 2;
+    // Which specialisation runs.  The 200-bin shape has lean kernels (two waves per SIMD, no Z / F_wave / restart I/O)
+    // for the feature sets a sweep meets -- several headings, MacCamy-Fuchs columns, frequency-dependent M / B (turbine
+    // aerodynamics, potential-flow coefficients), a resident extra excitation (BEM, second-order) -- and takes the
+    // smallest one that covers what this call needs; everything else (the drop-in's optional outputs) is the
+    // full-featured kernel at one wave per SIMD.
+    int lean = -1;
+    if (lp->rc_shape) {
+#define X(F) if (lean < 0 && (need & ~(F)) == 0) lean = (F);
+        RAFTX_LEAN128(X)
+#undef X
+    } else if (need == 0) {
+        lean = 0;
+    }
+    static const char *force_all = getenv("RAFTX_FORCE_ALL");           // tuning / tests: always the full-featured kernel
+    if (force_all && atoi(force_all)) lean = -1;
+    lp->lean = lean;
+    if (!solve_kernel(sh, lean >= 0 ? lean : KF_ALL, &lp->k)) NO_KERNEL(c, sh);
+    c->last_flags = lean >= 0 ? lean : KF_ALL;
+    c->last_minb = lp->k.minb;
+    static const int wgcu_env = getenv("RAFTX_WG_PER_CU") ? atoi(getenv("RAFTX_WG_PER_CU")) : 0;     // tuning: pairs per CU the LDS is budgeted for
+    lp->wg_per_cu = wgcu_env > 0 ? wgcu_env : std::max(1, lp->k.minb * 4 / (sh.threads / 64));
+    // the persistent form (raftx_kernels.h k_solve_dynamics_p / raftx_kp_f*): lean 200-bin launches of one LDS class that
+    // are not cut into slabs; RAFTX_PERSIST=0 keeps the one-workgroup-per-pair launches (A/B, tuning)
+    static const bool persist_env = !(getenv("RAFTX_PERSIST") && !atoi(getenv("RAFTX_PERSIST")));
+    lp->persist = persist_env && lp->rc_shape && lean >= 0 && (lp->xlg || RAFTX_XL_LDS);
+    if (!lp->persist) lp->k.kp = nullptr;
+    A->rc_n = c->last_rc = lp->rc_slots(c->maxS);
+    return 0;
+}
+
+// XiLast scratch of the shapes of xl_global(): a slot per RUNNING workgroup (xl_slot_acquire), not per pair; the slot
+// bits are cleared once -- every workgroup returns its slot
+static int ensure_xl_scratch(raftx_ctx *c, const LaunchPlan &lp) {
+    if (!lp.xlg) return 0;
+#ifdef RAFTX_XL_PER_PAIR
+    const size_t xl_regions = std::max<size_t>(XL_SLOTS, c->r_npair);
+#else
+    const size_t xl_regions = XL_SLOTS + KP_MAX_GRID;      // the slot pool + one region per workgroup of a persistent grid
+#endif
+    const size_t want = xl_regions * 12 * (size_t)lp.nw;
+    // (the whole device: fused kernels of the other streams may hold slots of the old slab)
+    if ((!c->rXl || c->rXl_n < want) && grow_device(c, &c->rXl, &c->rXl_n, want, DRAIN_DEVICE)) return -2;
+    return zeroed_once(c, &c->rXlSlots, (size_t)XL_POOLS * XL_POOL_WORDS);      // ahead of this ctx's launches, in stream order
+}
+// the restart point and the exported linearisation point, [npair,6,nw] each: both or neither
+static int ensure_xlio(raftx_ctx *c, size_t nxl) {
+    if (c->rXlio_n == nxl && c->rXl0 && c->rXlOut) return 0;
+    size_t n0 = 0, n1 = 0;
+    c->rXlio_n = 0;
+    int rc = grow_device(c, &c->rXl0, &n0, nxl);
+    if (!rc) rc = grow_device(c, &c->rXlOut, &n1, nxl);
+    if (rc) {
+        if (c->rXl0) (void)hipFree(c->rXl0);
+        if (c->rXlOut) (void)hipFree(c->rXlOut);
+        c->rXl0 = c->rXlOut = nullptr;
+        return rc;
+    }
+    c->rXlio_n = nxl;
+    return 0;
+}
+
+// LDS classes: the workgroups of a launch all get the LDS of its largest design, and the number of pairs a CU holds
+// (4 at C3) falls with it -- one 140-strip candidate would cost a whole 10 k-design sweep a quarter of its
+// residency.  Designs are therefore grouped by how many of their pairs fit a CU, one launch per group (largest
+// residency first), through a pair list; a batch of one class (the usual case) is one launch without a list.
+struct LdsClasses {
+    struct Class {
+        size_t npairs;                   // consecutive in pairList, in the order of `cls`
+        int S;                           // strips of its largest design
+    };
+    std::vector<Class> cls;              // in launch order; empty: the batch is of one class
+    std::vector<int> pairs;              // host copy of pairList (what its upload reads)
+};
+static int lds_classes(raftx_ctx *c, const LaunchPlan &lp, LdsClasses *out) {
+    const DevTables &T = c->T;
+    if ((int)c->hS.size() != T.nDesign) return 0;
+    auto fit = [&](int S_) { return std::min(lp.wg_per_cu, (int)(LDS_LIMIT / lp.lds(S_, 0))); };   // pairs a CU holds
+    std::vector<int> k_of((size_t)T.nDesign);
+    bool mixed = false;
+    for (int d = 0; d < T.nDesign; d++) mixed |= (k_of[(size_t)d] = fit(c->hS[(size_t)d])) != k_of[0];
+    if (!mixed) return 0;
+    if (c->pairList_n < c->r_npair && grow_device(c, &c->pairList, &c->pairList_n, c->r_npair)) return -2;
+    out->pairs.reserve((size_t)T.nDesign * T.nCase);       // (no reallocation under the uploads)
+    for (int kk = fit(0); kk >= 0; kk--) {
+        LdsClasses::Class k = {0, 0};
+        const size_t at = out->pairs.size();
+        for (int d = 0; d < T.nDesign; d++) {
+            if (k_of[(size_t)d] != kk) continue;
+            for (int ic = 0; ic < T.nCase; ic++) out->pairs.push_back(d * T.nCase + ic);
+            k.S = std::max(k.S, c->hS[(size_t)d]);
+        }
+        if (!(k.npairs = out->pairs.size() - at)) continue;
+        H2D(c, c->pairList + at, out->pairs.data() + at, k.npairs * sizeof(int));
+        out->cls.push_back(k);
+    }
+    return 0;
+}
+// what a launch in slabs needs: the identity pair list and the fork / join events
+static int ensure_slab_list(raftx_ctx *c) {
+    if (c->identList_n < c->r_npair) {
+        if (grow_device(c, &c->identList, &c->identList_n, c->r_npair)) return -2;
+        hipLaunchKernelGGL(k_iota, dim3((unsigned)((c->r_npair + 255) / 256)), dim3(256), 0, c->stream, (int)c->r_npair, c->identList);
+    }
+    if (!c->evFork) HIPCHK(c, hipEventCreateWithFlags(&c->evFork, hipEventDisableTiming));
+    if (!c->evJoin) HIPCHK(c, hipEventCreateWithFlags(&c->evJoin, hipEventDisableTiming));
+    return 0;
+}
+// A generation deferred to this launch (build_phase2): the generating form of the plain persistent kernel builds every
+// design's tables in the workgroup that solves it -- if this launch is one (`whole`: one grid, and every design claimed
+// exactly once); otherwise the generation kernels go first, here.  True: the launch has to generate.
+static bool resolve_generation(raftx_ctx *c, const LaunchPlan &lp, bool whole) {
+    BuildJob &J = c->job;
+    const DevTables &T = c->T;
+    if (!J.gen_deferred) return false;
+    J.gen_deferred = false;
+    const bool fused = whole && lp.k.kp && lp.lean == 0 && T.nCase == 1 && c->r_npair == (size_t)T.nDesign && c->r_npair > 0 &&
+                       J.nDesign == T.nDesign && J.gen_lds + KP_STASH * sizeof(double) <= LDS_LIMIT / (size_t)lp.wg_per_cu;
+    if (!fused) {
+        J.A.addup_in_design = 0;
+        launch_design(c, c->stream);
+        hipLaunchKernelGGL(k_geom_addup, dim3((unsigned)(((size_t)J.nDesign * 36 + 255) / 256)), dim3(256), 0, c->stream, J.A);
+    }
+    return fused;
+}
+
+// the three forms of the launch: every pair in one grid on the ctx stream (persistent where the kernel has a twin) ...
+static int launch_whole(raftx_ctx *c, const LaunchPlan &lp, const SolveArgs &A, size_t lds, bool gen_fused) {
+    if (!c->r_npair) return 0;
+    if (lp.k.kp)
+        return launch_persistent(c, lp.k.kp, c->T, A, c->r_npair, lp.sh.threads,
+                                 std::max(lds, gen_fused ? c->job.gen_lds : (size_t)0) + KP_STASH * sizeof(double), lp.wg_per_cu,
+                                 gen_fused ? &c->job.A : nullptr);
+    hipLaunchKernelGGL(lp.k.fn, dim3(grid_for_pairs(c->r_npair)), dim3(lp.sh.threads), lds, c->stream, c->T, A);
+    return 0;
+}
+// ... the slabs of `plan` on its side streams, each followed by plan->after (*rc_after: what that returned) ...
+static int launch_slabs(raftx_ctx *c, const LaunchPlan &lp, SolveArgs A, size_t lds, SlabPlan *plan, int *rc_after) {
+    HIPCHK(c, hipEventRecord(c->evFork, c->stream));       // the tables and the iota list are on the ctx stream
+    for (size_t k = 0; k < plan->alts.size() && k + 1 < plan->bnd.size(); k++)
+        HIPCHK(c, hipStreamWaitEvent(plan->alts[(plan->next + k) % plan->alts.size()], c->evFork, 0));
+    for (size_t k = 0; k + 1 < plan->bnd.size() && !*rc_after; k++) {
+        hipStream_t s = plan->alts[plan->next++ % plan->alts.size()];
+        A.pairs = c->identList + plan->bnd[k];
+        A.npairs = (int)(plan->bnd[k + 1] - plan->bnd[k]);
+        hipLaunchKernelGGL(lp.k.fn, dim3(grid_for_pairs((size_t)A.npairs)), dim3(lp.sh.threads), lds, s, c->T, A);
+        if (plan->after) *rc_after = plan->after(plan->bnd[k], plan->bnd[k + 1], s);
+    }
+    return 0;
+}
+// ... or one grid per LDS class on the ctx stream, each with the LDS and the cache slots of its own largest design
+static void launch_classes(raftx_ctx *c, const LaunchPlan &lp, SolveArgs A, const LdsClasses &classes) {
+    size_t at = 0;
+    for (const LdsClasses::Class &k : classes.cls) {
+        A.pairs = c->pairList + at;
+        A.npairs = (int)k.npairs;
+        at += k.npairs;
+        A.rc_n = lp.rc_slots(k.S);
+        hipLaunchKernelGGL(lp.k.fn, dim3(grid_for_pairs(k.npairs)), dim3(lp.sh.threads), lp.lds(k.S, A.rc_n), c->stream, c->T, A);
+    }
+}
+
+// the arguments of the fused kernel that do not depend on the launch plan; sizes the result buffers, uploads F_extra
+static int fill_solve_args(raftx_ctx *c, int nIter, double tol, double XiStart, const raftx_c128 *F_extra, int want_mask, SolveArgs *out) {
     if (check_ready(c)) return -1;
     if (nIter < 0) FAIL(c, "solve_dynamics: nIter < 0");
     HIPCHK(c, hipSetDevice(c->device));
-    const DevTables &T = c->T;
     if (ensure_results(c, want_mask, F_extra != nullptr)) return -1;
-    SolveArgs A;
+    SolveArgs &A = *out;
     A.nIter = nIter + 1;
     A.tol = tol;
     A.XiStart = XiStart;
@@ -2033,247 +2268,54 @@ static int solve_enqueue(raftx_ctx *c, int nIter, double tol, double XiStart, co
     A.F_wave = (want_mask & RAFTX_WANT_FWAVE) ? c->rFw : nullptr;
     A.Z = (want_mask & RAFTX_WANT_Z) ? c->rZ : nullptr;
     c->r_last_mask = want_mask;          // buffers of a wider earlier request stay allocated (ensure_results) but are NOT rewritten
+    A.pairs = nullptr;
+    A.npairs = 0;
+    A.Xl0 = nullptr;
+    A.XlOut = nullptr;
     A.dbg = nullptr;
 #ifdef RAFTX_PHASE_TIMING
-    if (!c->dbg) {
-        void *p_ = nullptr;
-        HIPCHK(c, hipMalloc(&p_, (10 + 2 * PT_CLOCK_BUCKETS) * sizeof(unsigned long long)));
-        c->dbg = reinterpret_cast<unsigned long long *>(p_);
-    }
-    HIPCHK(c, hipMemsetAsync(c->dbg, 0, (10 + 2 * PT_CLOCK_BUCKETS) * sizeof(unsigned long long), c->stream));
+    const size_t ndbg = 10 + 2 * PT_CLOCK_BUCKETS;
+    if (zeroed_once(c, &c->dbg, ndbg)) return -2;
+    HIPCHK(c, hipMemsetAsync(c->dbg, 0, ndbg * sizeof(unsigned long long), c->stream));
     HIPCHK(c, hipMemsetAsync(c->dbg + 8, 0xFF, sizeof(unsigned long long), c->stream));      // earliest start: a minimum
     A.dbg = c->dbg;
 #endif
     if (F_extra && c->r_nx) H2D(c, c->rFe, F_extra, c->r_nx * sizeof(cplx));
-    // the lean specialisation (no optional inputs / outputs) is the sweep path
-    int need = (T.MBw ? KF_FDEP : 0) | (A.Z ? KF_OUTZ : 0) | (A.F_wave ? KF_OUTF : 0) | (A.F_extra ? KF_EXTRA : 0) |
-                     (T.cm ? KF_MCF : 0) | (T.nHead > 1 ? KF_MULTI : 0);
-    const Shape sh = pick_shape(T.nw);
-    const bool xlg = xl_global(sh.nb, shape_maxt(sh));       // XiLast in a global scratch slab (raftx_kernels.h XlStore)
-    // Workgroups a CU can hold by registers (the shape's waves per SIMD); LDS beyond what that residency needs goes to
-    // the run-start cache (raftx_kernels.h Kin): as many 16-byte-per-bin slots as fit without costing a resident pair.
-    const bool rc_shape = shape_maxt(sh) == 128 && sh.nb == 2;          // RC of k_solve_dynamics
-    // Which specialisation runs.  The 200-bin shape has lean kernels (two waves per SIMD, no Z / F_wave / restart I/O)
-    // for the feature sets a sweep meets -- several headings, MacCamy-Fuchs columns, frequency-dependent M / B (turbine
-    // aerodynamics, potential-flow coefficients), a resident extra excitation (BEM, second-order) -- and takes the
-    // smallest one that covers what this call needs; everything else (the drop-in's optional outputs) is the
-    // full-featured kernel at one wave per SIMD.
-#define RAFTX_LEAN128(X) X(0) X(KF_FDEP) X(KF_MCF) X(KF_MULTI) X(KF_FDEP | KF_EXTRA) X(KF_FDEP | KF_MCF) X(KF_FDEP | KF_MULTI) \
-    X(KF_MCF | KF_MULTI) X(KF_FDEP | KF_EXTRA | KF_MULTI) X(KF_FDEP | KF_MCF | KF_MULTI) X(KF_OUTF) X(KF_OUTF | KF_MULTI)
-    if (c->have_xl0 || c->want_xlout) need |= KF_XLIO;
-    int lean = -1;
-    if (rc_shape) {
-#define X(F) if (lean < 0 && (need & ~(F)) == 0) lean = (F);
-        RAFTX_LEAN128(X)
-#undef X
-    } else if (need == 0) {
-        lean = 0;
-    }
-    static const char *force_all = getenv("RAFTX_FORCE_ALL");           // tuning / tests: always the full-featured kernel
-    if (force_all && atoi(force_all)) lean = -1;
-    const int minb_used = lean >= 0 ? shape_minb(sh) : 1;
-    c->last_flags = lean >= 0 ? lean : KF_ALL;
-    c->last_minb = minb_used;
-    static const int wgcu_env = getenv("RAFTX_WG_PER_CU") ? atoi(getenv("RAFTX_WG_PER_CU")) : 0;     // tuning: pairs per CU the LDS is budgeted for
-    const int wg_per_cu = wgcu_env > 0 ? wgcu_env : std::max(1, minb_used * 4 / (sh.threads / 64));
-    // the persistent form (raftx_kernels.h k_solve_dynamics_p / raftx_kp_f*): lean 200-bin launches of one LDS class that
-    // are not cut into slabs; RAFTX_PERSIST=0 keeps the one-workgroup-per-pair launches (A/B, tuning)
-    static const bool persist_env = !(getenv("RAFTX_PERSIST") && !atoi(getenv("RAFTX_PERSIST")));
-    const bool persist = persist_env && rc_shape && lean >= 0 && (xlg || RAFTX_XL_LDS);
-    auto rc_slots = [&](int S_) {
-        if (!(shape_maxt(sh) == 128 && sh.nb == 2)) return 0;                // (= rc_shape below)
-        static const char *env = getenv("RAFTX_RC_SLOTS");                 // tuning: cap (0 = no cache)
-        const int cap = env ? atoi(env) : 24;
-        const size_t base = lds_bytes(S_, xlg ? 0 : T.nw, sh.threads / 64, stage_policy(sh.nb, shape_maxt(sh)),
-                                      park_policy(sh.nb, shape_maxt(sh)), 0, T.nw);
-        const size_t budget = LDS_LIMIT / (size_t)wg_per_cu - (persist ? KP_STASH * sizeof(double) : 0);
-        if (budget <= base) return 0;
-        return (int)std::min<size_t>((size_t)cap, (budget - base) / (16 * (size_t)xl_row(T.nw)));
-    };
-    A.rc_n = rc_slots(c->maxS);
-    c->last_rc = A.rc_n;
-    const size_t lds = lds_bytes(c->maxS, xlg ? 0 : T.nw, sh.threads / 64, stage_policy(sh.nb, shape_maxt(sh)),
-                                 park_policy(sh.nb, shape_maxt(sh)), A.rc_n, rc_shape ? T.nw : 0);
-#ifdef RAFTX_XL_PER_PAIR
-    const size_t xl_regions = std::max<size_t>(XL_SLOTS, c->r_npair);
-#else
-    const size_t xl_regions = XL_SLOTS + KP_MAX_GRID;      // the slot pool + one region per workgroup of a persistent grid
-#endif
-    if (xlg && (!c->rXl || c->rXl_n < xl_regions * 12 * (size_t)T.nw)) {
-        // XiLast scratch: a slot per RUNNING workgroup (xl_slot_acquire), not per pair; the slot bits are cleared once --
-        // every workgroup returns its slot
-        HIPCHK(c, hipDeviceSynchronize());                 // fused kernels of the other streams may hold slots of the old slab
-        if (c->rXl) { (void)hipFree(c->rXl); }
-        c->rXl = nullptr;
-        c->rXl_n = 0;
-        void *p_ = nullptr;
-        HIPCHK(c, hipMalloc(&p_, xl_regions * 12 * (size_t)T.nw * sizeof(double)));
-        c->rXl = reinterpret_cast<double *>(p_);
-        c->rXl_n = xl_regions * 12 * (size_t)T.nw;
-    }
-    if (xlg && !c->rXlSlots) {                             // (on its own: a failed allocation above leaves no half-made pair)
-        void *p_ = nullptr;
-        HIPCHK(c, hipMalloc(&p_, XL_POOLS * XL_POOL_WORDS * sizeof(unsigned long long)));
-        c->rXlSlots = reinterpret_cast<unsigned long long *>(p_);
-        HIPCHK(c, hipMemsetAsync(c->rXlSlots, 0, XL_POOLS * XL_POOL_WORDS * sizeof(unsigned long long), c->stream));   // ahead of this ctx's launches, in stream order
-    }
+    return 0;
+}
+
+// enqueues the fused fixed point on the ctx stream between ev0 and ev1; does not wait for it
+static int solve_enqueue(raftx_ctx *c, int nIter, double tol, double XiStart, const raftx_c128 *F_extra, int want_mask,
+                         SlabPlan *plan = nullptr) {
+    SolveArgs A;
+    if (int rc = fill_solve_args(c, nIter, tol, XiStart, F_extra, want_mask, &A)) return rc;
+    LaunchPlan lp;
+    if (int rc = make_plan(c, &A, &lp)) return rc;
+    const size_t lds = lp.lds(c->maxS, A.rc_n);
+    if (int rc = ensure_xl_scratch(c, lp)) return rc;
     A.Xl = c->rXl;
     A.slots = c->rXlSlots;
-    // restart / export of the linearisation point (the re-entry of raft_model.py:1108-1131)
-    const size_t nxl = c->r_npair * 6 * (size_t)T.nw;
-    A.Xl0 = nullptr;
-    A.XlOut = nullptr;
-    if (c->have_xl0 || c->want_xlout) {
-        if (c->rXlio_n != nxl || !c->rXlOut) {
-            if (c->have_xl0) FAIL(c, "solve_dynamics: the linearisation point was set for a different batch shape");
-            HIPCHK(c, hipStreamSynchronize(c->stream));
-            if (c->rXl0) (void)hipFree(c->rXl0);
-            if (c->rXlOut) (void)hipFree(c->rXlOut);
-            c->rXl0 = c->rXlOut = nullptr;
-            void *p0 = nullptr, *p1 = nullptr;
-            HIPCHK(c, hipMalloc(&p0, (nxl ? nxl : 1) * sizeof(cplx)));
-            HIPCHK(c, hipMalloc(&p1, (nxl ? nxl : 1) * sizeof(cplx)));
-            c->rXl0 = reinterpret_cast<cplx *>(p0);
-            c->rXlOut = reinterpret_cast<cplx *>(p1);
-            c->rXlio_n = nxl;
-        }
+    if (c->have_xl0 || c->want_xlout) {       // restart / export of the linearisation point (the re-entry of raft_model.py:1108-1131)
+        const size_t nxl = c->r_npair * 6 * (size_t)c->T.nw;
+        if (c->have_xl0 && c->rXlio_n != nxl) FAIL(c, "solve_dynamics: the linearisation point was set for a different batch shape");
+        if (int rc = ensure_xlio(c, nxl)) return rc;
         if (c->have_xl0) A.Xl0 = c->rXl0;
         A.XlOut = c->rXlOut;
-        need |= KF_XLIO;
         c->have_xl0 = false;                  // one-shot
     }
-    // LDS classes: the workgroups of a launch all get the LDS of its largest design, and the number of pairs a CU holds
-    // (4 at C3) falls with it -- one 140-strip candidate would cost a whole 10 k-design sweep a quarter of its
-    // residency.  Designs are therefore grouped by how many of their pairs fit a CU, one launch per group (largest
-    // residency first), through a pair list; a batch of one class (the usual case) is one launch without a list.
-    std::vector<std::vector<int>> cls;
-    std::vector<int> clsS;
-    {
-        auto lds_of = [&](int S_) {
-            return lds_bytes(S_, xlg ? 0 : T.nw, sh.threads / 64, stage_policy(sh.nb, shape_maxt(sh)), park_policy(sh.nb, shape_maxt(sh)),
-                             0, rc_shape ? T.nw : 0);
-        };
-        auto fit = [&](int S_) { return std::min(wg_per_cu, (int)(LDS_LIMIT / lds_of(S_))); };   // pairs a CU holds
-        const int kmax = fit(0);
-        bool mixed = false;
-        if ((int)c->hS.size() == T.nDesign && T.nDesign > 0) {
-            const int k0 = fit(c->hS[0]);
-            for (int d = 1; d < T.nDesign && !mixed; d++) mixed = fit(c->hS[(size_t)d]) != k0;
-        }
-        if (mixed) {
-            cls.assign((size_t)kmax + 1, {});
-            clsS.assign((size_t)kmax + 1, 0);
-            for (int d = 0; d < T.nDesign; d++) {
-                const int S_ = c->hS[(size_t)d], kk = fit(S_);
-                for (int ic = 0; ic < T.nCase; ic++) cls[(size_t)kk].push_back(d * T.nCase + ic);
-                if (S_ > clsS[(size_t)kk]) clsS[(size_t)kk] = S_;
-            }
-            if (c->pairList_n < c->r_npair) {
-                HIPCHK(c, hipStreamSynchronize(c->stream));
-                if (c->pairList) (void)hipFree(c->pairList);
-                c->pairList = nullptr;
-                void *p_ = nullptr;
-                HIPCHK(c, hipMalloc(&p_, c->r_npair * sizeof(int)));
-                c->pairList = reinterpret_cast<int *>(p_);
-                c->pairList_n = c->r_npair;
-            }
-            size_t at = 0;
-            for (int kk = kmax; kk >= 0; kk--)
-                if (!cls[(size_t)kk].empty()) {
-                    H2D(c, c->pairList + at, cls[(size_t)kk].data(), cls[(size_t)kk].size() * sizeof(int));
-                    at += cls[(size_t)kk].size();
-                }
-        }
-    }
-    const bool slabbed = plan && cls.empty() && !plan->alts.empty() && plan->bnd.size() >= 2 && plan->bnd.back() == c->r_npair;
-    if (slabbed) {
-        if (c->identList_n < c->r_npair) {
-            HIPCHK(c, hipStreamSynchronize(c->stream));
-            if (c->identList) (void)hipFree(c->identList);
-            c->identList = nullptr;
-            void *p_ = nullptr;
-            HIPCHK(c, hipMalloc(&p_, c->r_npair * sizeof(int)));
-            c->identList = reinterpret_cast<int *>(p_);
-            c->identList_n = c->r_npair;
-            hipLaunchKernelGGL(k_iota, dim3((unsigned)((c->r_npair + 255) / 256)), dim3(256), 0, c->stream, (int)c->r_npair, c->identList);
-        }
-        if (!c->evFork) HIPCHK(c, hipEventCreateWithFlags(&c->evFork, hipEventDisableTiming));
-        if (!c->evJoin) HIPCHK(c, hipEventCreateWithFlags(&c->evJoin, hipEventDisableTiming));
-    }
-    // A generation deferred to this launch (build_phase2): the generating form of the plain persistent kernel builds every
-    // design's tables in the workgroup that solves it -- if this launch is one (every design claimed exactly once);
-    // otherwise the generation kernels go first, here.
-    BuildJob &J = c->job;
-    bool gen_fused = false;
-    if (J.gen_deferred) {
-        J.gen_deferred = false;
-        gen_fused = persist && lean == 0 && T.nCase == 1 && cls.empty() && !slabbed && c->r_npair == (size_t)T.nDesign && c->r_npair > 0 &&
-                    J.nDesign == T.nDesign && J.gen_lds + KP_STASH * sizeof(double) <= LDS_LIMIT / (size_t)wg_per_cu;
-        if (!gen_fused) {
-            J.A.addup_in_design = 0;
-            launch_design(c, c->stream);
-            hipLaunchKernelGGL(k_geom_addup, dim3((unsigned)(((size_t)J.nDesign * 36 + 255) / 256)), dim3(256), 0, c->stream, J.A);
-        }
-    }
-    c->last_gen_fused = gen_fused;
+    LdsClasses classes;
+    if (int rc = lds_classes(c, lp, &classes)) return rc;
+    const bool slabbed = plan && classes.cls.empty() && !plan->alts.empty() && plan->bnd.size() >= 2 && plan->bnd.back() == c->r_npair;
+    if (int rc = slabbed ? ensure_slab_list(c) : 0) return rc;
+    const bool whole = classes.cls.empty() && !slabbed;
+    const bool gen_fused = c->last_gen_fused = resolve_generation(c, lp, whole);
+    if (prep_lds(c, reinterpret_cast<const void *>(lp.k.fn), lds)) return -1;
+    HIPCHK(c, hipEventRecord(c->ev0, c->stream));
     int rc_after = 0;
-#define LAUNCH_SOLVE(NB_, MT_, MB_, FL)                                                                              \
-    do {                                                                                                             \
-        if (prep_lds(c, k_solve_dynamics<NB_, FL, MT_, MB_>, lds)) return -1;                                        \
-        HIPCHK(c, hipEventRecord(c->ev0, c->stream));                                                                \
-        A.pairs = nullptr;                                                                                           \
-        A.npairs = 0;                                                                                                \
-        if (c->r_npair && cls.empty() && !slabbed) {                                                                 \
-            kp_fn kp_ = (persist && NB_ == 2 && MT_ == 128 && MB_ == RAFTX_KP_MINB) ? kp_kernel(FL) : nullptr;       \
-            if (kp_) {                                                                                               \
-                if (launch_persistent(c, kp_, T, A, c->r_npair, sh.threads,                                          \
-                                      std::max(lds, gen_fused ? J.gen_lds : (size_t)0) + KP_STASH * sizeof(double), wg_per_cu, \
-                                      (gen_fused && FL == 0) ? &J.A : nullptr))                                      \
-                    return -1;                                                                                       \
-            } else {                                                                                                 \
-                hipLaunchKernelGGL((k_solve_dynamics<NB_, FL, MT_, MB_>), dim3(grid_for_pairs(c->r_npair)),          \
-                                   dim3(sh.threads), lds, c->stream, T, A);                                          \
-            }                                                                                                        \
-        }                                                                                                            \
-        if (slabbed) {                                            /* the tables and the iota list are on the ctx stream */ \
-            HIPCHK(c, hipEventRecord(c->evFork, c->stream));                                                         \
-            for (size_t k_ = 0; k_ < plan->alts.size() && k_ + 1 < plan->bnd.size(); k_++)                           \
-                HIPCHK(c, hipStreamWaitEvent(plan->alts[(plan->next + k_) % plan->alts.size()], c->evFork, 0));      \
-            for (size_t k_ = 0; k_ + 1 < plan->bnd.size() && !rc_after; k_++) {                                      \
-                hipStream_t s_ = plan->alts[plan->next++ % plan->alts.size()];                                       \
-                A.pairs = c->identList + plan->bnd[k_];                                                              \
-                A.npairs = (int)(plan->bnd[k_ + 1] - plan->bnd[k_]);                                                 \
-                hipLaunchKernelGGL((k_solve_dynamics<NB_, FL, MT_, MB_>), dim3(grid_for_pairs((size_t)A.npairs)),    \
-                                   dim3(sh.threads), lds, s_, T, A);                                                 \
-                if (plan->after) rc_after = plan->after(plan->bnd[k_], plan->bnd[k_ + 1], s_);                       \
-            }                                                                                                        \
-        }                                                                                                            \
-        size_t at_ = 0;                                                                                              \
-        for (int kk = (int)cls.size() - 1; kk >= 0; kk--) {                                                          \
-            const size_t n_ = cls[(size_t)kk].size();                                                                \
-            if (!n_) continue;                                                                                       \
-            A.pairs = c->pairList + at_;                                                                             \
-            A.npairs = (int)n_;                                                                                      \
-            at_ += n_;                                                                                               \
-            A.rc_n = rc_slots(clsS[(size_t)kk]);                                                                     \
-            const size_t l_ = lds_bytes(clsS[(size_t)kk], xlg ? 0 : T.nw, sh.threads / 64, stage_policy(sh.nb, shape_maxt(sh)), \
-                                        park_policy(sh.nb, shape_maxt(sh)), A.rc_n, rc_shape ? T.nw : 0);            \
-            hipLaunchKernelGGL((k_solve_dynamics<NB_, FL, MT_, MB_>), dim3(grid_for_pairs(n_)), dim3(sh.threads),    \
-                               l_, c->stream, T, A);                                                                 \
-        }                                                                                                            \
-        if (plan && plan->after && !slabbed) rc_after = plan->after(0, c->r_npair, c->stream);                       \
-    } while (0)
-#define TRY_LEAN_(F) if (lean == (F)) LAUNCH_SOLVE(2, 128, RAFTX_MINB128, (F));
-#define DISPATCH_ONE_(NB_, MT_, MB_)                                                                                 \
-    if (!hit_ && sh.nb == NB_ && sh.threads == MT_) {                                                                \
-        hit_ = true;                                                                                                 \
-        if (lean < 0) LAUNCH_SOLVE(NB_, MT_, 1, KF_ALL);   /* full-featured variant: trade occupancy for registers */ \
-        else if constexpr (NB_ == 2 && MT_ == 128) { RAFTX_LEAN128(TRY_LEAN_) }                                      \
-        else LAUNCH_SOLVE(NB_, MT_, MB_, 0);                                                                         \
-    }
-    DISPATCH_SHAPE(sh, _);
-#undef DISPATCH_ONE_
-#undef LAUNCH_SOLVE
+    if (whole && launch_whole(c, lp, A, lds, gen_fused)) return -1;
+    if (slabbed && launch_slabs(c, lp, A, lds, plan, &rc_after)) return -2;
+    if (!classes.cls.empty()) launch_classes(c, lp, A, classes);
+    if (plan && plan->after && !slabbed) rc_after = plan->after(0, c->r_npair, c->stream);
     HIPCHK(c, hipEventRecord(c->ev1, c->stream));
     HIPCHK(c, hipGetLastError());
     if (rc_after) FAIL(c, "solve_dynamics: what follows a slab of the launch could not be enqueued");
@@ -2303,18 +2345,7 @@ extern "C" int raftx_set_linearisation_point(raftx_ctx *c, const raftx_c128 *XiL
     if (XiLast0) {
         const DevTables &T = c->T;
         const size_t nxl = (size_t)T.nDesign * T.nCase * 6 * T.nw;
-        if (c->rXlio_n != nxl || !c->rXl0) {
-            HIPCHK(c, hipStreamSynchronize(c->stream));
-            if (c->rXl0) (void)hipFree(c->rXl0);
-            if (c->rXlOut) (void)hipFree(c->rXlOut);
-            c->rXl0 = c->rXlOut = nullptr;
-            void *p0 = nullptr, *p1 = nullptr;
-            HIPCHK(c, hipMalloc(&p0, (nxl ? nxl : 1) * sizeof(cplx)));
-            HIPCHK(c, hipMalloc(&p1, (nxl ? nxl : 1) * sizeof(cplx)));
-            c->rXl0 = reinterpret_cast<cplx *>(p0);
-            c->rXlOut = reinterpret_cast<cplx *>(p1);
-            c->rXlio_n = nxl;
-        }
+        if (int rc = ensure_xlio(c, nxl)) return rc;
         if (nxl) H2D(c, c->rXl0, XiLast0, nxl * sizeof(cplx));
         HIPCHK(c, hipStreamSynchronize(c->stream));
         c->have_xl0 = true;
@@ -2373,15 +2404,7 @@ extern "C" int raftx_bem_excitation(raftx_ctx *c, int nHeadBEM, const double *he
     const size_t npair = (size_t)T.nDesign * T.nCase, nx = npair * T.nHead * 6 * T.nw;
     const size_t nX = (size_t)T.nDesign * nHeadBEM * 6 * T.nw;
     c->bem_ready = false;
-    if (c->bemF_n < nx || !c->bemF) {
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        if (c->bemF) (void)hipFree(c->bemF);
-        c->bemF = nullptr;
-        void *p_ = nullptr;
-        HIPCHK(c, hipMalloc(&p_, (nx ? nx : 1) * sizeof(cplx)));
-        c->bemF = reinterpret_cast<cplx *>(p_);
-        c->bemF_n = nx;
-    }
+    if ((c->bemF_n < nx || !c->bemF) && grow_device(c, &c->bemF, &c->bemF_n, nx)) return -2;
     Scratch sc(c);
     double *dH = sc.alloc<double>(nHeadBEM), *dA = heading_adjust ? sc.alloc<double>(T.nDesign) : nullptr,
            *dXY = xy_ref ? sc.alloc<double>((size_t)T.nDesign * 2) : nullptr;
@@ -2696,16 +2719,7 @@ extern "C" int raftx_flex_start(raftx_ctx *c, int nUnit, int n, const raftx_c128
     if (nUnit < 1 || n < 6) FAIL(c, "flex_start: bad arguments (nUnit=%d, n=%d)", nUnit, n);
     HIPCHK(c, hipSetDevice(c->device));
     const size_t need = (size_t)nUnit * T.nCase * n * T.nw;
-    if (need > c->flexXl0_cap) {
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        if (c->flexXl0) (void)hipFree(c->flexXl0);
-        c->flexXl0 = nullptr;
-        c->flexXl0_cap = 0;
-        void *p_ = nullptr;
-        HIPCHK(c, hipMalloc(&p_, need * sizeof(cplx)));
-        c->flexXl0 = reinterpret_cast<cplx *>(p_);
-        c->flexXl0_cap = need;
-    }
+    if (need > c->flexXl0_cap && grow_device(c, &c->flexXl0, &c->flexXl0_cap, need)) return -2;
     H2D(c, c->flexXl0, XiLast0, need * sizeof(cplx));
     HIPCHK(c, hipStreamSynchronize(c->stream));           // the caller's array is free again
     c->flexXl0_n = need;
@@ -2918,15 +2932,7 @@ extern "C" int raftx_qtf_kay(raftx_ctx *c, int nSet, int nw2, const double *w2, 
     const size_t nItem = (size_t)itemOff[nSet], nq = (size_t)nSet * nw2 * nw2 * 6;
     if (nItem && !items) FAIL(c, "qtf_kay: missing items");
     c->kay_ready = false;
-    if (c->rKay_n < nq || !c->rKay) {
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        if (c->rKay) (void)hipFree(c->rKay);
-        c->rKay = nullptr;
-        void *p_ = nullptr;
-        HIPCHK(c, hipMalloc(&p_, (nq ? nq : 1) * sizeof(cplx)));
-        c->rKay = reinterpret_cast<cplx *>(p_);
-        c->rKay_n = nq;
-    }
+    if ((c->rKay_n < nq || !c->rKay) && grow_device(c, &c->rKay, &c->rKay_n, nq)) return -2;
     Scratch sc(c);
     double *dw = sc.alloc<double>(nw2), *dk = sc.alloc<double>(nw2), *dI = sc.alloc<double>(nItem * QK_N),
            *dB = sc.alloc<double>(nSet);
@@ -2997,15 +3003,8 @@ static int qtf_slender_impl(raftx_ctx *c, int nSet, int nw2, const double *w2, c
          *dTS = sc.alloc<cplx>((size_t)nSet * QTS_N * nw2);
     double *dD = sc.alloc<double>(nStrip * QD_N);
     cplx *dTA = sc.alloc<cplx>(nStrip * QT_N * nw2);
-    if (c->rQtf_n < nq || !c->rQtf) {                    // the result stays resident (raftx_qtf_force can reuse it)
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        if (c->rQtf) (void)hipFree(c->rQtf);
-        c->rQtf = nullptr;
-        void *p_ = nullptr;
-        HIPCHK(c, hipMalloc(&p_, (nq ? nq : 1) * sizeof(cplx)));
-        c->rQtf = reinterpret_cast<cplx *>(p_);
-        c->rQtf_n = nq;
-    }
+    // the result stays resident (raftx_qtf_force can reuse it)
+    if ((c->rQtf_n < nq || !c->rQtf) && grow_device(c, &c->rQtf, &c->rQtf_n, nq)) return -2;
     c->rQtf_sets = nSet;
     c->rQtf_nw2 = nw2;
     cplx *dQ = c->rQtf;

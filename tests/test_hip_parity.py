@@ -775,7 +775,7 @@ def test_bad_run_hints_are_demoted_not_trusted(hip_ctx, oracle_ctx):
 
 def test_ragged_batch_is_launched_per_lds_class(hip_ctx, oracle_ctx):
     """Designs whose strip counts put different numbers of pairs on a CU (5 ... 210 strips at nw = 200) in one batch:
-    the fused kernel is launched once per LDS class through a pair list (raftx_hip.hip: solve_enqueue); every design,
+    the fused kernel is launched once per LDS class through a pair list (raftx_hip.hip: lds_classes, launch_classes); every design,
     wherever its class puts it, gets the response the oracle computes for it."""
     rng = np.random.default_rng(77)
     S_list, nw, nC = [20, 150, 53, 53, 97, 5, 210, 53], 200, 2
