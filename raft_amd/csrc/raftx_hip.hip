@@ -737,9 +737,10 @@ struct DevPool {
 struct BuildJob {
     GeomArgs A;
     std::vector<void *> tmp;            // descriptor uploads and per-member scratch: back to the pool when the job retires
-    int nDesign = 0, nw = 0, add_mask = 0;
-    int64_t nMember = 0;
+    int nDesign = 0, nw = 0;
     int64_t maxMem = 0, maxSta = 0;     // members / stations of the largest design (host loop of phase 1)
+    size_t nStrips = 0, nRows = 0;      // totals of phase 1, read by phase 2 (wait_totals): wet strips, MacCamy-Fuchs rows,
+    int maxS = 0;                       // strips of the largest design
     double *M0d = nullptr, *C0d = nullptr;
     const double *B0d = nullptr, *MBwd = nullptr;
     bool active = false;
@@ -883,6 +884,20 @@ struct raftx_ctx {
 struct DevOffsets {
     const int64_t *memberOff, *stationOff, *capOff;      // device copies of the caller's arrays, absolute values
 };
+struct SeaStates { int nCase, nHead, nw; const double *w, *k; double depth, rho, g; const double *zeta, *beta; };   // sea states as a caller gives them (host arrays)
+// Where the designs of a build come from: host arrays of the whole batch (a build takes a slice of designs out of them),
+// alive until the build has been waited for.  The sweep crossing keeps the one of its batch for the blocks whose phase 1
+// raftx_sweep_launch enqueues.
+struct BuildSource {
+    const int64_t *memberOff, *stationOff, *capOff;      // the batch's own (absolute) offsets; capOff may be null
+    const double *members, *stations, *caps;             // descriptors (null with a variant program)
+    const double *pose, *M0, *B0, *C0, *MBw, *Fz_moor, *k;
+    double rho, g;
+    int nw, add_mask;
+    DevOffsets dOff{nullptr, nullptr, nullptr};          // the offsets resident for the whole batch; memberOff == nullptr: every build uploads its slice
+    const double *k_dev = nullptr;                       // wave numbers already resident (the crossing's sea-state tables), or null: k is uploaded
+    VariantSrc var{nullptr, nullptr};                    // prog == nullptr: the caller's descriptor arrays
+};
 // One sweep crossing in flight: everything raftx_sweep_wait needs to finish it.
 struct SweepSlot {
     bool busy = false;                   // launched (phase 2 enqueued), not yet waited for
@@ -902,14 +917,7 @@ struct SweepSlot {
     // phase 1 (descriptor upload + member pass) of the blocks behind the second one is enqueued by raftx_sweep_launch, one
     // block ahead of the block being launched: the caller's arrays (alive until the batch has been waited for) and the
     // batch's device offsets are kept for that
-    struct {
-        const int64_t *memberOff, *stationOff, *capOff;
-        const double *members, *stations, *caps, *pose, *M0, *B0, *C0, *Fz_moor, *k;
-        double rho, g;
-        int add_mask;
-        DevOffsets dOff;
-        VariantSrc var;                  // prog == nullptr: the caller's descriptor arrays
-    } p1;
+    BuildSource p1;
     size_t next_p1 = 0;                  // first block whose phase 1 has not been enqueued yet
     std::chrono::steady_clock::time_point t0;
     double tl[4] = {0, 0, 0, 0};
@@ -1129,17 +1137,32 @@ extern "C" int raftx_device_locality(int device, char *pci_bus_id, int len, int 
 extern "C" const char *raftx_last_error(raftx_ctx *c) { return c ? c->err : "null ctx"; }
 extern "C" double raftx_last_kernel_ms(raftx_ctx *c) { return c ? c->last_ms : 0.0; }
 
-template <typename Tp, typename Dp>
-static int upload(raftx_ctx *c, std::vector<void *> &bag, const Tp *host, size_t n, Dp *dev) {
-    *dev = nullptr;
-    if (!host || n == 0) return 0;
+// ---- device memory owned by a bag: a block of the ctx pool for n elements, remembered in `bag` (design_allocs, a job's
+// tmp, a slot's allocs, ..), which goes back to the pool as a whole (free_list).  A zero count still gives a valid,
+// never-read block.
+template <typename Tp>
+static int pool_alloc(raftx_ctx *c, std::vector<void *> &bag, size_t n, Tp **out) {
+    *out = nullptr;
     void *p = nullptr;
-    HIPCHK(c, c->pool.get(n * sizeof(Tp), &p));
+    HIPCHK(c, c->pool.get((n ? n : 1) * sizeof(Tp), &p));
     bag.push_back(p);
-    HIPCHK(c, hipMemcpyAsync(p, host, n * sizeof(Tp), hipMemcpyHostToDevice, c->stream));
-    *dev = reinterpret_cast<const Tp *>(p);
+    *out = reinterpret_cast<Tp *>(p);
     return 0;
 }
+// ... filled from host memory by a copy enqueued on `st`.  An absent or empty host array takes no block and gives a NULL
+// device pointer: the kernels test the optional tables for it.
+template <typename Tp, typename Dp>
+static int upload_on(raftx_ctx *c, hipStream_t st, std::vector<void *> &bag, const Tp *host, size_t n, Dp *dev) {
+    *dev = nullptr;
+    if (!host || n == 0) return 0;
+    Tp *p = nullptr;
+    if (pool_alloc(c, bag, n, &p)) return -2;
+    HIPCHK(c, hipMemcpyAsync(p, host, n * sizeof(Tp), hipMemcpyHostToDevice, st));
+    *dev = p;
+    return 0;
+}
+template <typename Tp, typename Dp>
+static int upload(raftx_ctx *c, std::vector<void *> &bag, const Tp *host, size_t n, Dp *dev) { return upload_on(c, c->stream, bag, host, n, dev); }
 
 extern "C" int raftx_upload_designs(raftx_ctx *c, int nDesign, const int64_t *stripOffsets, const double *strips,
                                     int nStripFields, const double *M0, const double *B0, const double *C0, int nw,
@@ -1195,22 +1218,15 @@ extern "C" int raftx_upload_designs(raftx_ctx *c, int nDesign, const int64_t *st
     return 0;
 }
 
-// ---- geometry -> strip tables + statics on the device (raftx_geom.h)
-template <typename Tp>
-static int dev_alloc(raftx_ctx *c, std::vector<void *> &bag, size_t n, Tp **out, bool zero = false) {
-    *out = nullptr;
-    void *p = nullptr;
-    HIPCHK(c, c->pool.get((n ? n : 1) * sizeof(Tp), &p));
-    bag.push_back(p);
-    if (zero) HIPCHK(c, hipMemsetAsync(p, 0, (n ? n : 1) * sizeof(Tp), c->stream));
-    *out = reinterpret_cast<Tp *>(p);
-    return 0;
-}
-
-// ---- raftx_build_designs in two phases, so that the sweep crossing can keep several design blocks in flight.
+// ---- geometry -> strip tables + statics on the device (raftx_geom.h): raftx_build_designs in two phases, so that the
+// sweep crossing can keep several design blocks in flight.
 // Phase 1 enqueues the descriptor H2D on sCopy and, behind it on sPrep, the member pass and the scans; the totals
 // (wet strips, MacCamy-Fuchs rows, strips of the largest design, error flags) and the design offsets land in page-locked
-// memory and evTot marks them.  Nothing here waits for the device.
+// memory and evTot marks them.  Nothing here waits for the device.  The layout of that landing area (raftx_ctx::pin =
+// GeomArgs::hostOut) in long longs, as k_geom_scan_t stores it through A.hostOut (raftx_geom.h):
+constexpr size_t PIN_TOT = 0;                // [0..2] wet strips, MacCamy-Fuchs rows, strips of the largest design
+constexpr size_t PIN_ERR = 3;                // [3..4] the four error flags of GeomArgs::err, as ints
+constexpr size_t PIN_OFF = 8;                // [8 .. 8 + nDesign] strip offsets of the designs
 static int pin_reserve(raftx_ctx *c, size_t n) {
     if (c->pin && c->pin_n >= n) return 0;
     if (c->pin) HIPCHK(c, hipHostFree(c->pin));
@@ -1221,211 +1237,200 @@ static int pin_reserve(raftx_ctx *c, size_t n) {
     c->pin_n = n;
     return 0;
 }
-template <typename Tp, typename Dp>
-static int upload_on(raftx_ctx *c, hipStream_t st, std::vector<void *> &bag, const Tp *host, size_t n, Dp *dev) {
-    *dev = nullptr;
-    if (!host || n == 0) return 0;
-    void *p = nullptr;
-    HIPCHK(c, c->pool.get(n * sizeof(Tp), &p));
-    bag.push_back(p);
-    HIPCHK(c, hipMemcpyAsync(p, host, n * sizeof(Tp), hipMemcpyHostToDevice, st));
-    *dev = reinterpret_cast<const Tp *>(p);
+// The check of a design source's arrays, made once by the entry point that takes them.  Callers and tests read the texts:
+// `bad` is the entry point's own ("build_designs: bad arguments" | "sweep_stats: bad design arguments"), `who` its prefix.
+static int check_source(raftx_ctx *c, const BuildSource &B, int nDesign, const char *who, const char *bad) {
+    const bool var = B.var.prog != nullptr;
+    if (nDesign < 0 || !B.memberOff || (!B.members && !var) || !B.stationOff || (!B.stations && !var) || !B.M0 || !B.B0 || !B.C0)
+        FAIL(c, "%s: %s", who, bad);
+    if (!var && (B.capOff == nullptr) != (B.caps == nullptr)) FAIL(c, "%s: capOff and caps must be given together", who);
     return 0;
 }
-// Designs [lo, lo + nDesign) of the caller's batch: memberOff / stationOff / capOff are the batch's own (absolute) host
-// arrays, the descriptor arrays are sliced here.  shared == NULL: the offsets of the slice are uploaded by this call.
 static void launch_scan(hipStream_t st, const GeomArgs &A) {
     static const int scan_t = getenv("RAFTX_SCAN_T") ? atoi(getenv("RAFTX_SCAN_T")) : 1024;     // tuning: 256 | 1024 threads
     if (scan_t == 256) hipLaunchKernelGGL(k_geom_scan_t<256>, dim3(1), dim3(256), 0, st, A);
     else hipLaunchKernelGGL(k_geom_scan_t<1024>, dim3(1), dim3(1024), 0, st, A);
 }
-static int build_phase1(raftx_ctx *c, hipStream_t sCopy, hipStream_t sPrep, int lo, int nDesign, const int64_t *memberOff,
-                        const double *members, const int64_t *stationOff, const double *stations, const int64_t *capOff,
-                        const double *caps, const double *pose, double rho, double g, int nw, const double *k, int add_mask,
-                        const double *M0, const double *B0, const double *C0, const double *MBw, const double *Fz_moor,
-                        const DevOffsets *shared, const double *k_dev = nullptr, const VariantSrc *var = nullptr) {
-    RangeScope range_("build phase 1: descriptor H2D, member pass, scans (enqueue)");
-    BuildJob &J = c->job;
-    if (var && !var->prog) var = nullptr;
-    if (nDesign < 0 || lo < 0 || !memberOff || (!members && !var) || !stationOff || (!stations && !var) || !M0 || !B0 || !C0)
-        FAIL(c, "build_designs: bad arguments");
-    if (!var && (capOff == nullptr) != (caps == nullptr)) FAIL(c, "build_designs: capOff and caps must be given together");
-    if (nw < 1 || nw > MAX_NW) FAIL(c, "build_designs: nw=%d outside 1..%d", nw, MAX_NW);
-    const int64_t m0 = memberOff[lo], m1 = memberOff[lo + nDesign], nMember = m1 - m0;
-    if (nMember < 0 || m0 < 0) FAIL(c, "build_designs: member offsets not monotone");
-    const int64_t s0 = stationOff[m0], s1 = stationOff[m1];
+// Designs [lo, lo + nDesign) of a source: their members [m0, m1), stations [s0, s1) and caps [c0, c1) in the batch's arrays.
+struct Slice { int lo; int64_t m0, m1, s0, s1, c0, c1; };
+static int slice_of(raftx_ctx *c, const BuildSource &B, int lo, int nDesign, Slice &L) {
+    if (lo < 0 || nDesign < 0) FAIL(c, "build_designs: bad arguments");
+    const int64_t m0 = B.memberOff[lo], m1 = B.memberOff[lo + nDesign];
+    if (m1 < m0 || m0 < 0) FAIL(c, "build_designs: member offsets not monotone");
+    const int64_t s0 = B.stationOff[m0], s1 = B.stationOff[m1];
     if (s1 < s0 || s0 < 0) FAIL(c, "build_designs: station offsets not monotone");
-    const int64_t c0 = capOff ? capOff[m0] : 0, c1 = capOff ? capOff[m1] : 0;
+    const int64_t c0 = B.capOff ? B.capOff[m0] : 0, c1 = B.capOff ? B.capOff[m1] : 0;
     if (c1 < c0 || c0 < 0) FAIL(c, "build_designs: cap offsets not monotone");
-    HIPCHK(c, hipSetDevice(c->device));
-    free_list(c, c->design_allocs);               // callers guarantee that nothing in flight reads the previous tables
-    free_list(c, J.tmp);
-    c->have_designs = false;
-    c->bem_ready = false;
-    c->g_n = 0;
-    if (pin_reserve(c, (size_t)nDesign + 9)) return -2;
-    std::vector<void *> &tmp = J.tmp;
+    L = {lo, m0, m1, s0, s1, c0, c1};
+    return 0;
+}
+// The slice's descriptors into device memory, copied on sCopy.  Offsets: the slice of the batch's resident arrays, or
+// uploaded here.  Members, stations and caps: the slice of the caller's arrays, or with a variant program only the
+// parameters (E then says what k_geom_expand writes the descriptors from).  The per-design matrices stay with the tables
+// (design_allocs); the rest goes back to the pool when the job retires.
+static int upload_descriptors(raftx_ctx *c, hipStream_t sCopy, const BuildSource &B, const Slice &L, ExpandArgs &E) {
+    BuildJob &J = c->job;
     GeomArgs &A = J.A;
-    memset(&A, 0, sizeof(A));
-    A.nDesign = nDesign;
-    A.nMember = nMember;
-    A.rho = rho; A.g = g; A.nw = nw; A.add_mask = add_mask;
-    A.mbase = m0; A.sbase = s0; A.cbase = c0;
-    A.hostOut = c->pin;
-    memset(c->pin, 0, 9 * sizeof(long long));
-    J.nDesign = nDesign; J.nw = nw; J.add_mask = add_mask; J.nMember = nMember;
+    std::vector<void *> &tmp = J.tmp, &keep = c->design_allocs;
+    const size_t lo = (size_t)L.lo, nDesign = (size_t)A.nDesign, nMember = (size_t)A.nMember, nw = (size_t)B.nw;
+    const size_t nSta = (size_t)(L.s1 - L.s0), nCap = (size_t)(L.c1 - L.c0);
     int rc = 0;
-    if (shared) {
-        A.memberOff = shared->memberOff + lo;
-        A.stationOff = shared->stationOff + m0;
-        A.capOff = capOff ? shared->capOff + m0 : nullptr;
+    if (B.dOff.memberOff) {
+        A.memberOff = B.dOff.memberOff + lo;
+        A.stationOff = B.dOff.stationOff + L.m0;
+        A.capOff = B.capOff ? B.dOff.capOff + L.m0 : nullptr;
     } else {
-        rc |= upload_on(c, sCopy, tmp, memberOff + lo, (size_t)nDesign + 1, &A.memberOff);
-        rc |= upload_on(c, sCopy, tmp, stationOff + m0, (size_t)nMember + 1, &A.stationOff);
-        if (capOff) rc |= upload_on(c, sCopy, tmp, capOff + m0, (size_t)nMember + 1, &A.capOff);
+        rc |= upload_on(c, sCopy, tmp, B.memberOff + lo, nDesign + 1, &A.memberOff);
+        rc |= upload_on(c, sCopy, tmp, B.stationOff + L.m0, nMember + 1, &A.stationOff);
+        if (B.capOff) rc |= upload_on(c, sCopy, tmp, B.capOff + L.m0, nMember + 1, &A.capOff);
     }
-    ExpandArgs E;
     memset(&E, 0, sizeof(E));
-    if (var) {
+    if (const VariantProg *P = B.var.prog) {
         // variants of one base unit: only their parameters cross the bus (nP doubles per design); the descriptors are
-        // written in HBM by k_geom_expand, enqueued below on sPrep ahead of the member pass
-        const VariantProg &P = *var->prog;
-        if (nMember != (int64_t)nDesign * P.nM || s1 - s0 != (int64_t)nDesign * P.nSt || c1 - c0 != (int64_t)nDesign * P.nCap)
-            FAIL(c, "build_designs: offsets do not describe %d variants of the program's base unit", nDesign);
-        void *pg = nullptr, *ps = nullptr, *pc = nullptr;
-        HIPCHK(c, c->pool.get(std::max<size_t>((size_t)nMember * RAFTX_GM_N, 1) * sizeof(double), &pg));
-        tmp.push_back(pg);
-        HIPCHK(c, c->pool.get(std::max<size_t>((size_t)(s1 - s0) * RAFTX_GS_N, 1) * sizeof(double), &ps));
-        tmp.push_back(ps);
-        HIPCHK(c, c->pool.get(std::max<size_t>((size_t)(c1 - c0) * RAFTX_GC_N, 1) * sizeof(double), &pc));
-        tmp.push_back(pc);
-        rc |= upload_on(c, sCopy, tmp, var->params + (size_t)lo * P.nP, (size_t)nDesign * P.nP, &E.params);
-        expand_args(P, nDesign, reinterpret_cast<double *>(pg), reinterpret_cast<double *>(ps), reinterpret_cast<double *>(pc), E);
-        A.gm = E.gm_out;
-        A.gs = E.gs_out;
-        if (capOff) A.caps = E.gc_out;
-    } else {
-        rc |= upload_on(c, sCopy, tmp, members + (size_t)m0 * RAFTX_GM_N, (size_t)nMember * RAFTX_GM_N, &A.gm);
-        rc |= upload_on(c, sCopy, tmp, stations + (size_t)s0 * RAFTX_GS_N, (size_t)(s1 - s0) * RAFTX_GS_N, &A.gs);
-    }
-    rc |= upload_on(c, sCopy, tmp, pose ? pose + (size_t)lo * 6 : nullptr, pose ? (size_t)nDesign * 6 : 0, &A.pose);
-    if (capOff && !var) {
-        if (c1 > c0) rc |= upload_on(c, sCopy, tmp, caps + (size_t)c0 * RAFTX_GC_N, (size_t)(c1 - c0) * RAFTX_GC_N, &A.caps);
-        else {                                        // no caps in this slice: a valid, never-read address
-            void *p_ = nullptr;
-            HIPCHK(c, c->pool.get(RAFTX_GC_N * sizeof(double), &p_));
-            tmp.push_back(p_);
-            A.caps = reinterpret_cast<const double *>(p_);
-        }
-    }
-    if (k_dev) A.k = k_dev;                       // wave numbers already resident (the sweep crossing's sea-state tables)
-    else rc |= upload_on(c, sCopy, c->design_allocs, k, k ? (size_t)nw : 0, &A.k);
-    const double *M0c = nullptr, *C0c = nullptr;
-    rc |= upload_on(c, sCopy, c->design_allocs, M0 + (size_t)lo * 36, (size_t)nDesign * 36, &M0c);
-    rc |= upload_on(c, sCopy, c->design_allocs, C0 + (size_t)lo * 36, (size_t)nDesign * 36, &C0c);
-    rc |= upload_on(c, sCopy, c->design_allocs, B0 + (size_t)lo * 36, (size_t)nDesign * 36, &J.B0d);
-    rc |= upload_on(c, sCopy, c->design_allocs, MBw ? MBw + (size_t)lo * 72 * nw : nullptr, MBw ? (size_t)nDesign * 72 * nw : 0, &J.MBwd);
-    if (Fz_moor) rc |= upload_on(c, sCopy, tmp, Fz_moor + lo, (size_t)nDesign, &A.Fz);
-    if (rc) return -2;
-    J.M0d = const_cast<double *>(M0c);
-    J.C0d = const_cast<double *>(C0c);
-    A.M0 = J.M0d;
-    A.C0 = J.C0d;
-    HIPCHK(c, hipEventRecord(c->evUp, sCopy));
-    HIPCHK(c, hipStreamWaitEvent(sPrep, c->evUp, 0));
-    if (var && nDesign > 0) {
-        // the expansion (0.09 ms of chip time) on the preparation stream, ahead of the member pass: its stores land inside the
-        // running fused kernel of the batch before (a high-priority stream of its own gained nothing: profiles/MEASUREMENT_HISTORY.md,
-        // "Closed scheduling experiments of the crossing")
-        launch_expand(E, sPrep);
-    }
-    // device-side scratch; on a pooled block a memset on sPrep is ordered before the kernels that use it
-    int *errd = nullptr;
-    {
-        std::vector<void *> &tb = tmp;
-        auto alloc = [&](size_t bytes, void **out, std::vector<void *> &bag) -> int {
-            HIPCHK(c, c->pool.get(bytes ? bytes : 8, out));
-            bag.push_back(*out);
-            return 0;
-        };
-        void *p_[13] = {nullptr};
-        if (alloc((size_t)nMember * sizeof(int), &p_[0], tb) || alloc((size_t)nMember * sizeof(int), &p_[1], tb) ||
-            alloc((size_t)nMember * MP_N * sizeof(double), &p_[4], tb) || alloc((size_t)nMember * MH_N * sizeof(double), &p_[5], tb) ||
-            alloc((size_t)nMember * MI_N * sizeof(double), &p_[6], tb) || alloc(4 * sizeof(int), &p_[7], tb) ||
-            alloc((size_t)nMember * sizeof(int), &p_[12], tb) ||
-            alloc((size_t)nDesign * sizeof(double), &p_[8], tb) || alloc(5 * sizeof(long long), &p_[9], tb) ||
-            alloc(((size_t)nDesign + 1) * sizeof(int64_t), &p_[10], c->design_allocs) ||
-            alloc(((size_t)nDesign + 1) * sizeof(int64_t), &p_[11], c->design_allocs))
+        // written in HBM by k_geom_expand, enqueued on sPrep ahead of the member pass
+        if (nMember != nDesign * P->nM || nSta != nDesign * P->nSt || nCap != nDesign * P->nCap)
+            FAIL(c, "build_designs: offsets do not describe %d variants of the program's base unit", A.nDesign);
+        double *gm = nullptr, *gs = nullptr, *gc = nullptr;
+        if (pool_alloc(c, tmp, nMember * RAFTX_GM_N, &gm) || pool_alloc(c, tmp, nSta * RAFTX_GS_N, &gs) ||
+            pool_alloc(c, tmp, nCap * RAFTX_GC_N, &gc))
             return -2;
-        A.cnt = (int *)p_[0]; A.cntm = (int *)p_[1];
-        A.mpose = (double *)p_[4]; A.mhyd = (double *)p_[5]; A.minert = (double *)p_[6];
-        errd = (int *)p_[7]; A.err = errd;
-        A.drho = (double *)p_[8];
-        A.tot = (long long *)p_[9];
-        A.off = (int64_t *)p_[10]; A.cmoff = (int64_t *)p_[11];
-        A.mdesign_w = (int *)p_[12]; A.mdesign = A.mdesign_w;
+        rc |= upload_on(c, sCopy, tmp, B.var.params + lo * P->nP, nDesign * P->nP, &E.params);
+        expand_args(*P, A.nDesign, gm, gs, gc, E);
+        A.gm = gm; A.gs = gs; A.caps = B.capOff ? gc : nullptr;
+    } else {
+        rc |= upload_on(c, sCopy, tmp, B.members + (size_t)L.m0 * RAFTX_GM_N, nMember * RAFTX_GM_N, &A.gm);
+        rc |= upload_on(c, sCopy, tmp, B.stations + (size_t)L.s0 * RAFTX_GS_N, nSta * RAFTX_GS_N, &A.gs);
     }
-    // the member offsets of every design, checked here (the kernels walk them): monotone, inside the slice; and the
-    // largest design's members / stations (they size the LDS of k_geom_design)
+    rc |= upload_on(c, sCopy, tmp, B.pose ? B.pose + lo * 6 : nullptr, nDesign * 6, &A.pose);
+    if (B.capOff && !B.var.prog) {
+        if (nCap) rc |= upload_on(c, sCopy, tmp, B.caps + (size_t)L.c0 * RAFTX_GC_N, nCap * RAFTX_GC_N, &A.caps);
+        else rc |= pool_alloc(c, tmp, RAFTX_GC_N, &A.caps);        // no caps in this slice: a valid, never-read address
+    }
+    if (B.k_dev) A.k = B.k_dev;                   // wave numbers already resident (the sweep crossing's sea-state tables)
+    else rc |= upload_on(c, sCopy, keep, B.k, nw, &A.k);
+    rc |= upload_on(c, sCopy, keep, B.M0 + lo * 36, nDesign * 36, &J.M0d);
+    rc |= upload_on(c, sCopy, keep, B.C0 + lo * 36, nDesign * 36, &J.C0d);
+    rc |= upload_on(c, sCopy, keep, B.B0 + lo * 36, nDesign * 36, &J.B0d);
+    rc |= upload_on(c, sCopy, keep, B.MBw ? B.MBw + lo * 72 * nw : nullptr, nDesign * 72 * nw, &J.MBwd);
+    if (B.Fz_moor) rc |= upload_on(c, sCopy, tmp, B.Fz_moor + lo, nDesign, &A.Fz);
+    if (rc) return -2;
+    A.M0 = J.M0d; A.C0 = J.C0d;
+    return 0;
+}
+// device-side scratch of the member pass and the scans (on a pooled block a memset on sPrep is ordered before the kernels
+// that use it); kept with the tables: the offsets the scans leave and the per-design results of the reductions
+static int alloc_member_scratch(raftx_ctx *c) {
+    GeomArgs &A = c->job.A;
+    std::vector<void *> &tmp = c->job.tmp, &keep = c->design_allocs;
+    const size_t nDesign = (size_t)A.nDesign, nMember = (size_t)A.nMember;
+    if (pool_alloc(c, tmp, nMember, &A.cnt) || pool_alloc(c, tmp, nMember, &A.cntm) || pool_alloc(c, tmp, nMember * MP_N, &A.mpose) ||
+        pool_alloc(c, tmp, nMember * MH_N, &A.mhyd) || pool_alloc(c, tmp, nMember * MI_N, &A.minert) || pool_alloc(c, tmp, 4, &A.err) ||
+        pool_alloc(c, tmp, nMember, &A.mdesign_w) || pool_alloc(c, tmp, nDesign, &A.drho) || pool_alloc(c, tmp, 5, &A.tot) ||
+        pool_alloc(c, keep, nDesign + 1, &A.off) || pool_alloc(c, keep, nDesign + 1, &A.cmoff) || pool_alloc(c, keep, nDesign * 36, &A.Ch) ||
+        pool_alloc(c, keep, nDesign * 6, &A.Wh) || pool_alloc(c, keep, nDesign * 36, &A.Ms) || pool_alloc(c, keep, nDesign * 36, &A.Cs) ||
+        pool_alloc(c, keep, nDesign * 6, &A.Ws) || pool_alloc(c, keep, nDesign * RAFTX_SP_N, &A.props))
+        return -2;
+    A.mdesign = A.mdesign_w;
+    return 0;
+}
+// the member offsets of every design, checked here (the kernels walk them): monotone, inside the slice; and the
+// largest design's members / stations (they size the LDS of k_geom_design)
+static int design_bounds(raftx_ctx *c, const BuildSource &B, const Slice &L) {
+    BuildJob &J = c->job;
     J.maxMem = J.maxSta = 0;
-    for (int d = 0; d < nDesign; d++) {
-        const int64_t a = memberOff[lo + d], b = memberOff[lo + d + 1];
-        if (b < a || a < m0 || b > m1) FAIL(c, "member offsets not monotone at design %d", lo + d);
-        if (stationOff[b] < stationOff[a]) FAIL(c, "build_designs: station offsets not monotone");
+    for (int d = 0; d < J.nDesign; d++) {
+        const int64_t a = B.memberOff[L.lo + d], b = B.memberOff[L.lo + d + 1];
+        if (b < a || a < L.m0 || b > L.m1) FAIL(c, "member offsets not monotone at design %d", L.lo + d);
+        if (B.stationOff[b] < B.stationOff[a]) FAIL(c, "build_designs: station offsets not monotone");
         J.maxMem = std::max(J.maxMem, b - a);
-        J.maxSta = std::max(J.maxSta, stationOff[b] - stationOff[a]);
+        J.maxSta = std::max(J.maxSta, B.stationOff[b] - B.stationOff[a]);
     }
+    return 0;
+}
+static int enqueue_member_pass(raftx_ctx *c, hipStream_t sPrep) {
+    BuildJob &J = c->job;
+    GeomArgs &A = J.A;
+    const int64_t nDesign = J.nDesign, nMember = A.nMember;
     hipLaunchKernelGGL(k_geom_zero, dim3((unsigned)(nDesign / 256 + 1)), dim3(256), 0, sPrep, A);
     HIPCHK(c, hipEventRecord(c->evZ, sPrep));
     HIPCHK(c, hipEventRecord(c->evG2, sPrep));
     A.mgrid = 0;
     if (nMember > 0) {
         // member kernels on a (member position, design) grid when that wastes few threads: wavefronts of like members
-        const int64_t maxMem = J.maxMem;
-        A.mgrid = (nDesign >= 64 && maxMem * nDesign <= nMember + nMember / 4) ? (int)maxMem : 0;
+        A.mgrid = (nDesign >= 64 && J.maxMem * nDesign <= nMember + nMember / 4) ? (int)J.maxMem : 0;
         const int64_t nThread = A.mgrid > 0 ? (int64_t)A.mgrid * nDesign : nMember;
         hipLaunchKernelGGL(k_geom_member, dim3((unsigned)((nThread + 127) / 128)), dim3(128), 0, sPrep, A);
-        if (add_mask & RAFTX_TRIM_BALLAST) {              // heave trim: density correction, then the inertia again
+        if (A.add_mask & RAFTX_TRIM_BALLAST) {            // heave trim: density correction, then the inertia again
             hipLaunchKernelGGL(k_geom_trim, dim3((unsigned)(nDesign / 128 + 1)), dim3(128), 0, sPrep, A);
             hipLaunchKernelGGL(k_geom_reinertia, dim3((unsigned)((nThread + 127) / 128)), dim3(128), 0, sPrep, A);
         }
     }
-    // the member -> platform reductions need the member pass only: they run on a side stream beside the scans, off the
-    // stream the fused kernel waits on (phase 2 orders the design kernel behind them)
-    if (dev_alloc(c, c->design_allocs, (size_t)nDesign * 36, &A.Ch) || dev_alloc(c, c->design_allocs, (size_t)nDesign * 6, &A.Wh) ||
-        dev_alloc(c, c->design_allocs, (size_t)nDesign * 36, &A.Ms) || dev_alloc(c, c->design_allocs, (size_t)nDesign * 36, &A.Cs) ||
-        dev_alloc(c, c->design_allocs, (size_t)nDesign * 6, &A.Ws) || dev_alloc(c, c->design_allocs, (size_t)nDesign * RAFTX_SP_N, &A.props))
-        return -2;
+    return 0;
+}
+// The scans (totals, error flags and design offsets reach the host through their own stores into page-locked memory,
+// A.hostOut: a D2H copy of them would queue on the DMA engine behind a bulk download of the previous batch) and the member
+// -> platform reductions, which need the member pass only.  A crossing's block (a preparation stream apart from its ctx
+// stream) runs the reductions on a side stream beside the scans, off the stream the fused kernel waits on (phase 2
+// orders the design kernel behind them) -- and the scan and its markers first: streams share hardware queues, and a
+// reduction submitted ahead of the scan on the same queue would sit on the path to the totals (the host waits for them
+// before it can size and launch the generation).
+static int enqueue_scan_reduce(raftx_ctx *c, hipStream_t sPrep) {
+    BuildJob &J = c->job;
+    const bool side = J.nDesign > 0 && sPrep != c->stream;
+    auto scan = [&]() -> int {
+        if (J.nDesign > 0) launch_scan(sPrep, J.A);
+        HIPCHK(c, hipEventRecord(c->evG3, sPrep));
+        HIPCHK(c, hipEventRecord(c->evTot, sPrep));
+        return 0;
+    };
     J.reduce_stream = nullptr;
-    const bool side = nDesign > 0 && sPrep != c->stream;          // crossings: a stream of its own per block context
-    if (side) HIPCHK(c, hipEventRecord(c->evMem, sPrep));
-    // the scan first: streams share hardware queues, and a reduction submitted ahead of it on the same queue would sit on
-    // the path to the totals (the host waits for them before it can size and launch the generation)
-    if (nDesign > 0 && side) launch_scan(sPrep, A);
-    if (side) {                                           // ... and its markers, for the same reason
-        HIPCHK(c, hipEventRecord(c->evG3, sPrep));
-        HIPCHK(c, hipEventRecord(c->evTot, sPrep));
+    hipStream_t sRed = sPrep;
+    if (side) {
+        HIPCHK(c, hipEventRecord(c->evMem, sPrep));
+        if (scan()) return -2;
+        if (!c->sAux) HIPCHK(c, hipStreamCreateWithFlags(&c->sAux, hipStreamNonBlocking));
+        sRed = c->sAux;
+        HIPCHK(c, hipStreamWaitEvent(sRed, c->evMem, 0));
     }
-    if (nDesign > 0) {
-        hipStream_t sRed = sPrep;
-        if (side) {
-            if (!c->sAux) HIPCHK(c, hipStreamCreateWithFlags(&c->sAux, hipStreamNonBlocking));
-            sRed = c->sAux;
-            HIPCHK(c, hipStreamWaitEvent(sRed, c->evMem, 0));
-        }
-        hipLaunchKernelGGL(k_geom_reduce, dim3((unsigned)(((size_t)nDesign * 3 + 63) / 64)), dim3(64), 0, sRed, A);
-        if (sRed != sPrep) {
-            HIPCHK(c, hipEventRecord(c->evRed, sRed));
-            J.reduce_stream = sRed;
-        }
+    if (J.nDesign > 0) hipLaunchKernelGGL(k_geom_reduce, dim3((unsigned)(((size_t)J.nDesign * 3 + 63) / 64)), dim3(64), 0, sRed, J.A);
+    if (!side) return scan();
+    HIPCHK(c, hipEventRecord(c->evRed, sRed));
+    J.reduce_stream = sRed;
+    return 0;
+}
+// Designs [lo, lo + nDesign) of the source, which its entry point has checked (check_source).
+static int build_phase1(raftx_ctx *c, hipStream_t sCopy, hipStream_t sPrep, const BuildSource &B, int lo, int nDesign) {
+    RangeScope range_("build phase 1: descriptor H2D, member pass, scans (enqueue)");
+    BuildJob &J = c->job;
+    Slice L;
+    if (int rc = slice_of(c, B, lo, nDesign, L)) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    free_list(c, c->design_allocs);               // callers guarantee that nothing in flight reads the previous tables
+    free_list(c, J.tmp);
+    c->have_designs = false; c->bem_ready = false; c->g_n = 0;
+    if (pin_reserve(c, PIN_OFF + (size_t)nDesign + 1)) return -2;
+    GeomArgs &A = J.A;
+    memset(&A, 0, sizeof(A));
+    A.nDesign = nDesign; A.nMember = L.m1 - L.m0;
+    A.rho = B.rho; A.g = B.g; A.nw = B.nw; A.add_mask = B.add_mask;
+    A.mbase = L.m0; A.sbase = L.s0; A.cbase = L.c0;
+    A.hostOut = c->pin;
+    memset(c->pin, 0, (PIN_OFF + 1) * sizeof(long long));
+    J.nDesign = nDesign; J.nw = B.nw;
+    ExpandArgs E;
+    if (int rc = upload_descriptors(c, sCopy, B, L, E)) return rc;
+    HIPCHK(c, hipEventRecord(c->evUp, sCopy));
+    HIPCHK(c, hipStreamWaitEvent(sPrep, c->evUp, 0));
+    if (B.var.prog && nDesign > 0) {
+        // the expansion (0.09 ms of chip time) on the preparation stream, ahead of the member pass: its stores land inside the
+        // running fused kernel of the batch before (a high-priority stream of its own gained nothing: profiles/MEASUREMENT_HISTORY.md,
+        // "Closed scheduling experiments of the crossing")
+        launch_expand(E, sPrep);
     }
-    // totals, error flags and design offsets reach the host through the kernels' own stores into page-locked memory
-    // (A.hostOut): a D2H copy of them would queue on the DMA engine behind a bulk download of the previous batch
-    if (!side) {
-        if (nDesign > 0) launch_scan(sPrep, A);
-        HIPCHK(c, hipEventRecord(c->evG3, sPrep));
-        HIPCHK(c, hipEventRecord(c->evTot, sPrep));
-    }
+    if (int rc = alloc_member_scratch(c)) return rc;
+    if (int rc = design_bounds(c, B, L)) return rc;
+    if (int rc = enqueue_member_pass(c, sPrep)) return rc;
+    if (int rc = enqueue_scan_reduce(c, sPrep)) return rc;
     J.active = true;
     return 0;
 }
@@ -1435,56 +1440,50 @@ static int build_phase1(raftx_ctx *c, hipStream_t sCopy, hipStream_t sPrep, int 
 // sGen: the stream the generation kernels go to (null: the ctx stream).  The sweep crossing gives the preparation stream
 // for every block but the first, so that a block's tables are generated WHILE the fused kernel of the block before it
 // runs (they fill the CUs its last residency round leaves idle); the ctx stream is ordered behind them by evG1.
+// kind: 0 = a raftx_build_designs call (tables + ABI copy of the strip records), or bits:
+constexpr int GEN_CROSSING = 1;      // a block of a sweep crossing (no ABI copy)
+constexpr int GEN_MAY_DEFER = 2;     // ... whose tables may be left to the fused kernel (RAFTX_FUSED_GEN=1)
+constexpr int GEN_PIPELINED = 4;     // ... with other crossings in flight (its member pass ran a step ago: the generation adds the design matrices up itself)
 static void launch_design(raftx_ctx *c, hipStream_t st) {
-    BuildJob &J = c->job;
-    hipLaunchKernelGGL(k_geom_design, dim3((unsigned)J.nDesign), dim3(GD_T), J.gen_lds, st, J.A);
+    hipLaunchKernelGGL(k_geom_design, dim3((unsigned)c->job.nDesign), dim3(GD_T), c->job.gen_lds, st, c->job.A);
 }
-// crossing: 0 = raftx_build_designs (tables + ABI copy); bits: 1 = a sweep crossing (no ABI copy), 2 = its tables may be left
-// to the fused kernel (RAFTX_FUSED_GEN=1), 4 = other crossings are in flight (its member pass ran a step ago: the generation
-// adds the design matrices up itself)
-static int build_phase2(raftx_ctx *c, int64_t *stripOffsets, hipStream_t sGen = nullptr, int crossing = 0) {
-    RangeScope range_("build phase 2: wait for totals, strip tables + statics (enqueue)");
+// the totals and error flags of phase 1, from the landing area, into the job; the strip offsets to the caller
+static int wait_totals(raftx_ctx *c, int64_t *stripOffsets) {
     BuildJob &J = c->job;
-    if (!J.active) FAIL(c, "build_designs: phase 2 without phase 1");
-    GeomArgs &A = J.A;
-    const int nDesign = J.nDesign, nw = J.nw;
     for (;;) {                                        // spin: the blocking wait costs ~0.2 ms of wake-up latency per block
         const hipError_t q = hipEventQuery(c->evTot);
         if (q == hipSuccess) break;
         if (q != hipErrorNotReady) HIPCHK(c, q);
     }
     HIPCHK(c, hipGetLastError());
-    const int *bad = reinterpret_cast<const int *>(c->pin + 3);
+    const int *bad = reinterpret_cast<const int *>(c->pin + PIN_ERR);
     if (bad[3] > 0) FAIL(c, "member %d: needs 2..%d stations, dlsMax > 0 and length > 0", bad[3] - 1, GEOM_MAX_STATIONS);
     if (bad[3] < 0) FAIL(c, "build_designs: member %d is MacCamy-Fuchs but no wave numbers were given", -bad[3] - 1);
     if (bad[0]) FAIL(c, "member %d: cap/bulkhead layout not supported (the reference raises here too)", bad[0] - 1);
     if (bad[1]) FAIL(c, "design %d: ballast trim needs some ballast volume", bad[1] - 1);
-    const size_t nStrips = (size_t)c->pin[0], nRows = (size_t)c->pin[1];
-    const int maxS = (int)c->pin[2];
-    if (stripOffsets) memcpy(stripOffsets, c->pin + 8, ((size_t)nDesign + 1) * sizeof(int64_t));
-    c->hS.resize((size_t)nDesign);
-    for (int d = 0; d < nDesign; d++) c->hS[(size_t)d] = (int)(c->pin[8 + d + 1] - c->pin[8 + d]);
-    std::vector<void *> &tmp = J.tmp;
+    J.nStrips = (size_t)c->pin[PIN_TOT]; J.nRows = (size_t)c->pin[PIN_TOT + 1]; J.maxS = (int)c->pin[PIN_TOT + 2];
+    const long long *off = c->pin + PIN_OFF;
+    if (stripOffsets) memcpy(stripOffsets, off, ((size_t)J.nDesign + 1) * sizeof(int64_t));
+    c->hS.resize((size_t)J.nDesign);
+    for (int d = 0; d < J.nDesign; d++) c->hS[(size_t)d] = (int)(off[d + 1] - off[d]);
+    return 0;
+}
+static int enqueue_generation(raftx_ctx *c, hipStream_t sGen, int kind) {
+    BuildJob &J = c->job;
+    GeomArgs &A = J.A;
+    const int nDesign = J.nDesign, nw = J.nw;
+    const size_t nRows = J.nRows;
     // RAFTX_FUSED_GEN=1: sweep crossings build their tables inside the fused kernel (raftx_fusedgen.h).  Measured and NOT
     // the default (profiles/r06_experiments/fused_generation_ab.txt): bit-identical, the gap between two fused kernels
     // shrinks from 0.30 to 0.09 ms, but the kernel grows by 0.50 ms -- the ~50 us of dependent loads per design are not
     // hidden by the seven other waves of the CU (each is bound by its own dependency chains, not by issue slots).
     const char *fg_ = getenv("RAFTX_FUSED_GEN");          // (read per call: tests switch it inside one process)
     const bool fused_gen = fg_ && atoi(fg_);
-    const bool defer = (crossing & 2) && fused_gen && nDesign > 0 && nRows == 0;
+    const bool defer = (kind & GEN_MAY_DEFER) && fused_gen && nDesign > 0 && nRows == 0;
     J.gen_deferred = false;
-    // the ABI copy of the strip records (raftx_fetch_strips) is for raftx_build_designs; a sweep crossing never
-    // fetches it: 137 MB of stores per 10 000 designs less between two fused kernels (k_geom_design checks the pointer)
-    A.abi = nullptr;
-    if ((!crossing && dev_alloc(c, c->design_allocs, nStrips * NF, &A.abi)) || dev_alloc(c, c->design_allocs, nStrips * DS_N, &A.ds) ||
-        dev_alloc(c, c->design_allocs, nStrips, &A.dsi) || dev_alloc(c, c->design_allocs, nRows * 3, &A.mcfaux) ||
-        dev_alloc(c, c->design_allocs, nRows * 2 * (size_t)nw, &A.cm) ||
-        dev_alloc(c, c->design_allocs, (size_t)nDesign * 36, &A.A))
-        return -2;
-    (void)tmp;
-    const size_t gd_lds = geom_design_lds(maxS, (int)J.maxSta, (int)J.maxMem);
+    const size_t gd_lds = geom_design_lds(J.maxS, (int)J.maxSta, (int)J.maxMem);
     if (gd_lds > 160 * 1024)
-        FAIL(c, "build_designs: a design has %d submerged strips (at most %d supported)", maxS, (int)((160 * 1024 - 16) / (8 * (GD_ROW + 2) + 12)));
+        FAIL(c, "build_designs: a design has %d submerged strips (at most %d supported)", J.maxS, (int)((160 * 1024 - 16) / (8 * (GD_ROW + 2) + 12)));
     if (gd_lds > 64 * 1024)
         HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void *>(k_geom_design), hipFuncAttributeMaxDynamicSharedMemorySize, (int)gd_lds));
     J.gen_lds = gd_lds;
@@ -1501,7 +1500,7 @@ static int build_phase2(raftx_ctx *c, int64_t *stripOffsets, hipStream_t sGen = 
         // design's matrices up itself -- one kernel and one launch gap less on the path between two fused kernels (same
         // additions in the same order: bit-identical).  RAFTX_ADDUP_KERNEL=1 keeps k_geom_addup.
         static const bool addup_kernel = getenv("RAFTX_ADDUP_KERNEL") && atoi(getenv("RAFTX_ADDUP_KERNEL"));
-        A.addup_in_design = ((crossing & 4) && !addup_kernel && nRows == 0 && !A.abi) ? 1 : 0;
+        A.addup_in_design = ((kind & GEN_PIPELINED) && !addup_kernel && nRows == 0 && !A.abi) ? 1 : 0;
         if (A.addup_in_design && J.reduce_stream) HIPCHK(c, hipStreamWaitEvent(sGen, c->evRed, 0));
         launch_design(c, sGen);
         if (!A.addup_in_design) {
@@ -1515,40 +1514,54 @@ static int build_phase2(raftx_ctx *c, int64_t *stripOffsets, hipStream_t sGen = 
         hipLaunchKernelGGL(k_geom_mcf, dim3((unsigned)nRows, (unsigned)((nw + 63) / 64)), dim3(64), 0, sGen, A, (int64_t)nRows);
     HIPCHK(c, hipEventRecord(c->evG1, sGen));
     if (sGen != c->stream) HIPCHK(c, hipStreamWaitEvent(c->stream, c->evG1, 0));
+    return 0;
+}
+// the finished job's tables become the designs of the ctx: what the solves (c->T) and the fetch calls (c->g_*) read
+static void publish_tables(raftx_ctx *c) {
+    const BuildJob &J = c->job;
+    const GeomArgs &A = J.A;
     DevTables &T = c->T;
-    T.nDesign = nDesign;
-    T.off = A.off;
-    T.ds = A.ds;
-    T.dsi = A.dsi;
-    T.M0 = J.M0d;
-    T.C0 = J.C0d;
-    T.B0 = J.B0d;
-    T.MBw = J.MBwd;
-    T.cmoff = nRows ? A.cmoff : nullptr;
-    T.cm = nRows ? A.cm : nullptr;
-    c->maxS = maxS;
-    c->nw_designs = nw;
-    c->have_designs = true;
-    c->g_n = nDesign;
-    c->g_nStrips = nStrips;
-    c->g_nRows = nRows;
-    c->g_abi = A.abi;
-    c->g_cm = A.cm;
+    T.nDesign = J.nDesign; T.off = A.off; T.ds = A.ds; T.dsi = A.dsi;
+    T.M0 = J.M0d; T.C0 = J.C0d; T.B0 = J.B0d; T.MBw = J.MBwd;
+    T.cmoff = J.nRows ? A.cmoff : nullptr; T.cm = J.nRows ? A.cm : nullptr;
+    c->maxS = J.maxS; c->nw_designs = J.nw; c->have_designs = true;
+    c->g_n = J.nDesign; c->g_nStrips = J.nStrips; c->g_nRows = J.nRows;
+    c->g_abi = A.abi; c->g_cm = A.cm;
     c->g_A = A.A; c->g_Ch = A.Ch; c->g_Wh = A.Wh; c->g_props = A.props;
     c->g_Ms = A.Ms; c->g_Cs = A.Cs; c->g_Ws = A.Ws;
+}
+static int build_phase2(raftx_ctx *c, int64_t *stripOffsets, hipStream_t sGen = nullptr, int kind = 0) {
+    RangeScope range_("build phase 2: wait for totals, strip tables + statics (enqueue)");
+    BuildJob &J = c->job;
+    GeomArgs &A = J.A;
+    if (!J.active) FAIL(c, "build_designs: phase 2 without phase 1");
+    if (int rc = wait_totals(c, stripOffsets)) return rc;
+    // the ABI copy of the strip records (raftx_fetch_strips) is for raftx_build_designs; a sweep crossing never
+    // fetches it: 137 MB of stores per 10 000 designs less between two fused kernels (k_geom_design checks the pointer)
+    std::vector<void *> &keep = c->design_allocs;
+    A.abi = nullptr;
+    if ((!kind && pool_alloc(c, keep, J.nStrips * NF, &A.abi)) || pool_alloc(c, keep, J.nStrips * DS_N, &A.ds) ||
+        pool_alloc(c, keep, J.nStrips, &A.dsi) || pool_alloc(c, keep, J.nRows * 3, &A.mcfaux) ||
+        pool_alloc(c, keep, J.nRows * 2 * (size_t)J.nw, &A.cm) || pool_alloc(c, keep, (size_t)J.nDesign * 36, &A.A))
+        return -2;
+    if (int rc = enqueue_generation(c, sGen, kind)) return rc;
+    publish_tables(c);
     return 0;
+}
+// a build that will not be finished, or has been (the caller has drained the device): its scratch back to the pool
+static void build_abandon(raftx_ctx *c) {
+    free_list(c, c->job.tmp);
+    c->job.active = false;
 }
 // kernel time of a finished build (both phases), and its scratch back to the pool
 static int build_retire(raftx_ctx *c, double *ms_out) {
-    BuildJob &J = c->job;
     float a = 0.f, b = 0.f;
-    if (J.active) {
+    if (c->job.active) {
         HIPCHK(c, hipEventElapsedTime(&a, c->evG2, c->evG3));
         HIPCHK(c, hipEventElapsedTime(&b, c->evG0, c->evG1));
     }
     if (ms_out) *ms_out = (double)a + (double)b;
-    free_list(c, J.tmp);
-    J.active = false;
+    build_abandon(c);
     return 0;
 }
 
@@ -1561,13 +1574,17 @@ extern "C" int raftx_build_designs(raftx_ctx *c, int nDesign, const int64_t *mem
     if (!stripOffsets) FAIL(c, "build_designs: bad arguments");
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    int rc = build_phase1(c, c->stream, c->stream, 0, nDesign, memberOff, members, stationOff, stations, capOff, caps, pose, rho,
-                          g, nw, k, add_mask, M0, B0, C0, MBw, Fz_moor, nullptr);
+    const BuildSource src{memberOff, stationOff, capOff, members, stations, caps, pose, M0, B0, C0, MBw, Fz_moor, k, rho, g, nw, add_mask};
+    int rc = check_source(c, src, nDesign, "build_designs", "bad arguments");
+    if (!rc && (nw < 1 || nw > MAX_NW)) {             // (not FAIL: the cleanup below has to follow)
+        snprintf(c->err, sizeof(c->err), "build_designs: nw=%d outside 1..%d", nw, MAX_NW);
+        rc = -1;
+    }
+    if (!rc) rc = build_phase1(c, c->stream, c->stream, src, 0, nDesign);
     if (!rc) rc = build_phase2(c, stripOffsets);
     const hipError_t e = hipStreamSynchronize(c->stream);     // host buffers may be released after return
     if (rc) {
-        free_list(c, c->job.tmp);
-        c->job.active = false;
+        build_abandon(c);
         c->have_designs = false;
         return rc;
     }
@@ -1612,9 +1629,9 @@ extern "C" int raftx_fetch_statics(raftx_ctx *c, double *A_morison, double *C_hy
 
 // The sea-state tables of one set of cases into device memory of ctx `c` (allocations into `bag`, fields into `T`), copied
 // on `st`, which has drained when this returns (the depth constants are host temporaries).
-static int upload_case_tables(raftx_ctx *c, hipStream_t st, std::vector<void *> &bag, DevTables &T, int nCase, int nHead, int nw,
-                              const double *w, const double *k, double depth, double rho, double g, const double *zeta,
-                              const double *beta) {
+static int upload_case_tables(raftx_ctx *c, hipStream_t st, std::vector<void *> &bag, DevTables &T, const SeaStates &sea) {
+    const int nCase = sea.nCase, nHead = sea.nHead, nw = sea.nw;
+    const double *k = sea.k, depth = sea.depth;
     // per-bin depth constants, computed once on the host in full libm precision.  The kernels derive
     // the depth regime (k == 0 / deep / finite) from k themselves, with the same rule.
     std::vector<double> csh(nw), cch(nw);
@@ -1628,19 +1645,15 @@ static int upload_case_tables(raftx_ctx *c, hipStream_t st, std::vector<void *> 
             cch[i] = 1.0 / (1.0 + e2kh);
         }
     }
-    T.nCase = nCase;
-    T.nHead = nHead;
-    T.nw = nw;
-    T.depth = depth;
-    T.rho = rho;
-    T.g = g;
+    T.nCase = nCase; T.nHead = nHead; T.nw = nw;
+    T.depth = depth; T.rho = sea.rho; T.g = sea.g;
     int rc = 0;
-    rc |= upload_on(c, st, bag, w, (size_t)nw, &T.w);
+    rc |= upload_on(c, st, bag, sea.w, (size_t)nw, &T.w);
     rc |= upload_on(c, st, bag, k, (size_t)nw, &T.k);
     rc |= upload_on(c, st, bag, csh.data(), (size_t)nw, &T.csh);
     rc |= upload_on(c, st, bag, cch.data(), (size_t)nw, &T.cch);
-    rc |= upload_on(c, st, bag, zeta, (size_t)nCase * nHead * nw, &T.zeta);
-    rc |= upload_on(c, st, bag, beta, (size_t)nCase * nHead, &T.beta);
+    rc |= upload_on(c, st, bag, sea.zeta, (size_t)nCase * nHead * nw, &T.zeta);
+    rc |= upload_on(c, st, bag, sea.beta, (size_t)nCase * nHead, &T.beta);
     const hipError_t e = hipStreamSynchronize(st);        // also on failure: csh / cch go out of scope
     if (rc) return -2;
     HIPCHK(c, e);
@@ -1658,7 +1671,7 @@ extern "C" int raftx_upload_cases(raftx_ctx *c, int nCase, int nHead, int nw, co
     free_list(c, c->case_allocs);
     c->have_cases = false;
     c->bem_ready = false;
-    if (int rc = upload_case_tables(c, c->stream, c->case_allocs, c->T, nCase, nHead, nw, w, k, depth, rho, g, zeta, beta)) return rc;
+    if (int rc = upload_case_tables(c, c->stream, c->case_allocs, c->T, SeaStates{nCase, nHead, nw, w, k, depth, rho, g, zeta, beta})) return rc;
     c->have_cases = true;
     return 0;
 }
@@ -2670,8 +2683,8 @@ extern "C" int raftx_dense_resident(raftx_ctx *c, int nSet, int n, int nw, const
     if (!w || !M || !B || !C) FAIL(c, "dense_resident: bad arguments");
     if (dense_check(c, "dense_resident", nSet, n, 1, nw)) return -1;
     const size_t nn = (size_t)n * n, nM = (size_t)nSet * nn * ((freq_mask & 1) ? nw : 1), nB = (size_t)nSet * nn * ((freq_mask & 2) ? nw : 1);
-    if (dev_alloc(c, R.allocs, (size_t)nw, &R.w) || dev_alloc(c, R.allocs, nM, &R.M) || dev_alloc(c, R.allocs, nB, &R.B) ||
-        dev_alloc(c, R.allocs, (size_t)nSet * nn, &R.C))
+    if (pool_alloc(c, R.allocs, (size_t)nw, &R.w) || pool_alloc(c, R.allocs, nM, &R.M) || pool_alloc(c, R.allocs, nB, &R.B) ||
+        pool_alloc(c, R.allocs, (size_t)nSet * nn, &R.C))
         return -2;
     H2D(c, R.w, w, nw * sizeof(double));
     H2D(c, R.M, M, nM * sizeof(double));
@@ -3190,34 +3203,26 @@ static void slot_release_cases(raftx_ctx *c, SweepSlot &S) {
 static int sweep_fail_drain(raftx_ctx *c, SweepSlot &S, int rc) {
     (void)hipDeviceSynchronize();
     for (raftx_ctx *sub : S.blk)
-        if (sub) {
-            free_list(sub, sub->job.tmp);
-            sub->job.active = false;
-        }
+        if (sub) build_abandon(sub);
     slot_release_cases(c, S);
     return rc;
 }
 
-static int sweep_prepare_impl(raftx_ctx *c, int slot, int nDesign, const int64_t *memberOff, const double *members,
-                              const int64_t *stationOff, const double *stations, const int64_t *capOff,
-                              const double *caps, const double *pose, double rho, double g, int add_mask,
-                              const double *M0, const double *B0, const double *C0, const double *Fz_moor, int nCase,
-                              int nHead, int nw, const double *w, const double *k, double depth, double rho_wave,
-                              double g_wave, const double *zeta, const double *beta, int nIter, double tol,
-                              double XiStart, int nChunk, double *sd, int32_t *niter, int32_t *flags,
-                              raftx_c128 *Xi, int64_t *stripOffsets, const VariantSrc *var) {
+// what the solve of a crossing is given: fixed-point settings, block count, and the caller's outputs
+struct SweepRun { int nIter; double tol, XiStart; int nChunk; double *sd; int32_t *niter, *flags; raftx_c128 *Xi; int64_t *stripOffsets; };
+static int sweep_prepare_impl(raftx_ctx *c, int slot, int nDesign, const BuildSource &src, const SeaStates &sea, const SweepRun &run) {
     RangeScope range_("raftx_sweep_prepare: descriptor H2D + member pass (enqueue)");
     if (!c) return -1;
     if (slot < 0 || slot >= RAFTX_NSLOT) FAIL(c, "sweep_prepare: slot must be 0 .. %d", RAFTX_NSLOT - 1);
     SweepSlot &S = c->slots[slot];
     if (S.busy || S.prepared) FAIL(c, "sweep_prepare: slot %d is still in flight (call raftx_sweep_wait first)", slot);
-    if (nDesign < 0 || !memberOff || (!members && !var) || !stationOff || (!stations && !var) || !M0 || !B0 || !C0)
-        FAIL(c, "sweep_stats: bad design arguments");
+    const int nCase = sea.nCase, nHead = sea.nHead, nw = sea.nw;
+    const double *w = sea.w, *k = sea.k, *zeta = sea.zeta, *beta = sea.beta;
+    if (int rc = check_source(c, src, nDesign, "sweep_stats", "bad design arguments")) return rc;
     if (nCase < 1 || nHead < 1 || nw < 1 || !w || !k || !zeta || !beta) FAIL(c, "sweep_stats: bad sea-state arguments");
-    if (!sd || !niter || !flags) FAIL(c, "sweep_stats: std, niter and flags are required");
-    if (!var && (capOff == nullptr) != (caps == nullptr)) FAIL(c, "sweep_stats: capOff and caps must be given together");
-    if (nIter < 0) FAIL(c, "sweep_stats: nIter < 0");
-    if (nChunk > 64) nChunk = 64;
+    if (!run.sd || !run.niter || !run.flags) FAIL(c, "sweep_stats: std, niter and flags are required");
+    if (run.nIter < 0) FAIL(c, "sweep_stats: nIter < 0");
+    const int nChunk = std::min(run.nChunk, 64);
     HIPCHK(c, hipSetDevice(c->device));
     S.t0 = std::chrono::steady_clock::now();
     auto since = [&]() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - S.t0).count(); };
@@ -3242,7 +3247,7 @@ static int sweep_prepare_impl(raftx_ctx *c, int slot, int nDesign, const int64_t
     {
         std::vector<double> key;
         key.reserve((size_t)nw * 2 + (size_t)nCase * nHead * (nw + 1) + 6);
-        key.push_back(nCase); key.push_back(nHead); key.push_back(nw); key.push_back(depth); key.push_back(rho_wave); key.push_back(g_wave);
+        key.push_back(nCase); key.push_back(nHead); key.push_back(nw); key.push_back(sea.depth); key.push_back(sea.rho); key.push_back(sea.g);
         key.insert(key.end(), w, w + nw);
         key.insert(key.end(), k, k + nw);
         key.insert(key.end(), zeta, zeta + (size_t)nCase * nHead * nw);
@@ -3258,7 +3263,7 @@ static int sweep_prepare_impl(raftx_ctx *c, int slot, int nDesign, const int64_t
             CaseSet &cs = c->csets[idle];
             cs.key.clear();
             free_list(c, cs.allocs);                      // users == 0: every crossing that read it has been waited for
-            if (int rc = upload_case_tables(c, c->sCopy, cs.allocs, cs.T, nCase, nHead, nw, w, k, depth, rho_wave, g_wave, zeta, beta)) {
+            if (int rc = upload_case_tables(c, c->sCopy, cs.allocs, cs.T, sea)) {
                 free_list(c, cs.allocs);
                 return rc;
             }
@@ -3274,42 +3279,41 @@ static int sweep_prepare_impl(raftx_ctx *c, int slot, int nDesign, const int64_t
     const std::vector<int> &bnd = S.bnd;
     const size_t nB = bnd.size() - 1;
     S.dw = nw > 1 ? w[1] - w[0] : w[0];
-    S.nIter = nIter; S.tol = tol; S.XiStart = XiStart;
+    S.nIter = run.nIter; S.tol = run.tol; S.XiStart = run.XiStart;
     S.blk.assign(nB, nullptr);
     std::vector<raftx_ctx *> &blk = S.blk;
     S.nCase = nCase; S.nHead = nHead; S.nw = nw;
-    S.sd = sd; S.niter = niter; S.flags = flags; S.Xi = Xi; S.stripOffsets = stripOffsets;
+    S.sd = run.sd; S.niter = run.niter; S.flags = run.flags; S.Xi = run.Xi; S.stripOffsets = run.stripOffsets;
     S.tl[0] = since();
     // the slot's previous crossing has been waited for: its tables and offset arrays are free
     free_list(c, S.allocs);
     S.modal.on = false;
-    // ---- the batch's offset arrays: one upload, shared by the blocks
-    DevOffsets dOff{nullptr, nullptr, nullptr};
+    // ---- the batch's offset arrays: one upload, shared by the blocks; its wave numbers are those of the sea-state set
+    S.p1 = src;
+    S.p1.k_dev = CT.k;
     {
-        const int64_t nMemberAll = memberOff[nDesign];
+        const int64_t nMemberAll = src.memberOff[nDesign];
         if (nMemberAll < 0) {
             slot_release_cases(c, S);
             FAIL(c, "sweep_stats: member offsets not monotone");
         }
-        int rc = upload_on(c, c->sCopy, S.allocs, memberOff, (size_t)nDesign + 1, &dOff.memberOff);
-        rc |= upload_on(c, c->sCopy, S.allocs, stationOff, (size_t)nMemberAll + 1, &dOff.stationOff);
-        if (capOff) rc |= upload_on(c, c->sCopy, S.allocs, capOff, (size_t)nMemberAll + 1, &dOff.capOff);
+        DevOffsets &dOff = S.p1.dOff;
+        int rc = upload_on(c, c->sCopy, S.allocs, src.memberOff, (size_t)nDesign + 1, &dOff.memberOff);
+        rc |= upload_on(c, c->sCopy, S.allocs, src.stationOff, (size_t)nMemberAll + 1, &dOff.stationOff);
+        if (src.capOff) rc |= upload_on(c, c->sCopy, S.allocs, src.capOff, (size_t)nMemberAll + 1, &dOff.capOff);
         if (rc) return sweep_fail_drain(c, S, -2);
     }
     // ---- phase 1: H2D on sCopy, member pass + scans on sPrep.  Every block here -- except for an isolated crossing cut into
     // slabs (responses wanted, nothing else in flight): there only the first two; raftx_sweep_launch enqueues the others one
     // block ahead of the block it launches.  (The ordinary streams share hardware queues: with every block's copies queued
     // first, the first slab's generation sat behind 1.7 ms of uploads -- profiles/r04_iso_timeline.txt.)
-    S.p1 = {memberOff, stationOff, capOff, members, stations, caps, pose, M0, B0, C0, Fz_moor, k, rho, g, add_mask, dOff,
-            var ? *var : VariantSrc{nullptr, nullptr}};
-    const size_t nFirst = (Xi && nB > 2 && !others_in_flight(c, slot)) ? 2 : nB;
+    const size_t nFirst = (run.Xi && nB > 2 && !others_in_flight(c, slot)) ? 2 : nB;
     for (size_t b = 0; b < nB; b++)
         if (block_ctx(c, slot, b, &blk[b])) return sweep_fail_drain(c, S, -1);
     for (size_t b = 0; b < nFirst; b++) {
         raftx_ctx *sub = blk[b];
         const int lo = bnd[b], n = bnd[b + 1] - lo;
-        const int rc = build_phase1(sub, c->sCopy, c->sPrep, lo, n, memberOff, members, stationOff, stations, capOff, caps, pose,
-                                    rho, g, nw, k, add_mask, M0, B0, C0, nullptr, Fz_moor, &S.p1.dOff, CT.k, var);
+        const int rc = build_phase1(sub, c->sCopy, c->sPrep, S.p1, lo, n);
         if (rc) {
             snprintf(c->err, sizeof(c->err), "sweep_stats (block %zu): %s", b, sub->err);
             return sweep_fail_drain(c, S, rc);
@@ -3329,9 +3333,9 @@ extern "C" int raftx_sweep_prepare(raftx_ctx *c, int slot, int nDesign, const in
                                   double g_wave, const double *zeta, const double *beta, int nIter, double tol,
                                   double XiStart, int nChunk, double *sd, int32_t *niter, int32_t *flags,
                                   raftx_c128 *Xi, int64_t *stripOffsets) {
-    return sweep_prepare_impl(c, slot, nDesign, memberOff, members, stationOff, stations, capOff, caps, pose, rho, g, add_mask, M0, B0,
-                              C0, Fz_moor, nCase, nHead, nw, w, k, depth, rho_wave, g_wave, zeta, beta, nIter, tol, XiStart, nChunk, sd,
-                              niter, flags, Xi, stripOffsets, nullptr);
+    const BuildSource src{memberOff, stationOff, capOff, members, stations, caps, pose, M0, B0, C0, nullptr, Fz_moor, k, rho, g, nw, add_mask};
+    return sweep_prepare_impl(c, slot, nDesign, src, SeaStates{nCase, nHead, nw, w, k, depth, rho_wave, g_wave, zeta, beta},
+                              SweepRun{nIter, tol, XiStart, nChunk, sd, niter, flags, Xi, stripOffsets});
 }
 
 // ---- parametric variants of one base unit (include/raftx.h; raft/parametersweep.py:39-87)
@@ -3465,11 +3469,11 @@ extern "C" int raftx_sweep_prepare_variants(raftx_ctx *c, int slot, int nDesign,
             FAIL(c, "sweep_prepare_variants: batches of variants in flight together must have the same size (%d in flight, %d asked)",
                  P.cachedN, nDesign);
     variant_offsets(P, nDesign);
-    const VariantSrc var{&P, params};
-    return sweep_prepare_impl(c, slot, nDesign, P.memberOff.data(), nullptr, P.stationOff.data(), nullptr,
-                              P.has_caps ? P.capOff.data() : nullptr, nullptr, pose, rho, g, add_mask, M0, B0, C0, Fz_moor, nCase, nHead,
-                              nw, w, k, depth, rho_wave, g_wave, zeta, beta, nIter, tol, XiStart, nChunk, sd, niter, flags, Xi,
-                              stripOffsets, &var);
+    BuildSource src{P.memberOff.data(), P.stationOff.data(), P.has_caps ? P.capOff.data() : nullptr, nullptr, nullptr, nullptr,
+                    pose, M0, B0, C0, nullptr, Fz_moor, k, rho, g, nw, add_mask};
+    src.var = {&P, params};
+    return sweep_prepare_impl(c, slot, nDesign, src, SeaStates{nCase, nHead, nw, w, k, depth, rho_wave, g_wave, zeta, beta},
+                              SweepRun{nIter, tol, XiStart, nChunk, sd, niter, flags, Xi, stripOffsets});
 }
 
 // The eigen analysis of one block of a crossing (raftx_sweep_modal) on stream st, which is behind whatever wrote the
@@ -3627,10 +3631,7 @@ extern "C" int raftx_sweep_launch(raftx_ctx *c, int slot) {
         int rc = 0;
         if (S.next_p1 < nB && S.next_p1 <= b + 1) {                     // deferred phase 1: keep one block's upload ahead
             const size_t bn = S.next_p1++;
-            rc = build_phase1(blk[bn], c->sCopy, c->sPrep, bnd[bn], bnd[bn + 1] - bnd[bn], S.p1.memberOff, S.p1.members,
-                              S.p1.stationOff, S.p1.stations, S.p1.capOff, S.p1.caps, S.p1.pose, S.p1.rho, S.p1.g, S.nw, S.p1.k,
-                              S.p1.add_mask, S.p1.M0, S.p1.B0, S.p1.C0, nullptr, S.p1.Fz_moor, &S.p1.dOff, c->csets[S.cset].T.k,
-                              &S.p1.var);
+            rc = build_phase1(blk[bn], c->sCopy, c->sPrep, S.p1, bnd[bn], bnd[bn + 1] - bnd[bn]);
             if (rc) snprintf(sub->err, sizeof(sub->err), "%s", blk[bn]->err);
         }
         // A crossing launched while another one is solving generates its tables on the generation stream: its member pass ran
@@ -3649,7 +3650,8 @@ extern "C" int raftx_sweep_launch(raftx_ctx *c, int slot) {
         S.tlb.push_back(since());
         // (a crossing: no ABI copy of the strip records; with RAFTX_FUSED_GEN=1 the tables are left to the fused kernel itself,
         // raftx_fusedgen.h -- build_phase2 / solve_enqueue decide)
-        if (!rc) rc = build_phase2(sub, nullptr, pipelined ? c->sGen : nullptr, 1 | ((nCase == 1 && !slab_mode) ? 2 : 0) | (pipelined ? 4 : 0));
+        const int kind = GEN_CROSSING | ((nCase == 1 && !slab_mode) ? GEN_MAY_DEFER : 0) | (pipelined ? GEN_PIPELINED : 0);
+        if (!rc) rc = build_phase2(sub, nullptr, pipelined ? c->sGen : nullptr, kind);
         S.tlb.push_back(since());
         if (!rc) {                                                      // the sea states this crossing was prepared with
             DevTables &T = sub->T;
@@ -3724,8 +3726,7 @@ extern "C" int raftx_sweep_cancel(raftx_ctx *c, int slot) {
     for (raftx_ctx *sub : S.blk)
         if (sub) {
             if (sub->sAux && e == hipSuccess) e = hipStreamSynchronize(sub->sAux);
-            free_list(sub, sub->job.tmp);
-            sub->job.active = false;
+            build_abandon(sub);
         }
     S.prepared = false;
     S.modal.on = false;
@@ -3753,10 +3754,7 @@ extern "C" int raftx_sweep_wait(raftx_ctx *c, int slot, double *timing_ms) {
     if (es != hipSuccess) {
         (void)hipDeviceSynchronize();
         slot_release_cases(c, S);
-        for (raftx_ctx *sub : S.blk) {
-            free_list(sub, sub->job.tmp);
-            sub->job.active = false;
-        }
+        for (raftx_ctx *sub : S.blk) build_abandon(sub);
         HIPCHK(c, es);
     }
     double tb = 0, ts = 0, tst = 0;
