@@ -179,7 +179,7 @@ int raftx_bem_excitation(raftx_ctx *ctx, int nHeadBEM, const double *headings_de
  *   std[d,c,j]   = sqrt(0.5 * sum_{ih,w} |Xi[d,c,ih,j,w]|^2)           (j = 3..5 in degrees, :2332-2354)
  *   psd[d,c,j,w] = sum_ih 0.5 |Xi[d,c,ih,j,w]|^2 / dw                   (optional, may be NULL)
  * so that a sweep can return ~48 B per (design, case) instead of 19 KB.  std [nDesign,nCase,6],
- * psd [nDesign,nCase,6,nw]; dw = w[1]-w[0] (raft_fowt.py:169). */
+ * psd [nDesign,nCase,6,nw]; dw = w[1]-w[0] (raft_fowt.py:169) must be > 0 (anything else, NaN included, is an error). */
 int raftx_motion_stats(raftx_ctx *ctx, double dw, double *std, double *psd);
 
 /* Restart / export of the fixed point's linearisation point, for the re-entry of raft_model.py:1108-1131
@@ -198,7 +198,8 @@ int raftx_fetch_linearisation_point(raftx_ctx *ctx, raftx_c128 *XiLast);
  * This is the getRMS/getPSD pattern of FOWT.saveTurbineOutputs for the nacelle accelerations
  * (raft/raft_fowt.py:2422-2444: hub rows of T, pow = 2) and the quasi-static mooring tensions
  * (:2367-2373: rows of J_moor, pow = 0); raftx_motion_stats is the special case L = diag(1,1,1,deg,deg,deg).
- * L [nDesign,nChan,6], pow [nChan] (0..4), std [nDesign,nCase,nChan], psd [nDesign,nCase,nChan,nw] or NULL. */
+ * L [nDesign,nChan,6], pow [nChan] (0..4), std [nDesign,nCase,nChan], psd [nDesign,nCase,nChan,nw] or NULL; dw must be
+ * > 0 (anything else, NaN included, is an error). */
 int raftx_channel_stats(raftx_ctx *ctx, int nChan, const double *L, const int32_t *pow, double dw,
                         double *std, double *psd);
 
@@ -210,7 +211,7 @@ int raftx_channel_stats(raftx_ctx *ctx, int nChan, const double *L, const int32_
  * (p = 0), inertial reaction -m a_CG h - I_CG (-w^2 Xi_pitch) (p = 2) and the aero reaction
  * -(-w^2 A_aero(w) + i w B_aero(w)) z^2 Xi_pitch (Gw); host feeder: raft_amd/dropin.py tower_base_rows.
  * L [nDesign,nChan,3,6] real; Gw [nDesign,nChan,6,nw] complex or NULL; std [nDesign,nCase,nChan];
- * psd [nDesign,nCase,nChan,nw] or NULL. */
+ * psd [nDesign,nCase,nChan,nw] or NULL; dw must be > 0 (anything else, NaN included, is an error). */
 int raftx_channel_stats_poly(raftx_ctx *ctx, int nChan, const double *L, const raftx_c128 *Gw, double dw,
                              double *std, double *psd);
 
@@ -224,7 +225,8 @@ int raftx_channel_stats_poly(raftx_ctx *ctx, int nChan, const double *L, const r
  * stiffness, Fi_base = -(Kf Xi_internal)[base node] (:2540-2601), all linear in the reduced response through the rows of T
  * (host feeder: raft_amd/dropin.py general_output_rows).
  * w [nw]; L [nChan,3,nDof] real; Gw [nChan,nDof,nw] complex or NULL; Xi [nResp,nDof,nw] (nResp = wave headings + 1);
- * std [nChan]; psd [nChan,nw] or NULL.  Independent of the upload_* state of the ctx. */
+ * std [nChan]; psd [nChan,nw] or NULL; dw must be > 0 (anything else, NaN included, is an error).  Independent of the
+ * upload_* state of the ctx. */
 int raftx_response_stats(raftx_ctx *ctx, int nChan, int nDof, int nResp, int nw, const double *w, const double *L,
                          const raftx_c128 *Gw, const raftx_c128 *Xi, double dw, double *std, double *psd);
 

@@ -2531,6 +2531,7 @@ extern "C" int raftx_response_stats(raftx_ctx *c, int nChan, int nDof, int nResp
     RangeScope range_("raftx_response_stats: linear channels of a caller-held response");
     if (!c) return -1;
     if (nChan < 0 || nDof < 1 || nResp < 1 || nw < 1 || !w || (nChan && !L) || !Xi || !sd) FAIL(c, "response_stats: bad arguments");
+    if (!(dw > 0.0)) FAIL(c, "response_stats: dw must be positive");
     if (!nChan) return 0;
     HIPCHK(c, hipSetDevice(c->device));
     Scratch sc(c);
