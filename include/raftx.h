@@ -351,7 +351,9 @@ int raftx_qtf_slender_rows(raftx_ctx *ctx, int nSet, int nw2, const double *w2, 
  * fill_value=0), then  f[j,mu] = 4 sqrt(sum_i S0[i] S0[i+mu] |Q_j(w_i, w_{i+mu})|^2) dw,
  * f_mean[j] = 2 sum_i S0[i] Re Q_j(w_i,w_i) dw, and the one-bin shift of :2241-2245.
  * qtf [nSet,nw2,nw2,6] host buffer, or NULL to use the QTFs left resident by the last raftx_qtf_slender
- * call on this ctx (same nSet, nw2).  S0 [nSet,nw]; f_mean [nSet,6]; f [nSet,6,nw] (real amplitudes). */
+ * call on this ctx (same nSet, nw2).  S0 [nSet,nw]; f_mean [nSet,6]; f [nSet,6,nw] (real amplitudes).
+ * nw2 must be >= 2, and nw small enough for the per-bin interpolation table of one workgroup,
+ * 8 (nw + (nw+1)/2 + 8) bytes <= 65536 (nw <= 5456): anything else is an error, before any launch. */
 int raftx_qtf_force(raftx_ctx *ctx, int nSet, int nw2, const double *w2, const raftx_c128 *qtf,
                     int nw, const double *w, double dw, const double *S0, double *f_mean, double *f);
 

@@ -22,15 +22,21 @@ fixed body, heading 30 deg) and against live-reference QTFs with body motions (t
 import numpy as np
 
 
-def _wave_kin(beta, w, k, h, r, rho, g):
+def _real(dtype):
+    """the real type that goes with the complex ``dtype`` (complex128 -> float64, clongdouble -> longdouble)"""
+    return np.finfo(np.dtype(dtype)).dtype.type
+
+
+def _wave_kin(beta, w, k, h, r, rho, g, dtype=np.complex128):
     """helpers.py:188-236 with zeta0 = 1: u [3,nw], ud [3,nw], pDyn [nw]."""
+    rd = _real(dtype)
     zeta = np.exp(-1j * (k * (np.cos(beta) * r[0] + np.sin(beta) * r[1])))
     z = r[2]
     nw = len(w)
-    u = np.zeros((3, nw), dtype=complex)
-    pd = np.zeros(nw, dtype=complex)
+    u = np.zeros((3, nw), dtype=dtype)
+    pd = np.zeros(nw, dtype=dtype)
     if z <= 0:
-        Sh, Ch, Cc = np.empty(nw), np.empty(nw), np.empty(nw)
+        Sh, Ch, Cc = np.empty(nw, dtype=rd), np.empty(nw, dtype=rd), np.empty(nw, dtype=rd)
         for i in range(nw):
             if k[i] == 0.0:
                 Sh[i], Ch[i], Cc[i] = 1.0, 99999.0, 99999.0
@@ -48,10 +54,10 @@ def _wave_kin(beta, w, k, h, r, rho, g):
     return u, 1j * w * u, pd
 
 
-def _grad_u1(w, k, beta, h, r):
+def _grad_u1(w, k, beta, h, r, dtype=np.complex128):
     """helpers.py:239-277: [3,3,nw]."""
     nw = len(w)
-    grad = np.zeros((3, 3, nw), dtype=complex)
+    grad = np.zeros((3, 3, nw), dtype=dtype)
     z = r[2]
     cosBeta, sinBeta = np.cos(np.deg2rad(beta)), np.sin(np.deg2rad(beta))        # (sic)
     if z > 0:
@@ -79,10 +85,10 @@ def _grad_u1(w, k, beta, h, r):
     return grad
 
 
-def _grad_pres1st(k, beta, h, r, rho, g):
+def _grad_pres1st(k, beta, h, r, rho, g, dtype=np.complex128):
     """helpers.py:283-308: [3,nw]."""
     nw = len(k)
-    grad = np.zeros((3, nw), dtype=complex)
+    grad = np.zeros((3, nw), dtype=dtype)
     z = r[2]
     cosBeta, sinBeta = np.cos(np.deg2rad(beta)), np.sin(np.deg2rad(beta))        # (sic), also in the phase
     if z > 0:
@@ -101,11 +107,11 @@ def _grad_pres1st(k, beta, h, r, rho, g):
     return grad
 
 
-def _pot2nd(w, k, beta, h, r, g, rho):
+def _pot2nd(w, k, beta, h, r, g, rho, dtype=np.complex128):
     """helpers.py:337-373 on the full grid: acc [3,nw,nw], p [nw,nw] (index order [i1,i2])."""
     nw = len(w)
-    acc = np.zeros((3, nw, nw), dtype=complex)
-    p = np.zeros((nw, nw), dtype=complex)
+    acc = np.zeros((3, nw, nw), dtype=dtype)
+    p = np.zeros((nw, nw), dtype=dtype)
     z = r[2]
     if z > 0:
         return acc, p
@@ -157,27 +163,54 @@ def _to6(f3, r, F):
     F[5] += r[0] * f3[1] - r[1] * f3[0]
 
 
-def qtf_slender_body(tab, Xi, beta, w, k, h, rho, g, M_struc, kay=None):
+def _to6_env(f3, r, E):
+    """what _to6 adds, in absolute values: |f_i| for the forces, |r_a| |f_b| per product of the moments."""
+    a, ar = np.abs(f3), np.abs(r)
+    E[0:3] += a
+    E[3] += ar[1] * a[2] + ar[2] * a[1]
+    E[4] += ar[2] * a[0] + ar[0] * a[2]
+    E[5] += ar[0] * a[1] + ar[1] * a[0]
+
+
+def _cross_env(a, b):
+    """sum of |a_i| |b_j| over the two products of every component of a x b (axis 0)"""
+    a, b = np.abs(a), np.abs(b)
+    return np.array([a[1] * b[2] + a[2] * b[1], a[2] * b[0] + a[0] * b[2], a[0] * b[1] + a[1] * b[0]])
+
+
+def qtf_slender_body(tab, Xi, beta, w, k, h, rho, g, M_struc, kay=None, dtype=np.complex128, return_envelope=False):
     """FOWT.calcQTF_slenderBody for one heading: qtf [nw,nw,6] (Hermitian-completed).
     tab: raft_amd.qtf.QtfTable; Xi [6,nw] motion RAOs on the 2nd-order grid (zeros = fixed body);
-    kay: optional [nw,nw,6] Kim & Yue table (upper triangle)."""
+    kay: optional [nw,nw,6] Kim & Yue table (upper triangle).
+    dtype: the complex type everything is evaluated in (np.clongdouble: the extended-precision reference of
+    tests/qtf_reference.py; the inputs are promoted exactly).
+    return_envelope: also return E [nw,nw,6] (real), the sum of the absolute values of every addend accumulated into the
+    QTF -- the five strip force terms as they go through _to6, the cross products of the Pinkster term per product of
+    components, the three parts of the waterline term, |kay| -- mirrored like the QTF: what the rounding error of an
+    evaluation in finite precision is proportional to."""
+    rd = _real(dtype)
+    w, k = np.asarray(w, dtype=rd), np.asarray(k, dtype=rd)
+    beta, h, rho, g = rd(beta), rd(h), rd(rho), rd(g)
     nw = len(w)
-    Xi = np.asarray(Xi, dtype=complex)
-    Q = np.zeros((6, nw, nw), dtype=complex)
+    Xi = np.asarray(Xi, dtype=dtype)
+    Q = np.zeros((6, nw, nw), dtype=dtype)
+    E = np.zeros((6, nw, nw), dtype=rd) if return_envelope else None
     up = (w[None, :] >= w[:, None])                                # i2 >= i1 (raft_member.py:1543-1544)
     one = lambda a: a[..., :, None]                                # index i1
     two = lambda a: a[..., None, :]                                # index i2
 
     # Pinkster IV: rotation of the first-order inertial forces (raft_fowt.py:2044-2062)
-    F1st = np.matmul(np.asarray(M_struc, dtype=float), (-w ** 2 * Xi))
+    F1st = np.matmul(np.asarray(M_struc, dtype=rd), (-w ** 2 * Xi))
     th = Xi[3:]
     for blk in (slice(0, 3), slice(3, 6)):
         a = np.cross(one(th), np.conj(two(F1st[blk])), axis=0)
         b = np.cross(np.conj(two(th)), one(F1st[blk]), axis=0)
         Q[blk] += 0.25 * (a + b)
+        if return_envelope:
+            E[blk] += 0.25 * (_cross_env(one(th), two(F1st[blk])) + _cross_env(two(th), one(F1st[blk])))
 
     OM = _cross_mat(1j * w * th)                                   # OMEGA = -getH(i w theta)  (:1588-1589)
-    for rec in tab.strips:
+    for rec in np.asarray(tab.strips, dtype=rd):
         r, q, p1, p2 = rec[0:3], rec[3:6], rec[6:9], rec[9:12]
         Ca1, Ca2, CaE, v_i, v_e, a_i = rec[12:18]
         p1M, p2M, qM = np.outer(p1, p1), np.outer(p2, p2), np.outer(q, q)
@@ -186,15 +219,15 @@ def qtf_slender_body(tab, Xi, beta, w, k, h, rho, g, M_struc, kay=None):
         # per-frequency kinematics at the strip (raft_member.py:1509-1519)
         dr = Xi[:3] + np.cross(th, r, axis=0)                      # SmallRotate(r, th) = th x r
         nodeV = 1j * w * dr
-        u, _, _ = _wave_kin(beta, w, k, h, r, rho, g)
-        gu = _grad_u1(w, k, beta, h, r)
+        u, _, _ = _wave_kin(beta, w, k, h, r, rho, g, dtype)
+        gu = _grad_u1(w, k, beta, h, r, dtype)
         gdudt = 1j * w * gu
         nar = np.tensordot(q, u - nodeV, axes=(0, 0))              # nodeV_axial_rel
-        gp = _grad_pres1st(k, beta, h, r, rho, g)
+        gp = _grad_pres1st(k, beta, h, r, rho, g, dtype)
         nodeVt = nodeV - np.tensordot(q, nodeV, axes=(0, 0)) * q[:, None]     # in-place quirk of axdivAcc
 
-        F2 = np.zeros((6, nw, nw), dtype=complex)
-        acc2, p2nd = _pot2nd(w, k, beta, h, r, g, rho)
+        F2 = np.zeros((6, nw, nw), dtype=dtype)
+        acc2, p2nd = _pot2nd(w, k, beta, h, r, g, rho, dtype)
         f_2nd = rho * v_i * _cmv(P1, acc2)
         conv = 0.25 * (_mv(one(gu), np.conj(two(u))) + _mv(np.conj(two(gu)), one(u)))
         f_conv = rho * v_i * _cmv(P1, conv)
@@ -229,15 +262,17 @@ def qtf_slender_body(tab, Xi, beta, w, k, h, rho, g, M_struc, kay=None):
         f_conv = f_conv + 0.25 * a_i * rho * (np.conj(u1p) * two(nar) + u2p * np.conj(one(nar)))
         for f3 in (f_2nd, f_conv, f_axdv, f_nab, f_rslb):
             _to6(f3, r, F2)
+            if return_envelope:
+                _to6_env(f3, r, E)
         Q += F2
 
     # waterline term of every member that crosses z = 0 (raft_member.py:1517-1534, 1635-1668)
-    for m in tab.members:
+    for m in np.asarray(tab.members, dtype=rd):
         if m[0] == 0.0:
             continue
         r_int, a_wl, Ca1, Ca2, p1, p2 = m[1:4], m[4], m[5], m[6], m[7:10], m[10:13]
         p1M, p2M = np.outer(p1, p1), np.outer(p2, p2)
-        _, ud_wl, eta = _wave_kin(beta, w, k, h, r_int, 1.0, 1.0)
+        _, ud_wl, eta = _wave_kin(beta, w, k, h, r_int, 1.0, 1.0, dtype)
         dr_wl = Xi[:3] + np.cross(th, r_int, axis=0)
         a_b = 1j * w * (1j * w * dr_wl)
         g_e1 = -g * (np.cross(th, p1, axis=0)[2] * p1[:, None] + np.cross(th, p2, axis=0)[2] * p2[:, None])
@@ -245,9 +280,16 @@ def qtf_slender_body(tab, Xi, beta, w, k, h, rho, g, M_struc, kay=None):
         f = 0.25 * (one(ud_wl) * np.conj(two(eta_r)) + np.conj(two(ud_wl)) * one(eta_r))
         f = rho * a_wl * _cmv((1.0 + Ca1) * p1M + (1.0 + Ca2) * p2M, f)
         a_eta = 0.25 * (one(a_b) * np.conj(two(eta_r)) + np.conj(two(a_b)) * one(eta_r))
-        f = f - rho * a_wl * _cmv(Ca1 * p1M + Ca2 * p2M, a_eta)
-        f = f - 0.25 * rho * a_wl * (one(g_e1) * np.conj(two(eta_r)) + np.conj(two(g_e1)) * one(eta_r))
-        F = np.zeros((6, nw, nw), dtype=complex)
+        f_ab = rho * a_wl * _cmv(Ca1 * p1M + Ca2 * p2M, a_eta)
+        if return_envelope:
+            _to6_env(f, r_int, E)
+            _to6_env(f_ab, r_int, E)
+        f = f - f_ab
+        f_ge = 0.25 * rho * a_wl * (one(g_e1) * np.conj(two(eta_r)) + np.conj(two(g_e1)) * one(eta_r))
+        if return_envelope:
+            _to6_env(f_ge, r_int, E)
+        f = f - f_ge
+        F = np.zeros((6, nw, nw), dtype=dtype)
         _to6(f, r_int, F)
         Q += F
 
@@ -258,4 +300,12 @@ def qtf_slender_body(tab, Xi, beta, w, k, h, rho, g, M_struc, kay=None):
     for i in range(6):                                             # Hermitian fill (raft_fowt.py:2069-2070)
         qi = qtf[:, :, i]
         qtf[:, :, i] = qi + np.conj(qi).T - np.diag(np.diag(np.conj(qi)))
-    return qtf
+    if not return_envelope:
+        return qtf
+    env = np.transpose(np.where(up[None], E, 0.0), (1, 2, 0)).copy()
+    if kay is not None:
+        env += np.abs(kay)
+    for i in range(6):
+        ei = env[:, :, i]
+        env[:, :, i] = ei + ei.T - np.diag(np.diag(ei))
+    return qtf, env

@@ -3086,6 +3086,9 @@ extern "C" int raftx_qtf_force(raftx_ctx *c, int nSet, int nw2, const double *w2
                                const double *w, double dw, const double *S0, double *f_mean, double *f) {
     if (!c) return -1;
     if (nSet < 0 || nw2 < 2 || nw < 1 || !w2 || !w || !S0 || !f_mean || !f) FAIL(c, "qtf_force: bad arguments");
+    // k_qtf_force keeps the interpolation index and weight of every first-order bin in LDS
+    const size_t lds = sizeof(double) * ((size_t)nw + ((size_t)nw + 1) / 2 + 8);
+    if (lds > 65536) FAIL(c, "qtf_force: nw=%d needs %zu bytes of LDS, a workgroup may ask for 65536", nw, lds);
     HIPCHK(c, hipSetDevice(c->device));
     const size_t nq = (size_t)nSet * nw2 * nw2 * 6;
     Scratch sc(c);
@@ -3110,7 +3113,6 @@ extern "C" int raftx_qtf_force(raftx_ctx *c, int nSet, int nw2, const double *w2
     }
     HIPCHK(c, hipEventRecord(c->ev0, c->stream));
     if (nSet) {
-        const size_t lds = sizeof(double) * ((size_t)nw + (nw + 1) / 2 + 8);
         hipLaunchKernelGGL(k_qtf_force, dim3((unsigned)(nSet * 6)), dim3(256), lds, c->stream, nSet, nw2, dw2, dQ, nw, dwv, dw,
                            dS, dfm, df);
     }
