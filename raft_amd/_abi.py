@@ -41,6 +41,8 @@ WANT_BDRAG, WANT_FWAVE, WANT_Z = 1, 2, 4
 # include/raftx_modal.h: implemented by the device library only (the oracle has no eigen solver), bound when present
 MODAL_EXPORTS = ("raftx_modal_batch", "raftx_modal_resident", "raftx_sweep_modal")
 MODAL_SMALL_DIAG, MODAL_NONPOSITIVE, MODAL_COMPLEX, MODAL_SINGULAR_M, MODAL_NO_CONVERGENCE = 1, 2, 4, 8, 16
+# include/raftx_current.h: mean current loads, the device library only (the oracle has no current-load sweep)
+CURRENT_EXPORTS = ("raftx_current_loads", "raftx_sweep_current")
 
 
 class RaftxError(RuntimeError):
@@ -143,6 +145,12 @@ class RaftxLib:
             L.raftx_modal_resident.restype = C.c_int
             L.raftx_sweep_modal.argtypes = [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp]
             L.raftx_sweep_modal.restype = C.c_int
+        self.has_current = all(hasattr(L, s) for s in CURRENT_EXPORTS)
+        if self.has_current:
+            L.raftx_current_loads.argtypes = [_vp, C.c_int, _vp, _vp, _vp, C.c_double, C.c_double, _vp]
+            L.raftx_current_loads.restype = C.c_int
+            L.raftx_sweep_current.argtypes = [_vp, C.c_int, C.c_int, _vp, _vp, _vp, C.c_double, _vp]
+            L.raftx_sweep_current.restype = C.c_int
         L.raftx_device_locality.argtypes = [C.c_int, C.c_char_p, C.c_int, C.POINTER(C.c_int)]
         L.raftx_device_locality.restype = C.c_int
         L.raftx_host_alloc.argtypes = [_vp, C.c_size_t, C.POINTER(_vp)]
@@ -634,6 +642,47 @@ class Context:
                                         _ptr(res["flags"]), _ptr(res["props"])), "raftx_sweep_modal")
         handle["modal_inputs"] = (dM, dC)                 # alive until the crossing has been waited for
         out["fn"], out["modes"], out["modal_flags"], out["props"] = res["fn"], res["modes"], res["flags"], res["props"]
+        return handle
+
+    # ------------------------------------------------------------- mean current loads (include/raftx_current.h)
+    def _current_lib(self, what):
+        if not self.rlib.has_current:
+            raise RaftxError("%s: %s does not implement include/raftx_current.h (the device library does)" % (what, self.rlib.path))
+        return self.rlib.lib
+
+    @staticmethod
+    def _current_in(n, speed, heading, Zref):
+        speed = _f64(np.atleast_1d(np.asarray(speed, dtype=np.float64)))
+        nCur = speed.shape[0] if speed.ndim == 1 else -1
+        speed = _f64(speed, (nCur,), "speed")
+        heading = _f64(np.broadcast_to(np.asarray(heading, dtype=np.float64), (nCur,)), (nCur,), "heading")
+        if Zref is not None:
+            Zref = _f64(np.broadcast_to(np.asarray(Zref, dtype=np.float64), (n,)), (n,), "Zref")
+        return nCur, speed, heading, Zref
+
+    def current_loads(self, speed, heading, depth, Zref=None, shearExp=0.12):
+        """Mean current loads D_hydro [nD,nCur,6] of the resident design set (raftx_current_loads; FOWT.calcCurrentLoads,
+        raft_fowt.py:1961-1985, for every design and current): speed [nCur] m/s, heading [nCur] deg, Zref scalar,
+        [nD] or None (0), shearExp the exponent of the power-law profile (raft_member.py:1846)."""
+        L = self._current_lib("current_loads")
+        n = self.nDesign
+        nCur, speed, heading, Zref = self._current_in(n, speed, heading, Zref)
+        D = np.zeros((n, nCur, 6))
+        self._check(L.raftx_current_loads(self._h, nCur, _ptr(speed), _ptr(heading), _ptr(Zref), float(depth), float(shearExp),
+                                          _ptr(D)), "raftx_current_loads")
+        return D
+
+    def sweep_current(self, handle, speed, heading, Zref=None, shearExp=0.12):
+        """Ask for the mean current loads of a PREPARED, not yet launched crossing (raftx_sweep_current; the depth is the
+        crossing's); ``sweep_wait`` then also returns D_hydro [nD,nCur,6].  Returns the handle."""
+        L = self._current_lib("sweep_current")
+        out = handle["out"]
+        n = out["niter"].shape[0]
+        nCur, speed, heading, Zref = self._current_in(n, speed, heading, Zref)
+        D = np.zeros((n, max(nCur, 0), 6))
+        self._check(L.raftx_sweep_current(self._h, int(handle["slot"]), nCur, _ptr(speed), _ptr(heading), _ptr(Zref), float(shearExp),
+                                          _ptr(D)), "raftx_sweep_current")
+        out["D_hydro"] = D
         return handle
 
     def fetch_statics(self):

@@ -42,6 +42,7 @@
 
 #include "../../include/raftx.h"
 #include "../../include/raftx_modal.h"
+#include "../../include/raftx_current.h"
 
 // roctx ranges around the phases of the host side: named spans for `rocprofv3 --marker-trace`.
 // librocprofiler-sdk-roctx is bound at run time on first use; without it (or outside a profiler) the ranges cost a branch.
@@ -82,6 +83,7 @@ struct RangeScope {
 #include "raftx_dense.h"
 #include "raftx_flex.h"
 #include "raftx_modal.h"
+#include "raftx_current.h"
 
 // Coupled array solve (raft_model.py:1164-1236): Xi = Z_sys^-1 F for every (system, bin).  One wavefront per
 // (system, bin), NBIN (1, 2 or 4: what fits LDS) consecutive bins per workgroup so that the loads of one matrix entry
@@ -815,6 +817,8 @@ struct raftx_ctx {
     size_t pinRes_n;
     double *pinModal = nullptr;          // page-locked landing area of a block's eigen analysis (raftx_sweep_modal)
     size_t pinModal_n = 0;
+    double *pinCur = nullptr;            // page-locked landing area of a block's current loads (raftx_sweep_current)
+    size_t pinCur_n = 0;
     hipStream_t sCopy, sPrep, sD2H, sGen; // internal streams of raftx_sweep_stats (created on first use)
     hipStream_t sSlab[2] = {nullptr, nullptr}; // with sGen: the streams the slabs of a crossing with responses out go to (SlabPlan)
     hipStream_t sD2Hhigh = nullptr;       // bulk download of the responses: a stream of the highest priority class, created when first needed
@@ -932,6 +936,15 @@ struct SweepSlot {
         int32_t *flags = nullptr;
         hipEvent_t evUp = nullptr;       // the copies of dM / dC have landed (sCopy)
     } modal;
+    struct {                             // raftx_sweep_current: mean current loads of the crossing's designs
+        bool on = false;
+        int nCur = 0;
+        double shearExp = 0;
+        std::vector<double> host;        // speed | cos | sin [3,nCur] | Zref [nDesign]: the source of the copies below
+        const double *par = nullptr, *Zref = nullptr;   // device copies (in S.allocs); Zref null: 0
+        double *D = nullptr;             // the caller's output [nDesign,nCur,6], filled by raftx_sweep_wait
+        hipEvent_t evUp = nullptr;       // the copies have landed (sCopy)
+    } current;
 };
 
 #define MAX_NW 2048
@@ -1086,12 +1099,14 @@ extern "C" void raftx_ctx_destroy(raftx_ctx *c) {
         free_list(c, c->slots[sl].allocs);
         if (c->slots[sl].evXi) (void)hipEventDestroy(c->slots[sl].evXi);
         if (c->slots[sl].modal.evUp) (void)hipEventDestroy(c->slots[sl].modal.evUp);
+        if (c->slots[sl].current.evUp) (void)hipEventDestroy(c->slots[sl].current.evUp);
     }
     delete[] c->slots;
     c->pool.trim();
     if (c->pin) (void)hipHostFree(c->pin);
     if (c->pinRes) (void)hipHostFree(c->pinRes);
     if (c->pinModal) (void)hipHostFree(c->pinModal);
+    if (c->pinCur) (void)hipHostFree(c->pinCur);
     for (hipEvent_t e : {c->evZ, c->ev0, c->ev1, c->evUp, c->evTot, c->evG0, c->evG1, c->evG2, c->evG3, c->evS0, c->evS1, c->evDone,
                          c->evMem, c->evRed})
         (void)hipEventDestroy(e);
@@ -3291,6 +3306,7 @@ static int sweep_prepare_impl(raftx_ctx *c, int slot, int nDesign, const BuildSo
     // the slot's previous crossing has been waited for: its tables and offset arrays are free
     free_list(c, S.allocs);
     S.modal.on = false;
+    S.current.on = false;
     // ---- the batch's offset arrays: one upload, shared by the blocks; its wave numbers are those of the sea-state set
     S.p1 = src;
     S.p1.k_dev = CT.k;
@@ -3516,6 +3532,36 @@ static hipError_t modal_block(raftx_ctx *sub, SweepSlot &S, int lo, int n, hipSt
     return hipGetLastError();
 }
 
+// The current loads of one block of a crossing (raftx_sweep_current) on stream st, behind the block's statistics kernel:
+// the block's strip tables are resident until the block is retired.  One wave per (design, tile of currents), the sums
+// written straight into the block's page-locked landing area [n,nCur,6], which raftx_sweep_wait copies out.
+static hipError_t current_block(raftx_ctx *sub, SweepSlot &S, int lo, int n, double depth, hipStream_t st) {
+    const size_t need = (size_t)n * S.current.nCur * 6;
+    if (!sub->pinCur || sub->pinCur_n < need) {
+        if (sub->pinCur) (void)hipHostFree(sub->pinCur);
+        sub->pinCur = nullptr;
+        sub->pinCur_n = 0;
+        void *p_ = nullptr;
+        const hipError_t e = hipHostMalloc(&p_, (need ? need : 1) * sizeof(double), hipHostMallocDefault);
+        if (e != hipSuccess) return e;
+        sub->pinCur = reinterpret_cast<double *>(p_);
+        sub->pinCur_n = need;
+    }
+    if (n == 0) return hipSuccess;
+    if (sub->T.nDesign != n || !sub->T.off || !sub->T.ds || !sub->T.dsi) return hipErrorInvalidValue;   // (the block kept no tables: internal error)
+    const hipError_t e = hipStreamWaitEvent(st, S.current.evUp, 0);
+    if (e != hipSuccess) return e;
+    CurrentArgs A;
+    A.nDesign = n; A.nCur = S.current.nCur;
+    A.off = sub->T.off; A.ds = sub->T.ds; A.dsi = sub->T.dsi;
+    A.par = S.current.par;
+    A.Zref = S.current.Zref ? S.current.Zref + lo : nullptr;
+    A.depth = depth; A.shearExp = S.current.shearExp;
+    A.D = sub->pinCur;
+    hipLaunchKernelGGL(k_current_loads, dim3(current_grid(n, A.nCur)), dim3(64 * CUR_WAVES), 0, st, A);
+    return hipGetLastError();
+}
+
 // The stream the responses of a crossing are downloaded on: one of the HIGHEST priority class, created when first needed (so
 // late, it does not move the other streams' hardware queues).  A priority class has hardware queues of its own and the highest
 // is served at once: the copy never sits in a queue with the next batch's kernels (ordinary stream) nor starts a step late
@@ -3545,6 +3591,7 @@ static int enqueue_stats(raftx_ctx *c, SweepSlot &S, size_t b, hipStream_t sDown
     }
     if (e == hipSuccess) e = hipEventRecord(sub->evS1, c->stream);
     if (e == hipSuccess && S.modal.on) e = modal_block(sub, S, lo, S.bnd[b + 1] - lo, c->stream);
+    if (e == hipSuccess && S.current.on) e = current_block(sub, S, lo, S.bnd[b + 1] - lo, c->csets[S.cset].T.depth, c->stream);
     if (e == hipSuccess) e = hipEventRecord(sub->evDone, c->stream);
     if (e == hipSuccess && S.Xi && !S.slab) {
         e = hipStreamWaitEvent(sDown, sub->evDone, 0);
@@ -3653,7 +3700,8 @@ extern "C" int raftx_sweep_launch(raftx_ctx *c, int slot) {
         S.tlb.push_back(since());
         // (a crossing: no ABI copy of the strip records; with RAFTX_FUSED_GEN=1 the tables are left to the fused kernel itself,
         // raftx_fusedgen.h -- build_phase2 / solve_enqueue decide)
-        const int kind = GEN_CROSSING | ((nCase == 1 && !slab_mode) ? GEN_MAY_DEFER : 0) | (pipelined ? GEN_PIPELINED : 0);
+        // (a crossing with current loads reads the tables after the solve: they are never left to the fused kernel)
+        const int kind = GEN_CROSSING | ((nCase == 1 && !slab_mode && !S.current.on) ? GEN_MAY_DEFER : 0) | (pipelined ? GEN_PIPELINED : 0);
         if (!rc) rc = build_phase2(sub, nullptr, pipelined ? c->sGen : nullptr, kind);
         S.tlb.push_back(since());
         if (!rc) {                                                      // the sea states this crossing was prepared with
@@ -3733,6 +3781,7 @@ extern "C" int raftx_sweep_cancel(raftx_ctx *c, int slot) {
         }
     S.prepared = false;
     S.modal.on = false;
+    S.current.on = false;
     slot_release_cases(c, S);
     HIPCHK(c, e);
     return 0;
@@ -3798,8 +3847,11 @@ extern "C" int raftx_sweep_wait(raftx_ctx *c, int slot, double *timing_ms) {
                 memcpy(S.modal.props + (size_t)lo * RAFTX_SP_N, pm + (size_t)n * 42, (size_t)n * RAFTX_SP_N * sizeof(double));
             memcpy(S.modal.flags + lo, pm + (size_t)n * (42 + RAFTX_SP_N), (size_t)n * sizeof(int32_t));
         }
+        if (S.current.on && n)
+            memcpy(S.current.D + (size_t)lo * S.current.nCur * 6, sub->pinCur, (size_t)n * S.current.nCur * 6 * sizeof(double));
     }
     S.modal.on = false;
+    S.current.on = false;
     const double wall = since();
     if (dbg_host)
         fprintf(stderr, "[raftx_sweep slot %d] host ms since submit: pre %.3f | phase-1 enqueued %.3f | phase-2 enqueued %.3f | ctx stream "
@@ -3914,6 +3966,89 @@ extern "C" int raftx_sweep_modal(raftx_ctx *c, int slot, const double *dM, const
     S.modal.flags = flags;
     S.modal.props = props;
     S.modal.on = true;
+    return 0;
+}
+
+// ---- mean current loads (include/raftx_current.h, raftx_current.h)
+// speed | cos | sin [3,nCur] (+ Zref [nDesign]) checked and laid out for the kernel (raft_member.py:1848: the heading in
+// degrees, cos / sin in libm precision on the host)
+static int current_params(raftx_ctx *c, const char *who, int nCur, const double *speed, const double *heading_deg, const double *Zref,
+                          size_t nDesign, double depth, double shearExp, std::vector<double> &host) {
+    if (nCur <= 0) FAIL(c, "%s: nCur must be positive (got %d)", who, nCur);
+    if (!speed || !heading_deg) FAIL(c, "%s: bad arguments", who);
+    if (!std::isfinite(depth) || !std::isfinite(shearExp)) FAIL(c, "%s: depth and shearExp must be finite", who);
+    host.resize((size_t)3 * nCur + (Zref ? nDesign : 0));
+    for (int i = 0; i < nCur; i++) {
+        if (!std::isfinite(speed[i]) || !std::isfinite(heading_deg[i])) FAIL(c, "%s: current %d has a non-finite speed or heading", who, i);
+        const double h = heading_deg[i] * (3.14159265358979323846 / 180.0);      // np.deg2rad
+        host[(size_t)i] = speed[i];
+        host[(size_t)nCur + i] = cos(h);
+        host[(size_t)2 * nCur + i] = sin(h);
+    }
+    for (size_t d = 0; d < nDesign; d++) {
+        const double z = Zref ? Zref[d] : 0.0;
+        if (!std::isfinite(z)) FAIL(c, "%s: Zref of design %zu is not finite", who, d);
+        if (!(depth + z > 0.0)) FAIL(c, "%s: depth + Zref must be positive (design %zu: %g + %g)", who, d, depth, z);
+        if (Zref) host[(size_t)3 * nCur + d] = z;
+    }
+    if (!Zref && !(depth > 0.0)) FAIL(c, "%s: depth + Zref must be positive (depth %g)", who, depth);
+    return 0;
+}
+
+extern "C" int raftx_current_loads(raftx_ctx *c, int nCur, const double *speed, const double *heading_deg, const double *Zref,
+                                   double depth, double shearExp, double *D) {
+    if (!c) return -1;
+    if (!c->have_designs) FAIL(c, "current_loads: no design set on this ctx (raftx_upload_designs / raftx_build_designs)");
+    if (!D) FAIL(c, "current_loads: bad arguments");
+    const int n = c->T.nDesign;
+    std::vector<double> host;
+    if (int rc = current_params(c, "current_loads", nCur, speed, heading_deg, Zref, (size_t)n, depth, shearExp, host)) return rc;
+    if (n == 0) return 0;
+    HIPCHK(c, hipSetDevice(c->device));
+    Scratch sc(c);
+    double *dpar = sc.alloc<double>(host.size()), *dD = sc.alloc<double>((size_t)n * nCur * 6);
+    if (!dpar || !dD) FAIL(c, "current_loads: device allocation failed");
+    H2D(c, dpar, host.data(), host.size() * sizeof(double));
+    CurrentArgs A;
+    A.nDesign = n; A.nCur = nCur;
+    A.off = c->T.off; A.ds = c->T.ds; A.dsi = c->T.dsi;
+    A.par = dpar;
+    A.Zref = Zref ? dpar + (size_t)3 * nCur : nullptr;
+    A.depth = depth; A.shearExp = shearExp;
+    A.D = dD;
+    HIPCHK(c, hipEventRecord(c->ev0, c->stream));
+    hipLaunchKernelGGL(k_current_loads, dim3(current_grid(n, nCur)), dim3(64 * CUR_WAVES), 0, c->stream, A);
+    if (finish_timed(c)) return -2;
+    D2H(c, D, dD, (size_t)n * nCur * 6 * sizeof(double));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+extern "C" int raftx_sweep_current(raftx_ctx *c, int slot, int nCur, const double *speed, const double *heading_deg,
+                                   const double *Zref, double shearExp, double *D) {
+    if (!c) return -1;
+    if (slot < 0 || slot >= RAFTX_NSLOT) FAIL(c, "sweep_current: slot must be 0 .. %d", RAFTX_NSLOT - 1);
+    SweepSlot &S = c->slots[slot];
+    if (S.busy) FAIL(c, "sweep_current: slot %d has been launched (call it between raftx_sweep_prepare and raftx_sweep_launch)", slot);
+    if (!S.prepared) FAIL(c, "sweep_current: nothing prepared on slot %d (raftx_sweep_prepare first)", slot);
+    if (!D) FAIL(c, "sweep_current: bad arguments");
+    if (S.cset < 0) FAIL(c, "sweep_current: slot %d has lost its sea-state tables (internal error)", slot);
+    const size_t n = S.bnd.empty() ? 0 : (size_t)S.bnd.back();
+    std::vector<double> host;
+    if (int rc = current_params(c, "sweep_current", nCur, speed, heading_deg, Zref, n, c->csets[S.cset].T.depth, shearExp, host)) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (S.current.evUp) HIPCHK(c, hipEventSynchronize(S.current.evUp));   // (a second request on one slot: the first copy has left the host array)
+    S.current.host.swap(host);                                           // alive until the slot is prepared again
+    const double *dpar = nullptr;
+    if (upload_on(c, c->sCopy, S.allocs, S.current.host.data(), S.current.host.size(), &dpar)) return -2;
+    if (!S.current.evUp) HIPCHK(c, hipEventCreateWithFlags(&S.current.evUp, hipEventDisableTiming));
+    HIPCHK(c, hipEventRecord(S.current.evUp, c->sCopy));
+    S.current.nCur = nCur;
+    S.current.shearExp = shearExp;
+    S.current.par = dpar;
+    S.current.Zref = Zref ? dpar + (size_t)3 * nCur : nullptr;
+    S.current.D = D;
+    S.current.on = true;
     return 0;
 }
 

@@ -15,6 +15,8 @@ read here (that is how the GPU-box tests run without /root/reference).
     raft/raft_fowt.py:2158    FOWT.calcHydroForce_2ndOrd(beta, S0, iCase=None, iWT=None, interpMode='qtf')
 are mirrored too (internal slender-body QTFs, potSecOrder == 1, incl. the re-entry of the drag iteration with the
 second-order force, raft_model.py:1108-1131).
+    raft/raft_fowt.py:1961    FOWT.calcCurrentLoads(case)
+is mirrored for rigid 6-DOF units (``install(current=True)``; include/raftx_current.h).
 
 On the device path too: units with more than 6 reduced DOFs (flexible members; Engine._solve_general, raftx_flex_solve),
 potential-flow coefficients on either kind of unit, submerged rotors on any unit of an array, arrays with a shared
@@ -189,6 +191,35 @@ class Engine:
         model.results['eigen']['frequencies'] = fns
         model.results['eigen']['modes'] = modes
         return fns, modes
+
+    # ------------------------------------------------------------------ mean current loads (include/raftx_current.h)
+    def calcCurrentLoads(self, fowt, case):
+        """FOWT.calcCurrentLoads (raft_fowt.py:1961-1985): the mean drag of the sheared current of ``case`` on the wet strips
+        of the unit's own members (raftx_current_loads on its strip table; the rotor tables are not part of it), about
+        the reduced-DOF point.  Sets and returns fowt.D_hydro [6].  Units with more than 6 reduced DOFs raise
+        UnsupportedFOWT."""
+        if int(getattr(fowt, "nDOF", 6)) != 6:
+            raise UnsupportedFOWT("FOWT.calcCurrentLoads: units with %d reduced DOFs are not covered (rigid 6-DOF units only)" % fowt.nDOF)
+
+        def scalar(key, default):                            # getFromDict(case, key, shape=0, default=default)
+            v = np.asarray(case.get(key, default), dtype=float)
+            if v.size != 1:
+                raise ValueError("case['%s'] must be a scalar" % key)
+            return float(v.reshape(-1)[0])
+        speed, heading = scalar("current_speed", 0.0), scalar("current_heading", 0.0)
+        Zref = 0.0                                           # raft_fowt.py:1971-1974: the LAST submerged rotor's hub depth
+        for rot in getattr(fowt, "rotorList", []):
+            if rot.r3[2] < 0:
+                Zref = float(rot.r3[2])
+        table = pack_fowt(fowt)
+        nw = max(len(np.atleast_1d(getattr(fowt, "w", [0.0]))), 1)
+        zero = np.zeros((1, 6, 6))
+        self._up_key = None                                  # the resident set is this unit's table with no matrices
+        self.ctx.upload_designs([table], zero, zero, zero, nw)
+        D = self.ctx.current_loads([speed], [heading], float(fowt.depth), Zref=Zref,
+                                   shearExp=float(getattr(fowt, "shearExp_water", 0.12)))
+        fowt.D_hydro = D[0, 0].copy()
+        return fowt.D_hydro
 
     # ------------------------------------------------------------------ per-member side effects (SURVEY.md 8b), on request
     @staticmethod
@@ -1465,13 +1496,18 @@ def fowt_solveEigen(fowt, display=0, outPath=None):
     return _default_engine.fowt_solveEigen(fowt, display=display, outPath=outPath)
 
 
-def install(raft_module=None, outputs=False, materialise_members=None, eigen=False):
+def calcCurrentLoads(fowt, case):
+    return _default_engine.calcCurrentLoads(fowt, case)
+
+
+def install(raft_module=None, outputs=False, materialise_members=None, eigen=False, current=False):
     """Monkey-patch a loaded reference package so that Model.analyzeCases & co
     run the hot path on the GPU.  Returns the originals for un-patching.
     outputs=True also routes FOWT.saveTurbineOutputs (statistics of the resident responses; rigid single units
     without MoorPy / controller outputs -- anything else raises UnsupportedFOWT, never a silent fallback).
     eigen=True also routes Model.solveEigen and FOWT.solveEigen (rigid single units; arrays and units with more than 6
     DOFs raise UnsupportedFOWT).
+    current=True also routes FOWT.calcCurrentLoads (rigid 6-DOF units; the underwater rotor's own current path is not covered).
     materialise_members=True / False: switch the default engine's per-member side effects (mem.u, ud, pDyn,
     F_hydro_iner, Bmat, F_exc_drag: Engine.materialise_members) on / off; None leaves the engine as it is."""
     if materialise_members is not None:
@@ -1499,6 +1535,9 @@ def install(raft_module=None, outputs=False, materialise_members=None, eigen=Fal
         saved["FOWT.solveEigen"] = raft_fowt.FOWT.solveEigen
         raft_model.Model.solveEigen = solveEigen
         raft_fowt.FOWT.solveEigen = fowt_solveEigen
+    if current:
+        saved["calcCurrentLoads"] = raft_fowt.FOWT.calcCurrentLoads
+        raft_fowt.FOWT.calcCurrentLoads = calcCurrentLoads
     return saved
 
 
@@ -1515,3 +1554,5 @@ def uninstall(saved):
     if 'Model.solveEigen' in saved:
         raft_model.Model.solveEigen = saved['Model.solveEigen']
         raft_fowt.FOWT.solveEigen = saved['FOWT.solveEigen']
+    if 'calcCurrentLoads' in saved:
+        raft_fowt.FOWT.calcCurrentLoads = saved['calcCurrentLoads']

@@ -173,6 +173,12 @@ class Sweep:
         props [nD,12] or None); ``periods(fn)`` gives the periods."""
         return ctx.modal_resident(dM, dC, want_props=want_props)
 
+    def run_current(self, ctx, speed, heading, Zref=None, shearExp=0.12):
+        """Mean current loads D_hydro [nD,nCur,6] of the designs resident on ``ctx`` (after ``upload``;
+        raftx_current_loads): FOWT.calcCurrentLoads (raft_fowt.py:1961-1985) of every design for the currents speed [nCur]
+        m/s / heading [nCur] deg at this sweep's depth; Zref scalar, [nD] or None (0: no submerged rotor)."""
+        return ctx.current_loads(speed, heading, self.depth, Zref=Zref, shearExp=shearExp)
+
     def run_stats(self, ctx, want_psd=False):
         """Solve and return only the response statistics (std [nD,nC,6], optional PSD) + niter/flags:
         ~60 B per (design, case) cross the bus instead of 19 KB (raft_fowt.py:2310-2357)."""
@@ -300,14 +306,16 @@ class GeometrySweep(Sweep):
                                             None if self.pose is None else self.pose[lo:hi], self.add_mask,
                                             None if self.MBw is None else self.MBw[lo:hi], self.rho, self.g), lo, hi)
 
-    def run_crossing(self, ctx, n_chunk=0, n_worker=0, want_Xi=False, Xi_out=None, modal=False, dM=None, dC=None, want_props=False):
+    def run_crossing(self, ctx, n_chunk=0, n_worker=0, want_Xi=False, Xi_out=None, modal=False, dM=None, dC=None, want_props=False,
+                     current=None):
         """The whole boundary crossing in ONE library call (raftx_sweep_stats): descriptors in, motion statistics +
         iteration counts (+ responses) out, with upload / generation / solve / download of consecutive design blocks
-        overlapped on the library's internal streams.  Nothing stays resident on ``ctx``.  modal=True: the streamed
-        form on slot 0 with the eigen analysis of every design (see ``prepare_crossing``)."""
-        if modal:
-            return self.wait_crossing(ctx, self.submit_crossing(ctx, 0, n_chunk=n_chunk, want_Xi=want_Xi, Xi_out=Xi_out, modal=True,
-                                                                dM=dM, dC=dC, want_props=want_props))
+        overlapped on the library's internal streams.  Nothing stays resident on ``ctx``.  modal=True / current=dict(..):
+        the streamed form on slot 0 with the eigen analysis / mean current loads of every design (see
+        ``prepare_crossing``)."""
+        if modal or current is not None:
+            return self.wait_crossing(ctx, self.submit_crossing(ctx, 0, n_chunk=n_chunk, want_Xi=want_Xi, Xi_out=Xi_out, modal=modal,
+                                                                dM=dM, dC=dC, want_props=want_props, current=current))
         self._crossing_supported()
         t = self.tables
         r = ctx.sweep_stats(t, self.M0, self.B0, self.C0, self.w, self.k, self.depth, self.zeta, self.beta, self.nIter,
@@ -316,15 +324,18 @@ class GeometrySweep(Sweep):
         self.off = r["strip_off"]
         return r
 
-    def prepare_crossing(self, ctx, slot, n_chunk=0, want_Xi=False, Xi_out=None, modal=False, dM=None, dC=None, want_props=False):
+    def prepare_crossing(self, ctx, slot, n_chunk=0, want_Xi=False, Xi_out=None, modal=False, dM=None, dC=None, want_props=False,
+                         current=None):
         """First stage of the streamed form of ``run_crossing`` for back-to-back batches: enqueue this batch's descriptor
         upload and member pass on ``slot`` (0 .. 3) and return a handle (raftx_sweep_prepare).  modal=True: the batch's
         eigen analysis rides along (raftx_sweep_modal on M_extra + device terms + dM, C_extra + device terms + dC) and
-        ``wait_crossing`` also returns fn, modes, modal_flags and props (``want_props``)."""
+        ``wait_crossing`` also returns fn, modes, modal_flags and props (``want_props``).  current=dict(speed=, heading=,
+        Zref=, shearExp=): the batch's mean current loads ride along (raftx_sweep_current, at this sweep's depth; Zref
+        and shearExp optional, 0 and 0.12) and ``wait_crossing`` also returns D_hydro [nD,nCur,6]."""
         self._crossing_supported()
-        return self._with_modal(ctx, ctx.sweep_prepare(slot, self.tables, self.M0, self.B0, self.C0, self.w, self.k, self.depth, self.zeta, self.beta,
+        return self._with_current(ctx, self._with_modal(ctx, ctx.sweep_prepare(slot, self.tables, self.M0, self.B0, self.C0, self.w, self.k, self.depth, self.zeta, self.beta,
                                  self.nIter, self.tol, self.XiStart, pose=self.pose, rho=self.rho, g=self.g, add_mask=self.add_mask,
-                                 n_chunk=n_chunk, want_Xi=want_Xi, Xi_out=Xi_out), modal, dM, dC, want_props)
+                                 n_chunk=n_chunk, want_Xi=want_Xi, Xi_out=Xi_out), modal, dM, dC, want_props), current)
 
     @staticmethod
     def _with_modal(ctx, handle, modal, dM, dC, want_props):
@@ -338,16 +349,31 @@ class GeometrySweep(Sweep):
             ctx.sweep_cancel(handle)
             raise
 
+    @staticmethod
+    def _with_current(ctx, handle, current):
+        if current is None:
+            return handle
+        unknown = set(current) - {"speed", "heading", "Zref", "shearExp"}
+        try:
+            if unknown or "speed" not in current or "heading" not in current:
+                raise ValueError("current=dict(speed=, heading=[, Zref=, shearExp=]) (got %s)" % sorted(current))
+            return ctx.sweep_current(handle, current["speed"], current["heading"], Zref=current.get("Zref"),
+                                     shearExp=0.12 if current.get("shearExp") is None else current["shearExp"])
+        except Exception:
+            ctx.sweep_cancel(handle)
+            raise
+
     def launch_crossing(self, ctx, handle):
         """Second stage: table generation, fused fixed point and statistics of a prepared batch (raftx_sweep_launch).  With
         launch(i+1), prepare(i+2), wait(i) per step a long sweep keeps three batches in flight and the fused kernels of
         consecutive batches follow each other without a gap."""
         return ctx.sweep_launch(handle)
 
-    def submit_crossing(self, ctx, slot, n_chunk=0, want_Xi=False, Xi_out=None, modal=False, dM=None, dC=None, want_props=False):
+    def submit_crossing(self, ctx, slot, n_chunk=0, want_Xi=False, Xi_out=None, modal=False, dM=None, dC=None, want_props=False,
+                        current=None):
         """prepare + launch in one call (raftx_sweep_submit); ``wait_crossing`` collects the results."""
         return self.launch_crossing(ctx, self.prepare_crossing(ctx, slot, n_chunk=n_chunk, want_Xi=want_Xi, Xi_out=Xi_out,
-                                                               modal=modal, dM=dM, dC=dC, want_props=want_props))
+                                                               modal=modal, dM=dM, dC=dC, want_props=want_props, current=current))
 
     def _crossing_supported(self):
         """raftx_sweep_stats / raftx_sweep_submit carry neither frequency-dependent matrices nor potential-flow excitation
@@ -713,19 +739,20 @@ class VariantSweep(GeometrySweep):
                            self.add_mask, self.rho, self.g)
         return self._take_bem(sub, lo, hi)
 
-    def prepare_crossing(self, ctx, slot, n_chunk=0, want_Xi=False, Xi_out=None, modal=False, dM=None, dC=None, want_props=False):
+    def prepare_crossing(self, ctx, slot, n_chunk=0, want_Xi=False, Xi_out=None, modal=False, dM=None, dC=None, want_props=False,
+                         current=None):
         self._crossing_supported()
         self._install(ctx)
-        return self._with_modal(ctx, ctx.sweep_prepare_variants(slot, self.params, self.M0, self.B0, self.C0, self.w, self.k, self.depth, self.zeta, self.beta,
+        return self._with_current(ctx, self._with_modal(ctx, ctx.sweep_prepare_variants(slot, self.params, self.M0, self.B0, self.C0, self.w, self.k, self.depth, self.zeta, self.beta,
                                           self.nIter, self.tol, self.XiStart, pose=self.pose, rho=self.rho, g=self.g,
                                           add_mask=self.add_mask, n_chunk=n_chunk, want_Xi=want_Xi, Xi_out=Xi_out),
-                                modal, dM, dC, want_props)
+                                modal, dM, dC, want_props), current)
 
     def run_crossing(self, ctx, n_chunk=0, n_worker=0, want_Xi=False, Xi_out=None, slot=0, modal=False, dM=None, dC=None,
-                     want_props=False):
+                     want_props=False, current=None):
         """One isolated crossing: prepare + launch + wait on ``slot``."""
         return self.wait_crossing(ctx, self.submit_crossing(ctx, slot, n_chunk=n_chunk, want_Xi=want_Xi, Xi_out=Xi_out, modal=modal,
-                                                            dM=dM, dC=dC, want_props=want_props))
+                                                            dM=dM, dC=dC, want_props=want_props, current=current))
 
     def upload(self, ctx):
         self.tables = self.expanded_tables(ctx)
