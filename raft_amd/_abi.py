@@ -397,6 +397,13 @@ class Context:
             caps = _f64(tables.caps, (cap_off[-1], 4), "caps")
             if caps.size == 0:
                 caps = np.zeros((1, 4))
+        nC, nH, nw, rest, out = self._sweep_seas_out(nD, M0, B0, C0, w, k, zeta, beta, pose, Fz_moor, want_Xi, Xi_out)
+        return nD, nC, nH, nw, (member_off, members, station_off, stations, cap_off, caps) + rest, out
+
+    @staticmethod
+    def _sweep_seas_out(nD, M0, B0, C0, w, k, zeta, beta, pose, Fz_moor, want_Xi, Xi_out):
+        """The half of a crossing's inputs that does not describe geometry -- matrices, pose, sea states -- checked, and its
+        freshly allocated outputs: (nC, nH, nw, (pose, M0, B0, C0, Fz, w, k, zeta, beta), out)."""
         M0, B0, C0 = _f64(M0, (nD, 6, 6), "M0"), _f64(B0, (nD, 6, 6), "B0"), _f64(C0, (nD, 6, 6), "C0")
         pose = None if pose is None else _f64(pose, (nD, 6), "pose")
         Fz = None if Fz_moor is None else _f64(Fz_moor, (nD,), "Fz_moor")
@@ -416,8 +423,7 @@ class Context:
             raise ValueError("Xi_out must be a C-contiguous complex128 array of shape %s" % ((nD, nC, nH, 6, nw),))
         out = dict(std=np.empty((nD, nC, 6)), niter=np.zeros((nD, nC), dtype=np.int32), flags=np.zeros((nD, nC), dtype=np.int32),
                    Xi=Xi, strip_off=np.zeros(nD + 1, dtype=np.int64), timing_ms=np.zeros(4))
-        inputs = (member_off, members, station_off, stations, cap_off, caps, pose, M0, B0, C0, Fz, w, k, zeta, beta)
-        return nD, nC, nH, nw, inputs, out
+        return nC, nH, nw, (pose, M0, B0, C0, Fz, w, k, zeta, beta), out
 
     def sweep_prepare(self, slot, tables, M0, B0, C0, w, k, depth, zeta, beta, nIter, tol=0.01, XiStart=0.1, pose=None,
                       rho=1025.0, g=9.81, rho_wave=1025.0, g_wave=9.81, add_mask=7, Fz_moor=None, n_chunk=0, want_Xi=False,
@@ -508,25 +514,9 @@ class Context:
         params = _f64(params)
         nD = params.shape[0]
         params = _f64(params, (nD, nP), "params")
-        M0, B0, C0 = _f64(M0, (nD, 6, 6), "M0"), _f64(B0, (nD, 6, 6), "B0"), _f64(C0, (nD, 6, 6), "C0")
-        pose = None if pose is None else _f64(pose, (nD, 6), "pose")
-        Fz = None if Fz_moor is None else _f64(Fz_moor, (nD,), "Fz_moor")
-        w = _f64(w)
-        nw = len(w)
-        k = _f64(k, (nw,), "k")
-        zeta = _f64(zeta)
-        if zeta.ndim == 2:
-            zeta, beta = zeta[None], np.asarray(beta, dtype=np.float64)[None]
-        nC, nH = zeta.shape[0], zeta.shape[1]
-        zeta, beta = _f64(zeta, (nC, nH, nw), "zeta"), _f64(beta, (nC, nH), "beta")
-        Xi = Xi_out
-        if Xi is None and want_Xi:
-            Xi = np.empty((nD, nC, nH, 6, nw), dtype=np.complex128)
-        if Xi is not None and (Xi.dtype != np.complex128 or Xi.shape != (nD, nC, nH, 6, nw) or not Xi.flags["C_CONTIGUOUS"]):
-            raise ValueError("Xi_out must be a C-contiguous complex128 array of shape %s" % ((nD, nC, nH, 6, nw),))
-        out = dict(std=np.empty((nD, nC, 6)), niter=np.zeros((nD, nC), dtype=np.int32), flags=np.zeros((nD, nC), dtype=np.int32),
-                   Xi=Xi, strip_off=np.zeros(nD + 1, dtype=np.int64), timing_ms=np.zeros(4))
-        inputs = (params, pose, M0, B0, C0, Fz, w, k, zeta, beta)
+        nC, nH, nw, rest, out = self._sweep_seas_out(nD, M0, B0, C0, w, k, zeta, beta, pose, Fz_moor, want_Xi, Xi_out)
+        inputs = (params,) + rest
+        pose, M0, B0, C0, Fz, w, k, zeta, beta = rest
         rc = self.rlib.lib.raftx_sweep_prepare_variants(self._h, int(slot), nD, _ptr(params), _ptr(pose), float(rho), float(g), int(add_mask),
                                                         _ptr(M0), _ptr(B0), _ptr(C0), _ptr(Fz), nC, nH, nw, _ptr(w), _ptr(k), float(depth),
                                                         float(rho_wave), float(g_wave), _ptr(zeta), _ptr(beta), int(nIter), float(tol),

@@ -734,6 +734,30 @@ struct DevPool {
     }
 };
 
+// A page-locked landing area of a ctx, written by kernels and read by the host: grow-only -- reserve(n) keeps a block that
+// holds n elements and replaces a smaller one (contents are not carried over; a zero count still gives a valid block) --
+// and released by raftx_ctx_destroy.
+template <typename Tp>
+struct Pinned {
+    Tp *p = nullptr;
+    size_t cap = 0;                      // elements p was reserved for
+    hipError_t reserve(size_t n) {
+        if (p && cap >= n) return hipSuccess;
+        release();
+        void *q = nullptr;
+        const hipError_t e = hipHostMalloc(&q, (n ? n : 1) * sizeof(Tp), hipHostMallocDefault);
+        if (e != hipSuccess) return e;
+        p = reinterpret_cast<Tp *>(q);
+        cap = n;
+        return hipSuccess;
+    }
+    void release() {
+        if (p) (void)hipHostFree(p);
+        p = nullptr;
+        cap = 0;
+    }
+};
+
 // A raftx_build_designs in flight: phase 1 (descriptor H2D, member pass, scans, totals to the host) has been enqueued,
 // phase 2 (strip tables, statics) follows once the totals are known.  The sweep crossing keeps several of them in flight.
 struct BuildJob {
@@ -811,14 +835,10 @@ struct raftx_ctx {
     hipEvent_t evMem, evRed;             // member pass done (preparation stream) / per-design reduction done (side stream)
     hipStream_t sAux;                    // side stream of the parent ctx: the reductions of the member pass run beside its scans
     BuildJob job;
-    long long *pin;                      // page-locked landing area of the build totals and offsets [8 + nDesign + 1]
-    size_t pin_n;
-    double *pinRes;                      // page-locked landing area of a block's statistics (sweep crossing)
-    size_t pinRes_n;
-    double *pinModal = nullptr;          // page-locked landing area of a block's eigen analysis (raftx_sweep_modal)
-    size_t pinModal_n = 0;
-    double *pinCur = nullptr;            // page-locked landing area of a block's current loads (raftx_sweep_current)
-    size_t pinCur_n = 0;
+    Pinned<long long> pin;               // landing area of the build totals and offsets [PIN_OFF + nDesign + 1]
+    Pinned<double> pinRes;               // ... of a block's statistics (sweep crossing)
+    Pinned<double> pinModal;             // ... of a block's eigen analysis (raftx_sweep_modal)
+    Pinned<double> pinCur;               // ... of a block's current loads (raftx_sweep_current)
     hipStream_t sCopy, sPrep, sD2H, sGen; // internal streams of raftx_sweep_stats (created on first use)
     hipStream_t sSlab[2] = {nullptr, nullptr}; // with sGen: the streams the slabs of a crossing with responses out go to (SlabPlan)
     hipStream_t sD2Hhigh = nullptr;       // bulk download of the responses: a stream of the highest priority class, created when first needed
@@ -923,7 +943,8 @@ struct SweepSlot {
     // batch's device offsets are kept for that
     BuildSource p1;
     size_t next_p1 = 0;                  // first block whose phase 1 has not been enqueued yet
-    std::chrono::steady_clock::time_point t0;
+    std::chrono::steady_clock::time_point t0;                             // raftx_sweep_prepare was entered
+    double since() const { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }   // host ms
     double tl[4] = {0, 0, 0, 0};
     double span[2] = {0, 0};             // fused launches of the crossing last waited for: start / end, ms since the ctx epoch
     size_t nSlabEv = 0;
@@ -1021,10 +1042,6 @@ extern "C" int raftx_ctx_create(int device_id, raftx_ctx **out) {
     c->comm_world = 1;
     c->owns_stream = true;
     c->slots = new SweepSlot[RAFTX_NSLOT];
-    c->pin = nullptr;
-    c->pin_n = 0;
-    c->pinRes = nullptr;
-    c->pinRes_n = 0;
     c->sCopy = c->sPrep = c->sD2H = c->sGen = nullptr;
     // the ctx stream -- the fused fixed points, table generation, statistics -- is of the default priority class (a high one
     // lost: profiles/MEASUREMENT_HISTORY.md, "Closed scheduling experiments of the crossing")
@@ -1103,10 +1120,10 @@ extern "C" void raftx_ctx_destroy(raftx_ctx *c) {
     }
     delete[] c->slots;
     c->pool.trim();
-    if (c->pin) (void)hipHostFree(c->pin);
-    if (c->pinRes) (void)hipHostFree(c->pinRes);
-    if (c->pinModal) (void)hipHostFree(c->pinModal);
-    if (c->pinCur) (void)hipHostFree(c->pinCur);
+    c->pin.release();
+    c->pinRes.release();
+    c->pinModal.release();
+    c->pinCur.release();
     for (hipEvent_t e : {c->evZ, c->ev0, c->ev1, c->evUp, c->evTot, c->evG0, c->evG1, c->evG2, c->evG3, c->evS0, c->evS1, c->evDone,
                          c->evMem, c->evRed})
         (void)hipEventDestroy(e);
@@ -1242,16 +1259,6 @@ extern "C" int raftx_upload_designs(raftx_ctx *c, int nDesign, const int64_t *st
 constexpr size_t PIN_TOT = 0;                // [0..2] wet strips, MacCamy-Fuchs rows, strips of the largest design
 constexpr size_t PIN_ERR = 3;                // [3..4] the four error flags of GeomArgs::err, as ints
 constexpr size_t PIN_OFF = 8;                // [8 .. 8 + nDesign] strip offsets of the designs
-static int pin_reserve(raftx_ctx *c, size_t n) {
-    if (c->pin && c->pin_n >= n) return 0;
-    if (c->pin) HIPCHK(c, hipHostFree(c->pin));
-    c->pin = nullptr;
-    void *p_ = nullptr;
-    HIPCHK(c, hipHostMalloc(&p_, n * sizeof(long long), hipHostMallocDefault));
-    c->pin = reinterpret_cast<long long *>(p_);
-    c->pin_n = n;
-    return 0;
-}
 // The check of a design source's arrays, made once by the entry point that takes them.  Callers and tests read the texts:
 // `bad` is the entry point's own ("build_designs: bad arguments" | "sweep_stats: bad design arguments"), `who` its prefix.
 static int check_source(raftx_ctx *c, const BuildSource &B, int nDesign, const char *who, const char *bad) {
@@ -1423,14 +1430,14 @@ static int build_phase1(raftx_ctx *c, hipStream_t sCopy, hipStream_t sPrep, cons
     free_list(c, c->design_allocs);               // callers guarantee that nothing in flight reads the previous tables
     free_list(c, J.tmp);
     c->have_designs = false; c->bem_ready = false; c->g_n = 0;
-    if (pin_reserve(c, PIN_OFF + (size_t)nDesign + 1)) return -2;
+    HIPCHK(c, c->pin.reserve(PIN_OFF + (size_t)nDesign + 1));
     GeomArgs &A = J.A;
     memset(&A, 0, sizeof(A));
     A.nDesign = nDesign; A.nMember = L.m1 - L.m0;
     A.rho = B.rho; A.g = B.g; A.nw = B.nw; A.add_mask = B.add_mask;
     A.mbase = L.m0; A.sbase = L.s0; A.cbase = L.c0;
-    A.hostOut = c->pin;
-    memset(c->pin, 0, (PIN_OFF + 1) * sizeof(long long));
+    A.hostOut = c->pin.p;
+    memset(c->pin.p, 0, (PIN_OFF + 1) * sizeof(long long));
     J.nDesign = nDesign; J.nw = B.nw;
     ExpandArgs E;
     if (int rc = upload_descriptors(c, sCopy, B, L, E)) return rc;
@@ -1471,13 +1478,13 @@ static int wait_totals(raftx_ctx *c, int64_t *stripOffsets) {
         if (q != hipErrorNotReady) HIPCHK(c, q);
     }
     HIPCHK(c, hipGetLastError());
-    const int *bad = reinterpret_cast<const int *>(c->pin + PIN_ERR);
+    const int *bad = reinterpret_cast<const int *>(c->pin.p + PIN_ERR);
     if (bad[3] > 0) FAIL(c, "member %d: needs 2..%d stations, dlsMax > 0 and length > 0", bad[3] - 1, GEOM_MAX_STATIONS);
     if (bad[3] < 0) FAIL(c, "build_designs: member %d is MacCamy-Fuchs but no wave numbers were given", -bad[3] - 1);
     if (bad[0]) FAIL(c, "member %d: cap/bulkhead layout not supported (the reference raises here too)", bad[0] - 1);
     if (bad[1]) FAIL(c, "design %d: ballast trim needs some ballast volume", bad[1] - 1);
-    J.nStrips = (size_t)c->pin[PIN_TOT]; J.nRows = (size_t)c->pin[PIN_TOT + 1]; J.maxS = (int)c->pin[PIN_TOT + 2];
-    const long long *off = c->pin + PIN_OFF;
+    J.nStrips = (size_t)c->pin.p[PIN_TOT]; J.nRows = (size_t)c->pin.p[PIN_TOT + 1]; J.maxS = (int)c->pin.p[PIN_TOT + 2];
+    const long long *off = c->pin.p + PIN_OFF;
     if (stripOffsets) memcpy(stripOffsets, off, ((size_t)J.nDesign + 1) * sizeof(int64_t));
     c->hS.resize((size_t)J.nDesign);
     for (int d = 0; d < J.nDesign; d++) c->hS[(size_t)d] = (int)(off[d + 1] - off[d]);
@@ -2796,7 +2803,7 @@ extern "C" int raftx_flex_solve(raftx_ctx *c, int nUnit, const int64_t *nodeOff,
     if (!dM || !dB || !dC || !dTn || !dW || !dBn || !dBd || !dOff || !dNodeUnit || !dAct || !dNi || !dFl || !dCount || !dXiN || !dFn ||
         !dFlin || !dFw || !dFd || !dRhs || !dXnew || !dXi || !dXl || !dXh || (!(reg1 && regH) && !dA) || (Z && !dZ))
         FAIL(c, "flex_solve: device allocation failed");
-    if (pin_reserve(c, 16)) return -2;
+    HIPCHK(c, c->pin.reserve(16));
     H2D(c, dM, M, nM * sizeof(double));
     H2D(c, dB, B, nB * sizeof(double));
     H2D(c, dC, C, (size_t)nUnit * nn * sizeof(double));
@@ -2827,7 +2834,7 @@ extern "C" int raftx_flex_solve(raftx_ctx *c, int nUnit, const int64_t *nodeOff,
     HIPCHK(c, hipEventRecord(e0, c->stream));
     const int nt = (n + 15) / 16;
     const dim3 gridB((unsigned)((nt * nt + 3) / 4), (unsigned)nSys), gridF((unsigned)((nxs + 255) / 256), (unsigned)(nSys * nHead));
-    volatile int *hCount = reinterpret_cast<volatile int *>(c->pin);
+    volatile int *hCount = reinterpret_cast<volatile int *>(c->pin.p);
     int *dIter = sc.alloc<int>(1);
     if (!dIter) FAIL(c, "flex_solve: device allocation failed");
     HIPCHK(c, hipMemsetAsync(dIter, 0, sizeof(int), c->stream));
@@ -3141,16 +3148,31 @@ extern "C" int raftx_qtf_force(raftx_ctx *c, int nSet, int nw2, const double *w2
 }
 
 // ------------------------------------------------------------------ one-call sweep crossing
-// raftx_sweep_stats: the designs are cut into a few blocks, every block owns a block context (device tables, result
-// buffers, memory pool, events -- created on first use, kept by the parent ctx) and ONE host thread drives four streams:
-//   sCopy   descriptor H2D of every block, back to back (the first block is small, so its tables are ready early)
+// raftx_sweep_stats = prepare + launch + wait on a free slot.  The designs are cut into a few blocks, every block owns a
+// block context (device tables, result buffers, memory pool, events -- created on first use, kept by the parent ctx) and
+// ONE host thread drives the streams of the parent ctx.  The steps, and the streams each of them enqueues on:
+//   prepare  checks | crossing_streams (creates sCopy, sPrep, sD2H, sGen) | acquire_cases (pins the sea-state set) |
+//            cut_blocks | upload_offsets | block_phase1 of the first blocks
+//   launch   slab_streams (creates sSlab) | per block launch_block: phase1_ahead, gate_generation, build_phase2,
+//            hand_sea_states, solve_enqueue, enqueue_stats | stats_after_join (slab mode)
+//   wait     sweep_drain | solve_span | collect_block per block | debug_timeline
+//   sCopy   descriptor H2D of every block, back to back (the first block is small, so its tables are ready early); ahead of
+//           them the sea-state tables (acquire_cases), the offsets and the inputs of raftx_sweep_modal / raftx_sweep_current
 //   sPrep   member pass + scans of a block as soon as its descriptors have landed, totals to page-locked memory
+//           (block_phase1, from prepare or, one block ahead, from launch)
 //   stream  (the ctx stream; every kernel that matters) strip generation, per-design reduction, the fused fixed point
 //           and the statistics of block 0, 1, 2, ... strictly one after the other -- the HIP events around each
 //           k_solve_dynamics launch therefore time that launch alone
-//   sD2H    full responses of a finished block (only when the caller asks for Xi)
+//   sGen    strip generation of a crossing launched beside others (launch_block), gated by gate_generation; with
+//           sSlab[0..1] the streams the slabs of an isolated crossing with responses out go to (slab_streams, SlabPlan)
+//   sD2H    full responses, only when the caller asks for Xi (download_stream: sD2Hhigh where the device has priority
+//           classes): whole blocks from enqueue_stats, or slab by slab from the slab plan
 // The host waits only for the few bytes of totals that size a block's strip table (they are ready long before the
 // compute stream reaches the block) and, at the end, for the streams to drain.
+// The slot of an entry point as `SweepSlot &S`; an index out of range is refused under the entry point's own name.
+#define SLOT_REF(S, c, slot, who)                                                                          \
+    if ((slot) < 0 || (slot) >= RAFTX_NSLOT) FAIL(c, who ": slot must be 0 .. %d", RAFTX_NSLOT - 1);       \
+    SweepSlot &S = (c)->slots[slot]
 static int block_ctx(raftx_ctx *c, int slot, size_t i, raftx_ctx **out) {
     std::vector<raftx_ctx *> &W = c->workers[slot];
     while (W.size() <= i) {
@@ -3226,24 +3248,8 @@ static int sweep_fail_drain(raftx_ctx *c, SweepSlot &S, int rc) {
     return rc;
 }
 
-// what the solve of a crossing is given: fixed-point settings, block count, and the caller's outputs
-struct SweepRun { int nIter; double tol, XiStart; int nChunk; double *sd; int32_t *niter, *flags; raftx_c128 *Xi; int64_t *stripOffsets; };
-static int sweep_prepare_impl(raftx_ctx *c, int slot, int nDesign, const BuildSource &src, const SeaStates &sea, const SweepRun &run) {
-    RangeScope range_("raftx_sweep_prepare: descriptor H2D + member pass (enqueue)");
-    if (!c) return -1;
-    if (slot < 0 || slot >= RAFTX_NSLOT) FAIL(c, "sweep_prepare: slot must be 0 .. %d", RAFTX_NSLOT - 1);
-    SweepSlot &S = c->slots[slot];
-    if (S.busy || S.prepared) FAIL(c, "sweep_prepare: slot %d is still in flight (call raftx_sweep_wait first)", slot);
-    const int nCase = sea.nCase, nHead = sea.nHead, nw = sea.nw;
-    const double *w = sea.w, *k = sea.k, *zeta = sea.zeta, *beta = sea.beta;
-    if (int rc = check_source(c, src, nDesign, "sweep_stats", "bad design arguments")) return rc;
-    if (nCase < 1 || nHead < 1 || nw < 1 || !w || !k || !zeta || !beta) FAIL(c, "sweep_stats: bad sea-state arguments");
-    if (!run.sd || !run.niter || !run.flags) FAIL(c, "sweep_stats: std, niter and flags are required");
-    if (run.nIter < 0) FAIL(c, "sweep_stats: nIter < 0");
-    const int nChunk = std::min(run.nChunk, 64);
-    HIPCHK(c, hipSetDevice(c->device));
-    S.t0 = std::chrono::steady_clock::now();
-    auto since = [&]() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - S.t0).count(); };
+// the streams of the crossings, owned by the parent ctx and shared by its slots, and the slot's download marker
+static int crossing_streams(raftx_ctx *c, SweepSlot &S) {
     if (!c->sCopy) {
         // All four are ordinary streams (the generation stream in a high priority class lost: profiles/MEASUREMENT_HISTORY.md,
         // "Closed scheduling experiments of the crossing").  Measured (scripts/ubench/queue_probe2.hip, scripts/gpu_prep.sh): a HIGH-priority
@@ -3258,88 +3264,110 @@ static int sweep_prepare_impl(raftx_ctx *c, int slot, int nDesign, const BuildSo
         HIPCHK(c, hipStreamCreateWithFlags(&c->sGen, hipStreamNonBlocking));
     }
     if (!S.evXi) HIPCHK(c, hipEventCreate(&S.evXi));
-    // sea-state tables: sets resident on the parent, shared by the blocks of every slot that was prepared with the same
-    // tables; identical tables are not uploaded again.  The slot pins its set until it is retired (wait / cancel / failure),
-    // so other sea states prepared on another slot meanwhile get a set of their own and leave this one alone.
-    if (nw > MAX_NW) FAIL(c, "nw=%d exceeds the %d bins per workgroup supported by this build", nw, MAX_NW);
-    {
-        std::vector<double> key;
-        key.reserve((size_t)nw * 2 + (size_t)nCase * nHead * (nw + 1) + 6);
-        key.push_back(nCase); key.push_back(nHead); key.push_back(nw); key.push_back(sea.depth); key.push_back(sea.rho); key.push_back(sea.g);
-        key.insert(key.end(), w, w + nw);
-        key.insert(key.end(), k, k + nw);
-        key.insert(key.end(), zeta, zeta + (size_t)nCase * nHead * nw);
-        key.insert(key.end(), beta, beta + (size_t)nCase * nHead);
-        int hit = -1, idle = -1;
-        for (int i = 0; i <= RAFTX_NSLOT; i++) {
-            CaseSet &cs = c->csets[i];
-            if (!cs.key.empty() && cs.key.size() == key.size() && memcmp(key.data(), cs.key.data(), key.size() * sizeof(double)) == 0) hit = i;
-            else if (cs.users == 0 && (idle < 0 || cs.stamp < c->csets[idle].stamp)) idle = i;
-        }
-        if (hit < 0) {
-            if (idle < 0) FAIL(c, "sweep_prepare: no free sea-state set (every set is pinned by a crossing in flight)");   // cannot happen: NSLOT + 1 sets
-            CaseSet &cs = c->csets[idle];
-            cs.key.clear();
-            free_list(c, cs.allocs);                      // users == 0: every crossing that read it has been waited for
-            if (int rc = upload_case_tables(c, c->sCopy, cs.allocs, cs.T, sea)) {
-                free_list(c, cs.allocs);
-                return rc;
-            }
-            cs.key.swap(key);
-            hit = idle;
-        }
-        c->csets[hit].users++;
-        c->csets[hit].stamp = ++c->cset_clock;
-        S.cset = hit;
+    return 0;
+}
+// Sea-state tables: sets resident on the parent, shared by the blocks of every slot that was prepared with the same
+// tables; identical tables are not uploaded again (others: on sCopy, into the idle set used longest ago).  The slot pins
+// its set (S.cset) until it is retired (wait / cancel / failure), so other sea states prepared meanwhile leave it alone.
+static int acquire_cases(raftx_ctx *c, SweepSlot &S, const SeaStates &sea) {
+    const int nCase = sea.nCase, nHead = sea.nHead, nw = sea.nw;
+    std::vector<double> key;
+    key.reserve((size_t)nw * 2 + (size_t)nCase * nHead * (nw + 1) + 6);
+    key.push_back(nCase); key.push_back(nHead); key.push_back(nw); key.push_back(sea.depth); key.push_back(sea.rho); key.push_back(sea.g);
+    key.insert(key.end(), sea.w, sea.w + nw);
+    key.insert(key.end(), sea.k, sea.k + nw);
+    key.insert(key.end(), sea.zeta, sea.zeta + (size_t)nCase * nHead * nw);
+    key.insert(key.end(), sea.beta, sea.beta + (size_t)nCase * nHead);
+    int hit = -1, idle = -1;
+    for (int i = 0; i <= RAFTX_NSLOT; i++) {
+        CaseSet &cs = c->csets[i];
+        if (!cs.key.empty() && cs.key.size() == key.size() && memcmp(key.data(), cs.key.data(), key.size() * sizeof(double)) == 0) hit = i;
+        else if (cs.users == 0 && (idle < 0 || cs.stamp < c->csets[idle].stamp)) idle = i;
     }
-    const DevTables &CT = c->csets[S.cset].T;
-    S.bnd = sweep_bounds(nDesign, (long)nDesign * nCase, nChunk, others_in_flight(c, slot));
-    const std::vector<int> &bnd = S.bnd;
-    const size_t nB = bnd.size() - 1;
-    S.dw = nw > 1 ? w[1] - w[0] : w[0];
+    if (hit < 0) {
+        if (idle < 0) FAIL(c, "sweep_prepare: no free sea-state set (every set is pinned by a crossing in flight)");   // cannot happen: NSLOT + 1 sets
+        CaseSet &cs = c->csets[idle];
+        cs.key.clear();
+        free_list(c, cs.allocs);                      // users == 0: every crossing that read it has been waited for
+        if (int rc = upload_case_tables(c, c->sCopy, cs.allocs, cs.T, sea)) {
+            free_list(c, cs.allocs);
+            return rc;
+        }
+        cs.key.swap(key);
+        hit = idle;
+    }
+    c->csets[hit].users++;
+    c->csets[hit].stamp = ++c->cset_clock;
+    S.cset = hit;
+    return 0;
+}
+// what the solve of a crossing is given: fixed-point settings, block count, and the caller's outputs
+struct SweepRun { int nIter; double tol, XiStart; int nChunk; double *sd; int32_t *niter, *flags; raftx_c128 *Xi; int64_t *stripOffsets; };
+// The slot takes the crossing: block bounds, settings and outputs.  The slot's previous crossing has been waited for, so
+// what it kept on the device goes back to the pool.
+static void cut_blocks(raftx_ctx *c, int slot, int nDesign, const SeaStates &sea, const SweepRun &run) {
+    SweepSlot &S = c->slots[slot];
+    S.bnd = sweep_bounds(nDesign, (long)nDesign * sea.nCase, std::min(run.nChunk, 64), others_in_flight(c, slot));
+    S.dw = sea.nw > 1 ? sea.w[1] - sea.w[0] : sea.w[0];
     S.nIter = run.nIter; S.tol = run.tol; S.XiStart = run.XiStart;
-    S.blk.assign(nB, nullptr);
-    std::vector<raftx_ctx *> &blk = S.blk;
-    S.nCase = nCase; S.nHead = nHead; S.nw = nw;
+    S.blk.assign(S.bnd.size() - 1, nullptr);
+    S.nCase = sea.nCase; S.nHead = sea.nHead; S.nw = sea.nw;
     S.sd = run.sd; S.niter = run.niter; S.flags = run.flags; S.Xi = run.Xi; S.stripOffsets = run.stripOffsets;
-    S.tl[0] = since();
-    // the slot's previous crossing has been waited for: its tables and offset arrays are free
+    S.tl[0] = S.since();
     free_list(c, S.allocs);
-    S.modal.on = false;
-    S.current.on = false;
-    // ---- the batch's offset arrays: one upload, shared by the blocks; its wave numbers are those of the sea-state set
+    S.modal.on = S.current.on = false;
+}
+// The batch's offset arrays: one upload on sCopy, shared by the blocks; its wave numbers are those of the sea-state set.
+static int upload_offsets(raftx_ctx *c, SweepSlot &S, const BuildSource &src, int nDesign) {
     S.p1 = src;
-    S.p1.k_dev = CT.k;
-    {
-        const int64_t nMemberAll = src.memberOff[nDesign];
-        if (nMemberAll < 0) {
-            slot_release_cases(c, S);
-            FAIL(c, "sweep_stats: member offsets not monotone");
-        }
-        DevOffsets &dOff = S.p1.dOff;
-        int rc = upload_on(c, c->sCopy, S.allocs, src.memberOff, (size_t)nDesign + 1, &dOff.memberOff);
-        rc |= upload_on(c, c->sCopy, S.allocs, src.stationOff, (size_t)nMemberAll + 1, &dOff.stationOff);
-        if (src.capOff) rc |= upload_on(c, c->sCopy, S.allocs, src.capOff, (size_t)nMemberAll + 1, &dOff.capOff);
-        if (rc) return sweep_fail_drain(c, S, -2);
+    S.p1.k_dev = c->csets[S.cset].T.k;
+    const int64_t nMemberAll = src.memberOff[nDesign];
+    DevOffsets &dOff = S.p1.dOff;
+    int rc = upload_on(c, c->sCopy, S.allocs, src.memberOff, (size_t)nDesign + 1, &dOff.memberOff);
+    rc |= upload_on(c, c->sCopy, S.allocs, src.stationOff, (size_t)nMemberAll + 1, &dOff.stationOff);
+    if (src.capOff) rc |= upload_on(c, c->sCopy, S.allocs, src.capOff, (size_t)nMemberAll + 1, &dOff.capOff);
+    return rc ? -2 : 0;
+}
+// phase 1 of block b: descriptor H2D on sCopy, member pass + scans on sPrep
+static int block_phase1(raftx_ctx *c, SweepSlot &S, size_t b) {
+    return build_phase1(S.blk[b], c->sCopy, c->sPrep, S.p1, S.bnd[b], S.bnd[b + 1] - S.bnd[b]);
+}
+
+static int sweep_prepare_impl(raftx_ctx *c, int slot, int nDesign, const BuildSource &src, const SeaStates &sea, const SweepRun &run) {
+    RangeScope range_("raftx_sweep_prepare: descriptor H2D + member pass (enqueue)");
+    if (!c) return -1;
+    SLOT_REF(S, c, slot, "sweep_prepare");
+    if (S.busy || S.prepared) FAIL(c, "sweep_prepare: slot %d is still in flight (call raftx_sweep_wait first)", slot);
+    if (int rc = check_source(c, src, nDesign, "sweep_stats", "bad design arguments")) return rc;
+    if (sea.nCase < 1 || sea.nHead < 1 || sea.nw < 1 || !sea.w || !sea.k || !sea.zeta || !sea.beta) FAIL(c, "sweep_stats: bad sea-state arguments");
+    if (!run.sd || !run.niter || !run.flags) FAIL(c, "sweep_stats: std, niter and flags are required");
+    if (run.nIter < 0) FAIL(c, "sweep_stats: nIter < 0");
+    HIPCHK(c, hipSetDevice(c->device));
+    S.t0 = std::chrono::steady_clock::now();
+    if (int rc = crossing_streams(c, S)) return rc;
+    if (sea.nw > MAX_NW) FAIL(c, "nw=%d exceeds the %d bins per workgroup supported by this build", sea.nw, MAX_NW);
+    if (int rc = acquire_cases(c, S, sea)) return rc;
+    // ---- the set is pinned: every return below releases it (slot_release_cases; sweep_fail_drain once work is enqueued)
+    cut_blocks(c, slot, nDesign, sea, run);
+    if (src.memberOff[nDesign] < 0) {
+        slot_release_cases(c, S);
+        FAIL(c, "sweep_stats: member offsets not monotone");
     }
+    if (int rc = upload_offsets(c, S, src, nDesign)) return sweep_fail_drain(c, S, rc);
     // ---- phase 1: H2D on sCopy, member pass + scans on sPrep.  Every block here -- except for an isolated crossing cut into
     // slabs (responses wanted, nothing else in flight): there only the first two; raftx_sweep_launch enqueues the others one
     // block ahead of the block it launches.  (The ordinary streams share hardware queues: with every block's copies queued
     // first, the first slab's generation sat behind 1.7 ms of uploads -- profiles/r04_iso_timeline.txt.)
-    const size_t nFirst = (run.Xi && nB > 2 && !others_in_flight(c, slot)) ? 2 : nB;
+    const size_t nB = S.blk.size(), nFirst = (run.Xi && nB > 2 && !others_in_flight(c, slot)) ? 2 : nB;
     for (size_t b = 0; b < nB; b++)
-        if (block_ctx(c, slot, b, &blk[b])) return sweep_fail_drain(c, S, -1);
-    for (size_t b = 0; b < nFirst; b++) {
-        raftx_ctx *sub = blk[b];
-        const int lo = bnd[b], n = bnd[b + 1] - lo;
-        const int rc = build_phase1(sub, c->sCopy, c->sPrep, S.p1, lo, n);
-        if (rc) {
-            snprintf(c->err, sizeof(c->err), "sweep_stats (block %zu): %s", b, sub->err);
+        if (block_ctx(c, slot, b, &S.blk[b])) return sweep_fail_drain(c, S, -1);
+    for (size_t b = 0; b < nFirst; b++)
+        if (const int rc = block_phase1(c, S, b)) {
+            snprintf(c->err, sizeof(c->err), "sweep_stats (block %zu): %s", b, S.blk[b]->err);
             return sweep_fail_drain(c, S, rc);
         }
-    }
     S.next_p1 = nFirst;
-    S.tl[1] = since();
+    S.tl[1] = S.since();
     S.prepared = true;
     return 0;
 }
@@ -3480,8 +3508,8 @@ extern "C" int raftx_sweep_prepare_variants(raftx_ctx *c, int slot, int nDesign,
     VariantProg &P = c->vprog;
     if (!P.nM) FAIL(c, "sweep_prepare_variants: no program (raftx_variant_program first)");
     if (nDesign < 0 || (!params && nDesign && P.nP)) FAIL(c, "sweep_prepare_variants: bad arguments");
-    if (slot < 0 || slot >= RAFTX_NSLOT) FAIL(c, "sweep_prepare_variants: slot must be 0 .. %d", RAFTX_NSLOT - 1);
-    if (c->slots[slot].busy || c->slots[slot].prepared)   // before the cached offset arrays are touched: the batch on this slot reads them
+    SLOT_REF(S, c, slot, "sweep_prepare_variants");
+    if (S.busy || S.prepared)                       // before the cached offset arrays are touched: the batch on this slot reads them
         FAIL(c, "sweep_prepare_variants: slot %d is still in flight (call raftx_sweep_wait first)", slot);
     for (int sl = 0; sl < RAFTX_NSLOT; sl++)        // the offset arrays of batches in flight are the cached ones: one batch size at a time
         if (sl != slot && (c->slots[sl].busy || c->slots[sl].prepared) && c->slots[sl].p1.var.prog && P.cachedN != nDesign)
@@ -3501,22 +3529,11 @@ extern "C" int raftx_sweep_prepare_variants(raftx_ctx *c, int slot, int nDesign,
 // [fn n*6 | modes n*36 | props n*SP_N | flags n int32], which raftx_sweep_wait copies out.
 static hipError_t modal_block(raftx_ctx *sub, SweepSlot &S, int lo, int n, hipStream_t st) {
     const size_t need = (size_t)n * (42 + RAFTX_SP_N) + ((size_t)n + 1) / 2;
-    if (!sub->pinModal || sub->pinModal_n < need) {
-        if (sub->pinModal) (void)hipHostFree(sub->pinModal);
-        sub->pinModal = nullptr;
-        sub->pinModal_n = 0;
-        void *p_ = nullptr;
-        const hipError_t e = hipHostMalloc(&p_, need * sizeof(double), hipHostMallocDefault);
-        if (e != hipSuccess) return e;
-        sub->pinModal = reinterpret_cast<double *>(p_);
-        sub->pinModal_n = need;
-    }
-    if (n == 0) return hipSuccess;
-    if (S.modal.evUp) {
-        const hipError_t e = hipStreamWaitEvent(st, S.modal.evUp, 0);
-        if (e != hipSuccess) return e;
-    }
-    double *pm = sub->pinModal;
+    hipError_t e = sub->pinModal.reserve(need);
+    if (e != hipSuccess || n == 0) return e;
+    if (S.modal.evUp) e = hipStreamWaitEvent(st, S.modal.evUp, 0);
+    if (e != hipSuccess) return e;
+    double *pm = sub->pinModal.p;
     ModalArgs A;
     A.n = n;
     A.M = sub->T.M0;
@@ -3536,20 +3553,10 @@ static hipError_t modal_block(raftx_ctx *sub, SweepSlot &S, int lo, int n, hipSt
 // the block's strip tables are resident until the block is retired.  One wave per (design, tile of currents), the sums
 // written straight into the block's page-locked landing area [n,nCur,6], which raftx_sweep_wait copies out.
 static hipError_t current_block(raftx_ctx *sub, SweepSlot &S, int lo, int n, double depth, hipStream_t st) {
-    const size_t need = (size_t)n * S.current.nCur * 6;
-    if (!sub->pinCur || sub->pinCur_n < need) {
-        if (sub->pinCur) (void)hipHostFree(sub->pinCur);
-        sub->pinCur = nullptr;
-        sub->pinCur_n = 0;
-        void *p_ = nullptr;
-        const hipError_t e = hipHostMalloc(&p_, (need ? need : 1) * sizeof(double), hipHostMallocDefault);
-        if (e != hipSuccess) return e;
-        sub->pinCur = reinterpret_cast<double *>(p_);
-        sub->pinCur_n = need;
-    }
-    if (n == 0) return hipSuccess;
+    hipError_t e = sub->pinCur.reserve((size_t)n * S.current.nCur * 6);
+    if (e != hipSuccess || n == 0) return e;
     if (sub->T.nDesign != n || !sub->T.off || !sub->T.ds || !sub->T.dsi) return hipErrorInvalidValue;   // (the block kept no tables: internal error)
-    const hipError_t e = hipStreamWaitEvent(st, S.current.evUp, 0);
+    e = hipStreamWaitEvent(st, S.current.evUp, 0);
     if (e != hipSuccess) return e;
     CurrentArgs A;
     A.nDesign = n; A.nCur = S.current.nCur;
@@ -3557,7 +3564,7 @@ static hipError_t current_block(raftx_ctx *sub, SweepSlot &S, int lo, int n, dou
     A.par = S.current.par;
     A.Zref = S.current.Zref ? S.current.Zref + lo : nullptr;
     A.depth = depth; A.shearExp = S.current.shearExp;
-    A.D = sub->pinCur;
+    A.D = sub->pinCur.p;
     hipLaunchKernelGGL(k_current_loads, dim3(current_grid(n, A.nCur)), dim3(64 * CUR_WAVES), 0, st, A);
     return hipGetLastError();
 }
@@ -3586,8 +3593,8 @@ static int enqueue_stats(raftx_ctx *c, SweepSlot &S, size_t b, hipStream_t sDown
     hipError_t e = hipEventRecord(sub->evS0, c->stream);
     if (npair) {
         hipLaunchKernelGGL(k_motion_stats, dim3((unsigned)npair), dim3(nw > 128 ? 256 : (nw > 64 ? 128 : 64)), 0, c->stream,
-                           (int)npair, nHead, nw, 1.0 / S.dw, sub->rXi, sub->pinRes, (double *)nullptr, (const int *)sub->rNi,
-                           (const int *)sub->rFl, reinterpret_cast<int *>(sub->pinRes + npair * 6));
+                           (int)npair, nHead, nw, 1.0 / S.dw, sub->rXi, sub->pinRes.p, (double *)nullptr, (const int *)sub->rNi,
+                           (const int *)sub->rFl, reinterpret_cast<int *>(sub->pinRes.p + npair * 6));
     }
     if (e == hipSuccess) e = hipEventRecord(sub->evS1, c->stream);
     if (e == hipSuccess && S.modal.on) e = modal_block(sub, S, lo, S.bnd[b + 1] - lo, c->stream);
@@ -3637,11 +3644,92 @@ static void slab_plan_block(SlabPlan &plan, SweepSlot &S, size_t b, size_t slab_
     };
 }
 
+// what raftx_sweep_launch decides once for all blocks of a crossing (with SweepSlot::slab): other crossings are prepared or
+// solving | the download stream, or null: no responses asked for | pairs per slab and the plan of the block being launched
+struct LaunchMode { bool pipelined; hipStream_t sDown; size_t slab_pairs; SlabPlan plan; };
+// the streams the slabs go to: the generation stream first, then the two slab streams (created when first needed)
+static int slab_streams(raftx_ctx *c, int n, SlabPlan &plan) {
+    hipStream_t *ss[3] = {&c->sGen, &c->sSlab[0], &c->sSlab[1]};
+    for (int i = 0; i < n; i++) {
+        if (!*ss[i]) HIPCHK(c, hipStreamCreateWithFlags(ss[i], hipStreamNonBlocking));
+        plan.alts.push_back(*ss[i]);
+    }
+    return 0;
+}
+// deferred phase 1: keeps one block's upload ahead of block b, the block being launched (whose err takes the text)
+static int phase1_ahead(raftx_ctx *c, SweepSlot &S, size_t b) {
+    if (S.next_p1 >= S.blk.size() || S.next_p1 > b + 1) return 0;
+    const size_t bn = S.next_p1++;
+    const int rc = block_phase1(c, S, bn);
+    if (rc) snprintf(S.blk[b]->err, sizeof(S.blk[b]->err), "%s", S.blk[bn]->err);
+    return rc;
+}
+// A crossing launched while another one is solving generates its tables on the generation stream: its member pass ran
+// a step earlier (raftx_sweep_prepare), so the tables can be built in the drain of the running fused kernel.  (The
+// blocks of an isolated crossing wait for their descriptor upload: everything on the ctx stream,
+// profiles/r02_crossing_splits.txt.)  Enqueued now, beside a fused kernel that has only just started, the generation
+// would be dispatched at once and take LDS from that kernel for its whole run (measured: +0.25 ms on the kernel).  A
+// small kernel queued BEHIND a running big grid is dispatched when that grid has been handed out -- which is when
+// the member pass of the batch prepared last gets onto the chip: the generation waits for that batch's first
+// kernel and so runs in the drain, beside that member pass.
+static int gate_generation(raftx_ctx *c, int slot) {
+    for (int sl = 0; sl < RAFTX_NSLOT; sl++)
+        if (sl != slot && c->slots[sl].prepared && !c->slots[sl].blk.empty() && c->slots[sl].blk[0])
+            if (hipStreamWaitEvent(c->sGen, c->slots[sl].blk[0]->evZ, 0) != hipSuccess) return -2;
+    return 0;
+}
+// the sea states a crossing was prepared with (the pinned set P of the parent) become those of a block's tables
+static void hand_sea_states(const DevTables &P, raftx_ctx *sub) {
+    DevTables &T = sub->T;
+    T.nCase = P.nCase; T.nHead = P.nHead; T.nw = P.nw;
+    T.w = P.w; T.k = P.k; T.csh = P.csh; T.cch = P.cch; T.zeta = P.zeta; T.beta = P.beta;
+    T.depth = P.depth; T.rho = P.rho; T.g = P.g;
+    sub->have_cases = true;
+}
+// Phase 2 + fixed point + statistics of block b on the ctx stream, behind the blocks before it (the scheduling variants that
+// lost -- a second compute stream among them: profiles/MEASUREMENT_HISTORY.md, "Closed scheduling experiments of the crossing").
+static int launch_block(raftx_ctx *c, SweepSlot &S, int slot, size_t b, LaunchMode &M) {
+    raftx_ctx *sub = S.blk[b];
+    int rc = phase1_ahead(c, S, b);
+    if (!rc && b == 0 && M.pipelined) rc = gate_generation(c, slot);
+    S.tlb.push_back(S.since());
+    // (a crossing: no ABI copy of the strip records; with RAFTX_FUSED_GEN=1 the tables are left to the fused kernel itself,
+    // raftx_fusedgen.h -- build_phase2 / solve_enqueue decide)
+    // (a crossing with current loads reads the tables after the solve: they are never left to the fused kernel)
+    const int kind = GEN_CROSSING | ((S.nCase == 1 && !S.slab && !S.current.on) ? GEN_MAY_DEFER : 0) | (M.pipelined ? GEN_PIPELINED : 0);
+    if (!rc) rc = build_phase2(sub, nullptr, M.pipelined ? c->sGen : nullptr, kind);
+    S.tlb.push_back(S.since());
+    if (!rc) {
+        hand_sea_states(c->csets[S.cset].T, sub);
+        if (S.slab) slab_plan_block(M.plan, S, b, M.slab_pairs, M.sDown);
+        rc = solve_enqueue(sub, S.nIter, S.tol, S.XiStart, nullptr, 0, S.slab ? &M.plan : nullptr);
+    }
+    const size_t need = (size_t)(S.bnd[b + 1] - S.bnd[b]) * S.nCase * 7 + 2;   // std [npair,6] | niter, flags [npair] int32 each
+    if (!rc && sub->pinRes.reserve(need) != hipSuccess) rc = -2;
+    if (!rc && !S.slab) rc = enqueue_stats(c, S, b, M.sDown);         // (slab mode: stats_after_join)
+    S.tlb.push_back(S.since());
+    if (rc) snprintf(c->err, sizeof(c->err), "sweep_stats (block %zu): %s", b, sub->err);
+    return rc;
+}
+// slab mode: the statistics read what the slabs wrote, so they go behind all of them, joined into the ctx stream
+static int stats_after_join(raftx_ctx *c, SweepSlot &S, LaunchMode &M) {
+    const size_t nB = S.blk.size();
+    if (!nB) return 0;
+    if (!S.blk[0]->evJoin && hipEventCreateWithFlags(&S.blk[0]->evJoin, hipEventDisableTiming) != hipSuccess) return -2;
+    if (int rc = slab_join(S.blk[0], c->stream, M.plan.alts)) return rc;
+    if (hipEventRecord(S.blk[nB - 1]->ev1, c->stream) != hipSuccess) return -2;
+    for (size_t b = 0; b < nB; b++)
+        if (int rc = enqueue_stats(c, S, b, M.sDown)) {
+            snprintf(c->err, sizeof(c->err), "sweep_stats (block %zu): %s", b, S.blk[b]->err);
+            return rc;
+        }
+    return 0;
+}
+
 extern "C" int raftx_sweep_launch(raftx_ctx *c, int slot) {
     RangeScope range_("raftx_sweep_launch: generation + fused fixed point + statistics (enqueue)");
     if (!c) return -1;
-    if (slot < 0 || slot >= RAFTX_NSLOT) FAIL(c, "sweep_launch: slot must be 0 .. %d", RAFTX_NSLOT - 1);
-    SweepSlot &S = c->slots[slot];
+    SLOT_REF(S, c, slot, "sweep_launch");
     if (!S.prepared) FAIL(c, "sweep_launch: nothing prepared on slot %d (raftx_sweep_prepare first)", slot);
     if (S.cset < 0 || c->csets[S.cset].T.nCase != S.nCase || c->csets[S.cset].T.nHead != S.nHead || c->csets[S.cset].T.nw != S.nw)
         FAIL(c, "sweep_launch: slot %d has lost its sea-state tables (internal error)", slot);
@@ -3650,98 +3738,20 @@ extern "C" int raftx_sweep_launch(raftx_ctx *c, int slot) {
         HIPCHK(c, hipEventCreate(&c->evEpoch));
         HIPCHK(c, hipEventRecord(c->evEpoch, c->stream));
     }
-    auto since = [&]() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - S.t0).count(); };
-    const std::vector<int> &bnd = S.bnd;
-    const size_t nB = bnd.size() - 1;
-    std::vector<raftx_ctx *> &blk = S.blk;
-    const int nCase = S.nCase;
-    S.prepared = false;
+    S.prepared = false;                                 // from here on every failure goes through sweep_fail_drain
     // ---- full responses, if asked for: every block's download is enqueued right behind the block's kernels (after ALL blocks,
     // the first download of an isolated call waited for the host to see the member pass of the LAST block: 1.6 ms late)
-    hipStream_t sDown = S.Xi ? download_stream(c) : nullptr;
-    // ---- phase 2 + fixed point + statistics of every block, in order, on the ctx stream (the scheduling variants that lost --
-    // a second compute stream among them: profiles/MEASUREMENT_HISTORY.md, "Closed scheduling experiments of the crossing")
-    int rc_all = 0;
     static const long slab_pairs = getenv("RAFTX_XI_SLAB_PAIRS") ? atol(getenv("RAFTX_XI_SLAB_PAIRS")) : 1024;
-    static const int slab_streams = getenv("RAFTX_XI_SLAB_STREAMS") ? std::min(3, std::max(1, atoi(getenv("RAFTX_XI_SLAB_STREAMS")))) : 1;
-    const bool pipelined = others_in_flight(c, slot);
-    const bool slab_mode = S.Xi && sDown && slab_pairs > 0 && !pipelined;
-    SlabPlan plan;
-    S.slab = slab_mode;
-    if (slab_mode) {
-        hipStream_t *ss[3] = {&c->sGen, &c->sSlab[0], &c->sSlab[1]};
-        for (int i = 0; i < slab_streams; i++) {
-            if (!*ss[i]) HIPCHK(c, hipStreamCreateWithFlags(ss[i], hipStreamNonBlocking));
-            plan.alts.push_back(*ss[i]);
-        }
-    }
+    static const int slab_streams_n = getenv("RAFTX_XI_SLAB_STREAMS") ? std::min(3, std::max(1, atoi(getenv("RAFTX_XI_SLAB_STREAMS")))) : 1;
+    LaunchMode M{others_in_flight(c, slot), S.Xi ? download_stream(c) : nullptr, (size_t)slab_pairs, {}};
+    S.slab = S.Xi && M.sDown && slab_pairs > 0 && !M.pipelined;
     S.tlb.clear();
-    for (size_t b = 0; b < nB && !rc_all; b++) {
-        raftx_ctx *sub = blk[b];
-        int rc = 0;
-        if (S.next_p1 < nB && S.next_p1 <= b + 1) {                     // deferred phase 1: keep one block's upload ahead
-            const size_t bn = S.next_p1++;
-            rc = build_phase1(blk[bn], c->sCopy, c->sPrep, S.p1, bnd[bn], bnd[bn + 1] - bnd[bn]);
-            if (rc) snprintf(sub->err, sizeof(sub->err), "%s", blk[bn]->err);
-        }
-        // A crossing launched while another one is solving generates its tables on the generation stream: its member pass ran
-        // a step earlier (raftx_sweep_prepare), so the tables can be built in the drain of the running fused kernel.  (The
-        // blocks of an isolated crossing wait for their descriptor upload: everything on the ctx stream,
-        // profiles/r02_crossing_splits.txt.)  Enqueued now, beside a fused kernel that has only just started, the generation
-        // would be dispatched at once and take LDS from that kernel for its whole run (measured: +0.25 ms on the kernel).  A
-        // small kernel queued BEHIND a running big grid is dispatched when that grid has been handed out -- which is when
-        // the member pass of the batch prepared last gets onto the chip: the generation waits for that batch's first
-        // kernel and so runs in the drain, beside that member pass.
-        if (b == 0 && pipelined) {
-            for (int sl = 0; sl < RAFTX_NSLOT && !rc; sl++)
-                if (sl != slot && c->slots[sl].prepared && !c->slots[sl].blk.empty() && c->slots[sl].blk[0])
-                    if (hipStreamWaitEvent(c->sGen, c->slots[sl].blk[0]->evZ, 0) != hipSuccess) rc = -2;
-        }
-        S.tlb.push_back(since());
-        // (a crossing: no ABI copy of the strip records; with RAFTX_FUSED_GEN=1 the tables are left to the fused kernel itself,
-        // raftx_fusedgen.h -- build_phase2 / solve_enqueue decide)
-        // (a crossing with current loads reads the tables after the solve: they are never left to the fused kernel)
-        const int kind = GEN_CROSSING | ((nCase == 1 && !slab_mode && !S.current.on) ? GEN_MAY_DEFER : 0) | (pipelined ? GEN_PIPELINED : 0);
-        if (!rc) rc = build_phase2(sub, nullptr, pipelined ? c->sGen : nullptr, kind);
-        S.tlb.push_back(since());
-        if (!rc) {                                                      // the sea states this crossing was prepared with
-            DevTables &T = sub->T;
-            const DevTables &P = c->csets[S.cset].T;
-            T.nCase = P.nCase; T.nHead = P.nHead; T.nw = P.nw;
-            T.w = P.w; T.k = P.k; T.csh = P.csh; T.cch = P.cch; T.zeta = P.zeta; T.beta = P.beta;
-            T.depth = P.depth; T.rho = P.rho; T.g = P.g;
-            sub->have_cases = true;
-            if (slab_mode) slab_plan_block(plan, S, b, (size_t)slab_pairs, sDown);
-            rc = solve_enqueue(sub, S.nIter, S.tol, S.XiStart, nullptr, 0, slab_mode ? &plan : nullptr);
-        }
-        const size_t need = (size_t)(bnd[b + 1] - bnd[b]) * nCase * 7 + 2;   // std [npair,6] | niter, flags [npair] int32 each
-        if (!rc && (!sub->pinRes || sub->pinRes_n < need)) {
-            if (sub->pinRes) (void)hipHostFree(sub->pinRes);
-            sub->pinRes = nullptr;
-            void *p_ = nullptr;
-            if (hipHostMalloc(&p_, need * sizeof(double), hipHostMallocDefault) != hipSuccess) rc = -2;
-            sub->pinRes = reinterpret_cast<double *>(p_);
-            sub->pinRes_n = need;
-        }
-        if (!rc && !slab_mode) rc = enqueue_stats(c, S, b, sDown);      // (slab mode: after the join, below)
-        S.tlb.push_back(since());
-        if (rc) {
-            snprintf(c->err, sizeof(c->err), "sweep_stats (block %zu): %s", b, sub->err);
-            rc_all = rc;
-        }
-    }
-    if (!rc_all && slab_mode) {                                         // the statistics read what the slabs wrote: behind all of them
-        if (!blk[0]->evJoin && hipEventCreateWithFlags(&blk[0]->evJoin, hipEventDisableTiming) != hipSuccess) rc_all = -2;
-        if (!rc_all) rc_all = slab_join(blk[0], c->stream, plan.alts);
-        if (!rc_all && hipEventRecord(blk[nB - 1]->ev1, c->stream) != hipSuccess) rc_all = -2;
-        for (size_t b = 0; b < nB && !rc_all; b++) {
-            rc_all = enqueue_stats(c, S, b, sDown);
-            if (rc_all) snprintf(c->err, sizeof(c->err), "sweep_stats (block %zu): %s", b, blk[b]->err);
-        }
-    }
-    if (!rc_all && S.Xi && hipEventRecord(S.evXi, sDown) != hipSuccess) rc_all = -2;
-    if (rc_all) return sweep_fail_drain(c, S, rc_all);
-    S.tl[2] = since();
+    int rc = S.slab ? slab_streams(c, slab_streams_n, M.plan) : 0;
+    for (size_t b = 0; b < S.blk.size() && !rc; b++) rc = launch_block(c, S, slot, b, M);
+    if (!rc && S.slab) rc = stats_after_join(c, S, M);
+    if (!rc && S.Xi && hipEventRecord(S.evXi, M.sDown) != hipSuccess) rc = -2;
+    if (rc) return sweep_fail_drain(c, S, rc);
+    S.tl[2] = S.since();
     S.busy = true;
     return 0;
 }
@@ -3766,8 +3776,7 @@ extern "C" int raftx_sweep_submit(raftx_ctx *c, int slot, int nDesign, const int
 // sea-state set released; the output arrays given at prepare time are not touched.
 extern "C" int raftx_sweep_cancel(raftx_ctx *c, int slot) {
     if (!c) return -1;
-    if (slot < 0 || slot >= RAFTX_NSLOT) FAIL(c, "sweep_cancel: slot must be 0 .. %d", RAFTX_NSLOT - 1);
-    SweepSlot &S = c->slots[slot];
+    SLOT_REF(S, c, slot, "sweep_cancel");
     if (S.busy) FAIL(c, "sweep_cancel: slot %d has been launched (raftx_sweep_wait collects it)", slot);
     if (!S.prepared) return 0;
     HIPCHK(c, hipSetDevice(c->device));
@@ -3780,106 +3789,120 @@ extern "C" int raftx_sweep_cancel(raftx_ctx *c, int slot) {
             build_abandon(sub);
         }
     S.prepared = false;
-    S.modal.on = false;
-    S.current.on = false;
+    S.modal.on = S.current.on = false;
     slot_release_cases(c, S);
     HIPCHK(c, e);
     return 0;
 }
 
-extern "C" int raftx_sweep_wait(raftx_ctx *c, int slot, double *timing_ms) {
-    RangeScope range_("raftx_sweep_wait: drain + outputs");
-    if (!c) return -1;
-    if (slot < 0 || slot >= RAFTX_NSLOT) FAIL(c, "sweep_wait: slot must be 0 .. %d", RAFTX_NSLOT - 1);
-    SweepSlot &S = c->slots[slot];
-    if (!S.busy) FAIL(c, "sweep_wait: nothing submitted on slot %d", slot);
-    HIPCHK(c, hipSetDevice(c->device));
-    static const bool dbg_host = getenv("RAFTX_SWEEP_DEBUG") != nullptr;
-    auto since = [&]() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - S.t0).count(); };
-    const size_t nB = S.blk.size();
-    S.busy = false;
-    hipError_t es = nB ? hipEventSynchronize(S.blk[nB - 1]->evDone) : hipSuccess;     // the ctx stream is in order: all blocks are done
-    S.tl[3] = since();
+// Waits for the last block's statistics (the ctx stream is in order: all blocks are done), then for the responses.  Either
+// way the sea-state set is released; a failure also drains the device and abandons the jobs of the blocks.
+static hipError_t sweep_drain(raftx_ctx *c, SweepSlot &S) {
+    hipError_t es = S.blk.empty() ? hipSuccess : hipEventSynchronize(S.blk.back()->evDone);
+    S.tl[3] = S.since();
     if (es == hipSuccess && S.Xi) es = hipEventSynchronize(S.evXi);
     if (es == hipSuccess) es = hipGetLastError();
     if (es == hipSuccess) slot_release_cases(c, S);
-    if (es != hipSuccess) {
-        (void)hipDeviceSynchronize();
-        slot_release_cases(c, S);
-        for (raftx_ctx *sub : S.blk) build_abandon(sub);
-        HIPCHK(c, es);
-    }
-    double tb = 0, ts = 0, tst = 0;
+    else (void)sweep_fail_drain(c, S, -2);
+    return es;
+}
+// ms from one event to another, best effort: a timing query must not lose the results of work that has been waited for.
+// On an error the value is zero, *ok (if given) is cleared, and the error does not stay behind for a later call to find.
+static double elapsed_ms(hipEvent_t from, hipEvent_t to, bool *ok = nullptr) {
+    float ms = 0.f;
+    if (hipEventElapsedTime(&ms, from, to) == hipSuccess) return ms;
+    (void)hipGetLastError();
+    if (ok) *ok = false;
+    return 0.0;
+}
+// where the fused launches of the crossing ran, ms since the ctx epoch (both zero: no span)
+static void solve_span(raftx_ctx *c, SweepSlot &S) {
     S.span[0] = S.span[1] = 0;
-    if (nB && c->evEpoch) {
-        float a = 0.f, b_ = 0.f;
-        HIPCHK(c, hipEventElapsedTime(&a, c->evEpoch, S.blk[0]->ev0));
-        HIPCHK(c, hipEventElapsedTime(&b_, c->evEpoch, S.blk[nB - 1]->ev1));
-        S.span[0] = a;
-        S.span[1] = b_;
+    if (S.blk.empty() || !c->evEpoch) return;
+    bool ok = true;
+    const double a = elapsed_ms(c->evEpoch, S.blk[0]->ev0, &ok), b = elapsed_ms(c->evEpoch, S.blk.back()->ev1, &ok);
+    if (ok) { S.span[0] = a; S.span[1] = b; }
+}
+// Block b of a crossing that has been waited for: its kernel times into t [.., generation, solve, statistics], its strip
+// offsets and landing areas out to the caller's arrays, its job retired.
+static void collect_block(SweepSlot &S, size_t b, double *t) {
+    raftx_ctx *sub = S.blk[b];
+    const int lo = S.bnd[b], n = S.bnd[b + 1] - lo;
+    const size_t npair = (size_t)n * S.nCase, p0 = (size_t)lo * S.nCase, nB = S.blk.size();
+    // slabs on their own streams: the span from the first block's first launch to the last slab's end (the generation
+    // of the later blocks runs inside it)
+    if (!S.slab) t[2] += elapsed_ms(sub->ev0, sub->ev1);
+    else if (b + 1 == nB) t[2] += elapsed_ms(S.blk[0]->ev0, sub->ev1);
+    t[3] += elapsed_ms(sub->evS0, sub->evS1);
+    if (S.stripOffsets)                                                 // block-relative offsets of phase 1 -> batch offsets
+        for (int i = 0; i < n; i++) S.stripOffsets[lo + i + 1] = S.stripOffsets[lo] + sub->pin.p[PIN_OFF + i + 1];
+    if (sub->job.active) t[1] += elapsed_ms(sub->evG2, sub->evG3) + elapsed_ms(sub->evG0, sub->evG1);   // (as build_retire)
+    build_abandon(sub);
+    const double *res = sub->pinRes.p;
+    memcpy(S.sd + p0 * 6, res, npair * 6 * sizeof(double));
+    memcpy(S.niter + p0, res + npair * 6, npair * sizeof(int));
+    memcpy(S.flags + p0, reinterpret_cast<const int *>(res + npair * 6) + npair, npair * sizeof(int));
+    if (S.modal.on) {
+        const double *pm = sub->pinModal.p;
+        memcpy(S.modal.fn + (size_t)lo * 6, pm, (size_t)n * 6 * sizeof(double));
+        memcpy(S.modal.modes + (size_t)lo * 36, pm + (size_t)n * 6, (size_t)n * 36 * sizeof(double));
+        if (S.modal.props)
+            memcpy(S.modal.props + (size_t)lo * RAFTX_SP_N, pm + (size_t)n * 42, (size_t)n * RAFTX_SP_N * sizeof(double));
+        memcpy(S.modal.flags + lo, pm + (size_t)n * (42 + RAFTX_SP_N), (size_t)n * sizeof(int32_t));
     }
+    if (S.current.on && n)
+        memcpy(S.current.D + (size_t)lo * S.current.nCur * 6, sub->pinCur.p, (size_t)n * S.current.nCur * 6 * sizeof(double));
+}
+// RAFTX_SWEEP_DEBUG: the host's timeline of the crossing on stderr
+static void debug_timeline(const SweepSlot &S, int slot, double wall) {
+    static const bool dbg_host = getenv("RAFTX_SWEEP_DEBUG") != nullptr;
+    if (!dbg_host) return;
+    fprintf(stderr, "[raftx_sweep slot %d] host ms since submit: pre %.3f | phase-1 enqueued %.3f | phase-2 enqueued %.3f | ctx stream "
+            "reached the end %.3f | done %.3f\n", slot, S.tl[0], S.tl[1], S.tl[2], S.tl[3], wall);
+    if (S.tlb.size() <= 3) return;
+    fprintf(stderr, "[raftx_sweep slot %d] launch loop, host ms per block (next upload enqueued | totals seen | block enqueued):", slot);
+    for (size_t i = 0; i + 2 < S.tlb.size(); i += 3) fprintf(stderr, "  %.3f %.3f %.3f", S.tlb[i], S.tlb[i + 1], S.tlb[i + 2]);
+    fprintf(stderr, "\n");
+}
+
+// Two ways out of a busy slot: the drain failed (-2; nothing copied, blocks abandoned) or not (0; every block collected and
+// retired, whatever the timing queries said).  Both leave the slot idle, without eigen-analysis / current-load requests.
+extern "C" int raftx_sweep_wait(raftx_ctx *c, int slot, double *timing_ms) {
+    RangeScope range_("raftx_sweep_wait: drain + outputs");
+    if (!c) return -1;
+    SLOT_REF(S, c, slot, "sweep_wait");
+    if (!S.busy) FAIL(c, "sweep_wait: nothing submitted on slot %d", slot);
+    HIPCHK(c, hipSetDevice(c->device));
+    S.busy = false;
+    const hipError_t es = sweep_drain(c, S);
+    if (es != hipSuccess) S.modal.on = S.current.on = false;
+    HIPCHK(c, es);
+    solve_span(c, S);
+    double t[4] = {0, 0, 0, 0};                           // wall | generation, solve, statistics kernels
     if (S.stripOffsets) S.stripOffsets[0] = 0;
-    for (size_t b = 0; b < nB; b++) {
-        raftx_ctx *sub = S.blk[b];
-        const int lo = S.bnd[b], n = S.bnd[b + 1] - lo;
-        const size_t npair = (size_t)n * S.nCase, p0 = (size_t)lo * S.nCase;
-        float ms = 0.f;
-        // slabs on their own streams: the span from the first block's first launch to the last slab's end (the generation
-        // of the later blocks runs inside it)
-        if (!S.slab) HIPCHK(c, hipEventElapsedTime(&ms, sub->ev0, sub->ev1));
-        else if (b + 1 == nB) HIPCHK(c, hipEventElapsedTime(&ms, S.blk[0]->ev0, sub->ev1));
-        ts += ms;
-        HIPCHK(c, hipEventElapsedTime(&ms, sub->evS0, sub->evS1));
-        tst += ms;
-        double g_ms = 0.0;
-        if (S.stripOffsets)                                             // block-relative offsets of phase 1 -> batch offsets
-            for (int i = 0; i < n; i++) S.stripOffsets[lo + i + 1] = S.stripOffsets[lo] + sub->pin[8 + i + 1];
-        if (build_retire(sub, &g_ms)) return -2;
-        tb += g_ms;
-        memcpy(S.sd + p0 * 6, sub->pinRes, npair * 6 * sizeof(double));
-        memcpy(S.niter + p0, sub->pinRes + npair * 6, npair * sizeof(int));
-        memcpy(S.flags + p0, reinterpret_cast<int *>(sub->pinRes + npair * 6) + npair, npair * sizeof(int));
-        if (S.modal.on) {
-            const double *pm = sub->pinModal;
-            memcpy(S.modal.fn + (size_t)lo * 6, pm, (size_t)n * 6 * sizeof(double));
-            memcpy(S.modal.modes + (size_t)lo * 36, pm + (size_t)n * 6, (size_t)n * 36 * sizeof(double));
-            if (S.modal.props)
-                memcpy(S.modal.props + (size_t)lo * RAFTX_SP_N, pm + (size_t)n * 42, (size_t)n * RAFTX_SP_N * sizeof(double));
-            memcpy(S.modal.flags + lo, pm + (size_t)n * (42 + RAFTX_SP_N), (size_t)n * sizeof(int32_t));
-        }
-        if (S.current.on && n)
-            memcpy(S.current.D + (size_t)lo * S.current.nCur * 6, sub->pinCur, (size_t)n * S.current.nCur * 6 * sizeof(double));
-    }
-    S.modal.on = false;
-    S.current.on = false;
-    const double wall = since();
-    if (dbg_host)
-        fprintf(stderr, "[raftx_sweep slot %d] host ms since submit: pre %.3f | phase-1 enqueued %.3f | phase-2 enqueued %.3f | ctx stream "
-                "reached the end %.3f | done %.3f\n", slot, S.tl[0], S.tl[1], S.tl[2], S.tl[3], wall);
-    if (dbg_host && S.tlb.size() > 3) {
-        fprintf(stderr, "[raftx_sweep slot %d] launch loop, host ms per block (next upload enqueued | totals seen | block enqueued):", slot);
-        for (size_t i = 0; i + 2 < S.tlb.size(); i += 3) fprintf(stderr, "  %.3f %.3f %.3f", S.tlb[i], S.tlb[i + 1], S.tlb[i + 2]);
-        fprintf(stderr, "\n");
-    }
-    if (timing_ms) { timing_ms[0] = wall; timing_ms[1] = tb; timing_ms[2] = ts; timing_ms[3] = tst; }
-    c->last_ms = ts;
+    for (size_t b = 0; b < S.blk.size(); b++) collect_block(S, b, t);
+    S.modal.on = S.current.on = false;
+    t[0] = S.since();
+    debug_timeline(S, slot, t[0]);
+    if (timing_ms) memcpy(timing_ms, t, sizeof(t));
+    c->last_ms = t[2];
     return 0;
 }
 
 extern "C" int raftx_sweep_solve_span(raftx_ctx *c, int slot, double *start_ms, double *end_ms) {
     if (!c) return -1;
-    if (slot < 0 || slot >= RAFTX_NSLOT) FAIL(c, "sweep_solve_span: slot must be 0 .. %d", RAFTX_NSLOT - 1);
-    if (c->slots[slot].busy) FAIL(c, "sweep_solve_span: slot %d has not been waited for", slot);
-    if (start_ms) *start_ms = c->slots[slot].span[0];
-    if (end_ms) *end_ms = c->slots[slot].span[1];
+    SLOT_REF(S, c, slot, "sweep_solve_span");
+    if (S.busy) FAIL(c, "sweep_solve_span: slot %d has not been waited for", slot);
+    if (start_ms) *start_ms = S.span[0];
+    if (end_ms) *end_ms = S.span[1];
     return 0;
 }
 
 extern "C" int raftx_sweep_generation(raftx_ctx *c, int slot, int *blocks_fused, int *blocks) {
     if (!c) return -1;
-    if (slot < 0 || slot >= RAFTX_NSLOT) FAIL(c, "sweep_generation: slot must be 0 .. %d", RAFTX_NSLOT - 1);
+    SLOT_REF(S, c, slot, "sweep_generation");
     int nf = 0, nb = 0;
-    for (raftx_ctx *sub : c->slots[slot].blk)
+    for (raftx_ctx *sub : S.blk)
         if (sub) {
             nb++;
             nf += sub->last_gen_fused ? 1 : 0;
@@ -3947,8 +3970,7 @@ extern "C" int raftx_modal_resident(raftx_ctx *c, const double *dM, const double
 extern "C" int raftx_sweep_modal(raftx_ctx *c, int slot, const double *dM, const double *dC, double *fn, double *modes,
                                  int32_t *flags, double *props) {
     if (!c) return -1;
-    if (slot < 0 || slot >= RAFTX_NSLOT) FAIL(c, "sweep_modal: slot must be 0 .. %d", RAFTX_NSLOT - 1);
-    SweepSlot &S = c->slots[slot];
+    SLOT_REF(S, c, slot, "sweep_modal");
     if (S.busy) FAIL(c, "sweep_modal: slot %d has been launched (call it between raftx_sweep_prepare and raftx_sweep_launch)", slot);
     if (!S.prepared) FAIL(c, "sweep_modal: nothing prepared on slot %d (raftx_sweep_prepare first)", slot);
     if (!fn || !modes || !flags) FAIL(c, "sweep_modal: bad arguments");
@@ -4027,8 +4049,7 @@ extern "C" int raftx_current_loads(raftx_ctx *c, int nCur, const double *speed, 
 extern "C" int raftx_sweep_current(raftx_ctx *c, int slot, int nCur, const double *speed, const double *heading_deg,
                                    const double *Zref, double shearExp, double *D) {
     if (!c) return -1;
-    if (slot < 0 || slot >= RAFTX_NSLOT) FAIL(c, "sweep_current: slot must be 0 .. %d", RAFTX_NSLOT - 1);
-    SweepSlot &S = c->slots[slot];
+    SLOT_REF(S, c, slot, "sweep_current");
     if (S.busy) FAIL(c, "sweep_current: slot %d has been launched (call it between raftx_sweep_prepare and raftx_sweep_launch)", slot);
     if (!S.prepared) FAIL(c, "sweep_current: nothing prepared on slot %d (raftx_sweep_prepare first)", slot);
     if (!D) FAIL(c, "sweep_current: bad arguments");

@@ -344,6 +344,85 @@ def test_hip_sweep_crossing_reuses_its_worker_streams_and_reports_errors(hip_ctx
     check_crossing(hip_ctx, 12, 3, 3)
 
 
+def _same_crossing(got, want):
+    for key in ("Xi", "std"):
+        assert got[key].shape == want[key].shape and np.array_equal(got[key].view(np.uint64), want[key].view(np.uint64)), key
+    assert np.array_equal(got["niter"], want["niter"]) and np.array_equal(got["flags"], want["flags"])
+    assert np.array_equal(got["strip_off"], want["strip_off"])
+
+
+def check_bad_design_in_a_block_the_launch_prepares(ctx, spoil, match):
+    """An isolated crossing with responses out and more than two blocks (8 designs, n_chunk=4): raftx_sweep_prepare
+    enqueues phase 1 of the first two blocks only, raftx_sweep_launch that of the others, one block ahead.  Design 5, in
+    block 2, is invalid: the launch reports it, the slot is idle again (nothing prepared), the context still works, and
+    the slot takes a staged crossing with other sea states that equals its blocking call bit for bit -- the failed
+    crossing has released the sea states it had pinned.  ``spoil`` makes the design invalid: "dlsMax" (a negative strip
+    length) or "cap" (a bulkhead closer to the member end than its own thickness; the CPU oracle does not check dlsMax)."""
+    z0, b0 = np.asarray(C3["zeta"]), np.asarray(C3["beta"])
+    fixed = lambda z, b: (C3["w"], C3["k"], float(C3["depth"]), z, b, int(C3["nIter"]), 0.01, float(C3["XiStart"]))
+    D, M0, B0, C0 = _c3_crossing_inputs(8)
+    bad = G.DesignTables(D.member_off, D.members.copy(), D.station_off, D.stations, D.cap_off, D.caps.copy())
+    if spoil == "dlsMax":
+        bad.members[int(D.member_off[5]), G.GM_DLSMAX] = -1.0
+    else:
+        m = next(m for m in range(int(D.member_off[5]), int(D.member_off[6])) if D.cap_off[m + 1] > D.cap_off[m])
+        bad.caps[int(D.cap_off[m])] = [0.05, 0.2, 0.0, 0.0]
+    h = ctx.sweep_prepare(0, bad, M0, B0, C0, *fixed(z0[None], b0[None]), n_chunk=4, want_Xi=True)
+    with pytest.raises(RaftxError, match=match):
+        ctx.sweep_launch(h)
+    with pytest.raises(RaftxError, match="nothing prepared"):
+        ctx.sweep_launch(h)
+    check_crossing(ctx, 5, 0, 0)
+    sea = (np.stack([0.5 * z0, 1.5 * z0]), np.stack([b0 + 0.3, b0 - 0.7]))
+    got = ctx.sweep_wait(ctx.sweep_launch(ctx.sweep_prepare(0, D, M0, B0, C0, *fixed(*sea), n_chunk=4, want_Xi=True)))
+    _same_crossing(got, ctx.sweep_stats(D, M0, B0, C0, *fixed(*sea), n_chunk=4, want_Xi=True))
+
+
+def check_sea_state_set_replaced_beside_pinned_ones(ctx):
+    """Four batches with four different sea states prepared on slots 0 .. 3 (all four sets pinned); slot 0 is launched,
+    waited for and prepared again with a fifth sea state while the other three are still pinned: it gets the free set or
+    the one just released, never a pinned one.  After everything has been collected a sixth sea state replaces the set
+    used longest ago, the first one's, and a batch with the first sea state runs once more.  Every batch equals its
+    blocking raftx_sweep_stats (computed afterwards: the sets are replaced again and again) bit for bit."""
+    z0, b0 = np.asarray(C3["zeta"]), np.asarray(C3["beta"])
+    seas = [(z0[None], b0[None]),
+            (np.stack([0.5 * z0, 1.5 * z0]), np.stack([b0 + 0.3, b0 - 0.7])),
+            (0.8 * z0[None], b0[None] + 1.1),
+            (0.3 * z0[None], b0[None] + 2.0),
+            (1.5 * z0[None], b0[None] - 0.7)]
+    fixed = lambda z, b: (C3["w"], C3["k"], float(C3["depth"]), z, b, int(C3["nIter"]), 0.01, float(C3["XiStart"]))
+    batches = [_c3_crossing_inputs(n) for n in (3, 5, 4, 6)]
+    runs = [(0, 0), (1, 1), (2, 2), (3, 3), (0, 4)]                       # (batch = slot, sea state) in the order prepared
+    prep = lambda r: ctx.sweep_prepare(r[0], *batches[r[0]], *fixed(*seas[r[1]]), want_Xi=True)
+    hs = [prep(r) for r in runs[:4]]
+    got = [ctx.sweep_wait(ctx.sweep_launch(hs[0]))]
+    hs.append(prep(runs[4]))
+    got += [ctx.sweep_wait(ctx.sweep_launch(h)) for h in hs[1:]]
+    ctx.sweep_stats(*batches[1], *fixed(0.6 * z0[None], b0[None] + 0.5))  # a sixth: the first one's set is replaced
+    runs.append((3, 0))
+    got.append(ctx.sweep_wait(ctx.sweep_submit(2, *batches[3], *fixed(*seas[0]), want_Xi=True)))
+    for (bi, si), g_ in zip(runs, got):
+        _same_crossing(g_, ctx.sweep_stats(*batches[bi], *fixed(*seas[si]), want_Xi=True))
+
+
+def test_oracle_bad_design_in_a_block_the_launch_prepares(oracle_ctx):
+    check_bad_design_in_a_block_the_launch_prepares(oracle_ctx, "cap", "cap/bulkhead")
+
+
+def test_oracle_sea_state_set_replaced_beside_pinned_ones(oracle_ctx):
+    check_sea_state_set_replaced_beside_pinned_ones(oracle_ctx)
+
+
+@pytest.mark.gpu
+def test_hip_bad_design_in_a_block_the_launch_prepares(hip_ctx):
+    check_bad_design_in_a_block_the_launch_prepares(hip_ctx, "dlsMax", "dlsMax")
+
+
+@pytest.mark.gpu
+def test_hip_sea_state_set_replaced_beside_pinned_ones(hip_ctx):
+    check_sea_state_set_replaced_beside_pinned_ones(hip_ctx)
+
+
 def check_streamed_crossings(ctx):
     """Two crossings in flight (raftx_sweep_submit on slots 0 and 1, then raftx_sweep_wait): different batches, the
     second submitted before the first is collected; each equals its blocking raftx_sweep_stats bit for bit.  Misuse is
