@@ -43,6 +43,8 @@ MODAL_EXPORTS = ("raftx_modal_batch", "raftx_modal_resident", "raftx_sweep_modal
 MODAL_SMALL_DIAG, MODAL_NONPOSITIVE, MODAL_COMPLEX, MODAL_SINGULAR_M, MODAL_NO_CONVERGENCE = 1, 2, 4, 8, 16
 # include/raftx_current.h: mean current loads, the device library only (the oracle has no current-load sweep)
 CURRENT_EXPORTS = ("raftx_current_loads", "raftx_sweep_current")
+# include/raftx_channels.h: output channels of a sweep crossing, the device library only
+CHANNEL_EXPORTS = ("raftx_sweep_channels",)
 
 
 class RaftxError(RuntimeError):
@@ -151,6 +153,10 @@ class RaftxLib:
             L.raftx_current_loads.restype = C.c_int
             L.raftx_sweep_current.argtypes = [_vp, C.c_int, C.c_int, _vp, _vp, _vp, C.c_double, _vp]
             L.raftx_sweep_current.restype = C.c_int
+        self.has_channels = all(hasattr(L, s) for s in CHANNEL_EXPORTS)
+        if self.has_channels:
+            L.raftx_sweep_channels.argtypes = [_vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int, _vp, _vp]
+            L.raftx_sweep_channels.restype = C.c_int
         L.raftx_device_locality.argtypes = [C.c_int, C.c_char_p, C.c_int, C.POINTER(C.c_int)]
         L.raftx_device_locality.restype = C.c_int
         L.raftx_host_alloc.argtypes = [_vp, C.c_size_t, C.POINTER(_vp)]
@@ -673,6 +679,37 @@ class Context:
         self._check(L.raftx_sweep_current(self._h, int(handle["slot"]), nCur, _ptr(speed), _ptr(heading), _ptr(Zref), float(shearExp),
                                           _ptr(D)), "raftx_sweep_current")
         out["D_hydro"] = D
+        return handle
+
+    # ------------------------------------------------------------- output channels of a crossing (include/raftx_channels.h)
+    def sweep_channels(self, handle, L, Gw=None):
+        """Ask for the standard deviations of linear output channels of a PREPARED, not yet launched crossing
+        (raftx_sweep_channels; the channels of ``channel_stats_poly``): L [nChan,3,6] (rows shared by all designs) or
+        [nD,nChan,3,6], Gw [nChan,6,nw] or [nD,nChan,6,nw] complex or None; ``sweep_wait`` then also returns chan_std
+        [nD,nCase,nChan].  Returns the handle."""
+        if not self.rlib.has_channels:
+            raise RaftxError("sweep_channels: %s does not implement include/raftx_channels.h (the device library does)" % self.rlib.path)
+        out = handle["out"]
+        n, nC = out["niter"].shape
+        nw = len(handle["inputs"][-4])                    # (.., w, k, zeta, beta)
+        L = _f64(L)
+        if L.ndim not in (3, 4):
+            raise ValueError("L has shape %s, expected [nChan,3,6] or [nDesign,nChan,3,6]" % (L.shape,))
+        nL = 1 if L.ndim == 3 else L.shape[0]
+        nCh = L.shape[-3]
+        L = _f64(L, ((nL,) if L.ndim == 4 else ()) + (nCh, 3, 6), "L")
+        nG = 0
+        if Gw is not None:
+            Gw = _c128(Gw)
+            if Gw.ndim not in (3, 4):
+                raise ValueError("Gw has shape %s, expected [nChan,6,nw] or [nDesign,nChan,6,nw]" % (Gw.shape,))
+            nG = 1 if Gw.ndim == 3 else Gw.shape[0]
+            Gw = _c128(Gw, ((nG,) if Gw.ndim == 4 else ()) + (nCh, 6, nw), "Gw")
+        std = np.zeros((n, nC, nCh))
+        self._check(self.rlib.lib.raftx_sweep_channels(self._h, int(handle["slot"]), nCh, nL, _ptr(L), nG, _ptr(Gw), _ptr(std)),
+                    "raftx_sweep_channels")
+        handle["channel_inputs"] = (L, Gw)                # alive until the crossing has been waited for
+        out["chan_std"] = std
         return handle
 
     def fetch_statics(self):

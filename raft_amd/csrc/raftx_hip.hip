@@ -43,6 +43,7 @@
 #include "../../include/raftx.h"
 #include "../../include/raftx_modal.h"
 #include "../../include/raftx_current.h"
+#include "../../include/raftx_channels.h"
 
 // roctx ranges around the phases of the host side: named spans for `rocprofv3 --marker-trace`.
 // librocprofiler-sdk-roctx is bound at run time on first use; without it (or outside a profiler) the ranges cost a branch.
@@ -84,6 +85,7 @@ struct RangeScope {
 #include "raftx_flex.h"
 #include "raftx_modal.h"
 #include "raftx_current.h"
+#include "raftx_channels.h"
 
 // Coupled array solve (raft_model.py:1164-1236): Xi = Z_sys^-1 F for every (system, bin).  One wavefront per
 // (system, bin), NBIN (1, 2 or 4: what fits LDS) consecutive bins per workgroup so that the loads of one matrix entry
@@ -839,6 +841,7 @@ struct raftx_ctx {
     Pinned<double> pinRes;               // ... of a block's statistics (sweep crossing)
     Pinned<double> pinModal;             // ... of a block's eigen analysis (raftx_sweep_modal)
     Pinned<double> pinCur;               // ... of a block's current loads (raftx_sweep_current)
+    Pinned<double> pinChan;              // ... of a block's output channels (raftx_sweep_channels) [pairs,nChan]
     hipStream_t sCopy, sPrep, sD2H, sGen; // internal streams of raftx_sweep_stats (created on first use)
     hipStream_t sSlab[2] = {nullptr, nullptr}; // with sGen: the streams the slabs of a crossing with responses out go to (SlabPlan)
     hipStream_t sD2Hhigh = nullptr;       // bulk download of the responses: a stream of the highest priority class, created when first needed
@@ -966,6 +969,14 @@ struct SweepSlot {
         double *D = nullptr;             // the caller's output [nDesign,nCur,6], filled by raftx_sweep_wait
         hipEvent_t evUp = nullptr;       // the copies have landed (sCopy)
     } current;
+    struct {                             // raftx_sweep_channels: output channels of the crossing's (design, case) pairs
+        bool on = false;
+        int nChan = 0, nL = 0, nG = 0;   // rows of L: 1 (shared) or nDesign; of Gw: 0 (none), 1 or nDesign
+        const double *L = nullptr;       // device copies (in S.allocs) [nL,nChan,3,6]
+        const cplx *Gw = nullptr;        // [nG,nChan,6,nw], or null
+        double *out = nullptr;           // the caller's output [nDesign,nCase,nChan], filled by raftx_sweep_wait
+        hipEvent_t evUp = nullptr;       // the copies have landed (sCopy)
+    } channels;
 };
 
 #define MAX_NW 2048
@@ -1117,6 +1128,7 @@ extern "C" void raftx_ctx_destroy(raftx_ctx *c) {
         if (c->slots[sl].evXi) (void)hipEventDestroy(c->slots[sl].evXi);
         if (c->slots[sl].modal.evUp) (void)hipEventDestroy(c->slots[sl].modal.evUp);
         if (c->slots[sl].current.evUp) (void)hipEventDestroy(c->slots[sl].current.evUp);
+        if (c->slots[sl].channels.evUp) (void)hipEventDestroy(c->slots[sl].channels.evUp);
     }
     delete[] c->slots;
     c->pool.trim();
@@ -1124,6 +1136,7 @@ extern "C" void raftx_ctx_destroy(raftx_ctx *c) {
     c->pinRes.release();
     c->pinModal.release();
     c->pinCur.release();
+    c->pinChan.release();
     for (hipEvent_t e : {c->evZ, c->ev0, c->ev1, c->evUp, c->evTot, c->evG0, c->evG1, c->evG2, c->evG3, c->evS0, c->evS1, c->evDone,
                          c->evMem, c->evRed})
         (void)hipEventDestroy(e);
@@ -3157,7 +3170,8 @@ extern "C" int raftx_qtf_force(raftx_ctx *c, int nSet, int nw2, const double *w2
 //            hand_sea_states, solve_enqueue, enqueue_stats | stats_after_join (slab mode)
 //   wait     sweep_drain | solve_span | collect_block per block | debug_timeline
 //   sCopy   descriptor H2D of every block, back to back (the first block is small, so its tables are ready early); ahead of
-//           them the sea-state tables (acquire_cases), the offsets and the inputs of raftx_sweep_modal / raftx_sweep_current
+//           them the sea-state tables (acquire_cases), the offsets and the inputs of raftx_sweep_modal / raftx_sweep_current /
+//           raftx_sweep_channels
 //   sPrep   member pass + scans of a block as soon as its descriptors have landed, totals to page-locked memory
 //           (block_phase1, from prepare or, one block ahead, from launch)
 //   stream  (the ctx stream; every kernel that matters) strip generation, per-design reduction, the fused fixed point
@@ -3315,7 +3329,7 @@ static void cut_blocks(raftx_ctx *c, int slot, int nDesign, const SeaStates &sea
     S.sd = run.sd; S.niter = run.niter; S.flags = run.flags; S.Xi = run.Xi; S.stripOffsets = run.stripOffsets;
     S.tl[0] = S.since();
     free_list(c, S.allocs);
-    S.modal.on = S.current.on = false;
+    S.modal.on = S.current.on = S.channels.on = false;
 }
 // The batch's offset arrays: one upload on sCopy, shared by the blocks; its wave numbers are those of the sea-state set.
 static int upload_offsets(raftx_ctx *c, SweepSlot &S, const BuildSource &src, int nDesign) {
@@ -3569,6 +3583,29 @@ static hipError_t current_block(raftx_ctx *sub, SweepSlot &S, int lo, int n, dou
     return hipGetLastError();
 }
 
+// The output channels of one block of a crossing (raftx_sweep_channels) on stream st, behind the block's statistics kernel
+// (and so behind everything that wrote the block's responses, the slabs of a crossing with responses out included): one
+// workgroup per pair, the standard deviations written straight into the block's page-locked landing area [pairs,nChan],
+// which raftx_sweep_wait copies out.  Per-design rows are taken at the block's first design.
+static hipError_t channels_block(raftx_ctx *sub, SweepSlot &S, int lo, int n, hipStream_t st) {
+    const size_t npair = (size_t)n * S.nCase;
+    hipError_t e = sub->pinChan.reserve(npair * S.channels.nChan);
+    if (e != hipSuccess || npair == 0) return e;
+    if (!sub->rXi || sub->r_nx < npair * S.nHead * 6 * S.nw || !sub->T.w) return hipErrorInvalidValue;   // (no resident responses: internal error)
+    e = hipStreamWaitEvent(st, S.channels.evUp, 0);
+    if (e != hipSuccess) return e;
+    ChannelArgs A;
+    A.nCase = S.nCase; A.nHead = S.nHead; A.nw = S.nw; A.nChan = S.channels.nChan;
+    A.strideL = S.channels.nL > 1 ? (size_t)A.nChan * 18 : 0;
+    A.strideG = S.channels.nG > 1 ? (size_t)A.nChan * 6 * S.nw : 0;
+    const double *L = S.channels.L + (size_t)lo * A.strideL;
+    const cplx *Gw = S.channels.Gw ? S.channels.Gw + (size_t)lo * A.strideG : nullptr;
+    const dim3 grid((unsigned)npair), wg(S.nw > 128 ? 256 : (S.nw > 64 ? 128 : 64));
+    if (Gw) hipLaunchKernelGGL(k_sweep_channels<true>, grid, wg, 0, st, A, (const double *)sub->T.w, (const cplx *)sub->rXi, L, Gw, sub->pinChan.p);
+    else hipLaunchKernelGGL(k_sweep_channels<false>, grid, wg, 0, st, A, (const double *)sub->T.w, (const cplx *)sub->rXi, L, Gw, sub->pinChan.p);
+    return hipGetLastError();
+}
+
 // The stream the responses of a crossing are downloaded on: one of the HIGHEST priority class, created when first needed (so
 // late, it does not move the other streams' hardware queues).  A priority class has hardware queues of its own and the highest
 // is served at once: the copy never sits in a queue with the next batch's kernels (ordinary stream) nor starts a step late
@@ -3599,6 +3636,7 @@ static int enqueue_stats(raftx_ctx *c, SweepSlot &S, size_t b, hipStream_t sDown
     if (e == hipSuccess) e = hipEventRecord(sub->evS1, c->stream);
     if (e == hipSuccess && S.modal.on) e = modal_block(sub, S, lo, S.bnd[b + 1] - lo, c->stream);
     if (e == hipSuccess && S.current.on) e = current_block(sub, S, lo, S.bnd[b + 1] - lo, c->csets[S.cset].T.depth, c->stream);
+    if (e == hipSuccess && S.channels.on) e = channels_block(sub, S, lo, S.bnd[b + 1] - lo, c->stream);
     if (e == hipSuccess) e = hipEventRecord(sub->evDone, c->stream);
     if (e == hipSuccess && S.Xi && !S.slab) {
         e = hipStreamWaitEvent(sDown, sub->evDone, 0);
@@ -3789,7 +3827,7 @@ extern "C" int raftx_sweep_cancel(raftx_ctx *c, int slot) {
             build_abandon(sub);
         }
     S.prepared = false;
-    S.modal.on = S.current.on = false;
+    S.modal.on = S.current.on = S.channels.on = false;
     slot_release_cases(c, S);
     HIPCHK(c, e);
     return 0;
@@ -3852,6 +3890,8 @@ static void collect_block(SweepSlot &S, size_t b, double *t) {
     }
     if (S.current.on && n)
         memcpy(S.current.D + (size_t)lo * S.current.nCur * 6, sub->pinCur.p, (size_t)n * S.current.nCur * 6 * sizeof(double));
+    if (S.channels.on && npair)
+        memcpy(S.channels.out + p0 * S.channels.nChan, sub->pinChan.p, npair * S.channels.nChan * sizeof(double));
 }
 // RAFTX_SWEEP_DEBUG: the host's timeline of the crossing on stderr
 static void debug_timeline(const SweepSlot &S, int slot, double wall) {
@@ -3875,13 +3915,13 @@ extern "C" int raftx_sweep_wait(raftx_ctx *c, int slot, double *timing_ms) {
     HIPCHK(c, hipSetDevice(c->device));
     S.busy = false;
     const hipError_t es = sweep_drain(c, S);
-    if (es != hipSuccess) S.modal.on = S.current.on = false;
+    if (es != hipSuccess) S.modal.on = S.current.on = S.channels.on = false;
     HIPCHK(c, es);
     solve_span(c, S);
     double t[4] = {0, 0, 0, 0};                           // wall | generation, solve, statistics kernels
     if (S.stripOffsets) S.stripOffsets[0] = 0;
     for (size_t b = 0; b < S.blk.size(); b++) collect_block(S, b, t);
-    S.modal.on = S.current.on = false;
+    S.modal.on = S.current.on = S.channels.on = false;
     t[0] = S.since();
     debug_timeline(S, slot, t[0]);
     if (timing_ms) memcpy(timing_ms, t, sizeof(t));
@@ -4070,6 +4110,37 @@ extern "C" int raftx_sweep_current(raftx_ctx *c, int slot, int nCur, const doubl
     S.current.Zref = Zref ? dpar + (size_t)3 * nCur : nullptr;
     S.current.D = D;
     S.current.on = true;
+    return 0;
+}
+
+// ---- output channels of a crossing (include/raftx_channels.h, raftx_channels.h)
+extern "C" int raftx_sweep_channels(raftx_ctx *c, int slot, int nChan, int nL, const double *L, int nG, const raftx_c128 *Gw,
+                                    double *chan_std) {
+    if (!c) return -1;
+    SLOT_REF(S, c, slot, "sweep_channels");
+    if (S.busy) FAIL(c, "sweep_channels: slot %d has been launched (call it between raftx_sweep_prepare and raftx_sweep_launch)", slot);
+    if (!S.prepared) FAIL(c, "sweep_channels: nothing prepared on slot %d (raftx_sweep_prepare first)", slot);
+    const int n = S.bnd.empty() ? 0 : S.bnd.back();
+    if (nChan < 1 || nChan > RAFTX_SWEEP_CHAN_MAX) FAIL(c, "sweep_channels: nChan=%d must be 1 .. %d", nChan, RAFTX_SWEEP_CHAN_MAX);
+    if (nL != 1 && nL != n) FAIL(c, "sweep_channels: nL=%d must be 1 (shared rows) or the %d designs of the crossing", nL, n);
+    if (nG != 0 && nG != 1 && nG != n) FAIL(c, "sweep_channels: nG=%d must be 0 (no Gw), 1 (shared) or the %d designs of the crossing", nG, n);
+    if (nG > 0 && !Gw) FAIL(c, "sweep_channels: nG=%d without Gw", nG);
+    if (!L || !chan_std) FAIL(c, "sweep_channels: bad arguments");
+    HIPCHK(c, hipSetDevice(c->device));
+    const double *dL = nullptr;
+    const raftx_c128 *dG = nullptr;
+    if (upload_on(c, c->sCopy, S.allocs, L, (size_t)nL * nChan * 18, &dL) ||
+        upload_on(c, c->sCopy, S.allocs, Gw, nG > 0 ? (size_t)nG * nChan * 6 * S.nw : 0, &dG))
+        return -2;
+    if (!S.channels.evUp) HIPCHK(c, hipEventCreateWithFlags(&S.channels.evUp, hipEventDisableTiming));
+    HIPCHK(c, hipEventRecord(S.channels.evUp, c->sCopy));
+    S.channels.nChan = nChan;
+    S.channels.nL = nL;
+    S.channels.nG = nG;
+    S.channels.L = dL;
+    S.channels.Gw = reinterpret_cast<const cplx *>(dG);
+    S.channels.out = chan_std;
+    S.channels.on = true;
     return 0;
 }
 

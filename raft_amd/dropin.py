@@ -769,29 +769,18 @@ class Engine:
         if getattr(self, "_resident", None) is not fowt:
             raise UnsupportedFOWT("saveTurbineOutputs: the responses of this FOWT are not resident on the device "
                                   "(call solveDynamics of its single-unit model first)")
-        J_moor, T_moor = _quasi_static_tension_rows(fowt)
-        if any(getattr(rot, "aeroServoMod", 0) > 1 for rot in fowt.rotorList):
-            raise UnsupportedFOWT("saveTurbineOutputs: rotor-controller outputs (raft_fowt.py:2640-2680) are not on the device path")
-        if np.any(np.abs(np.asarray(fowt.rigidBodyNode.r0[:3], dtype=float)) > 0):
-            raise UnsupportedFOWT("saveTurbineOutputs: reference node away from the PRP")
+        _, Lo, Go, info, T_moor = _output_rows(fowt, True)
         nr, nw = int(fowt.nrotors), fowt.nw
         deg = 57.29577951308232                                              # helpers.rad2deg
-        Lt, Gt, info = tower_base_rows(fowt)
-        nT = 0 if J_moor is None else J_moor.shape[0]
-        nCh = 6 + 4 * nr + nT
-        L = np.zeros((nCh, 3, 6))
-        if nT:
-            L[6 + 4 * nr:, 0, :] = J_moor                                    # tension amplitudes J Xi_PRP (:2367)
+        nT = 0 if T_moor is None else len(T_moor)
+        L = np.zeros((6 + len(Lo), 3, 6))
         for j in range(6):
             L[j, 0, j] = 1.0 if j < 3 else deg                               # motions; rotations in degrees (:2332-2354)
-        for ir, rotor in enumerate(fowt.rotorList):
-            T = np.asarray(rotor.nodeList[0].T, dtype=float)                 # hub motion = T Xi (:2423)
-            L[6 + 3 * ir:9 + 3 * ir, 2, :] = T[:3, :]                        # accelerations: w^2 x (:2426-2441)
-            L[6 + 3 * nr + ir] = Lt[ir]
+        L[6:] = Lo                                                           # accelerations | tower base | tensions
         Gw = None
-        if Gt is not None:
-            Gw = np.zeros((nCh, 6, nw), dtype=complex)
-            Gw[6 + 3 * nr:6 + 4 * nr] = Gt
+        if Go is not None:
+            Gw = np.zeros((len(L), 6, nw), dtype=complex)
+            Gw[6:] = Go
         std, psd = self.ctx.channel_stats_poly(L, fowt.dw, Gw=Gw, want_psd=True)
         std, psd = std[0, 0], psd[0, 0]
         Xi0 = np.asarray(fowt.r6, dtype=float) - np.array([fowt.x_ref, fowt.y_ref, 0, 0, 0, 0])
@@ -1324,6 +1313,51 @@ def tower_base_rows(fowt, only=None):
         Gw[ir, 4, :] = -(-w ** 2 * fowt.A_aero[0, 0, :, ir] + 1j * w * fowt.B_aero[0, 0, :, ir]) * (rotor.r_rel[2] - zBase) ** 2
         info.append((m, hArm))
     return L, (Gw if np.any(Gw) else None), info
+
+
+def _output_rows(fowt, tensions):
+    """(names, L [nChan,3,6], Gw [nChan,6,nw] or None, (m, hArm) per rotor, T_moor or None): the channels of
+    FOWT.saveTurbineOutputs beside the six motions, in the order hub accelerations (3 per rotor) | tower base (1 per rotor)
+    | quasi-static tensions, with the refusals of Engine.saveTurbineOutputs."""
+    J_moor, T_moor = _quasi_static_tension_rows(fowt) if tensions else (None, None)
+    if any(getattr(rot, "aeroServoMod", 0) > 1 for rot in fowt.rotorList):
+        raise UnsupportedFOWT("saveTurbineOutputs: rotor-controller outputs (raft_fowt.py:2640-2680) are not on the device path")
+    if np.any(np.abs(np.asarray(fowt.rigidBodyNode.r0[:3], dtype=float)) > 0):
+        raise UnsupportedFOWT("saveTurbineOutputs: reference node away from the PRP")
+    nr, nw = int(fowt.nrotors), fowt.nw
+    Lt, Gt, info = tower_base_rows(fowt)
+    nT = 0 if J_moor is None else J_moor.shape[0]
+    L = np.zeros((4 * nr + nT, 3, 6))
+    names = [""] * (4 * nr)
+    if nT:
+        L[4 * nr:, 0, :] = J_moor                                            # tension amplitudes J Xi_PRP (:2367)
+    for ir, rotor in enumerate(fowt.rotorList):
+        T = np.asarray(rotor.nodeList[0].T, dtype=float)                     # hub motion = T Xi (:2423)
+        L[3 * ir:3 + 3 * ir, 2, :] = T[:3, :]                                # accelerations: w^2 x (:2426-2441)
+        L[3 * nr + ir] = Lt[ir]
+        names[3 * ir:3 + 3 * ir] = ["A%sRNA[%d]" % (ax, ir) for ax in "xyz"]
+        names[3 * nr + ir] = "Mbase[%d]" % ir
+    names += ["Tmoor[%d]" % i for i in range(nT)]
+    Gw = None
+    if Gt is not None:
+        Gw = np.zeros((len(L), 6, nw), dtype=complex)
+        Gw[3 * nr:4 * nr] = Gt
+    return names, L, Gw, info, T_moor
+
+
+def sweep_output_rows(fowt, tensions=True):
+    """(names, L [nChan,3,6], Gw [nChan,6,nw] or None): the output channels of FOWT.saveTurbineOutputs (raft_fowt.py:2291-2745)
+    of a rigid unit as rows for ``channels=dict(L=, Gw=)`` of a sweep crossing (raftx_sweep_channels) or for
+    ``Sweep.run_channels`` -- what Engine.saveTurbineOutputs builds, without the six motions a crossing returns anyway:
+    AxRNA / AyRNA / AzRNA of every rotor (:2422-2444), Mbase of every rotor (:2500-2537) and, with ``tensions``, the
+    quasi-static line-end tensions Tmoor[i] of the unit's own mooring system (:2356-2373).  The refusals are
+    saveTurbineOutputs': a flexible tower, rotor-controller channels, a reference node away from the PRP, line dynamics.
+    In a sweep over platform variants of one turbine these rows are shared by all designs; per-design rows are for
+    sweeps whose mooring Jacobian differs per design."""
+    if _general(fowt):
+        raise UnsupportedFOWT("sweep_output_rows covers rigid 6-DOF FOWTs (nDOF=%d)" % fowt.nDOF)
+    names, L, Gw, _, _ = _output_rows(fowt, tensions)
+    return names, L, Gw
 
 
 def unit_matrices(fowt, nw):

@@ -307,15 +307,16 @@ class GeometrySweep(Sweep):
                                             None if self.MBw is None else self.MBw[lo:hi], self.rho, self.g), lo, hi)
 
     def run_crossing(self, ctx, n_chunk=0, n_worker=0, want_Xi=False, Xi_out=None, modal=False, dM=None, dC=None, want_props=False,
-                     current=None):
+                     current=None, channels=None):
         """The whole boundary crossing in ONE library call (raftx_sweep_stats): descriptors in, motion statistics +
         iteration counts (+ responses) out, with upload / generation / solve / download of consecutive design blocks
-        overlapped on the library's internal streams.  Nothing stays resident on ``ctx``.  modal=True / current=dict(..):
-        the streamed form on slot 0 with the eigen analysis / mean current loads of every design (see
-        ``prepare_crossing``)."""
-        if modal or current is not None:
+        overlapped on the library's internal streams.  Nothing stays resident on ``ctx``.  modal=True / current=dict(..) /
+        channels=dict(..): the streamed form on slot 0 with the eigen analysis / mean current loads of every design /
+        output channels of every (design, case) (see ``prepare_crossing``)."""
+        if modal or current is not None or channels is not None:
             return self.wait_crossing(ctx, self.submit_crossing(ctx, 0, n_chunk=n_chunk, want_Xi=want_Xi, Xi_out=Xi_out, modal=modal,
-                                                                dM=dM, dC=dC, want_props=want_props, current=current))
+                                                                dM=dM, dC=dC, want_props=want_props, current=current,
+                                                                channels=channels))
         self._crossing_supported()
         t = self.tables
         r = ctx.sweep_stats(t, self.M0, self.B0, self.C0, self.w, self.k, self.depth, self.zeta, self.beta, self.nIter,
@@ -325,17 +326,20 @@ class GeometrySweep(Sweep):
         return r
 
     def prepare_crossing(self, ctx, slot, n_chunk=0, want_Xi=False, Xi_out=None, modal=False, dM=None, dC=None, want_props=False,
-                         current=None):
+                         current=None, channels=None):
         """First stage of the streamed form of ``run_crossing`` for back-to-back batches: enqueue this batch's descriptor
         upload and member pass on ``slot`` (0 .. 3) and return a handle (raftx_sweep_prepare).  modal=True: the batch's
         eigen analysis rides along (raftx_sweep_modal on M_extra + device terms + dM, C_extra + device terms + dC) and
         ``wait_crossing`` also returns fn, modes, modal_flags and props (``want_props``).  current=dict(speed=, heading=,
         Zref=, shearExp=): the batch's mean current loads ride along (raftx_sweep_current, at this sweep's depth; Zref
-        and shearExp optional, 0 and 0.12) and ``wait_crossing`` also returns D_hydro [nD,nCur,6]."""
+        and shearExp optional, 0 and 0.12) and ``wait_crossing`` also returns D_hydro [nD,nCur,6].  channels=dict(L=, Gw=):
+        the standard deviations of linear output channels of every (design, case) ride along (raftx_sweep_channels: the
+        channels of ``run_channels``; L [nChan,3,6] shared or [nD,nChan,3,6], Gw optional -- raft_amd.dropin.sweep_output_rows
+        builds the rows of a unit) and ``wait_crossing`` also returns chan_std [nD,nCase,nChan]."""
         self._crossing_supported()
-        return self._with_current(ctx, self._with_modal(ctx, ctx.sweep_prepare(slot, self.tables, self.M0, self.B0, self.C0, self.w, self.k, self.depth, self.zeta, self.beta,
+        return self._with_channels(ctx, self._with_current(ctx, self._with_modal(ctx, ctx.sweep_prepare(slot, self.tables, self.M0, self.B0, self.C0, self.w, self.k, self.depth, self.zeta, self.beta,
                                  self.nIter, self.tol, self.XiStart, pose=self.pose, rho=self.rho, g=self.g, add_mask=self.add_mask,
-                                 n_chunk=n_chunk, want_Xi=want_Xi, Xi_out=Xi_out), modal, dM, dC, want_props), current)
+                                 n_chunk=n_chunk, want_Xi=want_Xi, Xi_out=Xi_out), modal, dM, dC, want_props), current), channels)
 
     @staticmethod
     def _with_modal(ctx, handle, modal, dM, dC, want_props):
@@ -363,6 +367,19 @@ class GeometrySweep(Sweep):
             ctx.sweep_cancel(handle)
             raise
 
+    @staticmethod
+    def _with_channels(ctx, handle, channels):
+        if channels is None:
+            return handle
+        try:
+            unknown = set(channels) - {"L", "Gw"}
+            if unknown or channels.get("L") is None:
+                raise ValueError("channels=dict(L=[, Gw=]) (got %s)" % sorted(channels))
+            return ctx.sweep_channels(handle, channels["L"], Gw=channels.get("Gw"))
+        except Exception:
+            ctx.sweep_cancel(handle)
+            raise
+
     def launch_crossing(self, ctx, handle):
         """Second stage: table generation, fused fixed point and statistics of a prepared batch (raftx_sweep_launch).  With
         launch(i+1), prepare(i+2), wait(i) per step a long sweep keeps three batches in flight and the fused kernels of
@@ -370,10 +387,11 @@ class GeometrySweep(Sweep):
         return ctx.sweep_launch(handle)
 
     def submit_crossing(self, ctx, slot, n_chunk=0, want_Xi=False, Xi_out=None, modal=False, dM=None, dC=None, want_props=False,
-                        current=None):
+                        current=None, channels=None):
         """prepare + launch in one call (raftx_sweep_submit); ``wait_crossing`` collects the results."""
         return self.launch_crossing(ctx, self.prepare_crossing(ctx, slot, n_chunk=n_chunk, want_Xi=want_Xi, Xi_out=Xi_out,
-                                                               modal=modal, dM=dM, dC=dC, want_props=want_props, current=current))
+                                                               modal=modal, dM=dM, dC=dC, want_props=want_props, current=current,
+                                                               channels=channels))
 
     def _crossing_supported(self):
         """raftx_sweep_stats / raftx_sweep_submit carry neither frequency-dependent matrices nor potential-flow excitation
@@ -740,19 +758,19 @@ class VariantSweep(GeometrySweep):
         return self._take_bem(sub, lo, hi)
 
     def prepare_crossing(self, ctx, slot, n_chunk=0, want_Xi=False, Xi_out=None, modal=False, dM=None, dC=None, want_props=False,
-                         current=None):
+                         current=None, channels=None):
         self._crossing_supported()
         self._install(ctx)
-        return self._with_current(ctx, self._with_modal(ctx, ctx.sweep_prepare_variants(slot, self.params, self.M0, self.B0, self.C0, self.w, self.k, self.depth, self.zeta, self.beta,
+        return self._with_channels(ctx, self._with_current(ctx, self._with_modal(ctx, ctx.sweep_prepare_variants(slot, self.params, self.M0, self.B0, self.C0, self.w, self.k, self.depth, self.zeta, self.beta,
                                           self.nIter, self.tol, self.XiStart, pose=self.pose, rho=self.rho, g=self.g,
                                           add_mask=self.add_mask, n_chunk=n_chunk, want_Xi=want_Xi, Xi_out=Xi_out),
-                                modal, dM, dC, want_props), current)
+                                modal, dM, dC, want_props), current), channels)
 
     def run_crossing(self, ctx, n_chunk=0, n_worker=0, want_Xi=False, Xi_out=None, slot=0, modal=False, dM=None, dC=None,
-                     want_props=False, current=None):
+                     want_props=False, current=None, channels=None):
         """One isolated crossing: prepare + launch + wait on ``slot``."""
         return self.wait_crossing(ctx, self.submit_crossing(ctx, slot, n_chunk=n_chunk, want_Xi=want_Xi, Xi_out=Xi_out, modal=modal,
-                                                            dM=dM, dC=dC, want_props=want_props, current=current))
+                                                            dM=dM, dC=dC, want_props=want_props, current=current, channels=channels))
 
     def upload(self, ctx):
         self.tables = self.expanded_tables(ctx)
