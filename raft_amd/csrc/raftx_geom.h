@@ -166,6 +166,11 @@ struct GeomArgs {
     int64_t mbase, sbase, cbase;
     int *mdesign_w;              // mdesign, writable (filled on the device by k_geom_zero)
     int mgrid;                   // > 0: member kernels run on a (member position < mgrid, design) grid, designs fastest
+    // fixed members of the job's variant program (k_geom_member_fixed), or fixRec == null: none.  The job's designs are then
+    // fixNM members each and have no pose; member position p of every design is fixed when fixIdx[p] >= 0, its record
+    const double *fixRec;        // [nFix,FR_N]
+    const int *fixInt, *fixIdx;  // [nFix,FR_I] [fixNM]
+    int fixNM;
     __device__ int64_t mo(int d) const { return memberOff[d] - mbase; }
     __device__ int64_t so(int64_t m) const { return stationOff[m] - sbase; }
     __device__ int64_t co(int64_t m) const { return capOff[m] - cbase; }
@@ -609,25 +614,25 @@ __device__ __forceinline__ void geom_load_row(const double *gs, int i, double (&
         r[2 * k + 1] = v.y;
     }
 }
-// Memory-wise the pass is a handful of round trips per member: the member's row and offsets, then ONE pass over its
-// stations -- each row read once into registers (geom_load_row) and used for the wet-strip count, the hydrostatics and the
-// inertia of the section it closes -- then the caps, and every result stored at the end.  (Up to round 5 the three
-// computations walked the station table one 8-byte load at a time, each waited for: ~130 dependent round trips, 149 us
-// for 1 700 wavefronts that issue VALU in 11 % of their cycles.)
-__global__ __launch_bounds__(128) void k_geom_member(GeomArgs A) {
+// What the member pass computes for ONE member, from its rows alone: pose, wet-strip counts, hydrostatics and inertia
+// into mp [MP_N], mh [MH_N], mi [MI_N], and what the caller has to record -- the counts, the inertia's return code, a
+// rejection.  One body for the per-design pass (k_geom_member) and for the fixed members of a variant program
+// (k_geom_member_fixed), so that both run the same instructions.  pose: the unit's six, or null.
+struct GMember {
+    int wet, wetm;               // wet strips / MacCamy-Fuchs rows
+    int code;                    // != 0: cap / bulkhead layout the reference refuses (mi has been zeroed)
+    int rej;                     // 1: bad station count / dlsMax / length, 2: MacCamy-Fuchs without wave numbers; nothing was written
+};
+#define FR_N (MP_N + MH_N + MI_N) // doubles of a fixed member's record: mp | mh | mi
+#define FR_I 4                    // ints of it: the four of GMember
+__device__ __forceinline__ GMember geom_member_body(const double *gmrow, const double *gs, const int n, const double *gc, const int ncap,
+                                                    const double *pose, const double rho, const double g, const bool trim,
+                                                    const bool haveK, double *mp, double *mh, double *mi) {
     GEOM_NOFMA
-    if (A.mgrid > 0 && A.err[2]) return;                  // member offsets rejected: the grid cannot be walked
-    const int64_t m = geom_member_of_thread(A);
-    if (m < 0) return;
-    if (A.err[2]) {                                       // member offsets rejected: mdesign is not valid
-        A.cnt[m] = 0;
-        A.cntm[m] = 0;
-        return;
-    }
-    // ---- first round trip: everything that hangs on m alone
+    GMember res = {0, 0, 0, 0};
     double gm[RAFTX_GM_N];
     {
-        const double2 *p = reinterpret_cast<const double2 *>(A.gm + (size_t)m * RAFTX_GM_N);
+        const double2 *p = reinterpret_cast<const double2 *>(gmrow);
 #pragma unroll
         for (int k = 0; k < RAFTX_GM_N / 2; k++) {
             const double2 v = p[k];
@@ -635,27 +640,18 @@ __global__ __launch_bounds__(128) void k_geom_member(GeomArgs A) {
             gm[2 * k + 1] = v.y;
         }
     }
-    const int64_t so0 = A.so(m), so1 = A.so(m + 1);
-    const int64_t co0 = A.capOff ? A.co(m) : 0, co1 = A.capOff ? A.co(m + 1) : 0;
-    const int d = A.mdesign[m];
-    const double *gs = A.gs + (size_t)so0 * RAFTX_GS_N;
-    const int n = (int)(so1 - so0);
     if (n < 2 || n > GEOM_MAX_STATIONS || !(gm[RAFTX_GM_DLSMAX] > 0.0) || !(gm[RAFTX_GM_L] > 0.0)) {
-        A.cnt[m] = 0;
-        A.cntm[m] = 0;
-        atomicCAS(A.err + 3, 0, (int)(m + 1));            // bad station count / dlsMax / length: the member is skipped
-        return;
+        res.rej = 1;                                        // bad station count / dlsMax / length: the member is skipped
+        return res;
     }
-    if (((int)gm[RAFTX_GM_FLAGS] & RAFTX_GM_FLAG_MCF) && gm[RAFTX_GM_SHAPE] != 0.0 && !A.k) {
-        A.cnt[m] = 0;
-        A.cntm[m] = 0;
-        atomicCAS(A.err + 3, 0, -(int)(m + 1));           // MacCamy-Fuchs member without wave numbers
-        return;
+    if (((int)gm[RAFTX_GM_FLAGS] & RAFTX_GM_FLAG_MCF) && gm[RAFTX_GM_SHAPE] != 0.0 && !haveK) {
+        res.rej = 2;                                        // MacCamy-Fuchs member without wave numbers
+        return res;
     }
     // ---- second round trip: the unit's pose and the first station row
     double ps[6] = {0, 0, 0, 0, 0, 0};
-    if (A.pose)
-        for (int i = 0; i < 6; i++) ps[i] = A.pose[(size_t)d * 6 + i];
+    if (pose)
+        for (int i = 0; i < 6; i++) ps[i] = pose[i];
     double a[RAFTX_GS_N], b[RAFTX_GS_N];
     geom_load_row(gs, 0, b);
     const bool circ = gm[RAFTX_GM_SHAPE] != 0.0;
@@ -707,10 +703,9 @@ __global__ __launch_bounds__(128) void k_geom_member(GeomArgs A) {
     for (int i = 0; i < 6; i++) F[i] = 0.0;
     const double beta2 = atan2(q[1], q[0]), phi2 = atan2(sqrt(q[0] * q[0] + q[1] * q[1]), q[2]);
     const double cosPhi = cos(phi2), sinPhi = sin(phi2), tanPhi = tan(phi2), cosBeta = cos(beta2), sinBeta = sin(beta2);
-    const double rg = A.rho * A.g;
+    const double rg = rho * g;
     const bool nostatic = (flags & RAFTX_GM_FLAG_NOSTATIC) != 0;          // nacelle members stay out of the statics (raft_fowt.py:876)
     const double rho_shell = gm[RAFTX_GM_RHOSHELL];
-    const bool trim = (A.add_mask & RAFTX_TRIM_BALLAST) != 0;
     for (int i = 1; i < n; i++) {
 #pragma unroll
         for (int f = 0; f < RAFTX_GS_N; f++) a[f] = b[f];
@@ -805,7 +800,6 @@ __global__ __launch_bounds__(128) void k_geom_member(GeomArgs A) {
         }
     }
     if (geom_along(rA[2], rB[2], b[RAFTX_GS_S], L) < 0) wet++;                           // group n: end B (b = the last station)
-    double *mh = A.mhyd + (size_t)m * MH_N, *mi = A.minert + (size_t)m * MI_N;
     if (!nostatic) {
         for (int i = 0; i < 36; i++) mh[i] = C[i];
         for (int i = 0; i < 6; i++) mh[36 + i] = F[i];
@@ -824,31 +818,107 @@ __global__ __launch_bounds__(128) void k_geom_member(GeomArgs A) {
             geom_load_row(gs, i, b);
             geom_inertia_section(J, a, b, circ, rho_shell, trim, 0.0, rA, q, p1, p2);
         }
-        const int ncap = A.capOff ? (int)(co1 - co0) : 0;
-        const double *gc = A.capOff ? A.caps + (size_t)co0 * RAFTX_GC_N : nullptr;
-        code = geom_inertia_caps_finish(J, gs, n, gc, ncap, circ, rho_shell, rA, q, p1, p2, A.g, mi);
+        code = geom_inertia_caps_finish(J, gs, n, gc, ncap, circ, rho_shell, rA, q, p1, p2, g, mi);
     }
     // ---- everything out
-    double *mp = A.mpose + (size_t)m * MP_N;
     for (int i = 0; i < 3; i++) {
         mp[i] = rA0[i]; mp[3 + i] = rA[i]; mp[6 + i] = q[i]; mp[9 + i] = p1[i]; mp[12 + i] = p2[i];
     }
     mp[15] = R[0][0]; mp[16] = R[0][1]; mp[17] = R[1][0]; mp[18] = R[1][1]; mp[19] = L;
     const int wetm = ((flags & RAFTX_GM_FLAG_MCF) && circ && !(flags & RAFTX_GM_FLAG_POTMOD)) ? wet : 0;
-    A.cnt[m] = wet;
-    A.cntm[m] = wetm;
-    // per-design totals (integer sums: the order of the additions does not matter)
-    if (wet) atomicAdd(reinterpret_cast<unsigned long long *>(A.off + d + 1), (unsigned long long)wet);
-    if (wetm) atomicAdd(reinterpret_cast<unsigned long long *>(A.cmoff + d + 1), (unsigned long long)wetm);
+    res.wet = wet;
+    res.wetm = wetm;
     if (nostatic) {
         for (int i = 0; i < MH_N; i++) mh[i] = 0.0;
         for (int i = 0; i < MI_N; i++) mi[i] = 0.0;
-        return;
+        return res;
     }
     if (code) {
         for (int i = 0; i < MI_N; i++) mi[i] = 0.0;
-        atomicCAS(A.err, 0, (int)(m + 1));
+        res.code = code;
     }
+    return res;
+}
+
+// Fixed members of a variant program (raftx_variant_program): members no edit touches -- k_geom_expand writes their base
+// rows unchanged into every design -- of a job without per-design poses.  Their pass runs once per program and key
+// (k_geom_member_fixed, one thread per fixed member, on the program's base rows); the per-design pass copies the record.
+struct FixedArgs {
+    int nFix;
+    const double *gm, *gs, *gc;  // the program's base rows
+    const int *desc;             // [nFix,5] member, first station, stations, first cap, caps
+    double rho, g;
+    int trim, haveK;             // the rest of the key: what the body reads besides the rows
+    double *rec;                 // [nFix,FR_N]
+    int *irec;                   // [nFix,FR_I]
+};
+__global__ __launch_bounds__(64) void k_geom_member_fixed(FixedArgs F) {
+    const int f = blockIdx.x * blockDim.x + threadIdx.x;
+    if (f >= F.nFix) return;
+    const int *ds = F.desc + (size_t)f * 5;
+    double *r = F.rec + (size_t)f * FR_N;
+    const GMember R = geom_member_body(F.gm + (size_t)ds[0] * RAFTX_GM_N, F.gs + (size_t)ds[1] * RAFTX_GS_N, ds[2],
+                                       ds[4] >= 0 ? F.gc + (size_t)ds[3] * RAFTX_GC_N : nullptr, ds[4] >= 0 ? ds[4] : 0, nullptr, F.rho,
+                                       F.g, F.trim != 0, F.haveK != 0, r, r + MP_N, r + MP_N + MH_N);
+    int *ir = F.irec + (size_t)f * FR_I;
+    ir[0] = R.wet; ir[1] = R.wetm; ir[2] = R.code; ir[3] = R.rej;
+}
+// Memory-wise the pass is a handful of round trips per member: the member's row and offsets, then ONE pass over its
+// stations -- each row read once into registers (geom_load_row) and used for the wet-strip count, the hydrostatics and the
+// inertia of the section it closes -- then the caps, and every result stored at the end.  (Up to round 5 the three
+// computations walked the station table one 8-byte load at a time, each waited for: ~130 dependent round trips, 149 us
+// for 1 700 wavefronts that issue VALU in 11 % of their cycles.)
+__global__ __launch_bounds__(128) void k_geom_member(GeomArgs A) {
+    GEOM_NOFMA
+    if (A.mgrid > 0 && A.err[2]) return;                  // member offsets rejected: the grid cannot be walked
+    const int64_t m = geom_member_of_thread(A);
+    if (m < 0) return;
+    if (A.err[2]) {                                       // member offsets rejected: mdesign is not valid
+        A.cnt[m] = 0;
+        A.cntm[m] = 0;
+        return;
+    }
+    GMember R;
+    int d;
+    const int fix = A.fixRec ? A.fixIdx[m % A.fixNM] : -1;
+    if (fix >= 0) {
+        // a fixed member of the job's variant program (uniform designs of fixNM members, no pose): the record of its pass
+        d = (int)(m / A.fixNM);
+        const int4 ir = *reinterpret_cast<const int4 *>(A.fixInt + (size_t)fix * FR_I);
+        R.wet = ir.x; R.wetm = ir.y; R.code = ir.z; R.rej = ir.w;
+        if (!R.rej) {
+            const double2 *src = reinterpret_cast<const double2 *>(A.fixRec + (size_t)fix * FR_N);
+            double2 *mp = reinterpret_cast<double2 *>(A.mpose + (size_t)m * MP_N), *mh = reinterpret_cast<double2 *>(A.mhyd + (size_t)m * MH_N),
+                    *mi = reinterpret_cast<double2 *>(A.minert + (size_t)m * MI_N);
+#pragma unroll
+            for (int i = 0; i < MP_N / 2; i++) mp[i] = src[i];
+#pragma unroll 8
+            for (int i = 0; i < MH_N / 2; i++) mh[i] = src[MP_N / 2 + i];
+#pragma unroll 8
+            for (int i = 0; i < MI_N / 2; i++) mi[i] = src[(MP_N + MH_N) / 2 + i];
+        }
+    } else {
+        // ---- first round trip: everything that hangs on m alone
+        const int64_t so0 = A.so(m), so1 = A.so(m + 1);
+        const int64_t co0 = A.capOff ? A.co(m) : 0, co1 = A.capOff ? A.co(m + 1) : 0;
+        d = A.mdesign[m];
+        R = geom_member_body(A.gm + (size_t)m * RAFTX_GM_N, A.gs + (size_t)so0 * RAFTX_GS_N, (int)(so1 - so0),
+                             A.capOff ? A.caps + (size_t)co0 * RAFTX_GC_N : nullptr, A.capOff ? (int)(co1 - co0) : 0,
+                             A.pose ? A.pose + (size_t)d * 6 : nullptr, A.rho, A.g, (A.add_mask & RAFTX_TRIM_BALLAST) != 0, A.k != nullptr,
+                             A.mpose + (size_t)m * MP_N, A.mhyd + (size_t)m * MH_N, A.minert + (size_t)m * MI_N);
+    }
+    if (R.rej) {
+        A.cnt[m] = 0;
+        A.cntm[m] = 0;
+        atomicCAS(A.err + 3, 0, R.rej == 1 ? (int)(m + 1) : -(int)(m + 1));
+        return;
+    }
+    A.cnt[m] = R.wet;
+    A.cntm[m] = R.wetm;
+    // per-design totals (integer sums: the order of the additions does not matter)
+    if (R.wet) atomicAdd(reinterpret_cast<unsigned long long *>(A.off + d + 1), (unsigned long long)R.wet);
+    if (R.wetm) atomicAdd(reinterpret_cast<unsigned long long *>(A.cmoff + d + 1), (unsigned long long)R.wetm);
+    if (R.code) atomicCAS(A.err, 0, (int)(m + 1));
 }
 
 // Model.adjustBallastDensity (raft_model.py:1789-1805), one thread per design: heave imbalance of the untrimmed unit ->
@@ -1125,6 +1195,9 @@ __device__ __forceinline__ void geom_design_block(const GeomArgs &A, const int d
         double *sgm = reinterpret_cast<double *>(okv + (((int)(ssta - okv) + nMem + 2) & ~1));      // [nMem][GD_GM_N]
         double *sgs = sgm + (size_t)nMem * GD_GM_N;                               // [nSta][RAFTX_GS_N]
         double *smp = sgs + (size_t)nSta * RAFTX_GS_N;                            // [nMem][GD_MP_N]
+        // the member pass's wet-strip count of member `lane`, loaded beside its station offset: a member without a wet strip
+        // (a tower; a brace above the water) takes no part in the candidate rounds below
+        int cnt_lane = 0;
         {
             // (the three tables are one contiguous stretch of LDS: a lane's loads of a round -- ten, enough for a design of 16
             // members and 64 stations -- and its first-station offset are all in flight before the first of them is waited for)
@@ -1132,6 +1205,7 @@ __device__ __forceinline__ void geom_design_block(const GeomArgs &A, const int d
             const int n0 = nMem * GD_GM_N, n01 = n0 + nSta * RAFTX_GS_N, total = n01 + nMem * GD_MP_N;
             constexpr int SU = 10;
             const int64_t so_lane = lane <= nMem ? A.so(m0 + lane) : s0;
+            cnt_lane = lane < nMem ? A.cnt[m0 + lane] : 0;
             for (int base = 0; base < total; base += SU * GD_T) {
                 double v[SU];
 #pragma unroll
@@ -1177,9 +1251,12 @@ __device__ __forceinline__ void geom_design_block(const GeomArgs &A, const int d
         for (int mi = lane; mi < nMem; mi += GD_T) {
             const int n = ssta[mi + 1] - ssta[mi];
             int *cum = mcum + ssta[mi] + 2 * mi;
+            // dry member: its groups count 0 and its width is 0 -- the member search below steps over it, wherever it stands
+            // in the member order (numbering, candidate indices and the compaction order of the others are what they were)
+            const bool dry = (mi == lane ? cnt_lane : A.cnt[m0 + mi]) == 0;
             int a = 0;
             cum[0] = 0;
-            for (int g = 0; g <= n; g++) { a += cum[g + 1]; cum[g + 1] = a; }
+            for (int g = 0; g <= n; g++) { a += dry ? 0 : cum[g + 1]; cum[g + 1] = a; }
             mbase[mi + 1] = a;
         }
         __syncthreads();

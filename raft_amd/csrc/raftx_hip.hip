@@ -792,8 +792,27 @@ struct CaseSet {
 
 // Edit program of parametric variants (raftx_variant_program): the base unit's descriptors and the affine edits, resident
 // on the device; the uniform offset arrays of a batch of nDesign variants on the host (cached per batch size).
+// The member pass of the program's FIXED members (no end edit, no diameter edit on a station: k_geom_expand writes their
+// base rows unchanged into every design), run once by k_geom_member_fixed and copied by the member pass of every job
+// without per-design poses.  Keyed by what the pass reads besides the rows.  A crossing pins the record it was prepared
+// with until it is retired, so that a crossing with another key writes another record (one more than there are slots).
+struct FixedRecord {
+    bool valid = false;
+    double rho = 0, g = 0;
+    int trim = 0, haveK = 0;
+    double *rec = nullptr;               // [nFix,FR_N]
+    int *irec = nullptr;                 // [nFix,FR_I]
+    int users = 0;                       // crossings prepared or in flight on this record
+    unsigned long long stamp = 0;
+    hipEvent_t ev = nullptr;             // the record has been written (on `stream`)
+    hipStream_t stream = nullptr;
+};
 struct VariantProg {
     int nM = 0, nSt = 0, nCap = 0, nP = 0;
+    int nFix = 0;                                                        // fixed members
+    int *fixDesc = nullptr, *fixIdx = nullptr;                           // [nFix,5] (FixedArgs::desc) / [nM] record of a member, or -1
+    FixedRecord recs[RAFTX_NSLOT + 1];
+    unsigned long long rec_clock = 0;
     bool has_caps = false;
     double *gm = nullptr, *gs = nullptr, *gc = nullptr;                  // base descriptors
     int *stMember = nullptr, *capMember = nullptr;                       // member of every station / cap row
@@ -809,6 +828,7 @@ struct VariantProg {
 struct VariantSrc {
     const VariantProg *prog;
     const double *params;                                                // host, [nDesign of the batch, nP]
+    const FixedRecord *rec = nullptr;                                    // the fixed members' record the batch's member passes copy, or null
 };
 
 static void expand_args(const VariantProg &P, int n, double *gm_out, double *gs_out, double *gc_out, ExpandArgs &E) {
@@ -929,6 +949,7 @@ struct BuildSource {
 struct SweepSlot {
     bool busy = false;                   // launched (phase 2 enqueued), not yet waited for
     int cset = -1;                       // the CaseSet of the parent this crossing was prepared with (pinned until retired)
+    int frec = -1;                       // ... and the FixedRecord of the parent's variant program, or -1
     bool prepared = false;               // phase 1 enqueued (descriptor upload, member pass), not yet launched
     int nIter = 0;
     double tol = 0, XiStart = 0, dw = 0;
@@ -1075,6 +1096,13 @@ static void free_list(raftx_ctx *c, std::vector<void *> &v) {
     v.clear();
 }
 
+// the variant program of a ctx, its fixed members' records and their events
+static void variant_release(raftx_ctx *c) {
+    for (FixedRecord &R : c->vprog.recs)
+        if (R.ev) (void)hipEventDestroy(R.ev);
+    free_list(c, c->vprog.allocs);
+    c->vprog = VariantProg();
+}
 extern "C" void raftx_ctx_destroy(raftx_ctx *c) {
     if (!c) return;
 #ifdef GEOM_PHASE_TIMING
@@ -1117,7 +1145,7 @@ extern "C" void raftx_ctx_destroy(raftx_ctx *c) {
     if (c->rKay) (void)hipFree(c->rKay);
     if (c->pairList) (void)hipFree(c->pairList);
     free_list(c, c->dense.allocs);
-    free_list(c, c->vprog.allocs);
+    variant_release(c);
     if (c->identList) (void)hipFree(c->identList);
     for (hipEvent_t e : c->evSlab) (void)hipEventDestroy(e);
     if (c->evFork) (void)hipEventDestroy(c->evFork);
@@ -1461,6 +1489,11 @@ static int build_phase1(raftx_ctx *c, hipStream_t sCopy, hipStream_t sPrep, cons
         // running fused kernel of the batch before (a high-priority stream of its own gained nothing: profiles/MEASUREMENT_HISTORY.md,
         // "Closed scheduling experiments of the crossing")
         launch_expand(E, sPrep);
+        if (const FixedRecord *R = B.var.rec) {
+            // the fixed members' pass ran once for the program: this job's member pass copies it
+            if (R->stream != sPrep) HIPCHK(c, hipStreamWaitEvent(sPrep, R->ev, 0));
+            A.fixRec = R->rec; A.fixInt = R->irec; A.fixIdx = B.var.prog->fixIdx; A.fixNM = B.var.prog->nM;
+        }
     }
     if (int rc = alloc_member_scratch(c)) return rc;
     if (int rc = design_bounds(c, B, L)) return rc;
@@ -3251,6 +3284,8 @@ static bool others_in_flight(raftx_ctx *c, int slot) {
 static void slot_release_cases(raftx_ctx *c, SweepSlot &S) {
     if (S.cset >= 0 && c->csets[S.cset].users > 0) c->csets[S.cset].users--;
     S.cset = -1;
+    if (S.frec >= 0 && c->vprog.recs[S.frec].users > 0) c->vprog.recs[S.frec].users--;
+    S.frec = -1;
 }
 
 // a crossing failed while it was being enqueued: drains the device, retires the jobs of its blocks, unpins its sea states
@@ -3347,6 +3382,7 @@ static int block_phase1(raftx_ctx *c, SweepSlot &S, size_t b) {
     return build_phase1(S.blk[b], c->sCopy, c->sPrep, S.p1, S.bnd[b], S.bnd[b + 1] - S.bnd[b]);
 }
 
+static int acquire_fixed(raftx_ctx *c, SweepSlot &S);
 static int sweep_prepare_impl(raftx_ctx *c, int slot, int nDesign, const BuildSource &src, const SeaStates &sea, const SweepRun &run) {
     RangeScope range_("raftx_sweep_prepare: descriptor H2D + member pass (enqueue)");
     if (!c) return -1;
@@ -3368,6 +3404,7 @@ static int sweep_prepare_impl(raftx_ctx *c, int slot, int nDesign, const BuildSo
         FAIL(c, "sweep_stats: member offsets not monotone");
     }
     if (int rc = upload_offsets(c, S, src, nDesign)) return sweep_fail_drain(c, S, rc);
+    if (int rc = acquire_fixed(c, S)) return sweep_fail_drain(c, S, rc);
     // ---- phase 1: H2D on sCopy, member pass + scans on sPrep.  Every block here -- except for an isolated crossing cut into
     // slabs (responses wanted, nothing else in flight): there only the first two; raftx_sweep_launch enqueues the others one
     // block ahead of the block it launches.  (The ordinary streams share hardware queues: with every block's copies queued
@@ -3410,8 +3447,7 @@ extern "C" int raftx_variant_program(raftx_ctx *c, int nMember, const double *me
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     VariantProg &P = c->vprog;
-    free_list(c, P.allocs);
-    P = VariantProg();
+    variant_release(c);                               // the fixed members' records go with the program
     if (nMember == 0) return 0;
     if (nMember < 0 || nParam < 0 || nParam > 64 || !members || !stationOff || !stations || (capOff == nullptr) != (caps == nullptr))
         FAIL(c, "variant_program: bad arguments");
@@ -3463,11 +3499,64 @@ extern "C" int raftx_variant_program(raftx_ctx *c, int nMember, const double *me
     rc |= up(diaCoef, (size_t)nSt * 2 * (nP + 1) * 8, (void **)&P.diaCoef);
     rc |= up(endEdit, (size_t)nM * 4, (void **)&P.endEdit);
     rc |= up(diaEdit, (size_t)nSt * 4, (void **)&P.diaEdit);
+    // fixed members: no end edit and no diameter edit on any of their stations
+    std::vector<int> desc, fidx((size_t)nM, -1);
+    for (int m = 0; m < nM; m++) {
+        bool fixed = endEdit[m] == 0;
+        for (int64_t i = stationOff[m]; fixed && i < stationOff[m + 1]; i++) fixed = diaEdit[i] == 0;
+        if (!fixed) continue;
+        fidx[(size_t)m] = P.nFix++;
+        desc.insert(desc.end(), {m, (int)stationOff[m], (int)(stationOff[m + 1] - stationOff[m]), capOff ? (int)capOff[m] : 0,
+                                 capOff ? (int)(capOff[m + 1] - capOff[m]) : -1});
+    }
+    if (P.nFix) {
+        rc |= up(desc.data(), desc.size() * 4, (void **)&P.fixDesc);
+        rc |= up(fidx.data(), (size_t)nM * 4, (void **)&P.fixIdx);
+        for (FixedRecord &R : P.recs) {
+            rc |= up(nullptr, (size_t)P.nFix * FR_N * 8, (void **)&R.rec);
+            rc |= up(nullptr, (size_t)P.nFix * FR_I * 4, (void **)&R.irec);
+            if (!rc) HIPCHK(c, hipMemset(R.rec, 0, (size_t)P.nFix * FR_N * 8));
+        }
+    }
     if (rc) {
-        free_list(c, P.allocs);
-        P = VariantProg();
+        variant_release(c);
         return rc;
     }
+    return 0;
+}
+// The record of the program's fixed members for the slot's crossing: the one with the crossing's key, or -- on sPrep,
+// ahead of the member passes that copy it -- k_geom_member_fixed into the idle record used longest ago.  Pinned by the
+// slot until it is retired (slot_release_cases).  No record: no fixed member, or per-design poses.
+static int acquire_fixed(raftx_ctx *c, SweepSlot &S) {
+    VariantProg &P = c->vprog;
+    BuildSource &src = S.p1;
+    src.var.rec = nullptr;
+    if (src.var.prog != &P || !P.nFix || src.pose) return 0;
+    const int trim = (src.add_mask & RAFTX_TRIM_BALLAST) != 0, haveK = src.k_dev != nullptr;
+    int hit = -1, idle = -1;
+    for (int i = 0; i <= RAFTX_NSLOT; i++) {
+        const FixedRecord &R = P.recs[i];
+        if (R.valid && R.rho == src.rho && R.g == src.g && R.trim == trim && R.haveK == haveK) hit = i;
+        else if (R.users == 0 && (idle < 0 || R.stamp < P.recs[idle].stamp)) idle = i;
+    }
+    if (hit < 0) {
+        if (idle < 0) FAIL(c, "sweep_prepare_variants: no free record of the fixed members");      // cannot happen: NSLOT + 1 records
+        FixedRecord &R = P.recs[idle];                // users == 0: every crossing that read it has been waited for
+        R.valid = false;
+        if (!R.ev) HIPCHK(c, hipEventCreateWithFlags(&R.ev, hipEventDisableTiming));
+        FixedArgs F{P.nFix, P.gm, P.gs, P.gc, P.fixDesc, src.rho, src.g, trim, haveK, R.rec, R.irec};
+        hipLaunchKernelGGL(k_geom_member_fixed, dim3((unsigned)((P.nFix + 63) / 64)), dim3(64), 0, c->sPrep, F);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipEventRecord(R.ev, c->sPrep));
+        R.stream = c->sPrep;
+        R.rho = src.rho; R.g = src.g; R.trim = trim; R.haveK = haveK;
+        R.valid = true;
+        hit = idle;
+    }
+    P.recs[hit].users++;
+    P.recs[hit].stamp = ++P.rec_clock;
+    S.frec = hit;
+    src.var.rec = &P.recs[hit];
     return 0;
 }
 // uniform offsets of n variants, cached on the program
