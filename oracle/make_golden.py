@@ -71,7 +71,7 @@ def fixture_c1():
     standin.save_fixture(os.path.join(GOLD, "c1_oc3spar.npz"), fx)
 
 
-def fixture_c2():
+def _c2_model_and_cases():
     d = rh.load_design(os.path.join(REF, "examples/VolturnUS-S_example.yaml"))
     d = rh.prepare_design(d)
     m = rh.build_model(d)
@@ -79,14 +79,17 @@ def fixture_c2():
              rh.make_case(Hs=6.0, Tp=12.0, heading=30.0),
              rh.make_case(Hs=[6.0, 3.0], Tp=[12.0, 9.0], heading=[0.0, 70.0],
                           spectrum=["JONSWAP", "JONSWAP"], gamma=[0, 0])]
+    return m, cases
+
+
+def fixture_c2():
+    m, cases = _c2_model_and_cases()
     fx = {"config": "C2 VolturnUS-S_example nw=200", "model": standin.snapshot_model(m),
           "cases": [run_case(m, c) for c in cases]}
     standin.save_fixture(os.path.join(GOLD, "c2_volturnus.npz"), fx)
 
 
-def fixture_pose():
-    """Non-trivial mean pose + XiStart != 0 + more iterations (exercises the
-    folded member-node -> reduced-DOF arm, SURVEY.md Appendix A)."""
+def _pose_model_and_cases():
     d = rh.load_design(os.path.join(REF, "tests/test_data/VolturnUS-S.yaml"))
     d = rh.prepare_design(d, settings=dict(XiStart=0.1, nIter=15))
     d["platform"]["potSecOrder"] = 0         # keep the QTF re-entry out of this fixture
@@ -94,9 +97,46 @@ def fixture_pose():
     cases = [rh.make_case(Hs=4.0, Tp=10.0, heading=30.0),
              rh.make_case(Hs=[4.0, 2.0], Tp=[10.0, 7.0], heading=[30.0, -70.0],
                           spectrum=["JONSWAP", "JONSWAP"], gamma=[0, 0])]
+    return m, cases
+
+
+def fixture_pose():
+    """Non-trivial mean pose + XiStart != 0 + more iterations (exercises the
+    folded member-node -> reduced-DOF arm, SURVEY.md Appendix A)."""
+    m, cases = _pose_model_and_cases()
     fx = {"config": "VolturnUS-S (MCF columns) at offset pose", "model": standin.snapshot_model(m),
           "cases": [run_case(m, c) for c in cases]}
     standin.save_fixture(os.path.join(GOLD, "pose_volturnus_mcf.npz"), fx)
+
+
+def fixture_linearisation_points():
+    """The linearisation point the reference's fixed point stops at (the argument of its LAST calcHydroLinearization call,
+    raft_model.py:1063): what B_hydro_drag of c2_volturnus.npz / pose_volturnus_mcf.npz was linearised about.  The runs
+    are those of fixture_c2 / fixture_pose again; their B_hydro_drag and F_hydro_iner must come out bit-equal to the
+    committed fixtures, which are left as they are (tests/test_strip_reference.py holds both to the entry-wise gate)."""
+    out = {"config": "last linearisation points of c2_volturnus.npz and pose_volturnus_mcf.npz (live reference)"}
+    for name, build in (("c2_volturnus", _c2_model_and_cases), ("pose_volturnus_mcf", _pose_model_and_cases)):
+        m, cases = build()
+        old = standin.load_fixture(name + ".npz")
+        pts = []
+        for ic, case in enumerate(cases):
+            f = m.fowtList[0]
+            seen = []
+            orig = f.calcHydroLinearization
+
+            def wrapped(Xi, _orig=orig, _seen=seen):
+                _seen.append(np.array(Xi))
+                return _orig(Xi)
+            f.calcHydroLinearization = wrapped
+            m.solveDynamics(copy.deepcopy(case))
+            del f.calcHydroLinearization
+            u = old["cases"][ic]["units"][0]
+            assert len(seen) == int(u["niter"])
+            assert np.array_equal(np.array(f.B_hydro_drag), u["B_hydro_drag"]), (name, ic)
+            assert np.array_equal(np.array(f.F_hydro_iner), u["F_hydro_iner"]), (name, ic)
+            pts.append(seen[-1])
+        out[name] = np.array(pts)
+    standin.save_fixture(os.path.join(GOLD, "strip_linpoints.npz"), out)
 
 
 def fixture_ref_goldens():
@@ -789,7 +829,7 @@ def fixture_flexible_moor():
     standin.save_fixture(os.path.join(GOLD, "flex_moormod2.npz"), fx)
 
 
-ALL = {"flexmcf": fixture_flexible_mcf, "flexmoor": fixture_flexible_moor, "flexible": fixture_flexible, "f4": fixture_f4, "c5full": fixture_c5_full, "refstatics": fixture_ref_statics, "refmembers": fixture_ref_members, "bem": fixture_bem, "geom": fixture_geom, "c5oc4": fixture_c5_oc4, "c5": fixture_c5, "qtf": fixture_qtf, "c1": fixture_c1, "c2": fixture_c2, "pose": fixture_pose,
+ALL = {"linpoints": fixture_linearisation_points, "flexmcf": fixture_flexible_mcf, "flexmoor": fixture_flexible_moor, "flexible": fixture_flexible, "f4": fixture_f4, "c5full": fixture_c5_full, "refstatics": fixture_ref_statics, "refmembers": fixture_ref_members, "bem": fixture_bem, "geom": fixture_geom, "c5oc4": fixture_c5_oc4, "c5": fixture_c5, "qtf": fixture_qtf, "c1": fixture_c1, "c2": fixture_c2, "pose": fixture_pose,
        "refgold": fixture_ref_goldens, "c4": fixture_c4, "c3": fixture_c3}
 
 if __name__ == "__main__":
