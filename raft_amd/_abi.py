@@ -45,6 +45,10 @@ MODAL_SMALL_DIAG, MODAL_NONPOSITIVE, MODAL_COMPLEX, MODAL_SINGULAR_M, MODAL_NO_C
 CURRENT_EXPORTS = ("raftx_current_loads", "raftx_sweep_current")
 # include/raftx_channels.h: output channels of a sweep crossing, the device library only
 CHANNEL_EXPORTS = ("raftx_sweep_channels",)
+# include/raftx_qtfgen.h: second-order QTF tables generated on the device, the device library only
+QTFGEN_EXPORTS = ("raftx_qtf_tables_build", "raftx_qtf_tables_build_variants", "raftx_qtf_tables_counts", "raftx_qtf_tables_fetch",
+                  "raftx_qtf_tables_kay_items", "raftx_qtf_slender_resident")
+QKG_N = 8          # doubles per row of the Kim & Yue geometry stream (RAFTX_QKG_N)
 
 
 class RaftxError(RuntimeError):
@@ -153,6 +157,21 @@ class RaftxLib:
             L.raftx_current_loads.restype = C.c_int
             L.raftx_sweep_current.argtypes = [_vp, C.c_int, C.c_int, _vp, _vp, _vp, C.c_double, _vp]
             L.raftx_sweep_current.restype = C.c_int
+        self.has_qtfgen = all(hasattr(L, s) for s in QTFGEN_EXPORTS)
+        if self.has_qtfgen:
+            L.raftx_qtf_tables_build.argtypes = [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]
+            L.raftx_qtf_tables_build.restype = C.c_int
+            L.raftx_qtf_tables_build_variants.argtypes = [_vp, C.c_int, _vp, _vp, _vp, _vp]
+            L.raftx_qtf_tables_build_variants.restype = C.c_int
+            L.raftx_qtf_tables_counts.argtypes = [_vp, _vp]
+            L.raftx_qtf_tables_counts.restype = C.c_int
+            L.raftx_qtf_tables_fetch.argtypes = [_vp, _vp, _vp, _vp, _vp]
+            L.raftx_qtf_tables_fetch.restype = C.c_int
+            L.raftx_qtf_tables_kay_items.argtypes = [_vp, C.c_int, _vp, _vp, _vp]
+            L.raftx_qtf_tables_kay_items.restype = C.c_int
+            L.raftx_qtf_slender_resident.argtypes = [_vp, C.c_int, C.c_int, _vp, _vp, C.c_double, C.c_double, C.c_double, _vp, _vp,
+                                                     _vp, C.c_int, _vp]
+            L.raftx_qtf_slender_resident.restype = C.c_int
         self.has_channels = all(hasattr(L, s) for s in CHANNEL_EXPORTS)
         if self.has_channels:
             L.raftx_sweep_channels.argtypes = [_vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int, _vp, _vp]
@@ -900,6 +919,112 @@ class Context:
                                              _ptr(soff), _ptr(strips), _ptr(moff), _ptr(members), _ptr(Xi), _ptr(beta),
                                              _ptr(Mstruc), _ptr(kay), _ptr(qtf))
         self._check(rc, "raftx_qtf_slender")
+        return qtf
+
+    # ------------------------------------------------------------- second-order tables on the device (include/raftx_qtfgen.h)
+    def _qtfgen_lib(self, what):
+        if not self.rlib.has_qtfgen:
+            raise RaftxError("%s: %s does not implement include/raftx_qtfgen.h (the device library does)" % (what, self.rlib.path))
+        return self.rlib.lib
+
+    def qtf_tables_build(self, tables, pose=None):
+        """The second-order strip / member records and Kim & Yue geometry of the designs ``tables`` (raft_amd.geometry
+        DesignTables: the descriptors build_designs takes) generated on the device and left resident
+        (raftx_qtf_tables_build).  pose [nD,6] or None.  Returns (strip_off, mem_off), [nD+1] each."""
+        L = self._qtfgen_lib("qtf_tables_build")
+        member_off = np.ascontiguousarray(tables.member_off, dtype=np.int64)
+        station_off = np.ascontiguousarray(tables.station_off, dtype=np.int64)
+        nD = len(member_off) - 1
+        members = _f64(tables.members, (member_off[-1], 16), "members")
+        if len(station_off) != member_off[-1] + 1:
+            raise ValueError("station_off has %d entries, expected %d" % (len(station_off), member_off[-1] + 1))
+        stations = _f64(tables.stations, (station_off[-1], 16), "stations")
+        if pose is not None:
+            pose = _f64(pose, (nD, 6), "pose")
+        soff, moff = np.zeros(nD + 1, dtype=np.int64), np.zeros(nD + 1, dtype=np.int64)
+        self._check(L.raftx_qtf_tables_build(self._h, nD, _ptr(member_off), _ptr(members), _ptr(station_off), _ptr(stations), _ptr(pose),
+                                             _ptr(soff), _ptr(moff)), "raftx_qtf_tables_build")
+        self._qtf_offsets = (soff, moff)
+        return soff, moff
+
+    def qtf_tables_build_variants(self, params, pose=None):
+        """The same for the variants ``params`` [nD,nParam] of the installed program (raftx_qtf_tables_build_variants): only
+        the parameters cross the bus."""
+        L = self._qtfgen_lib("qtf_tables_build_variants")
+        if getattr(self, "_vprog", None) is None:
+            raise RaftxError("qtf_tables_build_variants: no program installed (variant_program first)")
+        params = _f64(params)
+        nD = params.shape[0]
+        params = _f64(params, (nD, self._vprog[3]), "params")
+        if pose is not None:
+            pose = _f64(pose, (nD, 6), "pose")
+        soff, moff = np.zeros(nD + 1, dtype=np.int64), np.zeros(nD + 1, dtype=np.int64)
+        self._check(L.raftx_qtf_tables_build_variants(self._h, nD, _ptr(params), _ptr(pose), _ptr(soff), _ptr(moff)),
+                    "raftx_qtf_tables_build_variants")
+        self._qtf_offsets = (soff, moff)
+        return soff, moff
+
+    def qtf_tables_counts(self):
+        """(designs, strip records, member records, Kim & Yue rows, Kim & Yue items per heading) of the resident tables."""
+        L = self._qtfgen_lib("qtf_tables_counts")
+        n = np.zeros(5, dtype=np.int64)
+        self._check(L.raftx_qtf_tables_counts(self._h, _ptr(n)), "raftx_qtf_tables_counts")
+        return tuple(int(x) for x in n)
+
+    def qtf_tables_fetch(self, raw=False):
+        """The resident records as a list of raft_amd.qtf.QtfTable, one per design, with ``kay_geom`` filled
+        (raftx_qtf_tables_fetch).  raw=True: (strip_off, strips, mem_off, members, kay_off, kay_rows) instead."""
+        from .qtf import QtfTable, QS_N, QM_N
+        L = self._qtfgen_lib("qtf_tables_fetch")
+        nD, nS, nM, nK, _ = self.qtf_tables_counts()
+        strips, members, kay = np.zeros((nS, QS_N)), np.zeros((nM, QM_N)), np.zeros((nK, QKG_N))
+        koff = np.zeros(nD + 1, dtype=np.int64)
+        self._check(L.raftx_qtf_tables_fetch(self._h, _ptr(strips), _ptr(members), _ptr(koff), _ptr(kay)), "raftx_qtf_tables_fetch")
+        soff, moff = self._qtf_offsets                     # of the build that left these tables
+        if raw:
+            return soff, strips, moff, members, koff, kay
+        out = []
+        for d in range(nD):
+            geom, row = [], int(koff[d])
+            while row < koff[d + 1]:
+                h = kay[row:row + 2].reshape(-1)
+                ns = int(h[0])
+                nd = kay[row + 2:row + 2 + ns]
+                geom.append(dict(rA=h[1:4].copy(), rB=h[4:7].copy(), r=nd[:, 0:3].copy(), ds=nd[:, 3].copy(), dls=nd[:, 4].copy(),
+                                 p1=h[8:11].copy(), p2=h[11:14].copy()))
+                row += 2 + ns
+            out.append(QtfTable(strips[soff[d]:soff[d + 1]], members[moff[d]:moff[d + 1]], geom))
+        return out
+
+    def qtf_tables_kay_items(self, beta):
+        """Kim & Yue items of the resident tables at the headings beta [nCase] (raftx_qtf_tables_kay_items): (item_off
+        [nD*nCase+1], items [n,12]) for the sets s = d * nCase + c -- the records raft_amd.qtf.kay_items makes on the host."""
+        from .qtf import QK_N
+        L = self._qtfgen_lib("qtf_tables_kay_items")
+        beta = _f64(np.atleast_1d(beta))
+        nD, _, _, _, nI = self.qtf_tables_counts()
+        ioff = np.zeros(nD * len(beta) + 1, dtype=np.int64)
+        items = np.zeros((nI * len(beta), QK_N))
+        self._check(L.raftx_qtf_tables_kay_items(self._h, len(beta), _ptr(beta), _ptr(ioff), _ptr(items)), "raftx_qtf_tables_kay_items")
+        return ioff, items
+
+    def qtf_slender_resident(self, Xi, beta, w2, k2, depth, rho, g, Mstruc, Nm=10, fetch=True):
+        """Slender-body QTFs of every (design, sea state) on the RESIDENT tables (raftx_qtf_slender_resident): beta [nCase]
+        headings, Xi [nD*nCase,6,nw2] or None (the RAOs of the resident first-order responses), Mstruc [nD,6,6]; Nm > 0
+        adds the Kim & Yue correction of the MacCamy-Fuchs members, built on the device.  Set s = d * nCase + c.  The
+        result stays resident for qtf_force; returns qtf [nD*nCase,nw2,nw2,6] if fetch."""
+        L = self._qtfgen_lib("qtf_slender_resident")
+        w2 = _f64(w2)
+        nw2 = len(w2)
+        k2 = _f64(k2, (nw2,), "k2")
+        beta = _f64(np.atleast_1d(beta))
+        nC = len(beta)
+        nD = self.qtf_tables_counts()[0]
+        Xi = None if Xi is None else _c128(Xi, (nD * nC, 6, nw2), "Xi")
+        Mstruc = _f64(Mstruc, (nD, 6, 6), "Mstruc")
+        qtf = np.empty((nD * nC, nw2, nw2, 6), dtype=np.complex128) if fetch else None
+        self._check(L.raftx_qtf_slender_resident(self._h, nC, nw2, _ptr(w2), _ptr(k2), float(depth), float(rho), float(g), _ptr(Xi),
+                                                 _ptr(beta), _ptr(Mstruc), int(Nm), _ptr(qtf)), "raftx_qtf_slender_resident")
         return qtf
 
     def set_linearisation_point(self, XiLast0=None, keep_last=True):

@@ -277,6 +277,25 @@ __device__ inline GStrip geom_strip(const double *gs, int n, int g, int j, int n
     }
     return s;
 }
+// side volume (with the waterline scaling of a strip that pierces the surface, raft_member.py:1328-1330 = :1562-1568), end
+// volume and end area of a strip whose node lies at elevation z (:1320-1347 = :1613-1618): one body for the first-order
+// strip constants (k_geom_design) and the second-order strip records (raftx_qtfgen.h)
+__device__ __forceinline__ void geom_strip_volumes(const GStrip &st, bool circ, double z, double &v_i, double &v_end, double &a_i) {
+    GEOM_NOFMA
+    const double ds0 = st.ds0, ds1 = st.ds1, dr0 = st.drs0, dr1 = st.drs1, dls = st.dls;
+    if (circ) {
+        v_i = 0.25 * M_PI * ds0 * ds0 * dls;
+        const double a3 = ds0 + dr0, b3 = ds0 - dr0;
+        v_end = M_PI / 12.0 * fabs(a3 * a3 * a3 - b3 * b3 * b3);
+        a_i = M_PI * ds0 * dr0;
+    } else {
+        v_i = ds0 * ds1 * dls;
+        const double ma = 0.5 * ((ds0 + dr0) + (ds1 + dr1)), mb = 0.5 * ((ds0 - dr0) + (ds1 - dr1));
+        v_end = M_PI / 12.0 * (ma * ma * ma - mb * mb * mb);
+        a_i = (ds0 + dr0) * (ds1 + dr1) - (ds0 - dr0) * (ds1 - dr1);
+    }
+    if (z + 0.5 * dls > 0) v_i = v_i * (0.5 * dls - z) / dls;      // pierces the waterline, :1328-1330
+}
 // node position of a strip along the member (raft_member.py:362)
 __device__ inline double geom_along(double rA, double rB, double ls, double L) {
     GEOM_NOFMA
@@ -623,6 +642,48 @@ struct GMember {
     int code;                    // != 0: cap / bulkhead layout the reference refuses (mi has been zeroed)
     int rej;                     // 1: bad station count / dlsMax / length, 2: MacCamy-Fuchs without wave numbers; nothing was written
 };
+// Member.setPosition (raft_member.py:324-372) for a rigid member of a rigid unit at the pose ps[6] of its platform: the
+// undisplaced end A, the member's triad and ends at the pose, and the 2 x 2 block of the rotated section axes.  One body
+// for the member pass and for the generator of the second-order records (raftx_qtfgen.h): the nodes of both are the same bits.
+__device__ __forceinline__ void geom_pose(const double *gm, const double (&ps)[6], double (&rA0)[3], double (&q)[3], double (&p1)[3],
+                                          double (&p2)[3], double (&rA)[3], double (&rB)[3], double (&R)[2][2]) {
+    GEOM_NOFMA
+    double q0[3], nrm = 0.0;
+    for (int i = 0; i < 3; i++) {
+        rA0[i] = gm[RAFTX_GM_RA + i];
+        q0[i] = gm[RAFTX_GM_RB + i] - gm[RAFTX_GM_RA + i];
+        nrm += q0[i] * q0[i];
+    }
+    nrm = sqrt(nrm);
+    for (int i = 0; i < 3; i++) q0[i] /= nrm;
+    const double beta = atan2(q0[1], q0[0]);
+    const double phi = atan2(sqrt(q0[0] * q0[0] + q0[1] * q0[1]), q0[2]);
+    const double gam = gm[RAFTX_GM_GAMMA] * (M_PI / 180.0);
+    const double s1 = sin(beta), c1 = cos(beta), s2 = sin(phi), c2 = cos(phi), s3 = sin(gam), c3 = cos(gam);
+    const double R0[3][3] = {{c1 * c2 * c3 - s1 * s3, -c3 * s1 - c1 * c2 * s3, c1 * s2},
+                             {c1 * s3 + c2 * c3 * s1, c1 * c3 - c2 * s1 * s3, s1 * s2},
+                             {-c3 * s2, s2 * s3, c2}};
+    const double p10[3] = {R0[0][0], R0[1][0], R0[2][0]};
+    const double p20[3] = {q0[1] * p10[2] - q0[2] * p10[1], q0[2] * p10[0] - q0[0] * p10[2], q0[0] * p10[1] - q0[1] * p10[0]};
+    // platform rotation, helpers.py:439-466 with (x3, x2, x1) = (roll, pitch, yaw)
+    const double sy = sin(ps[5]), cy = cos(ps[5]), sp = sin(ps[4]), cp = cos(ps[4]), sr = sin(ps[3]), cr = cos(ps[3]);
+    const double Rp[3][3] = {{cy * cp, cy * sp * sr - cr * sy, sy * sr + cy * cr * sp},
+                             {cp * sy, cy * cr + sy * sp * sr, cr * sy * sp - cy * sr},
+                             {-sp, cp * sr, cp * cr}};
+    const double L = gm[RAFTX_GM_L];
+    for (int i = 0; i < 3; i++) {
+        q[i] = Rp[i][0] * q0[0] + Rp[i][1] * q0[1] + Rp[i][2] * q0[2];
+        p1[i] = Rp[i][0] * p10[0] + Rp[i][1] * p10[1] + Rp[i][2] * p10[2];
+        p2[i] = Rp[i][0] * p20[0] + Rp[i][1] * p20[1] + Rp[i][2] * p20[2];
+        // node displacement = unit displacement + (R_platform - I) rA0 (raft_fowt.py:706-718)
+        const double dsp = (Rp[i][0] - (i == 0 ? 1.0 : 0.0)) * rA0[0] + (Rp[i][1] - (i == 1 ? 1.0 : 0.0)) * rA0[1] +
+                           (Rp[i][2] - (i == 2 ? 1.0 : 0.0)) * rA0[2];
+        rA[i] = rA0[i] + (ps[i] + dsp);
+    }
+    for (int i = 0; i < 3; i++) rB[i] = rA[i] + L * q[i];
+    for (int i = 0; i < 2; i++)
+        for (int j = 0; j < 2; j++) R[i][j] = Rp[i][0] * R0[0][j] + Rp[i][1] * R0[1][j] + Rp[i][2] * R0[2][j];
+}
 #define FR_N (MP_N + MH_N + MI_N) // doubles of a fixed member's record: mp | mh | mi
 #define FR_I 4                    // ints of it: the four of GMember
 __device__ __forceinline__ GMember geom_member_body(const double *gmrow, const double *gs, const int n, const double *gc, const int ncap,
@@ -656,43 +717,9 @@ __device__ __forceinline__ GMember geom_member_body(const double *gmrow, const d
     geom_load_row(gs, 0, b);
     const bool circ = gm[RAFTX_GM_SHAPE] != 0.0;
     const int flags = (int)gm[RAFTX_GM_FLAGS];
-    // ---- Member.setPosition (raft_member.py:324-372) for a rigid member of a rigid unit
-    double rA0[3], q0[3], nrm = 0.0;
-    for (int i = 0; i < 3; i++) {
-        rA0[i] = gm[RAFTX_GM_RA + i];
-        q0[i] = gm[RAFTX_GM_RB + i] - gm[RAFTX_GM_RA + i];
-        nrm += q0[i] * q0[i];
-    }
-    nrm = sqrt(nrm);
-    for (int i = 0; i < 3; i++) q0[i] /= nrm;
-    const double beta = atan2(q0[1], q0[0]);
-    const double phi = atan2(sqrt(q0[0] * q0[0] + q0[1] * q0[1]), q0[2]);
-    const double gam = gm[RAFTX_GM_GAMMA] * (M_PI / 180.0);
-    const double s1 = sin(beta), c1 = cos(beta), s2 = sin(phi), c2 = cos(phi), s3 = sin(gam), c3 = cos(gam);
-    const double R0[3][3] = {{c1 * c2 * c3 - s1 * s3, -c3 * s1 - c1 * c2 * s3, c1 * s2},
-                             {c1 * s3 + c2 * c3 * s1, c1 * c3 - c2 * s1 * s3, s1 * s2},
-                             {-c3 * s2, s2 * s3, c2}};
-    const double p10[3] = {R0[0][0], R0[1][0], R0[2][0]};
-    const double p20[3] = {q0[1] * p10[2] - q0[2] * p10[1], q0[2] * p10[0] - q0[0] * p10[2], q0[0] * p10[1] - q0[1] * p10[0]};
-    // platform rotation, helpers.py:439-466 with (x3, x2, x1) = (roll, pitch, yaw)
-    const double sy = sin(ps[5]), cy = cos(ps[5]), sp = sin(ps[4]), cp = cos(ps[4]), sr = sin(ps[3]), cr = cos(ps[3]);
-    const double Rp[3][3] = {{cy * cp, cy * sp * sr - cr * sy, sy * sr + cy * cr * sp},
-                             {cp * sy, cy * cr + sy * sp * sr, cr * sy * sp - cy * sr},
-                             {-sp, cp * sr, cp * cr}};
-    double q[3], p1[3], p2[3], rA[3], rB[3], R[2][2];
+    double rA0[3], q[3], p1[3], p2[3], rA[3], rB[3], R[2][2];
     const double L = gm[RAFTX_GM_L];
-    for (int i = 0; i < 3; i++) {
-        q[i] = Rp[i][0] * q0[0] + Rp[i][1] * q0[1] + Rp[i][2] * q0[2];
-        p1[i] = Rp[i][0] * p10[0] + Rp[i][1] * p10[1] + Rp[i][2] * p10[2];
-        p2[i] = Rp[i][0] * p20[0] + Rp[i][1] * p20[1] + Rp[i][2] * p20[2];
-        // node displacement = unit displacement + (R_platform - I) rA0 (raft_fowt.py:706-718)
-        const double dsp = (Rp[i][0] - (i == 0 ? 1.0 : 0.0)) * rA0[0] + (Rp[i][1] - (i == 1 ? 1.0 : 0.0)) * rA0[1] +
-                           (Rp[i][2] - (i == 2 ? 1.0 : 0.0)) * rA0[2];
-        rA[i] = rA0[i] + (ps[i] + dsp);
-    }
-    for (int i = 0; i < 3; i++) rB[i] = rA[i] + L * q[i];
-    for (int i = 0; i < 2; i++)
-        for (int j = 0; j < 2; j++) R[i][j] = Rp[i][0] * R0[0][j] + Rp[i][1] * R0[1][j] + Rp[i][2] * R0[2][j];
+    geom_pose(gm, ps, rA0, q, p1, p2, rA, rB, R);
     // ---- one pass over the stations.  Wet strips (raft_member.py:1310: r[il,2] < 0): only the position ls of a candidate
     // matters here -- geom_strip's expressions for it, group by group: end A (ls = 0), the station intervals, end B
     int wet = 0;
@@ -1336,18 +1363,7 @@ __device__ __forceinline__ void geom_design_block(const GeomArgs &A, const int d
             const double ds0 = st.ds0, ds1 = st.ds1, dr0 = st.drs0, dr1 = st.drs1, dls = st.dls;
             if (!potMod) {
                 double v_i, v_end, a_i;
-                if (circ) {
-                    v_i = 0.25 * M_PI * ds0 * ds0 * dls;
-                    const double a3 = ds0 + dr0, b3 = ds0 - dr0;
-                    v_end = M_PI / 12.0 * fabs(a3 * a3 * a3 - b3 * b3 * b3);
-                    a_i = M_PI * ds0 * dr0;
-                } else {
-                    v_i = ds0 * ds1 * dls;
-                    const double ma = 0.5 * ((ds0 + dr0) + (ds1 + dr1)), mb = 0.5 * ((ds0 - dr0) + (ds1 - dr1));
-                    v_end = M_PI / 12.0 * (ma * ma * ma - mb * mb * mb);
-                    a_i = (ds0 + dr0) * (ds1 + dr1) - (ds0 - dr0) * (ds1 - dr1);
-                }
-                if (r[2] + 0.5 * dls > 0) v_i = v_i * (0.5 * dls - r[2]) / dls;      // pierces the waterline, :1328-1330
+                geom_strip_volumes(st, circ, r[2], v_i, v_end, a_i);
                 const double Ca1 = geom_interp_at(at, st.ls, gs, RAFTX_GS_CA + 1), Ca2 = geom_interp_at(at, st.ls, gs, RAFTX_GS_CA + 2);
                 const double CaE = geom_interp_at(at, st.ls, gs, RAFTX_GS_CA + 3);
                 row[RAFTX_F_IQ] = rho * v_end * CaE;

@@ -44,6 +44,7 @@
 #include "../../include/raftx_modal.h"
 #include "../../include/raftx_current.h"
 #include "../../include/raftx_channels.h"
+#include "../../include/raftx_qtfgen.h"
 
 // roctx ranges around the phases of the host side: named spans for `rocprofv3 --marker-trace`.
 // librocprofiler-sdk-roctx is bound at run time on first use; without it (or outside a profiler) the ranges cost a branch.
@@ -86,6 +87,7 @@ struct RangeScope {
 #include "raftx_modal.h"
 #include "raftx_current.h"
 #include "raftx_channels.h"
+#include "raftx_qtfgen.h"
 
 // Coupled array solve (raft_model.py:1164-1236): Xi = Z_sys^-1 F for every (system, bin).  One wavefront per
 // (system, bin), NBIN (1, 2 or 4: what fits LDS) consecutive bins per workgroup so that the loads of one matrix entry
@@ -847,6 +849,16 @@ struct DenseResident {
     double *w = nullptr, *M = nullptr, *B = nullptr, *C = nullptr;
     std::vector<void *> allocs;
 };
+// The second-order records of the last raftx_qtf_tables_build (include/raftx_qtfgen.h), resident until the next one.
+struct QtfResident {
+    bool valid = false;
+    int nDesign = 0;
+    std::vector<int64_t> off;            // host copy of dOff: [QG_CNT_N][nDesign+1] strips | members | Kim & Yue rows | items
+    int64_t *dOff = nullptr;
+    double *strips = nullptr, *members = nullptr, *kay = nullptr;
+    std::vector<void *> allocs;
+    int64_t total(int j) const { return off[(size_t)j * (nDesign + 1) + nDesign]; }
+};
 struct raftx_ctx {
     int device;
     hipStream_t stream;
@@ -926,6 +938,7 @@ struct raftx_ctx {
     std::vector<raftx_ctx *> workers[RAFTX_NSLOT]; // block contexts of the sweep crossings (device buffers, pool, events), per slot, kept for reuse
     struct SweepSlot *slots;             // [RAFTX_NSLOT] crossings in flight (raftx_sweep_prepare / _launch / _wait)
     VariantProg vprog;                   // raftx_variant_program
+    QtfResident qt;                      // raftx_qtf_tables_build
 };
 // Offset arrays of a whole batch, resident on the device (uploaded once by the sweep crossing, shared by its blocks).
 struct DevOffsets {
@@ -1132,6 +1145,7 @@ extern "C" void raftx_ctx_destroy(raftx_ctx *c) {
     free_list(c, c->design_allocs);
     free_list(c, c->case_allocs);
     free_list(c, c->result_allocs);
+    free_list(c, c->qt.allocs);
     for (CaseSet &cs : c->csets) free_list(c, cs.allocs);
     c->pool.trim();
     if (c->rXl) (void)hipFree(c->rXl);
@@ -3108,6 +3122,7 @@ static int qtf_slender_impl(raftx_ctx *c, int nSet, int nw2, const double *w2, c
         if (kay) H2D(c, dK, kay, nq * sizeof(cplx));
     }
     A.w = dw; A.k = dk; A.soff = dso; A.strips = dS; A.moff = dmo; A.members = dM; A.sset = dss; A.mset = dms;
+    A.srec = A.mrec = nullptr;                           // one table per set
     A.Xi = dXi; A.beta = dB; A.Ms = dMs; A.kay = dK; A.T = dT; A.TA = dTA; A.D = dD; A.TM = dTM; A.TS = dTS; A.qtf = dQ;
     A.row_off = row_off;
     A.row_stride = row_stride;
@@ -3624,6 +3639,286 @@ extern "C" int raftx_sweep_prepare_variants(raftx_ctx *c, int slot, int nDesign,
     src.var = {&P, params};
     return sweep_prepare_impl(c, slot, nDesign, src, SeaStates{nCase, nHead, nw, w, k, depth, rho_wave, g_wave, zeta, beta},
                               SweepRun{nIter, tol, XiStart, nChunk, sd, niter, flags, Xi, stripOffsets});
+}
+
+// ------------------------------------------------------------------ second-order tables on the device (include/raftx_qtfgen.h)
+static bool all_finite(const double *a, size_t n) {
+    for (size_t i = 0; i < n; i++)
+        if (!std::isfinite(a[i])) return false;
+    return true;
+}
+// The generator on descriptors that are in device memory already (uploaded, or written by k_geom_expand on the ctx stream):
+// member pass, offsets inside the designs, scan over the designs, the totals to the host, the write pass.  The tables of an
+// earlier build have been released by the caller's checks passing; `sc` owns the descriptors and the per-member scratch.
+static int qtfgen_run(raftx_ctx *c, Scratch &sc, const char *who, int nDesign, int64_t nMember, const int64_t *dMemberOff,
+                      const int64_t *dStationOff, const double *dgm, const double *dgs, const double *dpose, int64_t *stripOff_out,
+                      int64_t *memOff_out) {
+    QtfResident &Q = c->qt;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    free_list(c, Q.allocs);
+    Q = QtfResident();
+    const size_t nD1 = (size_t)nDesign + 1;
+    QGenArgs A;
+    memset(&A, 0, sizeof(A));
+    A.nDesign = nDesign; A.nMember = nMember; A.memberOff = dMemberOff; A.stationOff = dStationOff;
+    A.gm = dgm; A.gs = dgs; A.pose = dpose;
+    A.mdesign = sc.alloc<int>((size_t)nMember); A.mpose = sc.alloc<double>((size_t)nMember * QG_MP_N);
+    A.mcnt = sc.alloc<int>((size_t)nMember * QG_CNT_N); A.mcand = sc.alloc<int>((size_t)nMember);
+    A.dtot = sc.alloc<int>((size_t)std::max(nDesign, 1) * QG_CNT_N); A.err = sc.alloc<int>(1);
+    if (pool_alloc(c, Q.allocs, QG_CNT_N * nD1, &Q.dOff)) return -2;
+    A.off = Q.dOff;
+    if (!A.dtot || !A.err || (nMember && (!A.mdesign || !A.mpose || !A.mcnt || !A.mcand))) FAIL(c, "%s: device allocation failed", who);
+    HIPCHK(c, hipMemsetAsync(A.err, 0, sizeof(int), c->stream));
+    HIPCHK(c, hipMemsetAsync(A.dtot, 0, (size_t)std::max(nDesign, 1) * QG_CNT_N * sizeof(int), c->stream));
+    HIPCHK(c, hipEventRecord(c->ev0, c->stream));
+    const int64_t nThread = std::max<int64_t>(nMember, nDesign);
+    if (nThread) hipLaunchKernelGGL(k_qtfgen_member, dim3((unsigned)((nThread + 127) / 128)), dim3(128), 0, c->stream, A);
+    if (nDesign) hipLaunchKernelGGL(k_qtfgen_design, dim3((unsigned)((nDesign + 255) / 256)), dim3(256), 0, c->stream, A);
+    hipLaunchKernelGGL(k_qtfgen_scan, dim3(1), dim3(QG_SCAN_T), 0, c->stream, nDesign, A.dtot, A.off);
+    HIPCHK(c, hipGetLastError());
+    Q.off.resize(QG_CNT_N * nD1);
+    int err = 0;
+    D2H(c, Q.off.data(), Q.dOff, QG_CNT_N * nD1 * sizeof(int64_t));
+    D2H(c, &err, A.err, sizeof(int));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    Q.nDesign = nDesign;
+    if (err) {
+        free_list(c, Q.allocs);
+        Q = QtfResident();
+        FAIL(c, "%s: member %d has fewer than two stations, dlsMax <= 0 or no length", who, err - 1);
+    }
+    if (pool_alloc(c, Q.allocs, (size_t)Q.total(0) * QS_N, &Q.strips) || pool_alloc(c, Q.allocs, (size_t)Q.total(1) * QM_N, &Q.members) ||
+        pool_alloc(c, Q.allocs, (size_t)Q.total(2) * QKR_N, &Q.kay)) {
+        free_list(c, Q.allocs);
+        Q = QtfResident();
+        return -2;
+    }
+    A.strips = Q.strips; A.members = Q.members; A.kay = Q.kay;
+    if (nMember) hipLaunchKernelGGL(k_qtfgen_write, dim3((unsigned)((nMember + 3) / 4)), dim3(256), 0, c->stream, A);
+    if (finish_timed(c)) return -2;
+    Q.valid = true;
+    if (stripOff_out) memcpy(stripOff_out, Q.off.data(), nD1 * sizeof(int64_t));
+    if (memOff_out) memcpy(memOff_out, Q.off.data() + nD1, nD1 * sizeof(int64_t));
+    return 0;
+}
+
+extern "C" int raftx_qtf_tables_build(raftx_ctx *c, int nDesign, const int64_t *memberOff, const double *members,
+                                      const int64_t *stationOff, const double *stations, const double *pose, int64_t *stripOff_out,
+                                      int64_t *memOff_out) {
+    if (!c) return -1;
+    if (nDesign < 0 || !memberOff || !stationOff) FAIL(c, "qtf_tables_build: bad arguments");
+    for (int d = 0; d < nDesign; d++)
+        if (memberOff[d + 1] < memberOff[d]) FAIL(c, "qtf_tables_build: member offsets not monotone at design %d", d);
+    const int64_t m0 = memberOff[0], nMember = memberOff[nDesign] - m0;
+    if (m0 < 0) FAIL(c, "qtf_tables_build: member offsets not monotone at design 0");
+    for (int64_t m = 0; m < nMember; m++)
+        if (stationOff[m0 + m + 1] < stationOff[m0 + m]) FAIL(c, "qtf_tables_build: station offsets not monotone at member %lld", (long long)(m0 + m));
+    const int64_t s0 = stationOff[m0], nSta = stationOff[m0 + nMember] - s0;
+    if (s0 < 0) FAIL(c, "qtf_tables_build: station offsets not monotone at member %lld", (long long)m0);
+    if ((nMember && !members) || (nSta && !stations)) FAIL(c, "qtf_tables_build: bad arguments");
+    if (nMember >= ((int64_t)1 << 31)) FAIL(c, "qtf_tables_build: %lld members in one batch", (long long)nMember);
+    if (!all_finite(members + (size_t)m0 * RAFTX_GM_N, (size_t)nMember * RAFTX_GM_N) ||
+        !all_finite(stations + (size_t)s0 * RAFTX_GS_N, (size_t)nSta * RAFTX_GS_N) || (pose && !all_finite(pose, (size_t)nDesign * 6)))
+        FAIL(c, "qtf_tables_build: a member, station or pose value is not finite");
+    HIPCHK(c, hipSetDevice(c->device));
+    std::vector<int64_t> mo((size_t)nDesign + 1), so((size_t)nMember + 1);
+    for (int d = 0; d <= nDesign; d++) mo[(size_t)d] = memberOff[d] - m0;
+    for (int64_t m = 0; m <= nMember; m++) so[(size_t)m] = stationOff[m0 + m] - s0;
+    Scratch sc(c);
+    int64_t *dmo = sc.alloc<int64_t>(mo.size()), *dso = sc.alloc<int64_t>(so.size());
+    double *dgm = sc.alloc<double>((size_t)nMember * RAFTX_GM_N), *dgs = sc.alloc<double>((size_t)nSta * RAFTX_GS_N),
+           *dps = pose ? sc.alloc<double>((size_t)nDesign * 6) : nullptr;
+    if (!dmo || !dso || (nMember && !dgm) || (nSta && !dgs) || (pose && nDesign && !dps)) FAIL(c, "qtf_tables_build: device allocation failed");
+    H2D(c, dmo, mo.data(), mo.size() * sizeof(int64_t));
+    H2D(c, dso, so.data(), so.size() * sizeof(int64_t));
+    if (nMember) H2D(c, dgm, members + (size_t)m0 * RAFTX_GM_N, (size_t)nMember * RAFTX_GM_N * sizeof(double));
+    if (nSta) H2D(c, dgs, stations + (size_t)s0 * RAFTX_GS_N, (size_t)nSta * RAFTX_GS_N * sizeof(double));
+    if (dps) H2D(c, dps, pose, (size_t)nDesign * 6 * sizeof(double));
+    return qtfgen_run(c, sc, "qtf_tables_build", nDesign, nMember, dmo, dso, dgm, dgs, dps, stripOff_out, memOff_out);
+}
+
+extern "C" int raftx_qtf_tables_build_variants(raftx_ctx *c, int nDesign, const double *params, const double *pose,
+                                               int64_t *stripOff_out, int64_t *memOff_out) {
+    if (!c) return -1;
+    const VariantProg &P = c->vprog;
+    if (!P.nM) FAIL(c, "qtf_tables_build_variants: no program (raftx_variant_program first)");
+    if (nDesign < 0 || (!params && nDesign && P.nP)) FAIL(c, "qtf_tables_build_variants: bad arguments");
+    if ((params && !all_finite(params, (size_t)nDesign * P.nP)) || (pose && !all_finite(pose, (size_t)nDesign * 6)))
+        FAIL(c, "qtf_tables_build_variants: a parameter or pose value is not finite");
+    HIPCHK(c, hipSetDevice(c->device));
+    const int64_t nMember = (int64_t)nDesign * P.nM, nSta = (int64_t)nDesign * P.nSt;
+    if (nMember >= ((int64_t)1 << 31)) FAIL(c, "qtf_tables_build_variants: %lld members in one batch", (long long)nMember);
+    std::vector<int64_t> mo((size_t)nDesign + 1), so((size_t)nMember + 1);      // the uniform offsets of the batch
+    for (int d = 0; d <= nDesign; d++) mo[(size_t)d] = (int64_t)d * P.nM;
+    for (int d = 0; d < nDesign; d++)
+        for (int m = 0; m < P.nM; m++) so[(size_t)d * P.nM + m] = (int64_t)d * P.nSt + P.hS[(size_t)m];
+    so[(size_t)nMember] = nSta;
+    Scratch sc(c);
+    int64_t *dmo = sc.alloc<int64_t>(mo.size()), *dso = sc.alloc<int64_t>(so.size());
+    double *dp = sc.alloc<double>((size_t)nDesign * std::max(P.nP, 1)), *dgm = sc.alloc<double>((size_t)nMember * RAFTX_GM_N),
+           *dgs = sc.alloc<double>((size_t)std::max<int64_t>(nSta, 1) * RAFTX_GS_N),
+           *dgc = sc.alloc<double>((size_t)nDesign * std::max(P.nCap, 1) * RAFTX_GC_N),
+           *dps = pose ? sc.alloc<double>((size_t)nDesign * 6) : nullptr;
+    if (!dmo || !dso || (nDesign && (!dp || !dgm || !dgs || !dgc || (pose && !dps)))) FAIL(c, "qtf_tables_build_variants: device allocation failed");
+    H2D(c, dmo, mo.data(), mo.size() * sizeof(int64_t));
+    H2D(c, dso, so.data(), so.size() * sizeof(int64_t));
+    if (nDesign && P.nP) H2D(c, dp, params, (size_t)nDesign * P.nP * sizeof(double));
+    if (dps && nDesign) H2D(c, dps, pose, (size_t)nDesign * 6 * sizeof(double));
+    if (nDesign) {
+        ExpandArgs E;
+        memset(&E, 0, sizeof(E));
+        E.params = dp;
+        expand_args(P, nDesign, dgm, dgs, dgc, E);
+        launch_expand(E, c->stream);
+    }
+    return qtfgen_run(c, sc, "qtf_tables_build_variants", nDesign, nMember, dmo, dso, dgm, dgs, nDesign ? dps : nullptr, stripOff_out,
+                      memOff_out);
+}
+
+extern "C" int raftx_qtf_tables_counts(raftx_ctx *c, int64_t *counts) {
+    if (!c) return -1;
+    if (!counts) FAIL(c, "qtf_tables_counts: bad arguments");
+    if (!c->qt.valid) FAIL(c, "qtf_tables_counts: no resident tables (raftx_qtf_tables_build first)");
+    counts[0] = c->qt.nDesign;
+    for (int j = 0; j < QG_CNT_N; j++) counts[1 + j] = c->qt.total(j);
+    return 0;
+}
+
+extern "C" int raftx_qtf_tables_fetch(raftx_ctx *c, double *strips, double *members, int64_t *kayOff, double *kayNodes) {
+    if (!c) return -1;
+    const QtfResident &Q = c->qt;
+    if (!Q.valid) FAIL(c, "qtf_tables_fetch: no resident tables (raftx_qtf_tables_build first)");
+    HIPCHK(c, hipSetDevice(c->device));
+    if (strips && Q.total(0)) D2H(c, strips, Q.strips, (size_t)Q.total(0) * QS_N * sizeof(double));
+    if (members && Q.total(1)) D2H(c, members, Q.members, (size_t)Q.total(1) * QM_N * sizeof(double));
+    if (kayNodes && Q.total(2)) D2H(c, kayNodes, Q.kay, (size_t)Q.total(2) * QKR_N * sizeof(double));
+    if (kayOff) memcpy(kayOff, Q.off.data() + 2 * ((size_t)Q.nDesign + 1), ((size_t)Q.nDesign + 1) * sizeof(int64_t));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+// virtual offsets of the sets s = d * nCase + c over a per-design offset array: set s starts at nCase * off[d] + c * n_d
+static std::vector<int64_t> set_offsets(const int64_t *off, int nDesign, int nCase) {
+    std::vector<int64_t> v((size_t)nDesign * nCase + 1);
+    for (int d = 0; d < nDesign; d++)
+        for (int ic = 0; ic < nCase; ic++) v[(size_t)d * nCase + ic] = off[d] * nCase + ic * (off[d + 1] - off[d]);
+    v[(size_t)nDesign * nCase] = off[nDesign] * nCase;
+    return v;
+}
+
+extern "C" int raftx_qtf_tables_kay_items(raftx_ctx *c, int nCase, const double *beta, int64_t *itemOff, double *items) {
+    if (!c) return -1;
+    const QtfResident &Q = c->qt;
+    if (!Q.valid) FAIL(c, "qtf_tables_kay_items: no resident tables (raftx_qtf_tables_build first)");
+    if (nCase < 1 || !beta) FAIL(c, "qtf_tables_kay_items: bad arguments");
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t nSet = (size_t)Q.nDesign * nCase, nItem = (size_t)Q.total(3) * nCase;
+    if (itemOff) {
+        const std::vector<int64_t> v = set_offsets(Q.off.data() + 3 * ((size_t)Q.nDesign + 1), Q.nDesign, nCase);
+        memcpy(itemOff, v.data(), v.size() * sizeof(int64_t));
+    }
+    if (!items || !nItem) return 0;
+    Scratch sc(c);
+    double *dB = sc.alloc<double>(nCase), *dI = sc.alloc<double>(nItem * QK_N);
+    if (!dB || !dI) FAIL(c, "qtf_tables_kay_items: device allocation failed");
+    H2D(c, dB, beta, nCase * sizeof(double));
+    HIPCHK(c, hipEventRecord(c->ev0, c->stream));
+    hipLaunchKernelGGL(k_qtfgen_kay_items, dim3((unsigned)nSet), dim3(64), 0, c->stream, nCase, Q.nDesign, dB, Q.dOff, Q.kay, dI);
+    if (finish_timed(c)) return -2;
+    D2H(c, items, dI, nItem * QK_N * sizeof(double));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+extern "C" int raftx_qtf_slender_resident(raftx_ctx *c, int nCase, int nw2, const double *w2, const double *k2, double depth,
+                                          double rho, double g, const raftx_c128 *Xi, const double *beta, const double *Mstruc,
+                                          int Nm, raftx_c128 *qtf) {
+    if (!c) return -1;
+    const QtfResident &Q = c->qt;
+    if (!Q.valid) FAIL(c, "qtf_slender_resident: no resident tables (raftx_qtf_tables_build first)");
+    if (nCase < 1 || nw2 < 1 || !w2 || !k2 || !beta || !Mstruc) FAIL(c, "qtf_slender_resident: bad arguments");
+    if (Nm < 0 || Nm + 2 > KAY_MAXN) FAIL(c, "qtf_slender_resident: Nm=%d outside 0..%d", Nm, KAY_MAXN - 2);
+    const int nDesign = Q.nDesign;
+    const size_t nSet = (size_t)nDesign * nCase;
+    if (!Xi && (!c->rXi || !c->have_cases || c->r_npair != nSet || c->T.nCase != nCase))
+        FAIL(c, "qtf_slender_resident: Xi == NULL asks for the RAOs of the resident responses, but %s",
+             !c->rXi ? "nothing is resident" : "the resident (design, case) pairs are not these designs x sea states");
+    const size_t nStrip = (size_t)Q.total(0) * nCase, nMem = (size_t)Q.total(1) * nCase;
+    const size_t nItem = Nm > 0 ? (size_t)Q.total(3) * nCase : 0;
+    if (nStrip + nMem + nSet >= ((size_t)1 << 31)) FAIL(c, "qtf_slender_resident: %zu strips x sea states in one batch: cut it", nStrip);
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t nD1 = (size_t)nDesign + 1, nq = nSet * nw2 * nw2 * 6;
+    const std::vector<int64_t> soff = set_offsets(Q.off.data(), nDesign, nCase), moff = set_offsets(Q.off.data() + nD1, nDesign, nCase),
+                               ioff = set_offsets(Q.off.data() + 3 * nD1, nDesign, nCase);
+    std::vector<double> hB(nSet), hMs(nSet * 36);
+    for (size_t s = 0; s < nSet; s++) {
+        hB[s] = beta[s % nCase];
+        memcpy(&hMs[s * 36], Mstruc + (s / nCase) * 36, 36 * sizeof(double));
+    }
+    // bytes of device scratch this batch asks for (the tables of k_qtf_tables dominate), for the message of a failure
+    const size_t bytes = 16 * ((size_t)nw2 * (2 * nStrip * QT_N + nMem * QTM_N + nSet * (QTS_N + 6)) + nItem * KAY_ROWS * (size_t)nw2) +
+                         8 * (nStrip * (QD_N + 1) + nMem + nSet * 39 + nItem * QK_N) + 16 * nq * (nItem ? 2 : 1);
+    Scratch sc(c);
+    QtfArgs A;
+    A.nSet = (int)nSet; A.nw = nw2; A.depth = depth; A.rho = rho; A.g = g;
+    double *dw = sc.alloc<double>(nw2), *dk = sc.alloc<double>(nw2), *dB = sc.alloc<double>(nSet), *dMs = sc.alloc<double>(nSet * 36),
+           *dBc = sc.alloc<double>(nCase);
+    int64_t *dso = sc.alloc<int64_t>(nSet + 1), *dmo = sc.alloc<int64_t>(nSet + 1), *dio = sc.alloc<int64_t>(nSet + 1);
+    int *dss = sc.alloc<int>(nStrip), *dsr = sc.alloc<int>(nStrip), *dms = sc.alloc<int>(nMem), *dmr = sc.alloc<int>(nMem);
+    cplx *dXi = sc.alloc<cplx>(nSet * 6 * nw2);
+    cplx *dT = sc.alloc<cplx>(nStrip * QT_N * nw2), *dTM = sc.alloc<cplx>(nMem * QTM_N * nw2), *dTS = sc.alloc<cplx>(nSet * QTS_N * nw2);
+    double *dD = sc.alloc<double>(nStrip * QD_N);
+    cplx *dTA = sc.alloc<cplx>(nStrip * QT_N * nw2);
+    double *dI = sc.alloc<double>(nItem * QK_N), *dq = sc.alloc<double>(nw2);
+    cplx *dH = sc.alloc<cplx>(nItem * KAY_ROWS * nw2);
+    bool ok = !nSet || (dw && dk && dB && dMs && dBc && dso && dmo && dio && dXi && dTS && dq && (!nStrip || (dss && dsr && dT && dD && dTA)) &&
+                        (!nMem || (dms && dmr && dTM)) && (!nItem || (dI && dH)));
+    if (ok && nSet && (c->rQtf_n < nq || !c->rQtf) && grow_device(c, &c->rQtf, &c->rQtf_n, nq)) ok = false;
+    if (ok && nItem && (c->rKay_n < nq || !c->rKay) && grow_device(c, &c->rKay, &c->rKay_n, nq)) ok = false;
+    if (!ok)
+        FAIL(c, "qtf_slender_resident: device allocation failed: %zu bytes of scratch asked for (%zu sets, %zu per set): cut the batch",
+             bytes, nSet, nSet ? bytes / nSet : (size_t)0);
+    c->rQtf_sets = (int)nSet;
+    c->rQtf_nw2 = nw2;
+    c->kay_ready = false;                                // the table below belongs to this call alone
+    if (!nSet) return 0;
+    H2D(c, dw, w2, nw2 * sizeof(double));
+    H2D(c, dk, k2, nw2 * sizeof(double));
+    H2D(c, dB, hB.data(), nSet * sizeof(double));
+    H2D(c, dBc, beta, nCase * sizeof(double));
+    H2D(c, dMs, hMs.data(), nSet * 36 * sizeof(double));
+    H2D(c, dso, soff.data(), (nSet + 1) * sizeof(int64_t));
+    H2D(c, dmo, moff.data(), (nSet + 1) * sizeof(int64_t));
+    H2D(c, dio, ioff.data(), (nSet + 1) * sizeof(int64_t));
+    if (Xi) H2D(c, dXi, Xi, nSet * 6 * nw2 * sizeof(cplx));
+    if (nItem) HIPCHK(c, hipMemsetAsync(c->rKay, 0, nq * sizeof(cplx), c->stream));       // lower triangle stays zero
+    A.w = dw; A.k = dk; A.soff = dso; A.strips = Q.strips; A.moff = dmo; A.members = Q.members; A.sset = dss; A.mset = dms;
+    A.srec = dsr; A.mrec = dmr;
+    A.Xi = dXi; A.beta = dB; A.Ms = dMs; A.kay = nItem ? c->rKay : nullptr; A.T = dT; A.TA = dTA; A.D = dD; A.TM = dTM; A.TS = dTS;
+    A.qtf = c->rQtf;
+    A.row_off = 0; A.row_stride = 1; A.nrow = nw2;
+    HIPCHK(c, hipEventRecord(c->ev0, c->stream));
+    hipLaunchKernelGGL(k_qtfgen_sets, dim3((unsigned)nSet), dim3(64), 0, c->stream, nCase, nDesign, Q.dOff, dss, dsr, dms, dmr);
+    if (nItem) {
+        hipLaunchKernelGGL(k_qtfgen_kay_items, dim3((unsigned)nSet), dim3(64), 0, c->stream, nCase, nDesign, dBc, Q.dOff, Q.kay, dI);
+        hipLaunchKernelGGL(k_kay_tables, dim3((unsigned)nItem), dim3(128), 0, c->stream, nw2, Nm + 2, (int)nSet, depth, dk, dio, dI, dB, dH, dq);
+        hipLaunchKernelGGL(k_kay_pairs, dim3((unsigned)(nSet * nw2)), dim3(nw2 > 64 ? 128 : 64), 0, c->stream, nw2, Nm, depth, rho, g, dw,
+                           dk, dio, dI, dH, dq, c->rKay);
+    }
+    if (!Xi)                                             // motion RAOs straight from the resident first-order responses
+        hipLaunchKernelGGL(k_rao_to_grid, dim3((unsigned)(nSet * 6)), dim3(128), 0, c->stream, c->T.nCase, c->T.nHead, c->T.nw, nw2,
+                           c->T.w, c->T.zeta, dw, c->rXi, dXi);
+    hipLaunchKernelGGL(k_qtf_tables, dim3((unsigned)(nStrip + nMem + nSet)), dim3(nw2 > 128 ? 256 : 128), 0, c->stream, A, (int)nStrip,
+                       (int)nMem);
+    {
+        const int blk = nw2 > 64 ? 128 : 64;
+        const size_t per_xcd = (nSet * A.nrow + 7) / 8;  // see k_qtf_pairs: a slab of the (set, row) list per XCD
+        hipLaunchKernelGGL(k_qtf_pairs, dim3((unsigned)(per_xcd * 8)), dim3(blk), 0, c->stream, A);
+    }
+    if (finish_timed(c)) return -2;
+    if (qtf) D2H(c, qtf, c->rQtf, nq * sizeof(cplx));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return 0;
 }
 
 // The eigen analysis of one block of a crossing (raftx_sweep_modal) on stream st, which is behind whatever wrote the

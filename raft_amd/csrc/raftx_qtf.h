@@ -104,6 +104,8 @@ struct QtfArgs {
     const double *__restrict__ members;    // [nMem,QM_N]
     const int *__restrict__ sset;          // [nStrip] set of each strip
     const int *__restrict__ mset;          // [nMem]   set of each member
+    const int *__restrict__ srec;          // [nStrip] record of each strip in `strips`, or null: its own index.  With an index the
+    const int *__restrict__ mrec;          // [nMem]   sets of one design share ONE table (raftx_qtf_slender_resident); same for members
     const cplx *__restrict__ Xi;           // [nSet,6,nw]
     const double *__restrict__ beta;       // [nSet]
     const double *__restrict__ Ms;         // [nSet,36]
@@ -158,7 +160,7 @@ __global__ void __launch_bounds__(256) k_qtf_tables(QtfArgs A, int nStrip, int n
     for (int i = threadIdx.x; i < nw; i += blockDim.x) {
         const double w = A.w[i], k = A.k[i], h = A.depth;
         if (b < nStrip) {
-            const double *rec = A.strips + (size_t)b * QS_N;
+            const double *rec = A.strips + (size_t)(A.srec ? A.srec[b] : b) * QS_N;
             const int set = A.sset[b];
             const double beta = A.beta[set];
             const double r[3] = {rec[0], rec[1], rec[2]}, q[3] = {rec[3], rec[4], rec[5]};
@@ -257,7 +259,7 @@ __global__ void __launch_bounds__(256) k_qtf_tables(QtfArgs A, int nStrip, int n
             }
         } else if (b < nStrip + nMem) {
             const int m = b - nStrip;
-            const double *rec = A.members + (size_t)m * QM_N;
+            const double *rec = A.members + (size_t)(A.mrec ? A.mrec[m] : m) * QM_N;
             const int set = A.mset[m];
             cplx *T = A.TM + (size_t)m * QTM_N * nw;
             if (rec[0] != 0.0) {
@@ -453,7 +455,7 @@ __global__ void __launch_bounds__(128) k_qtf_pairs(QtfArgs A) {
         }
         // waterline term (:1635-1668)
         for (int64_t m = A.moff[set]; m < A.moff[set + 1]; m++) {
-            const double *rec = A.members + (size_t)m * QM_N;
+            const double *rec = A.members + (size_t)(A.mrec ? A.mrec[m] : m) * QM_N;
             if (rec[0] == 0.0) continue;
             const double r[3] = {rec[1], rec[2], rec[3]};
             const double a_wl = rec[4], Ca1 = rec[5], Ca2 = rec[6];

@@ -248,6 +248,11 @@ class Sweep:
         if kt is None and ctx.rlib.is_device and any(len(t.kay_geom) for t in tabs):
             ctx.qtf_kay(tabs, beta, w2, k2, self.depth, rho_water, self.g)        # Kim & Yue tables built on the device
         ctx.qtf_slender(tabs, Xi2, beta, w2, k2, self.depth, rho_water, self.g, Ms, kt, fetch=False)
+        return self._second_stage(ctx, r1, XiLast, w2, S0)
+
+    def _second_stage(self, ctx, r1, XiLast, w2, S0):
+        """Second-order force from the QTFs resident on ``ctx`` and the restarted fixed point (the last two launches)."""
+        nD, nC, nw = self.n_design, self.n_case, self.nw
         dw = float(self.w[1] - self.w[0])
         _, f2 = ctx.qtf_force(w2, self.w, dw, np.array([S0[c] for _ in range(nD) for c in range(nC)]), qtf=None,
                               n_set=nD * nC)
@@ -273,7 +278,8 @@ class GeometrySweep(Sweep):
     strip tables, MacCamy-Fuchs tables, Morison added mass, hydrostatics and member inertia on the device
     (raftx_build_designs) instead of uploading packed strips.  M_extra / C_extra [nD,6,6] carry what is not geometry
     (rotor-nacelle assembly, point inertias, mooring stiffness); ``add_mask`` selects what the device adds to them.
-    Everything else -- sharding by design, solve, statistics, farm and second-order paths -- is inherited."""
+    Everything else -- sharding by design, solve, statistics and the farm path -- is inherited; the second-order path can
+    generate its QTF tables on the device from the same descriptors (``run_second_order`` with qtf_tables=None)."""
 
     def __init__(self, tables, M_extra, B0, C_extra, w, k, depth, zeta, beta, nIter, XiStart, tol=0.01, pose=None,
                  add_mask=7, MBw=None, rho=1025.0, g=9.81):
@@ -403,6 +409,37 @@ class GeometrySweep(Sweep):
         r = ctx.sweep_wait(handle)
         self.off = r["strip_off"]
         return r
+
+    def _build_qtf_tables(self, ctx):
+        return ctx.qtf_tables_build(self.tables, pose=self.pose)
+
+    def run_second_order(self, ctx, qtf_tables=None, Mstruc=None, w2=None, k2=None, S0=None, rho_water=1025.0, kay=None, Nm=10):
+        """``Sweep.run_second_order`` for designs that exist as descriptors only.  With ``qtf_tables`` (one host
+        raft_amd.qtf.QtfTable per design) this IS the inherited method.  qtf_tables=None: the strip / member records and
+        the Kim & Yue geometry are generated on the device from the sweep's own descriptors (or parameters) and pose
+        (raftx_qtf_tables_build), one table per design serves all its sea states, and the QTFs come from
+        raftx_qtf_slender_resident (Kim & Yue correction with Nm + 1 terms, built on the device; Nm=0: none) -- the same
+        five launches otherwise.  Mstruc=None is then the device's M_struc (raftx_fetch_statics: the members' mass matrix)
+        plus this sweep's M_extra: a caller whose M_extra holds more than structural mass (added mass of a potential-flow
+        solution, for instance) passes Mstruc [nD,6,6] itself (it is the matrix of raft_fowt.py:2045)."""
+        if w2 is None or k2 is None or S0 is None:
+            raise ValueError("run_second_order needs w2, k2 and S0")
+        if qtf_tables is not None:
+            return super().run_second_order(ctx, qtf_tables, Mstruc, w2, k2, S0, rho_water=rho_water, kay=kay)
+        if kay is not None:
+            raise ValueError("kay (host Kim & Yue tables) belongs to host qtf_tables; the device path builds its own (Nm)")
+        if self.n_head != 1:
+            raise ValueError("run_second_order handles single-heading sea states")
+        self.upload(ctx)
+        self._build_qtf_tables(ctx)
+        if Mstruc is None:
+            Mstruc = ctx.fetch_statics()["M_struc"] + self.M0
+        ctx.set_linearisation_point(None, keep_last=True)
+        ctx.solve_dynamics_device(self.nIter, self.tol, self.XiStart)
+        r1 = ctx.fetch_results(want_Xi=True)
+        XiLast = ctx.fetch_linearisation_point()
+        ctx.qtf_slender_resident(None, self.beta[:, 0], w2, k2, self.depth, rho_water, self.g, Mstruc, Nm=Nm, fetch=False)
+        return self._second_stage(ctx, r1, XiLast, w2, S0)
 
     def upload(self, ctx):
         t = self.tables
@@ -771,6 +808,10 @@ class VariantSweep(GeometrySweep):
         """One isolated crossing: prepare + launch + wait on ``slot``."""
         return self.wait_crossing(ctx, self.submit_crossing(ctx, slot, n_chunk=n_chunk, want_Xi=want_Xi, Xi_out=Xi_out, modal=modal,
                                                             dM=dM, dC=dC, want_props=want_props, current=current, channels=channels))
+
+    def _build_qtf_tables(self, ctx):
+        self._install(ctx)
+        return ctx.qtf_tables_build_variants(self.params, pose=self.pose)
 
     def upload(self, ctx):
         self.tables = self.expanded_tables(ctx)
