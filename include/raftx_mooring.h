@@ -1,0 +1,86 @@
+/* raftx_mooring.h -- quasi-static mooring lines of rigid 6-DOF designs at a given pose (libraftx_hip.so only).
+ *
+ * Replaces, per unit, what the reference does with a MoorPy system for moorMod == 0 and lines that are ONE catenary
+ * segment from a fixed anchor to a point on the vessel:
+ *     raft_fowt.py:799-808     ms.solveEquilibrium (no free points: every line is solved on its own),
+ *                              C_moor = ms.getCoupledStiffnessA, F_moor = ms.getForces
+ *     raft_fowt.py:2356-2373   the tension Jacobian J_moor and the mean tensions T_moor (ends A, then ends B)
+ * at the pose the caller gives.  The mean-pose solve (Model.solveStatics) is not part of it.
+ *
+ * Line record (RAFTX_ML_N doubles):
+ *     0-2   anchor, global coordinates
+ *     3-5   fairlead in the body frame, relative to the unit's reference point
+ *     6     unstretched length L            7   EA            8   w, submerged weight per length
+ *     9     seabed friction CB: must be 0 (refused otherwise; friction is not covered)
+ *     10-15 zero
+ * The fairlead is at x[0:3] + R(x[3:6]) r_f, R = Rz Ry Rx of (roll, pitch, yaw): the rotation of the member descriptors.
+ * The elastic catenary (no seabed contact, or partly resting on a frictionless seabed when the anchor lies on it,
+ * |a_z + depth| <= 1e-6 depth) is solved for the fairlead's (HF, VF) by a damped Newton iteration to stagnation in fp64,
+ * at most 60 steps.  C_moor = -dF_moor/dx6 is the exact derivative for a translation and an infinitesimal rotation
+ * vector about the reference point applied on top of R; it includes the arm turning under a fixed force and is not
+ * symmetric in general.  J = dT/dx6 in the same sense.
+ *
+ * Flags (int32 per design; a flagged design's outputs are NaN, and only its own):
+ */
+#ifndef RAFTX_MOORING_H
+#define RAFTX_MOORING_H
+
+#include "raftx.h"
+
+#define RAFTX_ML_N 16
+#define RAFTX_MOOR_BAD_LINE        1   /* non-finite field or pose; L, EA or w <= 0; anchor below the seabed; fairlead not above the anchor */
+#define RAFTX_MOOR_VERTICAL        2   /* horizontal span XF <= 1e-9 L */
+#define RAFTX_MOOR_SLACK           4   /* L >= XF + ZF: the fully slack profile is not covered */
+#define RAFTX_MOOR_NO_CONVERGENCE  8   /* the Newton cap was reached */
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+/* Stateless (raft_fowt.py:799-808 and :2356-2373 for every design at once).  lines [nDesign,nLine,RAFTX_ML_N],
+ * pose [nDesign,6] (m, rad) or NULL (zero), depth > 0.  Outputs, each of which may be NULL except flags:
+ * C_moor [nDesign,6,6], F_moor [nDesign,6], T [nDesign,2 nLine] (ends A of all lines, then ends B: the order of
+ * getTensions), J [nDesign,2 nLine,6], line_out [nDesign,nLine,8] = HF, VF, HA, VA, L_B, iterations, branch
+ * (1 = seabed contact), 0, flags [nDesign].  The sums over the lines run in line order without atomics: the bits of a
+ * design depend on its own lines and pose only.  Errors, before any launch: nLine < 1, nDesign < 0, NULL lines or flags,
+ * a depth that is not positive and finite, a line with CB != 0. */
+int raftx_mooring_lines(raftx_ctx *ctx, int nDesign, int nLine, const double *lines, const double *pose, double depth,
+                        double *C_moor, double *F_moor, double *T, double *J, double *line_out, int32_t *flags);
+
+/* The mooring edits of a parametric sweep (raft/parametersweep.py:64-68, 79-83: the fairleads follow the outer
+ * columns): base records lines [nLine,RAFTX_ML_N] and, for lines with lineEdit != 0, anchor and fairlead coordinates
+ * (fields 0-5) that are affine in the variant parameters, lineCoef [nLine,6,nParam+1] = constant, then one coefficient
+ * per parameter, evaluated left to right without fused multiply-adds exactly as endCoef of raftx_variant_program.
+ * nParam must equal the installed variant program's (an error without one).  nLine = 0 clears the program; installing a
+ * new variant program does not. */
+int raftx_mooring_program(raftx_ctx *ctx, int nLine, const double *lines, int nParam, const double *lineCoef,
+                          const int32_t *lineEdit);
+
+/* The line records lines_out [nDesign,nLine,RAFTX_ML_N] of the variants params [nDesign,nParam], written by the device and
+ * copied back: for checks. */
+int raftx_mooring_expand(raftx_ctx *ctx, int nDesign, const double *params, double *lines_out);
+
+/* On a PREPARED, not yet launched sweep slot (raftx_sweep_prepare / raftx_sweep_prepare_variants), as raftx_sweep_modal: the
+ * mooring system of every design of the crossing (raft_fowt.py:799-808, 2356-2373) at the crossing's pose and depth.
+ * lines [nDesign,nLine,RAFTX_ML_N], or NULL on a raftx_sweep_prepare_variants slot: the records of the installed mooring
+ * program fed the slot's params (nLine must be the program's).  The kernels run at once on the copy stream, before the
+ * crossing is launched.
+ * add_stiffness != 0: every block's device C0 receives += C_moor after its upload and before anything reads it (k_geom_addup,
+ * the add-up inside k_geom_design and the generating fused kernel all wait for it): the crossing is the one a caller would
+ * get by passing C0 + C_moor, bit for bit.  A flagged design's C_moor is NaN: its pairs' responses are not finite, nobody
+ * else's.
+ * T_std [nDesign,nCase,2 nLine] or NULL: the standard deviations of J Xi (raft_fowt.py:2367-2371), by a second launch of
+ * k_sweep_channels per block on rows the mooring kernel left in device memory; a raftx_sweep_channels request on the same
+ * slot is not disturbed.  C_moor [nDesign,6,6], F_moor [nDesign,6], T_mean [nDesign,2 nLine] may be NULL; flags [nDesign]
+ * is required.  Results land in a page-locked area and raftx_sweep_wait fills the caller's arrays (alive until then; the
+ * inputs are copied).  A second request on a slot replaces the first; raftx_sweep_cancel and a new prepare drop it.
+ * Errors, before any launch: an idle or launched slot; CB != 0; lines == NULL without a variant slot, without a mooring
+ * program, or with another nLine / parameter count. */
+int raftx_sweep_mooring(raftx_ctx *ctx, int slot, int nLine, const double *lines, int add_stiffness, double *C_moor,
+                        double *F_moor, double *T_mean, double *T_std, int32_t *flags);
+
+#ifdef __cplusplus
+}
+#endif
+
+#endif /* RAFTX_MOORING_H */

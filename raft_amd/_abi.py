@@ -48,6 +48,10 @@ CHANNEL_EXPORTS = ("raftx_sweep_channels",)
 # include/raftx_qtfgen.h: second-order QTF tables generated on the device, the device library only
 QTFGEN_EXPORTS = ("raftx_qtf_tables_build", "raftx_qtf_tables_build_variants", "raftx_qtf_tables_counts", "raftx_qtf_tables_fetch",
                   "raftx_qtf_tables_kay_items", "raftx_qtf_slender_resident")
+# include/raftx_mooring.h: quasi-static mooring lines, the device library only
+MOORING_EXPORTS = ("raftx_mooring_lines", "raftx_mooring_program", "raftx_mooring_expand", "raftx_sweep_mooring")
+ML_N = 16          # doubles per mooring line record (RAFTX_ML_N)
+MOOR_BAD_LINE, MOOR_VERTICAL, MOOR_SLACK, MOOR_NO_CONVERGENCE = 1, 2, 4, 8
 QKG_N = 8          # doubles per row of the Kim & Yue geometry stream (RAFTX_QKG_N)
 
 
@@ -151,6 +155,16 @@ class RaftxLib:
             L.raftx_modal_resident.restype = C.c_int
             L.raftx_sweep_modal.argtypes = [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp]
             L.raftx_sweep_modal.restype = C.c_int
+        self.has_mooring = all(hasattr(L, s) for s in MOORING_EXPORTS)
+        if self.has_mooring:
+            L.raftx_mooring_lines.argtypes = [_vp, C.c_int, C.c_int, _vp, _vp, C.c_double, _vp, _vp, _vp, _vp, _vp, _vp]
+            L.raftx_mooring_lines.restype = C.c_int
+            L.raftx_mooring_program.argtypes = [_vp, C.c_int, _vp, C.c_int, _vp, _vp]
+            L.raftx_mooring_program.restype = C.c_int
+            L.raftx_mooring_expand.argtypes = [_vp, C.c_int, _vp, _vp]
+            L.raftx_mooring_expand.restype = C.c_int
+            L.raftx_sweep_mooring.argtypes = [_vp, C.c_int, C.c_int, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp]
+            L.raftx_sweep_mooring.restype = C.c_int
         self.has_current = all(hasattr(L, s) for s in CURRENT_EXPORTS)
         if self.has_current:
             L.raftx_current_loads.argtypes = [_vp, C.c_int, _vp, _vp, _vp, C.c_double, C.c_double, _vp]
@@ -698,6 +712,90 @@ class Context:
         self._check(L.raftx_sweep_current(self._h, int(handle["slot"]), nCur, _ptr(speed), _ptr(heading), _ptr(Zref), float(shearExp),
                                           _ptr(D)), "raftx_sweep_current")
         out["D_hydro"] = D
+        return handle
+
+    # ------------------------------------------------------------- quasi-static mooring lines (include/raftx_mooring.h)
+    def _mooring_lib(self, what):
+        if not self.rlib.has_mooring:
+            raise RaftxError("%s: %s does not implement include/raftx_mooring.h (the device library does)" % (what, self.rlib.path))
+        return self.rlib.lib
+
+    def mooring_lines(self, lines, depth, pose=None, want=("C", "F", "T", "J", "line_out")):
+        """The mooring system of every design at its pose (raftx_mooring_lines; raft_fowt.py:799-808, 2356-2373):
+        ``lines`` [nD,nLine,16] records (raft_amd/mooring.py), ``pose`` [nD,6] or None (zero).  Returns a dict with
+        C [nD,6,6], F [nD,6], T [nD,2 nLine], J [nD,2 nLine,6], line_out [nD,nLine,8] -- those named in ``want`` -- and
+        flags [nD] (int32; a flagged design's outputs are NaN)."""
+        L = self._mooring_lib("mooring_lines")
+        lines = _f64(lines)
+        if lines.ndim != 3 or lines.shape[2] != ML_N:
+            raise ValueError("lines has shape %s, expected [nDesign,nLine,%d]" % (lines.shape, ML_N))
+        nD, nL = lines.shape[:2]
+        pose = None if pose is None else _f64(pose, (nD, 6), "pose")
+        shapes = dict(C=(nD, 6, 6), F=(nD, 6), T=(nD, 2 * nL), J=(nD, 2 * nL, 6), line_out=(nD, nL, 8))
+        out = {k: (np.empty(shapes[k]) if k in want else None) for k in shapes}
+        out["flags"] = np.zeros(nD, dtype=np.int32)
+        self._check(L.raftx_mooring_lines(self._h, nD, nL, _ptr(lines), _ptr(pose), float(depth), _ptr(out["C"]), _ptr(out["F"]),
+                                          _ptr(out["T"]), _ptr(out["J"]), _ptr(out["line_out"]), _ptr(out["flags"])),
+                    "raftx_mooring_lines")
+        return {k: v for k, v in out.items() if v is not None}
+
+    def mooring_program(self, prog):
+        """Installs a raft_amd.mooring.MooringProgram (raftx_mooring_program); None clears it."""
+        L = self._mooring_lib("mooring_program")
+        if prog is None:
+            self._check(L.raftx_mooring_program(self._h, 0, None, 0, None, None), "raftx_mooring_program")
+            self._mprog = self._mprog_owner = None
+            return
+        n, nP = prog.n, prog.n_param
+        lines, coef = _f64(prog.lines, (n, ML_N), "lines"), _f64(prog.coef, (n, 6, nP + 1), "coef")
+        edit = np.ascontiguousarray(prog.edit, dtype=np.int32)
+        self._check(L.raftx_mooring_program(self._h, n, _ptr(lines), nP, _ptr(coef), _ptr(edit)), "raftx_mooring_program")
+        self._mprog = (n, nP)
+        self._mprog_owner = prog
+
+    def mooring_expand(self, params):
+        """Line records [nD,nLine,16] of the variants ``params`` [nD,nParam] of the installed mooring program, written by
+        the library (raftx_mooring_expand): for checks."""
+        L = self._mooring_lib("mooring_expand")
+        if getattr(self, "_mprog", None) is None:
+            raise RaftxError("mooring_expand: no program installed (mooring_program first)")
+        n, nP = self._mprog
+        params = _f64(params)
+        nD = params.shape[0]
+        params = _f64(params, (nD, nP), "params")
+        out = np.empty((nD, n, ML_N))
+        self._check(L.raftx_mooring_expand(self._h, nD, _ptr(params), _ptr(out)), "raftx_mooring_expand")
+        return out
+
+    def sweep_mooring(self, handle, lines=None, add_stiffness=True, tensions=True):
+        """Ask for the mooring system of a PREPARED, not yet launched crossing (raftx_sweep_mooring): ``lines``
+        [nD,nLine,16], or None on a crossing of variants for the installed mooring program fed the crossing's params.
+        add_stiffness: C_moor is added to every design's C0 on the device ahead of the add-up.  ``sweep_wait`` then also
+        returns C_moor [nD,6,6], F_moor [nD,6], T_mean [nD,2 nLine], moor_flags [nD] and, with ``tensions``, T_std
+        [nD,nCase,2 nLine].  Returns the handle."""
+        L = self._mooring_lib("sweep_mooring")
+        out = handle["out"]
+        n, nC = out["niter"].shape
+        if lines is None:
+            if getattr(self, "_mprog", None) is None:
+                raise RaftxError("sweep_mooring: no program installed (mooring_program first) and no lines given")
+            nL = self._mprog[0]
+        else:
+            lines = _f64(lines)
+            if lines.ndim != 3 or lines.shape[0] != n or lines.shape[2] != ML_N:
+                raise ValueError("lines has shape %s, expected [%d,nLine,%d]" % (lines.shape, n, ML_N))
+            nL = lines.shape[1]
+        res = dict(C_moor=np.zeros((n, 6, 6)), F_moor=np.zeros((n, 6)), T_mean=np.zeros((n, 2 * nL)),
+                   moor_flags=np.zeros(n, dtype=np.int32))
+        if tensions:
+            res["T_std"] = np.zeros((n, nC, 2 * nL))
+        self._check(L.raftx_sweep_mooring(self._h, int(handle["slot"]), nL, _ptr(lines), int(bool(add_stiffness)), _ptr(res["C_moor"]),
+                                          _ptr(res["F_moor"]), _ptr(res["T_mean"]), _ptr(res.get("T_std")), _ptr(res["moor_flags"])),
+                    "raftx_sweep_mooring")
+        handle["mooring_inputs"] = lines                  # alive until the crossing has been waited for
+        for k in ("T_std",):
+            out.pop(k, None)
+        out.update(res)
         return handle
 
     # ------------------------------------------------------------- output channels of a crossing (include/raftx_channels.h)

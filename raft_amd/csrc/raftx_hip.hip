@@ -45,6 +45,7 @@
 #include "../../include/raftx_current.h"
 #include "../../include/raftx_channels.h"
 #include "../../include/raftx_qtfgen.h"
+#include "../../include/raftx_mooring.h"
 
 // roctx ranges around the phases of the host side: named spans for `rocprofv3 --marker-trace`.
 // librocprofiler-sdk-roctx is bound at run time on first use; without it (or outside a profiler) the ranges cost a branch.
@@ -88,6 +89,7 @@ struct RangeScope {
 #include "raftx_current.h"
 #include "raftx_channels.h"
 #include "raftx_qtfgen.h"
+#include "raftx_mooring.h"
 
 // Coupled array solve (raft_model.py:1164-1236): Xi = Z_sys^-1 F for every (system, bin).  One wavefront per
 // (system, bin), NBIN (1, 2 or 4: what fits LDS) consecutive bins per workgroup so that the loads of one matrix entry
@@ -874,6 +876,8 @@ struct raftx_ctx {
     Pinned<double> pinModal;             // ... of a block's eigen analysis (raftx_sweep_modal)
     Pinned<double> pinCur;               // ... of a block's current loads (raftx_sweep_current)
     Pinned<double> pinChan;              // ... of a block's output channels (raftx_sweep_channels) [pairs,nChan]
+    Pinned<double> pinMoorT;             // ... of a block's tension statistics (raftx_sweep_mooring) [pairs,2 nLine]
+    hipEvent_t evMoor = nullptr;         // C_moor has been added to the block's C0 (raftx_sweep_mooring, sCopy)
     hipStream_t sCopy, sPrep, sD2H, sGen; // internal streams of raftx_sweep_stats (created on first use)
     hipStream_t sSlab[2] = {nullptr, nullptr}; // with sGen: the streams the slabs of a crossing with responses out go to (SlabPlan)
     hipStream_t sD2Hhigh = nullptr;       // bulk download of the responses: a stream of the highest priority class, created when first needed
@@ -938,6 +942,11 @@ struct raftx_ctx {
     std::vector<raftx_ctx *> workers[RAFTX_NSLOT]; // block contexts of the sweep crossings (device buffers, pool, events), per slot, kept for reuse
     struct SweepSlot *slots;             // [RAFTX_NSLOT] crossings in flight (raftx_sweep_prepare / _launch / _wait)
     VariantProg vprog;                   // raftx_variant_program
+    struct {                             // raftx_mooring_program: base records and the affine edits of their end points
+        int nLine = 0, nP = 0;
+        double *base = nullptr, *coef = nullptr;
+        int *edit = nullptr;
+    } mprog;
     QtfResident qt;                      // raftx_qtf_tables_build
 };
 // Offset arrays of a whole batch, resident on the device (uploaded once by the sweep crossing, shared by its blocks).
@@ -1011,6 +1020,15 @@ struct SweepSlot {
         double *out = nullptr;           // the caller's output [nDesign,nCase,nChan], filled by raftx_sweep_wait
         hipEvent_t evUp = nullptr;       // the copies have landed (sCopy)
     } channels;
+    struct {                             // raftx_sweep_mooring: the mooring system of the crossing's designs
+        bool on = false, add = false;
+        int nLine = 0;
+        const double *C = nullptr, *Lr = nullptr;   // device (in S.allocs): C_moor [nDesign,36]; J as channel rows [nDesign,2 nLine,3,6]
+        Pinned<double> pin;              // landing area: C | F | T | flags of the whole crossing
+        double *C_out = nullptr, *F_out = nullptr, *T_out = nullptr, *Tstd_out = nullptr;   // the caller's, filled by raftx_sweep_wait
+        int32_t *flags_out = nullptr;
+        hipEvent_t evUp = nullptr;       // the kernels have run and the landing area is filled (sCopy)
+    } mooring;
 };
 
 #define MAX_NW 2048
@@ -1116,6 +1134,14 @@ static void variant_release(raftx_ctx *c) {
     free_list(c, c->vprog.allocs);
     c->vprog = VariantProg();
 }
+static void mooring_program_release(raftx_ctx *c) {
+    if (c->mprog.base) (void)hipFree(c->mprog.base);
+    if (c->mprog.coef) (void)hipFree(c->mprog.coef);
+    if (c->mprog.edit) (void)hipFree(c->mprog.edit);
+    c->mprog.base = c->mprog.coef = nullptr;
+    c->mprog.edit = nullptr;
+    c->mprog.nLine = c->mprog.nP = 0;
+}
 extern "C" void raftx_ctx_destroy(raftx_ctx *c) {
     if (!c) return;
 #ifdef GEOM_PHASE_TIMING
@@ -1160,6 +1186,7 @@ extern "C" void raftx_ctx_destroy(raftx_ctx *c) {
     if (c->pairList) (void)hipFree(c->pairList);
     free_list(c, c->dense.allocs);
     variant_release(c);
+    mooring_program_release(c);
     if (c->identList) (void)hipFree(c->identList);
     for (hipEvent_t e : c->evSlab) (void)hipEventDestroy(e);
     if (c->evFork) (void)hipEventDestroy(c->evFork);
@@ -1171,6 +1198,8 @@ extern "C" void raftx_ctx_destroy(raftx_ctx *c) {
         if (c->slots[sl].modal.evUp) (void)hipEventDestroy(c->slots[sl].modal.evUp);
         if (c->slots[sl].current.evUp) (void)hipEventDestroy(c->slots[sl].current.evUp);
         if (c->slots[sl].channels.evUp) (void)hipEventDestroy(c->slots[sl].channels.evUp);
+        if (c->slots[sl].mooring.evUp) (void)hipEventDestroy(c->slots[sl].mooring.evUp);
+        c->slots[sl].mooring.pin.release();
     }
     delete[] c->slots;
     c->pool.trim();
@@ -1179,6 +1208,8 @@ extern "C" void raftx_ctx_destroy(raftx_ctx *c) {
     c->pinModal.release();
     c->pinCur.release();
     c->pinChan.release();
+    c->pinMoorT.release();
+    if (c->evMoor) (void)hipEventDestroy(c->evMoor);
     for (hipEvent_t e : {c->evZ, c->ev0, c->ev1, c->evUp, c->evTot, c->evG0, c->evG1, c->evG2, c->evG3, c->evS0, c->evS1, c->evDone,
                          c->evMem, c->evRed})
         (void)hipEventDestroy(e);
@@ -3379,7 +3410,7 @@ static void cut_blocks(raftx_ctx *c, int slot, int nDesign, const SeaStates &sea
     S.sd = run.sd; S.niter = run.niter; S.flags = run.flags; S.Xi = run.Xi; S.stripOffsets = run.stripOffsets;
     S.tl[0] = S.since();
     free_list(c, S.allocs);
-    S.modal.on = S.current.on = S.channels.on = false;
+    S.modal.on = S.current.on = S.channels.on = S.mooring.on = false;
 }
 // The batch's offset arrays: one upload on sCopy, shared by the blocks; its wave numbers are those of the sea-state set.
 static int upload_offsets(raftx_ctx *c, SweepSlot &S, const BuildSource &src, int nDesign) {
@@ -3990,6 +4021,42 @@ static hipError_t channels_block(raftx_ctx *sub, SweepSlot &S, int lo, int n, hi
     return hipGetLastError();
 }
 
+// The tension statistics of one block of a crossing (raftx_sweep_mooring with T_std): k_sweep_channels once more, on the rows
+// k_moor_design left in device memory (J in the first plane), into a landing area of its own -- a raftx_sweep_channels
+// request on the same slot keeps its rows and its area.
+static hipError_t mooring_std_block(raftx_ctx *sub, SweepSlot &S, int lo, int n, hipStream_t st) {
+    const size_t npair = (size_t)n * S.nCase;
+    const int nChan = 2 * S.mooring.nLine;
+    hipError_t e = sub->pinMoorT.reserve(npair * nChan);
+    if (e != hipSuccess || npair == 0) return e;
+    if (!sub->rXi || sub->r_nx < npair * S.nHead * 6 * S.nw || !sub->T.w) return hipErrorInvalidValue;
+    e = hipStreamWaitEvent(st, S.mooring.evUp, 0);
+    if (e != hipSuccess) return e;
+    ChannelArgs A;
+    A.nCase = S.nCase; A.nHead = S.nHead; A.nw = S.nw; A.nChan = nChan;
+    A.strideL = (size_t)nChan * 18;
+    A.strideG = 0;
+    const dim3 grid((unsigned)npair), wg(S.nw > 128 ? 256 : (S.nw > 64 ? 128 : 64));
+    hipLaunchKernelGGL(k_sweep_channels<false>, grid, wg, 0, st, A, (const double *)sub->T.w, (const cplx *)sub->rXi,
+                       S.mooring.Lr + (size_t)lo * A.strideL, (const cplx *)nullptr, sub->pinMoorT.p);
+    return hipGetLastError();
+}
+// C_moor into the C0 of block b (raftx_sweep_mooring with add_stiffness): on the copy stream, which is in order -- behind the
+// block's own upload of C0 and behind the mooring kernels of the request -- and ahead of everything that reads C0: the
+// generation stream and the ctx stream (k_geom_addup, the add-up inside k_geom_design, the generating fused kernel) wait for it.
+static int mooring_add_block(raftx_ctx *c, raftx_ctx *sub, SweepSlot &S, int lo, int n, bool pipelined) {
+    if (!n) return 0;
+    if (!sub->job.active || !sub->job.C0d) FAIL(sub, "sweep_mooring: the block has no uploaded C0 (internal error)");
+    if (!sub->evMoor) HIPCHK(sub, hipEventCreateWithFlags(&sub->evMoor, hipEventDisableTiming));
+    hipLaunchKernelGGL(k_moor_add, dim3(moor_grid((long long)n * 36)), dim3(MOOR_THREADS), 0, c->sCopy, sub->job.C0d,
+                       S.mooring.C + (size_t)lo * 36, (long long)n * 36);
+    HIPCHK(sub, hipGetLastError());
+    HIPCHK(sub, hipEventRecord(sub->evMoor, c->sCopy));
+    HIPCHK(sub, hipStreamWaitEvent(c->stream, sub->evMoor, 0));
+    if (pipelined && c->sGen) HIPCHK(sub, hipStreamWaitEvent(c->sGen, sub->evMoor, 0));
+    return 0;
+}
+
 // The stream the responses of a crossing are downloaded on: one of the HIGHEST priority class, created when first needed (so
 // late, it does not move the other streams' hardware queues).  A priority class has hardware queues of its own and the highest
 // is served at once: the copy never sits in a queue with the next batch's kernels (ordinary stream) nor starts a step late
@@ -4021,6 +4088,7 @@ static int enqueue_stats(raftx_ctx *c, SweepSlot &S, size_t b, hipStream_t sDown
     if (e == hipSuccess && S.modal.on) e = modal_block(sub, S, lo, S.bnd[b + 1] - lo, c->stream);
     if (e == hipSuccess && S.current.on) e = current_block(sub, S, lo, S.bnd[b + 1] - lo, c->csets[S.cset].T.depth, c->stream);
     if (e == hipSuccess && S.channels.on) e = channels_block(sub, S, lo, S.bnd[b + 1] - lo, c->stream);
+    if (e == hipSuccess && S.mooring.on && S.mooring.Tstd_out) e = mooring_std_block(sub, S, lo, S.bnd[b + 1] - lo, c->stream);
     if (e == hipSuccess) e = hipEventRecord(sub->evDone, c->stream);
     if (e == hipSuccess && S.Xi && !S.slab) {
         e = hipStreamWaitEvent(sDown, sub->evDone, 0);
@@ -4112,7 +4180,9 @@ static void hand_sea_states(const DevTables &P, raftx_ctx *sub) {
 // lost -- a second compute stream among them: profiles/MEASUREMENT_HISTORY.md, "Closed scheduling experiments of the crossing").
 static int launch_block(raftx_ctx *c, SweepSlot &S, int slot, size_t b, LaunchMode &M) {
     raftx_ctx *sub = S.blk[b];
-    int rc = phase1_ahead(c, S, b);
+    // (C_moor into this block's C0 first: on the copy stream ahead of the next block's uploads)
+    int rc = (S.mooring.on && S.mooring.add) ? mooring_add_block(c, sub, S, S.bnd[b], S.bnd[b + 1] - S.bnd[b], M.pipelined) : 0;
+    if (!rc) rc = phase1_ahead(c, S, b);
     if (!rc && b == 0 && M.pipelined) rc = gate_generation(c, slot);
     S.tlb.push_back(S.since());
     // (a crossing: no ABI copy of the strip records; with RAFTX_FUSED_GEN=1 the tables are left to the fused kernel itself,
@@ -4211,7 +4281,7 @@ extern "C" int raftx_sweep_cancel(raftx_ctx *c, int slot) {
             build_abandon(sub);
         }
     S.prepared = false;
-    S.modal.on = S.current.on = S.channels.on = false;
+    S.modal.on = S.current.on = S.channels.on = S.mooring.on = false;
     slot_release_cases(c, S);
     HIPCHK(c, e);
     return 0;
@@ -4276,6 +4346,22 @@ static void collect_block(SweepSlot &S, size_t b, double *t) {
         memcpy(S.current.D + (size_t)lo * S.current.nCur * 6, sub->pinCur.p, (size_t)n * S.current.nCur * 6 * sizeof(double));
     if (S.channels.on && npair)
         memcpy(S.channels.out + p0 * S.channels.nChan, sub->pinChan.p, npair * S.channels.nChan * sizeof(double));
+    if (S.mooring.on && S.mooring.Tstd_out && npair)
+        memcpy(S.mooring.Tstd_out + p0 * 2 * S.mooring.nLine, sub->pinMoorT.p, npair * 2 * S.mooring.nLine * sizeof(double));
+}
+// the crossing's mooring results out of their landing area (the copies were waited for with the crossing: sCopy is ahead of
+// every block through evUp, or waited for here)
+static hipError_t collect_mooring(SweepSlot &S) {
+    if (!S.mooring.on) return hipSuccess;
+    const hipError_t e = hipEventSynchronize(S.mooring.evUp);
+    if (e != hipSuccess) return e;
+    const size_t n = S.bnd.empty() ? 0 : (size_t)S.bnd.back(), nT = 2 * (size_t)S.mooring.nLine;
+    const double *p = S.mooring.pin.p;
+    if (S.mooring.C_out) memcpy(S.mooring.C_out, p, n * 36 * sizeof(double));
+    if (S.mooring.F_out) memcpy(S.mooring.F_out, p + n * 36, n * 6 * sizeof(double));
+    if (S.mooring.T_out) memcpy(S.mooring.T_out, p + n * 42, n * nT * sizeof(double));
+    memcpy(S.mooring.flags_out, p + n * (42 + nT), n * sizeof(int32_t));
+    return hipSuccess;
 }
 // RAFTX_SWEEP_DEBUG: the host's timeline of the crossing on stderr
 static void debug_timeline(const SweepSlot &S, int slot, double wall) {
@@ -4299,13 +4385,16 @@ extern "C" int raftx_sweep_wait(raftx_ctx *c, int slot, double *timing_ms) {
     HIPCHK(c, hipSetDevice(c->device));
     S.busy = false;
     const hipError_t es = sweep_drain(c, S);
-    if (es != hipSuccess) S.modal.on = S.current.on = S.channels.on = false;
+    if (es != hipSuccess) S.modal.on = S.current.on = S.channels.on = S.mooring.on = false;
     HIPCHK(c, es);
     solve_span(c, S);
     double t[4] = {0, 0, 0, 0};                           // wall | generation, solve, statistics kernels
     if (S.stripOffsets) S.stripOffsets[0] = 0;
     for (size_t b = 0; b < S.blk.size(); b++) collect_block(S, b, t);
-    S.modal.on = S.current.on = S.channels.on = false;
+    const hipError_t em = collect_mooring(S);
+    if (em != hipSuccess) S.mooring.on = false;
+    HIPCHK(c, em);
+    S.modal.on = S.current.on = S.channels.on = S.mooring.on = false;
     t[0] = S.since();
     debug_timeline(S, slot, t[0]);
     if (timing_ms) memcpy(timing_ms, t, sizeof(t));
@@ -4494,6 +4583,185 @@ extern "C" int raftx_sweep_current(raftx_ctx *c, int slot, int nCur, const doubl
     S.current.Zref = Zref ? dpar + (size_t)3 * nCur : nullptr;
     S.current.D = D;
     S.current.on = true;
+    return 0;
+}
+
+// ---- quasi-static mooring lines (include/raftx_mooring.h, raftx_mooring.h)
+extern "C" int raftx_mooring_lines(raftx_ctx *c, int nDesign, int nLine, const double *lines, const double *pose, double depth,
+                                   double *C_moor, double *F_moor, double *T, double *J, double *line_out, int32_t *flags) {
+    if (!c) return -1;
+    if (nLine < 1) FAIL(c, "mooring_lines: nLine must be positive (got %d)", nLine);
+    if (nDesign < 0) FAIL(c, "mooring_lines: nDesign must not be negative (got %d)", nDesign);
+    if (!lines || !flags) FAIL(c, "mooring_lines: bad arguments (lines and flags are required)");
+    if (!std::isfinite(depth) || !(depth > 0.0)) FAIL(c, "mooring_lines: the depth must be positive and finite (got %g)", depth);
+    const size_t nl = (size_t)nDesign * nLine;
+    for (size_t i = 0; i < nl; i++) {
+        const double cb = lines[i * RAFTX_ML_N + 9];
+        if (std::isfinite(cb) && cb != 0.0)
+            FAIL(c, "mooring_lines: line %zu of design %zu has seabed friction CB = %g: friction is not covered (CB must be 0)",
+                 i % nLine, i / nLine, cb);
+    }
+    if (nDesign == 0) return 0;
+    HIPCHK(c, hipSetDevice(c->device));
+    Scratch sc(c);
+    MoorArgs A;
+    memset(&A, 0, sizeof(A));
+    A.nDesign = nDesign; A.nLine = nLine; A.depth = depth;
+    double *dl = sc.alloc<double>(nl * RAFTX_ML_N), *dp = pose ? sc.alloc<double>((size_t)nDesign * 6) : nullptr;
+    A.lw = sc.alloc<double>(nl * MOOR_LW_N);
+    A.line_out = line_out ? sc.alloc<double>(nl * MOOR_LO_N) : nullptr;
+    A.C = C_moor ? sc.alloc<double>((size_t)nDesign * 36) : nullptr;
+    A.F = F_moor ? sc.alloc<double>((size_t)nDesign * 6) : nullptr;
+    A.T = T ? sc.alloc<double>(nl * 2) : nullptr;
+    A.J = J ? sc.alloc<double>(nl * 12) : nullptr;
+    A.flags = sc.alloc<int>((size_t)nDesign);
+    if (!dl || (pose && !dp) || !A.lw || (line_out && !A.line_out) || (C_moor && !A.C) || (F_moor && !A.F) || (T && !A.T) || (J && !A.J) ||
+        !A.flags)
+        FAIL(c, "mooring_lines: device allocation failed");
+    H2D(c, dl, lines, nl * RAFTX_ML_N * sizeof(double));
+    if (pose) H2D(c, dp, pose, (size_t)nDesign * 6 * sizeof(double));
+    A.lines = dl;
+    A.pose = dp;
+    HIPCHK(c, hipEventRecord(c->ev0, c->stream));
+    hipLaunchKernelGGL(k_moor_line, dim3(moor_grid((long long)nl)), dim3(MOOR_THREADS), 0, c->stream, A);
+    hipLaunchKernelGGL(k_moor_design, dim3(moor_grid(nDesign)), dim3(MOOR_THREADS), 0, c->stream, A);
+    if (finish_timed(c)) return -2;
+    if (C_moor) D2H(c, C_moor, A.C, (size_t)nDesign * 36 * sizeof(double));
+    if (F_moor) D2H(c, F_moor, A.F, (size_t)nDesign * 6 * sizeof(double));
+    if (T) D2H(c, T, A.T, nl * 2 * sizeof(double));
+    if (J) D2H(c, J, A.J, nl * 12 * sizeof(double));
+    if (line_out) D2H(c, line_out, A.line_out, nl * MOOR_LO_N * sizeof(double));
+    D2H(c, flags, A.flags, (size_t)nDesign * sizeof(int));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+extern "C" int raftx_mooring_program(raftx_ctx *c, int nLine, const double *lines, int nParam, const double *lineCoef,
+                                     const int32_t *lineEdit) {
+    if (!c) return -1;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (nLine == 0) {
+        mooring_program_release(c);
+        return 0;
+    }
+    if (nLine < 0 || !lines || !lineCoef || !lineEdit) FAIL(c, "mooring_program: bad arguments");
+    if (!c->vprog.nM) FAIL(c, "mooring_program: no variant program on this ctx (raftx_variant_program first)");
+    if (nParam != c->vprog.nP)
+        FAIL(c, "mooring_program: nParam=%d is not the %d parameters of the installed variant program", nParam, c->vprog.nP);
+    for (int l = 0; l < nLine; l++) {
+        const double cb = lines[(size_t)l * RAFTX_ML_N + 9];
+        if (std::isfinite(cb) && cb != 0.0)
+            FAIL(c, "mooring_program: line %d has seabed friction CB = %g: friction is not covered (CB must be 0)", l, cb);
+    }
+    mooring_program_release(c);
+    const size_t nb = (size_t)nLine * RAFTX_ML_N * 8, nc = (size_t)nLine * 6 * (nParam + 1) * 8, ne = (size_t)nLine * 4;
+    if (hipMalloc((void **)&c->mprog.base, nb) != hipSuccess || hipMalloc((void **)&c->mprog.coef, nc) != hipSuccess ||
+        hipMalloc((void **)&c->mprog.edit, ne) != hipSuccess) {
+        mooring_program_release(c);
+        FAIL(c, "mooring_program: device allocation failed");
+    }
+    HIPCHK(c, hipMemcpy(c->mprog.base, lines, nb, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(c->mprog.coef, lineCoef, nc, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(c->mprog.edit, lineEdit, ne, hipMemcpyHostToDevice));
+    c->mprog.nLine = nLine;
+    c->mprog.nP = nParam;
+    return 0;
+}
+
+extern "C" int raftx_mooring_expand(raftx_ctx *c, int nDesign, const double *params, double *lines_out) {
+    if (!c) return -1;
+    if (!c->mprog.nLine) FAIL(c, "mooring_expand: no program (raftx_mooring_program first)");
+    const int nP = c->mprog.nP, nLine = c->mprog.nLine;
+    if (nDesign < 0 || (!params && nDesign && nP) || !lines_out) FAIL(c, "mooring_expand: bad arguments");
+    if (!nDesign) return 0;
+    HIPCHK(c, hipSetDevice(c->device));
+    Scratch sc(c);
+    const size_t nl = (size_t)nDesign * nLine;
+    double *dp = sc.alloc<double>((size_t)nDesign * std::max(nP, 1)), *dout = sc.alloc<double>(nl * RAFTX_ML_N);
+    if (!dp || !dout) FAIL(c, "mooring_expand: device allocation failed");
+    if (nP) H2D(c, dp, params, (size_t)nDesign * nP * sizeof(double));
+    MoorExpandArgs E{nDesign, nLine, nP, c->mprog.base, c->mprog.coef, c->mprog.edit, dp, dout};
+    HIPCHK(c, hipEventRecord(c->ev0, c->stream));
+    hipLaunchKernelGGL(k_moor_expand, dim3(moor_grid((long long)nl)), dim3(MOOR_THREADS), 0, c->stream, E);
+    if (finish_timed(c)) return -2;
+    D2H(c, lines_out, dout, nl * RAFTX_ML_N * sizeof(double));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+extern "C" int raftx_sweep_mooring(raftx_ctx *c, int slot, int nLine, const double *lines, int add_stiffness, double *C_moor,
+                                   double *F_moor, double *T_mean, double *T_std, int32_t *flags) {
+    if (!c) return -1;
+    SLOT_REF(S, c, slot, "sweep_mooring");
+    if (S.busy) FAIL(c, "sweep_mooring: slot %d has been launched (call it between raftx_sweep_prepare and raftx_sweep_launch)", slot);
+    if (!S.prepared) FAIL(c, "sweep_mooring: nothing prepared on slot %d (raftx_sweep_prepare first)", slot);
+    if (!flags) FAIL(c, "sweep_mooring: bad arguments (flags is required)");
+    if (S.cset < 0) FAIL(c, "sweep_mooring: slot %d has lost its sea-state tables (internal error)", slot);
+    const size_t n = S.bnd.empty() ? 0 : (size_t)S.bnd.back();
+    const VariantProg *vp = S.p1.var.prog;
+    if (!lines) {
+        if (!vp) FAIL(c, "sweep_mooring: lines == NULL needs a slot prepared with raftx_sweep_prepare_variants");
+        if (!c->mprog.nLine) FAIL(c, "sweep_mooring: no mooring program (raftx_mooring_program first)");
+        if (c->mprog.nP != vp->nP) FAIL(c, "sweep_mooring: the mooring program has %d parameters, the variant program %d", c->mprog.nP, vp->nP);
+        if (nLine != c->mprog.nLine) FAIL(c, "sweep_mooring: nLine=%d is not the %d lines of the mooring program", nLine, c->mprog.nLine);
+    } else {
+        if (nLine < 1) FAIL(c, "sweep_mooring: nLine must be positive (got %d)", nLine);
+        for (size_t i = 0; i < n * (size_t)nLine; i++) {
+            const double cb = lines[i * RAFTX_ML_N + 9];
+            if (std::isfinite(cb) && cb != 0.0)
+                FAIL(c, "sweep_mooring: line %zu of design %zu has seabed friction CB = %g: friction is not covered (CB must be 0)",
+                     i % nLine, i / nLine, cb);
+        }
+    }
+    const double depth = c->csets[S.cset].T.depth;
+    if (!std::isfinite(depth) || !(depth > 0.0)) FAIL(c, "sweep_mooring: the depth must be positive and finite (got %g)", depth);
+    HIPCHK(c, hipSetDevice(c->device));
+    if (S.mooring.evUp) HIPCHK(c, hipEventSynchronize(S.mooring.evUp));   // (a second request on one slot: the landing area is free again)
+    else HIPCHK(c, hipEventCreateWithFlags(&S.mooring.evUp, hipEventDisableTiming));
+    S.mooring.on = false;
+    const size_t nl = n * (size_t)nLine, nT = 2 * (size_t)nLine;
+    HIPCHK(c, S.mooring.pin.reserve(n * (42 + nT) + (n + 1) / 2 + 1));
+    MoorArgs A;
+    memset(&A, 0, sizeof(A));
+    A.nDesign = (int)n; A.nLine = nLine; A.depth = depth;
+    const double *dl = nullptr, *dp = nullptr, *dpar = nullptr;
+    double *dexp = nullptr;
+    int rc = upload_on(c, c->sCopy, S.allocs, S.p1.pose, S.p1.pose ? n * 6 : 0, &dp);
+    if (lines) rc |= upload_on(c, c->sCopy, S.allocs, lines, nl * RAFTX_ML_N, &dl);
+    else {
+        rc |= upload_on(c, c->sCopy, S.allocs, S.p1.var.params, n * (size_t)vp->nP, &dpar);
+        rc |= pool_alloc(c, S.allocs, nl * RAFTX_ML_N, &dexp);
+        dl = dexp;
+    }
+    double *dlw = nullptr, *dC = nullptr, *dF = nullptr, *dT = nullptr, *dLr = nullptr;
+    int *dfl = nullptr;
+    rc |= pool_alloc(c, S.allocs, nl * MOOR_LW_N, &dlw) | pool_alloc(c, S.allocs, n * 36, &dC) | pool_alloc(c, S.allocs, n * 6, &dF) |
+          pool_alloc(c, S.allocs, nl * 2, &dT) | pool_alloc(c, S.allocs, nl * 36, &dLr) | pool_alloc(c, S.allocs, n, &dfl);
+    if (rc) return -2;
+    A.lw = dlw; A.C = dC; A.F = dF; A.T = dT; A.Lr = dLr; A.flags = dfl;
+    A.lines = dl; A.pose = dp;
+    if (n) {
+        if (!lines) {
+            MoorExpandArgs E{(int)n, nLine, vp->nP, c->mprog.base, c->mprog.coef, c->mprog.edit, dpar, dexp};
+            hipLaunchKernelGGL(k_moor_expand, dim3(moor_grid((long long)nl)), dim3(MOOR_THREADS), 0, c->sCopy, E);
+        }
+        hipLaunchKernelGGL(k_moor_line, dim3(moor_grid((long long)nl)), dim3(MOOR_THREADS), 0, c->sCopy, A);
+        hipLaunchKernelGGL(k_moor_design, dim3(moor_grid((long long)n)), dim3(MOOR_THREADS), 0, c->sCopy, A);
+        HIPCHK(c, hipGetLastError());
+        double *p = S.mooring.pin.p;
+        HIPCHK(c, hipMemcpyAsync(p, A.C, n * 36 * sizeof(double), hipMemcpyDeviceToHost, c->sCopy));
+        HIPCHK(c, hipMemcpyAsync(p + n * 36, A.F, n * 6 * sizeof(double), hipMemcpyDeviceToHost, c->sCopy));
+        HIPCHK(c, hipMemcpyAsync(p + n * 42, A.T, n * nT * sizeof(double), hipMemcpyDeviceToHost, c->sCopy));
+        HIPCHK(c, hipMemcpyAsync(p + n * (42 + nT), A.flags, n * sizeof(int), hipMemcpyDeviceToHost, c->sCopy));
+    }
+    HIPCHK(c, hipEventRecord(S.mooring.evUp, c->sCopy));
+    S.mooring.nLine = nLine;
+    S.mooring.add = add_stiffness != 0;
+    S.mooring.C = A.C; S.mooring.Lr = A.Lr;
+    S.mooring.C_out = C_moor; S.mooring.F_out = F_moor; S.mooring.T_out = T_mean; S.mooring.Tstd_out = T_std;
+    S.mooring.flags_out = flags;
+    S.mooring.on = true;
     return 0;
 }
 

@@ -481,3 +481,22 @@ def volturnus_program(base_design, heading_adjust=0.0):
         P.diameter(4 + k, c(12.4), c(pH=1.0))
         P.ends(7 + k, [c(ccD=0.5), zero, c(14.545)], [c(ocD=-0.5, ocR=1.0), zero, c(14.545)], heading=heads[3][k] + heading_adjust)
     return P
+
+
+def volturnus_mooring_program(base_design, rho=1025.0, g=9.81):
+    """The mooring edits of raft/parametersweep.py:64-68, 79-83 as a raft_amd.mooring.MooringProgram over the parameters
+    of ``volturnus_params``: the three fairleads sit on the outer face of the outer columns, at the radius ocR + ocD/2 and
+    the headings 180 / 60 / 300 deg (the edit of :79-83 is the one in force when the model is built: it runs after
+    :64-68 in every pass of the loops).  Anchors, depths of the fairleads, lengths and line types stay the base's."""
+    from .mooring import MooringProgram, lines_from_design
+    lines, _ = lines_from_design(base_design, rho=rho, g=g)
+    assert len(lines) == 3, "not the VolturnUS-S mooring layout"
+    P = MooringProgram(lines, 5)
+    c = lambda c0=0.0, ccD=0.0, ocD=0.0, T=0.0, ocR=0.0, pH=0.0: [c0, ccD, ocD, T, ocR, pH]
+    const = lambda v: c(float(v))
+    for l, (cx, cy) in enumerate(((-1.0, None), (np.cos(np.deg2rad(60)), np.sin(np.deg2rad(60))),
+                                  (np.cos(np.deg2rad(300)), np.sin(np.deg2rad(300))))):
+        a, f = lines[l, 0:3], lines[l, 3:6]
+        fy = const(f[1]) if cy is None else c(ocD=0.5 * cy, ocR=cy)              # :79 leaves y of the first fairlead alone
+        P.ends(l, [const(a[0]), const(a[1]), const(a[2])], [c(ocD=0.5 * cx, ocR=cx), fy, const(f[2])])
+    return P

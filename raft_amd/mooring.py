@@ -1,0 +1,105 @@
+"""Quasi-static mooring lines for the device (include/raftx_mooring.h): the YAML ``mooring:`` section as line records,
+and the affine edits of a parametric sweep's anchors and fairleads.
+
+A record is ML_N = 16 doubles: anchor (global) 0:3, fairlead (body frame, relative to the unit's reference point) 3:6,
+unstretched length 6, EA 7, submerged weight per length w 8, seabed friction CB 9 (must be 0), zeros.  Only what the
+library covers is parsed -- one catenary segment per line from a ``fixed`` point (end A) to a ``vessel`` point (end B),
+moorMod 0; everything else raises ``UnsupportedFOWT`` (as raft_amd.strips does for units the kernels do not cover).
+"""
+import numpy as np
+
+from .strips import UnsupportedFOWT
+
+ML_N = 16
+ML_ANCHOR, ML_FAIRLEAD, ML_L, ML_EA, ML_W, ML_CB = 0, 3, 6, 7, 8, 9
+FLAG_BAD_LINE, FLAG_VERTICAL, FLAG_SLACK, FLAG_NO_CONVERGENCE = 1, 2, 4, 8
+
+
+def lines_from_design(design, rho=1025.0, g=9.81):
+    """Line records [nLine,16] of ``design['mooring']`` (MoorPy's System.parseYAML for the layouts the library covers):
+    w = (mass_density - rho pi/4 d^2) g, EA = stiffness, in the order of the ``lines`` list.  Returns (records, depth)."""
+    moor = design.get("mooring") if isinstance(design, dict) else None
+    if not isinstance(moor, dict):
+        raise UnsupportedFOWT("the design has no mooring section")
+    if "file" in moor:
+        raise UnsupportedFOWT("the mooring system is a MoorDyn file (%s): only the YAML section is parsed" % moor["file"])
+    if int(moor.get("moorMod", 0)) != 0:
+        raise UnsupportedFOWT("moorMod = %s: line dynamics are not covered (moorMod 0 only)" % moor.get("moorMod"))
+    depth = float(moor["water_depth"])
+    points, types = {}, {}
+    for p in moor.get("points", []):
+        kind = str(p.get("type", "")).lower()
+        if kind not in ("fixed", "vessel"):
+            raise UnsupportedFOWT("mooring point %r is of type %r: free points are not covered" % (p.get("name"), p.get("type")))
+        points[p["name"]] = (kind, np.array(p["location"], dtype=float).reshape(3))
+    for t in moor.get("line_types", []):
+        types[t["name"]] = t
+    used = {}
+    recs = []
+    for ln in moor.get("lines", []):
+        for end in ("endA", "endB"):
+            if ln[end] not in points:
+                raise UnsupportedFOWT("mooring line %r: unknown point %r" % (ln.get("name"), ln[end]))
+            used[ln[end]] = used.get(ln[end], 0) + 1
+        (kA, pA), (kB, pB) = points[ln["endA"]], points[ln["endB"]]
+        if kA == "vessel" and kB == "vessel":
+            raise UnsupportedFOWT("mooring line %r has both ends on the vessel" % ln.get("name"))
+        if not (kA == "fixed" and kB == "vessel"):
+            raise UnsupportedFOWT("mooring line %r must run from a fixed point (end A) to a vessel point (end B)" % ln.get("name"))
+        if ln["type"] not in types:
+            raise UnsupportedFOWT("mooring line %r: unknown line type %r" % (ln.get("name"), ln["type"]))
+        t = types[ln["type"]]
+        d = float(t["diameter"])
+        rec = np.zeros(ML_N)
+        rec[ML_ANCHOR:ML_ANCHOR + 3] = pA
+        rec[ML_FAIRLEAD:ML_FAIRLEAD + 3] = pB
+        rec[ML_L] = float(ln["length"])
+        rec[ML_EA] = float(t["stiffness"])
+        rec[ML_W] = (float(t["mass_density"]) - rho * (np.pi / 4 * d * d)) * g
+        recs.append(rec)
+    if not recs:
+        raise UnsupportedFOWT("the mooring section has no lines")
+    shared = [n for n, k in used.items() if k > 1]
+    if shared:
+        raise UnsupportedFOWT("mooring point %r joins %d lines: multi-segment and bridle layouts are not covered" % (shared[0], used[shared[0]]))
+    return np.ascontiguousarray(recs), depth
+
+
+def tension_names(n):
+    """Names of the 2 n tension channels in the order of T / J: ends A of all lines, then ends B (getTensions)."""
+    return ["Tmoor_A%d" % (i + 1) for i in range(n)] + ["Tmoor_B%d" % (i + 1) for i in range(n)]
+
+
+class MooringProgram:
+    """Edit program of the mooring lines of a parametric sweep (raftx_mooring_program): base records + anchor / fairlead
+    coordinates that are affine in the sweep parameters -- value = c0 + c1*p1 + ..., left to right without fused
+    multiply-adds, as ``VariantProgram.ends``."""
+
+    def __init__(self, lines, n_param):
+        self.lines = np.ascontiguousarray(lines, dtype=float).reshape(-1, ML_N).copy()
+        self.n_param = int(n_param)
+        n = len(self.lines)
+        self.coef = np.zeros((n, 6, self.n_param + 1))
+        self.edit = np.zeros(n, dtype=np.int32)
+
+    @property
+    def n(self):
+        return len(self.lines)
+
+    def ends(self, l, anchor, fairlead):
+        """Anchor and fairlead of line l: [3][nParam+1] rows of coefficients each (constant, then one per parameter)."""
+        self.coef[l, :3] = np.asarray(anchor, dtype=float).reshape(3, self.n_param + 1)
+        self.coef[l, 3:] = np.asarray(fairlead, dtype=float).reshape(3, self.n_param + 1)
+        self.edit[l] = 1
+
+    def expand(self, params):
+        """The records [nD,nLine,16] of the variants ``params`` [nD,nParam] on the host: the library's evaluation order."""
+        params = np.ascontiguousarray(params, dtype=float).reshape(-1, self.n_param)
+        out = np.broadcast_to(self.lines, (len(params),) + self.lines.shape).copy()
+        for l in np.flatnonzero(self.edit):
+            for i in range(6):
+                v = np.full(len(params), self.coef[l, i, 0])
+                for q in range(self.n_param):
+                    v = v + self.coef[l, i, 1 + q] * params[:, q]
+                out[:, l, i] = v
+        return out

@@ -307,22 +307,25 @@ class GeometrySweep(Sweep):
         return self.tables.n_design
 
     def take(self, lo, hi):
+        return self._take_mooring(self._take_bem_geometry(lo, hi), lo, hi)
+
+    def _take_bem_geometry(self, lo, hi):
         return self._take_bem(GeometrySweep(self.tables.take(lo, hi), self.M0[lo:hi], self.B0[lo:hi], self.C0[lo:hi], self.w,
                                             self.k, self.depth, self.zeta, self.beta, self.nIter, self.XiStart, self.tol,
                                             None if self.pose is None else self.pose[lo:hi], self.add_mask,
                                             None if self.MBw is None else self.MBw[lo:hi], self.rho, self.g), lo, hi)
 
     def run_crossing(self, ctx, n_chunk=0, n_worker=0, want_Xi=False, Xi_out=None, modal=False, dM=None, dC=None, want_props=False,
-                     current=None, channels=None):
+                     current=None, channels=None, mooring=None):
         """The whole boundary crossing in ONE library call (raftx_sweep_stats): descriptors in, motion statistics +
         iteration counts (+ responses) out, with upload / generation / solve / download of consecutive design blocks
         overlapped on the library's internal streams.  Nothing stays resident on ``ctx``.  modal=True / current=dict(..) /
         channels=dict(..): the streamed form on slot 0 with the eigen analysis / mean current loads of every design /
         output channels of every (design, case) (see ``prepare_crossing``)."""
-        if modal or current is not None or channels is not None:
+        if modal or current is not None or channels is not None or mooring is not None or self.mooring is not None:
             return self.wait_crossing(ctx, self.submit_crossing(ctx, 0, n_chunk=n_chunk, want_Xi=want_Xi, Xi_out=Xi_out, modal=modal,
                                                                 dM=dM, dC=dC, want_props=want_props, current=current,
-                                                                channels=channels))
+                                                                channels=channels, mooring=mooring))
         self._crossing_supported()
         t = self.tables
         r = ctx.sweep_stats(t, self.M0, self.B0, self.C0, self.w, self.k, self.depth, self.zeta, self.beta, self.nIter,
@@ -332,7 +335,7 @@ class GeometrySweep(Sweep):
         return r
 
     def prepare_crossing(self, ctx, slot, n_chunk=0, want_Xi=False, Xi_out=None, modal=False, dM=None, dC=None, want_props=False,
-                         current=None, channels=None):
+                         current=None, channels=None, mooring=None):
         """First stage of the streamed form of ``run_crossing`` for back-to-back batches: enqueue this batch's descriptor
         upload and member pass on ``slot`` (0 .. 3) and return a handle (raftx_sweep_prepare).  modal=True: the batch's
         eigen analysis rides along (raftx_sweep_modal on M_extra + device terms + dM, C_extra + device terms + dC) and
@@ -341,11 +344,16 @@ class GeometrySweep(Sweep):
         and shearExp optional, 0 and 0.12) and ``wait_crossing`` also returns D_hydro [nD,nCur,6].  channels=dict(L=, Gw=):
         the standard deviations of linear output channels of every (design, case) ride along (raftx_sweep_channels: the
         channels of ``run_channels``; L [nChan,3,6] shared or [nD,nChan,3,6], Gw optional -- raft_amd.dropin.sweep_output_rows
-        builds the rows of a unit) and ``wait_crossing`` also returns chan_std [nD,nCase,nChan]."""
+        builds the rows of a unit) and ``wait_crossing`` also returns chan_std [nD,nCase,nChan].  mooring=dict(lines= |
+        program=, add_stiffness=True, tensions=True): the quasi-static mooring lines of every design ride along
+        (raftx_sweep_mooring; lines [nD,nLine,16] records of raft_amd.mooring, or program= a MooringProgram on a
+        VariantSweep, fed the batch's params): C_moor is added to the device C0 ahead of the add-up and ``wait_crossing``
+        also returns C_moor, F_moor, T_mean, T_std, moor_flags.  A request stored as ``sweep.mooring`` is used when the
+        argument is None; ``take`` shards its lines with the designs."""
         self._crossing_supported()
-        return self._with_channels(ctx, self._with_current(ctx, self._with_modal(ctx, ctx.sweep_prepare(slot, self.tables, self.M0, self.B0, self.C0, self.w, self.k, self.depth, self.zeta, self.beta,
+        return self._with_mooring(ctx, self._with_channels(ctx, self._with_current(ctx, self._with_modal(ctx, ctx.sweep_prepare(slot, self.tables, self.M0, self.B0, self.C0, self.w, self.k, self.depth, self.zeta, self.beta,
                                  self.nIter, self.tol, self.XiStart, pose=self.pose, rho=self.rho, g=self.g, add_mask=self.add_mask,
-                                 n_chunk=n_chunk, want_Xi=want_Xi, Xi_out=Xi_out), modal, dM, dC, want_props), current), channels)
+                                 n_chunk=n_chunk, want_Xi=want_Xi, Xi_out=Xi_out), modal, dM, dC, want_props), current), channels), mooring)
 
     @staticmethod
     def _with_modal(ctx, handle, modal, dM, dC, want_props):
@@ -386,6 +394,32 @@ class GeometrySweep(Sweep):
             ctx.sweep_cancel(handle)
             raise
 
+    mooring = None        # a standing mooring= request of this sweep (dict as in ``prepare_crossing``); ``take`` shards its lines
+
+    def _take_mooring(self, sub, lo, hi):
+        if self.mooring is not None:
+            sub.mooring = dict(self.mooring)
+            if sub.mooring.get("lines") is not None:
+                sub.mooring["lines"] = np.ascontiguousarray(np.asarray(self.mooring["lines"])[lo:hi])
+        return sub
+
+    def _with_mooring(self, ctx, handle, mooring):
+        mooring = self.mooring if mooring is None else mooring
+        if mooring is None:
+            return handle
+        try:
+            unknown = set(mooring) - {"lines", "program", "add_stiffness", "tensions"}
+            if unknown or (mooring.get("lines") is None) == (mooring.get("program") is None):
+                raise ValueError("mooring=dict(lines= | program=[, add_stiffness=, tensions=]) (got %s)" % sorted(mooring))
+            prog = mooring.get("program")
+            if prog is not None and getattr(ctx, "_mprog_owner", None) is not prog:
+                ctx.mooring_program(prog)
+            return ctx.sweep_mooring(handle, lines=mooring.get("lines"), add_stiffness=mooring.get("add_stiffness", True),
+                                     tensions=mooring.get("tensions", True))
+        except Exception:
+            ctx.sweep_cancel(handle)
+            raise
+
     def launch_crossing(self, ctx, handle):
         """Second stage: table generation, fused fixed point and statistics of a prepared batch (raftx_sweep_launch).  With
         launch(i+1), prepare(i+2), wait(i) per step a long sweep keeps three batches in flight and the fused kernels of
@@ -393,11 +427,11 @@ class GeometrySweep(Sweep):
         return ctx.sweep_launch(handle)
 
     def submit_crossing(self, ctx, slot, n_chunk=0, want_Xi=False, Xi_out=None, modal=False, dM=None, dC=None, want_props=False,
-                        current=None, channels=None):
+                        current=None, channels=None, mooring=None):
         """prepare + launch in one call (raftx_sweep_submit); ``wait_crossing`` collects the results."""
         return self.launch_crossing(ctx, self.prepare_crossing(ctx, slot, n_chunk=n_chunk, want_Xi=want_Xi, Xi_out=Xi_out,
                                                                modal=modal, dM=dM, dC=dC, want_props=want_props, current=current,
-                                                               channels=channels))
+                                                               channels=channels, mooring=mooring))
 
     def _crossing_supported(self):
         """raftx_sweep_stats / raftx_sweep_submit carry neither frequency-dependent matrices nor potential-flow excitation
@@ -792,22 +826,23 @@ class VariantSweep(GeometrySweep):
         sub = VariantSweep(self.program, self.params[lo:hi], self.M0[lo:hi], self.B0[lo:hi], self.C0[lo:hi], self.w, self.k, self.depth,
                            self.zeta, self.beta, self.nIter, self.XiStart, self.tol, None if self.pose is None else self.pose[lo:hi],
                            self.add_mask, self.rho, self.g)
-        return self._take_bem(sub, lo, hi)
+        return self._take_mooring(self._take_bem(sub, lo, hi), lo, hi)
 
     def prepare_crossing(self, ctx, slot, n_chunk=0, want_Xi=False, Xi_out=None, modal=False, dM=None, dC=None, want_props=False,
-                         current=None, channels=None):
+                         current=None, channels=None, mooring=None):
         self._crossing_supported()
         self._install(ctx)
-        return self._with_channels(ctx, self._with_current(ctx, self._with_modal(ctx, ctx.sweep_prepare_variants(slot, self.params, self.M0, self.B0, self.C0, self.w, self.k, self.depth, self.zeta, self.beta,
+        return self._with_mooring(ctx, self._with_channels(ctx, self._with_current(ctx, self._with_modal(ctx, ctx.sweep_prepare_variants(slot, self.params, self.M0, self.B0, self.C0, self.w, self.k, self.depth, self.zeta, self.beta,
                                           self.nIter, self.tol, self.XiStart, pose=self.pose, rho=self.rho, g=self.g,
                                           add_mask=self.add_mask, n_chunk=n_chunk, want_Xi=want_Xi, Xi_out=Xi_out),
-                                modal, dM, dC, want_props), current), channels)
+                                modal, dM, dC, want_props), current), channels), mooring)
 
     def run_crossing(self, ctx, n_chunk=0, n_worker=0, want_Xi=False, Xi_out=None, slot=0, modal=False, dM=None, dC=None,
-                     want_props=False, current=None, channels=None):
+                     want_props=False, current=None, channels=None, mooring=None):
         """One isolated crossing: prepare + launch + wait on ``slot``."""
         return self.wait_crossing(ctx, self.submit_crossing(ctx, slot, n_chunk=n_chunk, want_Xi=want_Xi, Xi_out=Xi_out, modal=modal,
-                                                            dM=dM, dC=dC, want_props=want_props, current=current, channels=channels))
+                                                            dM=dM, dC=dC, want_props=want_props, current=current, channels=channels,
+                                                            mooring=mooring))
 
     def _build_qtf_tables(self, ctx):
         self._install(ctx)
