@@ -51,6 +51,8 @@ QTFGEN_EXPORTS = ("raftx_qtf_tables_build", "raftx_qtf_tables_build_variants", "
 # include/raftx_mooring.h: quasi-static mooring lines, the device library only
 MOORING_EXPORTS = ("raftx_mooring_lines", "raftx_mooring_program", "raftx_mooring_expand", "raftx_sweep_mooring")
 ML_N = 16          # doubles per mooring line record (RAFTX_ML_N)
+# include/raftx_statics.h: the mean equilibrium pose, the device library only
+STATICS_EXPORTS = ("raftx_mean_pose",)
 MOOR_BAD_LINE, MOOR_VERTICAL, MOOR_SLACK, MOOR_NO_CONVERGENCE = 1, 2, 4, 8
 QKG_N = 8          # doubles per row of the Kim & Yue geometry stream (RAFTX_QKG_N)
 
@@ -165,6 +167,11 @@ class RaftxLib:
             L.raftx_mooring_expand.restype = C.c_int
             L.raftx_sweep_mooring.argtypes = [_vp, C.c_int, C.c_int, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp]
             L.raftx_sweep_mooring.restype = C.c_int
+        self.has_statics = all(hasattr(L, s) for s in STATICS_EXPORTS)
+        if self.has_statics:
+            L.raftx_mean_pose.argtypes = [_vp, C.c_int, C.c_int, _vp, _vp, C.c_double, _vp, _vp, _vp, _vp, _vp, C.c_int,
+                                          _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]
+            L.raftx_mean_pose.restype = C.c_int
         self.has_current = all(hasattr(L, s) for s in CURRENT_EXPORTS)
         if self.has_current:
             L.raftx_current_loads.argtypes = [_vp, C.c_int, _vp, _vp, _vp, C.c_double, C.c_double, _vp]
@@ -766,6 +773,43 @@ class Context:
         out = np.empty((nD, n, ML_N))
         self._check(L.raftx_mooring_expand(self._h, nD, _ptr(params), _ptr(out)), "raftx_mooring_expand")
         return out
+
+    # ------------------------------------------------------------- the mean equilibrium pose (include/raftx_statics.h)
+    def mean_pose(self, K_hs, F0, depth, lines=None, params=None, F_env=None, x_ref=None, tol=None, max_iter=0,
+                  want=("pose", "C", "F", "T", "J", "F_res", "iterations")):
+        """The mean pose of every design (raftx_mean_pose; Model.solveStatics, staticsMod 0 / forcingMod 0): ``K_hs``
+        [nD,6,6], ``F0`` [nD,6], ``lines`` [nD,nLine,16] -- or None: the installed mooring program fed ``params``
+        [nD,nParam] --, ``F_env`` / ``x_ref`` [nD,6] or None (zero), ``tol`` (m, rad) or None.  Returns a dict with pose
+        [nD,6], C [nD,6,6], F [nD,6], T [nD,2 nLine], J [nD,2 nLine,6], F_res [nD,6], iterations [nD] -- those named in
+        ``want`` -- and flags [nD] (int32; a flagged design's outputs are NaN)."""
+        if not self.rlib.has_statics:
+            raise RaftxError("mean_pose: %s does not implement include/raftx_statics.h (the device library does)" % self.rlib.path)
+        L = self.rlib.lib
+        K_hs = _f64(K_hs)
+        nD = K_hs.shape[0]
+        K_hs, F0 = _f64(K_hs, (nD, 6, 6), "K_hs"), _f64(F0, (nD, 6), "F0")
+        if lines is None:
+            if getattr(self, "_mprog", None) is None:
+                raise RaftxError("mean_pose: no program installed (mooring_program first) and no lines given")
+            nL, nP = self._mprog
+            params = _f64(params, (nD, nP), "params")
+        else:
+            lines = _f64(lines)
+            if lines.ndim != 3 or lines.shape[0] != nD or lines.shape[2] != ML_N:
+                raise ValueError("lines has shape %s, expected [%d,nLine,%d]" % (lines.shape, nD, ML_N))
+            nL, params = lines.shape[1], None
+        F_env = None if F_env is None else _f64(F_env, (nD, 6), "F_env")
+        x_ref = None if x_ref is None else _f64(x_ref, (nD, 6), "x_ref")
+        tol = None if tol is None else _f64(tol, (2,), "tol")
+        shapes = dict(pose=(nD, 6), C=(nD, 6, 6), F=(nD, 6), T=(nD, 2 * nL), J=(nD, 2 * nL, 6), F_res=(nD, 6))
+        out = {k: (np.empty(shapes[k]) if k in want else None) for k in shapes}
+        out["iterations"] = np.zeros(nD, dtype=np.int32) if "iterations" in want else None
+        out["flags"] = np.zeros(nD, dtype=np.int32)
+        self._check(L.raftx_mean_pose(self._h, nD, nL, _ptr(lines), _ptr(params), float(depth), _ptr(K_hs), _ptr(F0), _ptr(F_env),
+                                      _ptr(x_ref), _ptr(tol), int(max_iter), _ptr(out["pose"]), _ptr(out["C"]), _ptr(out["F"]),
+                                      _ptr(out["T"]), _ptr(out["J"]), _ptr(out["F_res"]), _ptr(out["iterations"]), _ptr(out["flags"])),
+                    "raftx_mean_pose")
+        return {k: v for k, v in out.items() if v is not None}
 
     def sweep_mooring(self, handle, lines=None, add_stiffness=True, tensions=True):
         """Ask for the mooring system of a PREPARED, not yet launched crossing (raftx_sweep_mooring): ``lines``

@@ -46,6 +46,7 @@
 #include "../../include/raftx_channels.h"
 #include "../../include/raftx_qtfgen.h"
 #include "../../include/raftx_mooring.h"
+#include "../../include/raftx_statics.h"
 
 // roctx ranges around the phases of the host side: named spans for `rocprofv3 --marker-trace`.
 // librocprofiler-sdk-roctx is bound at run time on first use; without it (or outside a profiler) the ranges cost a branch.
@@ -90,6 +91,7 @@ struct RangeScope {
 #include "raftx_channels.h"
 #include "raftx_qtfgen.h"
 #include "raftx_mooring.h"
+#include "raftx_statics.h"
 
 // Coupled array solve (raft_model.py:1164-1236): Xi = Z_sys^-1 F for every (system, bin).  One wavefront per
 // (system, bin), NBIN (1, 2 or 4: what fits LDS) consecutive bins per workgroup so that the loads of one matrix entry
@@ -4686,6 +4688,83 @@ extern "C" int raftx_mooring_expand(raftx_ctx *c, int nDesign, const double *par
     hipLaunchKernelGGL(k_moor_expand, dim3(moor_grid((long long)nl)), dim3(MOOR_THREADS), 0, c->stream, E);
     if (finish_timed(c)) return -2;
     D2H(c, lines_out, dout, nl * RAFTX_ML_N * sizeof(double));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+// ---- the mean equilibrium pose (include/raftx_statics.h, raftx_statics.h)
+extern "C" int raftx_mean_pose(raftx_ctx *c, int nDesign, int nLine, const double *lines, const double *params, double depth,
+                               const double *K_hs, const double *F0, const double *F_env, const double *x_ref, const double tol[2],
+                               int max_iter, double *pose, double *C_moor, double *F_moor, double *T, double *J, double *F_res,
+                               int32_t *iterations, int32_t *flags) {
+    if (!c) return -1;
+    if (nLine < 1) FAIL(c, "mean_pose: nLine must be positive (got %d)", nLine);
+    if (nDesign < 0) FAIL(c, "mean_pose: nDesign must not be negative (got %d)", nDesign);
+    if (!K_hs || !F0 || !flags) FAIL(c, "mean_pose: bad arguments (K_hs, F0 and flags are required)");
+    if (!std::isfinite(depth) || !(depth > 0.0)) FAIL(c, "mean_pose: the depth must be positive and finite (got %g)", depth);
+    const double tolT = tol ? tol[0] : 1e-9, tolR = tol ? tol[1] : 1e-10;
+    if (!std::isfinite(tolT) || !std::isfinite(tolR) || tolT < 0.0 || tolR < 0.0)
+        FAIL(c, "mean_pose: the tolerances must be finite and not negative (got %g m, %g rad)", tolT, tolR);
+    const size_t nl = (size_t)nDesign * nLine;
+    if (!lines) {
+        if (!c->mprog.nLine) FAIL(c, "mean_pose: lines == NULL without a mooring program (raftx_mooring_program first)");
+        if (nLine != c->mprog.nLine) FAIL(c, "mean_pose: nLine=%d is not the %d lines of the mooring program", nLine, c->mprog.nLine);
+        if (!params && nDesign && c->mprog.nP) FAIL(c, "mean_pose: lines == NULL needs params [nDesign,%d]", c->mprog.nP);
+    } else {
+        for (size_t i = 0; i < nl; i++) {
+            const double cb = lines[i * RAFTX_ML_N + 9];
+            if (std::isfinite(cb) && cb != 0.0)
+                FAIL(c, "mean_pose: line %zu of design %zu has seabed friction CB = %g: friction is not covered (CB must be 0)",
+                     i % nLine, i / nLine, cb);
+        }
+    }
+    if (nDesign == 0) return 0;
+    HIPCHK(c, hipSetDevice(c->device));
+    Scratch sc(c);
+    const size_t n = (size_t)nDesign;
+    MeanPoseArgs A;
+    memset(&A, 0, sizeof(A));
+    A.nDesign = nDesign; A.nLine = nLine; A.G = mean_pose_group(nLine); A.maxIter = max_iter > 0 ? max_iter : MP_MAX_IT;
+    A.depth = depth; A.tolT = tolT; A.tolR = tolR;
+    const int nP = lines ? 0 : c->mprog.nP;
+    double *dl = sc.alloc<double>(nl * RAFTX_ML_N), *dpar = (!lines && nP) ? sc.alloc<double>(n * nP) : nullptr;
+    double *dK = sc.alloc<double>(n * 36), *dF0 = sc.alloc<double>(n * 6), *dFe = F_env ? sc.alloc<double>(n * 6) : nullptr;
+    double *dxr = x_ref ? sc.alloc<double>(n * 6) : nullptr;
+    A.lw = sc.alloc<double>(nl * MOOR_LW_N);
+    A.pose = pose ? sc.alloc<double>(n * 6) : nullptr;
+    A.C = C_moor ? sc.alloc<double>(n * 36) : nullptr;
+    A.F = F_moor ? sc.alloc<double>(n * 6) : nullptr;
+    A.T = T ? sc.alloc<double>(nl * 2) : nullptr;
+    A.J = J ? sc.alloc<double>(nl * 12) : nullptr;
+    A.Fres = F_res ? sc.alloc<double>(n * 6) : nullptr;
+    A.iterations = iterations ? sc.alloc<int>(n) : nullptr;
+    A.flags = sc.alloc<int>(n);
+    if (!dl || (!lines && nP && !dpar) || !dK || !dF0 || (F_env && !dFe) || (x_ref && !dxr) || !A.lw || (pose && !A.pose) ||
+        (C_moor && !A.C) || (F_moor && !A.F) || (T && !A.T) || (J && !A.J) || (F_res && !A.Fres) || (iterations && !A.iterations) || !A.flags)
+        FAIL(c, "mean_pose: device allocation failed");
+    if (lines) H2D(c, dl, lines, nl * RAFTX_ML_N * sizeof(double));
+    else if (nP) H2D(c, dpar, params, n * nP * sizeof(double));
+    H2D(c, dK, K_hs, n * 36 * sizeof(double));
+    H2D(c, dF0, F0, n * 6 * sizeof(double));
+    if (F_env) H2D(c, dFe, F_env, n * 6 * sizeof(double));
+    if (x_ref) H2D(c, dxr, x_ref, n * 6 * sizeof(double));
+    A.lines = dl; A.K_hs = dK; A.F0 = dF0; A.F_env = dFe; A.x_ref = dxr;
+    HIPCHK(c, hipEventRecord(c->ev0, c->stream));
+    if (!lines) {                                                // the records of the program's variants, as raftx_mooring_expand
+        MoorExpandArgs E{nDesign, nLine, nP, c->mprog.base, c->mprog.coef, c->mprog.edit, dpar, dl};
+        hipLaunchKernelGGL(k_moor_expand, dim3(moor_grid((long long)nl)), dim3(MOOR_THREADS), 0, c->stream, E);
+    }
+    const int perBlock = MP_THREADS / A.G;
+    hipLaunchKernelGGL(k_mean_pose, dim3((unsigned)((nDesign + perBlock - 1) / perBlock)), dim3(MP_THREADS), 0, c->stream, A);
+    if (finish_timed(c)) return -2;
+    if (pose) D2H(c, pose, A.pose, n * 6 * sizeof(double));
+    if (C_moor) D2H(c, C_moor, A.C, n * 36 * sizeof(double));
+    if (F_moor) D2H(c, F_moor, A.F, n * 6 * sizeof(double));
+    if (T) D2H(c, T, A.T, nl * 2 * sizeof(double));
+    if (J) D2H(c, J, A.J, nl * 12 * sizeof(double));
+    if (F_res) D2H(c, F_res, A.Fres, n * 6 * sizeof(double));
+    if (iterations) D2H(c, iterations, A.iterations, n * sizeof(int));
+    D2H(c, flags, A.flags, n * sizeof(int));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return 0;
 }

@@ -60,13 +60,13 @@ __device__ __forceinline__ void moor_eval(const double H, const double V, const 
     }
 }
 
-__global__ void __launch_bounds__(MOOR_THREADS) k_moor_line(MoorArgs A) {
-    const long long t = (long long)blockIdx.x * MOOR_THREADS + threadIdx.x;
-    if (t >= (long long)A.nDesign * A.nLine) return;
-    const int d = (int)(t / A.nLine);
+// One line at the pose ps: the record lw [MOOR_LW_N] (in global memory) and lo [MOOR_LO_N].  The body of k_moor_line, shared
+// with k_mean_pose (raftx_statics.h).
+__device__ __forceinline__ void moor_line_record(const double *__restrict__ line, const double ps[6], const double depth,
+                                                 double *__restrict__ lw, double lo[MOOR_LO_N]) {
     double rec[RAFTX_ML_N];
     {
-        const double2 *p = reinterpret_cast<const double2 *>(A.lines + (size_t)t * RAFTX_ML_N);
+        const double2 *p = reinterpret_cast<const double2 *>(line);
 #pragma unroll
         for (int k = 0; k < RAFTX_ML_N / 2; k++) {
             const double2 v = p[k];
@@ -74,11 +74,6 @@ __global__ void __launch_bounds__(MOOR_THREADS) k_moor_line(MoorArgs A) {
             rec[2 * k + 1] = v.y;
         }
     }
-    double ps[6] = {0, 0, 0, 0, 0, 0};
-    if (A.pose)
-        for (int i = 0; i < 6; i++) ps[i] = A.pose[(size_t)d * 6 + i];
-    double *lw = A.lw + (size_t)t * MOOR_LW_N;
-    double lo[MOOR_LO_N];
     const double nan = __longlong_as_double(0x7ff8000000000000LL);
     for (int i = 0; i < MOOR_LO_N; i++) lo[i] = nan;
     int flag = 0;
@@ -87,7 +82,7 @@ __global__ void __launch_bounds__(MOOR_THREADS) k_moor_line(MoorArgs A) {
     for (int i = 0; i < 6; i++) fin = fin && isfinite(ps[i]);
     const double L = rec[6], EA = rec[7], w = rec[8], az = rec[2];
     double r[3] = {0, 0, 0}, XF = 0.0, ZF = 0.0, ux = 0.0, uy = 0.0;
-    if (!fin || !(L > 0.0) || !(EA > 0.0) || !(w > 0.0) || az < -A.depth - 1e-6 * A.depth) flag = RAFTX_MOOR_BAD_LINE;
+    if (!fin || !(L > 0.0) || !(EA > 0.0) || !(w > 0.0) || az < -depth - 1e-6 * depth) flag = RAFTX_MOOR_BAD_LINE;
     if (!flag) {
         // the arm R r_f with the rotation of geom_pose: the fairlead as end A of a unit vertical member, the unit turned but
         // not displaced; the displacement is added afterwards
@@ -109,7 +104,7 @@ __global__ void __launch_bounds__(MOOR_THREADS) k_moor_line(MoorArgs A) {
         else if (L >= XF + ZF) flag = RAFTX_MOOR_SLACK;
     }
     if (!flag) {
-        const bool seabed = fabs(az + A.depth) <= 1e-6 * A.depth;
+        const bool seabed = fabs(az + depth) <= 1e-6 * depth;
         const double lam = (L * L <= XF * XF + ZF * ZF) ? 0.2 : sqrt(3.0 * ((L * L - ZF * ZF) / (XF * XF) - 1.0));
         double H = fabs(w * XF / (2.0 * lam)), V = 0.5 * w * (ZF / tanh(lam) + L);
         MoorEval e;
@@ -169,8 +164,71 @@ __global__ void __launch_bounds__(MOOR_THREADS) k_moor_line(MoorArgs A) {
         }
     }
     lw[23] = (double)flag;
+}
+
+__global__ void __launch_bounds__(MOOR_THREADS) k_moor_line(MoorArgs A) {
+    const long long t = (long long)blockIdx.x * MOOR_THREADS + threadIdx.x;
+    if (t >= (long long)A.nDesign * A.nLine) return;
+    const int d = (int)(t / A.nLine);
+    double ps[6] = {0, 0, 0, 0, 0, 0};
+    if (A.pose)
+        for (int i = 0; i < 6; i++) ps[i] = A.pose[(size_t)d * 6 + i];
+    double lo[MOOR_LO_N];
+    moor_line_record(A.lines + (size_t)t * RAFTX_ML_N, ps, A.depth, A.lw + (size_t)t * MOOR_LW_N, lo);
     if (A.line_out)
         for (int i = 0; i < MOOR_LO_N; i++) A.line_out[(size_t)t * MOOR_LO_N + i] = lo[i];
+}
+
+// The share of one line record q in C_moor [36] and F_moor [6], and its rows of T and J: the sums of k_moor_design, shared with
+// k_mean_pose (raftx_statics.h).
+__device__ __forceinline__ void moor_line_share(const double *__restrict__ q, double C[36], double F[6]) {
+    const double f[3] = {q[0], q[1], q[2]}, r[3] = {q[3], q[4], q[5]};
+    double K[3][3];
+#pragma unroll
+    for (int i = 0; i < 3; i++)
+#pragma unroll
+        for (int j = 0; j < 3; j++) K[i][j] = q[6 + 3 * i + j];
+    // [r x] and [f x]
+    const double RX[3][3] = {{0.0, -r[2], r[1]}, {r[2], 0.0, -r[0]}, {-r[1], r[0], 0.0}};
+    const double FX[3][3] = {{0.0, -f[2], f[1]}, {f[2], 0.0, -f[0]}, {-f[1], f[0], 0.0}};
+    double KR[3][3], RK[3][3];                                // K [r x], [r x] K
+#pragma unroll
+    for (int i = 0; i < 3; i++)
+#pragma unroll
+        for (int j = 0; j < 3; j++) {
+            KR[i][j] = K[i][0] * RX[0][j] + K[i][1] * RX[1][j] + K[i][2] * RX[2][j];
+            RK[i][j] = RX[i][0] * K[0][j] + RX[i][1] * K[1][j] + RX[i][2] * K[2][j];
+        }
+#pragma unroll
+    for (int i = 0; i < 3; i++)
+#pragma unroll
+        for (int j = 0; j < 3; j++) {
+            const double rkr = RX[i][0] * KR[0][j] + RX[i][1] * KR[1][j] + RX[i][2] * KR[2][j];
+            const double fr = FX[i][0] * RX[0][j] + FX[i][1] * RX[1][j] + FX[i][2] * RX[2][j];     // the arm turning under a fixed force
+            C[6 * i + j] += K[i][j];
+            C[6 * i + 3 + j] += -KR[i][j];
+            C[6 * (3 + i) + j] += RK[i][j];
+            C[6 * (3 + i) + 3 + j] += -rkr - fr;
+        }
+    F[0] += f[0]; F[1] += f[1]; F[2] += f[2];
+    F[3] += r[1] * f[2] - r[2] * f[1];
+    F[4] += r[2] * f[0] - r[0] * f[2];
+    F[5] += r[0] * f[1] - r[1] * f[0];
+}
+__device__ __forceinline__ void moor_line_TJ(const double *__restrict__ q, const int l, const int nL, double *__restrict__ T,
+                                             double *__restrict__ J) {
+    const double r[3] = {q[3], q[4], q[5]};
+    if (T) { T[l] = q[21]; T[nL + l] = q[22]; }
+    if (J)
+#pragma unroll
+        for (int e = 0; e < 2; e++) {
+            const double *g = q + 15 + 3 * e;
+            double *o = J + (size_t)(e * nL + l) * 6;
+            o[0] = g[0]; o[1] = g[1]; o[2] = g[2];
+            o[3] = r[1] * g[2] - r[2] * g[1];
+            o[4] = r[2] * g[0] - r[0] * g[2];
+            o[5] = r[0] * g[1] - r[1] * g[0];
+        }
 }
 
 __global__ void __launch_bounds__(MOOR_THREADS) k_moor_design(MoorArgs A) {
@@ -199,49 +257,9 @@ __global__ void __launch_bounds__(MOOR_THREADS) k_moor_design(MoorArgs A) {
     for (int i = 0; i < 6; i++) F[i] = 0.0;
     for (int l = 0; l < nL; l++) {
         const double *q = lw0 + (size_t)l * MOOR_LW_N;
-        const double f[3] = {q[0], q[1], q[2]}, r[3] = {q[3], q[4], q[5]};
-        double K[3][3];
-#pragma unroll
-        for (int i = 0; i < 3; i++)
-#pragma unroll
-            for (int j = 0; j < 3; j++) K[i][j] = q[6 + 3 * i + j];
-        // [r x] and [f x]
-        const double RX[3][3] = {{0.0, -r[2], r[1]}, {r[2], 0.0, -r[0]}, {-r[1], r[0], 0.0}};
-        const double FX[3][3] = {{0.0, -f[2], f[1]}, {f[2], 0.0, -f[0]}, {-f[1], f[0], 0.0}};
-        double KR[3][3], RK[3][3];                                // K [r x], [r x] K
-#pragma unroll
-        for (int i = 0; i < 3; i++)
-#pragma unroll
-            for (int j = 0; j < 3; j++) {
-                KR[i][j] = K[i][0] * RX[0][j] + K[i][1] * RX[1][j] + K[i][2] * RX[2][j];
-                RK[i][j] = RX[i][0] * K[0][j] + RX[i][1] * K[1][j] + RX[i][2] * K[2][j];
-            }
-#pragma unroll
-        for (int i = 0; i < 3; i++)
-#pragma unroll
-            for (int j = 0; j < 3; j++) {
-                const double rkr = RX[i][0] * KR[0][j] + RX[i][1] * KR[1][j] + RX[i][2] * KR[2][j];
-                const double fr = FX[i][0] * RX[0][j] + FX[i][1] * RX[1][j] + FX[i][2] * RX[2][j];     // the arm turning under a fixed force
-                C[6 * i + j] += K[i][j];
-                C[6 * i + 3 + j] += -KR[i][j];
-                C[6 * (3 + i) + j] += RK[i][j];
-                C[6 * (3 + i) + 3 + j] += -rkr - fr;
-            }
-        F[0] += f[0]; F[1] += f[1]; F[2] += f[2];
-        F[3] += r[1] * f[2] - r[2] * f[1];
-        F[4] += r[2] * f[0] - r[0] * f[2];
-        F[5] += r[0] * f[1] - r[1] * f[0];
-        if (T) { T[l] = q[21]; T[nL + l] = q[22]; }
-        if (J)
-#pragma unroll
-            for (int e = 0; e < 2; e++) {
-                const double *g = q + 15 + 3 * e;
-                double *o = J + (size_t)(e * nL + l) * 6;
-                o[0] = g[0]; o[1] = g[1]; o[2] = g[2];
-                o[3] = r[1] * g[2] - r[2] * g[1];
-                o[4] = r[2] * g[0] - r[0] * g[2];
-                o[5] = r[0] * g[1] - r[1] * g[0];
-            }
+        moor_line_share(q, C, F);
+        const double r[3] = {q[3], q[4], q[5]};
+        moor_line_TJ(q, l, nL, T, J);
         if (A.Lr)
 #pragma unroll
             for (int e = 0; e < 2; e++) {

@@ -1,0 +1,215 @@
+// raftx_statics.h -- the mean equilibrium pose of every design (included by raftx_hip.hip; entry point in
+// include/raftx_statics.h): Model.solveStatics for staticsMod 0 / forcingMod 0, rigid 6-DOF units with lines of their own.
+//
+//   Y(x) = F0 + F_env - K_hs (x - x_ref) + F_moor(x) = 0         K = K_hs + C_moor(x)         x <- x + K^-1 Y
+//
+// with the safeguards of raft_model.py:824-861 (a zero diagonal takes the mean diagonal; LU with partial pivoting; while
+// dX.Y < 0 the diagonal grows by 10 %, at most ten times) and the step bounds of :667 by one common factor.
+//
+// Work decomposition: k_mean_pose is ONE launch for the whole iteration of the whole batch.  A design has a group of G lanes
+// (G = the power of two at or above nLine, at most 64; a workgroup is one wavefront of 64 / G designs).  Per step the lanes of
+// a group solve the design's lines in parallel -- moor_line_record, the body of k_moor_line, cold start -- into the records lw
+// in global memory; after a workgroup barrier EVERY lane of the group gathers the records in line order (moor_line_share, the
+// sums of k_moor_design: the same bits), forms Y and K and takes the step, so the group needs no broadcast: its lanes hold the
+// same x, bit for bit.  The records cross the barrier through memory, as between k_moor_line and k_moor_design, so no
+// multiply-add is contracted across the two halves that those kernels could not contract either: C_moor, F_moor, T, J are what
+// raftx_mooring_lines returns at the returned pose.  The loop is uniform over the workgroup (__syncthreads_or): a finished
+// design idles and its state is frozen, so a design's bits depend on its own inputs only -- not on its neighbours, the batch or
+// the grid.  No atomics; the only LDS is the 256 B behind __syncthreads_or.
+#pragma once
+
+#define MP_THREADS 64
+#define MP_MAX_IT 40
+
+struct MeanPoseArgs {
+    int nDesign, nLine, G, maxIter;
+    const double *__restrict__ lines;   // [nDesign,nLine,RAFTX_ML_N]
+    const double *__restrict__ K_hs;    // [nDesign,36]
+    const double *__restrict__ F0;      // [nDesign,6]
+    const double *__restrict__ F_env;   // [nDesign,6] or null
+    const double *__restrict__ x_ref;   // [nDesign,6] or null
+    double depth, tolT, tolR;
+    double *__restrict__ lw;            // [nDesign,nLine,MOOR_LW_N]
+    double *__restrict__ pose, *__restrict__ C, *__restrict__ F, *__restrict__ T, *__restrict__ J, *__restrict__ Fres;   // each or null
+    int *__restrict__ iterations;       // [nDesign] or null
+    int *__restrict__ flags;            // [nDesign]
+};
+
+// dX = K^-1 Y by Gaussian elimination of [K | Y] with partial pivoting (the first row of the largest |a|, as LAPACK's gesv
+// behind np.linalg.solve).  Rows are exchanged by selects so that every register index is static.  Returns false for a zero or
+// non-finite pivot or a non-finite solution.
+__device__ __forceinline__ bool mp_solve(const double K[36], const double Y[6], double dX[6]) {
+    double A[6][7];
+#pragma unroll
+    for (int i = 0; i < 6; i++) {
+#pragma unroll
+        for (int j = 0; j < 6; j++) A[i][j] = K[6 * i + j];
+        A[i][6] = Y[i];
+    }
+    bool ok = true;
+#pragma unroll
+    for (int k = 0; k < 6; k++) {
+        int p = k;
+        double best = fabs(A[k][k]);
+#pragma unroll
+        for (int i = k + 1; i < 6; i++) {
+            const double a = fabs(A[i][k]);
+            if (a > best) { best = a; p = i; }
+        }
+#pragma unroll
+        for (int i = k + 1; i < 6; i++) {
+            const bool sw = p == i;
+#pragma unroll
+            for (int j = k; j < 7; j++) {
+                const double u = A[k][j], v = A[i][j];
+                A[k][j] = sw ? v : u;
+                A[i][j] = sw ? u : v;
+            }
+        }
+        ok = ok && best > 0.0 && isfinite(best);
+#pragma unroll
+        for (int i = k + 1; i < 6; i++) {
+            const double m = A[i][k] / A[k][k];
+#pragma unroll
+            for (int j = k + 1; j < 7; j++) A[i][j] = A[i][j] - m * A[k][j];
+        }
+    }
+#pragma unroll
+    for (int i = 5; i >= 0; i--) {
+        double s = A[i][6];
+#pragma unroll
+        for (int j = i + 1; j < 6; j++) s = s - A[i][j] * dX[j];
+        dX[i] = s / A[i][i];
+    }
+#pragma unroll
+    for (int i = 0; i < 6; i++) ok = ok && isfinite(dX[i]);
+    return ok;
+}
+
+__global__ void __launch_bounds__(MP_THREADS) k_mean_pose(MeanPoseArgs A) {
+    const int G = A.G, nL = A.nLine;
+    const int d = blockIdx.x * (MP_THREADS / G) + (int)threadIdx.x / G, g = (int)threadIdx.x % G;
+    const bool live = d < A.nDesign;
+    const size_t dd = live ? (size_t)d : 0;
+    double x[6], xr[6];
+#pragma unroll
+    for (int i = 0; i < 6; i++) x[i] = xr[i] = (live && A.x_ref) ? A.x_ref[dd * 6 + i] : 0.0;
+    double *lw0 = A.lw + dd * nL * MOOR_LW_N;
+    int it = 0, flag = 0;
+    int phase = live ? 0 : 2;                                    // 0 iterating, 1 converged: the outputs at x are due, 2 finished
+    for (;;) {
+        if (phase < 2)
+            for (int l = g; l < nL; l += G) {
+                double lo[MOOR_LO_N];
+                moor_line_record(A.lines + (dd * nL + l) * RAFTX_ML_N, x, A.depth, lw0 + (size_t)l * MOOR_LW_N, lo);
+            }
+        __syncthreads();                                         // the group's records are in memory
+        if (phase < 2) {
+            int mf = 0;
+            for (int l = 0; l < nL; l++) mf |= (int)lw0[(size_t)l * MOOR_LW_N + 23];
+            if (mf) {
+                flag |= mf;
+                phase = 2;
+            } else {
+                double C[36], F[6], Y[6];
+#pragma unroll
+                for (int i = 0; i < 36; i++) C[i] = 0.0;
+#pragma unroll
+                for (int i = 0; i < 6; i++) F[i] = 0.0;
+                for (int l = 0; l < nL; l++) moor_line_share(lw0 + (size_t)l * MOOR_LW_N, C, F);
+                const double *Kh = A.K_hs + dd * 36;
+#pragma unroll
+                for (int i = 0; i < 6; i++) {
+                    double acc = 0.0;
+#pragma unroll
+                    for (int j = 0; j < 6; j++) acc = acc + Kh[6 * i + j] * (x[j] - xr[j]);
+                    const double base = A.F0[dd * 6 + i] + (A.F_env ? A.F_env[dd * 6 + i] : 0.0);
+                    Y[i] = (base - acc) + F[i];
+                }
+                if (phase == 1) {                                // the outputs at the returned pose; lane 0 of the group writes
+                    if (g == 0) {
+#pragma unroll
+                        for (int i = 0; i < 6; i++) {
+                            if (A.pose) A.pose[dd * 6 + i] = x[i];
+                            if (A.F) A.F[dd * 6 + i] = F[i];
+                            if (A.Fres) A.Fres[dd * 6 + i] = Y[i];
+                        }
+                        if (A.C)
+#pragma unroll
+                            for (int i = 0; i < 36; i++) A.C[dd * 36 + i] = C[i];
+                        if (A.T || A.J)
+                            for (int l = 0; l < nL; l++)
+                                moor_line_TJ(lw0 + (size_t)l * MOOR_LW_N, l, nL, A.T ? A.T + dd * 2 * nL : nullptr,
+                                             A.J ? A.J + dd * 12 * nL : nullptr);
+                    }
+                    phase = 2;
+                } else {
+                    double K[36], dX[6];
+#pragma unroll
+                    for (int i = 0; i < 36; i++) K[i] = Kh[i] + C[i];
+                    double kmean = 0.0;
+#pragma unroll
+                    for (int i = 0; i < 6; i++) kmean = kmean + K[7 * i];
+                    kmean = kmean / 6.0;
+#pragma unroll
+                    for (int i = 0; i < 6; i++)
+                        if (K[7 * i] == 0.0) K[7 * i] = kmean;
+                    bool ok = mp_solve(K, Y, dX);
+                    for (int tries = 0; tries < 10 && ok; tries++) {
+                        double dot = 0.0;
+#pragma unroll
+                        for (int i = 0; i < 6; i++) dot = dot + dX[i] * Y[i];
+                        if (!(dot < 0.0)) break;
+#pragma unroll
+                        for (int i = 0; i < 6; i++) K[7 * i] = K[7 * i] + 0.1 * fabs(K[7 * i]);
+                        ok = mp_solve(K, Y, dX);
+                    }
+                    if (!ok) {
+                        flag |= RAFTX_STATICS_SINGULAR;
+                        phase = 2;
+                    } else {
+                        const double cap[6] = {30.0, 30.0, 5.0, 0.1, 0.1, 0.1};
+                        double s = 1.0;
+#pragma unroll
+                        for (int i = 0; i < 6; i++)
+                            if (fabs(dX[i]) * s > cap[i]) s = cap[i] / fabs(dX[i]);
+                        bool conv = true;
+#pragma unroll
+                        for (int i = 0; i < 6; i++) {
+                            dX[i] = dX[i] * s;
+                            conv = conv && fabs(dX[i]) <= (i < 3 ? A.tolT : A.tolR);
+                            x[i] = x[i] + dX[i];
+                        }
+                        it++;
+                        if (conv) phase = 1;
+                        else if (it >= A.maxIter) {
+                            flag |= RAFTX_STATICS_POSE_CAP;
+                            phase = 2;
+                        }
+                    }
+                }
+            }
+        }
+        if (!__syncthreads_or(phase < 2)) break;                 // (also: every lane has read the records before they are rewritten)
+    }
+    if (!live || g != 0) return;
+    A.flags[d] = flag;
+    if (A.iterations) A.iterations[d] = it;
+    if (flag) {                                                  // a flagged design: NaN, in its own rows only
+        const double nan = __longlong_as_double(0x7ff8000000000000LL);
+        for (int i = 0; i < 6; i++) {
+            if (A.pose) A.pose[dd * 6 + i] = nan;
+            if (A.F) A.F[dd * 6 + i] = nan;
+            if (A.Fres) A.Fres[dd * 6 + i] = nan;
+        }
+        if (A.C) for (int i = 0; i < 36; i++) A.C[dd * 36 + i] = nan;
+        if (A.T) for (int i = 0; i < 2 * nL; i++) A.T[dd * 2 * nL + i] = nan;
+        if (A.J) for (int i = 0; i < 12 * nL; i++) A.J[dd * 12 * nL + i] = nan;
+    }
+}
+
+static inline int mean_pose_group(int nLine) {
+    int G = 1;
+    while (G < nLine && G < MP_THREADS) G *= 2;
+    return G;
+}

@@ -1,0 +1,70 @@
+"""The mean equilibrium pose of every design on the device (include/raftx_statics.h): Model.solveStatics for staticsMod 0 /
+forcingMod 0, rigid 6-DOF units with mooring lines of their own.
+
+``hydrostatics(ctx, ...)`` assembles K_hs and F0 of the resident design set from raftx_fetch_statics and the caller's
+terms that do not come from the geometry; ``mean_pose(ctx, ...)`` runs the one-launch Newton solve and returns a
+``MeanPose``.
+"""
+import numpy as np
+
+from . import mooring
+
+FLAG_POSE_CAP, FLAG_SINGULAR = 16, 32
+FLAG_NAMES = {mooring.FLAG_BAD_LINE: "bad line", mooring.FLAG_VERTICAL: "vertical line", mooring.FLAG_SLACK: "slack line",
+              mooring.FLAG_NO_CONVERGENCE: "line not converged", FLAG_POSE_CAP: "pose iteration cap", FLAG_SINGULAR: "singular system"}
+
+
+class MeanPose:
+    """Result of ``mean_pose``: pose [nD,6] (m, rad), C_moor [nD,6,6], F_moor [nD,6], T [nD,2 nLine] (ends A, then ends
+    B), J [nD,2 nLine,6], F_res [nD,6] (the residual at the pose), iterations [nD], flags [nD].  A flagged design's rows
+    are NaN."""
+
+    def __init__(self, res):
+        self.pose, self.C_moor, self.F_moor = res["pose"], res["C"], res["F"]
+        self.T, self.J, self.F_res = res["T"], res["J"], res["F_res"]
+        self.iterations, self.flags = res["iterations"], res["flags"]
+
+    @property
+    def ok(self):
+        """[nD] bool: the design converged and none of its lines was flagged."""
+        return self.flags == 0
+
+    def describe_flags(self, d):
+        return [name for bit, name in FLAG_NAMES.items() if int(self.flags[d]) & bit]
+
+
+def hydrostatics(ctx, C_extra=None, F_extra=None, current=None):
+    """(K_hs [nD,6,6], F0 [nD,6], F_env [nD,6] or None) of the resident design set (after a design build):
+    K_hs = C_struc + C_hydro + ``C_extra`` (the elastic stiffness, the turbine's share, ...), F0 = W_struc + W_hydro +
+    ``F_extra`` (f0_additional, the turbine's weight, ...), each extra [6,6] / [6] or per design.  ``current`` =
+    dict(speed=, heading=, depth=, Zref=None, shearExp=0.12) makes the library evaluate the mean current load of that ONE
+    current (raftx_current_loads) and return it as F_env."""
+    st = ctx.fetch_statics()
+    K_hs = st["C_struc"] + st["C_hydro"]
+    F0 = st["W_struc"] + st["W_hydro"]
+    if C_extra is not None:
+        K_hs = K_hs + np.asarray(C_extra, dtype=float)
+    if F_extra is not None:
+        F0 = F0 + np.asarray(F_extra, dtype=float)
+    F_env = None
+    if current is not None:
+        cur = dict(current)
+        D = ctx.current_loads([float(cur.pop("speed"))], [float(cur.pop("heading"))], float(cur.pop("depth")), **cur)
+        F_env = np.ascontiguousarray(D[:, 0, :])
+    return np.ascontiguousarray(K_hs), np.ascontiguousarray(F0), F_env
+
+
+def mean_pose(ctx, K_hs, F0, lines=None, depth=None, program=None, params=None, F_env=None, x_ref=None, tol=None, max_iter=0):
+    """Newton's iteration on F0 + F_env - K_hs (x - x_ref) + F_moor(x) = 0 for every design in one launch.  Give either
+    ``lines`` [nD,nLine,16] (raft_amd.mooring.lines_from_design), or ``program`` (a MooringProgram, installed here unless it already is;
+    None keeps the installed one) with ``params`` [nD,nParam].  ``tol`` = (m, rad), None: 1e-9, 1e-10."""
+    if depth is None:
+        raise ValueError("mean_pose: the water depth is required")
+    if lines is None:
+        if params is None:
+            raise ValueError("mean_pose: give lines, or a mooring program's params")
+        if program is not None and getattr(ctx, "_mprog_owner", None) is not program:
+            ctx.mooring_program(program)
+    elif params is not None or program is not None:
+        raise ValueError("mean_pose: lines and a mooring program exclude each other")
+    return MeanPose(ctx.mean_pose(K_hs, F0, depth, lines=lines, params=params, F_env=F_env, x_ref=x_ref, tol=tol, max_iter=max_iter))
