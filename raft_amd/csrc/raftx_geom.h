@@ -393,8 +393,11 @@ __device__ inline double geom_interp_inner(double x, const double *gs, int n, in
 }
 // M += translateMatrix6to6DOF(diag(m,m,m) (+) I_rot, r) with I_rot = Ix p1p1^T + Iy p2p2^T + Iz qq^T
 // (helpers.py:563-585, raft_member.py:507-516): [[m I, m H],[m H^T, m H H^T + I_rot]], H = getH(r)
+// whole: the sub-member of a zero-length section.  The reference builds its matrix with np.diag of the INTEGER mass 0
+// (raft_member.py:417,531) -- an integer array -- so the I_rot stored into it (:537) keeps the whole part of every entry only,
+// rounded towards zero.
 __device__ inline void geom_add_submember(double *M, double mass, const double (&Iv)[3], const double *p1, const double *p2,
-                                          const double *q, const double (&r)[3]) {
+                                          const double *q, const double (&r)[3], bool whole = false) {
     GEOM_NOFMA
     const double H[3][3] = {{0, r[2], -r[1]}, {-r[2], 0, r[0]}, {r[1], -r[0], 0}};
     for (int i = 0; i < 3; i++)
@@ -404,13 +407,14 @@ __device__ inline void geom_add_submember(double *M, double mass, const double (
             M[i * 6 + j] += (i == j) ? mass : 0.0;
             M[i * 6 + 3 + j] += mass * H[i][j];
             M[(3 + i) * 6 + j] += mass * H[j][i];
-            M[(3 + i) * 6 + 3 + j] += hh + (p1[i] * Iv[0] * p1[j] + p2[i] * Iv[1] * p2[j] + q[i] * Iv[2] * q[j]);
+            const double ir = p1[i] * Iv[0] * p1[j] + p2[i] * Iv[1] * p2[j] + q[i] * Iv[2] * q[j];
+            M[(3 + i) * 6 + 3 + j] += hh + (whole ? trunc(ir) : ir);
         }
 }
 
 // Member.getInertia + getWeight, rigid branch, about the member's own node (raft_member.py:380-836, 1179-1181).
-// Zero-length sections re-add the local inertia tensor of the previous section with zero mass, as the reference
-// does (Ixx, Iyy, Izz are not reset between sections, :420-513).  Returns a non-zero code for cap layouts the
+// Zero-length sections re-add the local inertia tensor of the previous section with zero mass and as whole numbers, as the
+// reference does (Ixx, Iyy, Izz are not reset between sections, :420-513; geom_add_submember).  Returns a non-zero code for cap layouts the
 // reference itself cannot handle.
 // The running sums of Member.getInertia over the sections and caps of one member.  In pieces, so that the member pass can feed
 // the sections from station rows it holds in registers (one pass over the stations for wet strips, hydrostatics and
@@ -473,7 +477,7 @@ __device__ inline void geom_inertia_section(GInertia &J, const double *a, const 
         }
         double rel[3];
         for (int c = 0; c < 3; c++) { mc[c] += mass * center[c]; rel[c] = center[c] - rA[c]; }
-        geom_add_submember(M, mass, I3, p1, p2, q, rel);
+        geom_add_submember(M, mass, I3, p1, p2, q, rel, !(l > 0));
     }
 }
 // the caps and bulkheads of the member (station table in memory: the interpolations look stations up by position), then the

@@ -1598,7 +1598,8 @@ static int enqueue_generation(raftx_ctx *c, hipStream_t sGen, int kind) {
     J.gen_deferred = false;
     const size_t gd_lds = geom_design_lds(J.maxS, (int)J.maxSta, (int)J.maxMem);
     if (gd_lds > 160 * 1024)
-        FAIL(c, "build_designs: a design has %d submerged strips (at most %d supported)", J.maxS, (int)((160 * 1024 - 16) / (8 * (GD_ROW + 2) + 12)));
+        FAIL(c, "build_designs: designs of up to %d submerged strips, %d stations and %d members need %zu B of LDS in k_geom_design, 160 KiB available",
+             J.maxS, (int)J.maxSta, (int)J.maxMem, gd_lds);
     if (gd_lds > 64 * 1024)
         HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void *>(k_geom_design), hipFuncAttributeMaxDynamicSharedMemorySize, (int)gd_lds));
     J.gen_lds = gd_lds;

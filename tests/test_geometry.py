@@ -59,6 +59,8 @@ def check_unit(ctx, u, tol):
     # mass / inertia / weight of the members alone (live reference with a massless RNA and no point inertias).
     # M_struc carries FrustumMOI's ill-conditioned tapered branch for caps whose hole is "tapered" by one rounding
     # error (OC4semi heave-plate bulkheads): agreement there hinges on the last bit of r**5, hence the looser gate.
+    # (tests/test_geom_reference.py / test_hip_geom_reference.py hold the same entries to a derived envelope instead: there the
+    # ill-conditioned quotient widens its own entries only, and every other entry is gated at a few rounding errors)
     assert rel_err(S["M_struc"][0], u["M_struc_bare"]) < max(tol, 2e-9), u["name"]
     assert rel_err(S["C_struc"][0], u["C_struc_bare"]) < tol
     assert rel_err(S["W_struc"][0], u["W_struc_bare"]) < tol
