@@ -540,9 +540,10 @@ int raftx_sweep_cancel(raftx_ctx *ctx, int slot);
  * Parametric VARIANTS of one base unit, expanded on the device (raft/parametersweep.py:39-87: a sweep edits a handful of
  * parameters per candidate -- column diameters, draft, column radius, pontoon height -- and the dependent geometry
  * follows).  The host describes the base unit once and, per candidate, sends only its nParam parameter values; the
- * library writes each candidate's member / station / cap descriptors in HBM (k_geom_expand) and goes on as
- * raftx_sweep_prepare does.  Per batch of 10^4 candidates: 0.4 MB of parameters instead of 66 MB of descriptors, and no
- * host work per candidate.
+ * library evaluates each candidate's member / station / cap descriptors from the base unit's rows where its kernels read
+ * them -- a crossing keeps no descriptor in HBM (only with RAFTX_FUSED_GEN=1 set when it is prepared are they written
+ * there, by k_geom_expand) -- and goes on as raftx_sweep_prepare does.  Per batch of 10^4 candidates: 0.4 MB of parameters
+ * instead of 66 MB of descriptors, and no host work per candidate.
  *
  * raftx_variant_program: the base unit's descriptors (as raftx_build_designs takes them, ONE design: nMember members,
  *   stationOff / capOff [nMember+1], capOff / caps may be NULL) and the edit program.  Edits are AFFINE in the parameters:

@@ -125,6 +125,18 @@ __host__ __device__ inline void derive_design_tables(const double *strips, int64
 }
 
 // ---------------------------------------------------------------------------------------------------------
+// The edit program of parametric variants of one base unit (raftx_variant_program), as the device sees it: the base
+// unit's rows, the affine edits, and the parameter rows of the designs at hand.  Design d is the base unit with the edits
+// evaluated at params[d]; its member m, station row and cap row are base member m % nM and the base rows of that member.
+struct VariantView {
+    int nM, nSt, nCap, nP;
+    const double *params;                                    // [n,nP]
+    const double *gm, *gs, *gc;                              // base rows
+    const int *stMember, *capMember;                         // base member of every base station / cap row
+    const double *stFrac, *fillFrac, *capFrac;               // positions as fractions of the member length
+    const double *endCoef, *headCS, *diaCoef;                // [nM,6,nP+1] [nM,2] [nSt,2,nP+1]
+    const int *endEdit, *diaEdit;                            // [nM] [nSt]
+};
 struct GeomArgs {
     int nDesign;
     int64_t nMember;
@@ -171,12 +183,138 @@ struct GeomArgs {
     const double *fixRec;        // [nFix,FR_N]
     const int *fixInt, *fixIdx;  // [nFix,FR_I] [fixNM]
     int fixNM;
+    // The job's variant program, rows on read (prog.params != null): gm, gs and caps are null, the designs are prog.nM
+    // members each with the program's uniform offsets, and the member pass, the ballast trim and the table generation
+    // evaluate a row where they load it (GeomRowsProg) from the base row and the block's parameter rows.  null: the job's
+    // rows are in gm / gs / caps (the caller's, or written by k_geom_expand).
+    VariantView prog;
     __device__ int64_t mo(int d) const { return memberOff[d] - mbase; }
     __device__ int64_t so(int64_t m) const { return stationOff[m] - sbase; }
     __device__ int64_t co(int64_t m) const { return capOff[m] - cbase; }
 };
 
 #define GEOM_NOFMA _Pragma("clang fp contract(off)")
+
+// ---- The rows of a variant from the base rows and the edits (raft/parametersweep.py:39-87 edits a handful of parameters
+// per candidate and the dependent geometry follows): the member's end points as affine functions of the parameters, its
+// length (raft_member.py:72), the heading rotation (:75-77, helpers.py:587-602), station / ballast / cap positions as
+// fractions of the length (:99,143,173), diameters as affine functions.  Every expression is evaluated like the host's
+// NumPy form -- left to right, no fused multiply-add -- so that the rows are the bits raft_amd/geometry.py SweepTables
+// produces (tests/test_geometry.py).  ONE source for them: k_geom_expand writes rows with these functions, and the
+// readers of a job that keeps no rows (GeomRowsProg, geom_design_block) patch the base row they have loaded with them.
+__device__ __forceinline__ double affine_eval(const double *coef, const double *p, int nP) {
+    GEOM_NOFMA
+    double v = coef[0];
+    for (int q = 0; q < nP; q++) v = v + coef[1 + q] * p[q];
+    return v;
+}
+// the six end coordinates (before the heading rotation) and the length of base member m at the parameter row p
+__device__ __forceinline__ void variant_ends(const VariantView &V, int m, const double *p, double (&e)[6], double &L) {
+    GEOM_NOFMA
+    for (int i = 0; i < 6; i++) e[i] = affine_eval(V.endCoef + ((size_t)m * 6 + i) * (V.nP + 1), p, V.nP);
+    const double dx = e[3] - e[0], dy = e[4] - e[1], dz = e[5] - e[2];
+    L = sqrt((dx * dx + dy * dy) + dz * dz);                 // |rB - rA| before the heading rotation (raft_member.py:72)
+}
+// the edited columns of the row o of an end-edited member m: heading rotation of rA and rB, and L
+template <class Row>
+__device__ __forceinline__ void variant_member_edit(const VariantView &V, int m, const double (&e)[6], double L, Row &o) {
+    GEOM_NOFMA
+    const double c = V.headCS[2 * m], s = V.headCS[2 * m + 1];
+    o[RAFTX_GM_RA + 0] = c * e[0] + (-s) * e[1];
+    o[RAFTX_GM_RA + 1] = s * e[0] + c * e[1];
+    o[RAFTX_GM_RA + 2] = e[2];
+    o[RAFTX_GM_RB + 0] = c * e[3] + (-s) * e[4];
+    o[RAFTX_GM_RB + 1] = s * e[3] + c * e[4];
+    o[RAFTX_GM_RB + 2] = e[5];
+    o[RAFTX_GM_L] = L;
+}
+// the edits of base station row idx: positions of a member with edited ends (ed; L its length), diameters where diaEdit
+__device__ __forceinline__ double variant_station_S(const VariantView &V, int idx, double L) {
+    GEOM_NOFMA
+    return V.stFrac[idx] * L;
+}
+__device__ __forceinline__ double variant_station_LFILL(const VariantView &V, int idx, double L) {
+    GEOM_NOFMA
+    return V.fillFrac[idx] * L;
+}
+__device__ __forceinline__ double variant_station_D(const VariantView &V, int idx, int c, const double *p) {
+    return affine_eval(V.diaCoef + ((size_t)idx * 2 + c) * (V.nP + 1), p, V.nP);
+}
+template <class Row>
+__device__ __forceinline__ void variant_station_edit(const VariantView &V, int idx, bool ed, double L, const double *p, Row &o) {
+    if (ed) {
+        o[RAFTX_GS_S] = variant_station_S(V, idx, L);
+        o[RAFTX_GS_LFILL] = variant_station_LFILL(V, idx, L);
+    }
+    if (V.diaEdit[idx]) {
+        o[RAFTX_GS_D] = variant_station_D(V, idx, 0, p);
+        o[RAFTX_GS_D + 1] = variant_station_D(V, idx, 1, p);
+    }
+}
+// the edit of base cap row idx of a member with edited ends
+__device__ __forceinline__ double variant_cap_S(const VariantView &V, int idx, double L) {
+    GEOM_NOFMA
+    return V.capFrac[idx] * L;
+}
+
+// a station row into registers: eight 16-byte loads, all in flight together (rows are 128-byte records of 16-byte-aligned
+// tables)
+__device__ __forceinline__ void geom_load_row(const double *gs, int i, double (&r)[RAFTX_GS_N]) {
+    const double2 *p = reinterpret_cast<const double2 *>(gs + (size_t)i * RAFTX_GS_N);
+#pragma unroll
+    for (int k = 0; k < RAFTX_GS_N / 2; k++) {
+        const double2 v = p[k];
+        r[2 * k] = v.x;
+        r[2 * k + 1] = v.y;
+    }
+}
+static_assert(RAFTX_GM_N == RAFTX_GS_N, "member and station rows are loaded alike");
+// Where the member pass and the ballast trim take ONE member's rows from: its member row, its n station rows, its caps.
+// Rows in memory (the caller's, k_geom_expand's, the program's base rows for k_geom_member_fixed) ...
+struct GeomRowsPlain {
+    const double *gmrow, *gs, *gc;
+    __device__ __forceinline__ void member(double (&gm)[RAFTX_GM_N]) const { geom_load_row(gmrow, 0, gm); }
+    __device__ __forceinline__ double mcol(int f) const { return gmrow[f]; }                       // a member column no edit touches
+    __device__ __forceinline__ void station(int i, double (&r)[RAFTX_GS_N]) const { geom_load_row(gs, i, r); }
+    __device__ __forceinline__ double st(int j, int f) const { return gs[(size_t)j * RAFTX_GS_N + f]; }
+    __device__ __forceinline__ double cap(int i, int f) const { return gc[(size_t)i * RAFTX_GC_N + f]; }
+};
+// ... or base member bm of the job's program at the parameter row of design d, rows evaluated on read: the base row is loaded
+// as a row in memory is (the same eight 16-byte loads in flight together) and the edited columns are patched with the
+// functions k_geom_expand writes rows with.  The member's ends and L are evaluated once, here.  s0 / c0: the member's
+// first base station / cap row.  In the (member position, design) layout of the member kernels (GeomArgs::mgrid) every
+// base-row address is the same for the 64 lanes of a wave: one line per load where the written rows took 64.
+struct GeomRowsProg {
+    const VariantView V;
+    const double *p;
+    int bm, s0, c0;
+    bool ed;
+    double e[6], L;
+    __device__ __forceinline__ GeomRowsProg(const VariantView &V_, int bm_, int s0_, int c0_, int d)
+        : V(V_), p(V_.params + (size_t)d * V_.nP), bm(bm_), s0(s0_), c0(c0_), ed(V_.endEdit[bm_] != 0), e{0, 0, 0, 0, 0, 0}, L(0.0) {
+        if (ed) variant_ends(V, bm, p, e, L);
+    }
+    __device__ __forceinline__ void member(double (&gm)[RAFTX_GM_N]) const {
+        geom_load_row(V.gm, bm, gm);
+        if (ed) variant_member_edit(V, bm, e, L, gm);
+    }
+    __device__ __forceinline__ double mcol(int f) const { return V.gm[(size_t)bm * RAFTX_GM_N + f]; }
+    __device__ __forceinline__ void station(int i, double (&r)[RAFTX_GS_N]) const {
+        geom_load_row(V.gs, s0 + i, r);
+        variant_station_edit(V, s0 + i, ed, L, p, r);
+    }
+    __device__ __forceinline__ double st(int j, int f) const {
+        const int idx = s0 + j;
+        if (f == RAFTX_GS_S && ed) return variant_station_S(V, idx, L);
+        if (f == RAFTX_GS_LFILL && ed) return variant_station_LFILL(V, idx, L);
+        if ((f == RAFTX_GS_D || f == RAFTX_GS_D + 1) && V.diaEdit[idx]) return variant_station_D(V, idx, f - RAFTX_GS_D, p);
+        return V.gs[(size_t)idx * RAFTX_GS_N + f];
+    }
+    __device__ __forceinline__ double cap(int i, int f) const {
+        if (f == RAFTX_GC_S && ed) return variant_cap_S(V, c0 + i, L);
+        return V.gc[(size_t)(c0 + i) * RAFTX_GC_N + f];
+    }
+};
 
 // numpy.interp for one abscissa over the station table (clamped; an exact hit on a repeated station returns the
 // LAST of the repeats, as numpy's binary search does) -- raft_member.py:1315-1318, 2061-2064
@@ -375,22 +513,29 @@ __device__ inline void geom_rect_moi(double La, double Wa, double Lb, double Wb,
     Iv[0] = y2 + z2; Iv[1] = x2 + z2; Iv[2] = x2 + y2;
 }
 // inner diameter / side length (d - 2t) along the member, np.interp semantics (raft_member.py:667,727)
-__device__ inline double geom_interp_inner(double x, const double *gs, int n, int c) {
+template <class Rows>
+__device__ __forceinline__ double geom_interp_inner_body(double x, const Rows &R, int n, int c) {
     GEOM_NOFMA
-#define DIN_(j) (gs[(size_t)(j) * RAFTX_GS_N + RAFTX_GS_D + c] - 2 * gs[(size_t)(j) * RAFTX_GS_N + RAFTX_GS_T])
-    if (x < gs[RAFTX_GS_S]) return DIN_(0);
-    if (x > gs[(size_t)(n - 1) * RAFTX_GS_N + RAFTX_GS_S]) return DIN_(n - 1);
+#define DIN_(j) (R.st(j, RAFTX_GS_D + c) - 2 * R.st(j, RAFTX_GS_T))
+    if (x < R.st(0, RAFTX_GS_S)) return DIN_(0);
+    if (x > R.st(n - 1, RAFTX_GS_S)) return DIN_(n - 1);
     int j = 0;
     for (int i = 0; i < n; i++)
-        if (gs[(size_t)i * RAFTX_GS_N + RAFTX_GS_S] <= x) j = i;
+        if (R.st(i, RAFTX_GS_S) <= x) j = i;
     const double fj = DIN_(j);
     if (j == n - 1) return fj;
-    const double xj = gs[(size_t)j * RAFTX_GS_N + RAFTX_GS_S];
+    const double xj = R.st(j, RAFTX_GS_S);
     if (xj == x) return fj;
-    const double slope = (DIN_(j + 1) - fj) / (gs[(size_t)(j + 1) * RAFTX_GS_N + RAFTX_GS_S] - xj);
+    const double slope = (DIN_(j + 1) - fj) / (R.st(j + 1, RAFTX_GS_S) - xj);
     return slope * (x - xj) + fj;
 #undef DIN_
 }
+// (rows in memory: a function of its own, as it has always been.  Rows on read: inlined into the caller -- a GeomRowsProg that is
+// passed on by address would have to live in scratch memory; for the same reason it holds the view by value, not a reference
+// into the kernel's arguments, which cost k_geom_member a 544-byte copy of them per lane)
+template <class Rows>
+__device__ inline double geom_interp_inner(double x, const Rows &R, int n, int c) { return geom_interp_inner_body(x, R, n, c); }
+__device__ __forceinline__ double geom_interp_inner(double x, const GeomRowsProg &R, int n, int c) { return geom_interp_inner_body(x, R, n, c); }
 // M += translateMatrix6to6DOF(diag(m,m,m) (+) I_rot, r) with I_rot = Ix p1p1^T + Iy p2p2^T + Iz qq^T
 // (helpers.py:563-585, raft_member.py:507-516): [[m I, m H],[m H^T, m H H^T + I_rot]], H = getH(r)
 // whole: the sub-member of a zero-length section.  The reference builds its matrix with np.diag of the INTEGER mass 0
@@ -482,58 +627,58 @@ __device__ inline void geom_inertia_section(GInertia &J, const double *a, const 
 }
 // the caps and bulkheads of the member (station table in memory: the interpolations look stations up by position), then the
 // totals into out[MI_N].  Non-zero: a cap layout the reference itself cannot handle.
-__device__ inline int geom_inertia_caps_finish(GInertia &J, const double *gs, int n, const double *gc, int ncap, bool circ,
-                                               double rho_shell, const double *rA, const double *q, const double *p1,
-                                               const double *p2, double g, double *out) {
+template <class Rows>
+__device__ __forceinline__ int geom_inertia_caps_body(GInertia &J, const Rows &R, int n, int ncap, bool circ,
+                                                      double rho_shell, const double *rA, const double *q, const double *p1,
+                                                      const double *p2, double g, double *out) {
     GEOM_NOFMA
     const int c1 = circ ? 0 : 1;
     double (&M)[36] = J.M;
     double (&mc)[3] = J.mc;
     const double vfill = J.vfill;
-    const double s0 = gs[RAFTX_GS_S], s1 = gs[(size_t)(n - 1) * RAFTX_GS_N + RAFTX_GS_S];
+    const double s0 = R.st(0, RAFTX_GS_S), s1 = R.st(n - 1, RAFTX_GS_S);
     for (int i = 0; i < ncap; i++) {
-        const double *cp = gc + (size_t)i * RAFTX_GC_N;
-        const double Lc = cp[RAFTX_GC_S], h = cp[RAFTX_GC_T];
+        const double Lc = R.cap(i, RAFTX_GC_S), h = R.cap(i, RAFTX_GC_T);
         double dA[2] = {0, 0}, dB[2] = {0, 0}, dAi[2] = {0, 0}, dBi[2] = {0, 0};
         int where;                                       // 0 bottom, 1 top, 2 middle
         if (Lc == s0) {
             where = 0;
             for (int c = 0; c <= c1; c++) {
-                dA[c] = gs[RAFTX_GS_D + c] - 2 * gs[RAFTX_GS_T];
-                dB[c] = geom_interp_inner(Lc + h, gs, n, c);
-                dAi[c] = cp[RAFTX_GC_DIN + c];
+                dA[c] = R.st(0, RAFTX_GS_D + c) - 2 * R.st(0, RAFTX_GS_T);
+                dB[c] = geom_interp_inner(Lc + h, R, n, c);
+                dAi[c] = R.cap(i, RAFTX_GC_DIN + c);
                 dBi[c] = dB[c] * (dAi[c] / dA[c]);
             }
         } else if (Lc == s1) {
             where = 1;
             if (!circ) return 2;                         // the reference fails here (slBi used before assignment, :731-735)
-            dA[0] = geom_interp_inner(Lc - h, gs, n, 0);
-            dB[0] = gs[(size_t)(n - 1) * RAFTX_GS_N + RAFTX_GS_D] - 2 * gs[(size_t)(n - 1) * RAFTX_GS_N + RAFTX_GS_T];
-            dBi[0] = cp[RAFTX_GC_DIN];
+            dA[0] = geom_interp_inner(Lc - h, R, n, 0);
+            dB[0] = R.st(n - 1, RAFTX_GS_D) - 2 * R.st(n - 1, RAFTX_GS_T);
+            dBi[0] = R.cap(i, RAFTX_GC_DIN);
             dAi[0] = dA[0] * (dBi[0] / dB[0]);
         } else if ((Lc > s0 && Lc < s0 + h) || (Lc < s1 && Lc > s1 - h)) {
             return 3;                                    // ValueError('This setup cannot be handled by getIneria yet')
         } else {
             where = 2;
             if (!circ) return 2;                         // np.interp on a 2-D table raises in the reference (:741-755)
-            if (i < ncap - 1 && Lc == gc[(size_t)(i + 1) * RAFTX_GC_N + RAFTX_GC_S]) {         // discontinuity: cap going down
+            if (i < ncap - 1 && Lc == R.cap(i + 1, RAFTX_GC_S)) {         // discontinuity: cap going down
                 if (i >= n) return 4;
-                dA[0] = geom_interp_inner(Lc - h, gs, n, 0);
-                dB[0] = gs[(size_t)i * RAFTX_GS_N + RAFTX_GS_D] - 2 * gs[(size_t)i * RAFTX_GS_N + RAFTX_GS_T];   // (sic) d[i] with the CAP index, :690
-                dBi[0] = cp[RAFTX_GC_DIN];
+                dA[0] = geom_interp_inner(Lc - h, R, n, 0);
+                dB[0] = R.st(i, RAFTX_GS_D) - 2 * R.st(i, RAFTX_GS_T);   // (sic) d[i] with the CAP index, :690
+                dBi[0] = R.cap(i, RAFTX_GC_DIN);
                 dAi[0] = dA[0] * (dBi[0] / dB[0]);
-            } else if (i > 0 && Lc == gc[(size_t)(i - 1) * RAFTX_GC_N + RAFTX_GC_S]) {       // ... and one going up
+            } else if (i > 0 && Lc == R.cap(i - 1, RAFTX_GC_S)) {       // ... and one going up
                 if (i >= n) return 4;
-                dA[0] = gs[(size_t)i * RAFTX_GS_N + RAFTX_GS_D] - 2 * gs[(size_t)i * RAFTX_GS_N + RAFTX_GS_T];
-                dB[0] = geom_interp_inner(Lc + h, gs, n, 0);
-                dAi[0] = cp[RAFTX_GC_DIN];
+                dA[0] = R.st(i, RAFTX_GS_D) - 2 * R.st(i, RAFTX_GS_T);
+                dB[0] = geom_interp_inner(Lc + h, R, n, 0);
+                dAi[0] = R.cap(i, RAFTX_GC_DIN);
                 dBi[0] = dB[0] * (dAi[0] / dA[0]);
             } else {
-                dA[0] = geom_interp_inner(Lc - h / 2, gs, n, 0);
-                dB[0] = geom_interp_inner(Lc + h / 2, gs, n, 0);
-                const double dM = geom_interp_inner(Lc, gs, n, 0);
-                dAi[0] = dA[0] * (cp[RAFTX_GC_DIN] / dM);
-                dBi[0] = dB[0] * (cp[RAFTX_GC_DIN] / dM);
+                dA[0] = geom_interp_inner(Lc - h / 2, R, n, 0);
+                dB[0] = geom_interp_inner(Lc + h / 2, R, n, 0);
+                const double dM = geom_interp_inner(Lc, R, n, 0);
+                dAi[0] = dA[0] * (R.cap(i, RAFTX_GC_DIN) / dM);
+                dBi[0] = dB[0] * (R.cap(i, RAFTX_GC_DIN) / dM);
             }
         }
         double Vo, hco, Vi, hci;
@@ -582,16 +727,33 @@ __device__ inline int geom_inertia_caps_finish(GInertia &J, const double *gs, in
     out[47] = vfill;                                                                 // member.vfill summed (raft_member.py:506)
     return 0;
 }
-__device__ inline int geom_member_inertia(const double *gm, const double *gs, int n, const double *gc, int ncap,
-                                          const double *rA, const double *q, const double *p1, const double *p2, double g,
-                                          bool trim, double drho, double *out) {
-    const bool circ = gm[RAFTX_GM_SHAPE] != 0.0;
-    const double rho_shell = gm[RAFTX_GM_RHOSHELL];
+template <class Rows>
+__device__ inline int geom_inertia_caps_finish(GInertia &J, const Rows &R, int n, int ncap, bool circ, double rho_shell, const double *rA,
+                                               const double *q, const double *p1, const double *p2, double g, double *out) {
+    return geom_inertia_caps_body(J, R, n, ncap, circ, rho_shell, rA, q, p1, p2, g, out);
+}
+__device__ __forceinline__ int geom_inertia_caps_finish(GInertia &J, const GeomRowsProg &R, int n, int ncap, bool circ, double rho_shell,
+                                                        const double *rA, const double *q, const double *p1, const double *p2, double g,
+                                                        double *out) {
+    return geom_inertia_caps_body(J, R, n, ncap, circ, rho_shell, rA, q, p1, p2, g, out);
+}
+// (the ballast trim's second pass over a member, k_geom_reinertia: the rows through the same loader as the member pass)
+template <class Rows>
+__device__ __forceinline__ int geom_member_inertia(const Rows &R, int n, int ncap, const double *rA, const double *q, const double *p1,
+                                                   const double *p2, double g, bool trim, double drho, double *out) {
+    const bool circ = R.mcol(RAFTX_GM_SHAPE) != 0.0;
+    const double rho_shell = R.mcol(RAFTX_GM_RHOSHELL);
     GInertia J;
     geom_inertia_init(J);
-    for (int i = 1; i < n; i++)
-        geom_inertia_section(J, gs + (size_t)(i - 1) * RAFTX_GS_N, gs + (size_t)i * RAFTX_GS_N, circ, rho_shell, trim, drho, rA, q, p1, p2);
-    return geom_inertia_caps_finish(J, gs, n, gc, ncap, circ, rho_shell, rA, q, p1, p2, g, out);
+    double a[RAFTX_GS_N], b[RAFTX_GS_N];
+    R.station(0, b);
+    for (int i = 1; i < n; i++) {
+#pragma unroll
+        for (int f = 0; f < RAFTX_GS_N; f++) a[f] = b[f];
+        R.station(i, b);
+        geom_inertia_section(J, a, b, circ, rho_shell, trim, drho, rA, q, p1, p2);
+    }
+    return geom_inertia_caps_finish(J, R, n, ncap, circ, rho_shell, rA, q, p1, p2, g, out);
 }
 
 // one thread per member: pose, wet-strip count, hydrostatics and inertia about the member's own node
@@ -609,7 +771,8 @@ __global__ void k_geom_zero(GeomArgs A) {
     if (d == 0) { A.off[0] = 0; A.cmoff[0] = 0; }
     // design index of every member (the host has checked that the member offsets are monotone and in range): this used
     // to be a kernel of its own between this one and the member pass, i.e. on the path between two batches
-    if (d < A.nDesign)
+    // (a job that reads its rows from the program has uniform designs: d = m / nM, and nobody reads mdesign)
+    if (d < A.nDesign && !A.prog.params)
         for (int64_t m = A.mo(d); m < A.mo(d + 1); m++) A.mdesign_w[m] = d;
 }
 #define GEOM_MAX_STATIONS 1024
@@ -625,17 +788,6 @@ __device__ inline int64_t geom_member_of_thread(const GeomArgs &A) {
     const int d = (int)(t % A.nDesign);
     const int64_t m = A.mo(d) + k;
     return m < A.mo(d + 1) ? m : -1;
-}
-// a station row into registers: eight 16-byte loads, all in flight together (rows are 128-byte records of 16-byte-aligned
-// tables)
-__device__ __forceinline__ void geom_load_row(const double *gs, int i, double (&r)[RAFTX_GS_N]) {
-    const double2 *p = reinterpret_cast<const double2 *>(gs + (size_t)i * RAFTX_GS_N);
-#pragma unroll
-    for (int k = 0; k < RAFTX_GS_N / 2; k++) {
-        const double2 v = p[k];
-        r[2 * k] = v.x;
-        r[2 * k + 1] = v.y;
-    }
 }
 // What the member pass computes for ONE member, from its rows alone: pose, wet-strip counts, hydrostatics and inertia
 // into mp [MP_N], mh [MH_N], mi [MI_N], and what the caller has to record -- the counts, the inertia's return code, a
@@ -690,21 +842,15 @@ __device__ __forceinline__ void geom_pose(const double *gm, const double (&ps)[6
 }
 #define FR_N (MP_N + MH_N + MI_N) // doubles of a fixed member's record: mp | mh | mi
 #define FR_I 4                    // ints of it: the four of GMember
-__device__ __forceinline__ GMember geom_member_body(const double *gmrow, const double *gs, const int n, const double *gc, const int ncap,
-                                                    const double *pose, const double rho, const double g, const bool trim,
-                                                    const bool haveK, double *mp, double *mh, double *mi) {
+// Rows: where the member's n station rows, its ncap caps and its own row come from (GeomRowsPlain | GeomRowsProg).
+template <class Rows>
+__device__ __forceinline__ GMember geom_member_body(const Rows &rows, const int n, const int ncap, const double *pose, const double rho,
+                                                    const double g, const bool trim, const bool haveK, double *mp, double *mh,
+                                                    double *mi) {
     GEOM_NOFMA
     GMember res = {0, 0, 0, 0};
     double gm[RAFTX_GM_N];
-    {
-        const double2 *p = reinterpret_cast<const double2 *>(gmrow);
-#pragma unroll
-        for (int k = 0; k < RAFTX_GM_N / 2; k++) {
-            const double2 v = p[k];
-            gm[2 * k] = v.x;
-            gm[2 * k + 1] = v.y;
-        }
-    }
+    rows.member(gm);
     if (n < 2 || n > GEOM_MAX_STATIONS || !(gm[RAFTX_GM_DLSMAX] > 0.0) || !(gm[RAFTX_GM_L] > 0.0)) {
         res.rej = 1;                                        // bad station count / dlsMax / length: the member is skipped
         return res;
@@ -718,7 +864,7 @@ __device__ __forceinline__ GMember geom_member_body(const double *gmrow, const d
     if (pose)
         for (int i = 0; i < 6; i++) ps[i] = pose[i];
     double a[RAFTX_GS_N], b[RAFTX_GS_N];
-    geom_load_row(gs, 0, b);
+    rows.station(0, b);
     const bool circ = gm[RAFTX_GM_SHAPE] != 0.0;
     const int flags = (int)gm[RAFTX_GM_FLAGS];
     double rA0[3], q[3], p1[3], p2[3], rA[3], rB[3], R[2][2];
@@ -740,7 +886,7 @@ __device__ __forceinline__ GMember geom_member_body(const double *gmrow, const d
     for (int i = 1; i < n; i++) {
 #pragma unroll
         for (int f = 0; f < RAFTX_GS_N; f++) a[f] = b[f];
-        geom_load_row(gs, i, b);
+        rows.station(i, b);
         {   // wet strips of the interval (group i)
             const double lstrip = b[RAFTX_GS_S] - a[RAFTX_GS_S];
             const int cntg = geom_interval_strips(lstrip, gm[RAFTX_GM_DLSMAX]);
@@ -842,14 +988,14 @@ __device__ __forceinline__ GMember geom_member_body(const double *gmrow, const d
     if (!nostatic) {
         GInertia J;
         geom_inertia_init(J);
-        geom_load_row(gs, 0, b);
+        rows.station(0, b);
         for (int i = 1; i < n; i++) {
 #pragma unroll
             for (int f = 0; f < RAFTX_GS_N; f++) a[f] = b[f];
-            geom_load_row(gs, i, b);
+            rows.station(i, b);
             geom_inertia_section(J, a, b, circ, rho_shell, trim, 0.0, rA, q, p1, p2);
         }
-        code = geom_inertia_caps_finish(J, gs, n, gc, ncap, circ, rho_shell, rA, q, p1, p2, g, mi);
+        code = geom_inertia_caps_finish(J, rows, n, ncap, circ, rho_shell, rA, q, p1, p2, g, mi);
     }
     // ---- everything out
     for (int i = 0; i < 3; i++) {
@@ -871,8 +1017,8 @@ __device__ __forceinline__ GMember geom_member_body(const double *gmrow, const d
     return res;
 }
 
-// Fixed members of a variant program (raftx_variant_program): members no edit touches -- k_geom_expand writes their base
-// rows unchanged into every design -- of a job without per-design poses.  Their pass runs once per program and key
+// Fixed members of a variant program (raftx_variant_program): members no edit touches -- every design has their base
+// rows unchanged -- of a job without per-design poses.  Their pass runs once per program and key
 // (k_geom_member_fixed, one thread per fixed member, on the program's base rows); the per-design pass copies the record.
 struct FixedArgs {
     int nFix;
@@ -888,9 +1034,10 @@ __global__ __launch_bounds__(64) void k_geom_member_fixed(FixedArgs F) {
     if (f >= F.nFix) return;
     const int *ds = F.desc + (size_t)f * 5;
     double *r = F.rec + (size_t)f * FR_N;
-    const GMember R = geom_member_body(F.gm + (size_t)ds[0] * RAFTX_GM_N, F.gs + (size_t)ds[1] * RAFTX_GS_N, ds[2],
-                                       ds[4] >= 0 ? F.gc + (size_t)ds[3] * RAFTX_GC_N : nullptr, ds[4] >= 0 ? ds[4] : 0, nullptr, F.rho,
-                                       F.g, F.trim != 0, F.haveK != 0, r, r + MP_N, r + MP_N + MH_N);
+    const GeomRowsPlain rows{F.gm + (size_t)ds[0] * RAFTX_GM_N, F.gs + (size_t)ds[1] * RAFTX_GS_N,
+                             ds[4] >= 0 ? F.gc + (size_t)ds[3] * RAFTX_GC_N : nullptr};
+    const GMember R = geom_member_body(rows, ds[2], ds[4] >= 0 ? ds[4] : 0, nullptr, F.rho, F.g, F.trim != 0, F.haveK != 0, r, r + MP_N,
+                                       r + MP_N + MH_N);
     int *ir = F.irec + (size_t)f * FR_I;
     ir[0] = R.wet; ir[1] = R.wetm; ir[2] = R.code; ir[3] = R.rej;
 }
@@ -932,11 +1079,20 @@ __global__ __launch_bounds__(128) void k_geom_member(GeomArgs A) {
         // ---- first round trip: everything that hangs on m alone
         const int64_t so0 = A.so(m), so1 = A.so(m + 1);
         const int64_t co0 = A.capOff ? A.co(m) : 0, co1 = A.capOff ? A.co(m + 1) : 0;
-        d = A.mdesign[m];
-        R = geom_member_body(A.gm + (size_t)m * RAFTX_GM_N, A.gs + (size_t)so0 * RAFTX_GS_N, (int)(so1 - so0),
-                             A.capOff ? A.caps + (size_t)co0 * RAFTX_GC_N : nullptr, A.capOff ? (int)(co1 - co0) : 0,
-                             A.pose ? A.pose + (size_t)d * 6 : nullptr, A.rho, A.g, (A.add_mask & RAFTX_TRIM_BALLAST) != 0, A.k != nullptr,
-                             A.mpose + (size_t)m * MP_N, A.mhyd + (size_t)m * MH_N, A.minert + (size_t)m * MI_N);
+        const int n = (int)(so1 - so0), ncap = A.capOff ? (int)(co1 - co0) : 0;
+        const bool trim = (A.add_mask & RAFTX_TRIM_BALLAST) != 0;
+        double *mp = A.mpose + (size_t)m * MP_N, *mh = A.mhyd + (size_t)m * MH_N, *mi = A.minert + (size_t)m * MI_N;
+        if (A.prog.params) {
+            // rows on read: design d of the block is the base unit at the block's parameter row d (uniform offsets)
+            d = (int)(m / A.prog.nM);
+            const GeomRowsProg rows(A.prog, (int)(m % A.prog.nM), (int)(so0 - (int64_t)d * A.prog.nSt), (int)(co0 - (int64_t)d * A.prog.nCap), d);
+            R = geom_member_body(rows, n, ncap, A.pose ? A.pose + (size_t)d * 6 : nullptr, A.rho, A.g, trim, A.k != nullptr, mp, mh, mi);
+        } else {
+            d = A.mdesign[m];
+            const GeomRowsPlain rows{A.gm + (size_t)m * RAFTX_GM_N, A.gs + (size_t)so0 * RAFTX_GS_N,
+                                     A.capOff ? A.caps + (size_t)co0 * RAFTX_GC_N : nullptr};
+            R = geom_member_body(rows, n, ncap, A.pose ? A.pose + (size_t)d * 6 : nullptr, A.rho, A.g, trim, A.k != nullptr, mp, mh, mi);
+        }
     }
     if (R.rej) {
         A.cnt[m] = 0;
@@ -979,15 +1135,24 @@ __global__ __launch_bounds__(128) void k_geom_reinertia(GeomArgs A) {
     if (A.err[2] | A.err[3]) return;                      // rejected descriptors: phase 2 reports them
     const int64_t m = geom_member_of_thread(A);
     if (m < 0) return;
-    const double *gm = A.gm + (size_t)m * RAFTX_GM_N;
-    if ((int)gm[RAFTX_GM_FLAGS] & RAFTX_GM_FLAG_NOSTATIC) return;
-    const double *gs = A.gs + (size_t)A.so(m) * RAFTX_GS_N;
-    const int n = (int)(A.so(m + 1) - A.so(m));
+    const int64_t so0 = A.so(m), co0 = A.capOff ? A.co(m) : 0;
+    const int n = (int)(A.so(m + 1) - so0);
     const double *mp = A.mpose + (size_t)m * MP_N;
-    const int ncap = A.capOff ? (int)(A.co(m + 1) - A.co(m)) : 0;
-    const double *gc = A.capOff ? A.caps + (size_t)A.co(m) * RAFTX_GC_N : nullptr;
+    const int ncap = A.capOff ? (int)(A.co(m + 1) - co0) : 0;
     double *mi = A.minert + (size_t)m * MI_N;
-    if (geom_member_inertia(gm, gs, n, gc, ncap, mp + 3, mp + 6, mp + 9, mp + 12, A.g, true, A.drho[A.mdesign[m]], mi))
+    int code;
+    if (A.prog.params) {
+        const int d = (int)(m / A.prog.nM);
+        const GeomRowsProg rows(A.prog, (int)(m % A.prog.nM), (int)(so0 - (int64_t)d * A.prog.nSt), (int)(co0 - (int64_t)d * A.prog.nCap), d);
+        if ((int)rows.mcol(RAFTX_GM_FLAGS) & RAFTX_GM_FLAG_NOSTATIC) return;
+        code = geom_member_inertia(rows, n, ncap, mp + 3, mp + 6, mp + 9, mp + 12, A.g, true, A.drho[d], mi);
+    } else {
+        const GeomRowsPlain rows{A.gm + (size_t)m * RAFTX_GM_N, A.gs + (size_t)so0 * RAFTX_GS_N,
+                                 A.capOff ? A.caps + (size_t)co0 * RAFTX_GC_N : nullptr};
+        if ((int)rows.mcol(RAFTX_GM_FLAGS) & RAFTX_GM_FLAG_NOSTATIC) return;
+        code = geom_member_inertia(rows, n, ncap, mp + 3, mp + 6, mp + 9, mp + 12, A.g, true, A.drho[A.mdesign[m]], mi);
+    }
+    if (code)
         for (int i = 0; i < MI_N; i++) mi[i] = 0.0;
 }
 
@@ -1192,8 +1357,9 @@ static_assert(GD_T % 64 == 0 && GD_T % DS_N == 0 && GD_T <= 256, "k_geom_design:
 // fused fixed point's generating form (raftx_fusedgen.h), where the workgroup that has claimed a pair builds its design's
 // tables itself.  gd_lds: geom_design_lds() bytes of LDS; wcnt: GD_T / 64 ints of LDS.  ABI: also the public-layout copy
 // of the strip records (raftx_fetch_strips).  ADDUP: the design's share of k_geom_addup in the same pass (the member ->
-// platform reductions must have finished).
-template <bool ABI, bool ADDUP>
+// platform reductions must have finished).  PROG: the job keeps no rows (GeomArgs::prog) -- the staged columns come from the
+// program's base rows, a few KB every design of the chip reads (L2), and the edited station columns are patched in LDS.
+template <bool ABI, bool ADDUP, bool PROG = false>
 __device__ __forceinline__ void geom_design_block(const GeomArgs &A, const int d, double *gd_lds, int *wcnt) {
     GEOM_NOFMA
     const int lane = threadIdx.x;                         // lane: thread of the design's workgroup (0 .. GD_T-1)
@@ -1232,7 +1398,9 @@ __device__ __forceinline__ void geom_design_block(const GeomArgs &A, const int d
         {
             // (the three tables are one contiguous stretch of LDS: a lane's loads of a round -- ten, enough for a design of 16
             // members and 64 stations -- and its first-station offset are all in flight before the first of them is waited for)
-            const double *g0 = A.gm + (size_t)m0 * RAFTX_GM_N, *g1 = A.gs + (size_t)s0 * RAFTX_GS_N, *g2 = A.mpose + (size_t)m0 * MP_N;
+            // (PROG: the three member columns are never edited, and the station rows are the base unit's until the patch below)
+            const double *g0 = PROG ? A.prog.gm : A.gm + (size_t)m0 * RAFTX_GM_N, *g1 = PROG ? A.prog.gs : A.gs + (size_t)s0 * RAFTX_GS_N,
+                         *g2 = A.mpose + (size_t)m0 * MP_N;
             const int n0 = nMem * GD_GM_N, n01 = n0 + nSta * RAFTX_GS_N, total = n01 + nMem * GD_MP_N;
             constexpr int SU = 10;
             const int64_t so_lane = lane <= nMem ? A.so(m0 + lane) : s0;
@@ -1264,6 +1432,31 @@ __device__ __forceinline__ void geom_design_block(const GeomArgs &A, const int d
             // (mbase doubles as the members' first-station table until the counts are in)
             if (lane <= nMem) mbase[lane] = ssta[lane] = (int)(so_lane - s0);
             for (int mi = lane + GD_T; mi <= nMem; mi += GD_T) mbase[mi] = ssta[mi] = (int)(A.so(m0 + mi) - s0);
+        }
+        if constexpr (PROG) {
+            // the edited columns of the staged station rows, a lane per (row, kind of edit): positions of a member with edited
+            // ends from its length -- the staged mpose[19], which the member pass stored from the row's own L (of a fixed
+            // member: the base row's) -- and diameters, with the functions k_geom_expand writes rows with
+            __syncthreads();
+            const VariantView &V = A.prog;
+            for (int u = lane; u < 2 * nSta; u += GD_T) {
+                const int idx = u >> 1;
+                double *o = sgs + (size_t)idx * RAFTX_GS_N;
+                if (u & 1) {
+                    if (V.diaEdit[idx]) {
+                        const double *p = V.params + (size_t)d * V.nP;
+                        o[RAFTX_GS_D] = variant_station_D(V, idx, 0, p);
+                        o[RAFTX_GS_D + 1] = variant_station_D(V, idx, 1, p);
+                    }
+                } else {
+                    const int bm = V.stMember[idx];
+                    if (V.endEdit[bm]) {
+                        const double L = smp[(size_t)bm * GD_MP_N + 12];
+                        o[RAFTX_GS_S] = variant_station_S(V, idx, L);
+                        o[RAFTX_GS_LFILL] = variant_station_LFILL(V, idx, L);
+                    }
+                }
+            }
         }
         __syncthreads();
         for (int u = lane; u < nSta + nMem; u += GD_T) {
@@ -1628,7 +1821,10 @@ __global__ __launch_bounds__(GD_T) void k_geom_design(GeomArgs A) {
     extern __shared__ double gd_lds[];
     __shared__ int wcnt[GD_T / 64];
     if ((int)blockIdx.x >= A.nDesign) return;
-    if (A.abi) geom_design_block<true, false>(A, (int)blockIdx.x, gd_lds, wcnt);
+    if (A.prog.params) {                                  // a crossing that keeps no rows (never with the ABI copy)
+        if (A.addup_in_design) geom_design_block<false, true, true>(A, (int)blockIdx.x, gd_lds, wcnt);
+        else geom_design_block<false, false, true>(A, (int)blockIdx.x, gd_lds, wcnt);
+    } else if (A.abi) geom_design_block<true, false>(A, (int)blockIdx.x, gd_lds, wcnt);
     else if (A.addup_in_design) geom_design_block<false, true>(A, (int)blockIdx.x, gd_lds, wcnt);       // sweep crossings
     else geom_design_block<false, false>(A, (int)blockIdx.x, gd_lds, wcnt);
 }
@@ -1713,31 +1909,15 @@ __global__ __launch_bounds__(64) void k_geom_reduce(GeomArgs A) {
 }
 
 // ------------------------------------------------------------------------------------------------------------------
-// Parametric variants of one base unit, written in HBM (raftx_variant_program / raftx_sweep_prepare_variants;
-// raft/parametersweep.py:39-87 edits a handful of parameters per candidate and the dependent geometry follows).
-// One thread per descriptor ROW of a variant -- member, station or cap -- builds it from the base row and the edits:
-// the member's end points as affine functions of the parameters, its length (raft_member.py:72), the heading rotation
-// (:75-77, helpers.py:587-602), station / ballast / cap positions as fractions of the length (:99,143,173), diameters
-// as affine functions.  Every expression is evaluated like the host's NumPy form -- left to right, no fused
-// multiply-add -- so that the rows are the bits raft_amd/geometry.py SweepTables produces (tests/test_geometry.py).
-// 6.6 KB per VolturnUS-S variant: a 10^4-design batch is 66 MB of stores (16-double rows, one full line per thread)
-// instead of 66 MB over PCIe.
-struct ExpandArgs {
-    int n, nM, nSt, nCap, nP;
-    const double *params;                                    // [n,nP]
-    const double *gm, *gs, *gc;                              // base rows
-    const int *stMember, *capMember;
-    const double *stFrac, *fillFrac, *capFrac;
-    const double *endCoef, *headCS, *diaCoef;                // [nM,6,nP+1] [nM,2] [nSt,2,nP+1]
-    const int *endEdit, *diaEdit;
+// Parametric variants of one base unit, written in HBM (raftx_expand_variants, the second-order generator, and the sweep
+// crossings whose tables are left to the generating fused form, RAFTX_FUSED_GEN=1; every other crossing keeps no rows
+// and evaluates them on read, GeomArgs::prog).  One thread per descriptor ROW of a variant -- member, station or cap --
+// builds it from the base row and the edits with the variant_* functions above, the one source of these bits.
+// 6.6 KB per VolturnUS-S variant: a 10^4-design batch is 66 MB of stores (16-double rows, one full line per thread).
+struct ExpandArgs : VariantView {
+    int n;
     double *gm_out, *gs_out, *gc_out;                        // [n*nM,GM_N] [n*nSt,GS_N] [n*nCap,GC_N]
 };
-__device__ inline double affine_eval(const double *coef, const double *p, int nP) {
-    GEOM_NOFMA
-    double v = coef[0];
-    for (int q = 0; q < nP; q++) v = v + coef[1 + q] * p[q];
-    return v;
-}
 // Kind-major grid: the first blocks take member rows, the next station rows, the last cap rows, GE_T consecutive rows of
 // ONE output array each.  A thread computes its row into an LDS tile (row stride 17 doubles: conflict-free for the
 // per-thread writes and for the read-back), then the block copies the tile out with 16-byte stores over consecutive
@@ -1762,39 +1942,19 @@ __global__ void __launch_bounds__(GE_T) k_geom_expand(ExpandArgs E, unsigned nbM
         const double *bm = E.gm + (size_t)m * RAFTX_GM_N;
         const bool ed = E.endEdit[m] != 0;
         double e[6] = {0, 0, 0, 0, 0, 0}, L = bm[RAFTX_GM_L];
-        if (ed) {
-            for (int i = 0; i < 6; i++) e[i] = affine_eval(E.endCoef + ((size_t)m * 6 + i) * (E.nP + 1), p, E.nP);
-            const double dx = e[3] - e[0], dy = e[4] - e[1], dz = e[5] - e[2];
-            L = sqrt((dx * dx + dy * dy) + dz * dz);         // |rB - rA| before the heading rotation (raft_member.py:72)
-        }
+        if (ed) variant_ends(E, m, p, e, L);
         double *o = tile + t * 17;
         if (kind == 0) {
             for (int i = 0; i < RAFTX_GM_N; i++) o[i] = bm[i];
-            if (ed) {
-                const double c = E.headCS[2 * m], s = E.headCS[2 * m + 1];
-                o[RAFTX_GM_RA + 0] = c * e[0] + (-s) * e[1];
-                o[RAFTX_GM_RA + 1] = s * e[0] + c * e[1];
-                o[RAFTX_GM_RA + 2] = e[2];
-                o[RAFTX_GM_RB + 0] = c * e[3] + (-s) * e[4];
-                o[RAFTX_GM_RB + 1] = s * e[3] + c * e[4];
-                o[RAFTX_GM_RB + 2] = e[5];
-                o[RAFTX_GM_L] = L;
-            }
+            if (ed) variant_member_edit(E, m, e, L, o);
         } else if (kind == 1) {
             const double *b = E.gs + (size_t)idx * RAFTX_GS_N;
             for (int i = 0; i < RAFTX_GS_N; i++) o[i] = b[i];
-            if (ed) {
-                o[RAFTX_GS_S] = E.stFrac[idx] * L;
-                o[RAFTX_GS_LFILL] = E.fillFrac[idx] * L;
-            }
-            if (E.diaEdit[idx]) {
-                o[RAFTX_GS_D] = affine_eval(E.diaCoef + ((size_t)idx * 2 + 0) * (E.nP + 1), p, E.nP);
-                o[RAFTX_GS_D + 1] = affine_eval(E.diaCoef + ((size_t)idx * 2 + 1) * (E.nP + 1), p, E.nP);
-            }
+            variant_station_edit(E, idx, ed, L, p, o);
         } else {
             const double *b = E.gc + (size_t)idx * RAFTX_GC_N;
             for (int i = 0; i < RAFTX_GC_N; i++) o[i] = b[i];
-            if (ed) o[RAFTX_GC_S] = E.capFrac[idx] * L;
+            if (ed) o[RAFTX_GC_S] = variant_cap_S(E, idx, L);
         }
     }
     __syncthreads();

@@ -798,8 +798,8 @@ struct CaseSet {
 
 // Edit program of parametric variants (raftx_variant_program): the base unit's descriptors and the affine edits, resident
 // on the device; the uniform offset arrays of a batch of nDesign variants on the host (cached per batch size).
-// The member pass of the program's FIXED members (no end edit, no diameter edit on a station: k_geom_expand writes their
-// base rows unchanged into every design), run once by k_geom_member_fixed and copied by the member pass of every job
+// The member pass of the program's FIXED members (no end edit, no diameter edit on a station: every design has their
+// base rows unchanged), run once by k_geom_member_fixed and copied by the member pass of every job
 // without per-design poses.  Keyed by what the pass reads besides the rows.  A crossing pins the record it was prepared
 // with until it is retired, so that a crossing with another key writes another record (one more than there are slots).
 struct FixedRecord {
@@ -837,14 +837,26 @@ struct VariantSrc {
     const FixedRecord *rec = nullptr;                                    // the fixed members' record the batch's member passes copy, or null
 };
 
+// the program as the kernels see it (V.params stays the caller's)
+static void variant_view(const VariantProg &P, VariantView &V) {
+    V.nM = P.nM; V.nSt = P.nSt; V.nCap = P.nCap; V.nP = P.nP;
+    V.gm = P.gm; V.gs = P.gs; V.gc = P.gc;
+    V.stMember = P.stMember; V.capMember = P.capMember;
+    V.stFrac = P.stFrac; V.fillFrac = P.fillFrac; V.capFrac = P.capFrac;
+    V.endCoef = P.endCoef; V.headCS = P.headCS; V.diaCoef = P.diaCoef;
+    V.endEdit = P.endEdit; V.diaEdit = P.diaEdit;
+}
 static void expand_args(const VariantProg &P, int n, double *gm_out, double *gs_out, double *gc_out, ExpandArgs &E) {
-    E.n = n; E.nM = P.nM; E.nSt = P.nSt; E.nCap = P.nCap; E.nP = P.nP;
-    E.gm = P.gm; E.gs = P.gs; E.gc = P.gc;
-    E.stMember = P.stMember; E.capMember = P.capMember;
-    E.stFrac = P.stFrac; E.fillFrac = P.fillFrac; E.capFrac = P.capFrac;
-    E.endCoef = P.endCoef; E.headCS = P.headCS; E.diaCoef = P.diaCoef;
-    E.endEdit = P.endEdit; E.diaEdit = P.diaEdit;
+    variant_view(P, E);
+    E.n = n;
     E.gm_out = gm_out; E.gs_out = gs_out; E.gc_out = gc_out;
+}
+// RAFTX_FUSED_GEN=1: sweep crossings build their tables inside the fused kernel (raftx_fusedgen.h).  Read per call -- tests
+// switch it inside one process -- when a crossing is prepared (its job then materialises its rows: the generating form
+// inlines the plain source of geom_design_block) and when its generation is enqueued.
+static bool fused_gen_asked() {
+    const char *fg = getenv("RAFTX_FUSED_GEN");
+    return fg && atoi(fg);
 }
 
 // resident matrices of the dense solves (raftx_dense_resident): device pointers owned by `allocs`
@@ -1376,8 +1388,9 @@ static int slice_of(raftx_ctx *c, const BuildSource &B, int lo, int nDesign, Sli
 }
 // The slice's descriptors into device memory, copied on sCopy.  Offsets: the slice of the batch's resident arrays, or
 // uploaded here.  Members, stations and caps: the slice of the caller's arrays, or with a variant program only the
-// parameters (E then says what k_geom_expand writes the descriptors from).  The per-design matrices stay with the tables
-// (design_allocs); the rest goes back to the pool when the job retires.
+// parameters -- the job then keeps no rows and its kernels evaluate them on read (A.prog), or, where the tables may be left
+// to the generating fused form, E says what k_geom_expand writes the rows from (E.gm_out != null).  The per-design matrices
+// stay with the tables (design_allocs); the rest goes back to the pool when the job retires.
 static int upload_descriptors(raftx_ctx *c, hipStream_t sCopy, const BuildSource &B, const Slice &L, ExpandArgs &E) {
     BuildJob &J = c->job;
     GeomArgs &A = J.A;
@@ -1396,17 +1409,27 @@ static int upload_descriptors(raftx_ctx *c, hipStream_t sCopy, const BuildSource
     }
     memset(&E, 0, sizeof(E));
     if (const VariantProg *P = B.var.prog) {
-        // variants of one base unit: only their parameters cross the bus (nP doubles per design); the descriptors are
-        // written in HBM by k_geom_expand, enqueued on sPrep ahead of the member pass
+        // variants of one base unit: only their parameters cross the bus (nP doubles per design).  No row is written: the
+        // member pass, the ballast trim and the generation evaluate a row from the base row where they load it ...
         if (nMember != nDesign * P->nM || nSta != nDesign * P->nSt || nCap != nDesign * P->nCap)
             FAIL(c, "build_designs: offsets do not describe %d variants of the program's base unit", A.nDesign);
-        double *gm = nullptr, *gs = nullptr, *gc = nullptr;
-        if (pool_alloc(c, tmp, nMember * RAFTX_GM_N, &gm) || pool_alloc(c, tmp, nSta * RAFTX_GS_N, &gs) ||
-            pool_alloc(c, tmp, nCap * RAFTX_GC_N, &gc))
-            return -2;
-        rc |= upload_on(c, sCopy, tmp, B.var.params + lo * P->nP, nDesign * P->nP, &E.params);
-        expand_args(*P, A.nDesign, gm, gs, gc, E);
-        A.gm = gm; A.gs = gs; A.caps = B.capOff ? gc : nullptr;
+        const double *params = nullptr;
+        if (nDesign * P->nP) rc |= upload_on(c, sCopy, tmp, B.var.params + lo * P->nP, nDesign * P->nP, &params);
+        else rc |= pool_alloc(c, tmp, 1, &params);                  // no parameter: a valid, never-read address (it marks A.prog)
+        if (fused_gen_asked()) {
+            // ... unless the generating fused form may take the tables: the rows in HBM, written by k_geom_expand on sPrep ahead of
+            // the member pass
+            double *gm = nullptr, *gs = nullptr, *gc = nullptr;
+            if (pool_alloc(c, tmp, nMember * RAFTX_GM_N, &gm) || pool_alloc(c, tmp, nSta * RAFTX_GS_N, &gs) ||
+                pool_alloc(c, tmp, nCap * RAFTX_GC_N, &gc))
+                return -2;
+            E.params = params;
+            expand_args(*P, A.nDesign, gm, gs, gc, E);
+            A.gm = gm; A.gs = gs; A.caps = B.capOff ? gc : nullptr;
+        } else {
+            variant_view(*P, A.prog);
+            A.prog.params = params;
+        }
     } else {
         rc |= upload_on(c, sCopy, tmp, B.members + (size_t)L.m0 * RAFTX_GM_N, nMember * RAFTX_GM_N, &A.gm);
         rc |= upload_on(c, sCopy, tmp, B.stations + (size_t)L.s0 * RAFTX_GS_N, nSta * RAFTX_GS_N, &A.gs);
@@ -1532,10 +1555,10 @@ static int build_phase1(raftx_ctx *c, hipStream_t sCopy, hipStream_t sPrep, cons
     HIPCHK(c, hipEventRecord(c->evUp, sCopy));
     HIPCHK(c, hipStreamWaitEvent(sPrep, c->evUp, 0));
     if (B.var.prog && nDesign > 0) {
-        // the expansion (0.09 ms of chip time) on the preparation stream, ahead of the member pass: its stores land inside the
-        // running fused kernel of the batch before (a high-priority stream of its own gained nothing: profiles/MEASUREMENT_HISTORY.md,
-        // "Closed scheduling experiments of the crossing")
-        launch_expand(E, sPrep);
+        // a job that materialises its rows (upload_descriptors): the expansion on the preparation stream, ahead of the member
+        // pass -- its stores land inside the running fused kernel of the batch before (a high-priority stream of its own gained
+        // nothing: profiles/MEASUREMENT_HISTORY.md, "Closed scheduling experiments of the crossing")
+        if (E.gm_out) launch_expand(E, sPrep);
         if (const FixedRecord *R = B.var.rec) {
             // the fixed members' pass ran once for the program: this job's member pass copies it
             if (R->stream != sPrep) HIPCHK(c, hipStreamWaitEvent(sPrep, R->ev, 0));
@@ -1592,9 +1615,9 @@ static int enqueue_generation(raftx_ctx *c, hipStream_t sGen, int kind) {
     // the default (profiles/r06_experiments/fused_generation_ab.txt): bit-identical, the gap between two fused kernels
     // shrinks from 0.30 to 0.09 ms, but the kernel grows by 0.50 ms -- the ~50 us of dependent loads per design are not
     // hidden by the seven other waves of the CU (each is bound by its own dependency chains, not by issue slots).
-    const char *fg_ = getenv("RAFTX_FUSED_GEN");          // (read per call: tests switch it inside one process)
-    const bool fused_gen = fg_ && atoi(fg_);
-    const bool defer = (kind & GEN_MAY_DEFER) && fused_gen && nDesign > 0 && nRows == 0;
+    // A job that keeps no rows (A.prog: prepared without the variable) takes the k_geom_design route: the generating form
+    // inlines the plain source.
+    const bool defer = (kind & GEN_MAY_DEFER) && fused_gen_asked() && !A.prog.params && nDesign > 0 && nRows == 0;
     J.gen_deferred = false;
     const size_t gd_lds = geom_design_lds(J.maxS, (int)J.maxSta, (int)J.maxMem);
     if (gd_lds > 160 * 1024)

@@ -781,8 +781,8 @@ def run_pipelined(sweep, lib, n_chunks=8, n_workers=2, device_id=0, fetch="Xi"):
 class VariantSweep(GeometrySweep):
     """A sweep whose designs are PARAMETRIC VARIANTS of one base unit (raft_amd/geometry.py VariantProgram;
     raft/parametersweep.py:39-87): per candidate only its parameter values cross the bus, the member / station / cap
-    descriptors are written on the device (raftx_sweep_prepare_variants -> k_geom_expand) and everything after that is
-    the GeometrySweep path.  ``params`` [nD,nParam]; M_extra / B0 / C_extra as GeometrySweep.
+    descriptors are evaluated on the device from the program's base rows, where the kernels read them
+    (raftx_sweep_prepare_variants), and everything after that is the GeometrySweep path.  ``params`` [nD,nParam]; M_extra / B0 / C_extra as GeometrySweep.
 
     ``set_params`` swaps in the next batch's candidates (same batch size: the library's slots stay configured).  The
     crossing calls (prepare / submit / wait, run_crossing) take the device path; ``upload`` / ``solve`` / ``run`` -- the
