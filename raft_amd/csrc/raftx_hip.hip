@@ -685,92 +685,13 @@ __global__ void __launch_bounds__(256) k_response_stats(int nDof, int nResp, int
 
 // ------------------------------------------------------------------ host side
 #define RAFTX_NSLOT RAFTX_SWEEP_SLOTS   // crossings in flight per context: one downloading its responses, one solving, one generated / queued, one uploading
-// Per-context device-memory pool: every call of the C-ABI needs a handful of device buffers (tables, results, scratch);
-// hipMalloc / hipFree cost 0.1-1 ms each and hipFree synchronises the whole device, which serialises contexts that
-// otherwise overlap copies and kernels on their own streams.  Blocks are rounded up (powers of two below 1 MiB, 1 MiB
-// multiples above), cached on release and handed out again; everything goes back to the driver in raftx_ctx_destroy.
-// Callers return blocks only after their stream has drained.
-struct DevPool {
-    std::multimap<size_t, void *> free_;
-    std::unordered_map<void *, size_t> size_;
-    static size_t round_up(size_t b) {
-        if (b < 256) b = 256;
-        if (b <= ((size_t)1 << 20)) {
-            size_t p = 256;
-            while (p < b) p <<= 1;
-            return p;
-        }
-        return (b + ((size_t)1 << 20) - 1) & ~(((size_t)1 << 20) - 1);
-    }
-    hipError_t get(size_t bytes, void **out) {
-        const size_t cap = round_up(bytes);
-        auto it = free_.lower_bound(cap);
-        if (it != free_.end() && it->first <= cap + cap / 2 + ((size_t)1 << 20)) {
-            *out = it->second;
-            free_.erase(it);
-            return hipSuccess;
-        }
-        static const bool dbg = getenv("RAFTX_POOL_DEBUG") != nullptr;   // tuning: pool misses (they cost a hipMalloc) on stderr
-        const auto t0 = std::chrono::steady_clock::now();
-        hipError_t e = hipMalloc(out, cap);
-        if (dbg)
-            fprintf(stderr, "[raftx pool] miss: hipMalloc(%zu) %.3f ms (%zu blocks free)\n", cap,
-                    std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(), free_.size());
-        if (e != hipSuccess) {                      // make room and retry once
-            (void)hipGetLastError();
-            trim();
-            e = hipMalloc(out, cap);
-        }
-        if (e == hipSuccess) size_[*out] = cap;
-        return e;
-    }
-    void put(void *p) {
-        if (!p) return;
-        auto it = size_.find(p);
-        if (it == size_.end()) {
-            (void)hipFree(p);
-            return;
-        }
-        free_.emplace(it->second, p);
-    }
-    void trim() {
-        for (auto &kv : free_) {
-            size_.erase(kv.second);
-            (void)hipFree(kv.second);
-        }
-        free_.clear();
-    }
-};
-
-// A page-locked landing area of a ctx, written by kernels and read by the host: grow-only -- reserve(n) keeps a block that
-// holds n elements and replaces a smaller one (contents are not carried over; a zero count still gives a valid block) --
-// and released by raftx_ctx_destroy.
-template <typename Tp>
-struct Pinned {
-    Tp *p = nullptr;
-    size_t cap = 0;                      // elements p was reserved for
-    hipError_t reserve(size_t n) {
-        if (p && cap >= n) return hipSuccess;
-        release();
-        void *q = nullptr;
-        const hipError_t e = hipHostMalloc(&q, (n ? n : 1) * sizeof(Tp), hipHostMallocDefault);
-        if (e != hipSuccess) return e;
-        p = reinterpret_cast<Tp *>(q);
-        cap = n;
-        return hipSuccess;
-    }
-    void release() {
-        if (p) (void)hipHostFree(p);
-        p = nullptr;
-        cap = 0;
-    }
-};
+#include "raftx_owned.h"
 
 // A raftx_build_designs in flight: phase 1 (descriptor H2D, member pass, scans, totals to the host) has been enqueued,
 // phase 2 (strip tables, statics) follows once the totals are known.  The sweep crossing keeps several of them in flight.
 struct BuildJob {
-    GeomArgs A;
-    std::vector<void *> tmp;            // descriptor uploads and per-member scratch: back to the pool when the job retires
+    GeomArgs A{};
+    Bag tmp;                            // descriptor uploads and per-member scratch: back to the pool when the job retires
     int nDesign = 0, nw = 0;
     int64_t maxMem = 0, maxSta = 0;     // members / stations of the largest design (host loop of phase 1)
     size_t nStrips = 0, nRows = 0;      // totals of phase 1, read by phase 2 (wait_totals): wet strips, MacCamy-Fuchs rows,
@@ -778,7 +699,7 @@ struct BuildJob {
     double *M0d = nullptr, *C0d = nullptr;
     const double *B0d = nullptr, *MBwd = nullptr;
     bool active = false;
-    hipStream_t reduce_stream = nullptr; // side stream the member -> platform reductions were launched on (evRed), or null
+    hipStream_t reduce_stream = nullptr; // (not owned) side stream the member -> platform reductions were launched on (evRed), or null
     // phase 2 left the tables of the designs to the fused kernel that solves them (raftx_fusedgen.h): nothing has been
     // written yet; solve_enqueue launches the generating form, or k_geom_design + k_geom_addup if it cannot
     bool gen_deferred = false;
@@ -790,8 +711,8 @@ struct BuildJob {
 // replace what an earlier batch still reads (its member pass reads k; its fused kernel everything).
 struct CaseSet {
     std::vector<double> key;             // nCase, nHead, nw, depth, rho, g, w, k, zeta, beta as given by the caller
-    DevTables T;                         // only the sea-state fields are used
-    std::vector<void *> allocs;
+    DevTables T{};                       // only the sea-state fields are used
+    Bag allocs;
     int users = 0;                       // crossings prepared or in flight on this set
     unsigned long long stamp = 0;        // last use (the idle set used longest ago is replaced)
 };
@@ -810,8 +731,8 @@ struct FixedRecord {
     int *irec = nullptr;                 // [nFix,FR_I]
     int users = 0;                       // crossings prepared or in flight on this record
     unsigned long long stamp = 0;
-    hipEvent_t ev = nullptr;             // the record has been written (on `stream`)
-    hipStream_t stream = nullptr;
+    Event ev;                            // the record has been written (on `stream`)
+    hipStream_t stream = nullptr;        // (not owned)
 };
 struct VariantProg {
     int nM = 0, nSt = 0, nCap = 0, nP = 0;
@@ -826,7 +747,7 @@ struct VariantProg {
     double *endCoef = nullptr, *headCS = nullptr, *diaCoef = nullptr;
     int *endEdit = nullptr, *diaEdit = nullptr;
     std::vector<int64_t> hS, hC;                                         // base stationOff / capOff (host)
-    std::vector<void *> allocs;
+    Bag allocs;                                                          // blocks outside the pool (Bag::get_outside)
     int cachedN = -1;
     std::vector<int64_t> memberOff, stationOff, capOff;                  // uniform offsets of cachedN variants
 };
@@ -863,7 +784,7 @@ static bool fused_gen_asked() {
 struct DenseResident {
     int nSet = 0, n = 0, nw = 0, freq_mask = 0;
     double *w = nullptr, *M = nullptr, *B = nullptr, *C = nullptr;
-    std::vector<void *> allocs;
+    Bag allocs;
 };
 // The second-order records of the last raftx_qtf_tables_build (include/raftx_qtfgen.h), resident until the next one.
 struct QtfResident {
@@ -872,97 +793,10 @@ struct QtfResident {
     std::vector<int64_t> off;            // host copy of dOff: [QG_CNT_N][nDesign+1] strips | members | Kim & Yue rows | items
     int64_t *dOff = nullptr;
     double *strips = nullptr, *members = nullptr, *kay = nullptr;
-    std::vector<void *> allocs;
+    Bag allocs;
     int64_t total(int j) const { return off[(size_t)j * (nDesign + 1) + nDesign]; }
 };
-struct raftx_ctx {
-    int device;
-    hipStream_t stream;
-    bool owns_stream;                    // false for the block contexts of raftx_sweep_stats (they run on the parent's stream)
-    hipEvent_t ev0, ev1;
-    hipEvent_t evUp, evTot, evG0, evG1, evG2, evG3, evS0, evS1, evDone;   // build phases, statistics, block finished
-    hipEvent_t evZ;                      // the first kernel of the member pass has run (phase 1)
-    hipEvent_t evMem, evRed;             // member pass done (preparation stream) / per-design reduction done (side stream)
-    hipStream_t sAux;                    // side stream of the parent ctx: the reductions of the member pass run beside its scans
-    BuildJob job;
-    Pinned<long long> pin;               // landing area of the build totals and offsets [PIN_OFF + nDesign + 1]
-    Pinned<double> pinRes;               // ... of a block's statistics (sweep crossing)
-    Pinned<double> pinModal;             // ... of a block's eigen analysis (raftx_sweep_modal)
-    Pinned<double> pinCur;               // ... of a block's current loads (raftx_sweep_current)
-    Pinned<double> pinChan;              // ... of a block's output channels (raftx_sweep_channels) [pairs,nChan]
-    Pinned<double> pinMoorT;             // ... of a block's tension statistics (raftx_sweep_mooring) [pairs,2 nLine]
-    hipEvent_t evMoor = nullptr;         // C_moor has been added to the block's C0 (raftx_sweep_mooring, sCopy)
-    hipStream_t sCopy, sPrep, sD2H, sGen; // internal streams of raftx_sweep_stats (created on first use)
-    hipStream_t sSlab[2] = {nullptr, nullptr}; // with sGen: the streams the slabs of a crossing with responses out go to (SlabPlan)
-    hipStream_t sD2Hhigh = nullptr;       // bulk download of the responses: a stream of the highest priority class, created when first needed
-    hipEvent_t evEpoch = nullptr;         // zero of raftx_sweep_solve_span: recorded when the first crossing of the ctx is launched
-    CaseSet csets[RAFTX_NSLOT + 1];      // sea-state tables of the sweep crossings: one per crossing in flight + one being replaced
-    unsigned long long cset_clock = 0;
-    char err[512];
-    DevTables T;
-    DevPool pool;
-    std::vector<void *> design_allocs, case_allocs, result_allocs;
-    // resident results of the last raftx_solve_dynamics_device
-    cplx *rXi, *rFw, *rZ, *rFe;
-    double *rB, *rXl;
-    cplx *flexXl0;                       // raftx_flex_start: the linearisation point of the next raftx_flex_solve (device copy)
-    size_t flexXl0_n, flexXl0_cap;       // entries set (0: none) / allocated
-    unsigned long long *rXlSlots;
-    size_t rXl_n;
-    unsigned *kpCtr = nullptr;           // claim counters of the persistent fused launches: a ring of KP_RING sets of 8 (one per XCD slab, 128 B apart)
-    unsigned kpNext = 0;
-    int nCU = 0;                         // compute units of the device (the persistent grid is what they hold at once)
-    int last_flags = -1, last_minb = 0, last_rc = 0;       // specialisation of the last fused-kernel launch (raftx_last_solve_kernel)
-    cplx *rQtf;                          // QTFs of the last raftx_qtf_slender call, kept for raftx_qtf_force
-    size_t rQtf_n;
-    int rQtf_sets, rQtf_nw2;
-    cplx *rXl0, *rXlOut;                 // optional restart point / exported linearisation point [npair,6,nw]
-    size_t rXlio_n;
-    bool have_xl0, want_xlout;
-    int *rNi, *rFl;
-    size_t r_npair, r_nx, r_nz;
-    int r_mask;
-    int r_last_mask = 0;                 // RAFTX_WANT_* outputs the LAST fused solve wrote (r_mask: what the buffers could hold)
-    bool r_fe;
-    int maxS;
-    std::vector<int> hS;                 // submerged strips of every design (host copy: LDS classes of the fused kernel)
-    int *pairList;                       // device pair lists of a launch split into LDS classes
-    size_t pairList_n;
-    DenseResident dense;                 // matrices kept for raftx_solve_dense_resident
-    int *identList = nullptr;            // 0, 1, 2, ..: the pair list of a launch cut into slabs (SlabPlan)
-    size_t identList_n = 0;
-    std::vector<hipEvent_t> evSlab;      // completion markers of the slabs (no timing), created as needed, kept
-    hipEvent_t evFork = nullptr, evJoin = nullptr;
-    unsigned long long *dbg;
-    double last_ms;
-    bool have_designs, have_cases;
-    int nw_designs;
-    cplx *rKay;                          // Kim & Yue table of raftx_qtf_kay, consumed by the next raftx_qtf_slender call
-    size_t rKay_n;
-    int rKay_sets, rKay_nw2;
-    bool kay_ready;
-    cplx *bemF;                          // resident BEM (+ added) excitation of raftx_bem_excitation [npair,nHead,6,nw]
-    size_t bemF_n;
-    bool bem_ready;
-    // results of the last raftx_build_designs (device pointers owned by design_allocs)
-    int g_n;
-    size_t g_nStrips, g_nRows;
-    double *g_abi, *g_A, *g_Ch, *g_Wh, *g_props, *g_Ms, *g_Cs, *g_Ws;
-    bool last_gen_fused = false;         // the last fused launch generated its designs' tables itself (raftx_fusedgen.h)
-    cplx *g_cm;
-    void *comm;                          // ncclComm_t of raftx_comm_init (RCCL), or null
-    int comm_rank, comm_world;
-    int *commFlag = nullptr;             // one int in HBM: the status word the ranks agree on before an exchange step (comm_agree)
-    std::vector<raftx_ctx *> workers[RAFTX_NSLOT]; // block contexts of the sweep crossings (device buffers, pool, events), per slot, kept for reuse
-    struct SweepSlot *slots;             // [RAFTX_NSLOT] crossings in flight (raftx_sweep_prepare / _launch / _wait)
-    VariantProg vprog;                   // raftx_variant_program
-    struct {                             // raftx_mooring_program: base records and the affine edits of their end points
-        int nLine = 0, nP = 0;
-        double *base = nullptr, *coef = nullptr;
-        int *edit = nullptr;
-    } mprog;
-    QtfResident qt;                      // raftx_qtf_tables_build
-};
+struct raftx_ctx;
 // Offset arrays of a whole batch, resident on the device (uploaded once by the sweep crossing, shared by its blocks).
 struct DevOffsets {
     const int64_t *memberOff, *stationOff, *capOff;      // device copies of the caller's arrays, absolute values
@@ -996,14 +830,14 @@ struct SweepSlot {
     int32_t *niter = nullptr, *flags = nullptr;
     raftx_c128 *Xi = nullptr;
     int64_t *stripOffsets = nullptr;
-    std::vector<void *> allocs;          // the batch's offset arrays on the device, shared by its blocks
-    hipEvent_t evXi = nullptr;           // download of the responses finished (sD2H)
+    Bag allocs;                          // the batch's offset arrays on the device, shared by its blocks
+    Event evXi;                          // download of the responses finished (sD2H)
     // phase 1 (descriptor upload + member pass) of the blocks behind the second one is enqueued by raftx_sweep_launch, one
     // block ahead of the block being launched: the caller's arrays (alive until the batch has been waited for) and the
     // batch's device offsets are kept for that
-    BuildSource p1;
+    BuildSource p1{};
     size_t next_p1 = 0;                  // first block whose phase 1 has not been enqueued yet
-    std::chrono::steady_clock::time_point t0;                             // raftx_sweep_prepare was entered
+    std::chrono::steady_clock::time_point t0{};                           // raftx_sweep_prepare was entered
     double since() const { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }   // host ms
     double tl[4] = {0, 0, 0, 0};
     double span[2] = {0, 0};             // fused launches of the crossing last waited for: start / end, ms since the ctx epoch
@@ -1015,7 +849,7 @@ struct SweepSlot {
         const double *dM = nullptr, *dC = nullptr;   // device copies [nDesign,36] (in S.allocs), or null
         double *fn = nullptr, *modes = nullptr, *props = nullptr;   // the caller's outputs, filled by raftx_sweep_wait
         int32_t *flags = nullptr;
-        hipEvent_t evUp = nullptr;       // the copies of dM / dC have landed (sCopy)
+        Event evUp;                      // the copies of dM / dC have landed (sCopy)
     } modal;
     struct {                             // raftx_sweep_current: mean current loads of the crossing's designs
         bool on = false;
@@ -1024,7 +858,7 @@ struct SweepSlot {
         std::vector<double> host;        // speed | cos | sin [3,nCur] | Zref [nDesign]: the source of the copies below
         const double *par = nullptr, *Zref = nullptr;   // device copies (in S.allocs); Zref null: 0
         double *D = nullptr;             // the caller's output [nDesign,nCur,6], filled by raftx_sweep_wait
-        hipEvent_t evUp = nullptr;       // the copies have landed (sCopy)
+        Event evUp;                      // the copies have landed (sCopy)
     } current;
     struct {                             // raftx_sweep_channels: output channels of the crossing's (design, case) pairs
         bool on = false;
@@ -1032,7 +866,7 @@ struct SweepSlot {
         const double *L = nullptr;       // device copies (in S.allocs) [nL,nChan,3,6]
         const cplx *Gw = nullptr;        // [nG,nChan,6,nw], or null
         double *out = nullptr;           // the caller's output [nDesign,nCase,nChan], filled by raftx_sweep_wait
-        hipEvent_t evUp = nullptr;       // the copies have landed (sCopy)
+        Event evUp;                      // the copies have landed (sCopy)
     } channels;
     struct {                             // raftx_sweep_mooring: the mooring system of the crossing's designs
         bool on = false, add = false;
@@ -1041,8 +875,103 @@ struct SweepSlot {
         Pinned<double> pin;              // landing area: C | F | T | flags of the whole crossing
         double *C_out = nullptr, *F_out = nullptr, *T_out = nullptr, *Tstd_out = nullptr;   // the caller's, filled by raftx_sweep_wait
         int32_t *flags_out = nullptr;
-        hipEvent_t evUp = nullptr;       // the kernels have run and the landing area is filled (sCopy)
+        Event evUp;                      // the kernels have run and the landing area is filled (sCopy)
     } mooring;
+    // The one place that switches the requests of a crossing off: a request left on would fire at the next raftx_sweep_wait
+    // and copy into a caller's array that may be gone.
+    void clear_requests() { modal.on = current.on = channels.on = mooring.on = false; }
+};
+
+// The host state of a context.  Every resource is held by an owner (raftx_owned.h), so raftx_ctx_destroy ends in `delete c`
+// and THE DECLARATION ORDER OF THE MEMBERS IS THE TEARDOWN ORDER, reversed: a member may use what is declared ahead of it
+// until it is destroyed.  Hence: the streams first (destroyed last, after the events recorded and the buffers used on
+// them; raftx_ctx_destroy has waited for what was enqueued), then the events, then the pool ahead of every bag -- each bag
+// is back in the pool before the pool returns its blocks to the driver -- then the buffers outside the pool, the landing
+// areas and the satellites that hold owners of their own.  A new resource goes behind the last thing it depends on.
+struct raftx_ctx {
+    int device = 0;
+    char err[512] = {0};
+    // ---- streams
+    Stream stream;                       // every kernel that matters; borrowed from the parent in the block contexts of raftx_sweep_stats
+    Stream sAux;                         // side stream of the parent ctx: the reductions of the member pass run beside its scans
+    Stream sCopy, sPrep, sD2H, sGen;     // internal streams of raftx_sweep_stats (created on first use)
+    Stream sSlab[2];                     // with sGen: the streams the slabs of a crossing with responses out go to (SlabPlan)
+    Stream sD2Hhigh;                     // bulk download of the responses: a stream of the highest priority class, created when first needed
+    // ---- events
+    Event ev0, ev1;
+    Event evUp, evTot, evG0, evG1, evG2, evG3, evS0, evS1, evDone;   // build phases, statistics, block finished
+    Event evZ;                           // the first kernel of the member pass has run (phase 1)
+    Event evMem, evRed;                  // member pass done (preparation stream) / per-design reduction done (side stream)
+    Event evMoor;                        // C_moor has been added to the block's C0 (raftx_sweep_mooring, sCopy)
+    Event evEpoch;                       // zero of raftx_sweep_solve_span: recorded when the first crossing of the ctx is launched
+    std::vector<Event> evSlab;           // completion markers of the slabs (no timing), created as needed, kept
+    Event evFork, evJoin;
+    // ---- the pool, then the bags that hold its blocks
+    DevPool pool;
+    Bag design_allocs, case_allocs, result_allocs;
+    BuildJob job;
+    CaseSet csets[RAFTX_NSLOT + 1];      // sea-state tables of the sweep crossings: one per crossing in flight + one being replaced
+    unsigned long long cset_clock = 0;
+    DenseResident dense;                 // matrices kept for raftx_solve_dense_resident
+    VariantProg vprog;                   // raftx_variant_program
+    QtfResident qt;                      // raftx_qtf_tables_build
+    SweepSlot slots[RAFTX_NSLOT];        // crossings in flight (raftx_sweep_prepare / _launch / _wait)
+    // ---- buffers outside the pool
+    DevBuf<double> rXl;
+    DevBuf<cplx> flexXl0;                // raftx_flex_start: the linearisation point of the next raftx_flex_solve (device copy)
+    size_t flexXl0_n = 0;                // entries set (0: none)
+    DevBuf<unsigned long long> rXlSlots;
+    DevBuf<unsigned> kpCtr;              // claim counters of the persistent fused launches: a ring of KP_RING sets of 8 (one per XCD slab, 128 B apart)
+    DevBuf<cplx> rQtf;                   // QTFs of the last raftx_qtf_slender call, kept for raftx_qtf_force
+    DevBuf<cplx> rXl0, rXlOut;           // optional restart point / exported linearisation point [npair,6,nw]: both or neither
+    DevBuf<int> pairList;                // device pair lists of a launch split into LDS classes
+    DevBuf<int> identList;               // 0, 1, 2, ..: the pair list of a launch cut into slabs (SlabPlan)
+    DevBuf<unsigned long long> dbg;
+    DevBuf<cplx> rKay;                   // Kim & Yue table of raftx_qtf_kay, consumed by the next raftx_qtf_slender call
+    DevBuf<cplx> bemF;                   // resident BEM (+ added) excitation of raftx_bem_excitation [npair,nHead,6,nw]
+    DevBuf<int> commFlag;                // one int in HBM: the status word the ranks agree on before an exchange step (comm_agree)
+    struct {                             // raftx_mooring_program: base records and the affine edits of their end points
+        int nLine = 0, nP = 0;
+        DevBuf<double> base, coef;
+        DevBuf<int> edit;
+    } mprog;
+    // ---- page-locked landing areas
+    Pinned<long long> pin;               // landing area of the build totals and offsets [PIN_OFF + nDesign + 1]
+    Pinned<double> pinRes;               // ... of a block's statistics (sweep crossing)
+    Pinned<double> pinModal;             // ... of a block's eigen analysis (raftx_sweep_modal)
+    Pinned<double> pinCur;               // ... of a block's current loads (raftx_sweep_current)
+    Pinned<double> pinChan;              // ... of a block's output channels (raftx_sweep_channels) [pairs,nChan]
+    Pinned<double> pinMoorT;             // ... of a block's tension statistics (raftx_sweep_mooring) [pairs,2 nLine]
+    // ---- plain state
+    DevTables T{};
+    // resident results of the last raftx_solve_dynamics_device (device pointers owned by result_allocs)
+    cplx *rXi = nullptr, *rFw = nullptr, *rZ = nullptr, *rFe = nullptr;
+    double *rB = nullptr;
+    int *rNi = nullptr, *rFl = nullptr;
+    size_t r_npair = 0, r_nx = 0, r_nz = 0;
+    int r_mask = 0;
+    int r_last_mask = 0;                 // RAFTX_WANT_* outputs the LAST fused solve wrote (r_mask: what the buffers could hold)
+    bool r_fe = false;
+    unsigned kpNext = 0;
+    int nCU = 0;                         // compute units of the device (the persistent grid is what they hold at once)
+    int last_flags = -1, last_minb = 0, last_rc = 0;       // specialisation of the last fused-kernel launch (raftx_last_solve_kernel)
+    int rQtf_sets = 0, rQtf_nw2 = 0, rKay_sets = 0, rKay_nw2 = 0;
+    bool have_xl0 = false, want_xlout = false;
+    int maxS = 0;
+    std::vector<int> hS;                 // submerged strips of every design (host copy: LDS classes of the fused kernel)
+    double last_ms = 0.0;
+    bool have_designs = false, have_cases = false;
+    int nw_designs = 0;
+    bool kay_ready = false, bem_ready = false;
+    // results of the last raftx_build_designs (device pointers owned by design_allocs)
+    int g_n = 0;
+    size_t g_nStrips = 0, g_nRows = 0;
+    double *g_abi = nullptr, *g_A = nullptr, *g_Ch = nullptr, *g_Wh = nullptr, *g_props = nullptr, *g_Ms = nullptr, *g_Cs = nullptr, *g_Ws = nullptr;
+    bool last_gen_fused = false;         // the last fused launch generated its designs' tables itself (raftx_fusedgen.h)
+    cplx *g_cm = nullptr;
+    void *comm = nullptr;                // ncclComm_t of raftx_comm_init (RCCL), or null
+    int comm_rank = 0, comm_world = 1;
+    std::vector<raftx_ctx *> workers[RAFTX_NSLOT]; // block contexts of the sweep crossings (device buffers, pool, events), per slot, kept for reuse; destroyed by raftx_ctx_destroy
 };
 
 #define MAX_NW 2048
@@ -1080,86 +1009,32 @@ extern "C" int raftx_ctx_create(int device_id, raftx_ctx **out) {
     if (device_id < 0 || device_id >= ndev) return -4;
     if (hipSetDevice(device_id) != hipSuccess) return -5;
     raftx_ctx *c = new raftx_ctx();
-    memset(&c->T, 0, sizeof(c->T));
     c->device = device_id;
-    c->err[0] = 0;
-    c->maxS = 0;
-    c->pairList = nullptr;
-    c->pairList_n = 0;
-    c->dbg = nullptr;
-    c->last_ms = 0.0;
-    c->have_designs = c->have_cases = false;
-    c->nw_designs = 0;
-    c->g_n = 0;
-    c->bemF = nullptr;
-    c->bemF_n = 0;
-    c->bem_ready = false;
-    c->rKay = nullptr;
-    c->rKay_n = 0;
-    c->rKay_sets = c->rKay_nw2 = 0;
-    c->kay_ready = false;
-    c->rXi = c->rFw = c->rZ = c->rFe = nullptr;
-    c->rB = c->rXl = nullptr;
-    c->rXlSlots = nullptr;
-    c->flexXl0 = nullptr;
-    c->flexXl0_n = c->flexXl0_cap = 0;
-    c->rXl_n = 0;
-    c->rQtf = nullptr;
-    c->rQtf_n = 0;
-    c->rQtf_sets = c->rQtf_nw2 = 0;
-    c->rXl0 = c->rXlOut = nullptr;
-    c->rXlio_n = 0;
-    c->have_xl0 = c->want_xlout = false;
-    c->rNi = c->rFl = nullptr;
-    c->r_npair = c->r_nx = c->r_nz = 0;
-    c->r_mask = 0;
-    c->r_fe = false;
-    c->comm = nullptr;
-    c->comm_rank = 0;
-    c->comm_world = 1;
-    c->owns_stream = true;
-    c->slots = new SweepSlot[RAFTX_NSLOT];
-    c->sCopy = c->sPrep = c->sD2H = c->sGen = nullptr;
     // the ctx stream -- the fused fixed points, table generation, statistics -- is of the default priority class (a high one
     // lost: profiles/MEASUREMENT_HISTORY.md, "Closed scheduling experiments of the crossing")
-    bool ok = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) == hipSuccess;
-    c->sAux = nullptr;
-    for (hipEvent_t *e : {&c->evZ, &c->ev0, &c->ev1, &c->evUp, &c->evTot, &c->evG0, &c->evG1, &c->evG2, &c->evG3, &c->evS0,
-                          &c->evS1, &c->evDone, &c->evMem, &c->evRed})
-        ok = ok && hipEventCreate(e) == hipSuccess;
+    bool ok = c->stream.ensure(hipStreamNonBlocking) == hipSuccess;
+    for (Event *e : {&c->evZ, &c->ev0, &c->ev1, &c->evUp, &c->evTot, &c->evG0, &c->evG1, &c->evG2, &c->evG3, &c->evS0,
+                     &c->evS1, &c->evDone, &c->evMem, &c->evRed})
+        ok = ok && e->ensure() == hipSuccess;
     if (!ok) {
-        delete[] c->slots;
-        delete c;
+        delete c;                                     // releases what was created
         return -6;
     }
     *out = c;
     return 0;
 }
 
-static void free_list(raftx_ctx *c, std::vector<void *> &v) {
-    for (void *p : v) c->pool.put(p);
-    v.clear();
-}
+// The variant program of a ctx, its fixed members' records and their events; the mooring program.  Both by move
+// assignment of a fresh value: the owners inside (Bag, Event, DevBuf) release what they hold before they take the new one.
+static void variant_release(raftx_ctx *c) { c->vprog = VariantProg(); }
+static void mooring_program_release(raftx_ctx *c) { c->mprog = {}; }
 
-// the variant program of a ctx, its fixed members' records and their events
-static void variant_release(raftx_ctx *c) {
-    for (FixedRecord &R : c->vprog.recs)
-        if (R.ev) (void)hipEventDestroy(R.ev);
-    free_list(c, c->vprog.allocs);
-    c->vprog = VariantProg();
-}
-static void mooring_program_release(raftx_ctx *c) {
-    if (c->mprog.base) (void)hipFree(c->mprog.base);
-    if (c->mprog.coef) (void)hipFree(c->mprog.coef);
-    if (c->mprog.edit) (void)hipFree(c->mprog.edit);
-    c->mprog.base = c->mprog.coef = nullptr;
-    c->mprog.edit = nullptr;
-    c->mprog.nLine = c->mprog.nP = 0;
-}
+// Only the ordered steps: everything the ctx holds is released by its owners, in the reverse of the declaration order of
+// raftx_ctx (see there).
 extern "C" void raftx_ctx_destroy(raftx_ctx *c) {
     if (!c) return;
 #ifdef GEOM_PHASE_TIMING
-    if (c->owns_stream && c->slots) {
+    if (c->stream.owned) {
         unsigned long long ph[10] = {0};
         (void)hipDeviceSynchronize();
         if (hipMemcpyFromSymbol(ph, HIP_SYMBOL(geom_phase_cycles), sizeof(ph)) == hipSuccess && ph[0]) {
@@ -1172,7 +1047,7 @@ extern "C" void raftx_ctx_destroy(raftx_ctx *c) {
     }
 #endif
     (void)raftx_comm_destroy(c);
-    if (c->owns_stream) {                             // a crossing prepared and never launched still has work on sCopy / sPrep
+    if (c->stream.owned) {                            // a crossing prepared and never launched still has work on sCopy / sPrep
         (void)hipSetDevice(c->device);
         (void)hipDeviceSynchronize();
     }
@@ -1182,56 +1057,6 @@ extern "C" void raftx_ctx_destroy(raftx_ctx *c) {
     }
     (void)hipSetDevice(c->device);
     (void)hipStreamSynchronize(c->stream);
-    free_list(c, c->design_allocs);
-    free_list(c, c->case_allocs);
-    free_list(c, c->result_allocs);
-    free_list(c, c->qt.allocs);
-    for (CaseSet &cs : c->csets) free_list(c, cs.allocs);
-    c->pool.trim();
-    if (c->rXl) (void)hipFree(c->rXl);
-    if (c->rXlSlots) (void)hipFree(c->rXlSlots);
-    if (c->kpCtr) (void)hipFree(c->kpCtr);
-    if (c->flexXl0) (void)hipFree(c->flexXl0);
-    if (c->rXl0) (void)hipFree(c->rXl0);
-    if (c->rXlOut) (void)hipFree(c->rXlOut);
-    if (c->rQtf) (void)hipFree(c->rQtf);
-    if (c->bemF) (void)hipFree(c->bemF);
-    if (c->rKay) (void)hipFree(c->rKay);
-    if (c->pairList) (void)hipFree(c->pairList);
-    free_list(c, c->dense.allocs);
-    variant_release(c);
-    mooring_program_release(c);
-    if (c->identList) (void)hipFree(c->identList);
-    for (hipEvent_t e : c->evSlab) (void)hipEventDestroy(e);
-    if (c->evFork) (void)hipEventDestroy(c->evFork);
-    if (c->evJoin) (void)hipEventDestroy(c->evJoin);
-    free_list(c, c->job.tmp);
-    for (int sl = 0; sl < RAFTX_NSLOT; sl++) {
-        free_list(c, c->slots[sl].allocs);
-        if (c->slots[sl].evXi) (void)hipEventDestroy(c->slots[sl].evXi);
-        if (c->slots[sl].modal.evUp) (void)hipEventDestroy(c->slots[sl].modal.evUp);
-        if (c->slots[sl].current.evUp) (void)hipEventDestroy(c->slots[sl].current.evUp);
-        if (c->slots[sl].channels.evUp) (void)hipEventDestroy(c->slots[sl].channels.evUp);
-        if (c->slots[sl].mooring.evUp) (void)hipEventDestroy(c->slots[sl].mooring.evUp);
-        c->slots[sl].mooring.pin.release();
-    }
-    delete[] c->slots;
-    c->pool.trim();
-    c->pin.release();
-    c->pinRes.release();
-    c->pinModal.release();
-    c->pinCur.release();
-    c->pinChan.release();
-    c->pinMoorT.release();
-    if (c->evMoor) (void)hipEventDestroy(c->evMoor);
-    for (hipEvent_t e : {c->evZ, c->ev0, c->ev1, c->evUp, c->evTot, c->evG0, c->evG1, c->evG2, c->evG3, c->evS0, c->evS1, c->evDone,
-                         c->evMem, c->evRed})
-        (void)hipEventDestroy(e);
-    if (c->sAux) (void)hipStreamDestroy(c->sAux);
-    if (c->evEpoch) (void)hipEventDestroy(c->evEpoch);
-    for (hipStream_t st : {c->sCopy, c->sPrep, c->sD2H, c->sGen, c->sD2Hhigh, c->sSlab[0], c->sSlab[1]})
-        if (st) (void)hipStreamDestroy(st);
-    if (c->owns_stream) (void)hipStreamDestroy(c->stream);
     delete c;
 }
 
@@ -1270,21 +1095,17 @@ extern "C" const char *raftx_last_error(raftx_ctx *c) { return c ? c->err : "nul
 extern "C" double raftx_last_kernel_ms(raftx_ctx *c) { return c ? c->last_ms : 0.0; }
 
 // ---- device memory owned by a bag: a block of the ctx pool for n elements, remembered in `bag` (design_allocs, a job's
-// tmp, a slot's allocs, ..), which goes back to the pool as a whole (free_list).  A zero count still gives a valid,
+// tmp, a slot's allocs, ..), which goes back to the pool as a whole (Bag::release).  A zero count still gives a valid,
 // never-read block.
 template <typename Tp>
-static int pool_alloc(raftx_ctx *c, std::vector<void *> &bag, size_t n, Tp **out) {
-    *out = nullptr;
-    void *p = nullptr;
-    HIPCHK(c, c->pool.get((n ? n : 1) * sizeof(Tp), &p));
-    bag.push_back(p);
-    *out = reinterpret_cast<Tp *>(p);
+static int pool_alloc(raftx_ctx *c, Bag &bag, size_t n, Tp **out) {
+    HIPCHK(c, bag.get(c->pool, n, out));
     return 0;
 }
 // ... filled from host memory by a copy enqueued on `st`.  An absent or empty host array takes no block and gives a NULL
 // device pointer: the kernels test the optional tables for it.
 template <typename Tp, typename Dp>
-static int upload_on(raftx_ctx *c, hipStream_t st, std::vector<void *> &bag, const Tp *host, size_t n, Dp *dev) {
+static int upload_on(raftx_ctx *c, hipStream_t st, Bag &bag, const Tp *host, size_t n, Dp *dev) {
     *dev = nullptr;
     if (!host || n == 0) return 0;
     Tp *p = nullptr;
@@ -1294,7 +1115,7 @@ static int upload_on(raftx_ctx *c, hipStream_t st, std::vector<void *> &bag, con
     return 0;
 }
 template <typename Tp, typename Dp>
-static int upload(raftx_ctx *c, std::vector<void *> &bag, const Tp *host, size_t n, Dp *dev) { return upload_on(c, c->stream, bag, host, n, dev); }
+static int upload(raftx_ctx *c, Bag &bag, const Tp *host, size_t n, Dp *dev) { return upload_on(c, c->stream, bag, host, n, dev); }
 
 extern "C" int raftx_upload_designs(raftx_ctx *c, int nDesign, const int64_t *stripOffsets, const double *strips,
                                     int nStripFields, const double *M0, const double *B0, const double *C0, int nw,
@@ -1305,7 +1126,7 @@ extern "C" int raftx_upload_designs(raftx_ctx *c, int nDesign, const int64_t *st
     if (nDesign < 0 || !stripOffsets || !M0 || !B0 || !C0) FAIL(c, "upload_designs: bad arguments");
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    free_list(c, c->design_allocs);
+    c->design_allocs.release();
     c->have_designs = false;
     c->bem_ready = false;
     int maxS = 0;
@@ -1394,7 +1215,7 @@ static int slice_of(raftx_ctx *c, const BuildSource &B, int lo, int nDesign, Sli
 static int upload_descriptors(raftx_ctx *c, hipStream_t sCopy, const BuildSource &B, const Slice &L, ExpandArgs &E) {
     BuildJob &J = c->job;
     GeomArgs &A = J.A;
-    std::vector<void *> &tmp = J.tmp, &keep = c->design_allocs;
+    Bag &tmp = J.tmp, &keep = c->design_allocs;
     const size_t lo = (size_t)L.lo, nDesign = (size_t)A.nDesign, nMember = (size_t)A.nMember, nw = (size_t)B.nw;
     const size_t nSta = (size_t)(L.s1 - L.s0), nCap = (size_t)(L.c1 - L.c0);
     int rc = 0;
@@ -1454,7 +1275,7 @@ static int upload_descriptors(raftx_ctx *c, hipStream_t sCopy, const BuildSource
 // that use it); kept with the tables: the offsets the scans leave and the per-design results of the reductions
 static int alloc_member_scratch(raftx_ctx *c) {
     GeomArgs &A = c->job.A;
-    std::vector<void *> &tmp = c->job.tmp, &keep = c->design_allocs;
+    Bag &tmp = c->job.tmp, &keep = c->design_allocs;
     const size_t nDesign = (size_t)A.nDesign, nMember = (size_t)A.nMember;
     if (pool_alloc(c, tmp, nMember, &A.cnt) || pool_alloc(c, tmp, nMember, &A.cntm) || pool_alloc(c, tmp, nMember * MP_N, &A.mpose) ||
         pool_alloc(c, tmp, nMember * MH_N, &A.mhyd) || pool_alloc(c, tmp, nMember * MI_N, &A.minert) || pool_alloc(c, tmp, 4, &A.err) ||
@@ -1521,7 +1342,7 @@ static int enqueue_scan_reduce(raftx_ctx *c, hipStream_t sPrep) {
     if (side) {
         HIPCHK(c, hipEventRecord(c->evMem, sPrep));
         if (scan()) return -2;
-        if (!c->sAux) HIPCHK(c, hipStreamCreateWithFlags(&c->sAux, hipStreamNonBlocking));
+        HIPCHK(c, c->sAux.ensure(hipStreamNonBlocking));
         sRed = c->sAux;
         HIPCHK(c, hipStreamWaitEvent(sRed, c->evMem, 0));
     }
@@ -1538,8 +1359,8 @@ static int build_phase1(raftx_ctx *c, hipStream_t sCopy, hipStream_t sPrep, cons
     Slice L;
     if (int rc = slice_of(c, B, lo, nDesign, L)) return rc;
     HIPCHK(c, hipSetDevice(c->device));
-    free_list(c, c->design_allocs);               // callers guarantee that nothing in flight reads the previous tables
-    free_list(c, J.tmp);
+    c->design_allocs.release();               // callers guarantee that nothing in flight reads the previous tables
+    J.tmp.release();
     c->have_designs = false; c->bem_ready = false; c->g_n = 0;
     HIPCHK(c, c->pin.reserve(PIN_OFF + (size_t)nDesign + 1));
     GeomArgs &A = J.A;
@@ -1677,7 +1498,7 @@ static int build_phase2(raftx_ctx *c, int64_t *stripOffsets, hipStream_t sGen = 
     if (int rc = wait_totals(c, stripOffsets)) return rc;
     // the ABI copy of the strip records (raftx_fetch_strips) is for raftx_build_designs; a sweep crossing never
     // fetches it: 137 MB of stores per 10 000 designs less between two fused kernels (k_geom_design checks the pointer)
-    std::vector<void *> &keep = c->design_allocs;
+    Bag &keep = c->design_allocs;
     A.abi = nullptr;
     if ((!kind && pool_alloc(c, keep, J.nStrips * NF, &A.abi)) || pool_alloc(c, keep, J.nStrips * DS_N, &A.ds) ||
         pool_alloc(c, keep, J.nStrips, &A.dsi) || pool_alloc(c, keep, J.nRows * 3, &A.mcfaux) ||
@@ -1689,7 +1510,7 @@ static int build_phase2(raftx_ctx *c, int64_t *stripOffsets, hipStream_t sGen = 
 }
 // a build that will not be finished, or has been (the caller has drained the device): its scratch back to the pool
 static void build_abandon(raftx_ctx *c) {
-    free_list(c, c->job.tmp);
+    c->job.tmp.release();
     c->job.active = false;
 }
 // kernel time of a finished build (both phases), and its scratch back to the pool
@@ -1768,7 +1589,7 @@ extern "C" int raftx_fetch_statics(raftx_ctx *c, double *A_morison, double *C_hy
 
 // The sea-state tables of one set of cases into device memory of ctx `c` (allocations into `bag`, fields into `T`), copied
 // on `st`, which has drained when this returns (the depth constants are host temporaries).
-static int upload_case_tables(raftx_ctx *c, hipStream_t st, std::vector<void *> &bag, DevTables &T, const SeaStates &sea) {
+static int upload_case_tables(raftx_ctx *c, hipStream_t st, Bag &bag, DevTables &T, const SeaStates &sea) {
     const int nCase = sea.nCase, nHead = sea.nHead, nw = sea.nw;
     const double *k = sea.k, depth = sea.depth;
     // per-bin depth constants, computed once on the host in full libm precision.  The kernels derive
@@ -1807,7 +1628,7 @@ extern "C" int raftx_upload_cases(raftx_ctx *c, int nCase, int nHead, int nw, co
     if (nw > MAX_NW) FAIL(c, "nw=%d exceeds the %d bins per workgroup supported by this build", nw, MAX_NW);
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    free_list(c, c->case_allocs);
+    c->case_allocs.release();
     c->have_cases = false;
     c->bem_ready = false;
     if (int rc = upload_case_tables(c, c->stream, c->case_allocs, c->T, SeaStates{nCase, nHead, nw, w, k, depth, rho, g, zeta, beta})) return rc;
@@ -1863,30 +1684,17 @@ static int prep_lds(raftx_ctx *c, const void *kernel, size_t bytes) {
 }
 #define NO_KERNEL(c, sh) FAIL(c, "no kernel for shape %d x %d", (sh).nb, (sh).threads)
 
-// Device buffers the ctx keeps outside the pool and regrows on demand.  Drains what may still use the old block (the ctx
-// stream, or the whole device), frees it and allocates room for want_n elements (at least one); on failure the pointer
-// is null and the size zero.  WHEN a buffer grows is its caller's rule.
+// Device buffers the ctx keeps outside the pool and regrows on demand: nothing to do while the block holds want_n
+// elements (FIT_EXACT: exactly want_n, for the buffers whose count is their shape); otherwise drains what may still use the
+// old block (the ctx stream, or the whole device -- the owner itself never synchronises) and lets the buffer grow; on
+// failure it is empty.
 enum Drain { DRAIN_STREAM, DRAIN_DEVICE };
+enum Fit { FIT_AT_LEAST, FIT_EXACT };
 template <typename Tp>
-static int grow_device(raftx_ctx *c, Tp **ptr, size_t *have_n, size_t want_n, Drain drain = DRAIN_STREAM) {
+static int grow_device(raftx_ctx *c, DevBuf<Tp> &buf, size_t want_n, Drain drain = DRAIN_STREAM, Fit fit = FIT_AT_LEAST) {
+    if (fit == FIT_EXACT ? (buf.p && buf.n == want_n) : buf.holds(want_n)) return 0;
     HIPCHK(c, drain == DRAIN_DEVICE ? hipDeviceSynchronize() : hipStreamSynchronize(c->stream));
-    if (*ptr) (void)hipFree(*ptr);
-    *ptr = nullptr;
-    *have_n = 0;
-    void *p_ = nullptr;
-    HIPCHK(c, hipMalloc(&p_, (want_n ? want_n : 1) * sizeof(Tp)));
-    *ptr = reinterpret_cast<Tp *>(p_);
-    *have_n = want_n;
-    return 0;
-}
-// allocated and zeroed (in the order of the ctx stream) the first time only
-template <typename Tp>
-static int zeroed_once(raftx_ctx *c, Tp **ptr, size_t n) {
-    if (*ptr) return 0;
-    void *p_ = nullptr;
-    HIPCHK(c, hipMalloc(&p_, n * sizeof(Tp)));
-    *ptr = reinterpret_cast<Tp *>(p_);
-    HIPCHK(c, hipMemsetAsync(*ptr, 0, n * sizeof(Tp), c->stream));
+    HIPCHK(c, buf.grow(want_n));
     return 0;
 }
 
@@ -1902,19 +1710,14 @@ static int check_ready(raftx_ctx *c) {
 // device scratch that lives for one call
 struct Scratch {
     raftx_ctx *c;
-    std::vector<void *> bag;
+    Bag bag;
     explicit Scratch(raftx_ctx *c_) : c(c_) {}
-    ~Scratch() {
-        (void)hipStreamSynchronize(c->stream);      // blocks go back to the pool only when nothing in flight uses them
-        free_list(c, bag);
-    }
+    ~Scratch() { (void)hipStreamSynchronize(c->stream); }   // ahead of the bag's release: blocks go back to the pool only when nothing in flight uses them
     template <typename Tp>
-    Tp *alloc(size_t n) {
-        void *p = nullptr;
-        if (n == 0) return nullptr;
-        if (c->pool.get(n * sizeof(Tp), &p) != hipSuccess) return nullptr;
-        bag.push_back(p);
-        return reinterpret_cast<Tp *>(p);
+    Tp *alloc(size_t n) {                           // null for a zero count, and when the pool has no room
+        Tp *p = nullptr;
+        if (n) (void)bag.get(c->pool, n, &p);
+        return p;
     }
 };
 
@@ -2058,11 +1861,9 @@ extern "C" int raftx_strip_drag(raftx_ctx *c, int design, int icase, const raftx
 
 template <typename Tp>
 static Tp *dev_alloc(raftx_ctx *c, size_t n) {
-    void *p = nullptr;
-    if (n == 0) n = 1;
-    if (c->pool.get(n * sizeof(Tp), &p) != hipSuccess) return nullptr;
-    c->result_allocs.push_back(p);
-    return reinterpret_cast<Tp *>(p);
+    Tp *p = nullptr;
+    (void)c->result_allocs.get(c->pool, n, &p);
+    return p;
 }
 
 // (re)size the ctx-owned result buffers for the current designs x cases
@@ -2074,7 +1875,7 @@ static int ensure_results(raftx_ctx *c, int want_mask, bool need_fe) {
               (c->r_mask & want_mask) == want_mask && (!need_fe || c->r_fe);
     if (ok) return 0;
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    free_list(c, c->result_allocs);
+    c->result_allocs.release();
     c->rXi = c->rFw = c->rZ = c->rFe = nullptr;
     c->rB = nullptr;
     c->rNi = c->rFl = nullptr;
@@ -2087,7 +1888,7 @@ static int ensure_results(raftx_ctx *c, int want_mask, bool need_fe) {
     if (need_fe) c->rFe = dev_alloc<cplx>(c, nx);
     if (!c->rXi || !c->rNi || !c->rFl || ((want_mask & RAFTX_WANT_BDRAG) && !c->rB) ||
         ((want_mask & RAFTX_WANT_FWAVE) && !c->rFw) || ((want_mask & RAFTX_WANT_Z) && !c->rZ) || (need_fe && !c->rFe)) {
-        free_list(c, c->result_allocs);
+        c->result_allocs.release();
         c->rXi = nullptr;
         FAIL(c, "solve_dynamics: device allocation of result buffers failed");
     }
@@ -2147,14 +1948,14 @@ static int launch_persistent(raftx_ctx *c, kp_fn kernel, const DevTables &T, con
         HIPCHK(c, hipGetDeviceProperties(&pr, c->device));
         c->nCU = pr.multiProcessorCount > 0 ? pr.multiProcessorCount : 256;
     }
-    if (zeroed_once(c, &c->kpCtr, (size_t)KP_RING * 9 * KP_CTR_STRIDE)) return -2;   // once: every launch leaves its set zeroed (kp_leave)
+    HIPCHK(c, c->kpCtr.zeroed_once((size_t)KP_RING * 9 * KP_CTR_STRIDE, c->stream));   // once: every launch leaves its set zeroed (kp_leave)
     if (lds > 64 * 1024)
         HIPCHK(c, hipFuncSetAttribute(gen ? reinterpret_cast<const void *>(raftx_kpg_f0) : reinterpret_cast<const void *>(kernel),
                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     PersistArgs P;
     P.T = T;
     P.A = A;
-    P.ctr = c->kpCtr + (size_t)(c->kpNext++ % KP_RING) * 9 * KP_CTR_STRIDE;   // (a set is reused KP_RING launches of this ctx later)
+    P.ctr = c->kpCtr.p + (size_t)(c->kpNext++ % KP_RING) * 9 * KP_CTR_STRIDE;   // (a set is reused KP_RING launches of this ctx later)
     P.xl_base = XL_SLOTS;
     static const int grid_env = getenv("RAFTX_KP_GRID") ? atoi(getenv("RAFTX_KP_GRID")) : 0;      // tuning: workgroups of the grid
     size_t grid = (size_t)(grid_env > 0 ? grid_env : wg_per_cu * c->nCU);
@@ -2282,24 +2083,19 @@ static int ensure_xl_scratch(raftx_ctx *c, const LaunchPlan &lp) {
 #endif
     const size_t want = xl_regions * 12 * (size_t)lp.nw;
     // (the whole device: fused kernels of the other streams may hold slots of the old slab)
-    if ((!c->rXl || c->rXl_n < want) && grow_device(c, &c->rXl, &c->rXl_n, want, DRAIN_DEVICE)) return -2;
-    return zeroed_once(c, &c->rXlSlots, (size_t)XL_POOLS * XL_POOL_WORDS);      // ahead of this ctx's launches, in stream order
+    if (grow_device(c, c->rXl, want, DRAIN_DEVICE)) return -2;
+    HIPCHK(c, c->rXlSlots.zeroed_once((size_t)XL_POOLS * XL_POOL_WORDS, c->stream));   // ahead of this ctx's launches, in stream order
+    return 0;
 }
 // the restart point and the exported linearisation point, [npair,6,nw] each: both or neither
 static int ensure_xlio(raftx_ctx *c, size_t nxl) {
-    if (c->rXlio_n == nxl && c->rXl0 && c->rXlOut) return 0;
-    size_t n0 = 0, n1 = 0;
-    c->rXlio_n = 0;
-    int rc = grow_device(c, &c->rXl0, &n0, nxl);
-    if (!rc) rc = grow_device(c, &c->rXlOut, &n1, nxl);
+    int rc = grow_device(c, c->rXl0, nxl, DRAIN_STREAM, FIT_EXACT);   // (their count is the batch shape: a smaller nxl replaces them too)
+    if (!rc) rc = grow_device(c, c->rXlOut, nxl, DRAIN_STREAM, FIT_EXACT);
     if (rc) {
-        if (c->rXl0) (void)hipFree(c->rXl0);
-        if (c->rXlOut) (void)hipFree(c->rXlOut);
-        c->rXl0 = c->rXlOut = nullptr;
-        return rc;
+        c->rXl0.release();
+        c->rXlOut.release();
     }
-    c->rXlio_n = nxl;
-    return 0;
+    return rc;
 }
 
 // LDS classes: the workgroups of a launch all get the LDS of its largest design, and the number of pairs a CU holds
@@ -2322,7 +2118,7 @@ static int lds_classes(raftx_ctx *c, const LaunchPlan &lp, LdsClasses *out) {
     bool mixed = false;
     for (int d = 0; d < T.nDesign; d++) mixed |= (k_of[(size_t)d] = fit(c->hS[(size_t)d])) != k_of[0];
     if (!mixed) return 0;
-    if (c->pairList_n < c->r_npair && grow_device(c, &c->pairList, &c->pairList_n, c->r_npair)) return -2;
+    if (grow_device(c, c->pairList, c->r_npair)) return -2;
     out->pairs.reserve((size_t)T.nDesign * T.nCase);       // (no reallocation under the uploads)
     for (int kk = fit(0); kk >= 0; kk--) {
         LdsClasses::Class k = {0, 0};
@@ -2333,19 +2129,19 @@ static int lds_classes(raftx_ctx *c, const LaunchPlan &lp, LdsClasses *out) {
             k.S = std::max(k.S, c->hS[(size_t)d]);
         }
         if (!(k.npairs = out->pairs.size() - at)) continue;
-        H2D(c, c->pairList + at, out->pairs.data() + at, k.npairs * sizeof(int));
+        H2D(c, c->pairList.p + at, out->pairs.data() + at, k.npairs * sizeof(int));
         out->cls.push_back(k);
     }
     return 0;
 }
 // what a launch in slabs needs: the identity pair list and the fork / join events
 static int ensure_slab_list(raftx_ctx *c) {
-    if (c->identList_n < c->r_npair) {
-        if (grow_device(c, &c->identList, &c->identList_n, c->r_npair)) return -2;
-        hipLaunchKernelGGL(k_iota, dim3((unsigned)((c->r_npair + 255) / 256)), dim3(256), 0, c->stream, (int)c->r_npair, c->identList);
+    if (!c->identList.holds(c->r_npair)) {
+        if (grow_device(c, c->identList, c->r_npair)) return -2;
+        hipLaunchKernelGGL(k_iota, dim3((unsigned)((c->r_npair + 255) / 256)), dim3(256), 0, c->stream, (int)c->r_npair, c->identList.p);
     }
-    if (!c->evFork) HIPCHK(c, hipEventCreateWithFlags(&c->evFork, hipEventDisableTiming));
-    if (!c->evJoin) HIPCHK(c, hipEventCreateWithFlags(&c->evJoin, hipEventDisableTiming));
+    HIPCHK(c, c->evFork.ensure(hipEventDisableTiming));
+    HIPCHK(c, c->evJoin.ensure(hipEventDisableTiming));
     return 0;
 }
 // A generation deferred to this launch (build_phase2): the generating form of the plain persistent kernel builds every
@@ -2383,7 +2179,7 @@ static int launch_slabs(raftx_ctx *c, const LaunchPlan &lp, SolveArgs A, size_t 
         HIPCHK(c, hipStreamWaitEvent(plan->alts[(plan->next + k) % plan->alts.size()], c->evFork, 0));
     for (size_t k = 0; k + 1 < plan->bnd.size() && !*rc_after; k++) {
         hipStream_t s = plan->alts[plan->next++ % plan->alts.size()];
-        A.pairs = c->identList + plan->bnd[k];
+        A.pairs = c->identList.p + plan->bnd[k];
         A.npairs = (int)(plan->bnd[k + 1] - plan->bnd[k]);
         hipLaunchKernelGGL(lp.k.fn, dim3(grid_for_pairs((size_t)A.npairs)), dim3(lp.sh.threads), lds, s, c->T, A);
         if (plan->after) *rc_after = plan->after(plan->bnd[k], plan->bnd[k + 1], s);
@@ -2394,7 +2190,7 @@ static int launch_slabs(raftx_ctx *c, const LaunchPlan &lp, SolveArgs A, size_t 
 static void launch_classes(raftx_ctx *c, const LaunchPlan &lp, SolveArgs A, const LdsClasses &classes) {
     size_t at = 0;
     for (const LdsClasses::Class &k : classes.cls) {
-        A.pairs = c->pairList + at;
+        A.pairs = c->pairList.p + at;
         A.npairs = (int)k.npairs;
         at += k.npairs;
         A.rc_n = lp.rc_slots(k.S);
@@ -2412,7 +2208,7 @@ static int fill_solve_args(raftx_ctx *c, int nIter, double tol, double XiStart, 
     A.nIter = nIter + 1;
     A.tol = tol;
     A.XiStart = XiStart;
-    A.F_extra = F_extra ? c->rFe : (c->bem_ready ? c->bemF : nullptr);
+    A.F_extra = F_extra ? c->rFe : (c->bem_ready ? c->bemF.p : nullptr);
     A.Xi = c->rXi;
     A.niter = c->rNi;
     A.flags = c->rFl;
@@ -2427,10 +2223,10 @@ static int fill_solve_args(raftx_ctx *c, int nIter, double tol, double XiStart, 
     A.dbg = nullptr;
 #ifdef RAFTX_PHASE_TIMING
     const size_t ndbg = 10 + 2 * PT_CLOCK_BUCKETS;
-    if (zeroed_once(c, &c->dbg, ndbg)) return -2;
-    HIPCHK(c, hipMemsetAsync(c->dbg, 0, ndbg * sizeof(unsigned long long), c->stream));
-    HIPCHK(c, hipMemsetAsync(c->dbg + 8, 0xFF, sizeof(unsigned long long), c->stream));      // earliest start: a minimum
-    A.dbg = c->dbg;
+    HIPCHK(c, c->dbg.zeroed_once(ndbg, c->stream));
+    HIPCHK(c, hipMemsetAsync(c->dbg.p, 0, ndbg * sizeof(unsigned long long), c->stream));
+    HIPCHK(c, hipMemsetAsync(c->dbg.p + 8, 0xFF, sizeof(unsigned long long), c->stream));      // earliest start: a minimum
+    A.dbg = c->dbg.p;
 #endif
     if (F_extra && c->r_nx) H2D(c, c->rFe, F_extra, c->r_nx * sizeof(cplx));
     return 0;
@@ -2445,14 +2241,14 @@ static int solve_enqueue(raftx_ctx *c, int nIter, double tol, double XiStart, co
     if (int rc = make_plan(c, &A, &lp)) return rc;
     const size_t lds = lp.lds(c->maxS, A.rc_n);
     if (int rc = ensure_xl_scratch(c, lp)) return rc;
-    A.Xl = c->rXl;
-    A.slots = c->rXlSlots;
+    A.Xl = c->rXl.p;
+    A.slots = c->rXlSlots.p;
     if (c->have_xl0 || c->want_xlout) {       // restart / export of the linearisation point (the re-entry of raft_model.py:1108-1131)
         const size_t nxl = c->r_npair * 6 * (size_t)c->T.nw;
-        if (c->have_xl0 && c->rXlio_n != nxl) FAIL(c, "solve_dynamics: the linearisation point was set for a different batch shape");
+        if (c->have_xl0 && c->rXl0.n != nxl) FAIL(c, "solve_dynamics: the linearisation point was set for a different batch shape");
         if (int rc = ensure_xlio(c, nxl)) return rc;
-        if (c->have_xl0) A.Xl0 = c->rXl0;
-        A.XlOut = c->rXlOut;
+        if (c->have_xl0) A.Xl0 = c->rXl0.p;
+        A.XlOut = c->rXlOut.p;
         c->have_xl0 = false;                  // one-shot
     }
     LdsClasses classes;
@@ -2498,7 +2294,7 @@ extern "C" int raftx_set_linearisation_point(raftx_ctx *c, const raftx_c128 *XiL
         const DevTables &T = c->T;
         const size_t nxl = (size_t)T.nDesign * T.nCase * 6 * T.nw;
         if (int rc = ensure_xlio(c, nxl)) return rc;
-        if (nxl) H2D(c, c->rXl0, XiLast0, nxl * sizeof(cplx));
+        if (nxl) H2D(c, c->rXl0.p, XiLast0, nxl * sizeof(cplx));
         HIPCHK(c, hipStreamSynchronize(c->stream));
         c->have_xl0 = true;
     }
@@ -2507,9 +2303,9 @@ extern "C" int raftx_set_linearisation_point(raftx_ctx *c, const raftx_c128 *XiL
 
 extern "C" int raftx_fetch_linearisation_point(raftx_ctx *c, raftx_c128 *XiLast) {
     if (!c) return -1;
-    if (!c->rXlOut || !XiLast) FAIL(c, "fetch_linearisation_point: nothing kept (call raftx_set_linearisation_point(ctx, ., 1) first)");
+    if (!c->rXlOut.p || !XiLast) FAIL(c, "fetch_linearisation_point: nothing kept (call raftx_set_linearisation_point(ctx, ., 1) first)");
     HIPCHK(c, hipSetDevice(c->device));
-    if (c->rXlio_n) D2H(c, XiLast, c->rXlOut, c->rXlio_n * sizeof(cplx));
+    if (c->rXlOut.n) D2H(c, XiLast, c->rXlOut.p, c->rXlOut.n * sizeof(cplx));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return 0;
 }
@@ -2556,7 +2352,7 @@ extern "C" int raftx_bem_excitation(raftx_ctx *c, int nHeadBEM, const double *he
     const size_t npair = (size_t)T.nDesign * T.nCase, nx = npair * T.nHead * 6 * T.nw;
     const size_t nX = (size_t)T.nDesign * nHeadBEM * 6 * T.nw;
     c->bem_ready = false;
-    if ((c->bemF_n < nx || !c->bemF) && grow_device(c, &c->bemF, &c->bemF_n, nx)) return -2;
+    if (grow_device(c, c->bemF, nx)) return -2;
     Scratch sc(c);
     double *dH = sc.alloc<double>(nHeadBEM), *dA = heading_adjust ? sc.alloc<double>(T.nDesign) : nullptr,
            *dXY = xy_ref ? sc.alloc<double>((size_t)T.nDesign * 2) : nullptr;
@@ -2573,9 +2369,9 @@ extern "C" int raftx_bem_excitation(raftx_ctx *c, int nHeadBEM, const double *he
     HIPCHK(c, hipEventRecord(c->ev0, c->stream));
     if (nx)
         hipLaunchKernelGGL(k_bem_excitation, dim3((unsigned)(npair * T.nHead)), dim3(T.nw > 128 ? 256 : (T.nw > 64 ? 128 : 64)), 0,
-                           c->stream, T, nHeadBEM, dH, dX, dA, dXY, dAdd, c->bemF);
+                           c->stream, T, nHeadBEM, dH, dX, dA, dXY, dAdd, c->bemF.p);
     if (finish_timed(c)) return -2;
-    if (nx && F_out) D2H(c, F_out, c->bemF, nx * sizeof(cplx));
+    if (nx && F_out) D2H(c, F_out, c->bemF.p, nx * sizeof(cplx));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->bem_ready = true;
     return 0;
@@ -2817,8 +2613,7 @@ extern "C" int raftx_dense_resident(raftx_ctx *c, int nSet, int n, int nw, const
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     DenseResident &R = c->dense;
-    free_list(c, R.allocs);
-    R = DenseResident();
+    R = DenseResident();                              // (move assignment: the old matrices' bag gives its blocks back first)
     if (nSet == 0) return 0;                                              // (release)
     if (!w || !M || !B || !C) FAIL(c, "dense_resident: bad arguments");
     if (dense_check(c, "dense_resident", nSet, n, 1, nw)) return -1;
@@ -2872,8 +2667,8 @@ extern "C" int raftx_flex_start(raftx_ctx *c, int nUnit, int n, const raftx_c128
     if (nUnit < 1 || n < 6) FAIL(c, "flex_start: bad arguments (nUnit=%d, n=%d)", nUnit, n);
     HIPCHK(c, hipSetDevice(c->device));
     const size_t need = (size_t)nUnit * T.nCase * n * T.nw;
-    if (need > c->flexXl0_cap && grow_device(c, &c->flexXl0, &c->flexXl0_cap, need)) return -2;
-    H2D(c, c->flexXl0, XiLast0, need * sizeof(cplx));
+    if (grow_device(c, c->flexXl0, need)) return -2;
+    H2D(c, c->flexXl0.p, XiLast0, need * sizeof(cplx));
     HIPCHK(c, hipStreamSynchronize(c->stream));           // the caller's array is free again
     c->flexXl0_n = need;
     return 0;
@@ -2943,7 +2738,7 @@ extern "C" int raftx_flex_solve(raftx_ctx *c, int nUnit, const int64_t *nodeOff,
         const size_t had = c->flexXl0_n;
         c->flexXl0_n = 0;
         if (had != nxl) FAIL(c, "flex_solve: the linearisation point of raftx_flex_start has %zu entries, this call %zu", had, nxl);
-        HIPCHK(c, hipMemcpyAsync(dXl, c->flexXl0, nxl * sizeof(cplx), hipMemcpyDeviceToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(dXl, c->flexXl0.p, nxl * sizeof(cplx), hipMemcpyDeviceToDevice, c->stream));
     } else {
         hipLaunchKernelGGL(k_flex_fill, dim3((unsigned)((nxl + 255) / 256)), dim3(256), 0, c->stream, nxl, cplx{XiStart, 0.0}, dXl);   // :999
     }
@@ -3085,7 +2880,7 @@ extern "C" int raftx_qtf_kay(raftx_ctx *c, int nSet, int nw2, const double *w2, 
     const size_t nItem = (size_t)itemOff[nSet], nq = (size_t)nSet * nw2 * nw2 * 6;
     if (nItem && !items) FAIL(c, "qtf_kay: missing items");
     c->kay_ready = false;
-    if ((c->rKay_n < nq || !c->rKay) && grow_device(c, &c->rKay, &c->rKay_n, nq)) return -2;
+    if (grow_device(c, c->rKay, nq)) return -2;
     Scratch sc(c);
     double *dw = sc.alloc<double>(nw2), *dk = sc.alloc<double>(nw2), *dI = sc.alloc<double>(nItem * QK_N),
            *dB = sc.alloc<double>(nSet);
@@ -3099,16 +2894,16 @@ extern "C" int raftx_qtf_kay(raftx_ctx *c, int nSet, int nw2, const double *w2, 
         H2D(c, dB, beta, nSet * sizeof(double));
         H2D(c, dio, itemOff, (nSet + 1) * sizeof(int64_t));
         if (nItem) H2D(c, dI, items, nItem * QK_N * sizeof(double));
-        HIPCHK(c, hipMemsetAsync(c->rKay, 0, nq * sizeof(cplx), c->stream));       // lower triangle stays zero
+        HIPCHK(c, hipMemsetAsync(c->rKay.p, 0, nq * sizeof(cplx), c->stream));       // lower triangle stays zero
     }
     HIPCHK(c, hipEventRecord(c->ev0, c->stream));
     if (nSet) {
         if (nItem) hipLaunchKernelGGL(k_kay_tables, dim3((unsigned)nItem), dim3(128), 0, c->stream, nw2, Nm + 2, nSet, depth, dk, dio, dI, dB, dH, dq);
         if (nItem) hipLaunchKernelGGL(k_kay_pairs, dim3((unsigned)((size_t)nSet * nw2)), dim3(nw2 > 64 ? 128 : 64), 0, c->stream, nw2, Nm,
-                                      depth, rho, g, dw, dk, dio, dI, dH, dq, c->rKay);
+                                      depth, rho, g, dw, dk, dio, dI, dH, dq, c->rKay.p);
     }
     if (finish_timed(c)) return -2;
-    if (nSet && kay_out) D2H(c, kay_out, c->rKay, nq * sizeof(cplx));
+    if (nSet && kay_out) D2H(c, kay_out, c->rKay.p, nq * sizeof(cplx));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->rKay_sets = nSet;
     c->rKay_nw2 = nw2;
@@ -3151,16 +2946,16 @@ static int qtf_slender_impl(raftx_ctx *c, int nSet, int nw2, const double *w2, c
     int *dss = sc.alloc<int>(nStrip), *dms = sc.alloc<int>(nMem);
     const bool use_resident_kay = !kay && c->kay_ready && c->rKay_sets == nSet && c->rKay_nw2 == nw2;
     c->kay_ready = false;                                // one-shot: a table never outlives the call it was made for
-    cplx *dXi = sc.alloc<cplx>((size_t)nSet * 6 * nw2), *dK = kay ? sc.alloc<cplx>(nq) : (use_resident_kay ? c->rKay : nullptr);
+    cplx *dXi = sc.alloc<cplx>((size_t)nSet * 6 * nw2), *dK = kay ? sc.alloc<cplx>(nq) : (use_resident_kay ? c->rKay.p : nullptr);
     cplx *dT = sc.alloc<cplx>(nStrip * QT_N * nw2), *dTM = sc.alloc<cplx>(nMem * QTM_N * nw2),
          *dTS = sc.alloc<cplx>((size_t)nSet * QTS_N * nw2);
     double *dD = sc.alloc<double>(nStrip * QD_N);
     cplx *dTA = sc.alloc<cplx>(nStrip * QT_N * nw2);
     // the result stays resident (raftx_qtf_force can reuse it)
-    if ((c->rQtf_n < nq || !c->rQtf) && grow_device(c, &c->rQtf, &c->rQtf_n, nq)) return -2;
+    if (grow_device(c, c->rQtf, nq)) return -2;
     c->rQtf_sets = nSet;
     c->rQtf_nw2 = nw2;
-    cplx *dQ = c->rQtf;
+    cplx *dQ = c->rQtf.p;
     if (nSet && (!dw || !dk || (nStrip && (!dS || !dss || !dT || !dD || !dTA)) || (nMem && (!dM || !dms || !dTM)) || !dB || !dMs || !dso ||
                  !dmo || !dXi || (kay && !dK) || !dTS || !dQ))
         FAIL(c, "qtf_slender: device allocation failed");
@@ -3239,9 +3034,9 @@ extern "C" int raftx_qtf_force(raftx_ctx *c, int nSet, int nw2, const double *w2
         if (nq) H2D(c, t, qtf, nq * sizeof(cplx));
         dQ = t;
     } else {
-        if (!c->rQtf || c->rQtf_sets != nSet || c->rQtf_nw2 != nw2)
+        if (!c->rQtf.p || c->rQtf_sets != nSet || c->rQtf_nw2 != nw2)
             FAIL(c, "qtf_force: no resident QTFs of this shape (run raftx_qtf_slender first or pass qtf)");
-        dQ = c->rQtf;
+        dQ = c->rQtf.p;
     }
     double *dw2 = sc.alloc<double>(nw2), *dwv = sc.alloc<double>(nw), *dS = sc.alloc<double>((size_t)nSet * nw),
            *dfm = sc.alloc<double>((size_t)nSet * 6), *df = sc.alloc<double>((size_t)nSet * 6 * nw);
@@ -3292,15 +3087,24 @@ extern "C" int raftx_qtf_force(raftx_ctx *c, int nSet, int nw2, const double *w2
 #define SLOT_REF(S, c, slot, who)                                                                          \
     if ((slot) < 0 || (slot) >= RAFTX_NSLOT) FAIL(c, who ": slot must be 0 .. %d", RAFTX_NSLOT - 1);       \
     SweepSlot &S = (c)->slots[slot]
+// The slot of a request entry point (raftx_sweep_modal / _current / _channels / _mooring, `who`): prepared and not yet
+// launched, and still with its sea-state set where the request reads it (sea).
+static int request_slot(raftx_ctx *c, int slot, const char *who, bool sea, SweepSlot **out) {
+    if (slot < 0 || slot >= RAFTX_NSLOT) FAIL(c, "%s: slot must be 0 .. %d", who, RAFTX_NSLOT - 1);
+    SweepSlot &S = c->slots[slot];
+    if (S.busy) FAIL(c, "%s: slot %d has been launched (call it between raftx_sweep_prepare and raftx_sweep_launch)", who, slot);
+    if (!S.prepared) FAIL(c, "%s: nothing prepared on slot %d (raftx_sweep_prepare first)", who, slot);
+    if (sea && S.cset < 0) FAIL(c, "%s: slot %d has lost its sea-state tables (internal error)", who, slot);
+    *out = &S;
+    return 0;
+}
 static int block_ctx(raftx_ctx *c, int slot, size_t i, raftx_ctx **out) {
     std::vector<raftx_ctx *> &W = c->workers[slot];
     while (W.size() <= i) {
         raftx_ctx *sub = nullptr;
         const int rc = raftx_ctx_create(c->device, &sub);
         if (rc) FAIL(c, "sweep_stats: cannot create a block context (rc=%d)", rc);
-        (void)hipStreamDestroy(sub->stream);          // block contexts run on the parent's stream
-        sub->stream = c->stream;
-        sub->owns_stream = false;
+        sub->stream.borrow(c->stream);                // block contexts run on the parent's stream: their own is destroyed
         W.push_back(sub);
     }
     *out = W[i];
@@ -3371,20 +3175,18 @@ static int sweep_fail_drain(raftx_ctx *c, SweepSlot &S, int rc) {
 
 // the streams of the crossings, owned by the parent ctx and shared by its slots, and the slot's download marker
 static int crossing_streams(raftx_ctx *c, SweepSlot &S) {
-    if (!c->sCopy) {
-        // All four are ordinary streams (the generation stream in a high priority class lost: profiles/MEASUREMENT_HISTORY.md,
-        // "Closed scheduling experiments of the crossing").  Measured (scripts/ubench/queue_probe2.hip, scripts/gpu_prep.sh): a HIGH-priority
-        // preparation stream whose hardware queue happens to sit apart from the busy one does get the next batch's member
-        // pass onto the chip early -- and the step gets SLOWER (4.21 vs 4.02 ms): its 184-VGPR waves break up the
-        // 2 x 256-VGPR residency of the fused kernel's workgroups, and the earlier generation / fused kernel of the next
-        // batch then only share the chip with the current one.  As it is, the member pass runs beside the fused kernel's
-        // last residency round, which costs nothing.
-        HIPCHK(c, hipStreamCreateWithFlags(&c->sCopy, hipStreamNonBlocking));
-        HIPCHK(c, hipStreamCreateWithFlags(&c->sPrep, hipStreamNonBlocking));
-        HIPCHK(c, hipStreamCreateWithFlags(&c->sD2H, hipStreamNonBlocking));
-        HIPCHK(c, hipStreamCreateWithFlags(&c->sGen, hipStreamNonBlocking));
-    }
-    if (!S.evXi) HIPCHK(c, hipEventCreate(&S.evXi));
+    // All four are ordinary streams (the generation stream in a high priority class lost: profiles/MEASUREMENT_HISTORY.md,
+    // "Closed scheduling experiments of the crossing").  Measured (scripts/ubench/queue_probe2.hip, scripts/gpu_prep.sh): a HIGH-priority
+    // preparation stream whose hardware queue happens to sit apart from the busy one does get the next batch's member
+    // pass onto the chip early -- and the step gets SLOWER (4.21 vs 4.02 ms): its 184-VGPR waves break up the
+    // 2 x 256-VGPR residency of the fused kernel's workgroups, and the earlier generation / fused kernel of the next
+    // batch then only share the chip with the current one.  As it is, the member pass runs beside the fused kernel's
+    // last residency round, which costs nothing.  (A stream whose creation failed is tried again by the next prepare.)
+    HIPCHK(c, c->sCopy.ensure(hipStreamNonBlocking));
+    HIPCHK(c, c->sPrep.ensure(hipStreamNonBlocking));
+    HIPCHK(c, c->sD2H.ensure(hipStreamNonBlocking));
+    HIPCHK(c, c->sGen.ensure(hipStreamNonBlocking));
+    HIPCHK(c, S.evXi.ensure());
     return 0;
 }
 // Sea-state tables: sets resident on the parent, shared by the blocks of every slot that was prepared with the same
@@ -3409,9 +3211,9 @@ static int acquire_cases(raftx_ctx *c, SweepSlot &S, const SeaStates &sea) {
         if (idle < 0) FAIL(c, "sweep_prepare: no free sea-state set (every set is pinned by a crossing in flight)");   // cannot happen: NSLOT + 1 sets
         CaseSet &cs = c->csets[idle];
         cs.key.clear();
-        free_list(c, cs.allocs);                      // users == 0: every crossing that read it has been waited for
+        cs.allocs.release();                      // users == 0: every crossing that read it has been waited for
         if (int rc = upload_case_tables(c, c->sCopy, cs.allocs, cs.T, sea)) {
-            free_list(c, cs.allocs);
+            cs.allocs.release();
             return rc;
         }
         cs.key.swap(key);
@@ -3435,8 +3237,8 @@ static void cut_blocks(raftx_ctx *c, int slot, int nDesign, const SeaStates &sea
     S.nCase = sea.nCase; S.nHead = sea.nHead; S.nw = sea.nw;
     S.sd = run.sd; S.niter = run.niter; S.flags = run.flags; S.Xi = run.Xi; S.stripOffsets = run.stripOffsets;
     S.tl[0] = S.since();
-    free_list(c, S.allocs);
-    S.modal.on = S.current.on = S.channels.on = S.mooring.on = false;
+    S.allocs.release();
+    S.clear_requests();
 }
 // The batch's offset arrays: one upload on sCopy, shared by the blocks; its wave numbers are those of the sea-state set.
 static int upload_offsets(raftx_ctx *c, SweepSlot &S, const BuildSource &src, int nDesign) {
@@ -3514,7 +3316,7 @@ extern "C" int raftx_variant_program(raftx_ctx *c, int nMember, const double *me
                                      const int32_t *endEdit, const double *headCS, const double *diaCoef, const int32_t *diaEdit) {
     if (!c) return -1;
     for (int sl = 0; sl < RAFTX_NSLOT; sl++)
-        if (c->slots && (c->slots[sl].busy || c->slots[sl].prepared) && c->slots[sl].p1.var.prog)
+        if ((c->slots[sl].busy || c->slots[sl].prepared) && c->slots[sl].p1.var.prog)
             FAIL(c, "variant_program: a batch of variants is still in flight (raftx_sweep_wait first)");
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -3552,8 +3354,7 @@ extern "C" int raftx_variant_program(raftx_ctx *c, int nMember, const double *me
     auto up = [&](const void *h, size_t bytes, void **d) -> int {
         *d = nullptr;
         if (!bytes) bytes = 8, h = nullptr;
-        HIPCHK(c, hipMalloc(d, bytes));
-        P.allocs.push_back(*d);
+        HIPCHK(c, P.allocs.get_outside(c->pool, bytes, d));
         if (h) HIPCHK(c, hipMemcpy(*d, h, bytes, hipMemcpyHostToDevice));
         return 0;
     };
@@ -3615,7 +3416,7 @@ static int acquire_fixed(raftx_ctx *c, SweepSlot &S) {
         if (idle < 0) FAIL(c, "sweep_prepare_variants: no free record of the fixed members");      // cannot happen: NSLOT + 1 records
         FixedRecord &R = P.recs[idle];                // users == 0: every crossing that read it has been waited for
         R.valid = false;
-        if (!R.ev) HIPCHK(c, hipEventCreateWithFlags(&R.ev, hipEventDisableTiming));
+        HIPCHK(c, R.ev.ensure(hipEventDisableTiming));
         FixedArgs F{P.nFix, P.gm, P.gs, P.gc, P.fixDesc, src.rho, src.g, trim, haveK, R.rec, R.irec};
         hipLaunchKernelGGL(k_geom_member_fixed, dim3((unsigned)((P.nFix + 63) / 64)), dim3(64), 0, c->sPrep, F);
         HIPCHK(c, hipGetLastError());
@@ -3712,8 +3513,7 @@ static int qtfgen_run(raftx_ctx *c, Scratch &sc, const char *who, int nDesign, i
                       int64_t *memOff_out) {
     QtfResident &Q = c->qt;
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    free_list(c, Q.allocs);
-    Q = QtfResident();
+    Q = QtfResident();                                // (move assignment: the old records' bag gives its blocks back first)
     const size_t nD1 = (size_t)nDesign + 1;
     QGenArgs A;
     memset(&A, 0, sizeof(A));
@@ -3740,13 +3540,11 @@ static int qtfgen_run(raftx_ctx *c, Scratch &sc, const char *who, int nDesign, i
     HIPCHK(c, hipStreamSynchronize(c->stream));
     Q.nDesign = nDesign;
     if (err) {
-        free_list(c, Q.allocs);
         Q = QtfResident();
         FAIL(c, "%s: member %d has fewer than two stations, dlsMax <= 0 or no length", who, err - 1);
     }
     if (pool_alloc(c, Q.allocs, (size_t)Q.total(0) * QS_N, &Q.strips) || pool_alloc(c, Q.allocs, (size_t)Q.total(1) * QM_N, &Q.members) ||
         pool_alloc(c, Q.allocs, (size_t)Q.total(2) * QKR_N, &Q.kay)) {
-        free_list(c, Q.allocs);
         Q = QtfResident();
         return -2;
     }
@@ -3930,8 +3728,8 @@ extern "C" int raftx_qtf_slender_resident(raftx_ctx *c, int nCase, int nw2, cons
     cplx *dH = sc.alloc<cplx>(nItem * KAY_ROWS * nw2);
     bool ok = !nSet || (dw && dk && dB && dMs && dBc && dso && dmo && dio && dXi && dTS && dq && (!nStrip || (dss && dsr && dT && dD && dTA)) &&
                         (!nMem || (dms && dmr && dTM)) && (!nItem || (dI && dH)));
-    if (ok && nSet && (c->rQtf_n < nq || !c->rQtf) && grow_device(c, &c->rQtf, &c->rQtf_n, nq)) ok = false;
-    if (ok && nItem && (c->rKay_n < nq || !c->rKay) && grow_device(c, &c->rKay, &c->rKay_n, nq)) ok = false;
+    if (ok && nSet && grow_device(c, c->rQtf, nq)) ok = false;
+    if (ok && nItem && grow_device(c, c->rKay, nq)) ok = false;
     if (!ok)
         FAIL(c, "qtf_slender_resident: device allocation failed: %zu bytes of scratch asked for (%zu sets, %zu per set): cut the batch",
              bytes, nSet, nSet ? bytes / nSet : (size_t)0);
@@ -3948,11 +3746,11 @@ extern "C" int raftx_qtf_slender_resident(raftx_ctx *c, int nCase, int nw2, cons
     H2D(c, dmo, moff.data(), (nSet + 1) * sizeof(int64_t));
     H2D(c, dio, ioff.data(), (nSet + 1) * sizeof(int64_t));
     if (Xi) H2D(c, dXi, Xi, nSet * 6 * nw2 * sizeof(cplx));
-    if (nItem) HIPCHK(c, hipMemsetAsync(c->rKay, 0, nq * sizeof(cplx), c->stream));       // lower triangle stays zero
+    if (nItem) HIPCHK(c, hipMemsetAsync(c->rKay.p, 0, nq * sizeof(cplx), c->stream));       // lower triangle stays zero
     A.w = dw; A.k = dk; A.soff = dso; A.strips = Q.strips; A.moff = dmo; A.members = Q.members; A.sset = dss; A.mset = dms;
     A.srec = dsr; A.mrec = dmr;
-    A.Xi = dXi; A.beta = dB; A.Ms = dMs; A.kay = nItem ? c->rKay : nullptr; A.T = dT; A.TA = dTA; A.D = dD; A.TM = dTM; A.TS = dTS;
-    A.qtf = c->rQtf;
+    A.Xi = dXi; A.beta = dB; A.Ms = dMs; A.kay = nItem ? c->rKay.p : nullptr; A.T = dT; A.TA = dTA; A.D = dD; A.TM = dTM; A.TS = dTS;
+    A.qtf = c->rQtf.p;
     A.row_off = 0; A.row_stride = 1; A.nrow = nw2;
     HIPCHK(c, hipEventRecord(c->ev0, c->stream));
     hipLaunchKernelGGL(k_qtfgen_sets, dim3((unsigned)nSet), dim3(64), 0, c->stream, nCase, nDesign, Q.dOff, dss, dsr, dms, dmr);
@@ -3960,7 +3758,7 @@ extern "C" int raftx_qtf_slender_resident(raftx_ctx *c, int nCase, int nw2, cons
         hipLaunchKernelGGL(k_qtfgen_kay_items, dim3((unsigned)nSet), dim3(64), 0, c->stream, nCase, nDesign, dBc, Q.dOff, Q.kay, dI);
         hipLaunchKernelGGL(k_kay_tables, dim3((unsigned)nItem), dim3(128), 0, c->stream, nw2, Nm + 2, (int)nSet, depth, dk, dio, dI, dB, dH, dq);
         hipLaunchKernelGGL(k_kay_pairs, dim3((unsigned)(nSet * nw2)), dim3(nw2 > 64 ? 128 : 64), 0, c->stream, nw2, Nm, depth, rho, g, dw,
-                           dk, dio, dI, dH, dq, c->rKay);
+                           dk, dio, dI, dH, dq, c->rKay.p);
     }
     if (!Xi)                                             // motion RAOs straight from the resident first-order responses
         hipLaunchKernelGGL(k_rao_to_grid, dim3((unsigned)(nSet * 6)), dim3(128), 0, c->stream, c->T.nCase, c->T.nHead, c->T.nw, nw2,
@@ -3973,7 +3771,7 @@ extern "C" int raftx_qtf_slender_resident(raftx_ctx *c, int nCase, int nw2, cons
         hipLaunchKernelGGL(k_qtf_pairs, dim3((unsigned)(per_xcd * 8)), dim3(blk), 0, c->stream, A);
     }
     if (finish_timed(c)) return -2;
-    if (qtf) D2H(c, qtf, c->rQtf, nq * sizeof(cplx));
+    if (qtf) D2H(c, qtf, c->rQtf.p, nq * sizeof(cplx));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return 0;
 }
@@ -4024,48 +3822,42 @@ static hipError_t current_block(raftx_ctx *sub, SweepSlot &S, int lo, int n, dou
     return hipGetLastError();
 }
 
-// The output channels of one block of a crossing (raftx_sweep_channels) on stream st, behind the block's statistics kernel
-// (and so behind everything that wrote the block's responses, the slabs of a crossing with responses out included): one
-// workgroup per pair, the standard deviations written straight into the block's page-locked landing area [pairs,nChan],
-// which raftx_sweep_wait copies out.  Per-design rows are taken at the block's first design.
-static hipError_t channels_block(raftx_ctx *sub, SweepSlot &S, int lo, int n, hipStream_t st) {
+// k_sweep_channels on one block of a crossing, on stream st behind the event `up` of the request that asked for it: one
+// workgroup per pair, the standard deviations of nChan channels written straight into the page-locked landing area
+// [pairs,nChan] that raftx_sweep_wait copies out.  L and Gw (or null) at the block's first design; a zero stride: shared rows.
+static hipError_t channel_rows_block(raftx_ctx *sub, const SweepSlot &S, int n, hipStream_t st, hipEvent_t up, int nChan, const double *L,
+                                     size_t strideL, const cplx *Gw, size_t strideG, Pinned<double> &land) {
     const size_t npair = (size_t)n * S.nCase;
-    hipError_t e = sub->pinChan.reserve(npair * S.channels.nChan);
+    hipError_t e = land.reserve(npair * nChan);
     if (e != hipSuccess || npair == 0) return e;
     if (!sub->rXi || sub->r_nx < npair * S.nHead * 6 * S.nw || !sub->T.w) return hipErrorInvalidValue;   // (no resident responses: internal error)
-    e = hipStreamWaitEvent(st, S.channels.evUp, 0);
+    e = hipStreamWaitEvent(st, up, 0);
     if (e != hipSuccess) return e;
     ChannelArgs A;
-    A.nCase = S.nCase; A.nHead = S.nHead; A.nw = S.nw; A.nChan = S.channels.nChan;
-    A.strideL = S.channels.nL > 1 ? (size_t)A.nChan * 18 : 0;
-    A.strideG = S.channels.nG > 1 ? (size_t)A.nChan * 6 * S.nw : 0;
-    const double *L = S.channels.L + (size_t)lo * A.strideL;
-    const cplx *Gw = S.channels.Gw ? S.channels.Gw + (size_t)lo * A.strideG : nullptr;
+    A.nCase = S.nCase; A.nHead = S.nHead; A.nw = S.nw; A.nChan = nChan;
+    A.strideL = strideL;
+    A.strideG = strideG;
     const dim3 grid((unsigned)npair), wg(S.nw > 128 ? 256 : (S.nw > 64 ? 128 : 64));
-    if (Gw) hipLaunchKernelGGL(k_sweep_channels<true>, grid, wg, 0, st, A, (const double *)sub->T.w, (const cplx *)sub->rXi, L, Gw, sub->pinChan.p);
-    else hipLaunchKernelGGL(k_sweep_channels<false>, grid, wg, 0, st, A, (const double *)sub->T.w, (const cplx *)sub->rXi, L, Gw, sub->pinChan.p);
+    if (Gw) hipLaunchKernelGGL(k_sweep_channels<true>, grid, wg, 0, st, A, (const double *)sub->T.w, (const cplx *)sub->rXi, L, Gw, land.p);
+    else hipLaunchKernelGGL(k_sweep_channels<false>, grid, wg, 0, st, A, (const double *)sub->T.w, (const cplx *)sub->rXi, L, Gw, land.p);
     return hipGetLastError();
 }
-
+// The output channels of one block of a crossing (raftx_sweep_channels), behind the block's statistics kernel (and so behind
+// everything that wrote the block's responses, the slabs of a crossing with responses out included).  Per-design rows are
+// taken at the block's first design.
+static hipError_t channels_block(raftx_ctx *sub, SweepSlot &S, int lo, int n, hipStream_t st) {
+    const int nChan = S.channels.nChan;
+    const size_t strideL = S.channels.nL > 1 ? (size_t)nChan * 18 : 0, strideG = S.channels.nG > 1 ? (size_t)nChan * 6 * S.nw : 0;
+    return channel_rows_block(sub, S, n, st, S.channels.evUp, nChan, S.channels.L + (size_t)lo * strideL, strideL,
+                              S.channels.Gw ? S.channels.Gw + (size_t)lo * strideG : nullptr, strideG, sub->pinChan);
+}
 // The tension statistics of one block of a crossing (raftx_sweep_mooring with T_std): k_sweep_channels once more, on the rows
 // k_moor_design left in device memory (J in the first plane), into a landing area of its own -- a raftx_sweep_channels
 // request on the same slot keeps its rows and its area.
 static hipError_t mooring_std_block(raftx_ctx *sub, SweepSlot &S, int lo, int n, hipStream_t st) {
-    const size_t npair = (size_t)n * S.nCase;
     const int nChan = 2 * S.mooring.nLine;
-    hipError_t e = sub->pinMoorT.reserve(npair * nChan);
-    if (e != hipSuccess || npair == 0) return e;
-    if (!sub->rXi || sub->r_nx < npair * S.nHead * 6 * S.nw || !sub->T.w) return hipErrorInvalidValue;
-    e = hipStreamWaitEvent(st, S.mooring.evUp, 0);
-    if (e != hipSuccess) return e;
-    ChannelArgs A;
-    A.nCase = S.nCase; A.nHead = S.nHead; A.nw = S.nw; A.nChan = nChan;
-    A.strideL = (size_t)nChan * 18;
-    A.strideG = 0;
-    const dim3 grid((unsigned)npair), wg(S.nw > 128 ? 256 : (S.nw > 64 ? 128 : 64));
-    hipLaunchKernelGGL(k_sweep_channels<false>, grid, wg, 0, st, A, (const double *)sub->T.w, (const cplx *)sub->rXi,
-                       S.mooring.Lr + (size_t)lo * A.strideL, (const cplx *)nullptr, sub->pinMoorT.p);
-    return hipGetLastError();
+    const size_t strideL = (size_t)nChan * 18;
+    return channel_rows_block(sub, S, n, st, S.mooring.evUp, nChan, S.mooring.Lr + (size_t)lo * strideL, strideL, nullptr, 0, sub->pinMoorT);
 }
 // C_moor into the C0 of block b (raftx_sweep_mooring with add_stiffness): on the copy stream, which is in order -- behind the
 // block's own upload of C0 and behind the mooring kernels of the request -- and ahead of everything that reads C0: the
@@ -4073,7 +3865,7 @@ static hipError_t mooring_std_block(raftx_ctx *sub, SweepSlot &S, int lo, int n,
 static int mooring_add_block(raftx_ctx *c, raftx_ctx *sub, SweepSlot &S, int lo, int n, bool pipelined) {
     if (!n) return 0;
     if (!sub->job.active || !sub->job.C0d) FAIL(sub, "sweep_mooring: the block has no uploaded C0 (internal error)");
-    if (!sub->evMoor) HIPCHK(sub, hipEventCreateWithFlags(&sub->evMoor, hipEventDisableTiming));
+    HIPCHK(sub, sub->evMoor.ensure(hipEventDisableTiming));
     hipLaunchKernelGGL(k_moor_add, dim3(moor_grid((long long)n * 36)), dim3(MOOR_THREADS), 0, c->sCopy, sub->job.C0d,
                        S.mooring.C + (size_t)lo * 36, (long long)n * 36);
     HIPCHK(sub, hipGetLastError());
@@ -4089,11 +3881,7 @@ static int mooring_add_block(raftx_ctx *c, raftx_ctx *sub, SweepSlot &S, int lo,
 // (lowest class): profiles/MEASUREMENT_HISTORY.md, "Closed scheduling experiments of the crossing".  A device with one class,
 // or a failed creation: the ordinary download stream.
 static hipStream_t download_stream(raftx_ctx *c) {
-    if (!c->sD2Hhigh) {
-        int least = 0, greatest = 0;
-        if (hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess && least != greatest)
-            (void)hipStreamCreateWithPriority(&c->sD2Hhigh, hipStreamNonBlocking, greatest);
-    }
+    (void)c->sD2Hhigh.ensure_highest(hipStreamNonBlocking);
     return c->sD2Hhigh ? c->sD2Hhigh : c->sD2H;
 }
 
@@ -4149,9 +3937,9 @@ static void slab_plan_block(SlabPlan &plan, SweepSlot &S, size_t b, size_t slab_
     plan.after = [=](size_t q0, size_t q1, hipStream_t s) -> int {
         if (q1 <= q0) return 0;
         while (sub->evSlab.size() <= *kslab) {
-            hipEvent_t e = nullptr;
-            if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) return -2;
-            sub->evSlab.push_back(e);
+            Event e;
+            if (e.ensure(hipEventDisableTiming) != hipSuccess) return -2;
+            sub->evSlab.push_back(std::move(e));
         }
         hipEvent_t e = sub->evSlab[(*kslab)++];
         if (hipEventRecord(e, s) != hipSuccess || hipStreamWaitEvent(sDown, e, 0) != hipSuccess) return -2;
@@ -4165,9 +3953,9 @@ static void slab_plan_block(SlabPlan &plan, SweepSlot &S, size_t b, size_t slab_
 struct LaunchMode { bool pipelined; hipStream_t sDown; size_t slab_pairs; SlabPlan plan; };
 // the streams the slabs go to: the generation stream first, then the two slab streams (created when first needed)
 static int slab_streams(raftx_ctx *c, int n, SlabPlan &plan) {
-    hipStream_t *ss[3] = {&c->sGen, &c->sSlab[0], &c->sSlab[1]};
+    Stream *ss[3] = {&c->sGen, &c->sSlab[0], &c->sSlab[1]};
     for (int i = 0; i < n; i++) {
-        if (!*ss[i]) HIPCHK(c, hipStreamCreateWithFlags(ss[i], hipStreamNonBlocking));
+        HIPCHK(c, ss[i]->ensure(hipStreamNonBlocking));
         plan.alts.push_back(*ss[i]);
     }
     return 0;
@@ -4233,7 +4021,7 @@ static int launch_block(raftx_ctx *c, SweepSlot &S, int slot, size_t b, LaunchMo
 static int stats_after_join(raftx_ctx *c, SweepSlot &S, LaunchMode &M) {
     const size_t nB = S.blk.size();
     if (!nB) return 0;
-    if (!S.blk[0]->evJoin && hipEventCreateWithFlags(&S.blk[0]->evJoin, hipEventDisableTiming) != hipSuccess) return -2;
+    if (S.blk[0]->evJoin.ensure(hipEventDisableTiming) != hipSuccess) return -2;
     if (int rc = slab_join(S.blk[0], c->stream, M.plan.alts)) return rc;
     if (hipEventRecord(S.blk[nB - 1]->ev1, c->stream) != hipSuccess) return -2;
     for (size_t b = 0; b < nB; b++)
@@ -4253,7 +4041,7 @@ extern "C" int raftx_sweep_launch(raftx_ctx *c, int slot) {
         FAIL(c, "sweep_launch: slot %d has lost its sea-state tables (internal error)", slot);
     HIPCHK(c, hipSetDevice(c->device));
     if (!c->evEpoch) {
-        HIPCHK(c, hipEventCreate(&c->evEpoch));
+        HIPCHK(c, c->evEpoch.ensure());
         HIPCHK(c, hipEventRecord(c->evEpoch, c->stream));
     }
     S.prepared = false;                                 // from here on every failure goes through sweep_fail_drain
@@ -4299,7 +4087,7 @@ extern "C" int raftx_sweep_cancel(raftx_ctx *c, int slot) {
     if (!S.prepared) return 0;
     HIPCHK(c, hipSetDevice(c->device));
     hipError_t e = hipSuccess;
-    for (hipStream_t st : {c->sCopy, c->sPrep})
+    for (hipStream_t st : {c->sCopy.s, c->sPrep.s})
         if (st && e == hipSuccess) e = hipStreamSynchronize(st);
     for (raftx_ctx *sub : S.blk)
         if (sub) {
@@ -4307,7 +4095,7 @@ extern "C" int raftx_sweep_cancel(raftx_ctx *c, int slot) {
             build_abandon(sub);
         }
     S.prepared = false;
-    S.modal.on = S.current.on = S.channels.on = S.mooring.on = false;
+    S.clear_requests();
     slot_release_cases(c, S);
     HIPCHK(c, e);
     return 0;
@@ -4411,16 +4199,15 @@ extern "C" int raftx_sweep_wait(raftx_ctx *c, int slot, double *timing_ms) {
     HIPCHK(c, hipSetDevice(c->device));
     S.busy = false;
     const hipError_t es = sweep_drain(c, S);
-    if (es != hipSuccess) S.modal.on = S.current.on = S.channels.on = S.mooring.on = false;
+    if (es != hipSuccess) S.clear_requests();
     HIPCHK(c, es);
     solve_span(c, S);
     double t[4] = {0, 0, 0, 0};                           // wall | generation, solve, statistics kernels
     if (S.stripOffsets) S.stripOffsets[0] = 0;
     for (size_t b = 0; b < S.blk.size(); b++) collect_block(S, b, t);
     const hipError_t em = collect_mooring(S);
-    if (em != hipSuccess) S.mooring.on = false;
+    S.clear_requests();
     HIPCHK(c, em);
-    S.modal.on = S.current.on = S.channels.on = S.mooring.on = false;
     t[0] = S.since();
     debug_timeline(S, slot, t[0]);
     if (timing_ms) memcpy(timing_ms, t, sizeof(t));
@@ -4509,23 +4296,19 @@ extern "C" int raftx_modal_resident(raftx_ctx *c, const double *dM, const double
 extern "C" int raftx_sweep_modal(raftx_ctx *c, int slot, const double *dM, const double *dC, double *fn, double *modes,
                                  int32_t *flags, double *props) {
     if (!c) return -1;
-    SLOT_REF(S, c, slot, "sweep_modal");
-    if (S.busy) FAIL(c, "sweep_modal: slot %d has been launched (call it between raftx_sweep_prepare and raftx_sweep_launch)", slot);
-    if (!S.prepared) FAIL(c, "sweep_modal: nothing prepared on slot %d (raftx_sweep_prepare first)", slot);
+    SweepSlot *slot_ = nullptr;
+    if (int rc = request_slot(c, slot, "sweep_modal", false, &slot_)) return rc;
+    SweepSlot &S = *slot_;
     if (!fn || !modes || !flags) FAIL(c, "sweep_modal: bad arguments");
     HIPCHK(c, hipSetDevice(c->device));
     const size_t n = S.bnd.empty() ? 0 : (size_t)S.bnd.back();
     const double *ddM = nullptr, *ddC = nullptr;
     if (upload_on(c, c->sCopy, S.allocs, dM, dM ? n * 36 : 0, &ddM) || upload_on(c, c->sCopy, S.allocs, dC, dC ? n * 36 : 0, &ddC))
         return -2;
-    if (!S.modal.evUp) HIPCHK(c, hipEventCreateWithFlags(&S.modal.evUp, hipEventDisableTiming));
+    HIPCHK(c, S.modal.evUp.ensure(hipEventDisableTiming));
     HIPCHK(c, hipEventRecord(S.modal.evUp, c->sCopy));
-    S.modal.dM = ddM;
-    S.modal.dC = ddC;
-    S.modal.fn = fn;
-    S.modal.modes = modes;
-    S.modal.flags = flags;
-    S.modal.props = props;
+    S.modal.dM = ddM; S.modal.dC = ddC;
+    S.modal.fn = fn; S.modal.modes = modes; S.modal.flags = flags; S.modal.props = props;
     S.modal.on = true;
     return 0;
 }
@@ -4588,11 +4371,10 @@ extern "C" int raftx_current_loads(raftx_ctx *c, int nCur, const double *speed, 
 extern "C" int raftx_sweep_current(raftx_ctx *c, int slot, int nCur, const double *speed, const double *heading_deg,
                                    const double *Zref, double shearExp, double *D) {
     if (!c) return -1;
-    SLOT_REF(S, c, slot, "sweep_current");
-    if (S.busy) FAIL(c, "sweep_current: slot %d has been launched (call it between raftx_sweep_prepare and raftx_sweep_launch)", slot);
-    if (!S.prepared) FAIL(c, "sweep_current: nothing prepared on slot %d (raftx_sweep_prepare first)", slot);
+    SweepSlot *slot_ = nullptr;
+    if (int rc = request_slot(c, slot, "sweep_current", true, &slot_)) return rc;
+    SweepSlot &S = *slot_;
     if (!D) FAIL(c, "sweep_current: bad arguments");
-    if (S.cset < 0) FAIL(c, "sweep_current: slot %d has lost its sea-state tables (internal error)", slot);
     const size_t n = S.bnd.empty() ? 0 : (size_t)S.bnd.back();
     std::vector<double> host;
     if (int rc = current_params(c, "sweep_current", nCur, speed, heading_deg, Zref, n, c->csets[S.cset].T.depth, shearExp, host)) return rc;
@@ -4601,12 +4383,10 @@ extern "C" int raftx_sweep_current(raftx_ctx *c, int slot, int nCur, const doubl
     S.current.host.swap(host);                                           // alive until the slot is prepared again
     const double *dpar = nullptr;
     if (upload_on(c, c->sCopy, S.allocs, S.current.host.data(), S.current.host.size(), &dpar)) return -2;
-    if (!S.current.evUp) HIPCHK(c, hipEventCreateWithFlags(&S.current.evUp, hipEventDisableTiming));
+    HIPCHK(c, S.current.evUp.ensure(hipEventDisableTiming));
     HIPCHK(c, hipEventRecord(S.current.evUp, c->sCopy));
-    S.current.nCur = nCur;
-    S.current.shearExp = shearExp;
-    S.current.par = dpar;
-    S.current.Zref = Zref ? dpar + (size_t)3 * nCur : nullptr;
+    S.current.nCur = nCur; S.current.shearExp = shearExp;
+    S.current.par = dpar; S.current.Zref = Zref ? dpar + (size_t)3 * nCur : nullptr;
     S.current.D = D;
     S.current.on = true;
     return 0;
@@ -4682,14 +4462,13 @@ extern "C" int raftx_mooring_program(raftx_ctx *c, int nLine, const double *line
     }
     mooring_program_release(c);
     const size_t nb = (size_t)nLine * RAFTX_ML_N * 8, nc = (size_t)nLine * 6 * (nParam + 1) * 8, ne = (size_t)nLine * 4;
-    if (hipMalloc((void **)&c->mprog.base, nb) != hipSuccess || hipMalloc((void **)&c->mprog.coef, nc) != hipSuccess ||
-        hipMalloc((void **)&c->mprog.edit, ne) != hipSuccess) {
+    if (c->mprog.base.grow(nb / 8) != hipSuccess || c->mprog.coef.grow(nc / 8) != hipSuccess || c->mprog.edit.grow(ne / 4) != hipSuccess) {
         mooring_program_release(c);
         FAIL(c, "mooring_program: device allocation failed");
     }
-    HIPCHK(c, hipMemcpy(c->mprog.base, lines, nb, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(c->mprog.coef, lineCoef, nc, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(c->mprog.edit, lineEdit, ne, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(c->mprog.base.p, lines, nb, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(c->mprog.coef.p, lineCoef, nc, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(c->mprog.edit.p, lineEdit, ne, hipMemcpyHostToDevice));
     c->mprog.nLine = nLine;
     c->mprog.nP = nParam;
     return 0;
@@ -4707,7 +4486,7 @@ extern "C" int raftx_mooring_expand(raftx_ctx *c, int nDesign, const double *par
     double *dp = sc.alloc<double>((size_t)nDesign * std::max(nP, 1)), *dout = sc.alloc<double>(nl * RAFTX_ML_N);
     if (!dp || !dout) FAIL(c, "mooring_expand: device allocation failed");
     if (nP) H2D(c, dp, params, (size_t)nDesign * nP * sizeof(double));
-    MoorExpandArgs E{nDesign, nLine, nP, c->mprog.base, c->mprog.coef, c->mprog.edit, dp, dout};
+    MoorExpandArgs E{nDesign, nLine, nP, c->mprog.base.p, c->mprog.coef.p, c->mprog.edit.p, dp, dout};
     HIPCHK(c, hipEventRecord(c->ev0, c->stream));
     hipLaunchKernelGGL(k_moor_expand, dim3(moor_grid((long long)nl)), dim3(MOOR_THREADS), 0, c->stream, E);
     if (finish_timed(c)) return -2;
@@ -4775,7 +4554,7 @@ extern "C" int raftx_mean_pose(raftx_ctx *c, int nDesign, int nLine, const doubl
     A.lines = dl; A.K_hs = dK; A.F0 = dF0; A.F_env = dFe; A.x_ref = dxr;
     HIPCHK(c, hipEventRecord(c->ev0, c->stream));
     if (!lines) {                                                // the records of the program's variants, as raftx_mooring_expand
-        MoorExpandArgs E{nDesign, nLine, nP, c->mprog.base, c->mprog.coef, c->mprog.edit, dpar, dl};
+        MoorExpandArgs E{nDesign, nLine, nP, c->mprog.base.p, c->mprog.coef.p, c->mprog.edit.p, dpar, dl};
         hipLaunchKernelGGL(k_moor_expand, dim3(moor_grid((long long)nl)), dim3(MOOR_THREADS), 0, c->stream, E);
     }
     const int perBlock = MP_THREADS / A.G;
@@ -4796,11 +4575,10 @@ extern "C" int raftx_mean_pose(raftx_ctx *c, int nDesign, int nLine, const doubl
 extern "C" int raftx_sweep_mooring(raftx_ctx *c, int slot, int nLine, const double *lines, int add_stiffness, double *C_moor,
                                    double *F_moor, double *T_mean, double *T_std, int32_t *flags) {
     if (!c) return -1;
-    SLOT_REF(S, c, slot, "sweep_mooring");
-    if (S.busy) FAIL(c, "sweep_mooring: slot %d has been launched (call it between raftx_sweep_prepare and raftx_sweep_launch)", slot);
-    if (!S.prepared) FAIL(c, "sweep_mooring: nothing prepared on slot %d (raftx_sweep_prepare first)", slot);
+    SweepSlot *slot_ = nullptr;
+    if (int rc = request_slot(c, slot, "sweep_mooring", true, &slot_)) return rc;
+    SweepSlot &S = *slot_;
     if (!flags) FAIL(c, "sweep_mooring: bad arguments (flags is required)");
-    if (S.cset < 0) FAIL(c, "sweep_mooring: slot %d has lost its sea-state tables (internal error)", slot);
     const size_t n = S.bnd.empty() ? 0 : (size_t)S.bnd.back();
     const VariantProg *vp = S.p1.var.prog;
     if (!lines) {
@@ -4821,8 +4599,8 @@ extern "C" int raftx_sweep_mooring(raftx_ctx *c, int slot, int nLine, const doub
     if (!std::isfinite(depth) || !(depth > 0.0)) FAIL(c, "sweep_mooring: the depth must be positive and finite (got %g)", depth);
     HIPCHK(c, hipSetDevice(c->device));
     if (S.mooring.evUp) HIPCHK(c, hipEventSynchronize(S.mooring.evUp));   // (a second request on one slot: the landing area is free again)
-    else HIPCHK(c, hipEventCreateWithFlags(&S.mooring.evUp, hipEventDisableTiming));
-    S.mooring.on = false;
+    else HIPCHK(c, S.mooring.evUp.ensure(hipEventDisableTiming));
+    S.mooring.on = false;                              // this request alone, while its landing area is rewritten: not clear_requests(), the slot's others stay
     const size_t nl = n * (size_t)nLine, nT = 2 * (size_t)nLine;
     HIPCHK(c, S.mooring.pin.reserve(n * (42 + nT) + (n + 1) / 2 + 1));
     MoorArgs A;
@@ -4846,7 +4624,7 @@ extern "C" int raftx_sweep_mooring(raftx_ctx *c, int slot, int nLine, const doub
     A.lines = dl; A.pose = dp;
     if (n) {
         if (!lines) {
-            MoorExpandArgs E{(int)n, nLine, vp->nP, c->mprog.base, c->mprog.coef, c->mprog.edit, dpar, dexp};
+            MoorExpandArgs E{(int)n, nLine, vp->nP, c->mprog.base.p, c->mprog.coef.p, c->mprog.edit.p, dpar, dexp};
             hipLaunchKernelGGL(k_moor_expand, dim3(moor_grid((long long)nl)), dim3(MOOR_THREADS), 0, c->sCopy, E);
         }
         hipLaunchKernelGGL(k_moor_line, dim3(moor_grid((long long)nl)), dim3(MOOR_THREADS), 0, c->sCopy, A);
@@ -4872,9 +4650,9 @@ extern "C" int raftx_sweep_mooring(raftx_ctx *c, int slot, int nLine, const doub
 extern "C" int raftx_sweep_channels(raftx_ctx *c, int slot, int nChan, int nL, const double *L, int nG, const raftx_c128 *Gw,
                                     double *chan_std) {
     if (!c) return -1;
-    SLOT_REF(S, c, slot, "sweep_channels");
-    if (S.busy) FAIL(c, "sweep_channels: slot %d has been launched (call it between raftx_sweep_prepare and raftx_sweep_launch)", slot);
-    if (!S.prepared) FAIL(c, "sweep_channels: nothing prepared on slot %d (raftx_sweep_prepare first)", slot);
+    SweepSlot *slot_ = nullptr;
+    if (int rc = request_slot(c, slot, "sweep_channels", false, &slot_)) return rc;
+    SweepSlot &S = *slot_;
     const int n = S.bnd.empty() ? 0 : S.bnd.back();
     if (nChan < 1 || nChan > RAFTX_SWEEP_CHAN_MAX) FAIL(c, "sweep_channels: nChan=%d must be 1 .. %d", nChan, RAFTX_SWEEP_CHAN_MAX);
     if (nL != 1 && nL != n) FAIL(c, "sweep_channels: nL=%d must be 1 (shared rows) or the %d designs of the crossing", nL, n);
@@ -4887,13 +4665,10 @@ extern "C" int raftx_sweep_channels(raftx_ctx *c, int slot, int nChan, int nL, c
     if (upload_on(c, c->sCopy, S.allocs, L, (size_t)nL * nChan * 18, &dL) ||
         upload_on(c, c->sCopy, S.allocs, Gw, nG > 0 ? (size_t)nG * nChan * 6 * S.nw : 0, &dG))
         return -2;
-    if (!S.channels.evUp) HIPCHK(c, hipEventCreateWithFlags(&S.channels.evUp, hipEventDisableTiming));
+    HIPCHK(c, S.channels.evUp.ensure(hipEventDisableTiming));
     HIPCHK(c, hipEventRecord(S.channels.evUp, c->sCopy));
-    S.channels.nChan = nChan;
-    S.channels.nL = nL;
-    S.channels.nG = nG;
-    S.channels.L = dL;
-    S.channels.Gw = reinterpret_cast<const cplx *>(dG);
+    S.channels.nChan = nChan; S.channels.nL = nL; S.channels.nG = nG;
+    S.channels.L = dL; S.channels.Gw = reinterpret_cast<const cplx *>(dG);
     S.channels.out = chan_std;
     S.channels.on = true;
     return 0;
@@ -5001,10 +4776,7 @@ extern "C" int raftx_comm_destroy(raftx_ctx *c) {
         }
         c->comm = nullptr;
     }
-    if (c->commFlag) {
-        (void)hipFree(c->commFlag);
-        c->commFlag = nullptr;
-    }
+    c->commFlag.release();
     c->comm_rank = 0;
     c->comm_world = 1;
     return 0;
@@ -5020,11 +4792,8 @@ extern "C" int raftx_comm_init(raftx_ctx *c, int rank, int world, const char *id
     ncclUniqueId id;
     memcpy(&id, id128, sizeof(id));
     ncclComm_t comm = nullptr;
-    if (!c->commFlag) {                                   // the status word of comm_agree: allocated HERE so that no exchange
-        void *p = nullptr;                                // step can fail on it later, between its peers' collectives
-        HIPCHK(c, hipMalloc(&p, sizeof(int)));
-        c->commFlag = reinterpret_cast<int *>(p);
-    }
+    // the status word of comm_agree: allocated HERE so that no exchange step can fail on it later, between its peers' collectives
+    if (!c->commFlag.p) HIPCHK(c, c->commFlag.grow(1));
     NCCLCHK(c, R, R->CommInitRank(&comm, world, id, rank));
     c->comm = comm;
     c->comm_rank = rank;
@@ -5049,17 +4818,17 @@ static int comm_agree(raftx_ctx *c, RcclApi *R, int local_rc) {
     // this rank's vote, never returned early: the AllReduce below is always posted, so the peers are not left waiting.
     // What cannot be recovered (documented in include/raftx.h): a rank whose AllReduce itself fails, or that dies.
     int mine = local_rc ? 1 : 0, worst = 0;
-    hipError_t e = hipMemcpyAsync(c->commFlag, &mine, sizeof(int), hipMemcpyHostToDevice, c->stream);
+    hipError_t e = hipMemcpyAsync(c->commFlag.p, &mine, sizeof(int), hipMemcpyHostToDevice, c->stream);
     if (e != hipSuccess) {                                // vote "failed" through a device-side fill instead (no host source)
         mine = 1;
         if (!local_rc) {
             snprintf(c->err, sizeof(c->err), "comm: status upload failed: %s", hipGetErrorString(e));
             local_rc = -2;
         }
-        (void)hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(c->commFlag), 1, 1, c->stream);
+        (void)hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(c->commFlag.p), 1, 1, c->stream);
     }
-    NCCLCHK(c, R, R->AllReduce(c->commFlag, c->commFlag, 1, ncclInt, ncclMax, reinterpret_cast<ncclComm_t>(c->comm), c->stream));
-    e = hipMemcpyAsync(&worst, c->commFlag, sizeof(int), hipMemcpyDeviceToHost, c->stream);
+    NCCLCHK(c, R, R->AllReduce(c->commFlag.p, c->commFlag.p, 1, ncclInt, ncclMax, reinterpret_cast<ncclComm_t>(c->comm), c->stream));
+    e = hipMemcpyAsync(&worst, c->commFlag.p, sizeof(int), hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     if (local_rc) return local_rc;                    // c->err already says why
     if (e != hipSuccess) FAIL(c, "comm: status download failed: %s", hipGetErrorString(e));
@@ -5212,15 +4981,15 @@ extern "C" int raftx_comm_reduce_sum(raftx_ctx *c, double *buf, size_t n, int ro
 // summed over the first lane of every workgroup, per phase (set-up+inertial, pass A, strip
 // phase, pass B, solve, tail).
 extern "C" int raftx_debug_phase_cycles(raftx_ctx *c, unsigned long long *out8) {
-    if (!c || !out8 || !c->dbg) return -1;
-    HIPCHK(c, hipMemcpy(out8, c->dbg, 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    if (!c || !out8 || !c->dbg.p) return -1;
+    HIPCHK(c, hipMemcpy(out8, c->dbg.p, 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     return 0;
 }
 // timing builds: the clock trace of the last fused launch -- out[2 b], out[2 b + 1] = shader cycles, 100 MHz ticks of the
 // workgroups that started in the b-th 125 us of the launch (PT_FLUSH); n_bucket <= 64
 extern "C" int raftx_debug_clock_trace(raftx_ctx *c, unsigned long long *out, int n_bucket) {
-    if (!c || !out || !c->dbg || n_bucket < 1 || n_bucket > PT_CLOCK_BUCKETS) return -1;
-    HIPCHK(c, hipMemcpy(out, c->dbg + 10, 2 * (size_t)n_bucket * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    if (!c || !out || !c->dbg.p || n_bucket < 1 || n_bucket > PT_CLOCK_BUCKETS) return -1;
+    HIPCHK(c, hipMemcpy(out, c->dbg.p + 10, 2 * (size_t)n_bucket * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     return 0;
 }
 #endif
