@@ -14,8 +14,13 @@
  * 1e-10 rad.  The rotations of the pose are (roll, pitch, yaw) as everywhere in raftx.h; the Newton step adds the
  * rotation-vector increment to them, as the reference does.
  *
+ * raftx_sweep_mean_pose composes the solve with a sweep crossing: hydrostatics at the reference pose, the solve, and the
+ * crossing at the solved pose, per design and on the device (the reference's order: solveStatics, setPosition,
+ * solveDynamics at the offset).
+ *
  * Not covered: staticsMod / forcingMod 1 (hydrostatics and loads re-evaluated at the pose), arrays with shared lines,
- * flexible units, and feeding the pose into a sweep crossing -- the pose is returned to the caller.
+ * flexible units; in a crossing also the design's own current load as F_env (its strip tables do not exist before the
+ * solve) and second-order tables at the solved pose.
  */
 #ifndef RAFTX_STATICS_H
 #define RAFTX_STATICS_H
@@ -50,6 +55,33 @@ int raftx_mean_pose(raftx_ctx *ctx, int nDesign, int nLine, const double *lines,
                     const double *K_hs, const double *F0, const double *F_env, const double *x_ref, const double tol[2],
                     int max_iter, double *pose, double *C_moor, double *F_moor, double *T, double *J, double *F_res,
                     int32_t *iterations, int32_t *flags);
+
+/* A request on a PREPARED, not yet launched slot (raftx.h: raftx_sweep_prepare / _prepare_variants), in the family of
+ * raftx_sweep_modal / _current / _mooring / _channels: the crossing runs at every design's own mean pose.  Per design, on the
+ * device, with no host wait between the steps; x_ref is the pose the slot was prepared with (zero if it had none):
+ *   1. the statics the slot's member pass leaves at x_ref (after the ballast trim, if the mask has it) give
+ *          K_hs = (C_struc + C_hydro) + C_extra        F0 = (W_struc + W_hydro) + F_extra
+ *      in exactly this association (the bits of raft_amd/statics.py hydrostatics()).  C_extra [nX,6,6] and F_extra [nX,6] enter
+ *      the statics only -- the crossing's own C0 is a separate thing and is not touched; nX = 0: none, 1: shared, nDesign: one
+ *      each; with nX > 0 either may still be NULL;
+ *   2. the solve of raftx_mean_pose from x_ref: lines [nDesign,nLine,RAFTX_ML_N], or NULL on a slot of variants: the records
+ *      of the installed mooring program fed the slot's params (the rules of raftx_sweep_mooring); depth is the slot's sea
+ *      states'; F_env [nDesign,6] or NULL; tol and max_iter as in raftx_mean_pose;
+ *   3. the member pass, its reductions and scans run again at the solved pose -- at x_ref for a flagged design -- without a
+ *      second ballast trim: the density correction is the one found at x_ref (adjustBallastDensity precedes solveStatics);
+ *   4. generation, the fused fixed point, the statistics and every rider proceed as for a crossing prepared with that pose.
+ * raftx_sweep_wait fills pose, F_res [nDesign,6], iterations and flags [nDesign] (each may be NULL except flags).  A design
+ * whose flags are not zero (the bits above) comes back as NaN in everything the crossing hands out for it -- std, Xi, the
+ * riders' outputs -- with RAFTX_FLAG_NAN set in its crossing flags, and its pose is NaN as raftx_mean_pose gives it; no other
+ * design's bits change.
+ * A raftx_sweep_mooring request made AFTER this one evaluates the lines at the device pose (add_stiffness, T_mean and T_std
+ * then mean "at the offset").  Errors: a slot that is idle or launched; a mooring request already on the slot; a second
+ * mean-pose request (it re-runs phase 1: refused, not replaced); the line errors of raftx_sweep_mooring; CB != 0; nX not 0, 1
+ * or nDesign; a bad tolerance.  A crossing with this request builds its tables with k_geom_design also under
+ * RAFTX_FUSED_GEN=1.  raftx_sweep_cancel and a new prepare drop the request. */
+int raftx_sweep_mean_pose(raftx_ctx *ctx, int slot, int nLine, const double *lines, int nX, const double *C_extra,
+                          const double *F_extra, const double *F_env, const double tol[2], int max_iter, double *pose,
+                          double *F_res, int32_t *iterations, int32_t *flags);
 
 #ifdef __cplusplus
 }

@@ -52,7 +52,7 @@ QTFGEN_EXPORTS = ("raftx_qtf_tables_build", "raftx_qtf_tables_build_variants", "
 MOORING_EXPORTS = ("raftx_mooring_lines", "raftx_mooring_program", "raftx_mooring_expand", "raftx_sweep_mooring")
 ML_N = 16          # doubles per mooring line record (RAFTX_ML_N)
 # include/raftx_statics.h: the mean equilibrium pose, the device library only
-STATICS_EXPORTS = ("raftx_mean_pose",)
+STATICS_EXPORTS = ("raftx_mean_pose", "raftx_sweep_mean_pose")
 MOOR_BAD_LINE, MOOR_VERTICAL, MOOR_SLACK, MOOR_NO_CONVERGENCE = 1, 2, 4, 8
 QKG_N = 8          # doubles per row of the Kim & Yue geometry stream (RAFTX_QKG_N)
 
@@ -172,6 +172,8 @@ class RaftxLib:
             L.raftx_mean_pose.argtypes = [_vp, C.c_int, C.c_int, _vp, _vp, C.c_double, _vp, _vp, _vp, _vp, _vp, C.c_int,
                                           _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]
             L.raftx_mean_pose.restype = C.c_int
+            L.raftx_sweep_mean_pose.argtypes = [_vp, C.c_int, C.c_int, _vp, C.c_int, _vp, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp]
+            L.raftx_sweep_mean_pose.restype = C.c_int
         self.has_current = all(hasattr(L, s) for s in CURRENT_EXPORTS)
         if self.has_current:
             L.raftx_current_loads.argtypes = [_vp, C.c_int, _vp, _vp, _vp, C.c_double, C.c_double, _vp]
@@ -810,6 +812,47 @@ class Context:
                                       _ptr(out["T"]), _ptr(out["J"]), _ptr(out["F_res"]), _ptr(out["iterations"]), _ptr(out["flags"])),
                     "raftx_mean_pose")
         return {k: v for k, v in out.items() if v is not None}
+
+    def sweep_mean_pose(self, handle, lines=None, C_extra=None, F_extra=None, F_env=None, tol=None, max_iter=0):
+        """Ask for a PREPARED, not yet launched crossing to run at every design's mean pose (raftx_sweep_mean_pose):
+        hydrostatics at the pose the crossing was prepared with, the Newton solve of ``mean_pose`` and the crossing at the
+        solved pose, all on the device.  ``lines`` [nD,nLine,16], or None on a crossing of variants for the installed
+        mooring program fed the crossing's params; ``C_extra`` [6,6] or [nD,6,6] and ``F_extra`` [6] or [nD,6] enter the
+        statics only (both shared or both per design); ``F_env`` [nD,6] or None.  ``sweep_wait`` then also returns pose
+        [nD,6], F_res [nD,6], pose_iterations [nD], pose_flags [nD]; a flagged design comes back as NaN.  Ask before
+        ``sweep_mooring``, which then evaluates the lines at the solved pose.  Returns the handle."""
+        if not self.rlib.has_statics:
+            raise RaftxError("sweep_mean_pose: %s does not implement include/raftx_statics.h (the device library does)" % self.rlib.path)
+        out = handle["out"]
+        n = out["niter"].shape[0]
+        if lines is None:
+            if getattr(self, "_mprog", None) is None:
+                raise RaftxError("sweep_mean_pose: no program installed (mooring_program first) and no lines given")
+            nL = self._mprog[0]
+        else:
+            lines = _f64(lines)
+            if lines.ndim != 3 or lines.shape[0] != n or lines.shape[2] != ML_N:
+                raise ValueError("lines has shape %s, expected [%d,nLine,%d]" % (lines.shape, n, ML_N))
+            nL = lines.shape[1]
+        nX = 0
+        if C_extra is not None or F_extra is not None:
+            per = [a.ndim == want for a, want in ((np.asarray(C_extra), 3), (np.asarray(F_extra), 2)) if a.ndim]
+            if len(set(per)) > 1:
+                raise ValueError("C_extra and F_extra must both be shared ([6,6], [6]) or both per design ([nD,6,6], [nD,6])")
+            nX = n if per[0] else 1
+            C_extra = None if C_extra is None else _f64(C_extra, ((n,) if per[0] else ()) + (6, 6), "C_extra")
+            F_extra = None if F_extra is None else _f64(F_extra, ((n,) if per[0] else ()) + (6,), "F_extra")
+        F_env = None if F_env is None else _f64(F_env, (n, 6), "F_env")
+        tol = None if tol is None else _f64(tol, (2,), "tol")
+        res = dict(pose=np.zeros((n, 6)), F_res=np.zeros((n, 6)), pose_iterations=np.zeros(n, dtype=np.int32),
+                   pose_flags=np.zeros(n, dtype=np.int32))
+        self._check(self.rlib.lib.raftx_sweep_mean_pose(self._h, int(handle["slot"]), nL, _ptr(lines), nX, _ptr(C_extra), _ptr(F_extra),
+                                                        _ptr(F_env), _ptr(tol), int(max_iter), _ptr(res["pose"]), _ptr(res["F_res"]),
+                                                        _ptr(res["pose_iterations"]), _ptr(res["pose_flags"])),
+                    "raftx_sweep_mean_pose")
+        handle["pose_inputs"] = (lines, C_extra, F_extra, F_env)   # alive until the crossing has been waited for
+        out.update(res)
+        return handle
 
     def sweep_mooring(self, handle, lines=None, add_stiffness=True, tensions=True):
         """Ask for the mooring system of a PREPARED, not yet launched crossing (raftx_sweep_mooring): ``lines``

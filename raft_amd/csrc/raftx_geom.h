@@ -775,6 +775,19 @@ __global__ void k_geom_zero(GeomArgs A) {
     if (d < A.nDesign && !A.prog.params)
         for (int64_t m = A.mo(d); m < A.mo(d + 1); m++) A.mdesign_w[m] = d;
 }
+// ... for a SECOND member pass of the same job at another pose (raftx_sweep_mean_pose): the counts and totals only.  The
+// ballast trim belongs to the first pass, at the reference pose (adjustBallastDensity precedes solveStatics), so drho stays --
+// k_geom_reinertia and props[RAFTX_SP_DRHO] read it again -- and so does err[]: an error the first pass raised must still
+// reach the host, and the second pass can only add to it (atomicCAS against 0).  mdesign is the first pass's.
+__global__ void k_geom_rezero(GeomArgs A) {
+    const int d = blockIdx.x * blockDim.x + threadIdx.x;
+    if (d < A.nDesign) {
+        A.off[d + 1] = 0;
+        A.cmoff[d + 1] = 0;
+    }
+    if (d < 5) A.tot[d] = 0;
+    if (d == 0) { A.off[0] = 0; A.cmoff[0] = 0; }
+}
 #define GEOM_MAX_STATIONS 1024
 // Member of this thread.  With A.mgrid > 0 the threads are laid out (member position, design) with the design running
 // fastest: a wavefront then holds the SAME member of 64 designs -- in a sweep the designs share a topology, so its lanes

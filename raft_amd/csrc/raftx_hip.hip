@@ -34,6 +34,7 @@
 #include <chrono>
 #include <map>
 #include <functional>
+#include <limits>
 #include <mutex>
 #include <type_traits>
 #include <thread>
@@ -877,9 +878,24 @@ struct SweepSlot {
         int32_t *flags_out = nullptr;
         Event evUp;                      // the kernels have run and the landing area is filled (sCopy)
     } mooring;
+    struct {                             // raftx_sweep_mean_pose: the crossing runs at every design's mean equilibrium pose
+        bool on = false;
+        int nLine = 0, nX = 0, maxIter = 0;
+        double tolT = 0, tolR = 0;
+        // device, the whole crossing (in S.allocs): the line records; the statics-only extras [nX,36] / [nX,6] and the loads
+        // [nDesign,6], each or null; what the solve reads (K_hs, F0), its scratch and what it leaves; the poses of the second pass
+        const double *lines = nullptr, *Cx = nullptr, *Fx = nullptr, *Fenv = nullptr;
+        double *K = nullptr, *F0 = nullptr, *lw = nullptr, *solved = nullptr, *placed = nullptr, *Fres = nullptr;
+        int *iter = nullptr, *fl = nullptr;
+        Pinned<double> pin;              // landing area: pose | F_res [nDesign,6] each | iterations | flags [nDesign] int32 each
+        double *pose_out = nullptr, *Fres_out = nullptr;                     // the caller's, filled by raftx_sweep_wait
+        int32_t *iter_out = nullptr, *flags_out = nullptr;
+        Event evUp;                      // the inputs have landed and the program's records have been written (sCopy)
+        int32_t *hFlags(size_t n) const { return reinterpret_cast<int32_t *>(pin.p + n * 12) + n; }
+    } pose;
     // The one place that switches the requests of a crossing off: a request left on would fire at the next raftx_sweep_wait
     // and copy into a caller's array that may be gone.
-    void clear_requests() { modal.on = current.on = channels.on = mooring.on = false; }
+    void clear_requests() { modal.on = current.on = channels.on = mooring.on = pose.on = false; }
 };
 
 // The host state of a context.  Every resource is held by an owner (raftx_owned.h), so raftx_ctx_destroy ends in `delete c`
@@ -903,6 +919,7 @@ struct raftx_ctx {
     Event evZ;                           // the first kernel of the member pass has run (phase 1)
     Event evMem, evRed;                  // member pass done (preparation stream) / per-design reduction done (side stream)
     Event evMoor;                        // C_moor has been added to the block's C0 (raftx_sweep_mooring, sCopy)
+    Event evPose;                        // the block's designs have their mean pose (raftx_sweep_mean_pose, preparation stream)
     Event evEpoch;                       // zero of raftx_sweep_solve_span: recorded when the first crossing of the ctx is launched
     std::vector<Event> evSlab;           // completion markers of the slabs (no timing), created as needed, kept
     Event evFork, evJoin;
@@ -1319,6 +1336,22 @@ static int enqueue_member_pass(raftx_ctx *c, hipStream_t sPrep) {
             hipLaunchKernelGGL(k_geom_reinertia, dim3((unsigned)((nThread + 127) / 128)), dim3(128), 0, sPrep, A);
         }
     }
+    return 0;
+}
+// The member pass of an enqueued job once more, at the poses A.pose now points to (raftx_sweep_mean_pose): the same grid, the
+// counts and totals cleared, no ballast trim -- the density correction is the first pass's, taken at the reference pose.
+static int enqueue_member_repass(raftx_ctx *c, hipStream_t sPrep) {
+    BuildJob &J = c->job;
+    GeomArgs &A = J.A;
+    const int64_t nDesign = J.nDesign, nMember = A.nMember;
+    hipLaunchKernelGGL(k_geom_rezero, dim3((unsigned)(nDesign / 256 + 1)), dim3(256), 0, sPrep, A);
+    if (nMember > 0) {
+        const int64_t nThread = A.mgrid > 0 ? (int64_t)A.mgrid * nDesign : nMember;
+        hipLaunchKernelGGL(k_geom_member, dim3((unsigned)((nThread + 127) / 128)), dim3(128), 0, sPrep, A);
+        if (A.add_mask & RAFTX_TRIM_BALLAST)
+            hipLaunchKernelGGL(k_geom_reinertia, dim3((unsigned)((nThread + 127) / 128)), dim3(128), 0, sPrep, A);
+    }
+    HIPCHK(c, hipGetLastError());
     return 0;
 }
 // The scans (totals, error flags and design offsets reach the host through their own stores into page-locked memory,
@@ -3169,6 +3202,7 @@ static int sweep_fail_drain(raftx_ctx *c, SweepSlot &S, int rc) {
     (void)hipDeviceSynchronize();
     for (raftx_ctx *sub : S.blk)
         if (sub) build_abandon(sub);
+    S.pose.on = false;                   // (its blocks' second passes went with the jobs)
     slot_release_cases(c, S);
     return rc;
 }
@@ -3254,6 +3288,68 @@ static int upload_offsets(raftx_ctx *c, SweepSlot &S, const BuildSource &src, in
 // phase 1 of block b: descriptor H2D on sCopy, member pass + scans on sPrep
 static int block_phase1(raftx_ctx *c, SweepSlot &S, size_t b) {
     return build_phase1(S.blk[b], c->sCopy, c->sPrep, S.p1, S.bnd[b], S.bnd[b + 1] - S.bnd[b]);
+}
+
+static void launch_mean_pose(hipStream_t st, MeanPoseArgs &A, int nDesign, int nLine, double depth, double tolT, double tolR, int max_iter);
+// The pose steps of block b (raftx_sweep_mean_pose), on the preparation stream behind the block's phase 1, no host wait between
+// them: K_hs and F0 from the statics the reductions left at the reference pose (k_pose_assemble, behind the side stream),
+// the Newton solve (k_mean_pose), the poses of the second pass and the outputs to the landing area (k_pose_place), then the
+// member pass, the reductions and the scans again at those poses.  The fixed members' record is for an unposed unit: off.
+static int block_pose(raftx_ctx *c, SweepSlot &S, size_t b) {
+    raftx_ctx *sub = S.blk[b];
+    BuildJob &J = sub->job;
+    GeomArgs &A = J.A;
+    const size_t lo = (size_t)S.bnd[b], nAll = (size_t)S.bnd.back();
+    const int n = S.bnd[b + 1] - S.bnd[b];
+    HIPCHK(sub, sub->evPose.ensure(hipEventDisableTiming));
+    hipStream_t sPrep = c->sPrep;
+    if (n > 0) {
+        if (!J.active || J.nDesign != n) FAIL(sub, "sweep_mean_pose: the block has no member pass in flight (internal error)");
+        HIPCHK(sub, hipStreamWaitEvent(sPrep, S.pose.evUp, 0));
+        if (J.reduce_stream) HIPCHK(sub, hipStreamWaitEvent(sPrep, sub->evRed, 0));
+        const auto &P = S.pose;
+        PoseAssembleArgs Q;
+        memset(&Q, 0, sizeof(Q));
+        Q.n = n; Q.Cs = A.Cs; Q.Ch = A.Ch; Q.Ws = A.Ws; Q.Wh = A.Wh;
+        Q.strideC = P.nX > 1 ? 36 : 0; Q.strideF = P.nX > 1 ? 6 : 0;
+        Q.Cx = P.Cx ? P.Cx + lo * Q.strideC : nullptr;
+        Q.Fx = P.Fx ? P.Fx + lo * Q.strideF : nullptr;
+        Q.K = P.K + lo * 36; Q.F0 = P.F0 + lo * 6;
+        hipLaunchKernelGGL(k_pose_assemble, dim3((unsigned)(((size_t)n * 42 + 255) / 256)), dim3(256), 0, sPrep, Q);
+        MeanPoseArgs M;
+        memset(&M, 0, sizeof(M));
+        M.lines = P.lines + lo * P.nLine * RAFTX_ML_N;
+        M.K_hs = Q.K; M.F0 = Q.F0;
+        M.F_env = P.Fenv ? P.Fenv + lo * 6 : nullptr;
+        M.x_ref = A.pose;                                        // the block's own upload of the caller's pose, or null
+        M.lw = P.lw + lo * P.nLine * MOOR_LW_N;
+        M.pose = P.solved + lo * 6; M.Fres = P.Fres + lo * 6;
+        M.iterations = P.iter + lo; M.flags = P.fl + lo;
+        launch_mean_pose(sPrep, M, n, P.nLine, c->csets[S.cset].T.depth, P.tolT, P.tolR, P.maxIter);
+        PosePlaceArgs L;
+        memset(&L, 0, sizeof(L));
+        L.n = n; L.solved = M.pose; L.x_ref = A.pose; L.Fres = M.Fres; L.iterations = M.iterations; L.flags = M.flags;
+        L.placed = P.placed + lo * 6;
+        L.hPose = P.pin.p + lo * 6; L.hFres = P.pin.p + nAll * 6 + lo * 6;
+        L.hIter = reinterpret_cast<int *>(P.pin.p + nAll * 12) + lo; L.hFlags = P.hFlags(nAll) + lo;
+        hipLaunchKernelGGL(k_pose_place, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, sPrep, L);
+        HIPCHK(sub, hipGetLastError());
+        A.pose = L.placed;
+        A.fixRec = nullptr; A.fixInt = nullptr; A.fixIdx = nullptr; A.fixNM = 0;
+    }
+    HIPCHK(sub, hipEventRecord(sub->evPose, sPrep));
+    if (n > 0) {
+        if (int rc = enqueue_member_repass(sub, sPrep)) return rc;
+        if (int rc = enqueue_scan_reduce(sub, sPrep)) return rc;
+    }
+    return 0;
+}
+// phase 1 of a block that has not had it yet (S.next_p1), with the pose steps of a crossing that asked for them
+static int block_phase1_next(raftx_ctx *c, SweepSlot &S, size_t *which = nullptr) {
+    const size_t bn = S.next_p1++;
+    if (which) *which = bn;
+    if (int rc = block_phase1(c, S, bn)) return rc;
+    return S.pose.on ? block_pose(c, S, bn) : 0;
 }
 
 static int acquire_fixed(raftx_ctx *c, SweepSlot &S);
@@ -3963,8 +4059,8 @@ static int slab_streams(raftx_ctx *c, int n, SlabPlan &plan) {
 // deferred phase 1: keeps one block's upload ahead of block b, the block being launched (whose err takes the text)
 static int phase1_ahead(raftx_ctx *c, SweepSlot &S, size_t b) {
     if (S.next_p1 >= S.blk.size() || S.next_p1 > b + 1) return 0;
-    const size_t bn = S.next_p1++;
-    const int rc = block_phase1(c, S, bn);
+    size_t bn = 0;
+    const int rc = block_phase1_next(c, S, &bn);
     if (rc) snprintf(S.blk[b]->err, sizeof(S.blk[b]->err), "%s", S.blk[bn]->err);
     return rc;
 }
@@ -4002,7 +4098,8 @@ static int launch_block(raftx_ctx *c, SweepSlot &S, int slot, size_t b, LaunchMo
     // (a crossing: no ABI copy of the strip records; with RAFTX_FUSED_GEN=1 the tables are left to the fused kernel itself,
     // raftx_fusedgen.h -- build_phase2 / solve_enqueue decide)
     // (a crossing with current loads reads the tables after the solve: they are never left to the fused kernel)
-    const int kind = GEN_CROSSING | ((S.nCase == 1 && !S.slab && !S.current.on) ? GEN_MAY_DEFER : 0) | (M.pipelined ? GEN_PIPELINED : 0);
+    // (nor with a mean-pose request: the second member pass is the plain one, and so is the generation)
+    const int kind = GEN_CROSSING | ((S.nCase == 1 && !S.slab && !S.current.on && !S.pose.on) ? GEN_MAY_DEFER : 0) | (M.pipelined ? GEN_PIPELINED : 0);
     if (!rc) rc = build_phase2(sub, nullptr, M.pipelined ? c->sGen : nullptr, kind);
     S.tlb.push_back(S.since());
     if (!rc) {
@@ -4177,6 +4274,44 @@ static hipError_t collect_mooring(SweepSlot &S) {
     memcpy(S.mooring.flags_out, p + n * (42 + nT), n * sizeof(int32_t));
     return hipSuccess;
 }
+// The solve's outputs out of their landing area (k_pose_place wrote them ahead of the block's second member pass, which the
+// crossing has been waited for through), and the pose-flagged designs: such a design was solved at the reference pose so that
+// its block could go on, and nothing of that may pass for a result -- everything handed out for it becomes NaN and its
+// flags take RAFTX_FLAG_NAN.  Host work after the copies: no other design's bits change.
+static void collect_pose(SweepSlot &S) {
+    if (!S.pose.on) return;
+    const size_t n = S.bnd.empty() ? 0 : (size_t)S.bnd.back(), nC = (size_t)S.nCase;
+    const double *p = S.pose.pin.p;
+    const int32_t *fl = S.pose.hFlags(n);
+    if (S.pose.pose_out) memcpy(S.pose.pose_out, p, n * 6 * sizeof(double));
+    if (S.pose.Fres_out) memcpy(S.pose.Fres_out, p + n * 6, n * 6 * sizeof(double));
+    if (S.pose.iter_out) memcpy(S.pose.iter_out, p + n * 12, n * sizeof(int32_t));
+    memcpy(S.pose.flags_out, fl, n * sizeof(int32_t));
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    auto blank = [&](double *a, size_t d, size_t per) {
+        if (a) std::fill(a + d * per, a + (d + 1) * per, nan);
+    };
+    for (size_t d = 0; d < n; d++) {
+        if (!fl[d]) continue;
+        blank(S.sd, d, nC * 6);
+        for (size_t i = 0; i < nC; i++) S.flags[d * nC + i] |= RAFTX_FLAG_NAN;
+        if (S.Xi) blank(reinterpret_cast<double *>(S.Xi), d, nC * S.nHead * 6 * S.nw * 2);
+        if (S.modal.on) {
+            blank(S.modal.fn, d, 6);
+            blank(S.modal.modes, d, 36);
+            blank(S.modal.props, d, RAFTX_SP_N);
+        }
+        if (S.current.on) blank(S.current.D, d, (size_t)S.current.nCur * 6);
+        if (S.channels.on) blank(S.channels.out, d, nC * S.channels.nChan);
+        if (S.mooring.on) {
+            const size_t nT = 2 * (size_t)S.mooring.nLine;
+            blank(S.mooring.C_out, d, 36);
+            blank(S.mooring.F_out, d, 6);
+            blank(S.mooring.T_out, d, nT);
+            blank(S.mooring.Tstd_out, d, nC * nT);
+        }
+    }
+}
 // RAFTX_SWEEP_DEBUG: the host's timeline of the crossing on stderr
 static void debug_timeline(const SweepSlot &S, int slot, double wall) {
     static const bool dbg_host = getenv("RAFTX_SWEEP_DEBUG") != nullptr;
@@ -4206,6 +4341,7 @@ extern "C" int raftx_sweep_wait(raftx_ctx *c, int slot, double *timing_ms) {
     if (S.stripOffsets) S.stripOffsets[0] = 0;
     for (size_t b = 0; b < S.blk.size(); b++) collect_block(S, b, t);
     const hipError_t em = collect_mooring(S);
+    if (em == hipSuccess) collect_pose(S);
     S.clear_requests();
     HIPCHK(c, em);
     t[0] = S.since();
@@ -4496,6 +4632,22 @@ extern "C" int raftx_mooring_expand(raftx_ctx *c, int nDesign, const double *par
 }
 
 // ---- the mean equilibrium pose (include/raftx_statics.h, raftx_statics.h)
+// the tolerances of an entry point `who`: {m, rad}, or null for the defaults
+static int mean_pose_tol(raftx_ctx *c, const char *who, const double tol[2], double *tolT, double *tolR) {
+    *tolT = tol ? tol[0] : 1e-9;
+    *tolR = tol ? tol[1] : 1e-10;
+    if (!std::isfinite(*tolT) || !std::isfinite(*tolR) || *tolT < 0.0 || *tolR < 0.0)
+        FAIL(c, "%s: the tolerances must be finite and not negative (got %g m, %g rad)", who, *tolT, *tolR);
+    return 0;
+}
+// The launch both entries share (raftx_mean_pose: a batch; raftx_sweep_mean_pose: a block of a crossing): A holds the arrays
+// of nDesign > 0 designs, the settings are filled in here, the whole iteration is one launch on st.
+static void launch_mean_pose(hipStream_t st, MeanPoseArgs &A, int nDesign, int nLine, double depth, double tolT, double tolR, int max_iter) {
+    A.nDesign = nDesign; A.nLine = nLine; A.G = mean_pose_group(nLine); A.maxIter = max_iter > 0 ? max_iter : MP_MAX_IT;
+    A.depth = depth; A.tolT = tolT; A.tolR = tolR;
+    const int perBlock = MP_THREADS / A.G;
+    hipLaunchKernelGGL(k_mean_pose, dim3((unsigned)((nDesign + perBlock - 1) / perBlock)), dim3(MP_THREADS), 0, st, A);
+}
 extern "C" int raftx_mean_pose(raftx_ctx *c, int nDesign, int nLine, const double *lines, const double *params, double depth,
                                const double *K_hs, const double *F0, const double *F_env, const double *x_ref, const double tol[2],
                                int max_iter, double *pose, double *C_moor, double *F_moor, double *T, double *J, double *F_res,
@@ -4505,9 +4657,8 @@ extern "C" int raftx_mean_pose(raftx_ctx *c, int nDesign, int nLine, const doubl
     if (nDesign < 0) FAIL(c, "mean_pose: nDesign must not be negative (got %d)", nDesign);
     if (!K_hs || !F0 || !flags) FAIL(c, "mean_pose: bad arguments (K_hs, F0 and flags are required)");
     if (!std::isfinite(depth) || !(depth > 0.0)) FAIL(c, "mean_pose: the depth must be positive and finite (got %g)", depth);
-    const double tolT = tol ? tol[0] : 1e-9, tolR = tol ? tol[1] : 1e-10;
-    if (!std::isfinite(tolT) || !std::isfinite(tolR) || tolT < 0.0 || tolR < 0.0)
-        FAIL(c, "mean_pose: the tolerances must be finite and not negative (got %g m, %g rad)", tolT, tolR);
+    double tolT, tolR;
+    if (int rc = mean_pose_tol(c, "mean_pose", tol, &tolT, &tolR)) return rc;
     const size_t nl = (size_t)nDesign * nLine;
     if (!lines) {
         if (!c->mprog.nLine) FAIL(c, "mean_pose: lines == NULL without a mooring program (raftx_mooring_program first)");
@@ -4527,8 +4678,6 @@ extern "C" int raftx_mean_pose(raftx_ctx *c, int nDesign, int nLine, const doubl
     const size_t n = (size_t)nDesign;
     MeanPoseArgs A;
     memset(&A, 0, sizeof(A));
-    A.nDesign = nDesign; A.nLine = nLine; A.G = mean_pose_group(nLine); A.maxIter = max_iter > 0 ? max_iter : MP_MAX_IT;
-    A.depth = depth; A.tolT = tolT; A.tolR = tolR;
     const int nP = lines ? 0 : c->mprog.nP;
     double *dl = sc.alloc<double>(nl * RAFTX_ML_N), *dpar = (!lines && nP) ? sc.alloc<double>(n * nP) : nullptr;
     double *dK = sc.alloc<double>(n * 36), *dF0 = sc.alloc<double>(n * 6), *dFe = F_env ? sc.alloc<double>(n * 6) : nullptr;
@@ -4557,8 +4706,7 @@ extern "C" int raftx_mean_pose(raftx_ctx *c, int nDesign, int nLine, const doubl
         MoorExpandArgs E{nDesign, nLine, nP, c->mprog.base.p, c->mprog.coef.p, c->mprog.edit.p, dpar, dl};
         hipLaunchKernelGGL(k_moor_expand, dim3(moor_grid((long long)nl)), dim3(MOOR_THREADS), 0, c->stream, E);
     }
-    const int perBlock = MP_THREADS / A.G;
-    hipLaunchKernelGGL(k_mean_pose, dim3((unsigned)((nDesign + perBlock - 1) / perBlock)), dim3(MP_THREADS), 0, c->stream, A);
+    launch_mean_pose(c->stream, A, nDesign, nLine, depth, tolT, tolR, max_iter);
     if (finish_timed(c)) return -2;
     if (pose) D2H(c, pose, A.pose, n * 6 * sizeof(double));
     if (C_moor) D2H(c, C_moor, A.C, n * 36 * sizeof(double));
@@ -4608,7 +4756,22 @@ extern "C" int raftx_sweep_mooring(raftx_ctx *c, int slot, int nLine, const doub
     A.nDesign = (int)n; A.nLine = nLine; A.depth = depth;
     const double *dl = nullptr, *dp = nullptr, *dpar = nullptr;
     double *dexp = nullptr;
-    int rc = upload_on(c, c->sCopy, S.allocs, S.p1.pose, S.p1.pose ? n * 6 : 0, &dp);
+    int rc = 0;
+    if (S.pose.on) {
+        // behind a raftx_sweep_mean_pose request: at the poses its placement kernels leave on the device, so every block's
+        // pose steps are enqueued now (the blocks whose phase 1 was left to raftx_sweep_launch included) and the copy stream
+        // waits for them
+        while (S.next_p1 < S.blk.size())
+            if (const int rp = block_phase1_next(c, S)) {
+                snprintf(c->err, sizeof(c->err), "sweep_mooring (block %zu): %s", S.next_p1 - 1, S.blk[S.next_p1 - 1]->err);
+                S.prepared = false;
+                S.clear_requests();
+                return sweep_fail_drain(c, S, rp);
+            }
+        for (raftx_ctx *sub : S.blk) HIPCHK(c, hipStreamWaitEvent(c->sCopy, sub->evPose, 0));
+        dp = S.pose.placed;
+    } else
+        rc = upload_on(c, c->sCopy, S.allocs, S.p1.pose, S.p1.pose ? n * 6 : 0, &dp);
     if (lines) rc |= upload_on(c, c->sCopy, S.allocs, lines, nl * RAFTX_ML_N, &dl);
     else {
         rc |= upload_on(c, c->sCopy, S.allocs, S.p1.var.params, n * (size_t)vp->nP, &dpar);
@@ -4643,6 +4806,81 @@ extern "C" int raftx_sweep_mooring(raftx_ctx *c, int slot, int nLine, const doub
     S.mooring.C_out = C_moor; S.mooring.F_out = F_moor; S.mooring.T_out = T_mean; S.mooring.Tstd_out = T_std;
     S.mooring.flags_out = flags;
     S.mooring.on = true;
+    return 0;
+}
+
+// ---- the crossing at every design's mean pose (include/raftx_statics.h)
+extern "C" int raftx_sweep_mean_pose(raftx_ctx *c, int slot, int nLine, const double *lines, int nX, const double *C_extra,
+                                     const double *F_extra, const double *F_env, const double tol[2], int max_iter, double *pose,
+                                     double *F_res, int32_t *iterations, int32_t *flags) {
+    if (!c) return -1;
+    SweepSlot *slot_ = nullptr;
+    if (int rc = request_slot(c, slot, "sweep_mean_pose", true, &slot_)) return rc;
+    SweepSlot &S = *slot_;
+    if (!flags) FAIL(c, "sweep_mean_pose: bad arguments (flags is required)");
+    // (unlike the other requests this one runs phase 1 again: a second one is refused, not taken in place of the first)
+    if (S.pose.on) FAIL(c, "sweep_mean_pose: slot %d already has a mean-pose request", slot);
+    if (S.mooring.on)
+        FAIL(c, "sweep_mean_pose: slot %d already has a mooring request, which was evaluated at the caller's pose (ask for the mean pose first)", slot);
+    const size_t n = S.bnd.empty() ? 0 : (size_t)S.bnd.back();
+    if (nX != 0 && nX != 1 && (size_t)nX != n)
+        FAIL(c, "sweep_mean_pose: nX=%d must be 0 (no extras), 1 (shared) or the %zu designs of the crossing", nX, n);
+    const VariantProg *vp = S.p1.var.prog;
+    if (!lines) {
+        if (!vp) FAIL(c, "sweep_mean_pose: lines == NULL needs a slot prepared with raftx_sweep_prepare_variants");
+        if (!c->mprog.nLine) FAIL(c, "sweep_mean_pose: no mooring program (raftx_mooring_program first)");
+        if (c->mprog.nP != vp->nP) FAIL(c, "sweep_mean_pose: the mooring program has %d parameters, the variant program %d", c->mprog.nP, vp->nP);
+        if (nLine != c->mprog.nLine) FAIL(c, "sweep_mean_pose: nLine=%d is not the %d lines of the mooring program", nLine, c->mprog.nLine);
+    } else {
+        if (nLine < 1) FAIL(c, "sweep_mean_pose: nLine must be positive (got %d)", nLine);
+        for (size_t i = 0; i < n * (size_t)nLine; i++) {
+            const double cb = lines[i * RAFTX_ML_N + 9];
+            if (std::isfinite(cb) && cb != 0.0)
+                FAIL(c, "sweep_mean_pose: line %zu of design %zu has seabed friction CB = %g: friction is not covered (CB must be 0)",
+                     i % nLine, i / nLine, cb);
+        }
+    }
+    const double depth = c->csets[S.cset].T.depth;
+    if (!std::isfinite(depth) || !(depth > 0.0)) FAIL(c, "sweep_mean_pose: the depth must be positive and finite (got %g)", depth);
+    double tolT, tolR;
+    if (int rc = mean_pose_tol(c, "sweep_mean_pose", tol, &tolT, &tolR)) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    auto &P = S.pose;
+    HIPCHK(c, P.evUp.ensure(hipEventDisableTiming));
+    HIPCHK(c, P.pin.reserve(n * 13 + 2));
+    const size_t nl = n * (size_t)nLine;
+    const double *dl = nullptr, *dpar = nullptr;
+    double *dexp = nullptr;
+    int rc = 0;
+    if (lines) rc |= upload_on(c, c->sCopy, S.allocs, lines, nl * RAFTX_ML_N, &dl);
+    else {
+        rc |= upload_on(c, c->sCopy, S.allocs, S.p1.var.params, n * (size_t)vp->nP, &dpar);
+        rc |= pool_alloc(c, S.allocs, nl * RAFTX_ML_N, &dexp);
+        dl = dexp;
+    }
+    rc |= upload_on(c, c->sCopy, S.allocs, C_extra, (size_t)nX * 36, &P.Cx) | upload_on(c, c->sCopy, S.allocs, F_extra, (size_t)nX * 6, &P.Fx) |
+          upload_on(c, c->sCopy, S.allocs, F_env, n * 6, &P.Fenv);
+    rc |= pool_alloc(c, S.allocs, n * 36, &P.K) | pool_alloc(c, S.allocs, n * 6, &P.F0) | pool_alloc(c, S.allocs, nl * MOOR_LW_N, &P.lw) |
+          pool_alloc(c, S.allocs, n * 6, &P.solved) | pool_alloc(c, S.allocs, n * 6, &P.placed) | pool_alloc(c, S.allocs, n * 6, &P.Fres) |
+          pool_alloc(c, S.allocs, n, &P.iter) | pool_alloc(c, S.allocs, n, &P.fl);
+    if (rc) return -2;
+    if (n && !lines) {
+        MoorExpandArgs E{(int)n, nLine, vp->nP, c->mprog.base.p, c->mprog.coef.p, c->mprog.edit.p, dpar, dexp};
+        hipLaunchKernelGGL(k_moor_expand, dim3(moor_grid((long long)nl)), dim3(MOOR_THREADS), 0, c->sCopy, E);
+        HIPCHK(c, hipGetLastError());
+    }
+    HIPCHK(c, hipEventRecord(P.evUp, c->sCopy));
+    P.lines = dl; P.nLine = nLine; P.nX = nX; P.maxIter = max_iter; P.tolT = tolT; P.tolR = tolR;
+    P.pose_out = pose; P.Fres_out = F_res; P.iter_out = iterations; P.flags_out = flags;
+    P.on = true;
+    // the blocks whose phase 1 raftx_sweep_prepare enqueued; raftx_sweep_launch does the others behind their phase 1
+    for (size_t b = 0; b < S.next_p1 && b < S.blk.size(); b++)
+        if (const int rb = block_pose(c, S, b)) {
+            snprintf(c->err, sizeof(c->err), "sweep_mean_pose (block %zu): %s", b, S.blk[b]->err);
+            S.prepared = false;
+            S.clear_requests();
+            return sweep_fail_drain(c, S, rb);
+        }
     return 0;
 }
 

@@ -208,6 +208,58 @@ __global__ void __launch_bounds__(MP_THREADS) k_mean_pose(MeanPoseArgs A) {
     }
 }
 
+// ---- the solve inside a sweep crossing (raftx_sweep_mean_pose): two small kernels around k_mean_pose, per block of the crossing.
+// k_pose_assemble forms the solve's inputs from what the member -> platform reductions left at the reference pose,
+//   K_hs = (C_struc + C_hydro) + C_extra          F0 = (W_struc + W_hydro) + F_extra
+// in the association of raft_amd/statics.py hydrostatics(): sums only, nothing to contract, so the bits are NumPy's.  An absent
+// extra adds nothing (not even a zero: -0 stays -0).  strideC / strideF: 36 / 6 for per-design extras, 0 for shared ones.
+struct PoseAssembleArgs {
+    int n;
+    const double *__restrict__ Cs, *__restrict__ Ch, *__restrict__ Ws, *__restrict__ Wh;   // [n,36] [n,36] [n,6] [n,6]
+    const double *__restrict__ Cx, *__restrict__ Fx;                                       // at the block's first design, or null
+    size_t strideC, strideF;
+    double *__restrict__ K, *__restrict__ F0;                                              // [n,36] [n,6]
+};
+__global__ void __launch_bounds__(256) k_pose_assemble(PoseAssembleArgs A) {
+    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x, nK = (size_t)A.n * 36, nF = (size_t)A.n * 6;
+    if (t < nK) {
+        double v = A.Cs[t] + A.Ch[t];
+        if (A.Cx) v = v + A.Cx[(t / 36) * A.strideC + t % 36];
+        A.K[t] = v;
+    } else if (t < nK + nF) {
+        const size_t u = t - nK;
+        double v = A.Ws[u] + A.Wh[u];
+        if (A.Fx) v = v + A.Fx[(u / 6) * A.strideF + u % 6];
+        A.F0[u] = v;
+    }
+}
+// k_pose_place, one lane per design: the pose the block's second member pass runs at -- the solved one, or the reference pose
+// for a flagged design (its solved pose is NaN, and a NaN pose must never reach geom_member_body: its rejections abort a whole
+// batch) -- and the solve's outputs straight into the slot's page-locked landing area (no small D2H copy to queue on the DMA
+// engine), the flagged design's as NaN as k_mean_pose left them.
+struct PosePlaceArgs {
+    int n;
+    const double *__restrict__ solved, *__restrict__ x_ref, *__restrict__ Fres;            // [n,6]; x_ref or null (zero)
+    const int *__restrict__ iterations, *__restrict__ flags;                               // [n]
+    double *__restrict__ placed;                                                           // [n,6] device
+    double *__restrict__ hPose, *__restrict__ hFres;                                       // [n,6] page-locked
+    int *__restrict__ hIter, *__restrict__ hFlags;                                         // [n] page-locked
+};
+__global__ void __launch_bounds__(64) k_pose_place(PosePlaceArgs A) {
+    const int d = blockIdx.x * blockDim.x + threadIdx.x;
+    if (d >= A.n) return;
+    const int fl = A.flags[d];
+#pragma unroll
+    for (int i = 0; i < 6; i++) {
+        const double xs = A.solved[(size_t)d * 6 + i];
+        A.placed[(size_t)d * 6 + i] = fl ? (A.x_ref ? A.x_ref[(size_t)d * 6 + i] : 0.0) : xs;
+        A.hPose[(size_t)d * 6 + i] = xs;
+        A.hFres[(size_t)d * 6 + i] = A.Fres[(size_t)d * 6 + i];
+    }
+    A.hIter[d] = A.iterations[d];
+    A.hFlags[d] = fl;
+}
+
 static inline int mean_pose_group(int nLine) {
     int G = 1;
     while (G < nLine && G < MP_THREADS) G *= 2;

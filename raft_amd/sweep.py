@@ -316,16 +316,17 @@ class GeometrySweep(Sweep):
                                             None if self.MBw is None else self.MBw[lo:hi], self.rho, self.g), lo, hi)
 
     def run_crossing(self, ctx, n_chunk=0, n_worker=0, want_Xi=False, Xi_out=None, modal=False, dM=None, dC=None, want_props=False,
-                     current=None, channels=None, mooring=None):
+                     current=None, channels=None, mooring=None, mean_pose=None):
         """The whole boundary crossing in ONE library call (raftx_sweep_stats): descriptors in, motion statistics +
         iteration counts (+ responses) out, with upload / generation / solve / download of consecutive design blocks
         overlapped on the library's internal streams.  Nothing stays resident on ``ctx``.  modal=True / current=dict(..) /
         channels=dict(..): the streamed form on slot 0 with the eigen analysis / mean current loads of every design /
         output channels of every (design, case) (see ``prepare_crossing``)."""
-        if modal or current is not None or channels is not None or mooring is not None or self.mooring is not None:
+        if (modal or current is not None or channels is not None or mooring is not None or self.mooring is not None or
+                mean_pose is not None or self.mean_pose is not None):
             return self.wait_crossing(ctx, self.submit_crossing(ctx, 0, n_chunk=n_chunk, want_Xi=want_Xi, Xi_out=Xi_out, modal=modal,
                                                                 dM=dM, dC=dC, want_props=want_props, current=current,
-                                                                channels=channels, mooring=mooring))
+                                                                channels=channels, mooring=mooring, mean_pose=mean_pose))
         self._crossing_supported()
         t = self.tables
         r = ctx.sweep_stats(t, self.M0, self.B0, self.C0, self.w, self.k, self.depth, self.zeta, self.beta, self.nIter,
@@ -335,7 +336,7 @@ class GeometrySweep(Sweep):
         return r
 
     def prepare_crossing(self, ctx, slot, n_chunk=0, want_Xi=False, Xi_out=None, modal=False, dM=None, dC=None, want_props=False,
-                         current=None, channels=None, mooring=None):
+                         current=None, channels=None, mooring=None, mean_pose=None):
         """First stage of the streamed form of ``run_crossing`` for back-to-back batches: enqueue this batch's descriptor
         upload and member pass on ``slot`` (0 .. 3) and return a handle (raftx_sweep_prepare).  modal=True: the batch's
         eigen analysis rides along (raftx_sweep_modal on M_extra + device terms + dM, C_extra + device terms + dC) and
@@ -349,11 +350,17 @@ class GeometrySweep(Sweep):
         (raftx_sweep_mooring; lines [nD,nLine,16] records of raft_amd.mooring, or program= a MooringProgram on a
         VariantSweep, fed the batch's params): C_moor is added to the device C0 ahead of the add-up and ``wait_crossing``
         also returns C_moor, F_moor, T_mean, T_std, moor_flags.  A request stored as ``sweep.mooring`` is used when the
-        argument is None; ``take`` shards its lines with the designs."""
+        argument is None; ``take`` shards its lines with the designs.  mean_pose=dict(lines= | program=, C_extra=, F_extra=,
+        F_env=, tol=, max_iter=): the crossing runs at every design's own mean equilibrium pose (raftx_sweep_mean_pose):
+        hydrostatics at this sweep's pose with C_extra / F_extra (statics only; [6,6] / [6] shared or per design), the Newton
+        solve of raft_amd.statics.mean_pose under F_env [nD,6], then the member pass again and the crossing at the solved
+        pose, all on the device; ``wait_crossing`` also returns pose, F_res, pose_iterations, pose_flags, and a flagged
+        design comes back as NaN.  It is issued ahead of a mooring= request of the same call, which then evaluates the lines
+        at the solved pose.  ``sweep.mean_pose`` is the standing form; ``take`` shards its per-design arrays."""
         self._crossing_supported()
-        return self._with_mooring(ctx, self._with_channels(ctx, self._with_current(ctx, self._with_modal(ctx, ctx.sweep_prepare(slot, self.tables, self.M0, self.B0, self.C0, self.w, self.k, self.depth, self.zeta, self.beta,
+        return self._with_mooring(ctx, self._with_mean_pose(ctx, self._with_channels(ctx, self._with_current(ctx, self._with_modal(ctx, ctx.sweep_prepare(slot, self.tables, self.M0, self.B0, self.C0, self.w, self.k, self.depth, self.zeta, self.beta,
                                  self.nIter, self.tol, self.XiStart, pose=self.pose, rho=self.rho, g=self.g, add_mask=self.add_mask,
-                                 n_chunk=n_chunk, want_Xi=want_Xi, Xi_out=Xi_out), modal, dM, dC, want_props), current), channels), mooring)
+                                 n_chunk=n_chunk, want_Xi=want_Xi, Xi_out=Xi_out), modal, dM, dC, want_props), current), channels), mean_pose), mooring)
 
     @staticmethod
     def _with_modal(ctx, handle, modal, dM, dC, want_props):
@@ -401,7 +408,7 @@ class GeometrySweep(Sweep):
             sub.mooring = dict(self.mooring)
             if sub.mooring.get("lines") is not None:
                 sub.mooring["lines"] = np.ascontiguousarray(np.asarray(self.mooring["lines"])[lo:hi])
-        return sub
+        return self._take_mean_pose(sub, lo, hi)
 
     def _with_mooring(self, ctx, handle, mooring):
         mooring = self.mooring if mooring is None else mooring
@@ -420,6 +427,41 @@ class GeometrySweep(Sweep):
             ctx.sweep_cancel(handle)
             raise
 
+    mean_pose = None      # a standing mean_pose= request of this sweep (dict as in ``prepare_crossing``); ``take`` shards it
+    _MEAN_POSE_KEYS = ("lines", "program", "C_extra", "F_extra", "F_env", "tol", "max_iter")
+
+    @classmethod
+    def _check_mean_pose(cls, mean_pose):
+        unknown = set(mean_pose) - set(cls._MEAN_POSE_KEYS)
+        if unknown or (mean_pose.get("lines") is None) == (mean_pose.get("program") is None):
+            raise ValueError("mean_pose=dict(lines= | program=[, C_extra=, F_extra=, F_env=, tol=, max_iter=]) (got %s)" % sorted(mean_pose))
+
+    def _take_mean_pose(self, sub, lo, hi):
+        if self.mean_pose is not None:
+            self._check_mean_pose(self.mean_pose)
+            sub.mean_pose = dict(self.mean_pose)
+            for key, shared_ndim in (("lines", None), ("F_env", None), ("C_extra", 2), ("F_extra", 1)):
+                a = self.mean_pose.get(key)
+                if a is not None and np.ndim(a) != shared_ndim:
+                    sub.mean_pose[key] = np.ascontiguousarray(np.asarray(a)[lo:hi])
+        return sub
+
+    def _with_mean_pose(self, ctx, handle, mean_pose):
+        mean_pose = self.mean_pose if mean_pose is None else mean_pose
+        if mean_pose is None:
+            return handle
+        try:
+            self._check_mean_pose(mean_pose)
+            prog = mean_pose.get("program")
+            if prog is not None and getattr(ctx, "_mprog_owner", None) is not prog:
+                ctx.mooring_program(prog)
+            return ctx.sweep_mean_pose(handle, lines=mean_pose.get("lines"), C_extra=mean_pose.get("C_extra"),
+                                       F_extra=mean_pose.get("F_extra"), F_env=mean_pose.get("F_env"), tol=mean_pose.get("tol"),
+                                       max_iter=mean_pose.get("max_iter") or 0)
+        except Exception:
+            ctx.sweep_cancel(handle)
+            raise
+
     def launch_crossing(self, ctx, handle):
         """Second stage: table generation, fused fixed point and statistics of a prepared batch (raftx_sweep_launch).  With
         launch(i+1), prepare(i+2), wait(i) per step a long sweep keeps three batches in flight and the fused kernels of
@@ -427,11 +469,11 @@ class GeometrySweep(Sweep):
         return ctx.sweep_launch(handle)
 
     def submit_crossing(self, ctx, slot, n_chunk=0, want_Xi=False, Xi_out=None, modal=False, dM=None, dC=None, want_props=False,
-                        current=None, channels=None, mooring=None):
+                        current=None, channels=None, mooring=None, mean_pose=None):
         """prepare + launch in one call (raftx_sweep_submit); ``wait_crossing`` collects the results."""
         return self.launch_crossing(ctx, self.prepare_crossing(ctx, slot, n_chunk=n_chunk, want_Xi=want_Xi, Xi_out=Xi_out,
                                                                modal=modal, dM=dM, dC=dC, want_props=want_props, current=current,
-                                                               channels=channels, mooring=mooring))
+                                                               channels=channels, mooring=mooring, mean_pose=mean_pose))
 
     def _crossing_supported(self):
         """raftx_sweep_stats / raftx_sweep_submit carry neither frequency-dependent matrices nor potential-flow excitation
@@ -829,20 +871,20 @@ class VariantSweep(GeometrySweep):
         return self._take_mooring(self._take_bem(sub, lo, hi), lo, hi)
 
     def prepare_crossing(self, ctx, slot, n_chunk=0, want_Xi=False, Xi_out=None, modal=False, dM=None, dC=None, want_props=False,
-                         current=None, channels=None, mooring=None):
+                         current=None, channels=None, mooring=None, mean_pose=None):
         self._crossing_supported()
         self._install(ctx)
-        return self._with_mooring(ctx, self._with_channels(ctx, self._with_current(ctx, self._with_modal(ctx, ctx.sweep_prepare_variants(slot, self.params, self.M0, self.B0, self.C0, self.w, self.k, self.depth, self.zeta, self.beta,
+        return self._with_mooring(ctx, self._with_mean_pose(ctx, self._with_channels(ctx, self._with_current(ctx, self._with_modal(ctx, ctx.sweep_prepare_variants(slot, self.params, self.M0, self.B0, self.C0, self.w, self.k, self.depth, self.zeta, self.beta,
                                           self.nIter, self.tol, self.XiStart, pose=self.pose, rho=self.rho, g=self.g,
                                           add_mask=self.add_mask, n_chunk=n_chunk, want_Xi=want_Xi, Xi_out=Xi_out),
-                                modal, dM, dC, want_props), current), channels), mooring)
+                                modal, dM, dC, want_props), current), channels), mean_pose), mooring)
 
     def run_crossing(self, ctx, n_chunk=0, n_worker=0, want_Xi=False, Xi_out=None, slot=0, modal=False, dM=None, dC=None,
-                     want_props=False, current=None, channels=None, mooring=None):
+                     want_props=False, current=None, channels=None, mooring=None, mean_pose=None):
         """One isolated crossing: prepare + launch + wait on ``slot``."""
         return self.wait_crossing(ctx, self.submit_crossing(ctx, slot, n_chunk=n_chunk, want_Xi=want_Xi, Xi_out=Xi_out, modal=modal,
                                                             dM=dM, dC=dC, want_props=want_props, current=current, channels=channels,
-                                                            mooring=mooring))
+                                                            mooring=mooring, mean_pose=mean_pose))
 
     def _build_qtf_tables(self, ctx):
         self._install(ctx)

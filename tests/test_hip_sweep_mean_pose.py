@@ -1,0 +1,285 @@
+"""The mean-pose request on a sweep crossing (raftx_sweep_mean_pose, include/raftx_statics.h): C3 variants under a thrust-like
+load, in the three forms of test_hip_sweep_mooring.py.  The request is a COMPOSITION of pieces that are each held to a
+reference elsewhere, so everything here is bit for bit: the crossing with ``mean_pose=`` against the host route it replaces
+(resident build at the reference pose, ``statics.hydrostatics``, ``statics.mean_pose``, the same crossing with ``pose=``)."""
+import numpy as np
+import pytest
+
+from raft_amd import geometry as G
+from raft_amd import snapshot as standin
+from raft_amd import statics
+from raft_amd._abi import RaftxError
+from raft_amd.sweep import GeometrySweep
+from tests import mooring_reference as mr
+from tests.test_geometry import C3, _c3_crossing_inputs
+from tests.test_hip_modal import _variant_sweep
+from tests.test_hip_sweep_channels import same_bits
+from tests.test_hip_sweep_mooring import BITS, DEPTH, PARENT_SHA, plain_hashes, program
+
+pytestmark = pytest.mark.gpu
+N = 6
+HUB = 150.0
+KEYS = BITS + ("strip_off",)
+POSE_KEYS = (("pose", "pose"), ("pose_iterations", "iterations"), ("F_res", "F_res"), ("pose_flags", "flags"))
+
+_u0 = [u for u in standin.load_fixture("geom_units.npz")["units"] if u["name"] == "C3-variant-0"][0]
+C_RNA = np.asarray(_u0["C_struc"]) - np.asarray(_u0["C_struc_bare"])      # the rotor-nacelle shares: statics only
+W_RNA = np.asarray(_u0["W_struc"]) - np.asarray(_u0["W_struc_bare"])
+
+
+def thrust(n):
+    """[n,6]: 0.2 .. 1.5 MN along x at hub height."""
+    T = np.linspace(0.2e6, 1.5e6, n)
+    F = np.zeros((n, 6))
+    F[:, 0], F[:, 4] = T, HUB * T
+    return F
+
+
+def descriptor_sweep(n, add_mask=7):
+    D, M0, B0, C0 = _c3_crossing_inputs(n)
+    return GeometrySweep(D, M0, B0, C0, C3["w"], C3["k"], DEPTH, np.asarray(C3["zeta"])[None], np.asarray(C3["beta"])[None],
+                         int(C3["nIter"]), float(C3["XiStart"]), add_mask=add_mask)
+
+
+def forms(n=N):
+    """(name, sweep, the request's line source, lines): variants + program, variants + lines, descriptors + lines."""
+    mp = program()
+    lines = mp.expand(G.volturnus_params(np.asarray(C3["scales"])[:n]))
+    return [("variants, program", _variant_sweep(n), dict(program=mp), lines), ("variants, lines", _variant_sweep(n), dict(lines=lines), lines),
+            ("descriptors, lines", descriptor_sweep(n), dict(lines=lines), lines)]
+
+
+def request(src, n, **kw):
+    return dict(C_extra=C_RNA, F_extra=W_RNA, F_env=thrust(n), **src, **kw)
+
+
+def run(ctx, sw, slot=0, n_chunk=1, **kw):
+    return sw.wait_crossing(ctx, sw.submit_crossing(ctx, slot, n_chunk=n_chunk, want_Xi=True, modal=True, **kw))
+
+
+def stand_alone(ctx, sw, lines, x_ref=None, **kw):
+    """The host route up to the pose: resident build at x_ref, hydrostatics, the stand-alone solve."""
+    keep, sw.pose = sw.pose, x_ref
+    try:
+        sw.upload(ctx)
+    finally:
+        sw.pose = keep
+    K_hs, F0, _ = statics.hydrostatics(ctx, C_extra=C_RNA, F_extra=W_RNA)
+    return statics.mean_pose(ctx, K_hs, F0, lines=lines, depth=DEPTH, F_env=thrust(len(lines)), x_ref=x_ref, **kw)
+
+
+def host_route(ctx, sw, lines, x_ref=None, n_chunk=1, **kw):
+    """(MeanPose, crossing with pose= that result)."""
+    res = stand_alone(ctx, sw, lines, x_ref)
+    assert not res.flags.any()
+    keep, sw.pose = sw.pose, res.pose
+    try:
+        return res, run(ctx, sw, n_chunk=n_chunk, **kw)
+    finally:
+        sw.pose = keep
+
+
+def assert_composition(got, res, want, what):
+    for k in KEYS:
+        assert same_bits(got[k], want[k]), (what, k)
+    for k, r in POSE_KEYS:
+        assert same_bits(got[k], getattr(res, r)), (what, k)
+
+
+def test_composition_bit_for_bit(hip_ctx):
+    for name, sw, src, lines in forms():
+        res, want = host_route(hip_ctx, sw, lines)
+        req = request(src, N)
+        for slot, n_chunk in ((0, 1), (0, 3), (2, 1), (2, 3)):
+            assert_composition(run(hip_ctx, sw, slot=slot, n_chunk=n_chunk, mean_pose=req), res, want, (name, slot, n_chunk))
+        h0 = sw.submit_crossing(hip_ctx, 0, want_Xi=True, modal=True, mean_pose=req)
+        h1 = sw.submit_crossing(hip_ctx, 1, n_chunk=3, want_Xi=True, modal=True, mean_pose=req)
+        for h in (h0, h1):
+            assert_composition(sw.wait_crossing(hip_ctx, h), res, want, (name, "two in flight"))
+
+
+def test_composition_from_a_reference_pose(hip_ctx):
+    """x_ref != 0: the start of the solve, the origin of the hydrostatic reaction, and no fixed-member records."""
+    x_ref = np.array([1.0, -0.5, 0.3, 0.01, -0.02, 0.03]) * np.linspace(0.5, 1.5, N)[:, None]
+    for name, sw, src, lines in forms()[::2]:
+        res, want = host_route(hip_ctx, sw, lines, x_ref=x_ref)
+        sw.pose = x_ref
+        assert_composition(run(hip_ctx, sw, n_chunk=3, mean_pose=request(src, N)), res, want, name)
+
+
+def twenty():
+    name, sw, src, lines = forms(20)[0]
+    return sw, src, lines
+
+
+def test_blocks_cut_through_a_workgroup_of_the_solve(hip_ctx):
+    """20 designs in three blocks: three lines make groups of four lanes, 16 designs a workgroup of k_mean_pose, so the
+    blocks' launches group the designs differently from the stand-alone launch over all twenty."""
+    sw, src, lines = twenty()
+    res, want = host_route(hip_ctx, sw, lines)
+    assert_composition(run(hip_ctx, sw, n_chunk=3, mean_pose=request(src, 20)), res, want, "20 designs, 3 blocks")
+
+
+def test_the_pose_matters(hip_ctx, oracle_ctx):
+    name, sw, src, lines = forms()[2]
+    got = run(hip_ctx, sw, mean_pose=request(src, N))
+    at_ref = run(hip_ctx, sw)
+    # the oracle's generator (CPU) at the solved pose: the wet-strip counts the crossing must have seen, and they are not
+    # the counts at the reference pose
+    t = sw.tables
+    build = lambda pose: oracle_ctx.build_designs(t.member_off, t.members, t.station_off, t.stations, sw.M0, sw.B0, sw.C0, sw.nw, pose=pose,
+                                                  k=sw.k, add_mask=7, cap_off=t.cap_off, caps=t.caps)
+    cnt_pose, cnt_ref = np.diff(build(got["pose"])), np.diff(build(None))
+    print("wet strips at the reference pose %s, at the mean pose %s; pitch %s deg" % (cnt_ref, cnt_pose, np.rad2deg(got["pose"][:, 4]).round(2)))
+    assert np.any(cnt_pose != cnt_ref)
+    assert np.array_equal(np.diff(got["strip_off"]), cnt_pose) and np.array_equal(np.diff(at_ref["strip_off"]), cnt_ref)
+    for d in range(N):
+        assert not same_bits(got["Xi"][d], at_ref["Xi"][d]), d
+
+
+def test_with_the_mooring_rider(hip_ctx):
+    """mean_pose= + mooring= is the pose= crossing fed C0 + C_moor: the lines are evaluated at the device pose."""
+    for name, sw, src, lines in forms():
+        res = stand_alone(hip_ctx, sw, lines)
+        C_base, sw.pose = sw.C0, res.pose
+        try:
+            t_only = run(hip_ctx, sw, mooring=dict(src))                   # the mooring-only request on the pose= crossing
+            sw.C0 = C_base + res.C_moor
+            want = run(hip_ctx, sw)
+        finally:
+            sw.C0, sw.pose = C_base, None
+        for n_chunk in (1, 3):
+            got = run(hip_ctx, sw, n_chunk=n_chunk, mean_pose=request(src, N), mooring=dict(add_stiffness=True, **src))
+            assert_composition(got, res, want, (name, n_chunk))
+            assert same_bits(got["C_moor"], res.C_moor) and same_bits(got["F_moor"], res.F_moor) and same_bits(got["T_mean"], res.T), name
+            assert same_bits(got["T_std"], t_only["T_std"]) and not got["moor_flags"].any(), name
+
+
+def test_ballast_trim_belongs_to_the_reference_pose(hip_ctx):
+    """Descriptor route, mask 7 | TRIM_BALLAST: the trim is taken at the reference pose and kept through the second member
+    pass -- bit for bit the untrimmed crossing of descriptors edited on the host with that density correction."""
+    name, _, src, lines = forms()[2]
+    sw = descriptor_sweep(N, add_mask=7 | G.TRIM_BALLAST)
+    res = stand_alone(hip_ctx, sw, lines)
+    assert not res.flags.any()
+    drho = hip_ctx.fetch_statics()["props"][:, G.SP_DRHO].copy()
+    assert np.all(drho != 0.0)
+    t = sw.tables
+    edited = descriptor_sweep(N)
+    st = edited.tables.stations = np.array(t.stations)
+    of_design = np.repeat(np.arange(N), np.diff(np.asarray(t.station_off)[np.asarray(t.member_off)]))
+    st[st[:, G.GS_RHOFILL] == 0.0, G.GS_LFILL] = 0.0
+    fill = st[:, G.GS_LFILL] > 0.0
+    st[fill, G.GS_RHOFILL] += drho[of_design[fill]]
+    edited.pose = res.pose
+    want = run(hip_ctx, edited)
+    got = run(hip_ctx, sw, n_chunk=3, want_props=True, mean_pose=request(src, N))
+    assert_composition(got, res, want, "ballast trim")
+    assert same_bits(got["props"][:, G.SP_DRHO], drho)
+
+
+def test_flagged_design_comes_back_nan_and_alone(hip_ctx):
+    for name, sw, src, lines in forms()[1:]:
+        clean = run(hip_ctx, sw, mean_pose=request(src, N))
+        assert not clean["pose_flags"].any() and np.all(np.isfinite(clean["std"]))
+        bad = lines.copy()
+        bad[2, 1, 6] = 5000.0                                              # fully slack
+        got = run(hip_ctx, sw, n_chunk=3, mean_pose=request(dict(lines=bad), N))
+        assert list(got["pose_flags"]) == [0, 0, mr.FLAG_SLACK, 0, 0, 0]
+        assert np.all(got["flags"][2] & 2)
+        for k in ("std", "Xi", "fn", "pose", "F_res"):
+            assert not np.any(np.isfinite(got[k][2].view(float))), (name, k)
+        keep = np.arange(N) != 2
+        for k in BITS + ("pose", "pose_iterations", "F_res"):
+            assert same_bits(got[k][keep], clean[k][keep]), (name, k)
+        assert same_bits(np.diff(got["strip_off"])[keep], np.diff(clean["strip_off"])[keep])
+        capped = run(hip_ctx, sw, mean_pose=request(dict(lines=bad), N, max_iter=1))      # one step is never within 1e-9 m
+        assert list(capped["pose_flags"]) == [statics.FLAG_POSE_CAP] * 2 + [mr.FLAG_SLACK] + [statics.FLAG_POSE_CAP] * 3
+        assert list(capped["pose_iterations"]) == [1, 1, 0, 1, 1, 1] and np.all(capped["flags"] & 2)
+        for k in ("std", "Xi", "fn", "pose", "F_res"):
+            assert not np.any(np.isfinite(capped[k].view(float))), (name, k)
+
+
+def test_a_design_depends_on_itself_only(hip_ctx):
+    sw, src, lines = twenty()
+    sw.mean_pose = request(src, 20)
+    batch = run(hip_ctx, sw, n_chunk=3)
+    for d in range(20):
+        alone = run(hip_ctx, sw.take(d, d + 1))
+        for k in BITS + ("pose", "pose_iterations", "F_res", "pose_flags"):
+            assert same_bits(alone[k][0], batch[k][d]), (d, k)
+        assert np.diff(alone["strip_off"])[0] == np.diff(batch["strip_off"])[d]
+
+
+def test_errors(hip_ctx):
+    name, sw, src, lines = forms()[1]
+    dname, dsw, dsrc, _ = forms()[2]
+    L, fl = hip_ctx.rlib.lib, np.zeros(N, dtype=np.int32)
+    call = lambda slot, nL, ln, nX=0, flags=fl: L.raftx_sweep_mean_pose(hip_ctx._h, slot, nL, None if ln is None else ln.ctypes.data, nX,
+                                                                        None, None, None, None, 0, None, None, None,
+                                                                        None if flags is None else flags.ctypes.data)
+    err = lambda: L.raftx_last_error(hip_ctx._h)
+    assert call(0, 3, lines) != 0 and b"nothing prepared" in err()          # an idle slot
+    h = sw.prepare_crossing(hip_ctx, 0)
+    assert call(0, 3, lines, flags=None) != 0 and b"flags is required" in err()
+    for nX in (2, N + 1, -1):
+        assert call(0, 3, lines, nX=nX) != 0 and b"nX=" in err()
+    fr = lines.copy()
+    fr[1, 0, 9] = 0.5
+    with pytest.raises(RaftxError, match="CB = 0.5"):
+        hip_ctx.sweep_mean_pose(h, lines=fr)
+    with pytest.raises(RaftxError, match="tolerances"):
+        hip_ctx.sweep_mean_pose(h, lines=lines, tol=(-1.0, 1e-9))
+    hip_ctx.sweep_mean_pose(h, **request(dict(lines=lines), N))
+    with pytest.raises(RaftxError, match="already has a mean-pose request"):
+        hip_ctx.sweep_mean_pose(h, lines=lines)
+    sw.launch_crossing(hip_ctx, h)
+    with pytest.raises(RaftxError, match="has been launched"):
+        hip_ctx.sweep_mean_pose(h, lines=lines)
+    out = sw.wait_crossing(hip_ctx, h)
+    assert not out["pose_flags"].any() and np.all(np.isfinite(out["std"]))
+    # a mooring request already on the slot was evaluated at the caller's pose
+    h = sw.prepare_crossing(hip_ctx, 0, mooring=dict(lines=lines))
+    with pytest.raises(RaftxError, match="already has a mooring request"):
+        hip_ctx.sweep_mean_pose(h, lines=lines)
+    hip_ctx.sweep_cancel(h)
+    # cancel drops the request
+    h = sw.prepare_crossing(hip_ctx, 0, mean_pose=request(dict(lines=lines), N))
+    hip_ctx.sweep_cancel(h)
+    plain = sw.run_crossing(hip_ctx)
+    assert "pose" not in plain and np.all(np.isfinite(plain["std"]))
+    # lines == NULL needs a program, and a slot of variants
+    hip_ctx.mooring_program(None)
+    h = sw.prepare_crossing(hip_ctx, 0)
+    with pytest.raises(RaftxError, match="no program"):
+        hip_ctx.sweep_mean_pose(h, lines=None)
+    assert call(0, 3, None) != 0 and b"no mooring program" in err()
+    hip_ctx.sweep_cancel(h)
+    h = dsw.prepare_crossing(hip_ctx, 1)
+    assert call(1, 3, None) != 0 and b"raftx_sweep_prepare_variants" in err()
+    hip_ctx.sweep_cancel(h)
+    with pytest.raises(ValueError, match="mean_pose=dict"):
+        sw.prepare_crossing(hip_ctx, 0, mean_pose=dict(lines=lines, program=program()))
+    with pytest.raises(ValueError, match="mean_pose=dict"):
+        sw.prepare_crossing(hip_ctx, 0, mean_pose=dict(lines=lines, thrust=1.0))
+
+
+def test_plain_crossing_is_unchanged_after_the_request(hip_ctx):
+    """A crossing without the request enqueues what it did before: the parent commit's bits, also on a slot the request used."""
+    name, sw, src, lines = forms()[0]
+    run(hip_ctx, sw, n_chunk=3, mean_pose=request(src, N))
+    assert plain_hashes(hip_ctx) == PARENT_SHA
+
+
+def test_fused_generation_switch_keeps_the_plain_generation(hip_ctx, monkeypatch):
+    """RAFTX_FUSED_GEN=1 (read per call) leaves a crossing's tables to the fused kernel; one with the request keeps
+    k_geom_design -- its second member pass is the plain one -- and its bits."""
+    name, sw, src, lines = forms()[0]
+    go = lambda **kw: sw.wait_crossing(hip_ctx, sw.submit_crossing(hip_ctx, 0, n_chunk=1, **kw))
+    want = go(mean_pose=request(src, N))
+    monkeypatch.setenv("RAFTX_FUSED_GEN", "1")
+    assert go()["generation_fused_blocks"] == (1, 1)                     # the switch is on for a plain crossing
+    got = go(mean_pose=request(src, N))
+    assert got["generation_fused_blocks"] == (0, 1)
+    for k in ("std", "niter", "flags", "strip_off", "pose", "pose_iterations", "F_res", "pose_flags"):
+        assert same_bits(got[k], want[k]), k
