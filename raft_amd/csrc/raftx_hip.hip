@@ -687,6 +687,7 @@ __global__ void __launch_bounds__(256) k_response_stats(int nDof, int nResp, int
 // ------------------------------------------------------------------ host side
 #define RAFTX_NSLOT RAFTX_SWEEP_SLOTS   // crossings in flight per context: one downloading its responses, one solving, one generated / queued, one uploading
 #include "raftx_owned.h"
+#include "raftx_landing.h"
 
 // A raftx_build_designs in flight: phase 1 (descriptor H2D, member pass, scans, totals to the host) has been enqueued,
 // phase 2 (strip tables, statics) follows once the totals are known.  The sweep crossing keeps several of them in flight.
@@ -816,6 +817,13 @@ struct BuildSource {
     const double *k_dev = nullptr;                       // wave numbers already resident (the crossing's sea-state tables), or null: k is uploaded
     VariantSrc var{nullptr, nullptr};                    // prog == nullptr: the caller's descriptor arrays
 };
+// rows [lo, lo + n) of `per` doubles each out of a landing region; row d of such an array made NaN (an array not asked for: nothing)
+static void rows_out(double *out, const double *src, size_t lo, size_t n, size_t per) {
+    if (out && n * per) memcpy(out + lo * per, src, n * per * sizeof(double));
+}
+static void blank_row(double *a, size_t d, size_t per) {
+    if (a) std::fill(a + d * per, a + (d + 1) * per, std::numeric_limits<double>::quiet_NaN());
+}
 // One sweep crossing in flight: everything raftx_sweep_wait needs to finish it.
 struct SweepSlot {
     bool busy = false;                   // launched (phase 2 enqueued), not yet waited for
@@ -845,14 +853,30 @@ struct SweepSlot {
     size_t nSlabEv = 0;
     bool slab = false;                   // this crossing's fused launches were cut into slabs (SlabPlan)
     std::vector<double> tlb;             // RAFTX_SWEEP_DEBUG: host time per block of raftx_sweep_launch (upload enqueued | totals seen | enqueued)
-    struct {                             // raftx_sweep_modal: eigen analysis of the crossing's designs
+    // The requests of a crossing.  Each knows the caller's arrays it fills: collect() copies a block's part (designs lo .. lo + n)
+    // out of the block's landing area `land`, blank() makes what the request handed out for design d NaN (collect_pose).
+    struct ModalReq {                    // raftx_sweep_modal: eigen analysis of the crossing's designs
         bool on = false;
         const double *dM = nullptr, *dC = nullptr;   // device copies [nDesign,36] (in S.allocs), or null
         double *fn = nullptr, *modes = nullptr, *props = nullptr;   // the caller's outputs, filled by raftx_sweep_wait
         int32_t *flags = nullptr;
         Event evUp;                      // the copies of dM / dC have landed (sCopy)
+        void collect(const double *land, size_t lo, size_t n, size_t) {
+            if (!on) return;
+            const landing::Modal L = landing::modal(n, RAFTX_SP_N);
+            rows_out(fn, land + L.fn, lo, n, 6);
+            rows_out(modes, land + L.modes, lo, n, 36);
+            rows_out(props, land + L.props, lo, n, RAFTX_SP_N);
+            memcpy(flags + lo, L.flags.in(land), n * sizeof(int32_t));
+        }
+        void blank(size_t d, size_t) {
+            if (!on) return;
+            blank_row(fn, d, 6);
+            blank_row(modes, d, 36);
+            blank_row(props, d, RAFTX_SP_N);
+        }
     } modal;
-    struct {                             // raftx_sweep_current: mean current loads of the crossing's designs
+    struct CurrentReq {                  // raftx_sweep_current: mean current loads of the crossing's designs
         bool on = false;
         int nCur = 0;
         double shearExp = 0;
@@ -860,25 +884,38 @@ struct SweepSlot {
         const double *par = nullptr, *Zref = nullptr;   // device copies (in S.allocs); Zref null: 0
         double *D = nullptr;             // the caller's output [nDesign,nCur,6], filled by raftx_sweep_wait
         Event evUp;                      // the copies have landed (sCopy)
+        void collect(const double *land, size_t lo, size_t n, size_t) { if (on) rows_out(D, land, lo, n, (size_t)nCur * 6); }
+        void blank(size_t d, size_t) { if (on) blank_row(D, d, (size_t)nCur * 6); }
     } current;
-    struct {                             // raftx_sweep_channels: output channels of the crossing's (design, case) pairs
+    struct ChannelsReq {                 // raftx_sweep_channels: output channels of the crossing's (design, case) pairs
         bool on = false;
         int nChan = 0, nL = 0, nG = 0;   // rows of L: 1 (shared) or nDesign; of Gw: 0 (none), 1 or nDesign
         const double *L = nullptr;       // device copies (in S.allocs) [nL,nChan,3,6]
         const cplx *Gw = nullptr;        // [nG,nChan,6,nw], or null
         double *out = nullptr;           // the caller's output [nDesign,nCase,nChan], filled by raftx_sweep_wait
         Event evUp;                      // the copies have landed (sCopy)
+        void collect(const double *land, size_t lo, size_t n, size_t nCase) { if (on) rows_out(out, land, lo, n, nCase * nChan); }
+        void blank(size_t d, size_t nCase) { if (on) blank_row(out, d, nCase * nChan); }
     } channels;
-    struct {                             // raftx_sweep_mooring: the mooring system of the crossing's designs
+    struct MooringReq {                  // raftx_sweep_mooring: the mooring system of the crossing's designs
         bool on = false, add = false;
         int nLine = 0;
         const double *C = nullptr, *Lr = nullptr;   // device (in S.allocs): C_moor [nDesign,36]; J as channel rows [nDesign,2 nLine,3,6]
-        Pinned<double> pin;              // landing area: C | F | T | flags of the whole crossing
+        Pinned<double> pin;              // landing area of the whole crossing (landing::mooring)
         double *C_out = nullptr, *F_out = nullptr, *T_out = nullptr, *Tstd_out = nullptr;   // the caller's, filled by raftx_sweep_wait
         int32_t *flags_out = nullptr;
         Event evUp;                      // the kernels have run and the landing area is filled (sCopy)
+        // (a block's part is T_std; the rest is the crossing's: collect_mooring)
+        void collect(const double *land, size_t lo, size_t n, size_t nCase) { if (on) rows_out(Tstd_out, land, lo, n, nCase * 2 * nLine); }
+        void blank(size_t d, size_t nCase) {
+            if (!on) return;
+            blank_row(C_out, d, 36);
+            blank_row(F_out, d, 6);
+            blank_row(T_out, d, 2 * (size_t)nLine);
+            blank_row(Tstd_out, d, nCase * 2 * nLine);
+        }
     } mooring;
-    struct {                             // raftx_sweep_mean_pose: the crossing runs at every design's mean equilibrium pose
+    struct PoseReq {                     // raftx_sweep_mean_pose: the crossing runs at every design's mean equilibrium pose
         bool on = false;
         int nLine = 0, nX = 0, maxIter = 0;
         double tolT = 0, tolR = 0;
@@ -887,12 +924,11 @@ struct SweepSlot {
         const double *lines = nullptr, *Cx = nullptr, *Fx = nullptr, *Fenv = nullptr;
         double *K = nullptr, *F0 = nullptr, *lw = nullptr, *solved = nullptr, *placed = nullptr, *Fres = nullptr;
         int *iter = nullptr, *fl = nullptr;
-        Pinned<double> pin;              // landing area: pose | F_res [nDesign,6] each | iterations | flags [nDesign] int32 each
+        Pinned<double> pin;              // landing area of the whole crossing (landing::pose)
         double *pose_out = nullptr, *Fres_out = nullptr;                     // the caller's, filled by raftx_sweep_wait
         int32_t *iter_out = nullptr, *flags_out = nullptr;
         Event evUp;                      // the inputs have landed and the program's records have been written (sCopy)
-        int32_t *hFlags(size_t n) const { return reinterpret_cast<int32_t *>(pin.p + n * 12) + n; }
-    } pose;
+    } pose;                              // (its outputs are the whole crossing's and say why a design is flagged: collect_pose, never blanked)
     // The one place that switches the requests of a crossing off: a request left on would fire at the next raftx_sweep_wait
     // and copy into a caller's array that may be gone.
     void clear_requests() { modal.on = current.on = channels.on = mooring.on = pose.on = false; }
@@ -3330,8 +3366,9 @@ static int block_pose(raftx_ctx *c, SweepSlot &S, size_t b) {
         memset(&L, 0, sizeof(L));
         L.n = n; L.solved = M.pose; L.x_ref = A.pose; L.Fres = M.Fres; L.iterations = M.iterations; L.flags = M.flags;
         L.placed = P.placed + lo * 6;
-        L.hPose = P.pin.p + lo * 6; L.hFres = P.pin.p + nAll * 6 + lo * 6;
-        L.hIter = reinterpret_cast<int *>(P.pin.p + nAll * 12) + lo; L.hFlags = P.hFlags(nAll) + lo;
+        const landing::Pose land = landing::pose(nAll);
+        L.hPose = P.pin.p + land.pose + lo * 6; L.hFres = P.pin.p + land.Fres + lo * 6;
+        L.hIter = land.iterations.in(P.pin.p) + lo; L.hFlags = land.flags.in(P.pin.p) + lo;
         hipLaunchKernelGGL(k_pose_place, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, sPrep, L);
         HIPCHK(sub, hipGetLastError());
         A.pose = L.placed;
@@ -3872,32 +3909,34 @@ extern "C" int raftx_qtf_slender_resident(raftx_ctx *c, int nCase, int nw2, cons
     return 0;
 }
 
+static void launch_modal(hipStream_t st, int n, const double *M, const double *C, const double *dM, const double *dC,
+                         const double *props_in, double *props_out, double *fn, double *modes, int32_t *flags) {
+    ModalArgs A{n, M, C, dM, dC, props_in, props_out, fn, modes, flags};
+    hipLaunchKernelGGL(k_modal, dim3((unsigned)(((size_t)n + MODAL_BS - 1) / MODAL_BS)), dim3(MODAL_BS), 0, st, A);
+}
 // The eigen analysis of one block of a crossing (raftx_sweep_modal) on stream st, which is behind whatever wrote the
 // block's summed M0 / C0 (k_geom_addup, k_geom_design with the add-up folded in, or the generating fused kernel): one
-// system per lane, the results written straight into the block's page-locked landing area
-// [fn n*6 | modes n*36 | props n*SP_N | flags n int32], which raftx_sweep_wait copies out.
+// system per lane, the results written straight into the block's page-locked landing area (landing::modal), which
+// raftx_sweep_wait copies out.
 static hipError_t modal_block(raftx_ctx *sub, SweepSlot &S, int lo, int n, hipStream_t st) {
-    const size_t need = (size_t)n * (42 + RAFTX_SP_N) + ((size_t)n + 1) / 2;
-    hipError_t e = sub->pinModal.reserve(need);
+    const landing::Modal land = landing::modal((size_t)n, RAFTX_SP_N);
+    hipError_t e = sub->pinModal.reserve(land.need);
     if (e != hipSuccess || n == 0) return e;
     if (S.modal.evUp) e = hipStreamWaitEvent(st, S.modal.evUp, 0);
     if (e != hipSuccess) return e;
     double *pm = sub->pinModal.p;
-    ModalArgs A;
-    A.n = n;
-    A.M = sub->T.M0;
-    A.C = sub->T.C0;
-    A.dM = S.modal.dM ? S.modal.dM + (size_t)lo * 36 : nullptr;
-    A.dC = S.modal.dC ? S.modal.dC + (size_t)lo * 36 : nullptr;
-    A.props_in = S.modal.props ? sub->g_props : nullptr;
-    A.props_out = pm + (size_t)n * 42;
-    A.fn = pm;
-    A.modes = pm + (size_t)n * 6;
-    A.flags = reinterpret_cast<int32_t *>(pm + (size_t)n * (42 + RAFTX_SP_N));
-    hipLaunchKernelGGL(k_modal, dim3((unsigned)(((size_t)n + MODAL_BS - 1) / MODAL_BS)), dim3(MODAL_BS), 0, st, A);
+    launch_modal(st, n, sub->T.M0, sub->T.C0, S.modal.dM ? S.modal.dM + (size_t)lo * 36 : nullptr,
+                 S.modal.dC ? S.modal.dC + (size_t)lo * 36 : nullptr, S.modal.props ? sub->g_props : nullptr, pm + land.props,
+                 pm + land.fn, pm + land.modes, land.flags.in(pm));
     return hipGetLastError();
 }
 
+// (the launch raftx_current_loads shares: the n designs of the tables T, par = speed | cos | sin [3,nCur])
+static void launch_current(hipStream_t st, const DevTables &T, int n, int nCur, const double *par, const double *Zref, double depth,
+                           double shearExp, double *D) {
+    CurrentArgs A{n, nCur, T.off, T.ds, T.dsi, par, Zref, depth, shearExp, D};
+    hipLaunchKernelGGL(k_current_loads, dim3(current_grid(n, nCur)), dim3(64 * CUR_WAVES), 0, st, A);
+}
 // The current loads of one block of a crossing (raftx_sweep_current) on stream st, behind the block's statistics kernel:
 // the block's strip tables are resident until the block is retired.  One wave per (design, tile of currents), the sums
 // written straight into the block's page-locked landing area [n,nCur,6], which raftx_sweep_wait copies out.
@@ -3907,14 +3946,8 @@ static hipError_t current_block(raftx_ctx *sub, SweepSlot &S, int lo, int n, dou
     if (sub->T.nDesign != n || !sub->T.off || !sub->T.ds || !sub->T.dsi) return hipErrorInvalidValue;   // (the block kept no tables: internal error)
     e = hipStreamWaitEvent(st, S.current.evUp, 0);
     if (e != hipSuccess) return e;
-    CurrentArgs A;
-    A.nDesign = n; A.nCur = S.current.nCur;
-    A.off = sub->T.off; A.ds = sub->T.ds; A.dsi = sub->T.dsi;
-    A.par = S.current.par;
-    A.Zref = S.current.Zref ? S.current.Zref + lo : nullptr;
-    A.depth = depth; A.shearExp = S.current.shearExp;
-    A.D = sub->pinCur.p;
-    hipLaunchKernelGGL(k_current_loads, dim3(current_grid(n, A.nCur)), dim3(64 * CUR_WAVES), 0, st, A);
+    launch_current(st, sub->T, n, S.current.nCur, S.current.par, S.current.Zref ? S.current.Zref + lo : nullptr, depth,
+                   S.current.shearExp, sub->pinCur.p);
     return hipGetLastError();
 }
 
@@ -3990,9 +4023,10 @@ static int enqueue_stats(raftx_ctx *c, SweepSlot &S, size_t b, hipStream_t sDown
     const size_t npair = (size_t)(S.bnd[b + 1] - lo) * nCase;
     hipError_t e = hipEventRecord(sub->evS0, c->stream);
     if (npair) {
+        const landing::Stats land = landing::stats(npair);              // (niter and flags: one run of 2 npair ints, from niter on)
         hipLaunchKernelGGL(k_motion_stats, dim3((unsigned)npair), dim3(nw > 128 ? 256 : (nw > 64 ? 128 : 64)), 0, c->stream,
-                           (int)npair, nHead, nw, 1.0 / S.dw, sub->rXi, sub->pinRes.p, (double *)nullptr, (const int *)sub->rNi,
-                           (const int *)sub->rFl, reinterpret_cast<int *>(sub->pinRes.p + npair * 6));
+                           (int)npair, nHead, nw, 1.0 / S.dw, sub->rXi, sub->pinRes.p + land.sd, (double *)nullptr, (const int *)sub->rNi,
+                           (const int *)sub->rFl, land.niter.in(sub->pinRes.p));
     }
     if (e == hipSuccess) e = hipEventRecord(sub->evS1, c->stream);
     if (e == hipSuccess && S.modal.on) e = modal_block(sub, S, lo, S.bnd[b + 1] - lo, c->stream);
@@ -4107,8 +4141,7 @@ static int launch_block(raftx_ctx *c, SweepSlot &S, int slot, size_t b, LaunchMo
         if (S.slab) slab_plan_block(M.plan, S, b, M.slab_pairs, M.sDown);
         rc = solve_enqueue(sub, S.nIter, S.tol, S.XiStart, nullptr, 0, S.slab ? &M.plan : nullptr);
     }
-    const size_t need = (size_t)(S.bnd[b + 1] - S.bnd[b]) * S.nCase * 7 + 2;   // std [npair,6] | niter, flags [npair] int32 each
-    if (!rc && sub->pinRes.reserve(need) != hipSuccess) rc = -2;
+    if (!rc && sub->pinRes.reserve(landing::stats((size_t)(S.bnd[b + 1] - S.bnd[b]) * S.nCase).need) != hipSuccess) rc = -2;
     if (!rc && !S.slab) rc = enqueue_stats(c, S, b, M.sDown);         // (slab mode: stats_after_join)
     S.tlb.push_back(S.since());
     if (rc) snprintf(c->err, sizeof(c->err), "sweep_stats (block %zu): %s", b, sub->err);
@@ -4241,24 +4274,15 @@ static void collect_block(SweepSlot &S, size_t b, double *t) {
         for (int i = 0; i < n; i++) S.stripOffsets[lo + i + 1] = S.stripOffsets[lo] + sub->pin.p[PIN_OFF + i + 1];
     if (sub->job.active) t[1] += elapsed_ms(sub->evG2, sub->evG3) + elapsed_ms(sub->evG0, sub->evG1);   // (as build_retire)
     build_abandon(sub);
+    const landing::Stats land = landing::stats(npair);
     const double *res = sub->pinRes.p;
-    memcpy(S.sd + p0 * 6, res, npair * 6 * sizeof(double));
-    memcpy(S.niter + p0, res + npair * 6, npair * sizeof(int));
-    memcpy(S.flags + p0, reinterpret_cast<const int *>(res + npair * 6) + npair, npair * sizeof(int));
-    if (S.modal.on) {
-        const double *pm = sub->pinModal.p;
-        memcpy(S.modal.fn + (size_t)lo * 6, pm, (size_t)n * 6 * sizeof(double));
-        memcpy(S.modal.modes + (size_t)lo * 36, pm + (size_t)n * 6, (size_t)n * 36 * sizeof(double));
-        if (S.modal.props)
-            memcpy(S.modal.props + (size_t)lo * RAFTX_SP_N, pm + (size_t)n * 42, (size_t)n * RAFTX_SP_N * sizeof(double));
-        memcpy(S.modal.flags + lo, pm + (size_t)n * (42 + RAFTX_SP_N), (size_t)n * sizeof(int32_t));
-    }
-    if (S.current.on && n)
-        memcpy(S.current.D + (size_t)lo * S.current.nCur * 6, sub->pinCur.p, (size_t)n * S.current.nCur * 6 * sizeof(double));
-    if (S.channels.on && npair)
-        memcpy(S.channels.out + p0 * S.channels.nChan, sub->pinChan.p, npair * S.channels.nChan * sizeof(double));
-    if (S.mooring.on && S.mooring.Tstd_out && npair)
-        memcpy(S.mooring.Tstd_out + p0 * 2 * S.mooring.nLine, sub->pinMoorT.p, npair * 2 * S.mooring.nLine * sizeof(double));
+    memcpy(S.sd + p0 * 6, res + land.sd, npair * 6 * sizeof(double));
+    memcpy(S.niter + p0, land.niter.in(res), npair * sizeof(int));
+    memcpy(S.flags + p0, land.flags.in(res), npair * sizeof(int));
+    S.modal.collect(sub->pinModal.p, lo, n, S.nCase);
+    S.current.collect(sub->pinCur.p, lo, n, S.nCase);
+    S.channels.collect(sub->pinChan.p, lo, n, S.nCase);
+    S.mooring.collect(sub->pinMoorT.p, lo, n, S.nCase);                 // (the pose request has nothing per block: collect_pose)
 }
 // the crossing's mooring results out of their landing area (the copies were waited for with the crossing: sCopy is ahead of
 // every block through evUp, or waited for here)
@@ -4267,11 +4291,12 @@ static hipError_t collect_mooring(SweepSlot &S) {
     const hipError_t e = hipEventSynchronize(S.mooring.evUp);
     if (e != hipSuccess) return e;
     const size_t n = S.bnd.empty() ? 0 : (size_t)S.bnd.back(), nT = 2 * (size_t)S.mooring.nLine;
+    const landing::Mooring land = landing::mooring(n, (size_t)S.mooring.nLine);
     const double *p = S.mooring.pin.p;
-    if (S.mooring.C_out) memcpy(S.mooring.C_out, p, n * 36 * sizeof(double));
-    if (S.mooring.F_out) memcpy(S.mooring.F_out, p + n * 36, n * 6 * sizeof(double));
-    if (S.mooring.T_out) memcpy(S.mooring.T_out, p + n * 42, n * nT * sizeof(double));
-    memcpy(S.mooring.flags_out, p + n * (42 + nT), n * sizeof(int32_t));
+    rows_out(S.mooring.C_out, p + land.C, 0, n, 36);
+    rows_out(S.mooring.F_out, p + land.F, 0, n, 6);
+    rows_out(S.mooring.T_out, p + land.T, 0, n, nT);
+    memcpy(S.mooring.flags_out, land.flags.in(p), n * sizeof(int32_t));
     return hipSuccess;
 }
 // The solve's outputs out of their landing area (k_pose_place wrote them ahead of the block's second member pass, which the
@@ -4281,35 +4306,22 @@ static hipError_t collect_mooring(SweepSlot &S) {
 static void collect_pose(SweepSlot &S) {
     if (!S.pose.on) return;
     const size_t n = S.bnd.empty() ? 0 : (size_t)S.bnd.back(), nC = (size_t)S.nCase;
+    const landing::Pose land = landing::pose(n);
     const double *p = S.pose.pin.p;
-    const int32_t *fl = S.pose.hFlags(n);
-    if (S.pose.pose_out) memcpy(S.pose.pose_out, p, n * 6 * sizeof(double));
-    if (S.pose.Fres_out) memcpy(S.pose.Fres_out, p + n * 6, n * 6 * sizeof(double));
-    if (S.pose.iter_out) memcpy(S.pose.iter_out, p + n * 12, n * sizeof(int32_t));
+    const int32_t *fl = land.flags.in(p);
+    rows_out(S.pose.pose_out, p + land.pose, 0, n, 6);
+    rows_out(S.pose.Fres_out, p + land.Fres, 0, n, 6);
+    if (S.pose.iter_out) memcpy(S.pose.iter_out, land.iterations.in(p), n * sizeof(int32_t));
     memcpy(S.pose.flags_out, fl, n * sizeof(int32_t));
-    const double nan = std::numeric_limits<double>::quiet_NaN();
-    auto blank = [&](double *a, size_t d, size_t per) {
-        if (a) std::fill(a + d * per, a + (d + 1) * per, nan);
-    };
     for (size_t d = 0; d < n; d++) {
         if (!fl[d]) continue;
-        blank(S.sd, d, nC * 6);
+        blank_row(S.sd, d, nC * 6);
         for (size_t i = 0; i < nC; i++) S.flags[d * nC + i] |= RAFTX_FLAG_NAN;
-        if (S.Xi) blank(reinterpret_cast<double *>(S.Xi), d, nC * S.nHead * 6 * S.nw * 2);
-        if (S.modal.on) {
-            blank(S.modal.fn, d, 6);
-            blank(S.modal.modes, d, 36);
-            blank(S.modal.props, d, RAFTX_SP_N);
-        }
-        if (S.current.on) blank(S.current.D, d, (size_t)S.current.nCur * 6);
-        if (S.channels.on) blank(S.channels.out, d, nC * S.channels.nChan);
-        if (S.mooring.on) {
-            const size_t nT = 2 * (size_t)S.mooring.nLine;
-            blank(S.mooring.C_out, d, 36);
-            blank(S.mooring.F_out, d, 6);
-            blank(S.mooring.T_out, d, nT);
-            blank(S.mooring.Tstd_out, d, nC * nT);
-        }
+        blank_row(reinterpret_cast<double *>(S.Xi), d, nC * S.nHead * 6 * S.nw * 2);
+        S.modal.blank(d, nC);
+        S.current.blank(d, nC);
+        S.channels.blank(d, nC);
+        S.mooring.blank(d, nC);
     }
 }
 // RAFTX_SWEEP_DEBUG: the host's timeline of the crossing on stderr
@@ -4382,12 +4394,8 @@ static int modal_launch(raftx_ctx *c, int n, const double *M, const double *C, c
     int32_t *dfl = sc.alloc<int32_t>((size_t)n);
     double *dpr = props_in ? sc.alloc<double>((size_t)n * RAFTX_SP_N) : nullptr;
     if (!dfn || !dmo || !dfl || (props_in && !dpr)) FAIL(c, "modal: device allocation failed");
-    ModalArgs A;
-    A.n = n; A.M = M; A.C = C; A.dM = dM; A.dC = dC;
-    A.props_in = props_in; A.props_out = dpr;
-    A.fn = dfn; A.modes = dmo; A.flags = dfl;
     HIPCHK(c, hipEventRecord(c->ev0, c->stream));
-    hipLaunchKernelGGL(k_modal, dim3((unsigned)(((size_t)n + MODAL_BS - 1) / MODAL_BS)), dim3(MODAL_BS), 0, c->stream, A);
+    launch_modal(c->stream, n, M, C, dM, dC, props_in, dpr, dfn, dmo, dfl);
     if (finish_timed(c)) return -2;
     D2H(c, fn, dfn, (size_t)n * 6 * sizeof(double));
     D2H(c, modes, dmo, (size_t)n * 36 * sizeof(double));
@@ -4489,15 +4497,8 @@ extern "C" int raftx_current_loads(raftx_ctx *c, int nCur, const double *speed, 
     double *dpar = sc.alloc<double>(host.size()), *dD = sc.alloc<double>((size_t)n * nCur * 6);
     if (!dpar || !dD) FAIL(c, "current_loads: device allocation failed");
     H2D(c, dpar, host.data(), host.size() * sizeof(double));
-    CurrentArgs A;
-    A.nDesign = n; A.nCur = nCur;
-    A.off = c->T.off; A.ds = c->T.ds; A.dsi = c->T.dsi;
-    A.par = dpar;
-    A.Zref = Zref ? dpar + (size_t)3 * nCur : nullptr;
-    A.depth = depth; A.shearExp = shearExp;
-    A.D = dD;
     HIPCHK(c, hipEventRecord(c->ev0, c->stream));
-    hipLaunchKernelGGL(k_current_loads, dim3(current_grid(n, nCur)), dim3(64 * CUR_WAVES), 0, c->stream, A);
+    launch_current(c->stream, c->T, n, nCur, dpar, Zref ? dpar + (size_t)3 * nCur : nullptr, depth, shearExp, dD);
     if (finish_timed(c)) return -2;
     D2H(c, D, dD, (size_t)n * nCur * 6 * sizeof(double));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -4529,27 +4530,79 @@ extern "C" int raftx_sweep_current(raftx_ctx *c, int slot, int nCur, const doubl
 }
 
 // ---- quasi-static mooring lines (include/raftx_mooring.h, raftx_mooring.h)
+// The line source of an entry point `who`: what valid records are, which calls may leave them to the mooring program, and
+// how either kind reaches the device.  (raftx_mooring_program checks its one unit's records itself, in its own wording.)
+static int check_lines(raftx_ctx *c, const char *who, size_t nDesign, int nLine, const double *lines) {
+    for (size_t i = 0; i < nDesign * (size_t)nLine; i++) {
+        const double cb = lines[i * RAFTX_ML_N + 9];
+        if (std::isfinite(cb) && cb != 0.0)
+            FAIL(c, "%s: line %zu of design %zu has seabed friction CB = %g: friction is not covered (CB must be 0)", who, i % nLine,
+                 i / nLine, cb);
+    }
+    return 0;
+}
+static int check_depth(raftx_ctx *c, const char *who, double depth) {
+    if (!std::isfinite(depth) || !(depth > 0.0)) FAIL(c, "%s: the depth must be positive and finite (got %g)", who, depth);
+    return 0;
+}
+// lines == NULL: the records are those of the mooring program, evaluated at nP_expected parameters per design
+static int check_line_program(raftx_ctx *c, const char *who, int nLine, int nP_expected, bool slot_has_variants) {
+    if (!slot_has_variants) FAIL(c, "%s: lines == NULL needs a slot prepared with raftx_sweep_prepare_variants", who);
+    if (!c->mprog.nLine) FAIL(c, "%s: no mooring program (raftx_mooring_program first)", who);
+    if (c->mprog.nP != nP_expected) FAIL(c, "%s: the mooring program has %d parameters, the variant program %d", who, c->mprog.nP, nP_expected);
+    if (nLine != c->mprog.nLine) FAIL(c, "%s: nLine=%d is not the %d lines of the mooring program", who, nLine, c->mprog.nLine);
+    return 0;
+}
+// ... of a request `who` on the prepared slot S of n designs, with the depth of the slot's sea states
+static int check_slot_lines(raftx_ctx *c, const char *who, const SweepSlot &S, size_t n, int nLine, const double *lines) {
+    const VariantProg *vp = S.p1.var.prog;
+    if (!lines) {
+        if (int rc = check_line_program(c, who, nLine, vp ? vp->nP : 0, vp != nullptr)) return rc;
+    } else {
+        if (nLine < 1) FAIL(c, "%s: nLine must be positive (got %d)", who, nLine);
+        if (int rc = check_lines(c, who, n, nLine, lines)) return rc;
+    }
+    return check_depth(c, who, c->csets[S.cset].T.depth);
+}
+// The records [n,nLine,RAFTX_ML_N] on the device, in blocks of `bag`, by copies on `st`: the caller's records uploaded, or
+// (records == nullptr) the program's parameters [n,nP] uploaded and a block taken that expand_lines fills.
+struct StagedLines { const double *lines = nullptr, *params = nullptr; double *expanded = nullptr; };
+static int stage_lines(raftx_ctx *c, hipStream_t st, Bag &bag, size_t n, int nLine, const double *records, const double *params,
+                       StagedLines &L) {
+    L = StagedLines{};
+    const size_t nrec = n * (size_t)nLine * RAFTX_ML_N;
+    if (records) return upload_on(c, st, bag, records, nrec, &L.lines);
+    if (upload_on(c, st, bag, params, n * (size_t)c->mprog.nP, &L.params) || pool_alloc(c, bag, nrec, &L.expanded)) return -2;
+    L.lines = L.expanded;
+    return 0;
+}
+// ... and k_moor_expand on `st`, when the source is the program (the caller's records: nothing)
+static int expand_lines(raftx_ctx *c, hipStream_t st, size_t n, int nLine, const StagedLines &L) {
+    if (!L.expanded || !n) return 0;
+    MoorExpandArgs E{(int)n, nLine, c->mprog.nP, c->mprog.base.p, c->mprog.coef.p, c->mprog.edit.p, L.params, L.expanded};
+    hipLaunchKernelGGL(k_moor_expand, dim3(moor_grid((long long)n * nLine)), dim3(MOOR_THREADS), 0, st, E);
+    HIPCHK(c, hipGetLastError());
+    return 0;
+}
+
 extern "C" int raftx_mooring_lines(raftx_ctx *c, int nDesign, int nLine, const double *lines, const double *pose, double depth,
                                    double *C_moor, double *F_moor, double *T, double *J, double *line_out, int32_t *flags) {
     if (!c) return -1;
     if (nLine < 1) FAIL(c, "mooring_lines: nLine must be positive (got %d)", nLine);
     if (nDesign < 0) FAIL(c, "mooring_lines: nDesign must not be negative (got %d)", nDesign);
     if (!lines || !flags) FAIL(c, "mooring_lines: bad arguments (lines and flags are required)");
-    if (!std::isfinite(depth) || !(depth > 0.0)) FAIL(c, "mooring_lines: the depth must be positive and finite (got %g)", depth);
-    const size_t nl = (size_t)nDesign * nLine;
-    for (size_t i = 0; i < nl; i++) {
-        const double cb = lines[i * RAFTX_ML_N + 9];
-        if (std::isfinite(cb) && cb != 0.0)
-            FAIL(c, "mooring_lines: line %zu of design %zu has seabed friction CB = %g: friction is not covered (CB must be 0)",
-                 i % nLine, i / nLine, cb);
-    }
+    if (int rc = check_depth(c, "mooring_lines", depth)) return rc;
+    if (int rc = check_lines(c, "mooring_lines", (size_t)nDesign, nLine, lines)) return rc;
     if (nDesign == 0) return 0;
     HIPCHK(c, hipSetDevice(c->device));
     Scratch sc(c);
+    const size_t nl = (size_t)nDesign * nLine;
+    StagedLines L;
+    if (stage_lines(c, c->stream, sc.bag, (size_t)nDesign, nLine, lines, nullptr, L)) return -2;
     MoorArgs A;
     memset(&A, 0, sizeof(A));
     A.nDesign = nDesign; A.nLine = nLine; A.depth = depth;
-    double *dl = sc.alloc<double>(nl * RAFTX_ML_N), *dp = pose ? sc.alloc<double>((size_t)nDesign * 6) : nullptr;
+    double *dp = pose ? sc.alloc<double>((size_t)nDesign * 6) : nullptr;
     A.lw = sc.alloc<double>(nl * MOOR_LW_N);
     A.line_out = line_out ? sc.alloc<double>(nl * MOOR_LO_N) : nullptr;
     A.C = C_moor ? sc.alloc<double>((size_t)nDesign * 36) : nullptr;
@@ -4557,12 +4610,10 @@ extern "C" int raftx_mooring_lines(raftx_ctx *c, int nDesign, int nLine, const d
     A.T = T ? sc.alloc<double>(nl * 2) : nullptr;
     A.J = J ? sc.alloc<double>(nl * 12) : nullptr;
     A.flags = sc.alloc<int>((size_t)nDesign);
-    if (!dl || (pose && !dp) || !A.lw || (line_out && !A.line_out) || (C_moor && !A.C) || (F_moor && !A.F) || (T && !A.T) || (J && !A.J) ||
-        !A.flags)
+    if ((pose && !dp) || !A.lw || (line_out && !A.line_out) || (C_moor && !A.C) || (F_moor && !A.F) || (T && !A.T) || (J && !A.J) || !A.flags)
         FAIL(c, "mooring_lines: device allocation failed");
-    H2D(c, dl, lines, nl * RAFTX_ML_N * sizeof(double));
     if (pose) H2D(c, dp, pose, (size_t)nDesign * 6 * sizeof(double));
-    A.lines = dl;
+    A.lines = L.lines;
     A.pose = dp;
     HIPCHK(c, hipEventRecord(c->ev0, c->stream));
     hipLaunchKernelGGL(k_moor_line, dim3(moor_grid((long long)nl)), dim3(MOOR_THREADS), 0, c->stream, A);
@@ -4618,15 +4669,12 @@ extern "C" int raftx_mooring_expand(raftx_ctx *c, int nDesign, const double *par
     if (!nDesign) return 0;
     HIPCHK(c, hipSetDevice(c->device));
     Scratch sc(c);
-    const size_t nl = (size_t)nDesign * nLine;
-    double *dp = sc.alloc<double>((size_t)nDesign * std::max(nP, 1)), *dout = sc.alloc<double>(nl * RAFTX_ML_N);
-    if (!dp || !dout) FAIL(c, "mooring_expand: device allocation failed");
-    if (nP) H2D(c, dp, params, (size_t)nDesign * nP * sizeof(double));
-    MoorExpandArgs E{nDesign, nLine, nP, c->mprog.base.p, c->mprog.coef.p, c->mprog.edit.p, dp, dout};
+    StagedLines L;
+    if (stage_lines(c, c->stream, sc.bag, (size_t)nDesign, nLine, nullptr, params, L)) return -2;
     HIPCHK(c, hipEventRecord(c->ev0, c->stream));
-    hipLaunchKernelGGL(k_moor_expand, dim3(moor_grid((long long)nl)), dim3(MOOR_THREADS), 0, c->stream, E);
+    if (int rc = expand_lines(c, c->stream, (size_t)nDesign, nLine, L)) return rc;
     if (finish_timed(c)) return -2;
-    D2H(c, lines_out, dout, nl * RAFTX_ML_N * sizeof(double));
+    D2H(c, lines_out, L.expanded, (size_t)nDesign * nLine * RAFTX_ML_N * sizeof(double));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return 0;
 }
@@ -4656,30 +4704,24 @@ extern "C" int raftx_mean_pose(raftx_ctx *c, int nDesign, int nLine, const doubl
     if (nLine < 1) FAIL(c, "mean_pose: nLine must be positive (got %d)", nLine);
     if (nDesign < 0) FAIL(c, "mean_pose: nDesign must not be negative (got %d)", nDesign);
     if (!K_hs || !F0 || !flags) FAIL(c, "mean_pose: bad arguments (K_hs, F0 and flags are required)");
-    if (!std::isfinite(depth) || !(depth > 0.0)) FAIL(c, "mean_pose: the depth must be positive and finite (got %g)", depth);
+    if (int rc = check_depth(c, "mean_pose", depth)) return rc;
     double tolT, tolR;
     if (int rc = mean_pose_tol(c, "mean_pose", tol, &tolT, &tolR)) return rc;
-    const size_t nl = (size_t)nDesign * nLine;
+    const size_t n = (size_t)nDesign, nl = n * nLine;
     if (!lines) {
+        // (a batch has no slot and no variant program to agree with; its no-program wording is its own)
         if (!c->mprog.nLine) FAIL(c, "mean_pose: lines == NULL without a mooring program (raftx_mooring_program first)");
-        if (nLine != c->mprog.nLine) FAIL(c, "mean_pose: nLine=%d is not the %d lines of the mooring program", nLine, c->mprog.nLine);
+        if (int rc = check_line_program(c, "mean_pose", nLine, c->mprog.nP, true)) return rc;
         if (!params && nDesign && c->mprog.nP) FAIL(c, "mean_pose: lines == NULL needs params [nDesign,%d]", c->mprog.nP);
-    } else {
-        for (size_t i = 0; i < nl; i++) {
-            const double cb = lines[i * RAFTX_ML_N + 9];
-            if (std::isfinite(cb) && cb != 0.0)
-                FAIL(c, "mean_pose: line %zu of design %zu has seabed friction CB = %g: friction is not covered (CB must be 0)",
-                     i % nLine, i / nLine, cb);
-        }
-    }
+    } else if (int rc = check_lines(c, "mean_pose", n, nLine, lines))
+        return rc;
     if (nDesign == 0) return 0;
     HIPCHK(c, hipSetDevice(c->device));
     Scratch sc(c);
-    const size_t n = (size_t)nDesign;
+    StagedLines L;
+    if (stage_lines(c, c->stream, sc.bag, n, nLine, lines, params, L)) return -2;
     MeanPoseArgs A;
     memset(&A, 0, sizeof(A));
-    const int nP = lines ? 0 : c->mprog.nP;
-    double *dl = sc.alloc<double>(nl * RAFTX_ML_N), *dpar = (!lines && nP) ? sc.alloc<double>(n * nP) : nullptr;
     double *dK = sc.alloc<double>(n * 36), *dF0 = sc.alloc<double>(n * 6), *dFe = F_env ? sc.alloc<double>(n * 6) : nullptr;
     double *dxr = x_ref ? sc.alloc<double>(n * 6) : nullptr;
     A.lw = sc.alloc<double>(nl * MOOR_LW_N);
@@ -4691,21 +4733,16 @@ extern "C" int raftx_mean_pose(raftx_ctx *c, int nDesign, int nLine, const doubl
     A.Fres = F_res ? sc.alloc<double>(n * 6) : nullptr;
     A.iterations = iterations ? sc.alloc<int>(n) : nullptr;
     A.flags = sc.alloc<int>(n);
-    if (!dl || (!lines && nP && !dpar) || !dK || !dF0 || (F_env && !dFe) || (x_ref && !dxr) || !A.lw || (pose && !A.pose) ||
-        (C_moor && !A.C) || (F_moor && !A.F) || (T && !A.T) || (J && !A.J) || (F_res && !A.Fres) || (iterations && !A.iterations) || !A.flags)
+    if (!dK || !dF0 || (F_env && !dFe) || (x_ref && !dxr) || !A.lw || (pose && !A.pose) || (C_moor && !A.C) || (F_moor && !A.F) ||
+        (T && !A.T) || (J && !A.J) || (F_res && !A.Fres) || (iterations && !A.iterations) || !A.flags)
         FAIL(c, "mean_pose: device allocation failed");
-    if (lines) H2D(c, dl, lines, nl * RAFTX_ML_N * sizeof(double));
-    else if (nP) H2D(c, dpar, params, n * nP * sizeof(double));
     H2D(c, dK, K_hs, n * 36 * sizeof(double));
     H2D(c, dF0, F0, n * 6 * sizeof(double));
     if (F_env) H2D(c, dFe, F_env, n * 6 * sizeof(double));
     if (x_ref) H2D(c, dxr, x_ref, n * 6 * sizeof(double));
-    A.lines = dl; A.K_hs = dK; A.F0 = dF0; A.F_env = dFe; A.x_ref = dxr;
+    A.lines = L.lines; A.K_hs = dK; A.F0 = dF0; A.F_env = dFe; A.x_ref = dxr;
     HIPCHK(c, hipEventRecord(c->ev0, c->stream));
-    if (!lines) {                                                // the records of the program's variants, as raftx_mooring_expand
-        MoorExpandArgs E{nDesign, nLine, nP, c->mprog.base.p, c->mprog.coef.p, c->mprog.edit.p, dpar, dl};
-        hipLaunchKernelGGL(k_moor_expand, dim3(moor_grid((long long)nl)), dim3(MOOR_THREADS), 0, c->stream, E);
-    }
+    if (int rc = expand_lines(c, c->stream, n, nLine, L)) return rc;   // (inside the timed window, as raftx_mooring_expand)
     launch_mean_pose(c->stream, A, nDesign, nLine, depth, tolT, tolR, max_iter);
     if (finish_timed(c)) return -2;
     if (pose) D2H(c, pose, A.pose, n * 6 * sizeof(double));
@@ -4728,34 +4765,19 @@ extern "C" int raftx_sweep_mooring(raftx_ctx *c, int slot, int nLine, const doub
     SweepSlot &S = *slot_;
     if (!flags) FAIL(c, "sweep_mooring: bad arguments (flags is required)");
     const size_t n = S.bnd.empty() ? 0 : (size_t)S.bnd.back();
-    const VariantProg *vp = S.p1.var.prog;
-    if (!lines) {
-        if (!vp) FAIL(c, "sweep_mooring: lines == NULL needs a slot prepared with raftx_sweep_prepare_variants");
-        if (!c->mprog.nLine) FAIL(c, "sweep_mooring: no mooring program (raftx_mooring_program first)");
-        if (c->mprog.nP != vp->nP) FAIL(c, "sweep_mooring: the mooring program has %d parameters, the variant program %d", c->mprog.nP, vp->nP);
-        if (nLine != c->mprog.nLine) FAIL(c, "sweep_mooring: nLine=%d is not the %d lines of the mooring program", nLine, c->mprog.nLine);
-    } else {
-        if (nLine < 1) FAIL(c, "sweep_mooring: nLine must be positive (got %d)", nLine);
-        for (size_t i = 0; i < n * (size_t)nLine; i++) {
-            const double cb = lines[i * RAFTX_ML_N + 9];
-            if (std::isfinite(cb) && cb != 0.0)
-                FAIL(c, "sweep_mooring: line %zu of design %zu has seabed friction CB = %g: friction is not covered (CB must be 0)",
-                     i % nLine, i / nLine, cb);
-        }
-    }
-    const double depth = c->csets[S.cset].T.depth;
-    if (!std::isfinite(depth) || !(depth > 0.0)) FAIL(c, "sweep_mooring: the depth must be positive and finite (got %g)", depth);
+    if (int rc = check_slot_lines(c, "sweep_mooring", S, n, nLine, lines)) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     if (S.mooring.evUp) HIPCHK(c, hipEventSynchronize(S.mooring.evUp));   // (a second request on one slot: the landing area is free again)
     else HIPCHK(c, S.mooring.evUp.ensure(hipEventDisableTiming));
     S.mooring.on = false;                              // this request alone, while its landing area is rewritten: not clear_requests(), the slot's others stay
-    const size_t nl = n * (size_t)nLine, nT = 2 * (size_t)nLine;
-    HIPCHK(c, S.mooring.pin.reserve(n * (42 + nT) + (n + 1) / 2 + 1));
+    const size_t nl = n * (size_t)nLine;
+    const landing::Mooring land = landing::mooring(n, (size_t)nLine);
+    HIPCHK(c, S.mooring.pin.reserve(land.need));
     MoorArgs A;
     memset(&A, 0, sizeof(A));
-    A.nDesign = (int)n; A.nLine = nLine; A.depth = depth;
-    const double *dl = nullptr, *dp = nullptr, *dpar = nullptr;
-    double *dexp = nullptr;
+    A.nDesign = (int)n; A.nLine = nLine; A.depth = c->csets[S.cset].T.depth;
+    const double *dp = nullptr;
+    StagedLines L;
     int rc = 0;
     if (S.pose.on) {
         // behind a raftx_sweep_mean_pose request: at the poses its placement kernels leave on the device, so every block's
@@ -4772,32 +4794,24 @@ extern "C" int raftx_sweep_mooring(raftx_ctx *c, int slot, int nLine, const doub
         dp = S.pose.placed;
     } else
         rc = upload_on(c, c->sCopy, S.allocs, S.p1.pose, S.p1.pose ? n * 6 : 0, &dp);
-    if (lines) rc |= upload_on(c, c->sCopy, S.allocs, lines, nl * RAFTX_ML_N, &dl);
-    else {
-        rc |= upload_on(c, c->sCopy, S.allocs, S.p1.var.params, n * (size_t)vp->nP, &dpar);
-        rc |= pool_alloc(c, S.allocs, nl * RAFTX_ML_N, &dexp);
-        dl = dexp;
-    }
+    rc |= stage_lines(c, c->sCopy, S.allocs, n, nLine, lines, S.p1.var.params, L);
     double *dlw = nullptr, *dC = nullptr, *dF = nullptr, *dT = nullptr, *dLr = nullptr;
     int *dfl = nullptr;
     rc |= pool_alloc(c, S.allocs, nl * MOOR_LW_N, &dlw) | pool_alloc(c, S.allocs, n * 36, &dC) | pool_alloc(c, S.allocs, n * 6, &dF) |
           pool_alloc(c, S.allocs, nl * 2, &dT) | pool_alloc(c, S.allocs, nl * 36, &dLr) | pool_alloc(c, S.allocs, n, &dfl);
     if (rc) return -2;
     A.lw = dlw; A.C = dC; A.F = dF; A.T = dT; A.Lr = dLr; A.flags = dfl;
-    A.lines = dl; A.pose = dp;
+    A.lines = L.lines; A.pose = dp;
     if (n) {
-        if (!lines) {
-            MoorExpandArgs E{(int)n, nLine, vp->nP, c->mprog.base.p, c->mprog.coef.p, c->mprog.edit.p, dpar, dexp};
-            hipLaunchKernelGGL(k_moor_expand, dim3(moor_grid((long long)nl)), dim3(MOOR_THREADS), 0, c->sCopy, E);
-        }
+        if (int re = expand_lines(c, c->sCopy, n, nLine, L)) return re;
         hipLaunchKernelGGL(k_moor_line, dim3(moor_grid((long long)nl)), dim3(MOOR_THREADS), 0, c->sCopy, A);
         hipLaunchKernelGGL(k_moor_design, dim3(moor_grid((long long)n)), dim3(MOOR_THREADS), 0, c->sCopy, A);
         HIPCHK(c, hipGetLastError());
         double *p = S.mooring.pin.p;
-        HIPCHK(c, hipMemcpyAsync(p, A.C, n * 36 * sizeof(double), hipMemcpyDeviceToHost, c->sCopy));
-        HIPCHK(c, hipMemcpyAsync(p + n * 36, A.F, n * 6 * sizeof(double), hipMemcpyDeviceToHost, c->sCopy));
-        HIPCHK(c, hipMemcpyAsync(p + n * 42, A.T, n * nT * sizeof(double), hipMemcpyDeviceToHost, c->sCopy));
-        HIPCHK(c, hipMemcpyAsync(p + n * (42 + nT), A.flags, n * sizeof(int), hipMemcpyDeviceToHost, c->sCopy));
+        HIPCHK(c, hipMemcpyAsync(p + land.C, A.C, n * 36 * sizeof(double), hipMemcpyDeviceToHost, c->sCopy));
+        HIPCHK(c, hipMemcpyAsync(p + land.F, A.F, n * 6 * sizeof(double), hipMemcpyDeviceToHost, c->sCopy));
+        HIPCHK(c, hipMemcpyAsync(p + land.T, A.T, nl * 2 * sizeof(double), hipMemcpyDeviceToHost, c->sCopy));
+        HIPCHK(c, hipMemcpyAsync(land.flags.in(p), A.flags, n * sizeof(int), hipMemcpyDeviceToHost, c->sCopy));
     }
     HIPCHK(c, hipEventRecord(S.mooring.evUp, c->sCopy));
     S.mooring.nLine = nLine;
@@ -4825,52 +4839,25 @@ extern "C" int raftx_sweep_mean_pose(raftx_ctx *c, int slot, int nLine, const do
     const size_t n = S.bnd.empty() ? 0 : (size_t)S.bnd.back();
     if (nX != 0 && nX != 1 && (size_t)nX != n)
         FAIL(c, "sweep_mean_pose: nX=%d must be 0 (no extras), 1 (shared) or the %zu designs of the crossing", nX, n);
-    const VariantProg *vp = S.p1.var.prog;
-    if (!lines) {
-        if (!vp) FAIL(c, "sweep_mean_pose: lines == NULL needs a slot prepared with raftx_sweep_prepare_variants");
-        if (!c->mprog.nLine) FAIL(c, "sweep_mean_pose: no mooring program (raftx_mooring_program first)");
-        if (c->mprog.nP != vp->nP) FAIL(c, "sweep_mean_pose: the mooring program has %d parameters, the variant program %d", c->mprog.nP, vp->nP);
-        if (nLine != c->mprog.nLine) FAIL(c, "sweep_mean_pose: nLine=%d is not the %d lines of the mooring program", nLine, c->mprog.nLine);
-    } else {
-        if (nLine < 1) FAIL(c, "sweep_mean_pose: nLine must be positive (got %d)", nLine);
-        for (size_t i = 0; i < n * (size_t)nLine; i++) {
-            const double cb = lines[i * RAFTX_ML_N + 9];
-            if (std::isfinite(cb) && cb != 0.0)
-                FAIL(c, "sweep_mean_pose: line %zu of design %zu has seabed friction CB = %g: friction is not covered (CB must be 0)",
-                     i % nLine, i / nLine, cb);
-        }
-    }
-    const double depth = c->csets[S.cset].T.depth;
-    if (!std::isfinite(depth) || !(depth > 0.0)) FAIL(c, "sweep_mean_pose: the depth must be positive and finite (got %g)", depth);
+    if (int rc = check_slot_lines(c, "sweep_mean_pose", S, n, nLine, lines)) return rc;
     double tolT, tolR;
     if (int rc = mean_pose_tol(c, "sweep_mean_pose", tol, &tolT, &tolR)) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     auto &P = S.pose;
     HIPCHK(c, P.evUp.ensure(hipEventDisableTiming));
-    HIPCHK(c, P.pin.reserve(n * 13 + 2));
+    HIPCHK(c, P.pin.reserve(landing::pose(n).need));
     const size_t nl = n * (size_t)nLine;
-    const double *dl = nullptr, *dpar = nullptr;
-    double *dexp = nullptr;
-    int rc = 0;
-    if (lines) rc |= upload_on(c, c->sCopy, S.allocs, lines, nl * RAFTX_ML_N, &dl);
-    else {
-        rc |= upload_on(c, c->sCopy, S.allocs, S.p1.var.params, n * (size_t)vp->nP, &dpar);
-        rc |= pool_alloc(c, S.allocs, nl * RAFTX_ML_N, &dexp);
-        dl = dexp;
-    }
+    StagedLines L;
+    int rc = stage_lines(c, c->sCopy, S.allocs, n, nLine, lines, S.p1.var.params, L);
     rc |= upload_on(c, c->sCopy, S.allocs, C_extra, (size_t)nX * 36, &P.Cx) | upload_on(c, c->sCopy, S.allocs, F_extra, (size_t)nX * 6, &P.Fx) |
           upload_on(c, c->sCopy, S.allocs, F_env, n * 6, &P.Fenv);
     rc |= pool_alloc(c, S.allocs, n * 36, &P.K) | pool_alloc(c, S.allocs, n * 6, &P.F0) | pool_alloc(c, S.allocs, nl * MOOR_LW_N, &P.lw) |
           pool_alloc(c, S.allocs, n * 6, &P.solved) | pool_alloc(c, S.allocs, n * 6, &P.placed) | pool_alloc(c, S.allocs, n * 6, &P.Fres) |
           pool_alloc(c, S.allocs, n, &P.iter) | pool_alloc(c, S.allocs, n, &P.fl);
     if (rc) return -2;
-    if (n && !lines) {
-        MoorExpandArgs E{(int)n, nLine, vp->nP, c->mprog.base.p, c->mprog.coef.p, c->mprog.edit.p, dpar, dexp};
-        hipLaunchKernelGGL(k_moor_expand, dim3(moor_grid((long long)nl)), dim3(MOOR_THREADS), 0, c->sCopy, E);
-        HIPCHK(c, hipGetLastError());
-    }
+    if (int re = expand_lines(c, c->sCopy, n, nLine, L)) return re;
     HIPCHK(c, hipEventRecord(P.evUp, c->sCopy));
-    P.lines = dl; P.nLine = nLine; P.nX = nX; P.maxIter = max_iter; P.tolT = tolT; P.tolR = tolR;
+    P.lines = L.lines; P.nLine = nLine; P.nX = nX; P.maxIter = max_iter; P.tolT = tolT; P.tolR = tolR;
     P.pose_out = pose; P.Fres_out = F_res; P.iter_out = iterations; P.flags_out = flags;
     P.on = true;
     // the blocks whose phase 1 raftx_sweep_prepare enqueued; raftx_sweep_launch does the others behind their phase 1

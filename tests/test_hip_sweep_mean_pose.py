@@ -13,7 +13,7 @@ from raft_amd.sweep import GeometrySweep
 from tests import mooring_reference as mr
 from tests.test_geometry import C3, _c3_crossing_inputs
 from tests.test_hip_modal import _variant_sweep
-from tests.test_hip_sweep_channels import same_bits
+from tests.test_hip_sweep_channels import same_bits, shared_rows
 from tests.test_hip_sweep_mooring import BITS, DEPTH, PARENT_SHA, plain_hashes, program
 
 pytestmark = pytest.mark.gpu
@@ -198,6 +198,40 @@ def test_flagged_design_comes_back_nan_and_alone(hip_ctx):
         assert list(capped["pose_iterations"]) == [1, 1, 0, 1, 1, 1] and np.all(capped["flags"] & 2)
         for k in ("std", "Xi", "fn", "pose", "F_res"):
             assert not np.any(np.isfinite(capped[k].view(float))), (name, k)
+
+
+def test_all_five_requests_on_one_crossing(hip_ctx):
+    """mean_pose= + mooring= + modal + current + channels on one crossing of two blocks: every output has the bits of the
+    crossing that carries its request alone (beside mean_pose= and mooring=), and a pose-flagged design comes back non-finite
+    in every request's outputs while the other designs keep the clean run's bits."""
+    name, sw, src, lines = forms()[1]
+    riders = {"modal": dict(modal=True, want_props=True), "current": dict(current=dict(speed=[0.8, 1.3], heading=[0.0, 40.0])),
+              "channels": dict(channels=shared_rows(True))}
+    own = {"modal": ("fn", "modes", "modal_flags", "props"), "current": ("D_hydro",), "channels": ("chan_std",)}
+    shared = ("std", "niter", "flags", "Xi", "strip_off", "pose", "F_res", "C_moor", "F_moor", "T_mean", "T_std")
+
+    def go(slot, ln, **kw):
+        return sw.wait_crossing(hip_ctx, sw.submit_crossing(hip_ctx, slot, n_chunk=3, want_Xi=True, mean_pose=request(dict(lines=ln), N),
+                                                            mooring=dict(add_stiffness=True, lines=ln), **kw))
+
+    everything = {k: v for r in riders.values() for k, v in r.items()}
+    clean = go(0, lines, **everything)
+    assert not clean["pose_flags"].any() and not clean["moor_flags"].any() and np.all(np.isfinite(clean["std"]))
+    on2 = go(2, lines, **everything)
+    for k in shared + sum(own.values(), ()):
+        assert same_bits(on2[k], clean[k]), ("slot 2", k)
+    for rider, kw in riders.items():
+        alone = go(0, lines, **kw)
+        for k in shared + own[rider]:
+            assert same_bits(clean[k], alone[k]), (rider, k)
+    bad = lines.copy()
+    bad[2, 1, 6] = 5000.0                                                  # fully slack
+    got = go(0, bad, **everything)
+    assert list(got["pose_flags"]) == [0, 0, mr.FLAG_SLACK, 0, 0, 0]
+    keep = np.arange(N) != 2
+    for k in ("std", "Xi", "fn", "modes", "props", "D_hydro", "chan_std", "C_moor", "F_moor", "T_mean", "T_std"):
+        assert not np.any(np.isfinite(got[k][2].view(float))), k
+        assert same_bits(got[k][keep], clean[k][keep]), k
 
 
 def test_a_design_depends_on_itself_only(hip_ctx):
