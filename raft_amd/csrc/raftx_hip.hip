@@ -1776,20 +1776,6 @@ static int check_ready(raftx_ctx *c) {
     return 0;
 }
 
-// device scratch that lives for one call
-struct Scratch {
-    raftx_ctx *c;
-    Bag bag;
-    explicit Scratch(raftx_ctx *c_) : c(c_) {}
-    ~Scratch() { (void)hipStreamSynchronize(c->stream); }   // ahead of the bag's release: blocks go back to the pool only when nothing in flight uses them
-    template <typename Tp>
-    Tp *alloc(size_t n) {                           // null for a zero count, and when the pool has no room
-        Tp *p = nullptr;
-        if (n) (void)bag.get(c->pool, n, &p);
-        return p;
-    }
-};
-
 #define D2H(c, dst, src, bytes) HIPCHK(c, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, (c)->stream))
 #define H2D(c, dst, src, bytes) HIPCHK(c, hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, (c)->stream))
 
@@ -1802,6 +1788,33 @@ static int finish_timed(raftx_ctx *c) {
     c->last_ms = ms;
     return 0;
 }
+
+// threads of a workgroup whose lanes stride the nw frequency bins of one row (the statistics and channel kernels, k_bem_excitation)
+static dim3 bin_threads(int nw) { return dim3(nw > 128 ? 256 : (nw > 64 ? 128 : 64)); }
+
+// The device scratch of one call and the call's protocol on the ctx stream (the arrays: Staging, raftx_owned.h):
+//   declare tmp / in / out | upload(who) | anything untimed | begin() | the kernels | finish()
+// A call that is not timed ends with download() where the others end with finish().
+struct Scratch : Staging {
+    raftx_ctx *c;
+    explicit Scratch(raftx_ctx *c_) : Staging(c_->pool), c(c_) {}
+    ~Scratch() { (void)hipStreamSynchronize(c->stream); }   // ahead of the bag's release: blocks go back to the pool only when nothing in flight uses them
+    int upload(const char *who) {                    // -1: a block was refused; else the uploads declared so far, in their order
+        if (failed) FAIL(c, "%s: device allocation failed", who);
+        HIPCHK(c, send(c->stream));
+        return 0;
+    }
+    int begin() {                                    // the timed window of raftx_last_kernel_ms opens
+        HIPCHK(c, hipEventRecord(c->ev0, c->stream));
+        return 0;
+    }
+    int download() {                                 // the result copies, in their order, and the caller's arrays are final
+        HIPCHK(c, fetch(c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        return 0;
+    }
+    int finish() { return finish_timed(c) ? -2 : download(); }   // ... after the window has closed and last_ms is set
+};
 
 // the instantiated kernel of a shape (nullptr: none)
 typedef void (*excitation_fn)(DevTables, cplx *);
@@ -1819,19 +1832,16 @@ extern "C" int raftx_excitation(raftx_ctx *c, raftx_c128 *F_iner) {
     size_t npair = (size_t)T.nDesign * T.nCase;
     size_t n = npair * T.nHead * 6 * T.nw;
     Scratch sc(c);
-    cplx *dF = sc.alloc<cplx>(n);
-    if (n && !dF) FAIL(c, "excitation: device allocation failed");
+    cplx *dF = sc.out<cplx>(F_iner, n);
+    if (int rc = sc.upload("excitation")) return rc;
     const Shape sh = pick_shape(T.nw);
-    HIPCHK(c, hipEventRecord(c->ev0, c->stream));
+    if (sc.begin()) return -2;
     if (npair) {
         excitation_fn kernel = excitation_kernel(sh);
         if (!kernel) NO_KERNEL(c, sh);
         hipLaunchKernelGGL(kernel, dim3((unsigned)(npair * T.nHead)), dim3(sh.threads), 0, c->stream, T, dF);
     }
-    if (finish_timed(c)) return -2;
-    if (n) D2H(c, F_iner, dF, n * sizeof(cplx));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return 0;
+    return sc.finish();
 }
 
 typedef void (*linearize_fn)(DevTables, const cplx *, double *, cplx *);
@@ -1861,17 +1871,12 @@ extern "C" int raftx_linearize(raftx_ctx *c, const raftx_c128 *Xi, double *B_dra
     const DevTables &T = c->T;
     size_t npair = (size_t)T.nDesign * T.nCase;
     Scratch sc(c);
-    cplx *dXi = sc.alloc<cplx>(npair * 6 * T.nw);
-    double *dB = B_drag ? sc.alloc<double>(npair * 36) : nullptr;
-    cplx *dF = F_drag ? sc.alloc<cplx>(npair * T.nHead * 6 * T.nw) : nullptr;
-    if (npair && (!dXi || (B_drag && !dB) || (F_drag && !dF))) FAIL(c, "linearize: device allocation failed");
-    if (npair) H2D(c, dXi, Xi, npair * 6 * T.nw * sizeof(cplx));
+    cplx *dXi = sc.in<cplx>(Xi, npair * 6 * T.nw);
+    double *dB = sc.out<double>(B_drag, npair * 36);
+    cplx *dF = sc.out<cplx>(F_drag, npair * T.nHead * 6 * T.nw);
+    if (int rc = sc.upload("linearize")) return rc;
     if (linearize_enqueue(c, dXi, dB, dF)) return -1;
-    if (finish_timed(c)) return -2;
-    if (dB) D2H(c, B_drag, dB, npair * 36 * sizeof(double));
-    if (dF) D2H(c, F_drag, dF, npair * T.nHead * 6 * T.nw * sizeof(cplx));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return 0;
+    return sc.finish();
 }
 
 // the resident strips of one design (host copy of its offsets)
@@ -1894,16 +1899,11 @@ extern "C" int raftx_strip_kinematics(raftx_ctx *c, int design, int icase, raftx
     const size_t n = (size_t)T.nHead * S * T.nw;
     if (!n) return 0;
     Scratch sc(c);
-    cplx *du = u ? sc.alloc<cplx>(n * 3) : nullptr, *dud = ud ? sc.alloc<cplx>(n * 3) : nullptr, *dp = pDyn ? sc.alloc<cplx>(n) : nullptr;
-    if ((u && !du) || (ud && !dud) || (pDyn && !dp)) FAIL(c, "strip_kinematics: device allocation failed");
-    HIPCHK(c, hipEventRecord(c->ev0, c->stream));
+    cplx *du = sc.out<cplx>(u, n * 3), *dud = sc.out<cplx>(ud, n * 3), *dp = sc.out<cplx>(pDyn, n);
+    if (int rc = sc.upload("strip_kinematics")) return rc;
+    if (sc.begin()) return -2;
     hipLaunchKernelGGL(k_strip_kinematics, dim3((unsigned)(S * T.nHead)), dim3(256), 0, c->stream, T, design, icase, du, dud, dp);
-    if (finish_timed(c)) return -2;
-    if (du) D2H(c, u, du, n * 3 * sizeof(cplx));
-    if (dud) D2H(c, ud, dud, n * 3 * sizeof(cplx));
-    if (dp) D2H(c, pDyn, dp, n * sizeof(cplx));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return 0;
+    return sc.finish();
 }
 extern "C" int raftx_strip_drag(raftx_ctx *c, int design, int icase, const raftx_c128 *Xi, int ih, double *Bmat,
                                 raftx_c128 *F_exc_drag) {
@@ -1915,17 +1915,13 @@ extern "C" int raftx_strip_drag(raftx_ctx *c, int design, int icase, const raftx
     if (ih < 0 || ih >= T.nHead) FAIL(c, "strip_drag: heading outside the resident sea state");
     if (!S) return 0;
     Scratch sc(c);
-    cplx *dXi = sc.alloc<cplx>((size_t)6 * T.nw), *dF = F_exc_drag ? sc.alloc<cplx>((size_t)S * 3 * T.nw) : nullptr;
-    double *dB = Bmat ? sc.alloc<double>((size_t)S * 9) : nullptr;
-    if (!dXi || (F_exc_drag && !dF) || (Bmat && !dB)) FAIL(c, "strip_drag: device allocation failed");
-    H2D(c, dXi, Xi, (size_t)6 * T.nw * sizeof(cplx));
-    HIPCHK(c, hipEventRecord(c->ev0, c->stream));
+    cplx *dXi = sc.in<cplx>(Xi, (size_t)6 * T.nw);
+    double *dB = sc.out<double>(Bmat, (size_t)S * 9);
+    cplx *dF = sc.out<cplx>(F_exc_drag, (size_t)S * 3 * T.nw);
+    if (int rc = sc.upload("strip_drag")) return rc;
+    if (sc.begin()) return -2;
     hipLaunchKernelGGL(k_strip_drag, dim3((unsigned)S), dim3(256), 0, c->stream, T, design, icase, ih, dXi, dB, dF);
-    if (finish_timed(c)) return -2;
-    if (dB) D2H(c, Bmat, dB, (size_t)S * 9 * sizeof(double));
-    if (dF) D2H(c, F_exc_drag, dF, (size_t)S * 3 * T.nw * sizeof(cplx));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return 0;
+    return sc.finish();
 }
 
 template <typename Tp>
@@ -2423,25 +2419,17 @@ extern "C" int raftx_bem_excitation(raftx_ctx *c, int nHeadBEM, const double *he
     c->bem_ready = false;
     if (grow_device(c, c->bemF, nx)) return -2;
     Scratch sc(c);
-    double *dH = sc.alloc<double>(nHeadBEM), *dA = heading_adjust ? sc.alloc<double>(T.nDesign) : nullptr,
-           *dXY = xy_ref ? sc.alloc<double>((size_t)T.nDesign * 2) : nullptr;
-    cplx *dX = sc.alloc<cplx>(nX), *dAdd = F_add ? sc.alloc<cplx>(nx) : nullptr;
-    if (nx && (!dH || !dX || (heading_adjust && !dA) || (xy_ref && !dXY) || (F_add && !dAdd)))
-        FAIL(c, "bem_excitation: device allocation failed");
-    if (nx) {
-        H2D(c, dH, headings_deg, nHeadBEM * sizeof(double));
-        H2D(c, dX, X_BEM, nX * sizeof(cplx));
-        if (dA) H2D(c, dA, heading_adjust, T.nDesign * sizeof(double));
-        if (dXY) H2D(c, dXY, xy_ref, (size_t)T.nDesign * 2 * sizeof(double));
-        if (dAdd) H2D(c, dAdd, F_add, nx * sizeof(cplx));
-    }
-    HIPCHK(c, hipEventRecord(c->ev0, c->stream));
+    double *dH = sc.in<double>(headings_deg, nHeadBEM);
+    cplx *dX = sc.in<cplx>(X_BEM, nX);
+    double *dA = sc.in<double>(heading_adjust, T.nDesign), *dXY = sc.in<double>(xy_ref, (size_t)T.nDesign * 2);
+    cplx *dAdd = sc.in<cplx>(F_add, nx);
+    sc.out_from(F_out, c->bemF.p, nx);
+    if (int rc = sc.upload("bem_excitation")) return rc;
+    if (sc.begin()) return -2;
     if (nx)
-        hipLaunchKernelGGL(k_bem_excitation, dim3((unsigned)(npair * T.nHead)), dim3(T.nw > 128 ? 256 : (T.nw > 64 ? 128 : 64)), 0,
-                           c->stream, T, nHeadBEM, dH, dX, dA, dXY, dAdd, c->bemF.p);
-    if (finish_timed(c)) return -2;
-    if (nx && F_out) D2H(c, F_out, c->bemF.p, nx * sizeof(cplx));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+        hipLaunchKernelGGL(k_bem_excitation, dim3((unsigned)(npair * T.nHead)), bin_threads(T.nw), 0, c->stream, T, nHeadBEM, dH, dX, dA,
+                           dXY, dAdd, c->bemF.p);
+    if (int rc = sc.finish()) return rc;
     c->bem_ready = true;
     return 0;
 }
@@ -2455,18 +2443,13 @@ extern "C" int raftx_motion_stats(raftx_ctx *c, double dw, double *sd, double *p
     const DevTables &T = c->T;
     const size_t npair = c->r_npair;
     Scratch sc(c);
-    double *dS = sc.alloc<double>(npair * 6);
-    double *dP = psd ? sc.alloc<double>(npair * 6 * T.nw) : nullptr;
-    if (npair && (!dS || (psd && !dP))) FAIL(c, "motion_stats: device allocation failed");
-    HIPCHK(c, hipEventRecord(c->ev0, c->stream));
+    double *dS = sc.out<double>(sd, npair * 6), *dP = sc.out<double>(psd, npair * 6 * T.nw);
+    if (int rc = sc.upload("motion_stats")) return rc;
+    if (sc.begin()) return -2;
     if (npair)
-        hipLaunchKernelGGL(k_motion_stats, dim3((unsigned)npair), dim3(T.nw > 128 ? 256 : (T.nw > 64 ? 128 : 64)), 0,
-                           c->stream, (int)npair, T.nHead, T.nw, 1.0 / dw, c->rXi, dS, dP);
-    if (finish_timed(c)) return -2;
-    if (npair) D2H(c, sd, dS, npair * 6 * sizeof(double));
-    if (npair && psd) D2H(c, psd, dP, npair * 6 * T.nw * sizeof(double));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return 0;
+        hipLaunchKernelGGL(k_motion_stats, dim3((unsigned)npair), bin_threads(T.nw), 0, c->stream, (int)npair, T.nHead, T.nw, 1.0 / dw,
+                           c->rXi, dS, dP);
+    return sc.finish();
 }
 
 extern "C" int raftx_channel_stats(raftx_ctx *c, int nChan, const double *L, const int32_t *pw, double dw, double *sd,
@@ -2481,23 +2464,15 @@ extern "C" int raftx_channel_stats(raftx_ctx *c, int nChan, const double *L, con
     const DevTables &T = c->T;
     const size_t npair = c->r_npair;
     Scratch sc(c);
-    double *dL = sc.alloc<double>((size_t)T.nDesign * nChan * 6), *dS = sc.alloc<double>(npair * nChan);
-    int *dP = sc.alloc<int>(nChan);
-    double *dPsd = psd ? sc.alloc<double>(npair * nChan * T.nw) : nullptr;
-    if (npair && nChan && (!dL || !dS || !dP || (psd && !dPsd))) FAIL(c, "channel_stats: device allocation failed");
-    if (npair && nChan) {
-        H2D(c, dL, L, (size_t)T.nDesign * nChan * 6 * sizeof(double));
-        H2D(c, dP, pw, nChan * sizeof(int));
-    }
-    HIPCHK(c, hipEventRecord(c->ev0, c->stream));
+    double *dL = sc.in<double>(L, (size_t)T.nDesign * nChan * 6);
+    int *dP = sc.in<int>(pw, nChan);
+    double *dS = sc.out<double>(sd, npair * nChan), *dPsd = sc.out<double>(psd, npair * nChan * T.nw);
+    if (int rc = sc.upload("channel_stats")) return rc;
+    if (sc.begin()) return -2;
     if (npair && nChan)
-        hipLaunchKernelGGL(k_channel_stats, dim3((unsigned)npair), dim3(T.nw > 128 ? 256 : (T.nw > 64 ? 128 : 64)), 0,
-                           c->stream, T.nCase, T.nHead, T.nw, nChan, 1.0 / dw, T.w, c->rXi, dL, dP, dS, dPsd);
-    if (finish_timed(c)) return -2;
-    if (npair && nChan) D2H(c, sd, dS, npair * nChan * sizeof(double));
-    if (npair && nChan && psd) D2H(c, psd, dPsd, npair * nChan * T.nw * sizeof(double));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return 0;
+        hipLaunchKernelGGL(k_channel_stats, dim3((unsigned)npair), bin_threads(T.nw), 0, c->stream, T.nCase, T.nHead, T.nw, nChan,
+                           1.0 / dw, T.w, c->rXi, dL, dP, dS, dPsd);
+    return sc.finish();
 }
 
 extern "C" int raftx_channel_stats_poly(raftx_ctx *c, int nChan, const double *L, const raftx_c128 *Gw, double dw, double *sd,
@@ -2510,24 +2485,15 @@ extern "C" int raftx_channel_stats_poly(raftx_ctx *c, int nChan, const double *L
     const DevTables &T = c->T;
     const size_t npair = c->r_npair;
     Scratch sc(c);
-    const size_t nL = (size_t)T.nDesign * nChan * 18, nG = (size_t)T.nDesign * nChan * 6 * T.nw;
-    double *dL = sc.alloc<double>(nL), *dS = sc.alloc<double>(npair * nChan);
-    cplx *dG = Gw ? sc.alloc<cplx>(nG) : nullptr;
-    double *dPsd = psd ? sc.alloc<double>(npair * nChan * T.nw) : nullptr;
-    if (npair && nChan && (!dL || !dS || (Gw && !dG) || (psd && !dPsd))) FAIL(c, "channel_stats_poly: device allocation failed");
-    if (npair && nChan) {
-        H2D(c, dL, L, nL * sizeof(double));
-        if (dG) H2D(c, dG, Gw, nG * sizeof(cplx));
-    }
-    HIPCHK(c, hipEventRecord(c->ev0, c->stream));
+    double *dL = sc.in<double>(L, (size_t)T.nDesign * nChan * 18);
+    cplx *dG = sc.in<cplx>(Gw, (size_t)T.nDesign * nChan * 6 * T.nw);
+    double *dS = sc.out<double>(sd, npair * nChan), *dPsd = sc.out<double>(psd, npair * nChan * T.nw);
+    if (int rc = sc.upload("channel_stats_poly")) return rc;
+    if (sc.begin()) return -2;
     if (npair && nChan)
-        hipLaunchKernelGGL(k_channel_stats_poly, dim3((unsigned)npair), dim3(T.nw > 128 ? 256 : (T.nw > 64 ? 128 : 64)), 0,
-                           c->stream, T.nCase, T.nHead, T.nw, nChan, 1.0 / dw, T.w, c->rXi, dL, dG, dS, dPsd);
-    if (finish_timed(c)) return -2;
-    if (npair && nChan) D2H(c, sd, dS, npair * nChan * sizeof(double));
-    if (npair && nChan && psd) D2H(c, psd, dPsd, npair * nChan * T.nw * sizeof(double));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return 0;
+        hipLaunchKernelGGL(k_channel_stats_poly, dim3((unsigned)npair), bin_threads(T.nw), 0, c->stream, T.nCase, T.nHead, T.nw, nChan,
+                           1.0 / dw, T.w, c->rXi, dL, dG, dS, dPsd);
+    return sc.finish();
 }
 
 extern "C" int raftx_response_stats(raftx_ctx *c, int nChan, int nDof, int nResp, int nw, const double *w, const double *L,
@@ -2539,22 +2505,28 @@ extern "C" int raftx_response_stats(raftx_ctx *c, int nChan, int nDof, int nResp
     if (!nChan) return 0;
     HIPCHK(c, hipSetDevice(c->device));
     Scratch sc(c);
-    const size_t nl = (size_t)nChan * 3 * nDof, ng = (size_t)nChan * nDof * nw, nx = (size_t)nResp * nDof * nw;
-    double *dw_ = sc.alloc<double>(nw), *dL = sc.alloc<double>(nl), *dS = sc.alloc<double>(nChan);
-    double *dP = psd ? sc.alloc<double>((size_t)nChan * nw) : nullptr;
-    cplx *dG = Gw ? sc.alloc<cplx>(ng) : nullptr, *dX = sc.alloc<cplx>(nx);
-    if (!dw_ || !dL || !dS || (psd && !dP) || (Gw && !dG) || !dX) FAIL(c, "response_stats: device allocation failed");
-    H2D(c, dw_, w, nw * sizeof(double));
-    H2D(c, dL, L, nl * sizeof(double));
-    if (dG) H2D(c, dG, Gw, ng * sizeof(cplx));
-    H2D(c, dX, Xi, nx * sizeof(cplx));
-    HIPCHK(c, hipEventRecord(c->ev0, c->stream));
-    hipLaunchKernelGGL(k_response_stats, dim3((unsigned)nChan), dim3(nw > 128 ? 256 : (nw > 64 ? 128 : 64)), 0, c->stream, nDof, nResp, nw,
-                       1.0 / dw, dw_, dX, dL, dG, dS, dP);
-    if (finish_timed(c)) return -2;
-    D2H(c, sd, dS, nChan * sizeof(double));
-    if (psd) D2H(c, psd, dP, (size_t)nChan * nw * sizeof(double));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    double *dw_ = sc.in<double>(w, nw), *dL = sc.in<double>(L, (size_t)nChan * 3 * nDof);
+    cplx *dG = sc.in<cplx>(Gw, (size_t)nChan * nDof * nw), *dX = sc.in<cplx>(Xi, (size_t)nResp * nDof * nw);
+    double *dS = sc.out<double>(sd, nChan), *dP = sc.out<double>(psd, (size_t)nChan * nw);
+    if (int rc = sc.upload("response_stats")) return rc;
+    if (sc.begin()) return -2;
+    hipLaunchKernelGGL(k_response_stats, dim3((unsigned)nChan), bin_threads(nw), 0, c->stream, nDof, nResp, nw, 1.0 / dw, dw_, dX, dL, dG,
+                       dS, dP);
+    return sc.finish();
+}
+
+// launches the LDS-resident solver, for the shapes launch_solve_system_rows has no kernel for (callers have checked that
+// the shape fits: solve_system_shape gives at most 150 KiB)
+template <bool RESIDENT>
+static int launch_solve_system_lds(raftx_ctx *c, int nSys, int nUnit, int nRhs, int nw, int nCase, const double *w, const cplx *Z,
+                                   const double *Mc, const double *Bc, const double *Cc, const cplx *F, cplx *X) {
+    size_t lds = 0;
+    const int nbin = solve_system_shape(6 * nUnit, nRhs, &lds);
+    if (lds > 64 * 1024)
+        HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void *>(k_solve_system<RESIDENT>),
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(k_solve_system<RESIDENT>, dim3((unsigned)((size_t)nSys * ((nw + nbin - 1) / nbin))), dim3(64 * nbin), lds,
+                       c->stream, nSys, nUnit, nRhs, nw, nCase, w, Z, Mc, Bc, Cc, F, X);
     return 0;
 }
 
@@ -2566,36 +2538,19 @@ extern "C" int raftx_solve_system(raftx_ctx *c, int nSys, int nUnit, int nRhs, i
     HIPCHK(c, hipSetDevice(c->device));
     const int n = 6 * nUnit;
     size_t lds = 0;
-    const int nbin = solve_system_shape(n, nRhs, &lds);
+    solve_system_shape(n, nRhs, &lds);
     if (lds > 150 * 1024) FAIL(c, "solve_system: %d DOFs x %d rhs does not fit the LDS-resident solver", n, nRhs);
     Scratch sc(c);
-    size_t nz = (size_t)nSys * nUnit * 36 * nw, nf = (size_t)nSys * nRhs * n * nw, nc = (size_t)nSys * n * n;
-    double *dw = sc.alloc<double>(nw);
-    cplx *dZ = sc.alloc<cplx>(nz), *dF = sc.alloc<cplx>(nf), *dX = sc.alloc<cplx>(nf);
-    double *dM = Mc ? sc.alloc<double>(nc) : nullptr, *dB = Bc ? sc.alloc<double>(nc) : nullptr,
-           *dC = Cc ? sc.alloc<double>(nc) : nullptr;
-    if (nSys && (!dw || !dZ || !dF || !dX || (Mc && !dM) || (Bc && !dB) || (Cc && !dC)))
-        FAIL(c, "solve_system: device allocation failed");
-    if (nSys) {
-        H2D(c, dw, w, nw * sizeof(double));
-        H2D(c, dZ, Zblk, nz * sizeof(cplx));
-        H2D(c, dF, F, nf * sizeof(cplx));
-        if (dM) H2D(c, dM, Mc, nc * sizeof(double));
-        if (dB) H2D(c, dB, Bc, nc * sizeof(double));
-        if (dC) H2D(c, dC, Cc, nc * sizeof(double));
-    }
-    HIPCHK(c, hipEventRecord(c->ev0, c->stream));
-    if (nSys && !launch_solve_system_rows<false>(c->stream, nSys, nUnit, nRhs, nw, 1, dw, dZ, dM, dB, dC, dF, dX)) {
-        if (lds > 64 * 1024)
-            HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void *>(k_solve_system<false>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(k_solve_system<false>, dim3((unsigned)((size_t)nSys * ((nw + nbin - 1) / nbin))), dim3(64 * nbin), lds,
-                           c->stream, nSys, nUnit, nRhs, nw, 1, dw, dZ, dM, dB, dC, dF, dX);
-    }
-    if (finish_timed(c)) return -2;
-    if (nSys) D2H(c, Xi, dX, nf * sizeof(cplx));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return 0;
+    const size_t nf = (size_t)nSys * nRhs * n * nw, nc = (size_t)nSys * n * n;
+    double *dw = sc.in<double>(w, nw);
+    cplx *dZ = sc.in<cplx>(Zblk, (size_t)nSys * nUnit * 36 * nw), *dF = sc.in<cplx>(F, nf);
+    double *dM = sc.in<double>(Mc, nc), *dB = sc.in<double>(Bc, nc), *dC = sc.in<double>(Cc, nc);
+    cplx *dX = sc.out<cplx>(Xi, nf);
+    if (int rc = sc.upload("solve_system")) return rc;
+    if (sc.begin()) return -2;
+    if (nSys && !launch_solve_system_rows<false>(c->stream, nSys, nUnit, nRhs, nw, 1, dw, dZ, dM, dB, dC, dF, dX))
+        if (int rc = launch_solve_system_lds<false>(c, nSys, nUnit, nRhs, nw, 1, dw, dZ, dM, dB, dC, dF, dX)) return rc;
+    return sc.finish();
 }
 
 // launch of the dense solves of nSys systems x nw bins on device arrays: the register-resident kernel where the augmented
@@ -2643,24 +2598,14 @@ static int solve_dense_impl(raftx_ctx *c, int nSys, int n, int nRhs, int nw, con
     Scratch sc(c);
     const bool reg = dense_reg_shape(n, nRhs);
     const size_t nn = (size_t)n * n, nf = (size_t)nSys * nRhs * n * nw;
-    const size_t nM = (size_t)nSys * nn * ((freq_mask & 1) ? nw : 1), nB = (size_t)nSys * nn * ((freq_mask & 2) ? nw : 1);
-    double *dw = sc.alloc<double>(nw), *dM = sc.alloc<double>(nM), *dB = sc.alloc<double>(nB), *dC = sc.alloc<double>((size_t)nSys * nn);
-    cplx *dF = sc.alloc<cplx>(nf), *dX = sc.alloc<cplx>(nf);
-    cplx *dA = reg ? nullptr : sc.alloc<cplx>((size_t)nSys * nw * n * (n + nRhs));
-    cplx *dZ = Z ? sc.alloc<cplx>((size_t)nSys * nn * nw) : nullptr;
-    if (!dw || !dM || !dB || !dC || !dF || !dX || (!reg && !dA) || (Z && !dZ)) FAIL(c, "solve_dense: device allocation failed");
-    H2D(c, dw, w, nw * sizeof(double));
-    H2D(c, dM, M, nM * sizeof(double));
-    H2D(c, dB, B, nB * sizeof(double));
-    H2D(c, dC, C, (size_t)nSys * nn * sizeof(double));
-    H2D(c, dF, F, nf * sizeof(cplx));
-    HIPCHK(c, hipEventRecord(c->ev0, c->stream));
+    double *dw = sc.in<double>(w, nw), *dM = sc.in<double>(M, (size_t)nSys * nn * ((freq_mask & 1) ? nw : 1)),
+           *dB = sc.in<double>(B, (size_t)nSys * nn * ((freq_mask & 2) ? nw : 1)), *dC = sc.in<double>(C, (size_t)nSys * nn);
+    cplx *dF = sc.in<cplx>(F, nf), *dX = sc.out<cplx>(Xi, nf), *dZ = sc.out<cplx>(Z, (size_t)nSys * nn * nw);
+    cplx *dA = reg ? nullptr : sc.tmp<cplx>((size_t)nSys * nw * n * (n + nRhs));
+    if (int rc = sc.upload("solve_dense")) return rc;
+    if (sc.begin()) return -2;
     if (dense_launch(c, nSys, 1, n, nRhs, nw, dw, dM, dB, dC, freq_mask, nullptr, dF, dX, dZ, dA)) return -1;
-    if (finish_timed(c)) return -2;
-    D2H(c, Xi, dX, nf * sizeof(cplx));
-    if (Z) D2H(c, Z, dZ, (size_t)nSys * nn * nw * sizeof(cplx));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return 0;
+    return sc.finish();
 }
 extern "C" int raftx_solve_dense(raftx_ctx *c, int n, int nRhs, int nw, const double *w, const double *M, const double *B,
                                  const double *C, int freq_mask, const raftx_c128 *F, raftx_c128 *Xi, raftx_c128 *Z) {
@@ -2710,20 +2655,13 @@ extern "C" int raftx_solve_dense_resident(raftx_ctx *c, int nPer, const double *
     Scratch sc(c);
     const bool reg = dense_reg_shape(n, nRhs);
     const size_t nn = (size_t)n * n, nf = (size_t)nSys * nRhs * n * nw;
-    double *dBadd = Badd ? sc.alloc<double>((size_t)nSys * nn) : nullptr;
-    cplx *dF = sc.alloc<cplx>(nf), *dX = sc.alloc<cplx>(nf);
-    cplx *dA = reg ? nullptr : sc.alloc<cplx>((size_t)nSys * nw * n * (n + nRhs));
-    cplx *dZ = Z ? sc.alloc<cplx>((size_t)nSys * nn * nw) : nullptr;
-    if ((Badd && !dBadd) || !dF || !dX || (!reg && !dA) || (Z && !dZ)) FAIL(c, "solve_dense_resident: device allocation failed");
-    if (Badd) H2D(c, dBadd, Badd, (size_t)nSys * nn * sizeof(double));
-    H2D(c, dF, F, nf * sizeof(cplx));
-    HIPCHK(c, hipEventRecord(c->ev0, c->stream));
+    double *dBadd = sc.in<double>(Badd, (size_t)nSys * nn);
+    cplx *dF = sc.in<cplx>(F, nf), *dX = sc.out<cplx>(Xi, nf), *dZ = sc.out<cplx>(Z, (size_t)nSys * nn * nw);
+    cplx *dA = reg ? nullptr : sc.tmp<cplx>((size_t)nSys * nw * n * (n + nRhs));
+    if (int rc = sc.upload("solve_dense_resident")) return rc;
+    if (sc.begin()) return -2;
     if (dense_launch(c, nSys, nPer, n, nRhs, nw, R.w, R.M, R.B, R.C, R.freq_mask, dBadd, dF, dX, dZ, dA)) return -1;
-    if (finish_timed(c)) return -2;
-    D2H(c, Xi, dX, nf * sizeof(cplx));
-    if (Z) D2H(c, Z, dZ, (size_t)nSys * nn * nw * sizeof(cplx));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return 0;
+    return sc.finish();
 }
 
 // include/raftx.h raftx_flex_start: the next raftx_flex_solve starts from this iterate (one-shot)
@@ -2768,19 +2706,19 @@ extern "C" int raftx_flex_solve(raftx_ctx *c, int nUnit, const int64_t *nodeOff,
     std::vector<int> hNodeUnit((size_t)nNode);
     for (int u = 0; u < nUnit; u++)
         for (int64_t i = nodeOff[u]; i < nodeOff[u + 1]; i++) hNodeUnit[(size_t)i] = u;
-    double *dM = sc.alloc<double>(nM), *dB = sc.alloc<double>(nB), *dC = sc.alloc<double>((size_t)nUnit * nn);
-    double *dTn = sc.alloc<double>((size_t)nNode * 6 * n), *dW = sc.alloc<double>((size_t)nCase * nNode * 6 * n);
-    double *dBn = sc.alloc<double>(npn * 36), *dBd = sc.alloc<double>((size_t)nSys * nn);
-    int64_t *dOff = sc.alloc<int64_t>((size_t)nUnit + 1);
-    int *dNodeUnit = sc.alloc<int>((size_t)nNode), *dAct = sc.alloc<int>((size_t)nSys), *dNi = sc.alloc<int>((size_t)nSys),
-        *dFl = sc.alloc<int>((size_t)nSys), *dCount = sc.alloc<int>(1);
-    cplx *dXiN = sc.alloc<cplx>(npn * 6 * nw), *dFn = sc.alloc<cplx>(npn * nHead * 6 * nw);
-    cplx *dFlin = sc.alloc<cplx>((size_t)nSys * nHead * nxs), *dFw = sc.alloc<cplx>((size_t)nSys * nHead * nxs);
-    cplx *dFd = sc.alloc<cplx>((size_t)nSys * nHead * nxs), *dRhs = sc.alloc<cplx>((size_t)nSys * nxs);
-    cplx *dXnew = sc.alloc<cplx>((size_t)nSys * nxs), *dXi = sc.alloc<cplx>((size_t)nSys * nxs), *dXl = sc.alloc<cplx>((size_t)nSys * nxs);
-    cplx *dXh = sc.alloc<cplx>((size_t)nSys * nHead * nxs);
-    cplx *dA = (reg1 && regH) ? nullptr : sc.alloc<cplx>((size_t)nSys * nw * n * (n + nHead));
-    cplx *dZ = Z ? sc.alloc<cplx>((size_t)nSys * nn * nw) : nullptr;
+    double *dM = sc.tmp<double>(nM), *dB = sc.tmp<double>(nB), *dC = sc.tmp<double>((size_t)nUnit * nn);
+    double *dTn = sc.tmp<double>((size_t)nNode * 6 * n), *dW = sc.tmp<double>((size_t)nCase * nNode * 6 * n);
+    double *dBn = sc.tmp<double>(npn * 36), *dBd = sc.tmp<double>((size_t)nSys * nn);
+    int64_t *dOff = sc.tmp<int64_t>((size_t)nUnit + 1);
+    int *dNodeUnit = sc.tmp<int>((size_t)nNode), *dAct = sc.tmp<int>((size_t)nSys), *dNi = sc.tmp<int>((size_t)nSys),
+        *dFl = sc.tmp<int>((size_t)nSys), *dCount = sc.tmp<int>(1);
+    cplx *dXiN = sc.tmp<cplx>(npn * 6 * nw), *dFn = sc.tmp<cplx>(npn * nHead * 6 * nw);
+    cplx *dFlin = sc.tmp<cplx>((size_t)nSys * nHead * nxs), *dFw = sc.tmp<cplx>((size_t)nSys * nHead * nxs);
+    cplx *dFd = sc.tmp<cplx>((size_t)nSys * nHead * nxs), *dRhs = sc.tmp<cplx>((size_t)nSys * nxs);
+    cplx *dXnew = sc.tmp<cplx>((size_t)nSys * nxs), *dXi = sc.tmp<cplx>((size_t)nSys * nxs), *dXl = sc.tmp<cplx>((size_t)nSys * nxs);
+    cplx *dXh = sc.tmp<cplx>((size_t)nSys * nHead * nxs);
+    cplx *dA = (reg1 && regH) ? nullptr : sc.tmp<cplx>((size_t)nSys * nw * n * (n + nHead));
+    cplx *dZ = Z ? sc.tmp<cplx>((size_t)nSys * nn * nw) : nullptr;
     if (!dM || !dB || !dC || !dTn || !dW || !dBn || !dBd || !dOff || !dNodeUnit || !dAct || !dNi || !dFl || !dCount || !dXiN || !dFn ||
         !dFlin || !dFw || !dFd || !dRhs || !dXnew || !dXi || !dXl || !dXh || (!(reg1 && regH) && !dA) || (Z && !dZ))
         FAIL(c, "flex_solve: device allocation failed");
@@ -2816,7 +2754,7 @@ extern "C" int raftx_flex_solve(raftx_ctx *c, int nUnit, const int64_t *nodeOff,
     const int nt = (n + 15) / 16;
     const dim3 gridB((unsigned)((nt * nt + 3) / 4), (unsigned)nSys), gridF((unsigned)((nxs + 255) / 256), (unsigned)(nSys * nHead));
     volatile int *hCount = reinterpret_cast<volatile int *>(c->pin.p);
-    int *dIter = sc.alloc<int>(1);
+    int *dIter = sc.tmp<int>(1);
     if (!dIter) FAIL(c, "flex_solve: device allocation failed");
     HIPCHK(c, hipMemsetAsync(dIter, 0, sizeof(int), c->stream));
     // one iteration: node motions -> linearisation of every (node, sea state) -> projections with the units' T -> dense solves ->
@@ -2899,44 +2837,31 @@ extern "C" int raftx_solve_system_resident(raftx_ctx *c, int nUnit, const double
     HIPCHK(c, hipSetDevice(c->device));
     const int nGroup = T.nDesign / nUnit, nSys = nGroup * T.nCase, n = 6 * nUnit, nRhs = T.nHead, nw = T.nw;
     size_t lds = 0;
-    const int nbin = solve_system_shape(n, nRhs, &lds);
+    solve_system_shape(n, nRhs, &lds);
     if (lds > 150 * 1024) FAIL(c, "solve_system: %d DOFs x %d rhs does not fit the LDS-resident solver", n, nRhs);
     Scratch sc(c);
-    size_t nf = (size_t)nSys * nRhs * n * nw, nc = (size_t)nGroup * n * n;
-    cplx *dX = sc.alloc<cplx>(nf);
-    double *dM = Mc ? sc.alloc<double>(nc) : nullptr, *dB = Bc ? sc.alloc<double>(nc) : nullptr,
-           *dC = Cc ? sc.alloc<double>(nc) : nullptr;
-    if (nSys && (!dX || (Mc && !dM) || (Bc && !dB) || (Cc && !dC))) FAIL(c, "solve_system_resident: device allocation failed");
-    if (dM) H2D(c, dM, Mc, nc * sizeof(double));
-    if (dB) H2D(c, dB, Bc, nc * sizeof(double));
-    if (dC) H2D(c, dC, Cc, nc * sizeof(double));
-    const cplx *Zsrc = c->rZ;
+    const size_t nc = (size_t)nGroup * n * n;
     const bool rows = solve_system_rows_ok(nUnit, nRhs);
-    if (assemble && !rows && nSys) {                     // no register-resident solver for this shape: materialise Z once
-        const size_t nz = (size_t)T.nDesign * T.nCase * 36 * nw;
-        cplx *dZ = sc.alloc<cplx>(nz);
-        if (!dZ) FAIL(c, "solve_system_resident: device allocation failed");
+    double *dM = sc.in<double>(Mc, nc), *dB = sc.in<double>(Bc, nc), *dC = sc.in<double>(Cc, nc);
+    cplx *dX = sc.out<cplx>(Xi, (size_t)nSys * nRhs * n * nw);
+    const size_t nz = assemble && !rows && nSys ? (size_t)T.nDesign * T.nCase * 36 * nw : 0;
+    cplx *dZ = sc.tmp<cplx>(nz);
+    if (int rc = sc.upload("solve_system_resident")) return rc;
+    const cplx *Zsrc = c->rZ;
+    if (dZ) {                                            // no register-resident solver for this shape: materialise Z once
         hipLaunchKernelGGL(k_assemble_unit_z, dim3((unsigned)((nz + 255) / 256)), dim3(256), 0, c->stream, T.nDesign * T.nCase, T.nCase, nw,
                            T.w, T.M0, T.B0, T.C0, c->rB, dZ);
         Zsrc = dZ;
     }
-    HIPCHK(c, hipEventRecord(c->ev0, c->stream));
+    if (sc.begin()) return -2;
     bool done = !nSys;
     if (!done && rows)
         done = assemble ? launch_solve_system_rows<true, true>(c->stream, nSys, nUnit, nRhs, nw, T.nCase, T.w, nullptr, dM, dB, dC, c->rFw, dX,
                                                                T.M0, T.B0, T.C0, c->rB)
                         : launch_solve_system_rows<true>(c->stream, nSys, nUnit, nRhs, nw, T.nCase, T.w, c->rZ, dM, dB, dC, c->rFw, dX);
-    if (!done) {
-        if (lds > 64 * 1024)
-            HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void *>(k_solve_system<true>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(k_solve_system<true>, dim3((unsigned)((size_t)nSys * ((nw + nbin - 1) / nbin))), dim3(64 * nbin), lds,
-                           c->stream, nSys, nUnit, nRhs, nw, T.nCase, T.w, Zsrc, dM, dB, dC, c->rFw, dX);
-    }
-    if (finish_timed(c)) return -2;
-    if (nSys) D2H(c, Xi, dX, nf * sizeof(cplx));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return 0;
+    if (!done)
+        if (int rc = launch_solve_system_lds<true>(c, nSys, nUnit, nRhs, nw, T.nCase, T.w, Zsrc, dM, dB, dC, c->rFw, dX)) return rc;
+    return sc.finish();
 }
 
 extern "C" int raftx_qtf_kay(raftx_ctx *c, int nSet, int nw2, const double *w2, const double *k2, double depth, double rho,
@@ -2951,29 +2876,20 @@ extern "C" int raftx_qtf_kay(raftx_ctx *c, int nSet, int nw2, const double *w2, 
     c->kay_ready = false;
     if (grow_device(c, c->rKay, nq)) return -2;
     Scratch sc(c);
-    double *dw = sc.alloc<double>(nw2), *dk = sc.alloc<double>(nw2), *dI = sc.alloc<double>(nItem * QK_N),
-           *dB = sc.alloc<double>(nSet);
-    int64_t *dio = sc.alloc<int64_t>(nSet + 1);
-    cplx *dH = sc.alloc<cplx>(nItem * KAY_ROWS * nw2);
-    double *dq = sc.alloc<double>(nw2);
-    if (nSet && (!dw || !dk || !dB || !dio || !dq || (nItem && (!dI || !dH)))) FAIL(c, "qtf_kay: device allocation failed");
-    if (nSet) {
-        H2D(c, dw, w2, nw2 * sizeof(double));
-        H2D(c, dk, k2, nw2 * sizeof(double));
-        H2D(c, dB, beta, nSet * sizeof(double));
-        H2D(c, dio, itemOff, (nSet + 1) * sizeof(int64_t));
-        if (nItem) H2D(c, dI, items, nItem * QK_N * sizeof(double));
-        HIPCHK(c, hipMemsetAsync(c->rKay.p, 0, nq * sizeof(cplx), c->stream));       // lower triangle stays zero
-    }
-    HIPCHK(c, hipEventRecord(c->ev0, c->stream));
+    double *dw = sc.in<double>(w2, nw2), *dk = sc.in<double>(k2, nw2), *dB = sc.in<double>(beta, nSet);
+    int64_t *dio = sc.in<int64_t>(itemOff, (size_t)nSet + 1);
+    double *dI = sc.in<double>(items, nItem * QK_N), *dq = sc.tmp<double>(nw2);
+    cplx *dH = sc.tmp<cplx>(nItem * KAY_ROWS * nw2);
+    sc.out_from(kay_out, c->rKay.p, nq);
+    if (int rc = sc.upload("qtf_kay")) return rc;
+    if (nSet) HIPCHK(c, hipMemsetAsync(c->rKay.p, 0, nq * sizeof(cplx), c->stream));       // lower triangle stays zero
+    if (sc.begin()) return -2;
     if (nSet) {
         if (nItem) hipLaunchKernelGGL(k_kay_tables, dim3((unsigned)nItem), dim3(128), 0, c->stream, nw2, Nm + 2, nSet, depth, dk, dio, dI, dB, dH, dq);
         if (nItem) hipLaunchKernelGGL(k_kay_pairs, dim3((unsigned)((size_t)nSet * nw2)), dim3(nw2 > 64 ? 128 : 64), 0, c->stream, nw2, Nm,
                                       depth, rho, g, dw, dk, dio, dI, dH, dq, c->rKay.p);
     }
-    if (finish_timed(c)) return -2;
-    if (nSet && kay_out) D2H(c, kay_out, c->rKay.p, nq * sizeof(cplx));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (int rc = sc.finish()) return rc;
     c->rKay_sets = nSet;
     c->rKay_nw2 = nw2;
     c->kay_ready = true;
@@ -3009,39 +2925,24 @@ static int qtf_slender_impl(raftx_ctx *c, int nSet, int nw2, const double *w2, c
     A.depth = depth;
     A.rho = rho;
     A.g = g;
-    double *dw = sc.alloc<double>(nw2), *dk = sc.alloc<double>(nw2), *dS = sc.alloc<double>(nStrip * QS_N),
-           *dM = sc.alloc<double>(nMem * QM_N), *dB = sc.alloc<double>(nSet), *dMs = sc.alloc<double>((size_t)nSet * 36);
-    int64_t *dso = sc.alloc<int64_t>(nSet + 1), *dmo = sc.alloc<int64_t>(nSet + 1);
-    int *dss = sc.alloc<int>(nStrip), *dms = sc.alloc<int>(nMem);
+    double *dw = sc.in<double>(w2, nw2), *dk = sc.in<double>(k2, nw2), *dS = sc.in<double>(strips, nStrip * QS_N),
+           *dM = sc.in<double>(members, nMem * QM_N), *dB = sc.in<double>(beta, nSet), *dMs = sc.in<double>(Mstruc, (size_t)nSet * 36);
+    int64_t *dso = sc.in<int64_t>(stripOff, (size_t)nSet + 1), *dmo = sc.in<int64_t>(memOff, (size_t)nSet + 1);
+    int *dss = sc.in<int>(sset.data(), nStrip), *dms = sc.in<int>(mset.data(), nMem);
     const bool use_resident_kay = !kay && c->kay_ready && c->rKay_sets == nSet && c->rKay_nw2 == nw2;
     c->kay_ready = false;                                // one-shot: a table never outlives the call it was made for
-    cplx *dXi = sc.alloc<cplx>((size_t)nSet * 6 * nw2), *dK = kay ? sc.alloc<cplx>(nq) : (use_resident_kay ? c->rKay.p : nullptr);
-    cplx *dT = sc.alloc<cplx>(nStrip * QT_N * nw2), *dTM = sc.alloc<cplx>(nMem * QTM_N * nw2),
-         *dTS = sc.alloc<cplx>((size_t)nSet * QTS_N * nw2);
-    double *dD = sc.alloc<double>(nStrip * QD_N);
-    cplx *dTA = sc.alloc<cplx>(nStrip * QT_N * nw2);
+    const size_t nXi = (size_t)nSet * 6 * nw2;           // the motion RAOs: the caller's, or k_rao_to_grid's below
+    cplx *dXi = Xi ? sc.in<cplx>(Xi, nXi) : sc.tmp<cplx>(nXi), *dK = kay ? sc.in<cplx>(kay, nq) : (use_resident_kay ? c->rKay.p : nullptr);
+    cplx *dT = sc.tmp<cplx>(nStrip * QT_N * nw2), *dTM = sc.tmp<cplx>(nMem * QTM_N * nw2), *dTS = sc.tmp<cplx>((size_t)nSet * QTS_N * nw2);
+    double *dD = sc.tmp<double>(nStrip * QD_N);
+    cplx *dTA = sc.tmp<cplx>(nStrip * QT_N * nw2);
     // the result stays resident (raftx_qtf_force can reuse it)
     if (grow_device(c, c->rQtf, nq)) return -2;
     c->rQtf_sets = nSet;
     c->rQtf_nw2 = nw2;
     cplx *dQ = c->rQtf.p;
-    if (nSet && (!dw || !dk || (nStrip && (!dS || !dss || !dT || !dD || !dTA)) || (nMem && (!dM || !dms || !dTM)) || !dB || !dMs || !dso ||
-                 !dmo || !dXi || (kay && !dK) || !dTS || !dQ))
-        FAIL(c, "qtf_slender: device allocation failed");
-    if (nSet) {
-        H2D(c, dw, w2, nw2 * sizeof(double));
-        H2D(c, dk, k2, nw2 * sizeof(double));
-        if (nStrip) H2D(c, dS, strips, nStrip * QS_N * sizeof(double));
-        if (nMem) H2D(c, dM, members, nMem * QM_N * sizeof(double));
-        H2D(c, dB, beta, nSet * sizeof(double));
-        H2D(c, dMs, Mstruc, (size_t)nSet * 36 * sizeof(double));
-        H2D(c, dso, stripOff, (nSet + 1) * sizeof(int64_t));
-        H2D(c, dmo, memOff, (nSet + 1) * sizeof(int64_t));
-        if (nStrip) H2D(c, dss, sset.data(), nStrip * sizeof(int));
-        if (nMem) H2D(c, dms, mset.data(), nMem * sizeof(int));
-        if (Xi) H2D(c, dXi, Xi, (size_t)nSet * 6 * nw2 * sizeof(cplx));
-        if (kay) H2D(c, dK, kay, nq * sizeof(cplx));
-    }
+    sc.out_from(qtf, dQ, nq);
+    if (int rc = sc.upload("qtf_slender")) return rc;
     A.w = dw; A.k = dk; A.soff = dso; A.strips = dS; A.moff = dmo; A.members = dM; A.sset = dss; A.mset = dms;
     A.srec = A.mrec = nullptr;                           // one table per set
     A.Xi = dXi; A.beta = dB; A.Ms = dMs; A.kay = dK; A.T = dT; A.TA = dTA; A.D = dD; A.TM = dTM; A.TS = dTS; A.qtf = dQ;
@@ -3050,7 +2951,7 @@ static int qtf_slender_impl(raftx_ctx *c, int nSet, int nw2, const double *w2, c
     A.nrow = (nw2 - row_off + row_stride - 1) / row_stride;           // rows w1 = row_off + m*row_stride of this call
     if (A.nrow < 0) A.nrow = 0;
     if (nSet && row_stride > 1) HIPCHK(c, hipMemsetAsync(dQ, 0, nq * sizeof(cplx), c->stream));   // other ranks' rows stay 0
-    HIPCHK(c, hipEventRecord(c->ev0, c->stream));
+    if (sc.begin()) return -2;
     if (nSet && !Xi)                                     // motion RAOs straight from the resident first-order responses
         hipLaunchKernelGGL(k_rao_to_grid, dim3((unsigned)((size_t)nSet * 6)), dim3(128), 0, c->stream, c->T.nCase, c->T.nHead,
                            c->T.nw, nw2, c->T.w, c->T.zeta, dw, c->rXi, dXi);
@@ -3064,10 +2965,7 @@ static int qtf_slender_impl(raftx_ctx *c, int nSet, int nw2, const double *w2, c
             hipLaunchKernelGGL(k_qtf_pairs, dim3((unsigned)(per_xcd * 8)), dim3(blk), 0, c->stream, A);
         }
     }
-    if (finish_timed(c)) return -2;
-    if (nSet && qtf) D2H(c, qtf, dQ, nq * sizeof(cplx));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return 0;
+    return sc.finish();
 }
 
 extern "C" int raftx_qtf_slender(raftx_ctx *c, int nSet, int nw2, const double *w2, const double *k2, double depth,
@@ -3096,37 +2994,18 @@ extern "C" int raftx_qtf_force(raftx_ctx *c, int nSet, int nw2, const double *w2
     HIPCHK(c, hipSetDevice(c->device));
     const size_t nq = (size_t)nSet * nw2 * nw2 * 6;
     Scratch sc(c);
-    const cplx *dQ = nullptr;
-    if (qtf) {
-        cplx *t = sc.alloc<cplx>(nq);
-        if (nq && !t) FAIL(c, "qtf_force: device allocation failed");
-        if (nq) H2D(c, t, qtf, nq * sizeof(cplx));
-        dQ = t;
-    } else {
-        if (!c->rQtf.p || c->rQtf_sets != nSet || c->rQtf_nw2 != nw2)
-            FAIL(c, "qtf_force: no resident QTFs of this shape (run raftx_qtf_slender first or pass qtf)");
-        dQ = c->rQtf.p;
-    }
-    double *dw2 = sc.alloc<double>(nw2), *dwv = sc.alloc<double>(nw), *dS = sc.alloc<double>((size_t)nSet * nw),
-           *dfm = sc.alloc<double>((size_t)nSet * 6), *df = sc.alloc<double>((size_t)nSet * 6 * nw);
-    if (nSet && (!dw2 || !dwv || !dS || !dfm || !df)) FAIL(c, "qtf_force: device allocation failed");
-    if (nSet) {
-        H2D(c, dw2, w2, nw2 * sizeof(double));
-        H2D(c, dwv, w, nw * sizeof(double));
-        H2D(c, dS, S0, (size_t)nSet * nw * sizeof(double));
-    }
-    HIPCHK(c, hipEventRecord(c->ev0, c->stream));
+    if (!qtf && (!c->rQtf.p || c->rQtf_sets != nSet || c->rQtf_nw2 != nw2))
+        FAIL(c, "qtf_force: no resident QTFs of this shape (run raftx_qtf_slender first or pass qtf)");
+    const cplx *dQ = qtf ? sc.in<cplx>(qtf, nq) : c->rQtf.p;
+    double *dw2 = sc.in<double>(w2, nw2), *dwv = sc.in<double>(w, nw), *dS = sc.in<double>(S0, (size_t)nSet * nw),
+           *dfm = sc.out<double>(f_mean, (size_t)nSet * 6), *df = sc.out<double>(f, (size_t)nSet * 6 * nw);
+    if (int rc = sc.upload("qtf_force")) return rc;
+    if (sc.begin()) return -2;
     if (nSet) {
         hipLaunchKernelGGL(k_qtf_force, dim3((unsigned)(nSet * 6)), dim3(256), lds, c->stream, nSet, nw2, dw2, dQ, nw, dwv, dw,
                            dS, dfm, df);
     }
-    if (finish_timed(c)) return -2;
-    if (nSet) {
-        D2H(c, f_mean, dfm, (size_t)nSet * 6 * sizeof(double));
-        D2H(c, f, df, (size_t)nSet * 6 * nw * sizeof(double));
-    }
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return 0;
+    return sc.finish();
 }
 
 // ------------------------------------------------------------------ one-call sweep crossing
@@ -3589,23 +3468,18 @@ extern "C" int raftx_expand_variants(raftx_ctx *c, int nDesign, const double *pa
     if (!nDesign) return 0;
     HIPCHK(c, hipSetDevice(c->device));
     Scratch sc(c);
-    double *dp = sc.alloc<double>((size_t)nDesign * std::max(P.nP, 1)), *dg = sc.alloc<double>((size_t)nDesign * P.nM * RAFTX_GM_N),
-           *ds_ = sc.alloc<double>((size_t)nDesign * std::max(P.nSt, 1) * RAFTX_GS_N),
-           *dc = sc.alloc<double>((size_t)nDesign * std::max(P.nCap, 1) * RAFTX_GC_N);
-    if (!dp || !dg || !ds_ || !dc) FAIL(c, "expand_variants: device allocation failed");
-    if (P.nP) H2D(c, dp, params, (size_t)nDesign * P.nP * sizeof(double));
+    const size_t nc = (size_t)nDesign * P.nCap * RAFTX_GC_N;
+    double *dp = sc.in<double>(params, (size_t)nDesign * P.nP), *dg = sc.out<double>(members, (size_t)nDesign * P.nM * RAFTX_GM_N),
+           *ds_ = sc.out<double>(stations, (size_t)nDesign * P.nSt * RAFTX_GS_N),
+           *dc = caps ? sc.out<double>(caps, nc) : sc.tmp<double>(nc);        // (the kernel writes the caps whether they are asked for or not)
+    if (int rc = sc.upload("expand_variants")) return rc;
     ExpandArgs E;
     memset(&E, 0, sizeof(E));
     E.params = dp;
     expand_args(P, nDesign, dg, ds_, dc, E);
-    HIPCHK(c, hipEventRecord(c->ev0, c->stream));
+    if (sc.begin()) return -2;
     launch_expand(E, c->stream);
-    if (finish_timed(c)) return -2;
-    D2H(c, members, dg, (size_t)nDesign * P.nM * RAFTX_GM_N * sizeof(double));
-    if (P.nSt) D2H(c, stations, ds_, (size_t)nDesign * P.nSt * RAFTX_GS_N * sizeof(double));
-    if (caps && P.nCap) D2H(c, caps, dc, (size_t)nDesign * P.nCap * RAFTX_GC_N * sizeof(double));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return 0;
+    return sc.finish();
 }
 extern "C" int raftx_sweep_prepare_variants(raftx_ctx *c, int slot, int nDesign, const double *params, const double *pose, double rho,
                                            double g, int add_mask, const double *M0, const double *B0, const double *C0,
@@ -3652,15 +3526,16 @@ static int qtfgen_run(raftx_ctx *c, Scratch &sc, const char *who, int nDesign, i
     memset(&A, 0, sizeof(A));
     A.nDesign = nDesign; A.nMember = nMember; A.memberOff = dMemberOff; A.stationOff = dStationOff;
     A.gm = dgm; A.gs = dgs; A.pose = dpose;
-    A.mdesign = sc.alloc<int>((size_t)nMember); A.mpose = sc.alloc<double>((size_t)nMember * QG_MP_N);
-    A.mcnt = sc.alloc<int>((size_t)nMember * QG_CNT_N); A.mcand = sc.alloc<int>((size_t)nMember);
-    A.dtot = sc.alloc<int>((size_t)std::max(nDesign, 1) * QG_CNT_N); A.err = sc.alloc<int>(1);
+    const size_t ntot = (size_t)std::max(nDesign, 1) * QG_CNT_N;
+    A.mdesign = sc.tmp<int>((size_t)nMember); A.mpose = sc.tmp<double>((size_t)nMember * QG_MP_N);
+    A.mcnt = sc.tmp<int>((size_t)nMember * QG_CNT_N); A.mcand = sc.tmp<int>((size_t)nMember);
+    A.dtot = sc.tmp<int>(ntot); A.err = sc.tmp<int>(1);
     if (pool_alloc(c, Q.allocs, QG_CNT_N * nD1, &Q.dOff)) return -2;
     A.off = Q.dOff;
-    if (!A.dtot || !A.err || (nMember && (!A.mdesign || !A.mpose || !A.mcnt || !A.mcand))) FAIL(c, "%s: device allocation failed", who);
+    if (int rc = sc.upload(who)) return rc;           // (the caller's arrays are on their way already: nothing new to send)
     HIPCHK(c, hipMemsetAsync(A.err, 0, sizeof(int), c->stream));
-    HIPCHK(c, hipMemsetAsync(A.dtot, 0, (size_t)std::max(nDesign, 1) * QG_CNT_N * sizeof(int), c->stream));
-    HIPCHK(c, hipEventRecord(c->ev0, c->stream));
+    HIPCHK(c, hipMemsetAsync(A.dtot, 0, ntot * sizeof(int), c->stream));
+    if (sc.begin()) return -2;
     const int64_t nThread = std::max<int64_t>(nMember, nDesign);
     if (nThread) hipLaunchKernelGGL(k_qtfgen_member, dim3((unsigned)((nThread + 127) / 128)), dim3(128), 0, c->stream, A);
     if (nDesign) hipLaunchKernelGGL(k_qtfgen_design, dim3((unsigned)((nDesign + 255) / 256)), dim3(256), 0, c->stream, A);
@@ -3713,15 +3588,10 @@ extern "C" int raftx_qtf_tables_build(raftx_ctx *c, int nDesign, const int64_t *
     for (int d = 0; d <= nDesign; d++) mo[(size_t)d] = memberOff[d] - m0;
     for (int64_t m = 0; m <= nMember; m++) so[(size_t)m] = stationOff[m0 + m] - s0;
     Scratch sc(c);
-    int64_t *dmo = sc.alloc<int64_t>(mo.size()), *dso = sc.alloc<int64_t>(so.size());
-    double *dgm = sc.alloc<double>((size_t)nMember * RAFTX_GM_N), *dgs = sc.alloc<double>((size_t)nSta * RAFTX_GS_N),
-           *dps = pose ? sc.alloc<double>((size_t)nDesign * 6) : nullptr;
-    if (!dmo || !dso || (nMember && !dgm) || (nSta && !dgs) || (pose && nDesign && !dps)) FAIL(c, "qtf_tables_build: device allocation failed");
-    H2D(c, dmo, mo.data(), mo.size() * sizeof(int64_t));
-    H2D(c, dso, so.data(), so.size() * sizeof(int64_t));
-    if (nMember) H2D(c, dgm, members + (size_t)m0 * RAFTX_GM_N, (size_t)nMember * RAFTX_GM_N * sizeof(double));
-    if (nSta) H2D(c, dgs, stations + (size_t)s0 * RAFTX_GS_N, (size_t)nSta * RAFTX_GS_N * sizeof(double));
-    if (dps) H2D(c, dps, pose, (size_t)nDesign * 6 * sizeof(double));
+    int64_t *dmo = sc.in<int64_t>(mo.data(), mo.size()), *dso = sc.in<int64_t>(so.data(), so.size());
+    double *dgm = sc.in<double>(members + (size_t)m0 * RAFTX_GM_N, (size_t)nMember * RAFTX_GM_N),
+           *dgs = sc.in<double>(stations + (size_t)s0 * RAFTX_GS_N, (size_t)nSta * RAFTX_GS_N), *dps = sc.in<double>(pose, (size_t)nDesign * 6);
+    if (int rc = sc.upload("qtf_tables_build")) return rc;
     return qtfgen_run(c, sc, "qtf_tables_build", nDesign, nMember, dmo, dso, dgm, dgs, dps, stripOff_out, memOff_out);
 }
 
@@ -3742,16 +3612,11 @@ extern "C" int raftx_qtf_tables_build_variants(raftx_ctx *c, int nDesign, const 
         for (int m = 0; m < P.nM; m++) so[(size_t)d * P.nM + m] = (int64_t)d * P.nSt + P.hS[(size_t)m];
     so[(size_t)nMember] = nSta;
     Scratch sc(c);
-    int64_t *dmo = sc.alloc<int64_t>(mo.size()), *dso = sc.alloc<int64_t>(so.size());
-    double *dp = sc.alloc<double>((size_t)nDesign * std::max(P.nP, 1)), *dgm = sc.alloc<double>((size_t)nMember * RAFTX_GM_N),
-           *dgs = sc.alloc<double>((size_t)std::max<int64_t>(nSta, 1) * RAFTX_GS_N),
-           *dgc = sc.alloc<double>((size_t)nDesign * std::max(P.nCap, 1) * RAFTX_GC_N),
-           *dps = pose ? sc.alloc<double>((size_t)nDesign * 6) : nullptr;
-    if (!dmo || !dso || (nDesign && (!dp || !dgm || !dgs || !dgc || (pose && !dps)))) FAIL(c, "qtf_tables_build_variants: device allocation failed");
-    H2D(c, dmo, mo.data(), mo.size() * sizeof(int64_t));
-    H2D(c, dso, so.data(), so.size() * sizeof(int64_t));
-    if (nDesign && P.nP) H2D(c, dp, params, (size_t)nDesign * P.nP * sizeof(double));
-    if (dps && nDesign) H2D(c, dps, pose, (size_t)nDesign * 6 * sizeof(double));
+    int64_t *dmo = sc.in<int64_t>(mo.data(), mo.size()), *dso = sc.in<int64_t>(so.data(), so.size());
+    double *dp = sc.in<double>(params, (size_t)nDesign * P.nP), *dps = sc.in<double>(pose, (size_t)nDesign * 6);
+    double *dgm = sc.tmp<double>((size_t)nMember * RAFTX_GM_N), *dgs = sc.tmp<double>((size_t)nSta * RAFTX_GS_N),
+           *dgc = sc.tmp<double>((size_t)nDesign * P.nCap * RAFTX_GC_N);
+    if (int rc = sc.upload("qtf_tables_build_variants")) return rc;
     if (nDesign) {
         ExpandArgs E;
         memset(&E, 0, sizeof(E));
@@ -3759,8 +3624,7 @@ extern "C" int raftx_qtf_tables_build_variants(raftx_ctx *c, int nDesign, const 
         expand_args(P, nDesign, dgm, dgs, dgc, E);
         launch_expand(E, c->stream);
     }
-    return qtfgen_run(c, sc, "qtf_tables_build_variants", nDesign, nMember, dmo, dso, dgm, dgs, nDesign ? dps : nullptr, stripOff_out,
-                      memOff_out);
+    return qtfgen_run(c, sc, "qtf_tables_build_variants", nDesign, nMember, dmo, dso, dgm, dgs, dps, stripOff_out, memOff_out);
 }
 
 extern "C" int raftx_qtf_tables_counts(raftx_ctx *c, int64_t *counts) {
@@ -3807,15 +3671,11 @@ extern "C" int raftx_qtf_tables_kay_items(raftx_ctx *c, int nCase, const double 
     }
     if (!items || !nItem) return 0;
     Scratch sc(c);
-    double *dB = sc.alloc<double>(nCase), *dI = sc.alloc<double>(nItem * QK_N);
-    if (!dB || !dI) FAIL(c, "qtf_tables_kay_items: device allocation failed");
-    H2D(c, dB, beta, nCase * sizeof(double));
-    HIPCHK(c, hipEventRecord(c->ev0, c->stream));
+    double *dB = sc.in<double>(beta, nCase), *dI = sc.out<double>(items, nItem * QK_N);
+    if (int rc = sc.upload("qtf_tables_kay_items")) return rc;
+    if (sc.begin()) return -2;
     hipLaunchKernelGGL(k_qtfgen_kay_items, dim3((unsigned)nSet), dim3(64), 0, c->stream, nCase, Q.nDesign, dB, Q.dOff, Q.kay, dI);
-    if (finish_timed(c)) return -2;
-    D2H(c, items, dI, nItem * QK_N * sizeof(double));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return 0;
+    return sc.finish();
 }
 
 extern "C" int raftx_qtf_slender_resident(raftx_ctx *c, int nCase, int nw2, const double *w2, const double *k2, double depth,
@@ -3849,18 +3709,18 @@ extern "C" int raftx_qtf_slender_resident(raftx_ctx *c, int nCase, int nw2, cons
     Scratch sc(c);
     QtfArgs A;
     A.nSet = (int)nSet; A.nw = nw2; A.depth = depth; A.rho = rho; A.g = g;
-    double *dw = sc.alloc<double>(nw2), *dk = sc.alloc<double>(nw2), *dB = sc.alloc<double>(nSet), *dMs = sc.alloc<double>(nSet * 36),
-           *dBc = sc.alloc<double>(nCase);
-    int64_t *dso = sc.alloc<int64_t>(nSet + 1), *dmo = sc.alloc<int64_t>(nSet + 1), *dio = sc.alloc<int64_t>(nSet + 1);
-    int *dss = sc.alloc<int>(nStrip), *dsr = sc.alloc<int>(nStrip), *dms = sc.alloc<int>(nMem), *dmr = sc.alloc<int>(nMem);
-    cplx *dXi = sc.alloc<cplx>(nSet * 6 * nw2);
-    cplx *dT = sc.alloc<cplx>(nStrip * QT_N * nw2), *dTM = sc.alloc<cplx>(nMem * QTM_N * nw2), *dTS = sc.alloc<cplx>(nSet * QTS_N * nw2);
-    double *dD = sc.alloc<double>(nStrip * QD_N);
-    cplx *dTA = sc.alloc<cplx>(nStrip * QT_N * nw2);
-    double *dI = sc.alloc<double>(nItem * QK_N), *dq = sc.alloc<double>(nw2);
-    cplx *dH = sc.alloc<cplx>(nItem * KAY_ROWS * nw2);
-    bool ok = !nSet || (dw && dk && dB && dMs && dBc && dso && dmo && dio && dXi && dTS && dq && (!nStrip || (dss && dsr && dT && dD && dTA)) &&
-                        (!nMem || (dms && dmr && dTM)) && (!nItem || (dI && dH)));
+    double *dw = sc.in<double>(w2, nw2), *dk = sc.in<double>(k2, nw2), *dB = sc.in<double>(hB.data(), nSet), *dBc = sc.in<double>(beta, nCase),
+           *dMs = sc.in<double>(hMs.data(), nSet * 36);
+    int64_t *dso = sc.in<int64_t>(soff.data(), nSet + 1), *dmo = sc.in<int64_t>(moff.data(), nSet + 1), *dio = sc.in<int64_t>(ioff.data(), nSet + 1);
+    const size_t nXi = nSet * 6 * nw2;                   // the motion RAOs: the caller's, or k_rao_to_grid's below
+    cplx *dXi = Xi ? sc.in<cplx>(Xi, nXi) : sc.tmp<cplx>(nXi);
+    int *dss = sc.tmp<int>(nStrip), *dsr = sc.tmp<int>(nStrip), *dms = sc.tmp<int>(nMem), *dmr = sc.tmp<int>(nMem);
+    cplx *dT = sc.tmp<cplx>(nStrip * QT_N * nw2), *dTM = sc.tmp<cplx>(nMem * QTM_N * nw2), *dTS = sc.tmp<cplx>(nSet * QTS_N * nw2);
+    double *dD = sc.tmp<double>(nStrip * QD_N);
+    cplx *dTA = sc.tmp<cplx>(nStrip * QT_N * nw2);
+    double *dI = sc.tmp<double>(nItem * QK_N), *dq = sc.tmp<double>(nw2);
+    cplx *dH = sc.tmp<cplx>(nItem * KAY_ROWS * nw2);
+    bool ok = !sc.failed;
     if (ok && nSet && grow_device(c, c->rQtf, nq)) ok = false;
     if (ok && nItem && grow_device(c, c->rKay, nq)) ok = false;
     if (!ok)
@@ -3870,22 +3730,15 @@ extern "C" int raftx_qtf_slender_resident(raftx_ctx *c, int nCase, int nw2, cons
     c->rQtf_nw2 = nw2;
     c->kay_ready = false;                                // the table below belongs to this call alone
     if (!nSet) return 0;
-    H2D(c, dw, w2, nw2 * sizeof(double));
-    H2D(c, dk, k2, nw2 * sizeof(double));
-    H2D(c, dB, hB.data(), nSet * sizeof(double));
-    H2D(c, dBc, beta, nCase * sizeof(double));
-    H2D(c, dMs, hMs.data(), nSet * 36 * sizeof(double));
-    H2D(c, dso, soff.data(), (nSet + 1) * sizeof(int64_t));
-    H2D(c, dmo, moff.data(), (nSet + 1) * sizeof(int64_t));
-    H2D(c, dio, ioff.data(), (nSet + 1) * sizeof(int64_t));
-    if (Xi) H2D(c, dXi, Xi, nSet * 6 * nw2 * sizeof(cplx));
+    sc.out_from(qtf, c->rQtf.p, nq);
+    if (int rc = sc.upload("qtf_slender_resident")) return rc;
     if (nItem) HIPCHK(c, hipMemsetAsync(c->rKay.p, 0, nq * sizeof(cplx), c->stream));       // lower triangle stays zero
     A.w = dw; A.k = dk; A.soff = dso; A.strips = Q.strips; A.moff = dmo; A.members = Q.members; A.sset = dss; A.mset = dms;
     A.srec = dsr; A.mrec = dmr;
     A.Xi = dXi; A.beta = dB; A.Ms = dMs; A.kay = nItem ? c->rKay.p : nullptr; A.T = dT; A.TA = dTA; A.D = dD; A.TM = dTM; A.TS = dTS;
     A.qtf = c->rQtf.p;
     A.row_off = 0; A.row_stride = 1; A.nrow = nw2;
-    HIPCHK(c, hipEventRecord(c->ev0, c->stream));
+    if (sc.begin()) return -2;
     hipLaunchKernelGGL(k_qtfgen_sets, dim3((unsigned)nSet), dim3(64), 0, c->stream, nCase, nDesign, Q.dOff, dss, dsr, dms, dmr);
     if (nItem) {
         hipLaunchKernelGGL(k_qtfgen_kay_items, dim3((unsigned)nSet), dim3(64), 0, c->stream, nCase, nDesign, dBc, Q.dOff, Q.kay, dI);
@@ -3903,10 +3756,7 @@ extern "C" int raftx_qtf_slender_resident(raftx_ctx *c, int nCase, int nw2, cons
         const size_t per_xcd = (nSet * A.nrow + 7) / 8;  // see k_qtf_pairs: a slab of the (set, row) list per XCD
         hipLaunchKernelGGL(k_qtf_pairs, dim3((unsigned)(per_xcd * 8)), dim3(blk), 0, c->stream, A);
     }
-    if (finish_timed(c)) return -2;
-    if (qtf) D2H(c, qtf, c->rQtf.p, nq * sizeof(cplx));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return 0;
+    return sc.finish();
 }
 
 static void launch_modal(hipStream_t st, int n, const double *M, const double *C, const double *dM, const double *dC,
@@ -3966,7 +3816,7 @@ static hipError_t channel_rows_block(raftx_ctx *sub, const SweepSlot &S, int n, 
     A.nCase = S.nCase; A.nHead = S.nHead; A.nw = S.nw; A.nChan = nChan;
     A.strideL = strideL;
     A.strideG = strideG;
-    const dim3 grid((unsigned)npair), wg(S.nw > 128 ? 256 : (S.nw > 64 ? 128 : 64));
+    const dim3 grid((unsigned)npair), wg = bin_threads(S.nw);
     if (Gw) hipLaunchKernelGGL(k_sweep_channels<true>, grid, wg, 0, st, A, (const double *)sub->T.w, (const cplx *)sub->rXi, L, Gw, land.p);
     else hipLaunchKernelGGL(k_sweep_channels<false>, grid, wg, 0, st, A, (const double *)sub->T.w, (const cplx *)sub->rXi, L, Gw, land.p);
     return hipGetLastError();
@@ -4024,7 +3874,7 @@ static int enqueue_stats(raftx_ctx *c, SweepSlot &S, size_t b, hipStream_t sDown
     hipError_t e = hipEventRecord(sub->evS0, c->stream);
     if (npair) {
         const landing::Stats land = landing::stats(npair);              // (niter and flags: one run of 2 npair ints, from niter on)
-        hipLaunchKernelGGL(k_motion_stats, dim3((unsigned)npair), dim3(nw > 128 ? 256 : (nw > 64 ? 128 : 64)), 0, c->stream,
+        hipLaunchKernelGGL(k_motion_stats, dim3((unsigned)npair), bin_threads(nw), 0, c->stream,
                            (int)npair, nHead, nw, 1.0 / S.dw, sub->rXi, sub->pinRes.p + land.sd, (double *)nullptr, (const int *)sub->rNi,
                            (const int *)sub->rFl, land.niter.in(sub->pinRes.p));
     }
@@ -4390,19 +4240,13 @@ extern "C" int raftx_sweep_generation(raftx_ctx *c, int slot, int *blocks_fused,
 static int modal_launch(raftx_ctx *c, int n, const double *M, const double *C, const double *dM, const double *dC,
                         const double *props_in, double *fn, double *modes, int32_t *flags, double *props) {
     Scratch sc(c);
-    double *dfn = sc.alloc<double>((size_t)n * 6), *dmo = sc.alloc<double>((size_t)n * 36);
-    int32_t *dfl = sc.alloc<int32_t>((size_t)n);
-    double *dpr = props_in ? sc.alloc<double>((size_t)n * RAFTX_SP_N) : nullptr;
-    if (!dfn || !dmo || !dfl || (props_in && !dpr)) FAIL(c, "modal: device allocation failed");
-    HIPCHK(c, hipEventRecord(c->ev0, c->stream));
+    double *dfn = sc.out<double>(fn, (size_t)n * 6), *dmo = sc.out<double>(modes, (size_t)n * 36);
+    int32_t *dfl = sc.out<int32_t>(flags, (size_t)n);
+    double *dpr = sc.out<double>(props, (size_t)n * RAFTX_SP_N);
+    if (int rc = sc.upload("modal")) return rc;
+    if (sc.begin()) return -2;
     launch_modal(c->stream, n, M, C, dM, dC, props_in, dpr, dfn, dmo, dfl);
-    if (finish_timed(c)) return -2;
-    D2H(c, fn, dfn, (size_t)n * 6 * sizeof(double));
-    D2H(c, modes, dmo, (size_t)n * 36 * sizeof(double));
-    D2H(c, flags, dfl, (size_t)n * sizeof(int32_t));
-    if (props) D2H(c, props, dpr, (size_t)n * RAFTX_SP_N * sizeof(double));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return 0;
+    return sc.finish();
 }
 
 extern "C" int raftx_modal_batch(raftx_ctx *c, int n, const double *M, const double *C, double *fn, double *modes,
@@ -4412,10 +4256,8 @@ extern "C" int raftx_modal_batch(raftx_ctx *c, int n, const double *M, const dou
     if (n == 0) return 0;
     HIPCHK(c, hipSetDevice(c->device));
     Scratch sc(c);
-    double *dM = sc.alloc<double>((size_t)n * 36), *dC = sc.alloc<double>((size_t)n * 36);
-    if (!dM || !dC) FAIL(c, "modal_batch: device allocation failed");
-    H2D(c, dM, M, (size_t)n * 36 * sizeof(double));
-    H2D(c, dC, C, (size_t)n * 36 * sizeof(double));
+    double *dM = sc.in<double>(M, (size_t)n * 36), *dC = sc.in<double>(C, (size_t)n * 36);
+    if (int rc = sc.upload("modal_batch")) return rc;
     return modal_launch(c, n, dM, dC, nullptr, nullptr, nullptr, fn, modes, flags, nullptr);
 }
 
@@ -4430,10 +4272,8 @@ extern "C" int raftx_modal_resident(raftx_ctx *c, const double *dM, const double
     if (n == 0) return 0;
     HIPCHK(c, hipSetDevice(c->device));
     Scratch sc(c);
-    double *ddM = dM ? sc.alloc<double>((size_t)n * 36) : nullptr, *ddC = dC ? sc.alloc<double>((size_t)n * 36) : nullptr;
-    if ((dM && !ddM) || (dC && !ddC)) FAIL(c, "modal_resident: device allocation failed");
-    if (dM) H2D(c, ddM, dM, (size_t)n * 36 * sizeof(double));
-    if (dC) H2D(c, ddC, dC, (size_t)n * 36 * sizeof(double));
+    double *ddM = sc.in<double>(dM, (size_t)n * 36), *ddC = sc.in<double>(dC, (size_t)n * 36);
+    if (int rc = sc.upload("modal_resident")) return rc;
     return modal_launch(c, n, c->T.M0, c->T.C0, ddM, ddC, props ? c->g_props : nullptr, fn, modes, flags, props);
 }
 
@@ -4494,15 +4334,11 @@ extern "C" int raftx_current_loads(raftx_ctx *c, int nCur, const double *speed, 
     if (n == 0) return 0;
     HIPCHK(c, hipSetDevice(c->device));
     Scratch sc(c);
-    double *dpar = sc.alloc<double>(host.size()), *dD = sc.alloc<double>((size_t)n * nCur * 6);
-    if (!dpar || !dD) FAIL(c, "current_loads: device allocation failed");
-    H2D(c, dpar, host.data(), host.size() * sizeof(double));
-    HIPCHK(c, hipEventRecord(c->ev0, c->stream));
+    double *dpar = sc.in<double>(host.data(), host.size()), *dD = sc.out<double>(D, (size_t)n * nCur * 6);
+    if (int rc = sc.upload("current_loads")) return rc;
+    if (sc.begin()) return -2;
     launch_current(c->stream, c->T, n, nCur, dpar, Zref ? dpar + (size_t)3 * nCur : nullptr, depth, shearExp, dD);
-    if (finish_timed(c)) return -2;
-    D2H(c, D, dD, (size_t)n * nCur * 6 * sizeof(double));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return 0;
+    return sc.finish();
 }
 
 extern "C" int raftx_sweep_current(raftx_ctx *c, int slot, int nCur, const double *speed, const double *heading_deg,
@@ -4602,31 +4438,20 @@ extern "C" int raftx_mooring_lines(raftx_ctx *c, int nDesign, int nLine, const d
     MoorArgs A;
     memset(&A, 0, sizeof(A));
     A.nDesign = nDesign; A.nLine = nLine; A.depth = depth;
-    double *dp = pose ? sc.alloc<double>((size_t)nDesign * 6) : nullptr;
-    A.lw = sc.alloc<double>(nl * MOOR_LW_N);
-    A.line_out = line_out ? sc.alloc<double>(nl * MOOR_LO_N) : nullptr;
-    A.C = C_moor ? sc.alloc<double>((size_t)nDesign * 36) : nullptr;
-    A.F = F_moor ? sc.alloc<double>((size_t)nDesign * 6) : nullptr;
-    A.T = T ? sc.alloc<double>(nl * 2) : nullptr;
-    A.J = J ? sc.alloc<double>(nl * 12) : nullptr;
-    A.flags = sc.alloc<int>((size_t)nDesign);
-    if ((pose && !dp) || !A.lw || (line_out && !A.line_out) || (C_moor && !A.C) || (F_moor && !A.F) || (T && !A.T) || (J && !A.J) || !A.flags)
-        FAIL(c, "mooring_lines: device allocation failed");
-    if (pose) H2D(c, dp, pose, (size_t)nDesign * 6 * sizeof(double));
     A.lines = L.lines;
-    A.pose = dp;
-    HIPCHK(c, hipEventRecord(c->ev0, c->stream));
+    A.pose = sc.in<double>(pose, (size_t)nDesign * 6);
+    A.lw = sc.tmp<double>(nl * MOOR_LW_N);
+    A.C = sc.out<double>(C_moor, (size_t)nDesign * 36);
+    A.F = sc.out<double>(F_moor, (size_t)nDesign * 6);
+    A.T = sc.out<double>(T, nl * 2);
+    A.J = sc.out<double>(J, nl * 12);
+    A.line_out = sc.out<double>(line_out, nl * MOOR_LO_N);
+    A.flags = sc.out<int>(flags, (size_t)nDesign);
+    if (int rc = sc.upload("mooring_lines")) return rc;
+    if (sc.begin()) return -2;
     hipLaunchKernelGGL(k_moor_line, dim3(moor_grid((long long)nl)), dim3(MOOR_THREADS), 0, c->stream, A);
     hipLaunchKernelGGL(k_moor_design, dim3(moor_grid(nDesign)), dim3(MOOR_THREADS), 0, c->stream, A);
-    if (finish_timed(c)) return -2;
-    if (C_moor) D2H(c, C_moor, A.C, (size_t)nDesign * 36 * sizeof(double));
-    if (F_moor) D2H(c, F_moor, A.F, (size_t)nDesign * 6 * sizeof(double));
-    if (T) D2H(c, T, A.T, nl * 2 * sizeof(double));
-    if (J) D2H(c, J, A.J, nl * 12 * sizeof(double));
-    if (line_out) D2H(c, line_out, A.line_out, nl * MOOR_LO_N * sizeof(double));
-    D2H(c, flags, A.flags, (size_t)nDesign * sizeof(int));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return 0;
+    return sc.finish();
 }
 
 extern "C" int raftx_mooring_program(raftx_ctx *c, int nLine, const double *lines, int nParam, const double *lineCoef,
@@ -4671,12 +4496,10 @@ extern "C" int raftx_mooring_expand(raftx_ctx *c, int nDesign, const double *par
     Scratch sc(c);
     StagedLines L;
     if (stage_lines(c, c->stream, sc.bag, (size_t)nDesign, nLine, nullptr, params, L)) return -2;
-    HIPCHK(c, hipEventRecord(c->ev0, c->stream));
+    sc.out_from(lines_out, L.expanded, (size_t)nDesign * nLine * RAFTX_ML_N);
+    if (sc.begin()) return -2;
     if (int rc = expand_lines(c, c->stream, (size_t)nDesign, nLine, L)) return rc;
-    if (finish_timed(c)) return -2;
-    D2H(c, lines_out, L.expanded, (size_t)nDesign * nLine * RAFTX_ML_N * sizeof(double));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return 0;
+    return sc.finish();
 }
 
 // ---- the mean equilibrium pose (include/raftx_statics.h, raftx_statics.h)
@@ -4722,39 +4545,25 @@ extern "C" int raftx_mean_pose(raftx_ctx *c, int nDesign, int nLine, const doubl
     if (stage_lines(c, c->stream, sc.bag, n, nLine, lines, params, L)) return -2;
     MeanPoseArgs A;
     memset(&A, 0, sizeof(A));
-    double *dK = sc.alloc<double>(n * 36), *dF0 = sc.alloc<double>(n * 6), *dFe = F_env ? sc.alloc<double>(n * 6) : nullptr;
-    double *dxr = x_ref ? sc.alloc<double>(n * 6) : nullptr;
-    A.lw = sc.alloc<double>(nl * MOOR_LW_N);
-    A.pose = pose ? sc.alloc<double>(n * 6) : nullptr;
-    A.C = C_moor ? sc.alloc<double>(n * 36) : nullptr;
-    A.F = F_moor ? sc.alloc<double>(n * 6) : nullptr;
-    A.T = T ? sc.alloc<double>(nl * 2) : nullptr;
-    A.J = J ? sc.alloc<double>(nl * 12) : nullptr;
-    A.Fres = F_res ? sc.alloc<double>(n * 6) : nullptr;
-    A.iterations = iterations ? sc.alloc<int>(n) : nullptr;
-    A.flags = sc.alloc<int>(n);
-    if (!dK || !dF0 || (F_env && !dFe) || (x_ref && !dxr) || !A.lw || (pose && !A.pose) || (C_moor && !A.C) || (F_moor && !A.F) ||
-        (T && !A.T) || (J && !A.J) || (F_res && !A.Fres) || (iterations && !A.iterations) || !A.flags)
-        FAIL(c, "mean_pose: device allocation failed");
-    H2D(c, dK, K_hs, n * 36 * sizeof(double));
-    H2D(c, dF0, F0, n * 6 * sizeof(double));
-    if (F_env) H2D(c, dFe, F_env, n * 6 * sizeof(double));
-    if (x_ref) H2D(c, dxr, x_ref, n * 6 * sizeof(double));
-    A.lines = L.lines; A.K_hs = dK; A.F0 = dF0; A.F_env = dFe; A.x_ref = dxr;
-    HIPCHK(c, hipEventRecord(c->ev0, c->stream));
+    A.lines = L.lines;
+    A.K_hs = sc.in<double>(K_hs, n * 36);
+    A.F0 = sc.in<double>(F0, n * 6);
+    A.F_env = sc.in<double>(F_env, n * 6);
+    A.x_ref = sc.in<double>(x_ref, n * 6);
+    A.lw = sc.tmp<double>(nl * MOOR_LW_N);
+    A.pose = sc.out<double>(pose, n * 6);
+    A.C = sc.out<double>(C_moor, n * 36);
+    A.F = sc.out<double>(F_moor, n * 6);
+    A.T = sc.out<double>(T, nl * 2);
+    A.J = sc.out<double>(J, nl * 12);
+    A.Fres = sc.out<double>(F_res, n * 6);
+    A.iterations = sc.out<int>(iterations, n);
+    A.flags = sc.out<int>(flags, n);
+    if (int rc = sc.upload("mean_pose")) return rc;
+    if (sc.begin()) return -2;
     if (int rc = expand_lines(c, c->stream, n, nLine, L)) return rc;   // (inside the timed window, as raftx_mooring_expand)
     launch_mean_pose(c->stream, A, nDesign, nLine, depth, tolT, tolR, max_iter);
-    if (finish_timed(c)) return -2;
-    if (pose) D2H(c, pose, A.pose, n * 6 * sizeof(double));
-    if (C_moor) D2H(c, C_moor, A.C, n * 36 * sizeof(double));
-    if (F_moor) D2H(c, F_moor, A.F, n * 6 * sizeof(double));
-    if (T) D2H(c, T, A.T, nl * 2 * sizeof(double));
-    if (J) D2H(c, J, A.J, nl * 12 * sizeof(double));
-    if (F_res) D2H(c, F_res, A.Fres, n * 6 * sizeof(double));
-    if (iterations) D2H(c, iterations, A.iterations, n * sizeof(int));
-    D2H(c, flags, A.flags, n * sizeof(int));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return 0;
+    return sc.finish();
 }
 
 extern "C" int raftx_sweep_mooring(raftx_ctx *c, int slot, int nLine, const double *lines, int add_stiffness, double *C_moor,
@@ -5078,7 +4887,7 @@ extern "C" int raftx_comm_broadcast(raftx_ctx *c, void *buf, size_t bytes, int r
     char *d = nullptr;
     COMM_LOCAL(rc, !buf && bytes, "comm_broadcast: buf is NULL");
     if (!rc && bytes) {
-        d = sc.alloc<char>(bytes);
+        d = sc.tmp<char>(bytes);
         COMM_LOCAL(rc, !d, "comm_broadcast: device allocation failed");
     }
     if (int a = comm_agree(c, R, rc)) return a;
@@ -5106,7 +4915,7 @@ static int gather_rows_dev(raftx_ctx *c, RcclApi *R, const void *dsend, const in
     if (!rc && me == root) {
         COMM_LOCAL(rc, !recv_host && total, "comm_gather: recv is NULL on root");
         if (!rc && total) {
-            dall = sc.alloc<char>(total * row_bytes);
+            dall = sc.tmp<char>(total * row_bytes);
             COMM_LOCAL(rc, !dall, "comm_gather: device allocation failed");
         }
     }
@@ -5154,7 +4963,7 @@ extern "C" int raftx_comm_gather_rows(raftx_ctx *c, const void *send, const int6
     if (!rc && nb) {
         COMM_LOCAL(rc, !send, "comm_gather_rows: send is NULL");
         if (!rc) {
-            d = sc.alloc<char>(nb);
+            d = sc.tmp<char>(nb);
             COMM_LOCAL(rc, !d, "comm_gather_rows: device allocation failed");
         }
         if (!rc && hipMemcpyAsync(d, send, nb, hipMemcpyHostToDevice, c->stream) != hipSuccess)
@@ -5188,7 +4997,7 @@ extern "C" int raftx_comm_reduce_sum(raftx_ctx *c, double *buf, size_t n, int ro
     double *d = nullptr;
     COMM_LOCAL(rc, !buf && n, "comm_reduce_sum: buf is NULL");
     if (!rc && n) {
-        d = sc.alloc<double>(n);
+        d = sc.tmp<double>(n);
         COMM_LOCAL(rc, !d, "comm_reduce_sum: device allocation failed");
     }
     if (int a = comm_agree(c, R, rc)) return a;
@@ -5254,19 +5063,14 @@ extern "C" int raftx_debug_flex_gemm(raftx_ctx *c, int K, int n, const double *A
     if (K < 1 || K % 6 || n < 1 || !A || !W || !out) FAIL(c, "debug_flex_gemm: K must be a multiple of 6");
     HIPCHK(c, hipSetDevice(c->device));
     Scratch sc(c);
-    double *dA = sc.alloc<double>((size_t)K * n), *dW = sc.alloc<double>((size_t)K * n), *dO = sc.alloc<double>((size_t)n * n);
-    int64_t *dOff = sc.alloc<int64_t>(2);
-    if (!dA || !dW || !dO || !dOff) FAIL(c, "debug_flex_gemm: device allocation failed");
     const int64_t off[2] = {0, K / 6};
-    H2D(c, dA, A, (size_t)K * n * sizeof(double));
-    H2D(c, dW, W, (size_t)K * n * sizeof(double));
-    H2D(c, dOff, off, sizeof(off));
+    double *dA = sc.in<double>(A, (size_t)K * n), *dW = sc.in<double>(W, (size_t)K * n), *dO = sc.out<double>(out, (size_t)n * n);
+    int64_t *dOff = sc.in<int64_t>(off, 2);
+    if (int rc = sc.upload("debug_flex_gemm")) return rc;
     const int nt = (n + 15) / 16;
     hipLaunchKernelGGL(k_flex_gemm_B, dim3((unsigned)((nt * nt + 3) / 4), 1), dim3(256), 0, c->stream, K / 6, 1, n, dOff, dA, dW,
                        (const int *)nullptr, dO);
-    D2H(c, out, dO, (size_t)n * n * sizeof(double));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return 0;
+    return sc.download();
 }
 extern "C" int raftx_debug_math_table(raftx_ctx *c, int n, const double *x, double *sin_out, double *cos_out, double *exp_out) {
     return debug_math(c, n, x, sin_out, cos_out, exp_out, 1);
@@ -5275,15 +5079,8 @@ static int debug_math(raftx_ctx *c, int n, const double *x, double *sin_out, dou
     if (!c || n < 0 || !x || !sin_out || !cos_out || !exp_out) return -1;
     HIPCHK(c, hipSetDevice(c->device));
     Scratch sc(c);
-    double *dx = sc.alloc<double>(n), *ds = sc.alloc<double>(n), *dc = sc.alloc<double>(n), *de = sc.alloc<double>(n);
-    if (n && (!dx || !ds || !dc || !de)) FAIL(c, "debug_math: device allocation failed");
-    if (n) {
-        H2D(c, dx, x, n * sizeof(double));
-        hipLaunchKernelGGL(k_debug_math, dim3((n + 255) / 256), dim3(256), 0, c->stream, n, dx, ds, dc, de, table);
-        D2H(c, sin_out, ds, n * sizeof(double));
-        D2H(c, cos_out, dc, n * sizeof(double));
-        D2H(c, exp_out, de, n * sizeof(double));
-    }
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return 0;
+    double *dx = sc.in<double>(x, n), *ds = sc.out<double>(sin_out, n), *dc = sc.out<double>(cos_out, n), *de = sc.out<double>(exp_out, n);
+    if (int rc = sc.upload("debug_math")) return rc;
+    if (n) hipLaunchKernelGGL(k_debug_math, dim3((n + 255) / 256), dim3(256), 0, c->stream, n, dx, ds, dc, de, table);
+    return sc.download();
 }

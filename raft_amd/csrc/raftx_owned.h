@@ -1,8 +1,9 @@
-// Owners of the HIP resources of a context: device blocks (DevPool + Bag; outside the pool: DevBuf), page-locked landing
-// areas (Pinned), events, streams.  Host only -- the HIP runtime API and the standard library, so that a plain host compiler
-// builds it (tests/csrc/owned_driver.cpp).  Every owner is non-copyable, movable where the library moves it, and releases
-// what it holds when destroyed; the allocation, free, create and destroy calls are spelled here and nowhere else.  Owners
-// never synchronise: what has to drain before a block is replaced or goes back to the pool is its caller's rule.
+// Owners of the HIP resources of a context: device blocks (DevPool + Bag; the arrays of one call: Staging; outside the pool:
+// DevBuf), page-locked landing areas (Pinned), events, streams.  Host only -- the HIP runtime API and the standard library,
+// so that a plain host compiler builds it (tests/csrc/owned_driver.cpp).  Every owner is non-copyable, movable where the
+// library moves it, and releases what it holds when destroyed; the allocation, free, create and destroy calls are spelled
+// here and nowhere else.  Owners never synchronise: what has to drain before a block is replaced or goes back to the pool
+// is its caller's rule.
 #pragma once
 #include <hip/hip_runtime_api.h>
 
@@ -117,6 +118,56 @@ struct Bag {
         pool = &from;
         blocks.push_back(p);
         return p;
+    }
+};
+
+// The device side of one call's arrays, each declared once together with its host side: tmp(n) is a device-only block,
+// in(host, n) a block plus a queued host-to-device copy of n elements, out(host, n) a block plus a queued device-to-host
+// copy, out_from(host, dev, n) a queued copy out of a block somebody else owns.  A zero count, and a null host array of
+// in / out, give null and queue nothing; a non-zero request the pool cannot meet gives null and sets `failed`, which stays
+// set.  send() issues the uploads declared since the last send() -- none of them once `failed` is set --, fetch() the
+// result copies, both in declaration order.
+struct Staging {
+    struct Copy { void *dst; const void *src; size_t bytes; };
+    DevPool &pool;
+    Bag bag;
+    std::vector<Copy> ups, downs;
+    bool failed = false;
+    explicit Staging(DevPool &pool_) : pool(pool_) {}
+    template <typename Tp>
+    Tp *tmp(size_t n) {
+        Tp *p = nullptr;
+        if (n && bag.get(pool, n, &p) != hipSuccess) failed = true;
+        return p;
+    }
+    template <typename Dp, typename Hp>
+    Dp *in(const Hp *host, size_t n) {
+        static_assert(sizeof(Dp) == sizeof(Hp), "host and device elements of one size");
+        Dp *p = host ? tmp<Dp>(n) : nullptr;
+        if (p) ups.push_back({p, host, n * sizeof(Dp)});
+        return p;
+    }
+    template <typename Dp, typename Hp>
+    Dp *out(Hp *host, size_t n) {
+        Dp *p = host ? tmp<Dp>(n) : nullptr;
+        out_from(host, p, n);
+        return p;
+    }
+    template <typename Dp, typename Hp>
+    void out_from(Hp *host, const Dp *dev, size_t n) {
+        static_assert(sizeof(Dp) == sizeof(Hp), "host and device elements of one size");
+        if (host && dev && n) downs.push_back({host, dev, n * sizeof(Dp)});
+    }
+    hipError_t send(hipStream_t st) {
+        if (failed) ups.clear();
+        return failed ? hipErrorOutOfMemory : issue(ups, hipMemcpyHostToDevice, st);
+    }
+    hipError_t fetch(hipStream_t st) { return issue(downs, hipMemcpyDeviceToHost, st); }
+    static hipError_t issue(std::vector<Copy> &q, hipMemcpyKind kind, hipStream_t st) {
+        hipError_t e = hipSuccess;
+        for (size_t i = 0; i < q.size() && e == hipSuccess; i++) e = hipMemcpyAsync(q[i].dst, q[i].src, q[i].bytes, kind, st);
+        q.clear();
+        return e;
     }
 };
 

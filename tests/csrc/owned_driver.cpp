@@ -12,10 +12,13 @@
 
 enum Kind { DEV, HOST, EVENT, STREAM, NKIND };
 static long live[NKIND], made[NKIND], freed[NKIND], calls[NKIND], fail_at[NKIND];   // fail_at: the call (1, 2, ..) that fails; 0: none
+static bool fail_also_next[NKIND];                  // ... and the call after it (the pool retries a failed hipMalloc once)
 static long memsets = 0;
+struct Logged { hipMemcpyKind kind; void *dst; const void *src; size_t bytes; };
+static std::vector<Logged> copies;                 // every hipMemcpyAsync, in the order issued
 
 static hipError_t make(Kind k, void **out, size_t bytes, hipError_t err) {
-    if (++calls[k] == fail_at[k]) {
+    if (++calls[k] == fail_at[k] || (fail_also_next[k] && calls[k] == fail_at[k] + 1)) {
         *out = nullptr;
         return err;
     }
@@ -40,6 +43,11 @@ hipError_t hipHostFree(void *ptr) { return drop(HOST, ptr); }
 hipError_t hipMemsetAsync(void *dst, int value, size_t sizeBytes, hipStream_t) {
     memsets++;
     memset(dst, value, sizeBytes);                  // (out of bounds: the sanitizer's to report)
+    return hipSuccess;
+}
+hipError_t hipMemcpyAsync(void *dst, const void *src, size_t sizeBytes, hipMemcpyKind kind, hipStream_t) {
+    copies.push_back({kind, dst, src, sizeBytes});
+    memcpy(dst, src, sizeBytes);                    // (out of bounds on either side: the sanitizer's to report)
     return hipSuccess;
 }
 hipError_t hipEventCreate(hipEvent_t *e) { return make(EVENT, reinterpret_cast<void **>(e), 1, hipErrorOutOfMemory); }
@@ -70,8 +78,10 @@ static void fresh() {
     for (int k = 0; k < NKIND; k++) {
         CHECK(live[k] == 0);                        // every scene leaves nothing behind
         made[k] = freed[k] = calls[k] = fail_at[k] = 0;
+        fail_also_next[k] = false;
     }
     memsets = 0;
+    copies.clear();
 }
 
 static void dev_buf() {
@@ -235,6 +245,110 @@ static void events_and_streams() {
     fresh();
 }
 
+// the arrays of one call (Staging): declared once with their host side, uploads by send, result copies by fetch alone
+static bool copied(size_t i, hipMemcpyKind kind, void *dst, const void *src, size_t bytes) {
+    return i < copies.size() && copies[i].kind == kind && copies[i].dst == dst && copies[i].src == src && copies[i].bytes == bytes;
+}
+static void staging() {
+    {                                               // nothing to stage: null, no transfer, no failure, no block
+        DevPool pool;
+        Staging s(pool);
+        double host[4] = {1, 2, 3, 4};
+        const double *none = nullptr;
+        double *nout = nullptr;
+        CHECK(!s.tmp<double>(0) && !s.in<double>(none, 4) && !s.in<double>(host, 0) && !s.out<double>(nout, 4) && !s.out<double>(host, 0));
+        s.out_from(nout, host, 4);
+        s.out_from(host, none, 4);
+        s.out_from(host, host, 0);
+        CHECK(!s.failed && s.ups.empty() && s.downs.empty() && s.bag.blocks.empty() && calls[DEV] == 0);
+        CHECK(s.send(nullptr) == hipSuccess && s.fetch(nullptr) == hipSuccess && copies.empty());
+    }
+    fresh();
+    {                                               // declaration order, exact byte counts, results only by fetch, a round trip
+        DevPool pool;
+        {
+            Staging s(pool);
+            const double a[3] = {1.5, -2.5, 3.5};
+            const int32_t b[5] = {7, 8, 9, 10, 11};
+            const char cc[7] = "abcdef";
+            double ra[3] = {0, 0, 0};
+            int32_t rb[5] = {0, 0, 0, 0, 0};
+            char rc[7] = "";
+            double *da = s.in<double>(a, 3);
+            float *scratch = s.tmp<float>(9);
+            int *db = s.in<int>(b, 5);
+            char *dc = s.in<char>(cc, 7);
+            CHECK(da && scratch && db && dc && !s.failed && live[DEV] == 4 && copies.empty());     // declared, nothing issued
+            s.out_from(rb, db, 5);
+            s.out_from(ra, da, 3);
+            s.out_from(rc, dc, 7);
+            CHECK(s.send(nullptr) == hipSuccess && copies.size() == 3);
+            CHECK(copied(0, hipMemcpyHostToDevice, da, a, 3 * sizeof(double)) && copied(1, hipMemcpyHostToDevice, db, b, 5 * sizeof(int32_t)) &&
+                  copied(2, hipMemcpyHostToDevice, dc, cc, 7));
+            CHECK(rb[0] == 0 && ra[0] == 0 && rc[0] == 0);                                          // no result copy yet
+            CHECK(s.send(nullptr) == hipSuccess && copies.size() == 3);                             // sent once
+            double later[2] = {4.0, 5.0};                                                            // declared after a send: the next send's
+            double *dl = s.in<double>(later, 2);
+            CHECK(s.send(nullptr) == hipSuccess && copies.size() == 4 && copied(3, hipMemcpyHostToDevice, dl, later, 2 * sizeof(double)));
+            CHECK(s.fetch(nullptr) == hipSuccess && copies.size() == 7);
+            CHECK(copied(4, hipMemcpyDeviceToHost, rb, db, 5 * sizeof(int32_t)) && copied(5, hipMemcpyDeviceToHost, ra, da, 3 * sizeof(double)) &&
+                  copied(6, hipMemcpyDeviceToHost, rc, dc, 7));
+            CHECK(!memcmp(ra, a, sizeof(a)) && !memcmp(rb, b, sizeof(b)) && !memcmp(rc, cc, sizeof(cc)));
+            CHECK(s.fetch(nullptr) == hipSuccess && copies.size() == 7);
+        }
+        CHECK(pool.free_.size() == 5 && live[DEV] == 5);                                            // every block back in the pool
+    }
+    fresh();
+    {                                               // out(): a block of its own, filled by "the kernel", copied by fetch
+        DevPool pool;
+        Staging s(pool);
+        double res[4] = {9, 9, 9, 9};
+        double *d = s.out<double>(res, 4);
+        CHECK(d && s.downs.size() == 1 && s.ups.empty());
+        for (int i = 0; i < 4; i++) d[i] = 0.25 * i;
+        CHECK(s.send(nullptr) == hipSuccess && copies.empty() && res[3] == 9);
+        CHECK(s.fetch(nullptr) == hipSuccess && copied(0, hipMemcpyDeviceToHost, res, d, 4 * sizeof(double)) && res[3] == 0.75);
+    }
+    fresh();
+    {                                               // a result out of a block somebody else owns: read from that pointer
+        DevPool pool;
+        Staging s(pool);
+        DevBuf<double> resident;
+        CHECK(resident.grow(6) == hipSuccess);
+        for (int i = 0; i < 6; i++) resident.p[i] = 10.0 + i;
+        double res[6] = {0, 0, 0, 0, 0, 0};
+        s.out_from(res, resident.p, 6);
+        CHECK(s.bag.blocks.empty() && s.downs.size() == 1);
+        CHECK(s.fetch(nullptr) == hipSuccess && copies.size() == 1 && copied(0, hipMemcpyDeviceToHost, res, resident.p, 6 * sizeof(double)));
+        CHECK(res[0] == 10.0 && res[5] == 15.0);
+    }
+    fresh();
+    for (int k : {1, 3, 5}) {                       // the k-th of five blocks refused: first, middle, last
+        DevPool pool;
+        {
+            Staging s(pool);
+            const double a[8] = {0};
+            double r[8];
+            void *p[5];
+            for (int i = 1; i <= 5; i++) {
+                if (i == k) {                       // (the pool tries twice: both attempts fail)
+                    fail_at[DEV] = calls[DEV] + 1;
+                    fail_also_next[DEV] = true;
+                }
+                p[i - 1] = i == 1 ? (void *)s.in<double>(a, 8) : i == 2 ? (void *)s.tmp<int>(100) : i == 3 ? (void *)s.out<double>(r, 8)
+                         : i == 4 ? (void *)s.in<double>(a, 4) : (void *)s.out<double>(r, 2);
+                CHECK((p[i - 1] == nullptr) == (i == k) && s.failed == (i >= k));                   // the flag stays set
+            }
+            CHECK(s.bag.blocks.size() == 4 && live[DEV] == 4 && !s.ups.empty() && !s.downs.empty());
+            CHECK(s.send(nullptr) == hipErrorOutOfMemory && copies.empty() && s.ups.empty());       // a failed call uploads nothing
+        }
+        CHECK(pool.free_.size() == 4 && live[DEV] == 4);                                            // every block back in the pool
+        pool.trim();
+        CHECK(live[DEV] == 0);
+        fresh();
+    }
+}
+
 // the shape of a context: members declared pool first, released in the reverse order by the destructor alone
 struct Holder {
     Stream stream;
@@ -264,6 +378,7 @@ int main() {
     bags();
     pinned();
     events_and_streams();
+    staging();
     holder();
     printf("OK %d\n", checks);
     return 0;

@@ -1,9 +1,11 @@
-"""The resource owners of the device library (raft_amd/csrc/raftx_owned.h: DevPool, Bag, DevBuf, Pinned, Event, Stream)
-compiled by a plain host compiler with -fsanitize=address,undefined into a stand-alone program
+"""The resource owners of the device library (raft_amd/csrc/raftx_owned.h: DevPool, Bag, Staging, DevBuf, Pinned, Event,
+Stream) compiled by a plain host compiler with -fsanitize=address,undefined into a stand-alone program
 (tests/csrc/owned_driver.cpp) whose HIP entry points are malloc-backed stand-ins that count live objects and fail on
 demand: every owner leaves nothing behind, a failed growth leaves an empty buffer, bags return their blocks to the pool
-and the pool frees each block once, moved-from owners release nothing, a borrowed stream is never destroyed.  No GPU and
-no HIP runtime are involved."""
+and the pool frees each block once, moved-from owners release nothing, a borrowed stream is never destroyed; the arrays
+of one call (Staging) are copied in declaration order with exact byte counts, results only by fetch, nothing for a null
+or empty array, and a refused block sets the flag and leaves every other block to the pool.  No GPU and no HIP runtime
+are involved."""
 import glob
 import os
 import shutil
@@ -53,4 +55,4 @@ def test_owners_release_everything_once_under_address_and_undefined_behaviour_sa
     r = subprocess.run([owned_driver], capture_output=True, text=True, env=env, timeout=120)
     assert r.returncode == 0, (r.stdout[-500:], r.stderr[-3000:])
     assert "ERROR: AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr and "LeakSanitizer" not in r.stderr, r.stderr[-3000:]
-    assert r.stdout.startswith("OK ") and int(r.stdout.split()[1]) > 50
+    assert r.stdout.startswith("OK ") and int(r.stdout.split()[1]) > 190
