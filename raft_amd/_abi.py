@@ -43,6 +43,8 @@ MODAL_EXPORTS = ("raftx_modal_batch", "raftx_modal_resident", "raftx_sweep_modal
 MODAL_SMALL_DIAG, MODAL_NONPOSITIVE, MODAL_COMPLEX, MODAL_SINGULAR_M, MODAL_NO_CONVERGENCE = 1, 2, 4, 8, 16
 # include/raftx_current.h: mean current loads, the device library only (the oracle has no current-load sweep)
 CURRENT_EXPORTS = ("raftx_current_loads", "raftx_sweep_current")
+# include/raftx_launch.h: the launch form of the fused fixed point, the device library only (the oracle has no launches)
+LAUNCH_EXPORTS = ("raftx_last_solve_launch",)
 # include/raftx_channels.h: output channels of a sweep crossing, the device library only
 CHANNEL_EXPORTS = ("raftx_sweep_channels",)
 # include/raftx_qtfgen.h: second-order QTF tables generated on the device, the device library only
@@ -195,6 +197,10 @@ class RaftxLib:
             L.raftx_qtf_slender_resident.argtypes = [_vp, C.c_int, C.c_int, _vp, _vp, C.c_double, C.c_double, C.c_double, _vp, _vp,
                                                      _vp, C.c_int, _vp]
             L.raftx_qtf_slender_resident.restype = C.c_int
+        self.has_launch = all(hasattr(L, s) for s in LAUNCH_EXPORTS)
+        if self.has_launch:
+            L.raftx_last_solve_launch.argtypes = [_vp, _vp, _vp, _vp]
+            L.raftx_last_solve_launch.restype = C.c_int
         self.has_channels = all(hasattr(L, s) for s in CHANNEL_EXPORTS)
         if self.has_channels:
             L.raftx_sweep_channels.argtypes = [_vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int, _vp, _vp]
@@ -1479,6 +1485,16 @@ class Context:
         rc = self.rlib.lib.raftx_last_solve_kernel(self._h, C.byref(f), C.byref(w), C.byref(n))
         self._check(rc, "raftx_last_solve_kernel")
         return f.value, w.value, n.value
+
+    def last_solve_launch(self):
+        """(persistent, grid, pairs) of the last fused launch: 1 for the persistent form, the workgroups of its grid, the
+        pairs of the batch (raftx_last_solve_launch)."""
+        if not self.rlib.has_launch:
+            raise RaftxError("%s does not implement include/raftx_launch.h (device library only)" % self.rlib.path)
+        p, g, n = C.c_int(0), C.c_int(0), C.c_int(0)
+        rc = self.rlib.lib.raftx_last_solve_launch(self._h, C.byref(p), C.byref(g), C.byref(n))
+        self._check(rc, "raftx_last_solve_launch")
+        return p.value, g.value, n.value
 
     def debug_math(self, x, table=False):
         """The device's own sincos / exp on x; table=True: the table-driven sincos of the fused kernel's run starts."""

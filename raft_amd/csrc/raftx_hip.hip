@@ -48,6 +48,7 @@
 #include "../../include/raftx_qtfgen.h"
 #include "../../include/raftx_mooring.h"
 #include "../../include/raftx_statics.h"
+#include "../../include/raftx_launch.h"
 
 // roctx ranges around the phases of the host side: named spans for `rocprofv3 --marker-trace`.
 // librocprofiler-sdk-roctx is bound at run time on first use; without it (or outside a profiler) the ranges cost a branch.
@@ -1008,6 +1009,7 @@ struct raftx_ctx {
     unsigned kpNext = 0;
     int nCU = 0;                         // compute units of the device (the persistent grid is what they hold at once)
     int last_flags = -1, last_minb = 0, last_rc = 0;       // specialisation of the last fused-kernel launch (raftx_last_solve_kernel)
+    int last_persist = 0, last_grid = 0, last_pairs = -1;  // its launch form: persistent?, workgroups, pairs (raftx_last_solve_launch)
     int rQtf_sets = 0, rQtf_nw2 = 0, rKay_sets = 0, rKay_nw2 = 0;
     bool have_xl0 = false, want_xlout = false;
     int maxS = 0;
@@ -2025,6 +2027,9 @@ static int launch_persistent(raftx_ctx *c, kp_fn kernel, const DevTables &T, con
     static const int grid_env = getenv("RAFTX_KP_GRID") ? atoi(getenv("RAFTX_KP_GRID")) : 0;      // tuning: workgroups of the grid
     size_t grid = (size_t)(grid_env > 0 ? grid_env : wg_per_cu * c->nCU);
     grid = std::min<size_t>(std::min<size_t>(grid, KP_MAX_GRID), grid_for_pairs(npairs));
+    c->last_persist = 1;
+    c->last_grid = (int)grid;
+    c->last_pairs = (int)npairs;
     if (gen) {                                            // the generating form: the workgroups build their designs' tables first
         PersistGenArgs PG;
         PG.P = P;
@@ -2230,6 +2235,7 @@ static bool resolve_generation(raftx_ctx *c, const LaunchPlan &lp, bool whole) {
 // the three forms of the launch: every pair in one grid on the ctx stream (persistent where the kernel has a twin) ...
 static int launch_whole(raftx_ctx *c, const LaunchPlan &lp, const SolveArgs &A, size_t lds, bool gen_fused) {
     if (!c->r_npair) return 0;
+    c->last_grid = (int)grid_for_pairs(c->r_npair);       // (launch_persistent records its own)
     if (lp.k.kp)
         return launch_persistent(c, lp.k.kp, c->T, A, c->r_npair, lp.sh.threads,
                                  std::max(lds, gen_fused ? c->job.gen_lds : (size_t)0) + KP_STASH * sizeof(double), lp.wg_per_cu,
@@ -2322,6 +2328,9 @@ static int solve_enqueue(raftx_ctx *c, int nIter, double tol, double XiStart, co
     if (int rc = slabbed ? ensure_slab_list(c) : 0) return rc;
     const bool whole = classes.cls.empty() && !slabbed;
     const bool gen_fused = c->last_gen_fused = resolve_generation(c, lp, whole);
+    c->last_persist = 0;                      // class and slabbed launches: per-pair grids, none recorded
+    c->last_grid = 0;
+    c->last_pairs = (int)c->r_npair;
     if (prep_lds(c, reinterpret_cast<const void *>(lp.k.fn), lds)) return -1;
     HIPCHK(c, hipEventRecord(c->ev0, c->stream));
     int rc_after = 0;
@@ -3990,6 +3999,7 @@ static int launch_block(raftx_ctx *c, SweepSlot &S, int slot, size_t b, LaunchMo
         hand_sea_states(c->csets[S.cset].T, sub);
         if (S.slab) slab_plan_block(M.plan, S, b, M.slab_pairs, M.sDown);
         rc = solve_enqueue(sub, S.nIter, S.tol, S.XiStart, nullptr, 0, S.slab ? &M.plan : nullptr);
+        if (!rc) c->last_persist = sub->last_persist, c->last_grid = sub->last_grid, c->last_pairs = sub->last_pairs;
     }
     if (!rc && sub->pinRes.reserve(landing::stats((size_t)(S.bnd[b + 1] - S.bnd[b]) * S.nCase).need) != hipSuccess) rc = -2;
     if (!rc && !S.slab) rc = enqueue_stats(c, S, b, M.sDown);         // (slab mode: stats_after_join)
@@ -5052,6 +5062,13 @@ extern "C" int raftx_last_solve_kernel(raftx_ctx *c, int *flags, int *waves_per_
     if (flags) *flags = c->last_flags;
     if (waves_per_simd) *waves_per_simd = c->last_minb;
     if (cache_slots) *cache_slots = c->last_rc;
+    return 0;
+}
+extern "C" int raftx_last_solve_launch(raftx_ctx *c, int *persistent, int *grid, int *pairs) {
+    if (!c || c->last_pairs < 0) return -1;
+    if (persistent) *persistent = c->last_persist;
+    if (grid) *grid = c->last_grid;
+    if (pairs) *pairs = c->last_pairs;
     return 0;
 }
 static int debug_math(raftx_ctx *c, int n, const double *x, double *sin_out, double *cos_out, double *exp_out, int table);

@@ -7,7 +7,7 @@ import pytest
 from raft_amd import dropin
 from raft_amd._abi import RaftxError
 from tests.util import (group_rel_err, rel_err, case_from_fixture, load_model_fixture, ref_headings,
-                        random_strips, random_matrices, synthetic_cases)
+                        random_strips, random_matrices, synthetic_cases, add_mcf_rows)
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-9
@@ -785,6 +785,7 @@ def test_ragged_batch_is_launched_per_lds_class(hip_ctx, oracle_ctx):
     _both(hip_ctx, oracle_ctx, tables, mats, cases)
     oh = hip_ctx.solve_dynamics(6, 0.01, 0.1)               # no optional outputs: the lean (sweep) specialisation
     oo = oracle_ctx.solve_dynamics(6, 0.01, 0.1)
+    assert hip_ctx.last_solve_launch() == (0, 0, len(S_list) * nC)      # several grids, one workgroup per pair: not the persistent form
     assert np.array_equal(oh["niter"], oo["niter"]) and np.array_equal(oh["flags"], oo["flags"])
     for d in range(len(S_list)):
         assert group_rel_err(oh["Xi"][d], oo["Xi"][d]) < TOL
@@ -819,16 +820,7 @@ def test_featured_sweep_kernels_run_lean_and_match_the_oracle(hip_ctx, oracle_ct
     S_list = [53, 47, 0, 60]
     tables = [(_member_run_table(rng, max(1, S // 10), 10) if S else random_strips(rng, 0)) for S in S_list]
     if mcf:
-        from raft_amd import strips as st
-        from raft_amd.strips import StripTable
-        for i, t in enumerate(tables):                                # member-run geometry, MacCamy-Fuchs rows on some strips
-            cms = []
-            for srow in range(t.n):
-                if rng.uniform() < mcf:
-                    t.strips[srow, st.F_MCF] = float(len(cms))
-                    t.strips[srow, st.F_IP1] = t.strips[srow, st.F_IP2] = 0.0
-                    cms.append(rng.uniform(1.2, 2.2, size=(2, nw)) + 1j * rng.uniform(-0.5, 0.5, size=(2, nw)))
-            tables[i] = StripTable(t.strips, np.array(cms) if cms else None)
+        tables = add_mcf_rows(rng, tables, mcf, nw)                   # member-run geometry, MacCamy-Fuchs rows on some strips
     mats = random_matrices(rng, len(S_list), nw, fdep)
     cases = synthetic_cases(rng, nC, nH, nw)
     _both(hip_ctx, oracle_ctx, tables, mats, cases)

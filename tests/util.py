@@ -47,6 +47,23 @@ def random_strips(rng, S, nw=0, mcf_frac=0.0):
     return StripTable(rec, np.array(cms) if cms else None)
 
 
+def add_mcf_rows(rng, tables, frac, nw):
+    """The tables with MacCamy-Fuchs rows on a fraction ``frac`` of their strips (geometry and run hints kept): the marked
+    strips lose their transverse added-mass terms and point at a row of complex coefficients [2,nw]."""
+    from raft_amd import strips as st
+    from raft_amd.strips import StripTable
+    out = []
+    for t in tables:
+        cms = []
+        for srow in range(t.n):
+            if rng.uniform() < frac:
+                t.strips[srow, st.F_MCF] = float(len(cms))
+                t.strips[srow, st.F_IP1] = t.strips[srow, st.F_IP2] = 0.0
+                cms.append(rng.uniform(1.2, 2.2, size=(2, nw)) + 1j * rng.uniform(-0.5, 0.5, size=(2, nw)))
+        out.append(StripTable(t.strips, np.array(cms) if cms else None))
+    return out
+
+
 def random_matrices(rng, nD, nw=0, freq_dep=False):
     M0 = np.zeros((nD, 6, 6))
     B0 = np.zeros((nD, 6, 6))
