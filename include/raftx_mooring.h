@@ -13,6 +13,23 @@
  *     6     unstretched length L            7   EA            8   w, submerged weight per length
  *     9     seabed friction CB: must be 0 (refused otherwise; friction is not covered)
  *     10-15 zero
+ * A COMPOSITE line -- segments in series, joined at free points that may carry a clump weight or a buoy (MoorPy: one Line
+ * per segment between points of type free) -- occupies consecutive rows, ordered anchor -> fairlead; nLine counts rows,
+ * that is segments, everywhere.  Its head row is the record above with the anchor-side segment's L, EA, w.  Each further
+ * segment is a CONTINUATION row:
+ *     15 (RAFTX_ML_CONT)   1
+ *     6-8                  its own L, EA, w            9   CB, must be 0
+ *     10 (RAFTX_ML_WJOINT) net submerged weight [N] of the point at its lower end, (m - rho v) g: negative for a buoy,
+ *                          0 for a plain joint
+ *     0-5, 11-14           zero
+ * At most RAFTX_MOOR_MAX_SEG rows per line.  A row with field 15 equal to 0 that no continuation row follows is a single line
+ * and takes the arithmetic, and gives the bits, of a batch without composite lines.  On a frictionless seabed HF is the same
+ * in every segment and V at the top of a segment is VF less the segments and points hanging above it, so the chain is
+ * solved for the fairlead's (HF, VF) like a single line, with the summed span and Jacobian; the guess uses the total length
+ * and the mean weight per length (which must be positive).  Only the anchor-side segment may rest on the seabed.
+ * C_moor and F_moor receive a chain once (from its head row); T and J have the two ends of every row, in the order of
+ * getTensions for a system with one Line per segment.  line_out of a continuation row: HF, V at its top, HF, V at its bottom,
+ * 0, the chain's iterations, 0; of a head row: its own segment's, L_B and the branch included.
  * The fairlead is at x[0:3] + R(x[3:6]) r_f, R = Rz Ry Rx of (roll, pitch, yaw): the rotation of the member descriptors.
  * The elastic catenary (no seabed contact, or partly resting on a frictionless seabed when the anchor lies on it,
  * |a_z + depth| <= 1e-6 depth) is solved for the fairlead's (HF, VF) by a damped Newton iteration to stagnation in fp64,
@@ -20,7 +37,11 @@
  * vector about the reference point applied on top of R; it includes the arm turning under a fixed force and is not
  * symmetric in general.  J = dT/dx6 in the same sense.
  *
- * Flags (int32 per design; a flagged design's outputs are NaN, and only its own):
+ * Flags (int32 per design; a flagged design's outputs are NaN, and only its own).  For a composite line BAD_LINE looks at
+ * the L, EA, w of every row (segments must be heavier than water: buoyancy enters through the points only), SLACK and
+ * VERTICAL at the total length.
+ * Still refused: bridles and any point joining more than two lines, lines with both ends on the vessel, seabed friction,
+ * the fully slack profile, seabed contact of any segment but the anchor-side one.
  */
 #ifndef RAFTX_MOORING_H
 #define RAFTX_MOORING_H
@@ -28,10 +49,16 @@
 #include "raftx.h"
 
 #define RAFTX_ML_N 16
+#define RAFTX_ML_WJOINT 10             /* continuation row: net submerged weight of the point at its lower end */
+#define RAFTX_ML_CONT 15               /* 1 in a continuation row of a composite line, 0 in a head row or a single line */
+#define RAFTX_MOOR_MAX_SEG 4           /* rows of one composite line, at most */
 #define RAFTX_MOOR_BAD_LINE        1   /* non-finite field or pose; L, EA or w <= 0; anchor below the seabed; fairlead not above the anchor */
 #define RAFTX_MOOR_VERTICAL        2   /* horizontal span XF <= 1e-9 L */
 #define RAFTX_MOOR_SLACK           4   /* L >= XF + ZF: the fully slack profile is not covered */
 #define RAFTX_MOOR_NO_CONVERGENCE  8   /* the Newton cap was reached */
+/* (16 and 32 are the flags of raftx_statics.h) */
+#define RAFTX_MOOR_GROUNDED       64   /* composite line: the anchor-side segment rests wholly on the seabed (V at its top <= 0), or a
+                                          joint or the sag of a segment lies more than 1e-6 depth below the seabed */
 
 #ifdef __cplusplus
 extern "C" {
@@ -43,7 +70,8 @@ extern "C" {
  * getTensions), J [nDesign,2 nLine,6], line_out [nDesign,nLine,8] = HF, VF, HA, VA, L_B, iterations, branch
  * (1 = seabed contact), 0, flags [nDesign].  The sums over the lines run in line order without atomics: the bits of a
  * design depend on its own lines and pose only.  Errors, before any launch: nLine < 1, nDesign < 0, NULL lines or flags,
- * a depth that is not positive and finite, a line with CB != 0. */
+ * a depth that is not positive and finite, a line with CB != 0, a design whose row 0 is a continuation row, a composite
+ * line of more than RAFTX_MOOR_MAX_SEG rows. */
 int raftx_mooring_lines(raftx_ctx *ctx, int nDesign, int nLine, const double *lines, const double *pose, double depth,
                         double *C_moor, double *F_moor, double *T, double *J, double *line_out, int32_t *flags);
 
@@ -52,7 +80,8 @@ int raftx_mooring_lines(raftx_ctx *ctx, int nDesign, int nLine, const double *li
  * (fields 0-5) that are affine in the variant parameters, lineCoef [nLine,6,nParam+1] = constant, then one coefficient
  * per parameter, evaluated left to right without fused multiply-adds exactly as endCoef of raftx_variant_program.
  * nParam must equal the installed variant program's (an error without one).  nLine = 0 clears the program; installing a
- * new variant program does not. */
+ * new variant program does not.  Continuation rows are carried unchanged to every variant; a lineEdit on one is an error
+ * (the anchor and the fairlead of a composite line are its head row's), as are the record errors of raftx_mooring_lines. */
 int raftx_mooring_program(raftx_ctx *ctx, int nLine, const double *lines, int nParam, const double *lineCoef,
                           const int32_t *lineEdit);
 

@@ -3,7 +3,8 @@
  * Replaces, per unit, the solve of Model.solveStatics (raft_model.py:550-963) for staticsMod == 0 and forcingMod == 0:
  *     Y(x) = F0 + F_env - K_hs (x - x_ref) + F_moor(x) = 0
  * by Newton's iteration x <- x + (K_hs + C_moor(x))^-1 Y(x) from x = x_ref, with F_moor and the exact C_moor of
- * include/raftx_mooring.h (the same line types; every line solved from a cold start at every iterate) and the reference's
+ * include/raftx_mooring.h (the same line types, composite lines of head and continuation rows included: nLine counts rows,
+ * and a chain is solved by the lane of its head row; every line solved from a cold start at every iterate) and the reference's
  * safeguards (raft_model.py:824-861, :667), per step:
  *     a zero diagonal entry of K takes the mean of the diagonal;
  *     dX = K^-1 Y by LU with partial pivoting; while dX.Y < 0 the diagonal grows by 10 % and the solve is repeated, at
@@ -27,7 +28,8 @@
 
 #include "raftx_mooring.h"
 
-/* flags [nDesign]: the RAFTX_MOOR_* bits of the iterate that raised them (raftx_mooring.h: 1, 2, 4, 8), and */
+/* flags [nDesign]: the RAFTX_MOOR_* bits of the iterate that raised them (raftx_mooring.h: 1, 2, 4, 8 and 64, a composite
+ * line grounded at that iterate), and */
 #define RAFTX_STATICS_POSE_CAP   16   /* max_iter steps were taken and the last one was not within tol */
 #define RAFTX_STATICS_SINGULAR   32   /* a zero or non-finite pivot, or a non-finite step */
 
@@ -50,7 +52,8 @@ extern "C" {
  * taken; flags [nDesign].  A flagged design's outputs are NaN, and only its own; iterations stays the count.  A design's
  * bits depend on its own inputs only.
  * Errors, before any launch: nLine < 1, nDesign < 0, NULL K_hs, F0 or flags, a depth that is not positive and finite, a
- * tolerance that is negative or not finite, a line with CB != 0, lines == NULL without a mooring program, with another nLine, or without params. */
+ * tolerance that is negative or not finite, a line with CB != 0, a design whose row 0 is a continuation row, a composite line
+ * of more than RAFTX_MOOR_MAX_SEG rows, lines == NULL without a mooring program, with another nLine, or without params. */
 int raftx_mean_pose(raftx_ctx *ctx, int nDesign, int nLine, const double *lines, const double *params, double depth,
                     const double *K_hs, const double *F0, const double *F_env, const double *x_ref, const double tol[2],
                     int max_iter, double *pose, double *C_moor, double *F_moor, double *T, double *J, double *F_res,

@@ -53,9 +53,12 @@ QTFGEN_EXPORTS = ("raftx_qtf_tables_build", "raftx_qtf_tables_build_variants", "
 # include/raftx_mooring.h: quasi-static mooring lines, the device library only
 MOORING_EXPORTS = ("raftx_mooring_lines", "raftx_mooring_program", "raftx_mooring_expand", "raftx_sweep_mooring")
 ML_N = 16          # doubles per mooring line record (RAFTX_ML_N)
+ML_WJOINT, ML_CONT = 10, 15   # continuation rows of a composite line (RAFTX_ML_WJOINT, RAFTX_ML_CONT)
+MOOR_MAX_SEG = 4   # rows of one composite line, at most (RAFTX_MOOR_MAX_SEG)
 # include/raftx_statics.h: the mean equilibrium pose, the device library only
 STATICS_EXPORTS = ("raftx_mean_pose", "raftx_sweep_mean_pose")
 MOOR_BAD_LINE, MOOR_VERTICAL, MOOR_SLACK, MOOR_NO_CONVERGENCE = 1, 2, 4, 8
+MOOR_GROUNDED = 64
 QKG_N = 8          # doubles per row of the Kim & Yue geometry stream (RAFTX_QKG_N)
 
 

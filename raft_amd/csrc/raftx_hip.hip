@@ -918,7 +918,7 @@ struct SweepSlot {
     } mooring;
     struct PoseReq {                     // raftx_sweep_mean_pose: the crossing runs at every design's mean equilibrium pose
         bool on = false;
-        int nLine = 0, nX = 0, maxIter = 0;
+        int nLine = 0, nX = 0, maxIter = 0, chains = 0;
         double tolT = 0, tolR = 0;
         // device, the whole crossing (in S.allocs): the line records; the statics-only extras [nX,36] / [nX,6] and the loads
         // [nDesign,6], each or null; what the solve reads (K_hs, F0), its scratch and what it leaves; the poses of the second pass
@@ -985,7 +985,7 @@ struct raftx_ctx {
     DevBuf<cplx> bemF;                   // resident BEM (+ added) excitation of raftx_bem_excitation [npair,nHead,6,nw]
     DevBuf<int> commFlag;                // one int in HBM: the status word the ranks agree on before an exchange step (comm_agree)
     struct {                             // raftx_mooring_program: base records and the affine edits of their end points
-        int nLine = 0, nP = 0;
+        int nLine = 0, nP = 0, chains = 0;   // chains: a continuation row among the base records
         DevBuf<double> base, coef;
         DevBuf<int> edit;
     } mprog;
@@ -3243,6 +3243,7 @@ static int block_pose(raftx_ctx *c, SweepSlot &S, size_t b) {
         MeanPoseArgs M;
         memset(&M, 0, sizeof(M));
         M.lines = P.lines + lo * P.nLine * RAFTX_ML_N;
+        M.chains = P.chains;
         M.K_hs = Q.K; M.F0 = Q.F0;
         M.F_env = P.Fenv ? P.Fenv + lo * 6 : nullptr;
         M.x_ref = A.pose;                                        // the block's own upload of the caller's pose, or null
@@ -4378,12 +4379,23 @@ extern "C" int raftx_sweep_current(raftx_ctx *c, int slot, int nCur, const doubl
 // ---- quasi-static mooring lines (include/raftx_mooring.h, raftx_mooring.h)
 // The line source of an entry point `who`: what valid records are, which calls may leave them to the mooring program, and
 // how either kind reaches the device.  (raftx_mooring_program checks its one unit's records itself, in its own wording.)
-static int check_lines(raftx_ctx *c, const char *who, size_t nDesign, int nLine, const double *lines) {
+// *chains: whether any row is a continuation row of a composite line (the CHAINS kernels are needed)
+static int check_lines(raftx_ctx *c, const char *who, size_t nDesign, int nLine, const double *lines, int *chains) {
+    *chains = 0;
+    int run = 0;                                                 // rows of the line the current row belongs to
     for (size_t i = 0; i < nDesign * (size_t)nLine; i++) {
         const double cb = lines[i * RAFTX_ML_N + 9];
         if (std::isfinite(cb) && cb != 0.0)
             FAIL(c, "%s: line %zu of design %zu has seabed friction CB = %g: friction is not covered (CB must be 0)", who, i % nLine,
                  i / nLine, cb);
+        if (lines[i * RAFTX_ML_N + RAFTX_ML_CONT] != 0.0) {
+            if (i % nLine == 0) FAIL(c, "%s: row 0 of design %zu is a continuation row: a composite line starts with its head row", who, i / nLine);
+            if (++run > RAFTX_MOOR_MAX_SEG)
+                FAIL(c, "%s: the composite line ending in row %zu of design %zu has more than %d rows", who, i % nLine, i / nLine,
+                     RAFTX_MOOR_MAX_SEG);
+            *chains = 1;
+        } else
+            run = 1;
     }
     return 0;
 }
@@ -4400,13 +4412,14 @@ static int check_line_program(raftx_ctx *c, const char *who, int nLine, int nP_e
     return 0;
 }
 // ... of a request `who` on the prepared slot S of n designs, with the depth of the slot's sea states
-static int check_slot_lines(raftx_ctx *c, const char *who, const SweepSlot &S, size_t n, int nLine, const double *lines) {
+static int check_slot_lines(raftx_ctx *c, const char *who, const SweepSlot &S, size_t n, int nLine, const double *lines, int *chains) {
     const VariantProg *vp = S.p1.var.prog;
     if (!lines) {
         if (int rc = check_line_program(c, who, nLine, vp ? vp->nP : 0, vp != nullptr)) return rc;
+        *chains = c->mprog.chains;
     } else {
         if (nLine < 1) FAIL(c, "%s: nLine must be positive (got %d)", who, nLine);
-        if (int rc = check_lines(c, who, n, nLine, lines)) return rc;
+        if (int rc = check_lines(c, who, n, nLine, lines, chains)) return rc;
     }
     return check_depth(c, who, c->csets[S.cset].T.depth);
 }
@@ -4431,6 +4444,13 @@ static int expand_lines(raftx_ctx *c, hipStream_t st, size_t n, int nLine, const
     return 0;
 }
 
+// k_moor_line over the records of A: the chain instantiation only where a continuation row is among them
+static void launch_moor_line(hipStream_t st, const MoorArgs &A) {
+    const dim3 grid(moor_grid((long long)A.nDesign * A.nLine));
+    if (A.chains) hipLaunchKernelGGL(k_moor_line<true>, grid, dim3(MOOR_THREADS), 0, st, A);
+    else hipLaunchKernelGGL(k_moor_line<false>, grid, dim3(MOOR_THREADS), 0, st, A);
+}
+
 extern "C" int raftx_mooring_lines(raftx_ctx *c, int nDesign, int nLine, const double *lines, const double *pose, double depth,
                                    double *C_moor, double *F_moor, double *T, double *J, double *line_out, int32_t *flags) {
     if (!c) return -1;
@@ -4438,7 +4458,8 @@ extern "C" int raftx_mooring_lines(raftx_ctx *c, int nDesign, int nLine, const d
     if (nDesign < 0) FAIL(c, "mooring_lines: nDesign must not be negative (got %d)", nDesign);
     if (!lines || !flags) FAIL(c, "mooring_lines: bad arguments (lines and flags are required)");
     if (int rc = check_depth(c, "mooring_lines", depth)) return rc;
-    if (int rc = check_lines(c, "mooring_lines", (size_t)nDesign, nLine, lines)) return rc;
+    int chains = 0;
+    if (int rc = check_lines(c, "mooring_lines", (size_t)nDesign, nLine, lines, &chains)) return rc;
     if (nDesign == 0) return 0;
     HIPCHK(c, hipSetDevice(c->device));
     Scratch sc(c);
@@ -4459,7 +4480,8 @@ extern "C" int raftx_mooring_lines(raftx_ctx *c, int nDesign, int nLine, const d
     A.flags = sc.out<int>(flags, (size_t)nDesign);
     if (int rc = sc.upload("mooring_lines")) return rc;
     if (sc.begin()) return -2;
-    hipLaunchKernelGGL(k_moor_line, dim3(moor_grid((long long)nl)), dim3(MOOR_THREADS), 0, c->stream, A);
+    A.chains = chains;
+    launch_moor_line(c->stream, A);
     hipLaunchKernelGGL(k_moor_design, dim3(moor_grid(nDesign)), dim3(MOOR_THREADS), 0, c->stream, A);
     return sc.finish();
 }
@@ -4477,10 +4499,19 @@ extern "C" int raftx_mooring_program(raftx_ctx *c, int nLine, const double *line
     if (!c->vprog.nM) FAIL(c, "mooring_program: no variant program on this ctx (raftx_variant_program first)");
     if (nParam != c->vprog.nP)
         FAIL(c, "mooring_program: nParam=%d is not the %d parameters of the installed variant program", nParam, c->vprog.nP);
-    for (int l = 0; l < nLine; l++) {
+    int chains = 0;
+    for (int l = 0, run = 0; l < nLine; l++) {
         const double cb = lines[(size_t)l * RAFTX_ML_N + 9];
         if (std::isfinite(cb) && cb != 0.0)
             FAIL(c, "mooring_program: line %d has seabed friction CB = %g: friction is not covered (CB must be 0)", l, cb);
+        if (lines[(size_t)l * RAFTX_ML_N + RAFTX_ML_CONT] != 0.0) {
+            if (l == 0) FAIL(c, "mooring_program: row 0 is a continuation row: a composite line starts with its head row");
+            if (++run > RAFTX_MOOR_MAX_SEG) FAIL(c, "mooring_program: the composite line ending in row %d has more than %d rows", l, RAFTX_MOOR_MAX_SEG);
+            if (lineEdit[l])
+                FAIL(c, "mooring_program: lineEdit on row %d, a continuation row: the anchor and the fairlead are the head row's", l);
+            chains = 1;
+        } else
+            run = 1;
     }
     mooring_program_release(c);
     const size_t nb = (size_t)nLine * RAFTX_ML_N * 8, nc = (size_t)nLine * 6 * (nParam + 1) * 8, ne = (size_t)nLine * 4;
@@ -4493,6 +4524,7 @@ extern "C" int raftx_mooring_program(raftx_ctx *c, int nLine, const double *line
     HIPCHK(c, hipMemcpy(c->mprog.edit.p, lineEdit, ne, hipMemcpyHostToDevice));
     c->mprog.nLine = nLine;
     c->mprog.nP = nParam;
+    c->mprog.chains = chains;
     return 0;
 }
 
@@ -4527,7 +4559,9 @@ static void launch_mean_pose(hipStream_t st, MeanPoseArgs &A, int nDesign, int n
     A.nDesign = nDesign; A.nLine = nLine; A.G = mean_pose_group(nLine); A.maxIter = max_iter > 0 ? max_iter : MP_MAX_IT;
     A.depth = depth; A.tolT = tolT; A.tolR = tolR;
     const int perBlock = MP_THREADS / A.G;
-    hipLaunchKernelGGL(k_mean_pose, dim3((unsigned)((nDesign + perBlock - 1) / perBlock)), dim3(MP_THREADS), 0, st, A);
+    const dim3 grid((unsigned)((nDesign + perBlock - 1) / perBlock));
+    if (A.chains) hipLaunchKernelGGL(k_mean_pose<true>, grid, dim3(MP_THREADS), 0, st, A);
+    else hipLaunchKernelGGL(k_mean_pose<false>, grid, dim3(MP_THREADS), 0, st, A);
 }
 extern "C" int raftx_mean_pose(raftx_ctx *c, int nDesign, int nLine, const double *lines, const double *params, double depth,
                                const double *K_hs, const double *F0, const double *F_env, const double *x_ref, const double tol[2],
@@ -4541,12 +4575,14 @@ extern "C" int raftx_mean_pose(raftx_ctx *c, int nDesign, int nLine, const doubl
     double tolT, tolR;
     if (int rc = mean_pose_tol(c, "mean_pose", tol, &tolT, &tolR)) return rc;
     const size_t n = (size_t)nDesign, nl = n * nLine;
+    int chains = 0;
     if (!lines) {
         // (a batch has no slot and no variant program to agree with; its no-program wording is its own)
         if (!c->mprog.nLine) FAIL(c, "mean_pose: lines == NULL without a mooring program (raftx_mooring_program first)");
         if (int rc = check_line_program(c, "mean_pose", nLine, c->mprog.nP, true)) return rc;
         if (!params && nDesign && c->mprog.nP) FAIL(c, "mean_pose: lines == NULL needs params [nDesign,%d]", c->mprog.nP);
-    } else if (int rc = check_lines(c, "mean_pose", n, nLine, lines))
+        chains = c->mprog.chains;
+    } else if (int rc = check_lines(c, "mean_pose", n, nLine, lines, &chains))
         return rc;
     if (nDesign == 0) return 0;
     HIPCHK(c, hipSetDevice(c->device));
@@ -4556,6 +4592,7 @@ extern "C" int raftx_mean_pose(raftx_ctx *c, int nDesign, int nLine, const doubl
     MeanPoseArgs A;
     memset(&A, 0, sizeof(A));
     A.lines = L.lines;
+    A.chains = chains;
     A.K_hs = sc.in<double>(K_hs, n * 36);
     A.F0 = sc.in<double>(F0, n * 6);
     A.F_env = sc.in<double>(F_env, n * 6);
@@ -4584,7 +4621,8 @@ extern "C" int raftx_sweep_mooring(raftx_ctx *c, int slot, int nLine, const doub
     SweepSlot &S = *slot_;
     if (!flags) FAIL(c, "sweep_mooring: bad arguments (flags is required)");
     const size_t n = S.bnd.empty() ? 0 : (size_t)S.bnd.back();
-    if (int rc = check_slot_lines(c, "sweep_mooring", S, n, nLine, lines)) return rc;
+    int chains = 0;
+    if (int rc = check_slot_lines(c, "sweep_mooring", S, n, nLine, lines, &chains)) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     if (S.mooring.evUp) HIPCHK(c, hipEventSynchronize(S.mooring.evUp));   // (a second request on one slot: the landing area is free again)
     else HIPCHK(c, S.mooring.evUp.ensure(hipEventDisableTiming));
@@ -4595,6 +4633,7 @@ extern "C" int raftx_sweep_mooring(raftx_ctx *c, int slot, int nLine, const doub
     MoorArgs A;
     memset(&A, 0, sizeof(A));
     A.nDesign = (int)n; A.nLine = nLine; A.depth = c->csets[S.cset].T.depth;
+    A.chains = chains;
     const double *dp = nullptr;
     StagedLines L;
     int rc = 0;
@@ -4623,7 +4662,7 @@ extern "C" int raftx_sweep_mooring(raftx_ctx *c, int slot, int nLine, const doub
     A.lines = L.lines; A.pose = dp;
     if (n) {
         if (int re = expand_lines(c, c->sCopy, n, nLine, L)) return re;
-        hipLaunchKernelGGL(k_moor_line, dim3(moor_grid((long long)nl)), dim3(MOOR_THREADS), 0, c->sCopy, A);
+        launch_moor_line(c->sCopy, A);
         hipLaunchKernelGGL(k_moor_design, dim3(moor_grid((long long)n)), dim3(MOOR_THREADS), 0, c->sCopy, A);
         HIPCHK(c, hipGetLastError());
         double *p = S.mooring.pin.p;
@@ -4658,7 +4697,8 @@ extern "C" int raftx_sweep_mean_pose(raftx_ctx *c, int slot, int nLine, const do
     const size_t n = S.bnd.empty() ? 0 : (size_t)S.bnd.back();
     if (nX != 0 && nX != 1 && (size_t)nX != n)
         FAIL(c, "sweep_mean_pose: nX=%d must be 0 (no extras), 1 (shared) or the %zu designs of the crossing", nX, n);
-    if (int rc = check_slot_lines(c, "sweep_mean_pose", S, n, nLine, lines)) return rc;
+    int chains = 0;
+    if (int rc = check_slot_lines(c, "sweep_mean_pose", S, n, nLine, lines, &chains)) return rc;
     double tolT, tolR;
     if (int rc = mean_pose_tol(c, "sweep_mean_pose", tol, &tolT, &tolR)) return rc;
     HIPCHK(c, hipSetDevice(c->device));
@@ -4676,7 +4716,7 @@ extern "C" int raftx_sweep_mean_pose(raftx_ctx *c, int slot, int nLine, const do
     if (rc) return -2;
     if (int re = expand_lines(c, c->sCopy, n, nLine, L)) return re;
     HIPCHK(c, hipEventRecord(P.evUp, c->sCopy));
-    P.lines = L.lines; P.nLine = nLine; P.nX = nX; P.maxIter = max_iter; P.tolT = tolT; P.tolR = tolR;
+    P.lines = L.lines; P.nLine = nLine; P.chains = chains; P.nX = nX; P.maxIter = max_iter; P.tolT = tolT; P.tolR = tolR;
     P.pose_out = pose; P.Fres_out = F_res; P.iter_out = iterations; P.flags_out = flags;
     P.on = true;
     // the blocks whose phase 1 raftx_sweep_prepare enqueued; raftx_sweep_launch does the others behind their phase 1

@@ -9,6 +9,14 @@
 // chosen anew at every evaluation (contact: VF < wL with the anchor on the seabed).  The differences sF - 1, sF - sA and
 // 1/sF - 1/sA are written as quotients that do not cancel.
 //
+// A composite line (include/raftx_mooring.h: a head row and up to RAFTX_MOOR_MAX_SEG - 1 continuation rows, segments joined
+// at free points that may carry a weight or a buoy) has the same two unknowns: on a frictionless seabed HF is common to
+// every segment, and the vertical force at the top of segment i is VF minus the weight hanging above it, so X = sum X_i,
+// Z = sum Z_i and the Jacobian is the sum of the segments' (moor_chain_eval).  The lane of the head row solves the chain and
+// writes the records of all its rows; the lanes of continuation rows do nothing.  The chain code exists only in the
+// CHAINS instantiations, which the host picks when a batch holds a continuation row: single-row batches run the code and
+// give the bits they always did.
+//
 // Work decomposition: k_moor_line, one lane per (design, line), solves the line and leaves a record of MOOR_LW_N doubles
 // (force, arm, 3 x 3 stiffness at the fairlead, the gradients of both end tensions); k_moor_design, one lane per design,
 // adds the lines' shares of C_moor / F_moor in line order and writes T and J.  No atomics, no LDS: a design's bits
@@ -30,6 +38,7 @@ struct MoorArgs {
     double *__restrict__ line_out;      // [nDesign,nLine,MOOR_LO_N] or null
     double *__restrict__ C, *__restrict__ F, *__restrict__ T, *__restrict__ J;      // [nDesign,36] [.,6] [.,2 nLine] [.,2 nLine,6], each or null
     int *__restrict__ flags;            // [nDesign]
+    int chains;                         // host side only: a continuation row among the records, so the CHAINS kernels run
     double *__restrict__ Lr;            // [nDesign,2 nLine,3,6] or null: J as rows of k_sweep_channels (plane 0 = J, the other two zero)
 };
 
@@ -60,10 +69,211 @@ __device__ __forceinline__ void moor_eval(const double H, const double V, const 
     }
 }
 
+// The arm R r_f of the fairlead rec[3:6] with the rotation of geom_pose: the fairlead as end A of a unit vertical member, the
+// unit turned but not displaced; the displacement is added afterwards
+__device__ __forceinline__ void moor_arm(const double rec[RAFTX_ML_N], const double ps[6], double (&r)[3]) {
+    double gm[RAFTX_GM_N];
+    for (int i = 0; i < RAFTX_GM_N; i++) gm[i] = 0.0;
+    gm[RAFTX_GM_RA] = rec[3]; gm[RAFTX_GM_RA + 1] = rec[4]; gm[RAFTX_GM_RA + 2] = rec[5];
+    gm[RAFTX_GM_RB] = rec[3]; gm[RAFTX_GM_RB + 1] = rec[4]; gm[RAFTX_GM_RB + 2] = rec[5] + 1.0;
+    gm[RAFTX_GM_L] = 1.0;
+    const double pr[6] = {0.0, 0.0, 0.0, ps[3], ps[4], ps[5]};
+    double rA0[3], q[3], p1[3], p2[3], rB[3], R2[2][2];
+    geom_pose(gm, pr, rA0, q, p1, p2, r, rB, R2);
+}
+
+// ---- composite lines.  The segments of a chain, anchor side first; Wj is the net weight of the point at a segment's lower
+// end (0 for the anchor-side one).  Every loop over them is unrolled to RAFTX_MOOR_MAX_SEG so that they stay in registers.
+struct MoorChain {
+    int n;
+    double L[RAFTX_MOOR_MAX_SEG], EA[RAFTX_MOOR_MAX_SEG], w[RAFTX_MOOR_MAX_SEG], Wj[RAFTX_MOOR_MAX_SEG];
+};
+// X, Z and the Jacobian of the whole chain at the fairlead's (H, V): the sums of the segments', marching from the fairlead
+// down with V at the top of a segment = V less the segments and joints hanging above it.  Only the anchor-side segment may rest
+// on the seabed (moor_eval's contact branch with its own V); where all of it rests (V at its top <= 0) it is a straight
+// stretched length on the bed, which the contact branch approaches with a continuous Jacobian.  Vtop [n]: each segment's V.
+__device__ __forceinline__ void moor_chain_eval(const double H, const double V, const MoorChain &c, const bool seabed, MoorEval &e,
+                                                double Vtop[RAFTX_MOOR_MAX_SEG]) {
+    e.X = 0.0; e.Z = 0.0; e.a11 = 0.0; e.a12 = 0.0; e.a22 = 0.0; e.contact = 0;
+    double Vt = V;
+#pragma unroll
+    for (int i = RAFTX_MOOR_MAX_SEG - 1; i >= 0; i--) {
+        if (i >= c.n) continue;
+        Vtop[i] = Vt;
+        if (i == 0 && seabed && Vt <= 0.0) {
+            e.X += c.L[0] + H * c.L[0] / c.EA[0];
+            e.a11 += c.L[0] / c.EA[0];
+            e.contact = 1;
+        } else {
+            MoorEval s;
+            moor_eval(H, Vt, c.L[i], c.EA[i], c.w[i], seabed && i == 0, s);
+            e.X += s.X; e.Z += s.Z; e.a11 += s.a11; e.a12 += s.a12; e.a22 += s.a22;
+            if (i == 0) e.contact = s.contact;
+        }
+        Vt = (Vt - c.w[i] * c.L[i]) - c.Wj[i];
+    }
+}
+
+// A chain at the pose ps: the head row `line` and the nc continuation rows after it.  The records lw of all its rows and, where
+// lo_out is not null and the chain is not flagged, their line_out rows.  NOT inlined, and every argument a scalar or a pointer
+// to global memory: k_moor_line and k_mean_pose call one body, so the records of a chain are the same bits from both (for a
+// single line the two kernels' inlined copies of one source have always agreed; nothing promises that of a second, larger body).
+struct MoorPose { double v[6]; };
+__device__ __noinline__ void moor_chain_record(const double *__restrict__ line, const int nc, const MoorPose pose, const double depth,
+                                               double *__restrict__ lw, double *__restrict__ lo_out) {
+    double rec[RAFTX_ML_N], ps[6];
+#pragma unroll
+    for (int i = 0; i < RAFTX_ML_N; i++) rec[i] = line[i];
+#pragma unroll
+    for (int i = 0; i < 6; i++) ps[i] = pose.v[i];
+    MoorChain c;
+    c.n = nc + 1;
+    c.L[0] = rec[6]; c.EA[0] = rec[7]; c.w[0] = rec[8]; c.Wj[0] = 0.0;
+    bool fin = true;
+    for (int i = 0; i < 10; i++) fin = fin && isfinite(rec[i]);
+    for (int i = 0; i < 6; i++) fin = fin && isfinite(ps[i]);
+    bool pos = c.L[0] > 0.0 && c.EA[0] > 0.0 && c.w[0] > 0.0;
+    double Lt = c.L[0], Wt = c.w[0] * c.L[0];
+#pragma unroll
+    for (int i = 1; i < RAFTX_MOOR_MAX_SEG; i++) {
+        c.L[i] = 1.0; c.EA[i] = 1.0; c.w[i] = 1.0; c.Wj[i] = 0.0;
+        if (i >= c.n) continue;
+        const double *p = line + (size_t)i * RAFTX_ML_N;
+        c.L[i] = p[6]; c.EA[i] = p[7]; c.w[i] = p[8]; c.Wj[i] = p[RAFTX_ML_WJOINT];
+        fin = fin && isfinite(c.L[i]) && isfinite(c.EA[i]) && isfinite(c.w[i]) && isfinite(p[9]) && isfinite(c.Wj[i]);
+        pos = pos && c.L[i] > 0.0 && c.EA[i] > 0.0 && c.w[i] > 0.0;
+        Lt += c.L[i];
+        Wt += c.w[i] * c.L[i] + c.Wj[i];
+    }
+    const double az = rec[2];
+    int flag = 0;
+    double r[3] = {0, 0, 0}, XF = 0.0, ZF = 0.0, ux = 0.0, uy = 0.0;
+    if (!fin || !pos || !(Wt > 0.0) || az < -depth - 1e-6 * depth) flag = RAFTX_MOOR_BAD_LINE;
+    if (!flag) {
+        moor_arm(rec, ps, r);
+        const double dx = (ps[0] + r[0]) - rec[0], dy = (ps[1] + r[1]) - rec[1];
+        XF = sqrt(dx * dx + dy * dy);
+        ZF = (ps[2] + r[2]) - az;
+        ux = dx / XF;
+        uy = dy / XF;
+        if (!(ZF > 0.0)) flag = RAFTX_MOOR_BAD_LINE;
+        else if (XF <= 1e-9 * Lt) flag = RAFTX_MOOR_VERTICAL;
+        else if (Lt >= XF + ZF) flag = RAFTX_MOOR_SLACK;
+    }
+    double H = 0.0, V = 0.0, Vtop[RAFTX_MOOR_MAX_SEG] = {0, 0, 0, 0};
+    MoorEval e;
+    int it = 0;
+    if (!flag) {
+        const bool seabed = fabs(az + depth) <= 1e-6 * depth;
+        const double we = Wt / Lt;                                // the effective weight per length of the guess
+        const double lam = (Lt * Lt <= XF * XF + ZF * ZF) ? 0.2 : sqrt(3.0 * ((Lt * Lt - ZF * ZF) / (XF * XF) - 1.0));
+        H = fabs(we * XF / (2.0 * lam));
+        V = 0.5 * we * (ZF / tanh(lam) + Lt);
+        moor_chain_eval(H, V, c, seabed, e, Vtop);
+        double eX = e.X - XF, eZ = e.Z - ZF, res = fmax(fabs(eX), fabs(eZ)) / Lt, a = 1.0;
+        bool conv = res == 0.0;
+        while (!conv && it < MOOR_MAX_IT) {
+            it++;
+            const double det = e.a11 * e.a22 - e.a12 * e.a12;
+            const double dH = -(e.a22 * eX - e.a12 * eZ) / det, dV = -(e.a11 * eZ - e.a12 * eX) / det;
+            double s = a;
+            if (H + s * dH <= 0.0) s = -0.5 * H / dH;
+            const double Ht = H + s * dH, Vt = V + s * dV;
+            MoorEval n;
+            double Vn[RAFTX_MOOR_MAX_SEG] = {0, 0, 0, 0};
+            moor_chain_eval(Ht, Vt, c, seabed, n, Vn);
+            const double nX = n.X - XF, nZ = n.Z - ZF, rn = fmax(fabs(nX), fabs(nZ)) / Lt;
+            if (rn < res) {
+                H = Ht; V = Vt; e = n; eX = nX; eZ = nZ; res = rn; a = 1.0;
+#pragma unroll
+                for (int i = 0; i < RAFTX_MOOR_MAX_SEG; i++) Vtop[i] = Vn[i];
+                conv = res == 0.0;
+            } else if (res <= MOOR_TIGHT) {
+                conv = true;
+            } else {
+                a *= 0.5;
+                if (a < 0x1p-40) break;
+            }
+        }
+        if (!conv) flag = RAFTX_MOOR_NO_CONVERGENCE;
+        else if (seabed && Vtop[0] <= 0.0) flag = RAFTX_MOOR_GROUNDED;      // the anchor-side segment rests wholly: so would its upper joint
+        else {
+            // the joints and the sags (where V changes sign inside a segment) against the seabed, from the anchor up
+            const double floor = -depth - 1e-6 * depth;
+            double z = az;
+#pragma unroll
+            for (int i = 0; i < RAFTX_MOOR_MAX_SEG; i++) {
+                if (i >= c.n) continue;
+                const double Vb = Vtop[i] - c.w[i] * c.L[i];
+                if (!(i == 0 && e.contact) && Vb < 0.0 && Vtop[i] > 0.0) {
+                    const double vb = Vb / H, sb = sqrt(1.0 + vb * vb);
+                    const double drop = (H / c.w[i]) * (vb * vb / (sb + 1.0)) + Vb * Vb / (2.0 * c.EA[i] * c.w[i]);
+                    if (z - drop < floor) flag = RAFTX_MOOR_GROUNDED;
+                }
+                MoorEval s;
+                moor_eval(H, Vtop[i], c.L[i], c.EA[i], c.w[i], seabed && i == 0, s);
+                z += s.Z;
+                if (i + 1 < c.n && z < floor) flag = RAFTX_MOOR_GROUNDED;
+            }
+        }
+    }
+    if (!flag) {
+        const double det = e.a11 * e.a22 - e.a12 * e.a12;
+        const double k11 = e.a22 / det, k12 = -e.a12 / det, k22 = e.a11 / det;
+        const double th = H / XF;
+#pragma unroll
+        for (int i = 0; i < RAFTX_MOOR_MAX_SEG; i++) {
+            if (i >= c.n) continue;
+            double *q = lw + (size_t)i * MOOR_LW_N;
+            const bool ct = i == 0 && e.contact;
+            const double VB = Vtop[i], VA = ct ? 0.0 : VB - c.w[i] * c.L[i];
+            const double TB = sqrt(H * H + VB * VB), TA = sqrt(H * H + VA * VA);
+            if (i == 0) {
+                q[0] = -H * ux; q[1] = -H * uy; q[2] = -V;
+                q[6] = k11 * ux * ux + th * (1.0 - ux * ux);
+                q[7] = k11 * ux * uy - th * (ux * uy);
+                q[8] = k12 * ux;
+                q[9] = q[7];
+                q[10] = k11 * uy * uy + th * (1.0 - uy * uy);
+                q[11] = k12 * uy;
+                q[12] = q[8];
+                q[13] = q[11];
+                q[14] = k22;
+            } else {
+                q[0] = 0.0; q[1] = 0.0; q[2] = 0.0;
+                for (int k = 6; k < 15; k++) q[k] = 0.0;
+            }
+            q[3] = r[0]; q[4] = r[1]; q[5] = r[2];
+            const double gAX = (H * k11 + VA * k12) / TA, gAZ = (H * k12 + VA * k22) / TA;
+            const double gBX = (H * k11 + VB * k12) / TB, gBZ = (H * k12 + VB * k22) / TB;
+            q[15] = gAX * ux; q[16] = gAX * uy; q[17] = gAZ;
+            q[18] = gBX * ux; q[19] = gBX * uy; q[20] = gBZ;
+            q[21] = TA;
+            q[22] = TB;
+            double *o = lo_out ? lo_out + (size_t)i * MOOR_LO_N : nullptr;
+            if (o) {
+                o[0] = H; o[1] = VB; o[2] = H; o[3] = VA;
+                o[4] = ct ? c.L[0] - VB / c.w[0] : 0.0;
+                o[5] = (double)it;
+                o[6] = ct ? 1.0 : 0.0;
+                o[7] = 0.0;
+            }
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < RAFTX_MOOR_MAX_SEG; i++)
+        if (i < c.n) lw[(size_t)i * MOOR_LW_N + 23] = (double)flag;
+}
+
 // One line at the pose ps: the record lw [MOOR_LW_N] (in global memory) and lo [MOOR_LO_N].  The body of k_moor_line, shared
-// with k_mean_pose (raftx_statics.h).
-__device__ __forceinline__ void moor_line_record(const double *__restrict__ line, const double ps[6], const double depth,
-                                                 double *__restrict__ lw, double lo[MOOR_LO_N]) {
+// with k_mean_pose (raftx_statics.h).  Returns true: lo is this row's line_out.  CHAINS: `line` may be the head row of a
+// composite line, with its continuation rows among the nAfter rows of the design that follow it -- then the records of all of
+// them are written, and their line_out rows at lo_out (this row's place in global memory, or null) unless the chain is flagged
+// -- or a continuation row itself, for which nothing is written; false is returned in both cases.
+template <bool CHAINS>
+__device__ __forceinline__ bool moor_line_record(const double *__restrict__ line, const int nAfter, const double ps[6],
+                                                 const double depth, double *__restrict__ lw, double lo[MOOR_LO_N],
+                                                 double *__restrict__ lo_out) {
     double rec[RAFTX_ML_N];
     {
         const double2 *p = reinterpret_cast<const double2 *>(line);
@@ -76,6 +286,18 @@ __device__ __forceinline__ void moor_line_record(const double *__restrict__ line
     }
     const double nan = __longlong_as_double(0x7ff8000000000000LL);
     for (int i = 0; i < MOOR_LO_N; i++) lo[i] = nan;
+    if (CHAINS) {
+        if (rec[RAFTX_ML_CONT] != 0.0) return false;
+        int nc = 0;
+        while (nc < nAfter && nc < RAFTX_MOOR_MAX_SEG - 1 && line[(size_t)(nc + 1) * RAFTX_ML_N + RAFTX_ML_CONT] != 0.0) nc++;
+        if (nc) {
+            MoorPose pose;
+#pragma unroll
+            for (int i = 0; i < 6; i++) pose.v[i] = ps[i];
+            moor_chain_record(line, nc, pose, depth, lw, lo_out);
+            return false;
+        }
+    }
     int flag = 0;
     bool fin = true;
     for (int i = 0; i < 10; i++) fin = fin && isfinite(rec[i]);
@@ -84,16 +306,7 @@ __device__ __forceinline__ void moor_line_record(const double *__restrict__ line
     double r[3] = {0, 0, 0}, XF = 0.0, ZF = 0.0, ux = 0.0, uy = 0.0;
     if (!fin || !(L > 0.0) || !(EA > 0.0) || !(w > 0.0) || az < -depth - 1e-6 * depth) flag = RAFTX_MOOR_BAD_LINE;
     if (!flag) {
-        // the arm R r_f with the rotation of geom_pose: the fairlead as end A of a unit vertical member, the unit turned but
-        // not displaced; the displacement is added afterwards
-        double gm[RAFTX_GM_N];
-        for (int i = 0; i < RAFTX_GM_N; i++) gm[i] = 0.0;
-        gm[RAFTX_GM_RA] = rec[3]; gm[RAFTX_GM_RA + 1] = rec[4]; gm[RAFTX_GM_RA + 2] = rec[5];
-        gm[RAFTX_GM_RB] = rec[3]; gm[RAFTX_GM_RB + 1] = rec[4]; gm[RAFTX_GM_RB + 2] = rec[5] + 1.0;
-        gm[RAFTX_GM_L] = 1.0;
-        const double pr[6] = {0.0, 0.0, 0.0, ps[3], ps[4], ps[5]};
-        double rA0[3], q[3], p1[3], p2[3], rB[3], R2[2][2];
-        geom_pose(gm, pr, rA0, q, p1, p2, r, rB, R2);
+        moor_arm(rec, ps, r);
         const double dx = (ps[0] + r[0]) - rec[0], dy = (ps[1] + r[1]) - rec[1];
         XF = sqrt(dx * dx + dy * dy);
         ZF = (ps[2] + r[2]) - az;
@@ -164,8 +377,10 @@ __device__ __forceinline__ void moor_line_record(const double *__restrict__ line
         }
     }
     lw[23] = (double)flag;
+    return true;
 }
 
+template <bool CHAINS>
 __global__ void __launch_bounds__(MOOR_THREADS) k_moor_line(MoorArgs A) {
     const long long t = (long long)blockIdx.x * MOOR_THREADS + threadIdx.x;
     if (t >= (long long)A.nDesign * A.nLine) return;
@@ -174,8 +389,10 @@ __global__ void __launch_bounds__(MOOR_THREADS) k_moor_line(MoorArgs A) {
     if (A.pose)
         for (int i = 0; i < 6; i++) ps[i] = A.pose[(size_t)d * 6 + i];
     double lo[MOOR_LO_N];
-    moor_line_record(A.lines + (size_t)t * RAFTX_ML_N, ps, A.depth, A.lw + (size_t)t * MOOR_LW_N, lo);
-    if (A.line_out)
+    const bool mine = moor_line_record<CHAINS>(A.lines + (size_t)t * RAFTX_ML_N, A.nLine - 1 - (int)(t % A.nLine), ps, A.depth,
+                                               A.lw + (size_t)t * MOOR_LW_N, lo,
+                                               A.line_out ? A.line_out + (size_t)t * MOOR_LO_N : nullptr);
+    if (A.line_out && mine)
         for (int i = 0; i < MOOR_LO_N; i++) A.line_out[(size_t)t * MOOR_LO_N + i] = lo[i];
 }
 

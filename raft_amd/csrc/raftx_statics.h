@@ -33,6 +33,7 @@ struct MeanPoseArgs {
     double *__restrict__ pose, *__restrict__ C, *__restrict__ F, *__restrict__ T, *__restrict__ J, *__restrict__ Fres;   // each or null
     int *__restrict__ iterations;       // [nDesign] or null
     int *__restrict__ flags;            // [nDesign]
+    int chains;                         // host side only: a continuation row among the records, so k_mean_pose<true> runs
 };
 
 // dX = K^-1 Y by Gaussian elimination of [K | Y] with partial pivoting (the first row of the largest |a|, as LAPACK's gesv
@@ -86,6 +87,7 @@ __device__ __forceinline__ bool mp_solve(const double K[36], const double Y[6], 
     return ok;
 }
 
+template <bool CHAINS>
 __global__ void __launch_bounds__(MP_THREADS) k_mean_pose(MeanPoseArgs A) {
     const int G = A.G, nL = A.nLine;
     const int d = blockIdx.x * (MP_THREADS / G) + (int)threadIdx.x / G, g = (int)threadIdx.x % G;
@@ -101,7 +103,8 @@ __global__ void __launch_bounds__(MP_THREADS) k_mean_pose(MeanPoseArgs A) {
         if (phase < 2)
             for (int l = g; l < nL; l += G) {
                 double lo[MOOR_LO_N];
-                moor_line_record(A.lines + (dd * nL + l) * RAFTX_ML_N, x, A.depth, lw0 + (size_t)l * MOOR_LW_N, lo);
+                moor_line_record<CHAINS>(A.lines + (dd * nL + l) * RAFTX_ML_N, nL - 1 - l, x, A.depth, lw0 + (size_t)l * MOOR_LW_N, lo,
+                                         nullptr);
             }
         __syncthreads();                                         // the group's records are in memory
         if (phase < 2) {

@@ -12,7 +12,10 @@ from .strips import UnsupportedFOWT
 
 ML_N = 16
 ML_ANCHOR, ML_FAIRLEAD, ML_L, ML_EA, ML_W, ML_CB = 0, 3, 6, 7, 8, 9
+ML_WJOINT, ML_CONT = 10, 15    # continuation rows of a composite line: the weight of the point at the lower end; the mark
+MAX_SEG = 4                    # rows of one composite line, at most
 FLAG_BAD_LINE, FLAG_VERTICAL, FLAG_SLACK, FLAG_NO_CONVERGENCE = 1, 2, 4, 8
+FLAG_GROUNDED = 64
 
 
 def lines_from_design(design, rho=1025.0, g=9.81):
@@ -65,6 +68,94 @@ def lines_from_design(design, rho=1025.0, g=9.81):
     return np.ascontiguousarray(recs), depth
 
 
+def chains_from_design(design, rho=1025.0, g=9.81):
+    """Row records [nRow,16] of ``design['mooring']`` with COMPOSITE lines: segments joined at ``free`` (or ``connection``)
+    points that exactly two lines meet at, followed from each ``fixed`` point to a ``vessel`` point.  A line's rows are
+    consecutive, anchor -> fairlead: the head row as in ``lines_from_design`` with the anchor-side segment's L, EA, w, then
+    a continuation row per further segment (field 15 = 1, its own L, EA, w, and in field 10 the net submerged weight
+    (m - rho v) g of the point at its lower end).  Lines come in the order of the ``lines`` list's anchor-side segments.
+    Returns (records, depth, row_names); for a deck without free points the records are those of ``lines_from_design``."""
+    moor = design.get("mooring") if isinstance(design, dict) else None
+    if not isinstance(moor, dict):
+        raise UnsupportedFOWT("the design has no mooring section")
+    if "file" in moor:
+        raise UnsupportedFOWT("the mooring system is a MoorDyn file (%s): only the YAML section is parsed" % moor["file"])
+    if int(moor.get("moorMod", 0)) != 0:
+        raise UnsupportedFOWT("moorMod = %s: line dynamics are not covered (moorMod 0 only)" % moor.get("moorMod"))
+    depth = float(moor["water_depth"])
+    points = {}
+    for p in moor.get("points", []):
+        kind = str(p.get("type", "")).lower()
+        kind = "free" if kind == "connection" else kind
+        if kind not in ("fixed", "vessel", "free"):
+            raise UnsupportedFOWT("mooring point %r is of type %r" % (p.get("name"), p.get("type")))
+        weight = (float(p.get("m", 0.0)) - rho * float(p.get("v", 0.0))) * g
+        points[p["name"]] = (kind, np.array(p["location"], dtype=float).reshape(3), weight)
+    types = {t["name"]: t for t in moor.get("line_types", [])}
+    lines = list(moor.get("lines", []))
+    if not lines:
+        raise UnsupportedFOWT("the mooring section has no lines")
+    at = {}                                                      # point -> the lines that end there
+    for i, ln in enumerate(lines):
+        for end in ("endA", "endB"):
+            if ln[end] not in points:
+                raise UnsupportedFOWT("mooring line %r: unknown point %r" % (ln.get("name"), ln[end]))
+            at.setdefault(ln[end], []).append(i)
+        if ln["type"] not in types:
+            raise UnsupportedFOWT("mooring line %r: unknown line type %r" % (ln.get("name"), ln["type"]))
+        if points[ln["endA"]][0] == "vessel" and points[ln["endB"]][0] == "vessel":
+            raise UnsupportedFOWT("mooring line %r has both ends on the vessel" % ln.get("name"))
+    for name, (kind, _, _) in points.items():
+        k = len(at.get(name, []))
+        if k > 2 or (k == 2 and kind != "free"):
+            raise UnsupportedFOWT("mooring point %r joins %d lines: bridles and shared anchors or fairleads are not covered" % (name, k))
+        if kind == "free" and k == 1:
+            raise UnsupportedFOWT("free mooring point %r ends a single line: a dangling end is not covered" % name)
+
+    def other(ln, name):
+        return ln["endB"] if ln["endA"] == name else ln["endA"]
+
+    recs, names, used = [], [], set()
+    for i, ln in enumerate(lines):
+        ends = [e for e in ("endA", "endB") if points[ln[e]][0] == "fixed"]
+        if not ends or i in used:
+            continue
+        if len(ends) == 2:
+            raise UnsupportedFOWT("mooring line %r runs between two fixed points" % ln.get("name"))
+        here, rows, cur = ln[ends[0]], 0, i
+        anchor = points[here][1]
+        first = len(recs)
+        while True:
+            seg = lines[cur]
+            used.add(cur)
+            t = types[seg["type"]]
+            d = float(t["diameter"])
+            rec = np.zeros(ML_N)
+            rec[ML_L] = float(seg["length"])
+            rec[ML_EA] = float(t["stiffness"])
+            rec[ML_W] = (float(t["mass_density"]) - rho * (np.pi / 4 * d * d)) * g
+            if rows:
+                rec[ML_WJOINT], rec[ML_CONT] = points[here][2], 1.0
+            recs.append(rec)
+            names.append(seg.get("name", "line%d" % (cur + 1)))
+            rows += 1
+            if rows > MAX_SEG:
+                raise UnsupportedFOWT("the mooring line from %r has more than %d segments" % (ln[ends[0]], MAX_SEG))
+            here = other(seg, here)
+            kind = points[here][0]
+            if kind == "vessel":
+                break
+            if kind == "fixed":
+                raise UnsupportedFOWT("the mooring line from %r ends at the fixed point %r" % (ln[ends[0]], here))
+            cur = [j for j in at[here] if j != cur][0]
+        recs[first][ML_ANCHOR:ML_ANCHOR + 3] = anchor
+        recs[first][ML_FAIRLEAD:ML_FAIRLEAD + 3] = points[here][1]
+    left = [lines[j].get("name", "line%d" % (j + 1)) for j in range(len(lines)) if j not in used]
+    if left:
+        raise UnsupportedFOWT("mooring line %r belongs to a chain without a fixed end" % left[0])
+    return np.ascontiguousarray(recs), depth, names
+
+
 def tension_names(n):
     """Names of the 2 n tension channels in the order of T / J: ends A of all lines, then ends B (getTensions)."""
     return ["Tmoor_A%d" % (i + 1) for i in range(n)] + ["Tmoor_B%d" % (i + 1) for i in range(n)]
@@ -87,7 +178,10 @@ class MooringProgram:
         return len(self.lines)
 
     def ends(self, l, anchor, fairlead):
-        """Anchor and fairlead of line l: [3][nParam+1] rows of coefficients each (constant, then one per parameter)."""
+        """Anchor and fairlead of line l: [3][nParam+1] rows of coefficients each (constant, then one per parameter).
+        Of a composite line they are the head row's: a continuation row is refused."""
+        if self.lines[l, ML_CONT] != 0:
+            raise ValueError("row %d is a continuation row of a composite line: its anchor and fairlead are the head row's" % l)
         self.coef[l, :3] = np.asarray(anchor, dtype=float).reshape(3, self.n_param + 1)
         self.coef[l, 3:] = np.asarray(fairlead, dtype=float).reshape(3, self.n_param + 1)
         self.edit[l] = 1
