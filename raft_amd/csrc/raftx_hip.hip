@@ -972,8 +972,11 @@ struct raftx_ctx {
     SweepSlot slots[RAFTX_NSLOT];        // crossings in flight (raftx_sweep_prepare / _launch / _wait)
     // ---- buffers outside the pool
     DevBuf<double> rXl;
-    DevBuf<cplx> flexXl0;                // raftx_flex_start: the linearisation point of the next raftx_flex_solve (device copy)
-    size_t flexXl0_n = 0;                // entries set (0: none)
+    struct FlexStart {                   // raftx_flex_start: the linearisation point of the next raftx_flex_solve, one-shot
+        DevBuf<cplx> x;                  // device copy
+        size_t n = 0;                    // entries set (0: none)
+        size_t take() { return std::exchange(n, (size_t)0); }   // the size of a pending start, which is spent with this
+    } flexStart;
     DevBuf<unsigned long long> rXlSlots;
     DevBuf<unsigned> kpCtr;              // claim counters of the persistent fused launches: a ring of KP_RING sets of 8 (one per XCD slab, 128 B apart)
     DevBuf<cplx> rQtf;                   // QTFs of the last raftx_qtf_slender call, kept for raftx_qtf_force
@@ -2568,24 +2571,35 @@ static bool dense_reg_shape(int n, int nRhs) {
     static const bool dense_l2 = getenv("RAFTX_DENSE_L2") && atoi(getenv("RAFTX_DENSE_L2"));     // tuning / tests: the L2-workspace kernel
     return !dense_l2 && n + nRhs <= 160;
 }
-static int dense_launch(raftx_ctx *c, int nSys, int mdiv, int n, int nRhs, int nw, const double *dw, const double *dM, const double *dB,
-                        const double *dC, int freq_mask, const double *dBadd, const cplx *dF, cplx *dX, cplx *dZ, cplx *dA,
-                        const int *dActive = nullptr) {
-    const dim3 grid((unsigned)nw, (unsigned)nSys);
-    if (dense_reg_shape(n, nRhs)) {
+// size of the L2-workspace kernel's block A, in elements: 0 where the register kernel takes the shape
+static size_t dense_workspace(int nSys, int n, int nRhs, int nw) {
+    return dense_reg_shape(n, nRhs) ? 0 : (size_t)nSys * nw * n * (n + nRhs);
+}
+struct DenseSolve {                      // one launch; optional: Badd [nSys,n,n] on top of B, active (0: system skipped), Z out
+    int nSys, mdiv, n, nRhs, nw;
+    const double *w, *M, *B, *C;
+    int freq_mask;
+    const double *Badd = nullptr;
+    const int *active = nullptr;
+    const cplx *F = nullptr;
+    cplx *X = nullptr, *Z = nullptr, *A = nullptr;       // A: dense_workspace() elements
+};
+static int dense_launch(raftx_ctx *c, const DenseSolve &d) {
+    const dim3 grid((unsigned)d.nw, (unsigned)d.nSys);
+    if (dense_reg_shape(d.n, d.nRhs)) {
 #define DENSE_REG_(RB_, CB_)                                                                                            \
-        hipLaunchKernelGGL((k_solve_dense_reg2<RB_, CB_, 16>), grid, dim3(512), 0, c->stream, n, nRhs, nw, dw, dM, dB, dC, freq_mask, \
-                           mdiv, dBadd, dActive, dF, dX, dZ)
+        hipLaunchKernelGGL((k_solve_dense_reg2<RB_, CB_, 16>), grid, dim3(512), 0, c->stream, d.n, d.nRhs, d.nw, d.w, d.M, d.B, d.C, \
+                           d.freq_mask, d.mdiv, d.Badd, d.active, d.F, d.X, d.Z)
         // entries per thread: the smallest 32 RB x 16 CB grid that holds [Z | F] (measured at 60 DOFs: 0.076 ms with 3 x 6
         // against 0.136 with 5 x 10 and 0.23 for the L2-workspace kernel)
-        if (n + nRhs <= 32) DENSE_REG_(1, 2);
-        else if (n + nRhs <= 64) DENSE_REG_(2, 4);
-        else if (n + nRhs <= 96) DENSE_REG_(3, 6);
-        else if (n + nRhs <= 128) DENSE_REG_(4, 8);
+        if (d.n + d.nRhs <= 32) DENSE_REG_(1, 2);
+        else if (d.n + d.nRhs <= 64) DENSE_REG_(2, 4);
+        else if (d.n + d.nRhs <= 96) DENSE_REG_(3, 6);
+        else if (d.n + d.nRhs <= 128) DENSE_REG_(4, 8);
         else DENSE_REG_(5, 10);
 #undef DENSE_REG_
     } else {
-        hipLaunchKernelGGL(k_solve_dense, grid, dim3(256), 0, c->stream, n, nRhs, nw, dw, dM, dB, dC, freq_mask, mdiv, dBadd, dActive, dF, dA, dX, dZ);
+        hipLaunchKernelGGL(k_solve_dense, grid, dim3(256), 0, c->stream, d.n, d.nRhs, d.nw, d.w, d.M, d.B, d.C, d.freq_mask, d.mdiv, d.Badd, d.active, d.F, d.A, d.X, d.Z);
     }
     HIPCHK(c, hipGetLastError());
     return 0;
@@ -2605,15 +2619,16 @@ static int solve_dense_impl(raftx_ctx *c, int nSys, int n, int nRhs, int nw, con
     if (nSys == 0) return 0;
     HIPCHK(c, hipSetDevice(c->device));
     Scratch sc(c);
-    const bool reg = dense_reg_shape(n, nRhs);
     const size_t nn = (size_t)n * n, nf = (size_t)nSys * nRhs * n * nw;
-    double *dw = sc.in<double>(w, nw), *dM = sc.in<double>(M, (size_t)nSys * nn * ((freq_mask & 1) ? nw : 1)),
-           *dB = sc.in<double>(B, (size_t)nSys * nn * ((freq_mask & 2) ? nw : 1)), *dC = sc.in<double>(C, (size_t)nSys * nn);
-    cplx *dF = sc.in<cplx>(F, nf), *dX = sc.out<cplx>(Xi, nf), *dZ = sc.out<cplx>(Z, (size_t)nSys * nn * nw);
-    cplx *dA = reg ? nullptr : sc.tmp<cplx>((size_t)nSys * nw * n * (n + nRhs));
+    DenseSolve d;
+    d.nSys = nSys; d.mdiv = 1; d.n = n; d.nRhs = nRhs; d.nw = nw; d.freq_mask = freq_mask;
+    d.w = sc.in<double>(w, nw); d.M = sc.in<double>(M, (size_t)nSys * nn * ((freq_mask & 1) ? nw : 1));
+    d.B = sc.in<double>(B, (size_t)nSys * nn * ((freq_mask & 2) ? nw : 1)); d.C = sc.in<double>(C, (size_t)nSys * nn);
+    d.F = sc.in<cplx>(F, nf); d.X = sc.out<cplx>(Xi, nf); d.Z = sc.out<cplx>(Z, (size_t)nSys * nn * nw);
+    d.A = sc.tmp<cplx>(dense_workspace(nSys, n, nRhs, nw));
     if (int rc = sc.upload("solve_dense")) return rc;
     if (sc.begin()) return -2;
-    if (dense_launch(c, nSys, 1, n, nRhs, nw, dw, dM, dB, dC, freq_mask, nullptr, dF, dX, dZ, dA)) return -1;
+    if (dense_launch(c, d)) return -1;
     return sc.finish();
 }
 extern "C" int raftx_solve_dense(raftx_ctx *c, int n, int nRhs, int nw, const double *w, const double *M, const double *B,
@@ -2662,35 +2677,145 @@ extern "C" int raftx_solve_dense_resident(raftx_ctx *c, int nPer, const double *
     if (dense_check(c, "solve_dense_resident", nSys, n, nRhs, nw)) return -1;
     HIPCHK(c, hipSetDevice(c->device));
     Scratch sc(c);
-    const bool reg = dense_reg_shape(n, nRhs);
     const size_t nn = (size_t)n * n, nf = (size_t)nSys * nRhs * n * nw;
-    double *dBadd = sc.in<double>(Badd, (size_t)nSys * nn);
-    cplx *dF = sc.in<cplx>(F, nf), *dX = sc.out<cplx>(Xi, nf), *dZ = sc.out<cplx>(Z, (size_t)nSys * nn * nw);
-    cplx *dA = reg ? nullptr : sc.tmp<cplx>((size_t)nSys * nw * n * (n + nRhs));
+    DenseSolve d;
+    d.nSys = nSys; d.mdiv = nPer; d.n = n; d.nRhs = nRhs; d.nw = nw; d.freq_mask = R.freq_mask;
+    d.w = R.w; d.M = R.M; d.B = R.B; d.C = R.C; d.Badd = sc.in<double>(Badd, (size_t)nSys * nn);
+    d.F = sc.in<cplx>(F, nf); d.X = sc.out<cplx>(Xi, nf); d.Z = sc.out<cplx>(Z, (size_t)nSys * nn * nw);
+    d.A = sc.tmp<cplx>(dense_workspace(nSys, n, nRhs, nw));
     if (int rc = sc.upload("solve_dense_resident")) return rc;
     if (sc.begin()) return -2;
-    if (dense_launch(c, nSys, nPer, n, nRhs, nw, R.w, R.M, R.B, R.C, R.freq_mask, dBadd, dF, dX, dZ, dA)) return -1;
+    if (dense_launch(c, d)) return -1;
     return sc.finish();
 }
 
 // include/raftx.h raftx_flex_start: the next raftx_flex_solve starts from this iterate (one-shot)
 extern "C" int raftx_flex_start(raftx_ctx *c, int nUnit, int n, const raftx_c128 *XiLast0) {
     if (!c) return -1;
-    c->flexXl0_n = 0;
+    c->flexStart.take();
     if (!XiLast0) return 0;
     if (check_ready(c)) return -1;
     const DevTables &T = c->T;
     if (nUnit < 1 || n < 6) FAIL(c, "flex_start: bad arguments (nUnit=%d, n=%d)", nUnit, n);
     HIPCHK(c, hipSetDevice(c->device));
     const size_t need = (size_t)nUnit * T.nCase * n * T.nw;
-    if (grow_device(c, c->flexXl0, need)) return -2;
-    H2D(c, c->flexXl0.p, XiLast0, need * sizeof(cplx));
+    if (grow_device(c, c->flexStart.x, need)) return -2;
+    H2D(c, c->flexStart.x.p, XiLast0, need * sizeof(cplx));
     HIPCHK(c, hipStreamSynchronize(c->stream));           // the caller's array is free again
-    c->flexXl0_n = need;
+    c->flexStart.n = need;
     return 0;
 }
 
-// The fixed point of flexible units on the device (raftx_flex.h; include/raftx.h raftx_flex_solve).
+// The fixed point of flexible units on the device (raftx_flex.h; include/raftx.h raftx_flex_solve): the counts of a call,
+// its device arrays, and its steps in the order raftx_flex_solve takes them.
+struct FlexShape {
+    int nUnit, nNode, nCase, nHead, nw, n, nSys, freq_mask;
+    size_t nn, nxs, npn, nM, nB, nxl, nxh;               // n^2, n nw, nodes x sea states, entries of M, of B, of one iterate, of all headings
+    bool started;                                         // raftx_flex_start gave the first iterate
+};
+struct FlexArrays {
+    double *M, *B, *C, *Tn, *W, *Bn, *Bd;
+    int64_t *off;
+    int *nodeUnit, *act, *ni, *fl, *count, *iter;
+    cplx *Flin, *XiN, *Fn, *Fw, *Fd, *rhs, *Xnew, *Xi, *Xl, *Xh, *A, *Z;
+};
+static DenseSolve flex_dense(const raftx_ctx *c, const FlexShape &S, const FlexArrays &A) {   // what the two solves of the fixed point share
+    DenseSolve d;
+    d.nSys = S.nSys; d.mdiv = S.nCase; d.n = S.n; d.nw = S.nw; d.freq_mask = S.freq_mask;
+    d.w = c->T.w; d.M = A.M; d.B = A.B; d.C = A.C; d.Badd = A.Bd; d.A = A.A;
+    return d;
+}
+// the shape of the call against the resident tables; a pending start is taken here, whether it fits or not
+static int flex_check(raftx_ctx *c, int nUnit, const int64_t *nodeOff, int n, int freq_mask, FlexShape &S) {
+    const DevTables &T = c->T;
+    S.nUnit = nUnit; S.nNode = T.nDesign; S.nCase = T.nCase; S.nHead = T.nHead; S.nw = T.nw; S.n = n; S.nSys = nUnit * T.nCase;
+    if (nodeOff[0] != 0 || nodeOff[nUnit] != S.nNode) FAIL(c, "flex_solve: nodeOff must run from 0 to the %d resident node tables", S.nNode);
+    for (int u = 0; u < nUnit; u++)
+        if (nodeOff[u + 1] < nodeOff[u]) FAIL(c, "flex_solve: node offsets not monotone");
+    if (dense_check(c, "flex_solve", S.nSys, n, S.nHead, S.nw)) return -1;
+    if (n < 6) FAIL(c, "flex_solve: n = %d reduced DOFs", n);
+    if (!S.nSys || !S.nNode) FAIL(c, "flex_solve: device allocation failed");   // (no sea states, no nodes: the wording the empty blocks always had)
+    S.freq_mask = freq_mask;
+    S.nn = (size_t)n * n; S.nxs = (size_t)n * S.nw; S.npn = (size_t)S.nNode * S.nCase;
+    S.nM = nUnit * S.nn * ((freq_mask & 1) ? S.nw : 1); S.nB = nUnit * S.nn * ((freq_mask & 2) ? S.nw : 1);
+    S.nxl = S.nSys * S.nxs; S.nxh = S.nxl * S.nHead;
+    const size_t had = c->flexStart.take();
+    S.started = had != 0;
+    if (had && had != S.nxl) FAIL(c, "flex_solve: the linearisation point of raftx_flex_start has %zu entries, this call %zu", had, S.nxl);
+    return 0;
+}
+static int flex_reset(raftx_ctx *c, const FlexShape &S, const FlexArrays &A) {
+    HIPCHK(c, hipMemsetAsync(A.ni, 0, S.nSys * sizeof(int), c->stream));
+    HIPCHK(c, hipMemsetAsync(A.fl, 0, S.nSys * sizeof(int), c->stream));
+    HIPCHK(c, hipMemsetAsync(A.Bd, 0, S.nSys * S.nn * sizeof(double), c->stream));
+    HIPCHK(c, hipMemsetAsync(A.Xi, 0, S.nxl * sizeof(cplx), c->stream));
+    HIPCHK(c, hipMemsetAsync(A.Fd, 0, S.nxh * sizeof(cplx), c->stream));
+    return 0;
+}
+static int flex_first_iterate(raftx_ctx *c, const FlexShape &S, const FlexArrays &A, double XiStart) {
+    if (S.started)
+        HIPCHK(c, hipMemcpyAsync(A.Xl, c->flexStart.x.p, S.nxl * sizeof(cplx), hipMemcpyDeviceToDevice, c->stream));
+    else
+        hipLaunchKernelGGL(k_flex_fill, dim3((unsigned)((S.nxl + 255) / 256)), dim3(256), 0, c->stream, S.nxl, cplx{XiStart, 0.0}, A.Xl);   // :999
+    return 0;
+}
+// one iteration: node motions -> linearisation of every (node, sea state) -> projections with the units' T -> dense solves ->
+// convergence test / relaxation -> the count of pairs still iterating to the host (the ctx's page-locked area)
+static int flex_iteration(raftx_ctx *c, const FlexShape &S, const FlexArrays &A, double tol) {
+    const int nt = (S.n + 15) / 16;
+    const dim3 gridB((unsigned)((nt * nt + 3) / 4), (unsigned)S.nSys), gridF((unsigned)((S.nxs + 255) / 256), (unsigned)(S.nSys * S.nHead));
+    hipLaunchKernelGGL(k_flex_node_motion, dim3((unsigned)S.npn), dim3(256), 0, c->stream, S.nCase, S.n, S.nw, A.nodeUnit, A.Tn, A.Xl, A.XiN);
+    if (linearize_enqueue(c, A.XiN, A.Bn, A.Fn, false)) return -1;
+    hipLaunchKernelGGL(k_flex_w, dim3((unsigned)S.npn), dim3(256), 0, c->stream, S.nNode, S.nCase, S.n, A.Tn, A.Bn, A.W);
+    hipLaunchKernelGGL(k_flex_gemm_B, gridB, dim3(256), 0, c->stream, S.nNode, S.nCase, S.n, A.off, A.Tn, A.W, A.act, A.Bd);
+    hipLaunchKernelGGL(k_flex_project_F, gridF, dim3(256), 0, c->stream, S.nCase, S.nHead, S.n, S.nw, A.off, A.Tn, A.Fn, A.Flin, A.act, A.Fw, A.Fd, A.rhs);
+    DenseSolve d = flex_dense(c, S, A);
+    d.nRhs = 1; d.active = A.act; d.F = A.rhs; d.X = A.Xnew;
+    if (dense_launch(c, d)) return -1;
+    HIPCHK(c, hipMemsetAsync(A.count, 0, sizeof(int), c->stream));
+    hipLaunchKernelGGL(k_flex_converge, dim3((unsigned)S.nSys), dim3(256), 0, c->stream, S.n, S.nw, tol, A.iter, A.Xnew, A.Xi, A.Xl, A.act, A.ni, A.fl, A.count);
+    hipLaunchKernelGGL(k_flex_tick, dim3(1), dim3(1), 0, c->stream, A.iter);
+    HIPCHK(c, hipMemcpyAsync(c->pin.p, A.count, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    return 0;
+}
+// The launches of an iteration are the same every time (the iteration number lives in device memory), so they can be
+// captured ONCE into a hipGraph and replayed: RAFTX_FLEX_GRAPH=1.  Measured (scripts/bench_flex.py, prof_flex_dropin.py): the
+// capture + instantiation of every call costs more than the four or five replays save -- 13.5 against 13.1 ms for a batch
+// of 16 units x 3 sea states, 2.5-2.9 against 2.3 ms for a single unit -- so plain launches are the default (a graph kept
+// across calls of one shape would pay; not built).  The first iteration always runs plainly (it sets the kernels' LDS
+// attributes, which a capture must not contain); a capture or instantiation that fails leaves plain launches.
+struct FlexGraph : NoCopy {              // the handles of the captured iteration, released on every path
+    hipGraph_t graph = nullptr;
+    hipGraphExec_t exec = nullptr;
+    ~FlexGraph() { if (exec) (void)hipGraphExecDestroy(exec); if (graph) (void)hipGraphDestroy(graph); }
+};
+static int flex_iterate(raftx_ctx *c, const FlexShape &S, const FlexArrays &A, int nIter, double tol) {
+    static const bool use_graph = getenv("RAFTX_FLEX_GRAPH") && atoi(getenv("RAFTX_FLEX_GRAPH"));
+    const volatile int *hCount = reinterpret_cast<volatile int *>(c->pin.p);
+    HIPCHK(c, hipMemsetAsync(A.iter, 0, sizeof(int), c->stream));
+    FlexGraph g;
+    int rc = 0;
+    for (int it = 0; it <= nIter && !rc; it++) {                          // :977, 1052
+        if (it == 1 && use_graph && nIter > 1 && hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal) == hipSuccess) {
+            const int rcq = flex_iteration(c, S, A, tol);
+            const hipError_t ee = hipStreamEndCapture(c->stream, &g.graph);
+            if (rcq || ee != hipSuccess || !g.graph || hipGraphInstantiate(&g.exec, g.graph, nullptr, nullptr, 0) != hipSuccess) g.exec = nullptr;
+            (void)hipGetLastError();
+        }
+        if (g.exec) rc = hipGraphLaunch(g.exec, c->stream) != hipSuccess ? -2 : 0;
+        else rc = flex_iteration(c, S, A, tol);
+        if (!rc && hipStreamSynchronize(c->stream) != hipSuccess) rc = -2;
+        if (!rc && *hCount == 0) break;
+    }
+    if (rc) FAIL(c, "flex_solve: an iteration could not be enqueued (%s)", hipGetErrorString(hipGetLastError()));
+    return 0;
+}
+// every heading with the impedance of the pair's last iteration (:1155, 1191, 1212-1216)
+static int flex_all_headings(raftx_ctx *c, const FlexShape &S, const FlexArrays &A) {
+    DenseSolve d = flex_dense(c, S, A);
+    d.nRhs = S.nHead; d.F = A.Fw; d.X = A.Xh; d.Z = A.Z;
+    return dense_launch(c, d) ? -1 : 0;
+}
 extern "C" int raftx_flex_solve(raftx_ctx *c, int nUnit, const int64_t *nodeOff, int n, const double *Tn, const double *M,
                                 const double *B, const double *C, int freq_mask, const raftx_c128 *F_lin, int nIter, double tol,
                                 double XiStart, raftx_c128 *Xi, int32_t *niter, int32_t *flags, double *B_drag, raftx_c128 *F_drag,
@@ -2700,132 +2825,33 @@ extern "C" int raftx_flex_solve(raftx_ctx *c, int nUnit, const int64_t *nodeOff,
     if (nUnit < 1 || !nodeOff || !Tn || !M || !B || !C || !F_lin || !Xi || !niter || !flags || nIter < 0)
         FAIL(c, "flex_solve: bad arguments");
     HIPCHK(c, hipSetDevice(c->device));
-    const DevTables &T = c->T;
-    const int nCase = T.nCase, nHead = T.nHead, nw = T.nw, nNode = T.nDesign;
-    if (nodeOff[0] != 0 || nodeOff[nUnit] != nNode) FAIL(c, "flex_solve: nodeOff must run from 0 to the %d resident node tables", nNode);
-    for (int u = 0; u < nUnit; u++)
-        if (nodeOff[u + 1] < nodeOff[u]) FAIL(c, "flex_solve: node offsets not monotone");
-    const int nSys = nUnit * nCase;
-    if (dense_check(c, "flex_solve", nSys, n, nHead, nw)) return -1;
-    if (n < 6) FAIL(c, "flex_solve: n = %d reduced DOFs", n);
-    Scratch sc(c);
-    const size_t nn = (size_t)n * n, nxs = (size_t)n * nw, npn = (size_t)nNode * nCase;
-    const size_t nM = (size_t)nUnit * nn * ((freq_mask & 1) ? nw : 1), nB = (size_t)nUnit * nn * ((freq_mask & 2) ? nw : 1);
-    const bool reg1 = dense_reg_shape(n, 1), regH = dense_reg_shape(n, nHead);
-    std::vector<int> hNodeUnit((size_t)nNode);
+    FlexShape S;
+    if (flex_check(c, nUnit, nodeOff, n, freq_mask, S)) return -1;
+    std::vector<int> hNodeUnit((size_t)S.nNode), ones((size_t)S.nSys, 1);       // (uploaded: they live until the call returns)
     for (int u = 0; u < nUnit; u++)
         for (int64_t i = nodeOff[u]; i < nodeOff[u + 1]; i++) hNodeUnit[(size_t)i] = u;
-    double *dM = sc.tmp<double>(nM), *dB = sc.tmp<double>(nB), *dC = sc.tmp<double>((size_t)nUnit * nn);
-    double *dTn = sc.tmp<double>((size_t)nNode * 6 * n), *dW = sc.tmp<double>((size_t)nCase * nNode * 6 * n);
-    double *dBn = sc.tmp<double>(npn * 36), *dBd = sc.tmp<double>((size_t)nSys * nn);
-    int64_t *dOff = sc.tmp<int64_t>((size_t)nUnit + 1);
-    int *dNodeUnit = sc.tmp<int>((size_t)nNode), *dAct = sc.tmp<int>((size_t)nSys), *dNi = sc.tmp<int>((size_t)nSys),
-        *dFl = sc.tmp<int>((size_t)nSys), *dCount = sc.tmp<int>(1);
-    cplx *dXiN = sc.tmp<cplx>(npn * 6 * nw), *dFn = sc.tmp<cplx>(npn * nHead * 6 * nw);
-    cplx *dFlin = sc.tmp<cplx>((size_t)nSys * nHead * nxs), *dFw = sc.tmp<cplx>((size_t)nSys * nHead * nxs);
-    cplx *dFd = sc.tmp<cplx>((size_t)nSys * nHead * nxs), *dRhs = sc.tmp<cplx>((size_t)nSys * nxs);
-    cplx *dXnew = sc.tmp<cplx>((size_t)nSys * nxs), *dXi = sc.tmp<cplx>((size_t)nSys * nxs), *dXl = sc.tmp<cplx>((size_t)nSys * nxs);
-    cplx *dXh = sc.tmp<cplx>((size_t)nSys * nHead * nxs);
-    cplx *dA = (reg1 && regH) ? nullptr : sc.tmp<cplx>((size_t)nSys * nw * n * (n + nHead));
-    cplx *dZ = Z ? sc.tmp<cplx>((size_t)nSys * nn * nw) : nullptr;
-    if (!dM || !dB || !dC || !dTn || !dW || !dBn || !dBd || !dOff || !dNodeUnit || !dAct || !dNi || !dFl || !dCount || !dXiN || !dFn ||
-        !dFlin || !dFw || !dFd || !dRhs || !dXnew || !dXi || !dXl || !dXh || (!(reg1 && regH) && !dA) || (Z && !dZ))
-        FAIL(c, "flex_solve: device allocation failed");
+    Scratch sc(c);
+    FlexArrays A;
+    A.M = sc.in<double>(M, S.nM); A.B = sc.in<double>(B, S.nB); A.C = sc.in<double>(C, nUnit * S.nn);
+    A.Tn = sc.in<double>(Tn, (size_t)S.nNode * 6 * n); A.off = sc.in<int64_t>(nodeOff, (size_t)nUnit + 1);
+    A.nodeUnit = sc.in<int>(hNodeUnit.data(), hNodeUnit.size()); A.Flin = sc.in<cplx>(F_lin, S.nxh); A.act = sc.in<int>(ones.data(), ones.size());
+    A.W = sc.tmp<double>(S.npn * 6 * n); A.Bn = sc.tmp<double>(S.npn * 36); A.Bd = sc.tmp<double>(S.nSys * S.nn);
+    A.ni = sc.tmp<int>(S.nSys); A.fl = sc.tmp<int>(S.nSys); A.count = sc.tmp<int>(1); A.iter = sc.tmp<int>(1);
+    A.XiN = sc.tmp<cplx>(S.npn * 6 * S.nw); A.Fn = sc.tmp<cplx>(S.npn * S.nHead * 6 * S.nw);
+    A.Fw = sc.tmp<cplx>(S.nxh); A.Fd = sc.tmp<cplx>(S.nxh); A.Xh = sc.tmp<cplx>(S.nxh);
+    A.rhs = sc.tmp<cplx>(S.nxl); A.Xnew = sc.tmp<cplx>(S.nxl); A.Xi = sc.tmp<cplx>(S.nxl); A.Xl = sc.tmp<cplx>(S.nxl);
+    A.A = sc.tmp<cplx>(dense_workspace(S.nSys, n, S.nHead, S.nw));               // (the one-column solve of an iteration needs no more)
+    A.Z = Z ? sc.tmp<cplx>(S.nSys * S.nn * S.nw) : nullptr;
+    sc.out_from(Xi, A.Xh, S.nxh); sc.out_from(niter, A.ni, (size_t)S.nSys); sc.out_from(flags, A.fl, (size_t)S.nSys);   // copied in this order
+    sc.out_from(B_drag, A.Bd, S.nSys * S.nn); sc.out_from(F_drag, A.Fd, S.nxh); sc.out_from(Z, A.Z, S.nSys * S.nn * S.nw);
+    if (int rc = sc.upload("flex_solve")) return rc;
     HIPCHK(c, c->pin.reserve(16));
-    H2D(c, dM, M, nM * sizeof(double));
-    H2D(c, dB, B, nB * sizeof(double));
-    H2D(c, dC, C, (size_t)nUnit * nn * sizeof(double));
-    H2D(c, dTn, Tn, (size_t)nNode * 6 * n * sizeof(double));
-    H2D(c, dOff, nodeOff, ((size_t)nUnit + 1) * sizeof(int64_t));
-    H2D(c, dNodeUnit, hNodeUnit.data(), (size_t)nNode * sizeof(int));
-    H2D(c, dFlin, F_lin, (size_t)nSys * nHead * nxs * sizeof(cplx));
-    HIPCHK(c, hipMemsetAsync(dNi, 0, (size_t)nSys * sizeof(int), c->stream));
-    HIPCHK(c, hipMemsetAsync(dFl, 0, (size_t)nSys * sizeof(int), c->stream));
-    HIPCHK(c, hipMemsetAsync(dBd, 0, (size_t)nSys * nn * sizeof(double), c->stream));
-    HIPCHK(c, hipMemsetAsync(dXi, 0, (size_t)nSys * nxs * sizeof(cplx), c->stream));
-    HIPCHK(c, hipMemsetAsync(dFd, 0, (size_t)nSys * nHead * nxs * sizeof(cplx), c->stream));
-    {
-        std::vector<int> ones((size_t)nSys, 1);
-        H2D(c, dAct, ones.data(), (size_t)nSys * sizeof(int));
-        HIPCHK(c, hipStreamSynchronize(c->stream));                       // (the host vectors above go out of scope)
-    }
-    const size_t nxl = (size_t)nSys * nxs;
-    if (c->flexXl0_n) {                                                   // raftx_flex_start: an explicit iterate, one-shot
-        const size_t had = c->flexXl0_n;
-        c->flexXl0_n = 0;
-        if (had != nxl) FAIL(c, "flex_solve: the linearisation point of raftx_flex_start has %zu entries, this call %zu", had, nxl);
-        HIPCHK(c, hipMemcpyAsync(dXl, c->flexXl0.p, nxl * sizeof(cplx), hipMemcpyDeviceToDevice, c->stream));
-    } else {
-        hipLaunchKernelGGL(k_flex_fill, dim3((unsigned)((nxl + 255) / 256)), dim3(256), 0, c->stream, nxl, cplx{XiStart, 0.0}, dXl);   // :999
-    }
-    hipEvent_t e0 = c->evG2, e1 = c->evG3;                                // (free here: the span of the whole fixed point)
-    HIPCHK(c, hipEventRecord(e0, c->stream));
-    const int nt = (n + 15) / 16;
-    const dim3 gridB((unsigned)((nt * nt + 3) / 4), (unsigned)nSys), gridF((unsigned)((nxs + 255) / 256), (unsigned)(nSys * nHead));
-    volatile int *hCount = reinterpret_cast<volatile int *>(c->pin.p);
-    int *dIter = sc.tmp<int>(1);
-    if (!dIter) FAIL(c, "flex_solve: device allocation failed");
-    HIPCHK(c, hipMemsetAsync(dIter, 0, sizeof(int), c->stream));
-    // one iteration: node motions -> linearisation of every (node, sea state) -> projections with the units' T -> dense solves ->
-    // convergence test / relaxation -> the count of pairs still iterating to the host
-    auto enqueue_iteration = [&]() -> int {
-        hipLaunchKernelGGL(k_flex_node_motion, dim3((unsigned)npn), dim3(256), 0, c->stream, nCase, n, nw, dNodeUnit, dTn, dXl, dXiN);
-        if (linearize_enqueue(c, dXiN, dBn, dFn, false)) return -1;
-        hipLaunchKernelGGL(k_flex_w, dim3((unsigned)npn), dim3(256), 0, c->stream, nNode, nCase, n, dTn, dBn, dW);
-        hipLaunchKernelGGL(k_flex_gemm_B, gridB, dim3(256), 0, c->stream, nNode, nCase, n, dOff, dTn, dW, dAct, dBd);
-        hipLaunchKernelGGL(k_flex_project_F, gridF, dim3(256), 0, c->stream, nCase, nHead, n, nw, dOff, dTn, dFn, dFlin, dAct, dFw, dFd, dRhs);
-        if (dense_launch(c, nSys, nCase, n, 1, nw, T.w, dM, dB, dC, freq_mask, dBd, dRhs, dXnew, nullptr, dA, dAct)) return -1;
-        HIPCHK(c, hipMemsetAsync(dCount, 0, sizeof(int), c->stream));
-        hipLaunchKernelGGL(k_flex_converge, dim3((unsigned)nSys), dim3(256), 0, c->stream, n, nw, tol, dIter, dXnew, dXi, dXl, dAct, dNi, dFl,
-                           dCount);
-        hipLaunchKernelGGL(k_flex_tick, dim3(1), dim3(1), 0, c->stream, dIter);
-        HIPCHK(c, hipMemcpyAsync(const_cast<int *>(hCount), dCount, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-        return 0;
-    };
-    // The launches of an iteration are the same every time (the iteration number lives in device memory), so they can be
-    // captured ONCE into a hipGraph and replayed: RAFTX_FLEX_GRAPH=1.  Measured (scripts/bench_flex.py, prof_flex_dropin.py): the
-    // capture + instantiation of every call costs more than the four or five replays save -- 13.5 against 13.1 ms for a batch
-    // of 16 units x 3 sea states, 2.5-2.9 against 2.3 ms for a single unit -- so plain launches are the default (a graph kept
-    // across calls of one shape would pay; not built).  The first iteration always runs plainly (it sets the kernels' LDS
-    // attributes, which a capture must not contain).
-    static const bool use_graph = getenv("RAFTX_FLEX_GRAPH") && atoi(getenv("RAFTX_FLEX_GRAPH"));
-    hipGraph_t graph = nullptr;
-    hipGraphExec_t gexec = nullptr;
-    int rc_it = 0;
-    for (int it = 0; it <= nIter && !rc_it; it++) {                       // :977, 1052
-        if (it == 1 && use_graph && nIter > 1) {
-            if (hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal) == hipSuccess) {
-                const int rcq = enqueue_iteration();
-                const hipError_t ee = hipStreamEndCapture(c->stream, &graph);
-                if (rcq || ee != hipSuccess || !graph || hipGraphInstantiate(&gexec, graph, nullptr, nullptr, 0) != hipSuccess) gexec = nullptr;
-                (void)hipGetLastError();
-            }
-        }
-        if (gexec && it >= 1) {
-            if (hipGraphLaunch(gexec, c->stream) != hipSuccess) rc_it = -2;
-        } else {
-            rc_it = enqueue_iteration();
-        }
-        if (!rc_it && hipStreamSynchronize(c->stream) != hipSuccess) rc_it = -2;
-        if (!rc_it && *hCount == 0) break;
-    }
-    if (gexec) (void)hipGraphExecDestroy(gexec);
-    if (graph) (void)hipGraphDestroy(graph);
-    if (rc_it) FAIL(c, "flex_solve: an iteration could not be enqueued (%s)", hipGetErrorString(hipGetLastError()));
-    // every heading with the impedance of the pair's last iteration (:1155, 1191, 1212-1216)
-    if (dense_launch(c, nSys, nCase, n, nHead, nw, T.w, dM, dB, dC, freq_mask, dBd, dFw, dXh, dZ, dA)) return -1;
-    HIPCHK(c, hipEventRecord(e1, c->stream));
-    D2H(c, Xi, dXh, (size_t)nSys * nHead * nxs * sizeof(cplx));
-    D2H(c, niter, dNi, (size_t)nSys * sizeof(int));
-    D2H(c, flags, dFl, (size_t)nSys * sizeof(int));
-    if (B_drag) D2H(c, B_drag, dBd, (size_t)nSys * nn * sizeof(double));
-    if (F_drag) D2H(c, F_drag, dFd, (size_t)nSys * nHead * nxs * sizeof(cplx));
-    if (Z) D2H(c, Z, dZ, (size_t)nSys * nn * nw * sizeof(cplx));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    float ms = 0.f;
-    HIPCHK(c, hipEventElapsedTime(&ms, e0, e1));
-    c->last_ms = ms;
-    return 0;
+    if (int rc = flex_reset(c, S, A)) return rc;
+    if (int rc = flex_first_iterate(c, S, A, XiStart)) return rc;
+    if (sc.begin()) return -2;                                                  // the span of the whole fixed point
+    if (int rc = flex_iterate(c, S, A, nIter, tol)) return rc;
+    if (int rc = flex_all_headings(c, S, A)) return rc;
+    return sc.finish();
 }
 
 extern "C" int raftx_solve_system_resident(raftx_ctx *c, int nUnit, const double *Mc, const double *Bc, const double *Cc,
