@@ -40,8 +40,29 @@
  * Flags (int32 per design; a flagged design's outputs are NaN, and only its own).  For a composite line BAD_LINE looks at
  * the L, EA, w of every row (segments must be heavier than water: buoyancy enters through the points only), SLACK and
  * VERTICAL at the total length.
- * Still refused: bridles and any point joining more than two lines, lines with both ends on the vessel, seabed friction,
- * the fully slack profile, seabed contact of any segment but the anchor-side one.
+ *
+ * A BRIDLE (crowfoot, delta connection) -- a stem from the anchor to a free junction, and 2 .. RAFTX_MOOR_MAX_LEG legs from the
+ * junction to fairleads of their own -- occupies consecutive rows too:
+ *     stem rows   the head row and its continuation rows exactly as above (anchor -> junction), at most RAFTX_MOOR_MAX_SEG; the
+ *                 head row's fields 3-5 must be zero: the stem ends at the junction, not on the vessel
+ *     leg rows    14 (RAFTX_ML_LEG) 1, 15 zero; 3-5 the leg's fairlead in the body frame; 6-8 its own L, EA, w; 9 CB, must be 0;
+ *                 10 (RAFTX_ML_WJOINT) on the FIRST leg row the junction's net submerged weight [N] (negative for a buoy), 0 on
+ *                 the others; every other field zero
+ * The junction's three coordinates are the unknowns of a damped Newton iteration (at most 60 steps, to stagnation) on the sum
+ * of the stem's end force, every leg's lower-end force (a leg is one suspended catenary: it never rests on the seabed) and the
+ * junction weight.  C_moor is the stiffness condensed to the fairleads, over all pairs of legs -- the fairleads are coupled
+ * through the junction -- with the arm-turning term of every fairlead; J of every row end includes the junction's motion.
+ * T and J keep their layout (a leg's end A is at the junction, its end B at its fairlead); C_moor and F_moor receive a bridle
+ * once; line_out of a leg row: HF, V at its top, HF, V at its bottom, 0, the junction iteration's steps, 0, 0 (the stem rows
+ * hold the junction iteration's steps in field 5 as well).  A batch without a leg row takes the code path, the kernels and the
+ * bits of a library without bridles.  Flags of a bridle: BAD_LINE as for a composite line, over all its rows (and a fairlead
+ * not above the anchor); SLACK when L_stem + L_leg >= XF + ZF from the anchor to the leg's fairlead holds for EVERY leg;
+ * GROUNDED by the composite line's rule for the stem, or the junction or the sag of a leg more than 1e-6 depth below the
+ * seabed; NO_CONVERGENCE when the junction iteration reaches its cap or finds no admissible start.
+ * Every entry point that takes line records takes bridles: raftx_mooring_lines, raftx_mooring_program, raftx_mean_pose
+ * (include/raftx_statics.h), raftx_sweep_mooring and raftx_sweep_mean_pose.
+ * Still refused: lines with both ends on the vessel, shared anchors, junctions joined to junctions, seabed friction, the fully
+ * slack profile, seabed contact of any segment but the anchor-side one.
  */
 #ifndef RAFTX_MOORING_H
 #define RAFTX_MOORING_H
@@ -50,8 +71,10 @@
 
 #define RAFTX_ML_N 16
 #define RAFTX_ML_WJOINT 10             /* continuation row: net submerged weight of the point at its lower end */
+#define RAFTX_ML_LEG 14                /* 1 in a leg row of a bridle (field 15 is 0 there), 0 in every other row */
 #define RAFTX_ML_CONT 15               /* 1 in a continuation row of a composite line, 0 in a head row or a single line */
-#define RAFTX_MOOR_MAX_SEG 4           /* rows of one composite line, at most */
+#define RAFTX_MOOR_MAX_SEG 4           /* rows of one composite line, or stem rows of one bridle, at most */
+#define RAFTX_MOOR_MAX_LEG 3           /* leg rows of one bridle, at most (and at least 2) */
 #define RAFTX_MOOR_BAD_LINE        1   /* non-finite field or pose; L, EA or w <= 0; anchor below the seabed; fairlead not above the anchor */
 #define RAFTX_MOOR_VERTICAL        2   /* horizontal span XF <= 1e-9 L */
 #define RAFTX_MOOR_SLACK           4   /* L >= XF + ZF: the fully slack profile is not covered */
@@ -71,7 +94,8 @@ extern "C" {
  * (1 = seabed contact), 0, flags [nDesign].  The sums over the lines run in line order without atomics: the bits of a
  * design depend on its own lines and pose only.  Errors, before any launch: nLine < 1, nDesign < 0, NULL lines or flags,
  * a depth that is not positive and finite, a line with CB != 0, a design whose row 0 is a continuation row, a composite
- * line of more than RAFTX_MOOR_MAX_SEG rows. */
+ * line of more than RAFTX_MOOR_MAX_SEG rows; a leg row that follows no head row, a bridle of one leg or of more than
+ * RAFTX_MOOR_MAX_LEG, a non-zero fairlead on the head row of a bridle, a row with both marks. */
 int raftx_mooring_lines(raftx_ctx *ctx, int nDesign, int nLine, const double *lines, const double *pose, double depth,
                         double *C_moor, double *F_moor, double *T, double *J, double *line_out, int32_t *flags);
 
@@ -81,7 +105,9 @@ int raftx_mooring_lines(raftx_ctx *ctx, int nDesign, int nLine, const double *li
  * per parameter, evaluated left to right without fused multiply-adds exactly as endCoef of raftx_variant_program.
  * nParam must equal the installed variant program's (an error without one).  nLine = 0 clears the program; installing a
  * new variant program does not.  Continuation rows are carried unchanged to every variant; a lineEdit on one is an error
- * (the anchor and the fairlead of a composite line are its head row's), as are the record errors of raftx_mooring_lines. */
+ * (the anchor and the fairlead of a composite line are its head row's), as are the record errors of raftx_mooring_lines.
+ * A lineEdit on a leg row of a bridle may move its fairlead only (fields 3-5), on the head row of a bridle its anchor only
+ * (fields 0-2): a non-zero coefficient for one of the other three fields is an error. */
 int raftx_mooring_program(raftx_ctx *ctx, int nLine, const double *lines, int nParam, const double *lineCoef,
                           const int32_t *lineEdit);
 

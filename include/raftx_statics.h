@@ -3,8 +3,8 @@
  * Replaces, per unit, the solve of Model.solveStatics (raft_model.py:550-963) for staticsMod == 0 and forcingMod == 0:
  *     Y(x) = F0 + F_env - K_hs (x - x_ref) + F_moor(x) = 0
  * by Newton's iteration x <- x + (K_hs + C_moor(x))^-1 Y(x) from x = x_ref, with F_moor and the exact C_moor of
- * include/raftx_mooring.h (the same line types, composite lines of head and continuation rows included: nLine counts rows,
- * and a chain is solved by the lane of its head row; every line solved from a cold start at every iterate) and the reference's
+ * include/raftx_mooring.h (the same line types, composite lines of head and continuation rows and bridles of stem and leg rows
+ * included: nLine counts rows, and a chain or a bridle is solved by the lane of its head row; every line solved from a cold start at every iterate) and the reference's
  * safeguards (raft_model.py:824-861, :667), per step:
  *     a zero diagonal entry of K takes the mean of the diagonal;
  *     dX = K^-1 Y by LU with partial pivoting; while dX.Y < 0 the diagonal grows by 10 % and the solve is repeated, at
@@ -53,7 +53,7 @@ extern "C" {
  * bits depend on its own inputs only.
  * Errors, before any launch: nLine < 1, nDesign < 0, NULL K_hs, F0 or flags, a depth that is not positive and finite, a
  * tolerance that is negative or not finite, a line with CB != 0, a design whose row 0 is a continuation row, a composite line
- * of more than RAFTX_MOOR_MAX_SEG rows, lines == NULL without a mooring program, with another nLine, or without params. */
+ * of more than RAFTX_MOOR_MAX_SEG rows, the bridle errors of raftx_mooring_lines, lines == NULL without a mooring program, with another nLine, or without params. */
 int raftx_mean_pose(raftx_ctx *ctx, int nDesign, int nLine, const double *lines, const double *params, double depth,
                     const double *K_hs, const double *F0, const double *F_env, const double *x_ref, const double tol[2],
                     int max_iter, double *pose, double *C_moor, double *F_moor, double *T, double *J, double *F_res,

@@ -55,6 +55,7 @@ MOORING_EXPORTS = ("raftx_mooring_lines", "raftx_mooring_program", "raftx_moorin
 ML_N = 16          # doubles per mooring line record (RAFTX_ML_N)
 ML_WJOINT, ML_CONT = 10, 15   # continuation rows of a composite line (RAFTX_ML_WJOINT, RAFTX_ML_CONT)
 MOOR_MAX_SEG = 4   # rows of one composite line, at most (RAFTX_MOOR_MAX_SEG)
+ML_LEG, MOOR_MAX_LEG = 14, 3   # leg rows of a bridle: the mark and how many at most (RAFTX_ML_LEG, RAFTX_MOOR_MAX_LEG)
 # include/raftx_statics.h: the mean equilibrium pose, the device library only
 STATICS_EXPORTS = ("raftx_mean_pose", "raftx_sweep_mean_pose")
 MOOR_BAD_LINE, MOOR_VERTICAL, MOOR_SLACK, MOOR_NO_CONVERGENCE = 1, 2, 4, 8

@@ -918,12 +918,12 @@ struct SweepSlot {
     } mooring;
     struct PoseReq {                     // raftx_sweep_mean_pose: the crossing runs at every design's mean equilibrium pose
         bool on = false;
-        int nLine = 0, nX = 0, maxIter = 0, chains = 0;
+        int nLine = 0, nX = 0, maxIter = 0, chains = 0;       // chains: the kind of the records (check_lines)
         double tolT = 0, tolR = 0;
         // device, the whole crossing (in S.allocs): the line records; the statics-only extras [nX,36] / [nX,6] and the loads
         // [nDesign,6], each or null; what the solve reads (K_hs, F0), its scratch and what it leaves; the poses of the second pass
         const double *lines = nullptr, *Cx = nullptr, *Fx = nullptr, *Fenv = nullptr;
-        double *K = nullptr, *F0 = nullptr, *lw = nullptr, *solved = nullptr, *placed = nullptr, *Fres = nullptr;
+        double *K = nullptr, *F0 = nullptr, *lw = nullptr, *bw = nullptr, *solved = nullptr, *placed = nullptr, *Fres = nullptr;
         int *iter = nullptr, *fl = nullptr;
         Pinned<double> pin;              // landing area of the whole crossing (landing::pose)
         double *pose_out = nullptr, *Fres_out = nullptr;                     // the caller's, filled by raftx_sweep_wait
@@ -988,7 +988,7 @@ struct raftx_ctx {
     DevBuf<cplx> bemF;                   // resident BEM (+ added) excitation of raftx_bem_excitation [npair,nHead,6,nw]
     DevBuf<int> commFlag;                // one int in HBM: the status word the ranks agree on before an exchange step (comm_agree)
     struct {                             // raftx_mooring_program: base records and the affine edits of their end points
-        int nLine = 0, nP = 0, chains = 0;   // chains: a continuation row among the base records
+        int nLine = 0, nP = 0, chains = 0;   // chains: the kind of the base records (check_lines: 0, 1 continuation rows, 2 leg rows)
         DevBuf<double> base, coef;
         DevBuf<int> edit;
     } mprog;
@@ -3274,6 +3274,7 @@ static int block_pose(raftx_ctx *c, SweepSlot &S, size_t b) {
         M.F_env = P.Fenv ? P.Fenv + lo * 6 : nullptr;
         M.x_ref = A.pose;                                        // the block's own upload of the caller's pose, or null
         M.lw = P.lw + lo * P.nLine * MOOR_LW_N;
+        M.bw = P.bw ? P.bw + lo * P.nLine * MOOR_BW_N : nullptr;
         M.pose = P.solved + lo * 6; M.Fres = P.Fres + lo * 6;
         M.iterations = P.iter + lo; M.flags = P.fl + lo;
         launch_mean_pose(sPrep, M, n, P.nLine, c->csets[S.cset].T.depth, P.tolT, P.tolR, P.maxIter);
@@ -4405,24 +4406,45 @@ extern "C" int raftx_sweep_current(raftx_ctx *c, int slot, int nCur, const doubl
 // ---- quasi-static mooring lines (include/raftx_mooring.h, raftx_mooring.h)
 // The line source of an entry point `who`: what valid records are, which calls may leave them to the mooring program, and
 // how either kind reaches the device.  (raftx_mooring_program checks its one unit's records itself, in its own wording.)
-// *chains: whether any row is a continuation row of a composite line (the CHAINS kernels are needed)
+// *chains: the kind of the records, which picks the kernels: 0 single rows only, 1 a continuation row of a composite line among
+// them (the CHAINS kernels), 2 a leg row of a bridle (the BRIDLES kernels, which cover composite lines too)
 static int check_lines(raftx_ctx *c, const char *who, size_t nDesign, int nLine, const double *lines, int *chains) {
     *chains = 0;
-    int run = 0;                                                 // rows of the line the current row belongs to
-    for (size_t i = 0; i < nDesign * (size_t)nLine; i++) {
-        const double cb = lines[i * RAFTX_ML_N + 9];
-        if (std::isfinite(cb) && cb != 0.0)
-            FAIL(c, "%s: line %zu of design %zu has seabed friction CB = %g: friction is not covered (CB must be 0)", who, i % nLine,
-                 i / nLine, cb);
-        if (lines[i * RAFTX_ML_N + RAFTX_ML_CONT] != 0.0) {
-            if (i % nLine == 0) FAIL(c, "%s: row 0 of design %zu is a continuation row: a composite line starts with its head row", who, i / nLine);
-            if (++run > RAFTX_MOOR_MAX_SEG)
-                FAIL(c, "%s: the composite line ending in row %zu of design %zu has more than %d rows", who, i % nLine, i / nLine,
-                     RAFTX_MOOR_MAX_SEG);
-            *chains = 1;
-        } else
-            run = 1;
+    int kind = 0;
+    for (size_t d = 0; d < nDesign; d++) {
+        const double *row = lines + d * (size_t)nLine * RAFTX_ML_N;
+        int run = 0, legs = 0;                                   // rows of the line the current row belongs to; legs of its bridle so far
+        for (int l = 0; l < nLine; l++, row += RAFTX_ML_N) {
+            const double cb = row[9];
+            if (std::isfinite(cb) && cb != 0.0)
+                FAIL(c, "%s: line %d of design %zu has seabed friction CB = %g: friction is not covered (CB must be 0)", who, l, d, cb);
+            const bool cont = row[RAFTX_ML_CONT] != 0.0, leg = row[RAFTX_ML_LEG] != 0.0;
+            if (!cont && !leg) {                                 // a head row or a single line
+                if (legs == 1) FAIL(c, "%s: the bridle before row %d of design %zu has exactly one leg: a bridle has 2 to %d", who, l, d, RAFTX_MOOR_MAX_LEG);
+                run = 1;
+                legs = 0;
+            } else if (leg) {
+                if (cont) FAIL(c, "%s: row %d of design %zu is marked as a leg row and as a continuation row", who, l, d);
+                if (!run) FAIL(c, "%s: row %d of design %zu is a leg row that follows no head row", who, l, d);
+                if (!legs) {
+                    const double *head = row - (size_t)run * RAFTX_ML_N;
+                    if (head[3] != 0.0 || head[4] != 0.0 || head[5] != 0.0)
+                        FAIL(c, "%s: row %d of design %zu heads a bridle and has a fairlead: its fields 3-5 must be zero (the stem ends at the junction)",
+                             who, l - run, d);
+                }
+                if (++legs > RAFTX_MOOR_MAX_LEG) FAIL(c, "%s: the bridle with leg row %d of design %zu has more than %d legs", who, l, d, RAFTX_MOOR_MAX_LEG);
+                kind = 2;
+            } else {
+                if (l == 0) FAIL(c, "%s: row 0 of design %zu is a continuation row: a composite line starts with its head row", who, d);
+                if (legs) FAIL(c, "%s: row %d of design %zu is a continuation row after a leg row: the stem's rows come first", who, l, d);
+                if (++run > RAFTX_MOOR_MAX_SEG)
+                    FAIL(c, "%s: the composite line ending in row %d of design %zu has more than %d rows", who, l, d, RAFTX_MOOR_MAX_SEG);
+                kind |= 1;
+            }
+        }
+        if (legs == 1) FAIL(c, "%s: the bridle ending design %zu has exactly one leg: a bridle has 2 to %d", who, d, RAFTX_MOOR_MAX_LEG);
     }
+    *chains = kind >= 2 ? 2 : kind;
     return 0;
 }
 static int check_depth(raftx_ctx *c, const char *who, double depth) {
@@ -4470,10 +4492,17 @@ static int expand_lines(raftx_ctx *c, hipStream_t st, size_t n, int nLine, const
     return 0;
 }
 
-// k_moor_line over the records of A: the chain instantiation only where a continuation row is among them
+// k_moor_line and k_moor_design over the records of A: the chain instantiation only where a continuation row is among them, the
+// bridle instantiations only where a leg row is
+static void launch_moor_design(hipStream_t st, const MoorArgs &A) {
+    const dim3 grid(moor_grid((long long)A.nDesign));
+    if (A.chains == 2) hipLaunchKernelGGL(k_moor_design<true>, grid, dim3(MOOR_THREADS), 0, st, A);
+    else hipLaunchKernelGGL(k_moor_design<false>, grid, dim3(MOOR_THREADS), 0, st, A);
+}
 static void launch_moor_line(hipStream_t st, const MoorArgs &A) {
     const dim3 grid(moor_grid((long long)A.nDesign * A.nLine));
-    if (A.chains) hipLaunchKernelGGL(k_moor_line<true>, grid, dim3(MOOR_THREADS), 0, st, A);
+    if (A.chains == 2) hipLaunchKernelGGL((k_moor_line<true, true>), grid, dim3(MOOR_THREADS), 0, st, A);
+    else if (A.chains) hipLaunchKernelGGL(k_moor_line<true>, grid, dim3(MOOR_THREADS), 0, st, A);
     else hipLaunchKernelGGL(k_moor_line<false>, grid, dim3(MOOR_THREADS), 0, st, A);
 }
 
@@ -4498,6 +4527,7 @@ extern "C" int raftx_mooring_lines(raftx_ctx *c, int nDesign, int nLine, const d
     A.lines = L.lines;
     A.pose = sc.in<double>(pose, (size_t)nDesign * 6);
     A.lw = sc.tmp<double>(nl * MOOR_LW_N);
+    if (chains == 2) A.bw = sc.tmp<double>(nl * MOOR_BW_N);
     A.C = sc.out<double>(C_moor, (size_t)nDesign * 36);
     A.F = sc.out<double>(F_moor, (size_t)nDesign * 6);
     A.T = sc.out<double>(T, nl * 2);
@@ -4508,7 +4538,7 @@ extern "C" int raftx_mooring_lines(raftx_ctx *c, int nDesign, int nLine, const d
     if (sc.begin()) return -2;
     A.chains = chains;
     launch_moor_line(c->stream, A);
-    hipLaunchKernelGGL(k_moor_design, dim3(moor_grid(nDesign)), dim3(MOOR_THREADS), 0, c->stream, A);
+    launch_moor_design(c->stream, A);
     return sc.finish();
 }
 
@@ -4530,14 +4560,33 @@ extern "C" int raftx_mooring_program(raftx_ctx *c, int nLine, const double *line
         const double cb = lines[(size_t)l * RAFTX_ML_N + 9];
         if (std::isfinite(cb) && cb != 0.0)
             FAIL(c, "mooring_program: line %d has seabed friction CB = %g: friction is not covered (CB must be 0)", l, cb);
+        if (lines[(size_t)l * RAFTX_ML_N + RAFTX_ML_LEG] != 0.0) continue;          // (leg rows: check_lines below)
         if (lines[(size_t)l * RAFTX_ML_N + RAFTX_ML_CONT] != 0.0) {
             if (l == 0) FAIL(c, "mooring_program: row 0 is a continuation row: a composite line starts with its head row");
             if (++run > RAFTX_MOOR_MAX_SEG) FAIL(c, "mooring_program: the composite line ending in row %d has more than %d rows", l, RAFTX_MOOR_MAX_SEG);
-            if (lineEdit[l])
-                FAIL(c, "mooring_program: lineEdit on row %d, a continuation row: the anchor and the fairlead are the head row's", l);
-            chains = 1;
         } else
             run = 1;
+    }
+    if (int rc = check_lines(c, "mooring_program", 1, nLine, lines, &chains)) return rc;     // the bridle errors, and the kind of the records
+    for (int l = 0; l < nLine; l++) {
+        if (!lineEdit[l]) continue;
+        const double *row = lines + (size_t)l * RAFTX_ML_N;
+        if (row[RAFTX_ML_CONT] != 0.0)
+            FAIL(c, "mooring_program: lineEdit on row %d, a continuation row: the anchor and the fairlead are the head row's", l);
+        // a leg row has a fairlead and no anchor, the head row of a bridle an anchor and no fairlead: the coefficients of the
+        // other three fields must all be zero (k_moor_expand then writes the zeros the record format asks for)
+        int lo = 0, hi = 0;
+        if (row[RAFTX_ML_LEG] != 0.0) { lo = 0; hi = 3; }
+        else {
+            int k = l + 1;
+            while (k < nLine && lines[(size_t)k * RAFTX_ML_N + RAFTX_ML_CONT] != 0.0) k++;
+            if (k < nLine && lines[(size_t)k * RAFTX_ML_N + RAFTX_ML_LEG] != 0.0) { lo = 3; hi = 6; }
+        }
+        for (int f = lo; f < hi; f++)
+            for (int k = 0; k <= nParam; k++)
+                if (lineCoef[((size_t)l * 6 + f) * (nParam + 1) + k] != 0.0)
+                    FAIL(c, "mooring_program: lineEdit on row %d, %s, has a coefficient for field %d: only fields %s may be edited there", l,
+                         lo == 0 ? "a leg row of a bridle" : "the head row of a bridle", f, lo == 0 ? "3-5 (the leg's fairlead)" : "0-2 (the anchor)");
     }
     mooring_program_release(c);
     const size_t nb = (size_t)nLine * RAFTX_ML_N * 8, nc = (size_t)nLine * 6 * (nParam + 1) * 8, ne = (size_t)nLine * 4;
@@ -4586,7 +4635,8 @@ static void launch_mean_pose(hipStream_t st, MeanPoseArgs &A, int nDesign, int n
     A.depth = depth; A.tolT = tolT; A.tolR = tolR;
     const int perBlock = MP_THREADS / A.G;
     const dim3 grid((unsigned)((nDesign + perBlock - 1) / perBlock));
-    if (A.chains) hipLaunchKernelGGL(k_mean_pose<true>, grid, dim3(MP_THREADS), 0, st, A);
+    if (A.chains == 2) hipLaunchKernelGGL((k_mean_pose<true, true>), grid, dim3(MP_THREADS), 0, st, A);
+    else if (A.chains) hipLaunchKernelGGL(k_mean_pose<true>, grid, dim3(MP_THREADS), 0, st, A);
     else hipLaunchKernelGGL(k_mean_pose<false>, grid, dim3(MP_THREADS), 0, st, A);
 }
 extern "C" int raftx_mean_pose(raftx_ctx *c, int nDesign, int nLine, const double *lines, const double *params, double depth,
@@ -4624,6 +4674,7 @@ extern "C" int raftx_mean_pose(raftx_ctx *c, int nDesign, int nLine, const doubl
     A.F_env = sc.in<double>(F_env, n * 6);
     A.x_ref = sc.in<double>(x_ref, n * 6);
     A.lw = sc.tmp<double>(nl * MOOR_LW_N);
+    if (chains == 2) A.bw = sc.tmp<double>(nl * MOOR_BW_N);
     A.pose = sc.out<double>(pose, n * 6);
     A.C = sc.out<double>(C_moor, n * 36);
     A.F = sc.out<double>(F_moor, n * 6);
@@ -4679,17 +4730,19 @@ extern "C" int raftx_sweep_mooring(raftx_ctx *c, int slot, int nLine, const doub
     } else
         rc = upload_on(c, c->sCopy, S.allocs, S.p1.pose, S.p1.pose ? n * 6 : 0, &dp);
     rc |= stage_lines(c, c->sCopy, S.allocs, n, nLine, lines, S.p1.var.params, L);
-    double *dlw = nullptr, *dC = nullptr, *dF = nullptr, *dT = nullptr, *dLr = nullptr;
+    double *dlw = nullptr, *dbw = nullptr, *dC = nullptr, *dF = nullptr, *dT = nullptr, *dLr = nullptr;
     int *dfl = nullptr;
     rc |= pool_alloc(c, S.allocs, nl * MOOR_LW_N, &dlw) | pool_alloc(c, S.allocs, n * 36, &dC) | pool_alloc(c, S.allocs, n * 6, &dF) |
           pool_alloc(c, S.allocs, nl * 2, &dT) | pool_alloc(c, S.allocs, nl * 36, &dLr) | pool_alloc(c, S.allocs, n, &dfl);
+    if (chains == 2) rc |= pool_alloc(c, S.allocs, nl * MOOR_BW_N, &dbw);
     if (rc) return -2;
+    A.bw = dbw;
     A.lw = dlw; A.C = dC; A.F = dF; A.T = dT; A.Lr = dLr; A.flags = dfl;
     A.lines = L.lines; A.pose = dp;
     if (n) {
         if (int re = expand_lines(c, c->sCopy, n, nLine, L)) return re;
         launch_moor_line(c->sCopy, A);
-        hipLaunchKernelGGL(k_moor_design, dim3(moor_grid((long long)n)), dim3(MOOR_THREADS), 0, c->sCopy, A);
+        launch_moor_design(c->sCopy, A);
         HIPCHK(c, hipGetLastError());
         double *p = S.mooring.pin.p;
         HIPCHK(c, hipMemcpyAsync(p + land.C, A.C, n * 36 * sizeof(double), hipMemcpyDeviceToHost, c->sCopy));
@@ -4739,6 +4792,8 @@ extern "C" int raftx_sweep_mean_pose(raftx_ctx *c, int slot, int nLine, const do
     rc |= pool_alloc(c, S.allocs, n * 36, &P.K) | pool_alloc(c, S.allocs, n * 6, &P.F0) | pool_alloc(c, S.allocs, nl * MOOR_LW_N, &P.lw) |
           pool_alloc(c, S.allocs, n * 6, &P.solved) | pool_alloc(c, S.allocs, n * 6, &P.placed) | pool_alloc(c, S.allocs, n * 6, &P.Fres) |
           pool_alloc(c, S.allocs, n, &P.iter) | pool_alloc(c, S.allocs, n, &P.fl);
+    P.bw = nullptr;
+    if (chains == 2) rc |= pool_alloc(c, S.allocs, nl * MOOR_BW_N, &P.bw);
     if (rc) return -2;
     if (int re = expand_lines(c, c->sCopy, n, nLine, L)) return re;
     HIPCHK(c, hipEventRecord(P.evUp, c->sCopy));

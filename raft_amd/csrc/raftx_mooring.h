@@ -17,6 +17,10 @@
 // CHAINS instantiations, which the host picks when a batch holds a continuation row: single-row batches run the code and
 // give the bits they always did.
 //
+// A bridle (stem rows, then leg rows with field 14 set) has the junction's three coordinates as unknowns and fairleads that are
+// coupled through it: moor_bridle_record below, a record array of its own (MOOR_BW_N per row), and third instantiations
+// (BRIDLES) that the host picks when a batch holds a leg row.
+//
 // Work decomposition: k_moor_line, one lane per (design, line), solves the line and leaves a record of MOOR_LW_N doubles
 // (force, arm, 3 x 3 stiffness at the fairlead, the gradients of both end tensions); k_moor_design, one lane per design,
 // adds the lines' shares of C_moor / F_moor in line order and writes T and J.  No atomics, no LDS: a design's bits
@@ -28,6 +32,9 @@
 #define MOOR_TIGHT 1e-10          // max(|dX|, |dZ|) / L below which a step that does not improve ends the iteration
 #define MOOR_LW_N 24              // f 0:3 | r 3:6 | K 6:15 | gA 15:18 | gB 18:21 | TA 21 | TB 22 | flag 23
 #define MOOR_LO_N 8               // HF, VF, HA, VA, L_B, iterations, branch, 0
+#define MOOR_BW_N 56              // a bridle's row: C share 0:36 | F 36:42 (head row only) | TA 42 | TB 43 | JA 44:50 | JB 50:56
+#define MOOR_BR_MAX_IT 60         // steps of the junction iteration, at most
+#define MOOR_BR_GROW 1e3          // ... and the growth of its residual that ONE step may bring, when the step before brought none
 
 struct MoorArgs {
     int nDesign, nLine;
@@ -38,8 +45,9 @@ struct MoorArgs {
     double *__restrict__ line_out;      // [nDesign,nLine,MOOR_LO_N] or null
     double *__restrict__ C, *__restrict__ F, *__restrict__ T, *__restrict__ J;      // [nDesign,36] [.,6] [.,2 nLine] [.,2 nLine,6], each or null
     int *__restrict__ flags;            // [nDesign]
-    int chains;                         // host side only: a continuation row among the records, so the CHAINS kernels run
+    int chains;                         // host side only: 1 a continuation row among the records, so the CHAINS kernels run; 2 a leg row: BRIDLES
     double *__restrict__ Lr;            // [nDesign,2 nLine,3,6] or null: J as rows of k_sweep_channels (plane 0 = J, the other two zero)
+    double *__restrict__ bw;            // [nDesign,nLine,MOOR_BW_N], only with bridles
 };
 
 struct MoorEval {
@@ -265,15 +273,506 @@ __device__ __noinline__ void moor_chain_record(const double *__restrict__ line, 
         if (i < c.n) lw[(size_t)i * MOOR_LW_N + 23] = (double)flag;
 }
 
+// ---- bridles (include/raftx_mooring.h: stem rows anchor -> junction, then 2 .. RAFTX_MOOR_MAX_LEG leg rows junction ->
+// fairlead).  The unknown is the junction P; at every P the stem is shot in the vertical plane through the anchor and P
+// (moor_chain_eval) and every leg, a suspended catenary, in its own plane (moor_eval without a seabed), and
+//     R(P) = f_stem + sum f_leg,lower end - (0, 0, W_junction) = 0,       dR/dP = -K_PP = -(K_stem + sum K_leg)
+// with the 3 x 3 end stiffness K = [k11 u u' + HF/XF (I_h - u u'), k12 u; k12 u', k22] of an element, (k) the inverse of its
+// catenary Jacobian.  At the solution the fairleads see K_ij = K_i d_ij - K_i K_PP^-1 K_j, and dP/dx6 = K_PP^-1 sum K_j [I, -[r_j x]].
+// The legs of the rows after a head row `line` and its nc continuation rows (0: no bridle), within the nAfter rows that follow
+__device__ __forceinline__ int moor_bridle_legs(const double *__restrict__ line, const int nAfter, const int nc) {
+    int n = 0;
+    while (nc + n < nAfter && n < RAFTX_MOOR_MAX_LEG && line[(size_t)(nc + n + 1) * RAFTX_ML_N + RAFTX_ML_LEG] != 0.0) n++;
+    return n;
+}
+// The rows of the bridle whose head row is `line` (0: `line` is no head row of a bridle)
+__device__ __forceinline__ int moor_bridle_rows(const double *__restrict__ line, const int nAfter) {
+    if (line[RAFTX_ML_CONT] != 0.0 || line[RAFTX_ML_LEG] != 0.0) return 0;
+    int nc = 0;
+    while (nc < nAfter && nc < RAFTX_MOOR_MAX_SEG - 1 && line[(size_t)(nc + 1) * RAFTX_ML_N + RAFTX_ML_CONT] != 0.0) nc++;
+    const int nleg = moor_bridle_legs(line, nAfter, nc);
+    return nleg ? nc + 1 + nleg : 0;
+}
+
+// One element between its ends, XF apart horizontally and ZF vertically: the Newton iteration of moor_line_record /
+// moor_chain_record, cold start.  KIND 0: the chain c; 1: one suspended segment (c.L[0], c.EA[0], c.w[0]; no seabed); 2: the
+// chain c with the suspended segment top = (L, EA, w, weight of the point at its lower end) above it -- (H, V) at the top of
+// that segment, Vtop the chain's own.
+template <int KIND>
+__device__ __forceinline__ void moor_shoot_eval(const double H, const double V, const MoorChain &c, const bool seabed, const double top[4],
+                                                MoorEval &e, double Vtop[RAFTX_MOOR_MAX_SEG]) {
+    if (KIND == 1) moor_eval(H, V, c.L[0], c.EA[0], c.w[0], false, e);
+    else if (KIND == 0) moor_chain_eval(H, V, c, seabed, e, Vtop);
+    else {
+        MoorEval t;
+        moor_eval(H, V, top[0], top[1], top[2], false, t);
+        moor_chain_eval(H, (V - top[2] * top[0]) - top[3], c, seabed, e, Vtop);
+        e.X = t.X + e.X; e.Z = t.Z + e.Z; e.a11 = t.a11 + e.a11; e.a12 = t.a12 + e.a12; e.a22 = t.a22 + e.a22;
+    }
+}
+template <int KIND>
+__device__ __forceinline__ bool moor_shoot(const MoorChain &c, const bool seabed, const double top[4], const double Lt, const double we,
+                                           const double XF, const double ZF, double &H, double &V, MoorEval &e,
+                                           double Vtop[RAFTX_MOOR_MAX_SEG]) {
+    const double lam = (Lt * Lt <= XF * XF + ZF * ZF) ? 0.2 : sqrt(3.0 * ((Lt * Lt - ZF * ZF) / (XF * XF) - 1.0));
+    H = fabs(we * XF / (2.0 * lam));
+    V = 0.5 * we * (ZF / tanh(lam) + Lt);
+    moor_shoot_eval<KIND>(H, V, c, seabed, top, e, Vtop);
+    double eX = e.X - XF, eZ = e.Z - ZF, res = fmax(fabs(eX), fabs(eZ)) / Lt, a = 1.0;
+    bool conv = res == 0.0;
+    int it = 0;
+    while (!conv && it < MOOR_MAX_IT) {
+        it++;
+        const double det = e.a11 * e.a22 - e.a12 * e.a12;
+        const double dH = -(e.a22 * eX - e.a12 * eZ) / det, dV = -(e.a11 * eZ - e.a12 * eX) / det;
+        double s = a;
+        if (H + s * dH <= 0.0) s = -0.5 * H / dH;
+        const double Ht = H + s * dH, Vt = V + s * dV;
+        MoorEval n;
+        double Vn[RAFTX_MOOR_MAX_SEG] = {0, 0, 0, 0};
+        moor_shoot_eval<KIND>(Ht, Vt, c, seabed, top, n, Vn);
+        const double nX = n.X - XF, nZ = n.Z - ZF, rn = fmax(fabs(nX), fabs(nZ)) / Lt;
+        if (rn < res) {
+            H = Ht; V = Vt; e = n; eX = nX; eZ = nZ; res = rn; a = 1.0;
+            if (KIND != 1)
+#pragma unroll
+                for (int i = 0; i < RAFTX_MOOR_MAX_SEG; i++) Vtop[i] = Vn[i];
+            conv = res == 0.0;
+        } else if (res <= MOOR_TIGHT) {
+            conv = true;
+        } else {
+            a *= 0.5;
+            if (a < 0x1p-40) break;
+        }
+    }
+    return conv;
+}
+
+// A solved element at one junction position: its end force pieces and the 3 x 3 end stiffness K (xx xy xz yy yz zz)
+struct MoorEnd {
+    double H, V, ux, uy, k11, k12, k22, K[6];
+};
+__device__ __forceinline__ void moor_end_set(MoorEnd &m, const double H, const double V, const MoorEval &e, const double ux,
+                                             const double uy, const double XF) {
+    const double det = e.a11 * e.a22 - e.a12 * e.a12;
+    m.H = H; m.V = V; m.ux = ux; m.uy = uy;
+    m.k11 = e.a22 / det; m.k12 = -e.a12 / det; m.k22 = e.a11 / det;
+    const double th = H / XF;
+    m.K[0] = m.k11 * ux * ux + th * (1.0 - ux * ux);
+    m.K[1] = m.k11 * ux * uy - th * (ux * uy);
+    m.K[2] = m.k12 * ux;
+    m.K[3] = m.k11 * uy * uy + th * (1.0 - uy * uy);
+    m.K[4] = m.k12 * uy;
+    m.K[5] = m.k22;
+}
+// y = S x with S symmetric (xx xy xz yy yz zz)
+__device__ __forceinline__ void moor_sym_mul(const double S[6], const double x[3], double y[3]) {
+    y[0] = S[0] * x[0] + S[1] * x[1] + S[2] * x[2];
+    y[1] = S[1] * x[0] + S[3] * x[1] + S[4] * x[2];
+    y[2] = S[2] * x[0] + S[4] * x[1] + S[5] * x[2];
+}
+__device__ __forceinline__ double moor_sym_at(const double S[6], const int i, const int j) {
+    const int a = i < j ? i : j, b = i < j ? j : i;
+    return S[a == 0 ? b : (a == 1 ? 2 + b : 5)];
+}
+
+// A bridle at the pose: the head row `line`, its nc continuation rows and the nleg leg rows after them.  The lw records of all
+// its rows carry the flag only; its share of C_moor / F_moor and every row end's T and J go to the bw records (MOOR_BW_N per
+// row, bw at the head row's); line_out rows at lo_out unless flagged.  NOT inlined, for the reason moor_chain_record gives.
+__device__ __noinline__ void moor_bridle_record(const double *__restrict__ line, const int nc, const int nleg, const MoorPose pose,
+                                                const double depth, double *__restrict__ lw, double *__restrict__ bw,
+                                                double *__restrict__ lo_out) {
+    const int nrow = nc + 1 + nleg;
+    double rec[RAFTX_ML_N], ps[6];
+#pragma unroll
+    for (int i = 0; i < RAFTX_ML_N; i++) rec[i] = line[i];
+#pragma unroll
+    for (int i = 0; i < 6; i++) ps[i] = pose.v[i];
+    MoorChain c;                                                 // the stem
+    c.n = nc + 1;
+    c.L[0] = rec[6]; c.EA[0] = rec[7]; c.w[0] = rec[8]; c.Wj[0] = 0.0;
+    bool fin = true;
+    for (int i = 0; i < 10; i++) fin = fin && isfinite(rec[i]);
+    for (int i = 0; i < 6; i++) fin = fin && isfinite(ps[i]);
+    bool pos = c.L[0] > 0.0 && c.EA[0] > 0.0 && c.w[0] > 0.0;
+    double Ls = c.L[0], Ws = c.w[0] * c.L[0];
+#pragma unroll
+    for (int i = 1; i < RAFTX_MOOR_MAX_SEG; i++) {
+        c.L[i] = 1.0; c.EA[i] = 1.0; c.w[i] = 1.0; c.Wj[i] = 0.0;
+        if (i >= c.n) continue;
+        const double *p = line + (size_t)i * RAFTX_ML_N;
+        c.L[i] = p[6]; c.EA[i] = p[7]; c.w[i] = p[8]; c.Wj[i] = p[RAFTX_ML_WJOINT];
+        fin = fin && isfinite(c.L[i]) && isfinite(c.EA[i]) && isfinite(c.w[i]) && isfinite(p[9]) && isfinite(c.Wj[i]);
+        pos = pos && c.L[i] > 0.0 && c.EA[i] > 0.0 && c.w[i] > 0.0;
+        Ls += c.L[i];
+        Ws += c.w[i] * c.L[i] + c.Wj[i];
+    }
+    MoorChain g[RAFTX_MOOR_MAX_LEG];                             // the legs, one segment each
+    double rl[RAFTX_MOOR_MAX_LEG][3], pf[RAFTX_MOOR_MAX_LEG][3];  // arms R r_f and fairlead positions
+    double Wj = 0.0, Wl = 0.0;
+#pragma unroll
+    for (int i = 0; i < RAFTX_MOOR_MAX_LEG; i++) {
+        g[i].n = 1; g[i].L[0] = 1.0; g[i].EA[0] = 1.0; g[i].w[0] = 1.0; g[i].Wj[0] = 0.0;
+        rl[i][0] = rl[i][1] = rl[i][2] = 0.0;
+        pf[i][0] = pf[i][1] = pf[i][2] = 0.0;
+        if (i >= nleg) continue;
+        const double *p = line + (size_t)(nc + 1 + i) * RAFTX_ML_N;
+        double lr[RAFTX_ML_N];
+#pragma unroll
+        for (int k = 0; k < RAFTX_ML_N; k++) lr[k] = p[k];
+        for (int k = 3; k < 11; k++) fin = fin && isfinite(lr[k]);
+        g[i].L[0] = lr[6]; g[i].EA[0] = lr[7]; g[i].w[0] = lr[8];
+        pos = pos && lr[6] > 0.0 && lr[7] > 0.0 && lr[8] > 0.0;
+        if (i == 0) Wj = lr[RAFTX_ML_WJOINT];
+        Wl += lr[8] * lr[6];
+        if (fin) {
+            moor_arm(lr, ps, rl[i]);
+#pragma unroll
+            for (int k = 0; k < 3; k++) pf[i][k] = ps[k] + rl[i][k];
+        }
+    }
+    const double az = rec[2];
+    const double Wt = Ws + Wl;                                   // the scale of the force balance
+    int flag = 0;
+    if (!fin || !pos || !(Ws > 0.0) || !(Wt + Wj > 0.0) || az < -depth - 1e-6 * depth) flag = RAFTX_MOOR_BAD_LINE;
+    if (!flag) {
+        bool slack = true;
+#pragma unroll
+        for (int i = 0; i < RAFTX_MOOR_MAX_LEG; i++) {
+            if (i >= nleg) continue;
+            const double dx = pf[i][0] - rec[0], dy = pf[i][1] - rec[1], XFi = sqrt(dx * dx + dy * dy), ZFi = pf[i][2] - az;
+            if (!(ZFi > 0.0)) flag = RAFTX_MOOR_BAD_LINE;
+            slack = slack && (Ls + g[i].L[0] >= XFi + ZFi);
+        }
+        if (!flag && slack) flag = RAFTX_MOOR_SLACK;
+    }
+    const bool seabed = fabs(az + depth) <= 1e-6 * depth;
+    const double wes = Ws / Ls;
+    // the accepted state: junction, residual, elements
+    double P[3] = {0, 0, 0}, R[3] = {0, 0, 0}, d[3] = {0, 0, 0}, Ki[6] = {0, 0, 0, 0, 0, 0}, res = 0.0, a = 1.0;
+    MoorEnd S, G[RAFTX_MOOR_MAX_LEG];
+    MoorEval es;
+    double Vtop[RAFTX_MOOR_MAX_SEG] = {0, 0, 0, 0}, XFs = 0.0;
+    int it = 0;
+    bool have = false, conv = false, up = false;
+    if (!flag) {
+        // the start: the stem with ONE equivalent leg above it (the legs' summed EA and weight, their mean length along the axis)
+        // to the centroid of the fairleads, shot as a composite line; the junction is that leg's span below the centroid.  Where
+        // this plane problem has no solution: on the straight line from the anchor to the centroid.
+        double cf[3] = {0, 0, 0};
+#pragma unroll
+        for (int i = 0; i < RAFTX_MOOR_MAX_LEG; i++)
+            if (i < nleg)
+                for (int k = 0; k < 3; k++) cf[k] += pf[i][k];
+        for (int k = 0; k < 3; k++) cf[k] = cf[k] / (double)nleg;
+        double Le = 0.0, EAe = 0.0;
+#pragma unroll
+        for (int i = 0; i < RAFTX_MOOR_MAX_LEG; i++) {
+            if (i >= nleg) continue;
+            const double ox = pf[i][0] - cf[0], oy = pf[i][1] - cf[1], oz = pf[i][2] - cf[2], Li = g[i].L[0];
+            Le += sqrt(fmax(Li * Li - (ox * ox + oy * oy + oz * oz), 0.25 * Li * Li));
+            EAe += g[i].EA[0];
+        }
+        Le = Le / (double)nleg;
+        double Pt[3];
+#pragma unroll
+        for (int k = 0; k < 3; k++) Pt[k] = rec[k] + (Ls / (Ls + Le)) * (cf[k] - rec[k]);
+        {
+            const double dxc = cf[0] - rec[0], dyc = cf[1] - rec[1], ZFc = cf[2] - az, XFc = sqrt(dxc * dxc + dyc * dyc);
+            if (XFc > 1e-9 * (Ls + Le) && (!seabed || Ls + Le < XFc + ZFc)) {
+                const double top[4] = {Le, EAe, Wl / Le, Wj};
+                double H0, V0, V4[RAFTX_MOOR_MAX_SEG] = {0, 0, 0, 0};
+                MoorEval e0;
+                if (moor_shoot<2>(c, seabed, top, Ls + Le, (Wt + Wj) / (Ls + Le), XFc, ZFc, H0, V0, e0, V4)) {
+                    MoorEval t;
+                    moor_eval(H0, V0, top[0], top[1], top[2], false, t);
+                    Pt[0] = cf[0] - t.X * (dxc / XFc);
+                    Pt[1] = cf[1] - t.X * (dyc / XFc);
+                    Pt[2] = cf[2] - t.Z;
+                }
+            }
+        }
+        for (;;) {
+            // everything at the trial junction Pt
+            bool ok = true;
+            MoorEnd St, Gt[RAFTX_MOOR_MAX_LEG];
+            MoorEval et;
+            double Vt[RAFTX_MOOR_MAX_SEG] = {0, 0, 0, 0}, Rt[3], Kt[6], XFt = 0.0;
+            {
+                const double dx = Pt[0] - rec[0], dy = Pt[1] - rec[1], ZF = Pt[2] - az;
+                XFt = sqrt(dx * dx + dy * dy);
+                ok = XFt > 1e-9 * Ls && (!seabed || (ZF > 0.0 && Ls < XFt + ZF));      // (a stem on the seabed: no fully slack profile)
+                if (ok) {
+                    double H, V;
+                    ok = moor_shoot<0>(c, seabed, nullptr, Ls, wes, XFt, ZF, H, V, et, Vt);
+                    moor_end_set(St, H, V, et, dx / XFt, dy / XFt, XFt);
+                    Rt[0] = -H * St.ux; Rt[1] = -H * St.uy; Rt[2] = -V - Wj;
+#pragma unroll
+                    for (int k = 0; k < 6; k++) Kt[k] = St.K[k];
+                }
+            }
+#pragma unroll
+            for (int i = 0; i < RAFTX_MOOR_MAX_LEG; i++) {
+                if (i >= nleg || !ok) continue;
+                const double dx = pf[i][0] - Pt[0], dy = pf[i][1] - Pt[1], ZF = pf[i][2] - Pt[2];
+                const double XF = sqrt(dx * dx + dy * dy);
+                ok = XF > 1e-9 * g[i].L[0];
+                if (!ok) continue;
+                double H, V, Vn[RAFTX_MOOR_MAX_SEG];
+                MoorEval el;
+                ok = moor_shoot<1>(g[i], false, nullptr, g[i].L[0], g[i].w[0], XF, ZF, H, V, el, Vn);
+                moor_end_set(Gt[i], H, V, el, dx / XF, dy / XF, XF);
+                Rt[0] += H * Gt[i].ux; Rt[1] += H * Gt[i].uy; Rt[2] += V - g[i].w[0] * g[i].L[0];
+#pragma unroll
+                for (int k = 0; k < 6; k++) Kt[k] += Gt[i].K[k];
+            }
+            const double rt = ok ? fmax(fmax(fabs(Rt[0]), fabs(Rt[1])), fabs(Rt[2])) / Wt : 0.0;
+            bool take = false;
+            if (!have) {
+                if (!ok) break;                                  // no start: NO_CONVERGENCE
+                take = true;
+            } else if (ok && rt < res) {
+                take = true;
+                up = false;
+            } else if (res <= MOOR_TIGHT) {
+                conv = true;
+                break;
+            } else if (ok && !up && a == 1.0 && rt <= MOOR_BR_GROW * res) {
+                take = true;                                     // a full step from the soft side lands on the stiff side: Newton's way in
+                up = true;
+            } else {
+                a *= 0.5;
+                if (a < 0x1p-40) break;
+            }
+            if (take) {
+                have = true;
+#pragma unroll
+                for (int k = 0; k < 3; k++) { P[k] = Pt[k]; R[k] = Rt[k]; }
+                res = rt; a = 1.0;
+                S = St; es = et; XFs = XFt;
+#pragma unroll
+                for (int i = 0; i < RAFTX_MOOR_MAX_SEG; i++) Vtop[i] = Vt[i];
+#pragma unroll
+                for (int i = 0; i < RAFTX_MOOR_MAX_LEG; i++) G[i] = Gt[i];
+                // K_PP^-1 (symmetric) by cofactors, and the Newton step d = K_PP^-1 R
+                const double c0 = Kt[3] * Kt[5] - Kt[4] * Kt[4], c1 = Kt[2] * Kt[4] - Kt[1] * Kt[5], c2 = Kt[1] * Kt[4] - Kt[2] * Kt[3];
+                const double det = Kt[0] * c0 + Kt[1] * c1 + Kt[2] * c2;
+                Ki[0] = c0 / det; Ki[1] = c1 / det; Ki[2] = c2 / det;
+                Ki[3] = (Kt[0] * Kt[5] - Kt[2] * Kt[2]) / det;
+                Ki[4] = (Kt[1] * Kt[2] - Kt[0] * Kt[4]) / det;
+                Ki[5] = (Kt[0] * Kt[3] - Kt[1] * Kt[1]) / det;
+                moor_sym_mul(Ki, R, d);
+                if (res == 0.0) { conv = true; break; }
+            }
+            if (it >= MOOR_BR_MAX_IT) break;
+            it++;
+#pragma unroll
+            for (int k = 0; k < 3; k++) Pt[k] = P[k] + a * d[k];
+        }
+        if (!conv) flag = RAFTX_MOOR_NO_CONVERGENCE;
+    }
+    if (!flag) {
+        // the seabed: the stem by the chain's rule, then the junction and the sags of the legs
+        const double floor = -depth - 1e-6 * depth;
+        if (seabed && Vtop[0] <= 0.0) flag = RAFTX_MOOR_GROUNDED;
+        double z = az;
+#pragma unroll
+        for (int i = 0; i < RAFTX_MOOR_MAX_SEG; i++) {
+            if (i >= c.n) continue;
+            const double Vb = Vtop[i] - c.w[i] * c.L[i];
+            if (!(i == 0 && es.contact) && Vb < 0.0 && Vtop[i] > 0.0) {
+                const double vb = Vb / S.H, sb = sqrt(1.0 + vb * vb);
+                const double drop = (S.H / c.w[i]) * (vb * vb / (sb + 1.0)) + Vb * Vb / (2.0 * c.EA[i] * c.w[i]);
+                if (z - drop < floor) flag = RAFTX_MOOR_GROUNDED;
+            }
+            MoorEval s;
+            moor_eval(S.H, Vtop[i], c.L[i], c.EA[i], c.w[i], seabed && i == 0, s);
+            z += s.Z;
+            if (i + 1 < c.n && z < floor) flag = RAFTX_MOOR_GROUNDED;
+        }
+        if (P[2] < floor) flag = RAFTX_MOOR_GROUNDED;
+#pragma unroll
+        for (int i = 0; i < RAFTX_MOOR_MAX_LEG; i++) {
+            if (i >= nleg) continue;
+            const double Vb = G[i].V - g[i].w[0] * g[i].L[0];
+            if (Vb < 0.0 && G[i].V > 0.0) {
+                const double vb = Vb / G[i].H, sb = sqrt(1.0 + vb * vb);
+                const double drop = (G[i].H / g[i].w[0]) * (vb * vb / (sb + 1.0)) + Vb * Vb / (2.0 * g[i].EA[0] * g[i].w[0]);
+                if (P[2] - drop < floor) flag = RAFTX_MOOR_GROUNDED;
+            }
+        }
+    }
+    if (!flag) {
+        // D_j = K_PP^-1 K_j, and dP/dx6 = sum_j D_j [I, -[r_j x]]
+        double D[RAFTX_MOOR_MAX_LEG][3][3], DP[3][6];
+#pragma unroll
+        for (int i = 0; i < 3; i++)
+#pragma unroll
+            for (int j = 0; j < 6; j++) DP[i][j] = 0.0;
+#pragma unroll
+        for (int j = 0; j < RAFTX_MOOR_MAX_LEG; j++) {
+            if (j >= nleg) continue;
+            const double *r = rl[j];
+            const double RX[3][3] = {{0.0, -r[2], r[1]}, {r[2], 0.0, -r[0]}, {-r[1], r[0], 0.0}};
+#pragma unroll
+            for (int i = 0; i < 3; i++) {
+#pragma unroll
+                for (int k = 0; k < 3; k++)
+                    D[j][i][k] = moor_sym_at(Ki, i, 0) * moor_sym_at(G[j].K, 0, k) + moor_sym_at(Ki, i, 1) * moor_sym_at(G[j].K, 1, k) +
+                                 moor_sym_at(Ki, i, 2) * moor_sym_at(G[j].K, 2, k);
+#pragma unroll
+                for (int k = 0; k < 3; k++) {
+                    DP[i][k] += D[j][i][k];
+                    DP[i][3 + k] += -(D[j][i][0] * RX[0][k] + D[j][i][1] * RX[1][k] + D[j][i][2] * RX[2][k]);
+                }
+            }
+        }
+        // the share of C_moor and F_moor: over the pairs of fairleads, then the arm turning of each
+        double C[36], F[6];
+#pragma unroll
+        for (int i = 0; i < 36; i++) C[i] = 0.0;
+#pragma unroll
+        for (int i = 0; i < 6; i++) F[i] = 0.0;
+#pragma unroll
+        for (int i = 0; i < RAFTX_MOOR_MAX_LEG; i++) {
+            if (i >= nleg) continue;
+            const double *ri = rl[i];
+            const double RI[3][3] = {{0.0, -ri[2], ri[1]}, {ri[2], 0.0, -ri[0]}, {-ri[1], ri[0], 0.0}};
+            const double f[3] = {-G[i].H * G[i].ux, -G[i].H * G[i].uy, -G[i].V};
+            const double FX[3][3] = {{0.0, -f[2], f[1]}, {f[2], 0.0, -f[0]}, {-f[1], f[0], 0.0}};
+#pragma unroll
+            for (int j = 0; j < RAFTX_MOOR_MAX_LEG; j++) {
+                if (j >= nleg) continue;
+                const double *rj = rl[j];
+                const double RJ[3][3] = {{0.0, -rj[2], rj[1]}, {rj[2], 0.0, -rj[0]}, {-rj[1], rj[0], 0.0}};
+                double M[3][3], MR[3][3], RM[3][3];                 // K_ij, K_ij [r_j x], [r_i x] K_ij
+#pragma unroll
+                for (int p = 0; p < 3; p++)
+#pragma unroll
+                    for (int q = 0; q < 3; q++) {
+                        const double kd = moor_sym_at(G[i].K, p, 0) * D[j][0][q] + moor_sym_at(G[i].K, p, 1) * D[j][1][q] +
+                                          moor_sym_at(G[i].K, p, 2) * D[j][2][q];
+                        M[p][q] = (i == j ? moor_sym_at(G[i].K, p, q) : 0.0) - kd;
+                    }
+#pragma unroll
+                for (int p = 0; p < 3; p++)
+#pragma unroll
+                    for (int q = 0; q < 3; q++) {
+                        MR[p][q] = M[p][0] * RJ[0][q] + M[p][1] * RJ[1][q] + M[p][2] * RJ[2][q];
+                        RM[p][q] = RI[p][0] * M[0][q] + RI[p][1] * M[1][q] + RI[p][2] * M[2][q];
+                    }
+#pragma unroll
+                for (int p = 0; p < 3; p++)
+#pragma unroll
+                    for (int q = 0; q < 3; q++) {
+                        const double rmr = RI[p][0] * MR[0][q] + RI[p][1] * MR[1][q] + RI[p][2] * MR[2][q];
+                        C[6 * p + q] += M[p][q];
+                        C[6 * p + 3 + q] += -MR[p][q];
+                        C[6 * (3 + p) + q] += RM[p][q];
+                        C[6 * (3 + p) + 3 + q] += -rmr;
+                    }
+            }
+#pragma unroll
+            for (int p = 0; p < 3; p++)
+#pragma unroll
+                for (int q = 0; q < 3; q++)
+                    C[6 * (3 + p) + 3 + q] += -(FX[p][0] * RI[0][q] + FX[p][1] * RI[1][q] + FX[p][2] * RI[2][q]);
+            F[0] += f[0]; F[1] += f[1]; F[2] += f[2];
+            F[3] += ri[1] * f[2] - ri[2] * f[1];
+            F[4] += ri[2] * f[0] - ri[0] * f[2];
+            F[5] += ri[0] * f[1] - ri[1] * f[0];
+        }
+#pragma unroll
+        for (int i = 0; i < 36; i++) bw[i] = C[i];
+#pragma unroll
+        for (int i = 0; i < 6; i++) bw[36 + i] = F[i];
+        // the stem's rows: T and its gradient for a junction displacement, through dP/dx6
+#pragma unroll
+        for (int i = 0; i < RAFTX_MOOR_MAX_SEG; i++) {
+            if (i >= c.n) continue;
+            double *b = bw + (size_t)i * MOOR_BW_N;
+            const bool ct = i == 0 && es.contact;
+            const double VB = Vtop[i], VA = ct ? 0.0 : VB - c.w[i] * c.L[i];
+            const double TB = sqrt(S.H * S.H + VB * VB), TA = sqrt(S.H * S.H + VA * VA);
+            b[42] = TA; b[43] = TB;
+#pragma unroll
+            for (int e = 0; e < 2; e++) {
+                const double Vx = e ? VB : VA, Tx = e ? TB : TA;
+                const double gX = (S.H * S.k11 + Vx * S.k12) / Tx, gZ = (S.H * S.k12 + Vx * S.k22) / Tx;
+                const double g3[3] = {gX * S.ux, gX * S.uy, gZ};
+#pragma unroll
+                for (int k = 0; k < 6; k++) b[44 + 6 * e + k] = g3[0] * DP[0][k] + g3[1] * DP[1][k] + g3[2] * DP[2][k];
+            }
+            double *o = lo_out ? lo_out + (size_t)i * MOOR_LO_N : nullptr;
+            if (o) {
+                o[0] = S.H; o[1] = VB; o[2] = S.H; o[3] = VA;
+                o[4] = ct ? c.L[0] - VB / c.w[0] : 0.0;
+                o[5] = (double)it;
+                o[6] = ct ? 1.0 : 0.0;
+                o[7] = 0.0;
+            }
+        }
+        // the legs' rows: the relative displacement of their ends is [I, -[r_i x]] - dP/dx6
+#pragma unroll
+        for (int i = 0; i < RAFTX_MOOR_MAX_LEG; i++) {
+            if (i >= nleg) continue;
+            double *b = bw + (size_t)(c.n + i) * MOOR_BW_N;
+            const double *r = rl[i];
+            const double RX[3][3] = {{0.0, -r[2], r[1]}, {r[2], 0.0, -r[0]}, {-r[1], r[0], 0.0}};
+            const double H = G[i].H, VB = G[i].V, VA = VB - g[i].w[0] * g[i].L[0];
+            const double TB = sqrt(H * H + VB * VB), TA = sqrt(H * H + VA * VA);
+            b[42] = TA; b[43] = TB;
+#pragma unroll
+            for (int e = 0; e < 2; e++) {
+                const double Vx = e ? VB : VA, Tx = e ? TB : TA;
+                const double gX = (H * G[i].k11 + Vx * G[i].k12) / Tx, gZ = (H * G[i].k12 + Vx * G[i].k22) / Tx;
+                const double g3[3] = {gX * G[i].ux, gX * G[i].uy, gZ};
+#pragma unroll
+                for (int k = 0; k < 3; k++) {
+                    b[44 + 6 * e + k] = (g3[k] - g3[0] * DP[0][k]) - g3[1] * DP[1][k] - g3[2] * DP[2][k];
+                    const double gr = -(g3[0] * RX[0][k] + g3[1] * RX[1][k] + g3[2] * RX[2][k]);
+                    b[44 + 6 * e + 3 + k] = (gr - g3[0] * DP[0][3 + k]) - g3[1] * DP[1][3 + k] - g3[2] * DP[2][3 + k];
+                }
+            }
+            double *o = lo_out ? lo_out + (size_t)(c.n + i) * MOOR_LO_N : nullptr;
+            if (o) {
+                o[0] = H; o[1] = VB; o[2] = H; o[3] = VA; o[4] = 0.0; o[5] = (double)it; o[6] = 0.0; o[7] = 0.0;
+            }
+        }
+    }
+    for (int i = 0; i < nrow; i++) {
+        double *q = lw + (size_t)i * MOOR_LW_N;
+        for (int k = 0; k < 23; k++) q[k] = 0.0;
+        q[23] = (double)flag;
+    }
+}
+
+// The share of a bridle (the bw record of its head row) in C_moor and F_moor, and a row's T and J: k_moor_design's part
+__device__ __forceinline__ void moor_bridle_share(const double *__restrict__ b, double C[36], double F[6]) {
+#pragma unroll
+    for (int i = 0; i < 36; i++) C[i] += b[i];
+#pragma unroll
+    for (int i = 0; i < 6; i++) F[i] += b[36 + i];
+}
+__device__ __forceinline__ void moor_bridle_TJ(const double *__restrict__ b, const int l, const int nL, double *__restrict__ T,
+                                               double *__restrict__ J) {
+    if (T) { T[l] = b[42]; T[nL + l] = b[43]; }
+    if (J)
+#pragma unroll
+        for (int e = 0; e < 2; e++)
+#pragma unroll
+            for (int k = 0; k < 6; k++) J[(size_t)(e * nL + l) * 6 + k] = b[44 + 6 * e + k];
+}
+
 // One line at the pose ps: the record lw [MOOR_LW_N] (in global memory) and lo [MOOR_LO_N].  The body of k_moor_line, shared
 // with k_mean_pose (raftx_statics.h).  Returns true: lo is this row's line_out.  CHAINS: `line` may be the head row of a
 // composite line, with its continuation rows among the nAfter rows of the design that follow it -- then the records of all of
 // them are written, and their line_out rows at lo_out (this row's place in global memory, or null) unless the chain is flagged
 // -- or a continuation row itself, for which nothing is written; false is returned in both cases.
-template <bool CHAINS>
+template <bool CHAINS, bool BRIDLES = false>
 __device__ __forceinline__ bool moor_line_record(const double *__restrict__ line, const int nAfter, const double ps[6],
                                                  const double depth, double *__restrict__ lw, double lo[MOOR_LO_N],
-                                                 double *__restrict__ lo_out) {
+                                                 double *__restrict__ lo_out, double *__restrict__ bw = nullptr) {
     double rec[RAFTX_ML_N];
     {
         const double2 *p = reinterpret_cast<const double2 *>(line);
@@ -288,8 +787,19 @@ __device__ __forceinline__ bool moor_line_record(const double *__restrict__ line
     for (int i = 0; i < MOOR_LO_N; i++) lo[i] = nan;
     if (CHAINS) {
         if (rec[RAFTX_ML_CONT] != 0.0) return false;
+        if (BRIDLES && rec[RAFTX_ML_LEG] != 0.0) return false;
         int nc = 0;
         while (nc < nAfter && nc < RAFTX_MOOR_MAX_SEG - 1 && line[(size_t)(nc + 1) * RAFTX_ML_N + RAFTX_ML_CONT] != 0.0) nc++;
+        if (BRIDLES) {
+            const int nleg = moor_bridle_legs(line, nAfter, nc);
+            if (nleg) {
+                MoorPose pose;
+#pragma unroll
+                for (int i = 0; i < 6; i++) pose.v[i] = ps[i];
+                moor_bridle_record(line, nc, nleg, pose, depth, lw, bw, lo_out);
+                return false;
+            }
+        }
         if (nc) {
             MoorPose pose;
 #pragma unroll
@@ -380,7 +890,7 @@ __device__ __forceinline__ bool moor_line_record(const double *__restrict__ line
     return true;
 }
 
-template <bool CHAINS>
+template <bool CHAINS, bool BRIDLES = false>
 __global__ void __launch_bounds__(MOOR_THREADS) k_moor_line(MoorArgs A) {
     const long long t = (long long)blockIdx.x * MOOR_THREADS + threadIdx.x;
     if (t >= (long long)A.nDesign * A.nLine) return;
@@ -389,9 +899,10 @@ __global__ void __launch_bounds__(MOOR_THREADS) k_moor_line(MoorArgs A) {
     if (A.pose)
         for (int i = 0; i < 6; i++) ps[i] = A.pose[(size_t)d * 6 + i];
     double lo[MOOR_LO_N];
-    const bool mine = moor_line_record<CHAINS>(A.lines + (size_t)t * RAFTX_ML_N, A.nLine - 1 - (int)(t % A.nLine), ps, A.depth,
-                                               A.lw + (size_t)t * MOOR_LW_N, lo,
-                                               A.line_out ? A.line_out + (size_t)t * MOOR_LO_N : nullptr);
+    const bool mine = moor_line_record<CHAINS, BRIDLES>(A.lines + (size_t)t * RAFTX_ML_N, A.nLine - 1 - (int)(t % A.nLine), ps, A.depth,
+                                                        A.lw + (size_t)t * MOOR_LW_N, lo,
+                                                        A.line_out ? A.line_out + (size_t)t * MOOR_LO_N : nullptr,
+                                                        BRIDLES ? A.bw + (size_t)t * MOOR_BW_N : nullptr);
     if (A.line_out && mine)
         for (int i = 0; i < MOOR_LO_N; i++) A.line_out[(size_t)t * MOOR_LO_N + i] = lo[i];
 }
@@ -448,6 +959,7 @@ __device__ __forceinline__ void moor_line_TJ(const double *__restrict__ q, const
         }
 }
 
+template <bool BRIDLES>
 __global__ void __launch_bounds__(MOOR_THREADS) k_moor_design(MoorArgs A) {
     const int d = blockIdx.x * MOOR_THREADS + threadIdx.x;
     if (d >= A.nDesign) return;
@@ -474,6 +986,25 @@ __global__ void __launch_bounds__(MOOR_THREADS) k_moor_design(MoorArgs A) {
     for (int i = 0; i < 6; i++) F[i] = 0.0;
     for (int l = 0; l < nL; l++) {
         const double *q = lw0 + (size_t)l * MOOR_LW_N;
+        if (BRIDLES) {
+            const int nb = moor_bridle_rows(A.lines + ((size_t)d * nL + l) * RAFTX_ML_N, nL - 1 - l);
+            if (nb) {                                            // a bridle, from its head row: the share once, T and J of all its rows
+                const double *b = A.bw + ((size_t)d * nL + l) * MOOR_BW_N;
+                moor_bridle_share(b, C, F);
+                for (int k = 0; k < nb; k++) {
+                    moor_bridle_TJ(b + (size_t)k * MOOR_BW_N, l + k, nL, T, J);
+                    if (A.Lr)
+#pragma unroll
+                        for (int e = 0; e < 2; e++) {
+                            double *o = A.Lr + ((size_t)d * 2 * nL + (e * nL + l + k)) * 18;
+#pragma unroll
+                            for (int i = 0; i < 18; i++) o[i] = i < 6 ? b[(size_t)k * MOOR_BW_N + 44 + 6 * e + i] : 0.0;
+                        }
+                }
+                l += nb - 1;
+                continue;
+            }
+        }
         moor_line_share(q, C, F);
         const double r[3] = {q[3], q[4], q[5]};
         moor_line_TJ(q, l, nL, T, J);

@@ -33,7 +33,8 @@ struct MeanPoseArgs {
     double *__restrict__ pose, *__restrict__ C, *__restrict__ F, *__restrict__ T, *__restrict__ J, *__restrict__ Fres;   // each or null
     int *__restrict__ iterations;       // [nDesign] or null
     int *__restrict__ flags;            // [nDesign]
-    int chains;                         // host side only: a continuation row among the records, so k_mean_pose<true> runs
+    int chains;                         // host side only: 1 a continuation row among the records, so k_mean_pose<true> runs; 2 a leg row
+    double *__restrict__ bw;            // [nDesign,nLine,MOOR_BW_N], only with bridles
 };
 
 // dX = K^-1 Y by Gaussian elimination of [K | Y] with partial pivoting (the first row of the largest |a|, as LAPACK's gesv
@@ -87,7 +88,7 @@ __device__ __forceinline__ bool mp_solve(const double K[36], const double Y[6], 
     return ok;
 }
 
-template <bool CHAINS>
+template <bool CHAINS, bool BRIDLES = false>
 __global__ void __launch_bounds__(MP_THREADS) k_mean_pose(MeanPoseArgs A) {
     const int G = A.G, nL = A.nLine;
     const int d = blockIdx.x * (MP_THREADS / G) + (int)threadIdx.x / G, g = (int)threadIdx.x % G;
@@ -103,8 +104,8 @@ __global__ void __launch_bounds__(MP_THREADS) k_mean_pose(MeanPoseArgs A) {
         if (phase < 2)
             for (int l = g; l < nL; l += G) {
                 double lo[MOOR_LO_N];
-                moor_line_record<CHAINS>(A.lines + (dd * nL + l) * RAFTX_ML_N, nL - 1 - l, x, A.depth, lw0 + (size_t)l * MOOR_LW_N, lo,
-                                         nullptr);
+                moor_line_record<CHAINS, BRIDLES>(A.lines + (dd * nL + l) * RAFTX_ML_N, nL - 1 - l, x, A.depth, lw0 + (size_t)l * MOOR_LW_N,
+                                                  lo, nullptr, BRIDLES ? A.bw + (dd * nL + l) * MOOR_BW_N : nullptr);
             }
         __syncthreads();                                         // the group's records are in memory
         if (phase < 2) {
@@ -119,7 +120,17 @@ __global__ void __launch_bounds__(MP_THREADS) k_mean_pose(MeanPoseArgs A) {
                 for (int i = 0; i < 36; i++) C[i] = 0.0;
 #pragma unroll
                 for (int i = 0; i < 6; i++) F[i] = 0.0;
-                for (int l = 0; l < nL; l++) moor_line_share(lw0 + (size_t)l * MOOR_LW_N, C, F);
+                for (int l = 0; l < nL; l++) {
+                    if (BRIDLES) {                                // a bridle from its head row, once (k_moor_design's order)
+                        const int nb = moor_bridle_rows(A.lines + (dd * nL + l) * RAFTX_ML_N, nL - 1 - l);
+                        if (nb) {
+                            moor_bridle_share(A.bw + (dd * nL + l) * MOOR_BW_N, C, F);
+                            l += nb - 1;
+                            continue;
+                        }
+                    }
+                    moor_line_share(lw0 + (size_t)l * MOOR_LW_N, C, F);
+                }
                 const double *Kh = A.K_hs + dd * 36;
 #pragma unroll
                 for (int i = 0; i < 6; i++) {
@@ -141,9 +152,18 @@ __global__ void __launch_bounds__(MP_THREADS) k_mean_pose(MeanPoseArgs A) {
 #pragma unroll
                             for (int i = 0; i < 36; i++) A.C[dd * 36 + i] = C[i];
                         if (A.T || A.J)
-                            for (int l = 0; l < nL; l++)
-                                moor_line_TJ(lw0 + (size_t)l * MOOR_LW_N, l, nL, A.T ? A.T + dd * 2 * nL : nullptr,
-                                             A.J ? A.J + dd * 12 * nL : nullptr);
+                            for (int l = 0; l < nL; l++) {
+                                double *Td = A.T ? A.T + dd * 2 * nL : nullptr, *Jd = A.J ? A.J + dd * 12 * nL : nullptr;
+                                if (BRIDLES) {
+                                    const int nb = moor_bridle_rows(A.lines + (dd * nL + l) * RAFTX_ML_N, nL - 1 - l);
+                                    if (nb) {
+                                        for (int k = 0; k < nb; k++) moor_bridle_TJ(A.bw + (dd * nL + l + k) * MOOR_BW_N, l + k, nL, Td, Jd);
+                                        l += nb - 1;
+                                        continue;
+                                    }
+                                }
+                                moor_line_TJ(lw0 + (size_t)l * MOOR_LW_N, l, nL, Td, Jd);
+                            }
                     }
                     phase = 2;
                 } else {

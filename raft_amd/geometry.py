@@ -500,3 +500,38 @@ def volturnus_mooring_program(base_design, rho=1025.0, g=9.81):
         fy = const(f[1]) if cy is None else c(ocD=0.5 * cy, ocR=cy)              # :79 leaves y of the first fairlead alone
         P.ends(l, [const(a[0]), const(a[1]), const(a[2])], [c(ocD=0.5 * cx, ocR=cx), fy, const(f[2])])
     return P
+
+
+def volturnus_bridle_program(base_design, stem=780.0, leg=110.0, rho=1025.0, g=9.81):
+    """The deck of ``volturnus_mooring_program`` with every line ending in a two-leg bridle on NEIGHBOURING outer columns (a
+    delta connection, the usual way to give a narrow platform yaw stiffness), as a raft_amd.mooring.MooringProgram over the
+    parameters of ``volturnus_params``.  Bridle k keeps line k's anchor radius and depth, line type and fairlead depth; its
+    anchor lies midway between two columns (headings 120 / 240 / 0 deg), its stem (one row, length ``stem``) ends at the
+    junction, and its two legs (length ``leg`` each) run to the outer faces of the columns either side, at the radius
+    ocR + ocD/2 and the headings (60, 180) / (180, 300) / (300, 60) deg: the leg rows' fairleads follow the columns as the
+    single lines' do (raft/parametersweep.py:79-83); the anchors do not move.  Rows: stem, leg, leg per bridle
+    (include/raftx_mooring.h)."""
+    from .mooring import ML_LEG, ML_N, MooringProgram, lines_from_design
+    lines, _ = lines_from_design(base_design, rho=rho, g=g)
+    assert len(lines) == 3, "not the VolturnUS-S mooring layout"
+    col = {60: (np.cos(np.deg2rad(60)), np.sin(np.deg2rad(60))), 180: (-1.0, 0.0), 300: (np.cos(np.deg2rad(300)), np.sin(np.deg2rad(300)))}
+    rows = np.zeros((9, ML_N))
+    for k, (head, pair) in enumerate(((120.0, (60, 180)), (240.0, (180, 300)), (0.0, (300, 60)))):
+        a = lines[k, 0:3]
+        R = float(np.hypot(a[0], a[1]))
+        rows[3 * k, 0:3] = (R * np.cos(np.deg2rad(head)), R * np.sin(np.deg2rad(head)), a[2])
+        rows[3 * k, 6:9] = (stem, lines[k, 7], lines[k, 8])
+        r0 = float(np.hypot(lines[k, 3], lines[k, 4]))              # the base deck's fairlead radius: the unedited records
+        for i, h in enumerate(pair):
+            row = rows[3 * k + 1 + i]
+            row[3:6] = (r0 * col[h][0], r0 * col[h][1], lines[k, 5])
+            row[6:9] = (leg, lines[k, 7], lines[k, 8])
+            row[ML_LEG] = 1.0
+    P = MooringProgram(rows, 5)
+    c = lambda c0=0.0, ccD=0.0, ocD=0.0, T=0.0, ocR=0.0, pH=0.0: [c0, ccD, ocD, T, ocR, pH]
+    for k, pair in enumerate(((60, 180), (180, 300), (300, 60))):
+        for i, h in enumerate(pair):
+            cx, cy = col[h]
+            P.ends(3 * k + 1 + i, None, [c(ocD=0.5 * cx, ocR=cx), c(ocD=0.5 * cy, ocR=cy), c(float(lines[k, 5]))])
+    return P
+
