@@ -1,0 +1,75 @@
+#!/usr/bin/env python
+"""A sweep over the length of the shared line of a two-unit VolturnUS-S farm (include/raftx_array_mooring.h):
+
+    python examples/shared_mooring_farm.py [n_lengths] [L_min] [L_max]
+
+Two units 1600 m apart, each with the deck's three chains (unit 1's turned by 180 degrees), joined by one shared line between
+the facing columns.  Per candidate length, all on the device: the farm's mean pose over its 12 DOFs (raftx_array_mean_pose,
+every farm of the sweep in one launch), the coupled 12 x 12 mooring stiffness, the mean tensions and their Jacobian at that pose
+(raftx_array_mooring_lines), and the coupled response of the two units with that stiffness as the farm's coupling matrix
+(Sweep.run_farm(array_mooring=...): the units' hydrodynamics stay linearised at their reference poses).  Printed: the mean
+offsets of both units, the worst line tension as mean + 3 sigma, and the surge-surge coupling C[0,6].
+
+Runs on the committed fixtures (no reference tree needed)."""
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+from raft_amd import backend, geometry as G, mooring, statics            # noqa: E402
+from raft_amd.sweep import VariantSweep                                  # noqa: E402
+from raft_amd import snapshot as standin                                 # noqa: E402
+
+SPACING = 1600.0
+SHARED = dict(unitA=0, rA=(58.0, 0.0, -14.0), unitB=1, rB=(-58.0, 0.0, -14.0), EA=2.0e8, w=300.0)
+
+
+def main():
+    n = int(sys.argv[1]) if len(sys.argv) > 1 else 64
+    L_min = float(sys.argv[2]) if len(sys.argv) > 2 else 1486.0
+    L_max = float(sys.argv[3]) if len(sys.argv) > 3 else 1496.0
+    fg = standin.load_fixture("geom_units.npz")
+    c3 = standin.load_fixture("c3_variants.npz")
+    base = json.loads(fg["c3_base_json"])
+    moor = json.loads(str(np.load(os.path.join(standin.GOLDEN_DIR, "refgold_mooring.npz"))["VolturnUS-S/design"]))
+    u0 = [u for u in fg["units"] if u["name"] == "C3-variant-0"][0]
+    M_rna = np.asarray(u0["M_struc"]) - np.asarray(u0["M_struc_bare"])             # rotor-nacelle assembly: not geometry
+    C_rna = np.asarray(u0["C_struc"]) - np.asarray(u0["C_struc_bare"])
+    W_rna = np.asarray(u0["W_struc"]) - np.asarray(u0["W_struc_bare"])
+    depth = float(c3["depth"])
+    nD = 2 * n                                                           # the units of farm g are designs 2 g and 2 g + 1
+    params = G.volturnus_params(np.ones((nD, 5)))
+    rep = lambda a: np.repeat(a[None], nD, axis=0)
+    sweep = VariantSweep(G.volturnus_program(base), params, rep(M_rna), np.zeros((nD, 6, 6)), np.zeros((nD, 6, 6)), c3["w"], c3["k"],
+                         depth, np.asarray(c3["zeta"])[None], np.asarray(c3["beta"])[None], int(c3["nIter"]), float(c3["XiStart"]),
+                         add_mask=G.ADD_MORISON | G.ADD_HYDROSTATIC | G.ADD_INERTIA | G.TRIM_BALLAST)
+    ctx = backend.default_context(0)
+    sweep.upload(ctx)
+    K_hs, F0, _ = statics.hydrostatics(ctx, C_extra=C_rna, F_extra=W_rna)
+    deck, _ = mooring.lines_from_design(moor)
+    loc = [(0.0, 0.0), (SPACING, 0.0)]
+    lengths = np.linspace(L_min, L_max, n)
+    lines = np.ascontiguousarray([mooring.array_lines([deck, deck], loc, [0.0, 180.0], [dict(SHARED, L=float(L))]) for L in lengths])
+    t0 = time.perf_counter()
+    res = statics.array_mean_pose(ctx, K_hs.reshape(n, 2, 6, 6), F0.reshape(n, 2, 6), lines, loc, depth)
+    t_pose, k_pose = time.perf_counter() - t0, ctx.last_kernel_ms()
+    ok = res.ok
+    print("%d farms: mean pose in %.2f ms (kernel %.3f ms), %d..%d Newton steps, %d flagged"
+          % (n, 1e3 * t_pose, k_pose, res.iterations[ok].min() if ok.any() else 0, res.iterations[ok].max() if ok.any() else 0, (~ok).sum()))
+    for g in np.flatnonzero(~ok)[:5]:
+        print("   L = %.1f m: %s" % (lengths[g], ", ".join(res.describe_flags(g))))
+    pose = np.where(ok[:, None, None], res.pose, np.array([[x, y, 0, 0, 0, 0] for x, y in loc])[None])
+    out = sweep.run_farm(ctx, 2, array_mooring=dict(lines=lines, pose=np.ascontiguousarray(pose), depth=depth))
+    worst = (out["T_mean"][:, None, :] + 3.0 * out["T_std"]).max(axis=(1, 2))
+    print("   L [m]   unit 0 surge  unit 1 surge   worst T (mean + 3 sigma) [N]   C[0,6] [N/m]")
+    for g in np.flatnonzero(ok)[:: max(1, int(ok.sum()) // 8)]:
+        print("%8.1f %12.2f %13.2f %22.4g %21.4g" % (lengths[g], res.pose[g, 0, 0], res.pose[g, 1, 0] - SPACING, worst[g], out["C_moor"][g, 0, 6]))
+
+
+if __name__ == "__main__":
+    main()

@@ -61,7 +61,8 @@
  * seabed; NO_CONVERGENCE when the junction iteration reaches its cap or finds no admissible start.
  * Every entry point that takes line records takes bridles: raftx_mooring_lines, raftx_mooring_program, raftx_mean_pose
  * (include/raftx_statics.h), raftx_sweep_mooring and raftx_sweep_mean_pose.
- * Still refused: lines with both ends on the vessel, shared anchors, junctions joined to junctions, seabed friction, the fully
+ * Still refused: lines with both ends on ONE vessel (a line from one unit of an array to another is a shared row of
+ * include/raftx_array_mooring.h), shared anchors, junctions joined to junctions, seabed friction, the fully
  * slack profile, seabed contact of any segment but the anchor-side one.
  */
 #ifndef RAFTX_MOORING_H

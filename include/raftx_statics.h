@@ -19,8 +19,8 @@
  * crossing at the solved pose, per design and on the device (the reference's order: solveStatics, setPosition,
  * solveDynamics at the offset).
  *
- * Not covered: staticsMod / forcingMod 1 (hydrostatics and loads re-evaluated at the pose), arrays with shared lines,
- * flexible units; in a crossing also the design's own current load as F_env (its strip tables do not exist before the
+ * Not covered: staticsMod / forcingMod 1 (hydrostatics and loads re-evaluated at the pose), flexible units (arrays with shared
+ * lines have an entry of their own: raftx_array_mean_pose, include/raftx_array_mooring.h); in a crossing also the design's own current load as F_env (its strip tables do not exist before the
  * solve) and second-order tables at the solved pose.
  */
 #ifndef RAFTX_STATICS_H

@@ -58,6 +58,9 @@ MOOR_MAX_SEG = 4   # rows of one composite line, at most (RAFTX_MOOR_MAX_SEG)
 ML_LEG, MOOR_MAX_LEG = 14, 3   # leg rows of a bridle: the mark and how many at most (RAFTX_ML_LEG, RAFTX_MOOR_MAX_LEG)
 # include/raftx_statics.h: the mean equilibrium pose, the device library only
 STATICS_EXPORTS = ("raftx_mean_pose", "raftx_sweep_mean_pose")
+# include/raftx_array_mooring.h: arrays of units with shared lines, the device library only
+ARRAY_MOORING_EXPORTS = ("raftx_array_mooring_lines", "raftx_array_mean_pose")
+ML_UNIT_B, ML_UNIT_A, ARRAY_MAX_UNIT = 11, 12, 6   # RAFTX_ML_UNIT_B, RAFTX_ML_UNIT_A, RAFTX_ARRAY_MAX_UNIT
 MOOR_BAD_LINE, MOOR_VERTICAL, MOOR_SLACK, MOOR_NO_CONVERGENCE = 1, 2, 4, 8
 MOOR_GROUNDED = 64
 QKG_N = 8          # doubles per row of the Kim & Yue geometry stream (RAFTX_QKG_N)
@@ -180,6 +183,13 @@ class RaftxLib:
             L.raftx_mean_pose.restype = C.c_int
             L.raftx_sweep_mean_pose.argtypes = [_vp, C.c_int, C.c_int, _vp, C.c_int, _vp, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp]
             L.raftx_sweep_mean_pose.restype = C.c_int
+        self.has_array_mooring = all(hasattr(L, s) for s in ARRAY_MOORING_EXPORTS)
+        if self.has_array_mooring:
+            L.raftx_array_mooring_lines.argtypes = [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_double, _vp, _vp, _vp, _vp, _vp, _vp]
+            L.raftx_array_mooring_lines.restype = C.c_int
+            L.raftx_array_mean_pose.argtypes = [_vp, C.c_int, C.c_int, C.c_int, _vp, C.c_double, _vp, _vp, _vp, _vp, _vp, C.c_int,
+                                                _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]
+            L.raftx_array_mean_pose.restype = C.c_int
         self.has_current = all(hasattr(L, s) for s in CURRENT_EXPORTS)
         if self.has_current:
             L.raftx_current_loads.argtypes = [_vp, C.c_int, _vp, _vp, _vp, C.c_double, C.c_double, _vp]
@@ -821,6 +831,70 @@ class Context:
                                       _ptr(x_ref), _ptr(tol), int(max_iter), _ptr(out["pose"]), _ptr(out["C"]), _ptr(out["F"]),
                                       _ptr(out["T"]), _ptr(out["J"]), _ptr(out["F_res"]), _ptr(out["iterations"]), _ptr(out["flags"])),
                     "raftx_mean_pose")
+        return {k: v for k, v in out.items() if v is not None}
+
+    # ------------------------------------------------------------- arrays with shared lines (include/raftx_array_mooring.h)
+    def _array_lib(self, what):
+        if not self.rlib.has_array_mooring:
+            raise RaftxError("%s: %s does not implement include/raftx_array_mooring.h (the device library does)" % (what, self.rlib.path))
+        return self.rlib.lib
+
+    @staticmethod
+    def _array_lines(lines):
+        lines = _f64(lines)
+        if lines.ndim != 3 or lines.shape[2] != ML_N:
+            raise ValueError("lines has shape %s, expected [nArray,nLine,%d]" % (lines.shape, ML_N))
+        return lines
+
+    def array_mooring_lines(self, lines, pose, depth, want=("C", "F", "T", "J", "line_out")):
+        """The mooring system of every array at its units' poses (raftx_array_mooring_lines): ``lines`` [nA,nLine,16] array
+        rows (raft_amd.mooring.array_lines), ``pose`` [nA,nUnit,6] global.  Returns a dict with C [nA,6 nUnit,6 nUnit] (the
+        layout of Cc of solve_system), F [nA,6 nUnit], T [nA,2 nLine], J [nA,2 nLine,6 nUnit], line_out [nA,nLine,8] -- those
+        named in ``want`` -- and flags [nA] (int32; a flagged array's outputs are NaN)."""
+        L = self._array_lib("array_mooring_lines")
+        lines = self._array_lines(lines)
+        nA, nL = lines.shape[:2]
+        pose = _f64(pose)
+        if pose.ndim != 3 or pose.shape[0] != nA or pose.shape[2] != 6:
+            raise ValueError("pose has shape %s, expected [%d,nUnit,6]" % (pose.shape, nA))
+        nU = pose.shape[1]
+        n = 6 * nU
+        shapes = dict(C=(nA, n, n), F=(nA, n), T=(nA, 2 * nL), J=(nA, 2 * nL, n), line_out=(nA, nL, 8))
+        out = {k: (np.empty(shapes[k]) if k in want else None) for k in shapes}
+        out["flags"] = np.zeros(nA, dtype=np.int32)
+        self._check(L.raftx_array_mooring_lines(self._h, nA, nU, nL, _ptr(lines), _ptr(pose), float(depth), _ptr(out["C"]),
+                                                _ptr(out["F"]), _ptr(out["T"]), _ptr(out["J"]), _ptr(out["line_out"]),
+                                                _ptr(out["flags"])), "raftx_array_mooring_lines")
+        return {k: v for k, v in out.items() if v is not None}
+
+    def array_mean_pose(self, K_hs, F0, x_ref, depth, lines, F_env=None, tol=None, max_iter=0,
+                        want=("pose", "C", "F", "T", "J", "F_res", "iterations")):
+        """The mean pose of every array (raftx_array_mean_pose): Newton over all 6 nUnit DOFs in one launch.  ``K_hs``
+        [nA,nUnit,6,6], ``F0`` [nA,nUnit,6], ``x_ref`` [nA,nUnit,6] (the units' locations: the start and the origin of the
+        hydrostatic reaction), ``lines`` [nA,nLine,16] array rows, ``F_env`` [nA,nUnit,6] or None.  Returns a dict with pose
+        [nA,nUnit,6], C, F, T, J as ``array_mooring_lines``, F_res [nA,6 nUnit], iterations [nA] -- those named in ``want`` --
+        and flags [nA]."""
+        L = self._array_lib("array_mean_pose")
+        K_hs = _f64(K_hs)
+        if K_hs.ndim != 4 or K_hs.shape[2:] != (6, 6):
+            raise ValueError("K_hs has shape %s, expected [nArray,nUnit,6,6]" % (K_hs.shape,))
+        nA, nU = K_hs.shape[:2]
+        n = 6 * nU
+        F0, x_ref = _f64(F0, (nA, nU, 6), "F0"), _f64(x_ref, (nA, nU, 6), "x_ref")
+        F_env = None if F_env is None else _f64(F_env, (nA, nU, 6), "F_env")
+        lines = self._array_lines(lines)
+        if lines.shape[0] != nA:
+            raise ValueError("lines has shape %s, expected [%d,nLine,%d]" % (lines.shape, nA, ML_N))
+        nL = lines.shape[1]
+        tol = None if tol is None else _f64(tol, (2,), "tol")
+        shapes = dict(pose=(nA, nU, 6), C=(nA, n, n), F=(nA, n), T=(nA, 2 * nL), J=(nA, 2 * nL, n), F_res=(nA, n))
+        out = {k: (np.empty(shapes[k]) if k in want else None) for k in shapes}
+        out["iterations"] = np.zeros(nA, dtype=np.int32) if "iterations" in want else None
+        out["flags"] = np.zeros(nA, dtype=np.int32)
+        self._check(L.raftx_array_mean_pose(self._h, nA, nU, nL, _ptr(lines), float(depth), _ptr(K_hs), _ptr(F0), _ptr(F_env),
+                                            _ptr(x_ref), _ptr(tol), int(max_iter), _ptr(out["pose"]), _ptr(out["C"]), _ptr(out["F"]),
+                                            _ptr(out["T"]), _ptr(out["J"]), _ptr(out["F_res"]), _ptr(out["iterations"]),
+                                            _ptr(out["flags"])), "raftx_array_mean_pose")
         return {k: v for k, v in out.items() if v is not None}
 
     def sweep_mean_pose(self, handle, lines=None, C_extra=None, F_extra=None, F_env=None, tol=None, max_iter=0):

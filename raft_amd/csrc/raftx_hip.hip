@@ -48,6 +48,7 @@
 #include "../../include/raftx_qtfgen.h"
 #include "../../include/raftx_mooring.h"
 #include "../../include/raftx_statics.h"
+#include "../../include/raftx_array_mooring.h"
 #include "../../include/raftx_launch.h"
 
 // roctx ranges around the phases of the host side: named spans for `rocprofv3 --marker-trace`.
@@ -94,6 +95,7 @@ struct RangeScope {
 #include "raftx_qtfgen.h"
 #include "raftx_mooring.h"
 #include "raftx_statics.h"
+#include "raftx_array_mooring.h"
 
 // Coupled array solve (raft_model.py:1164-1236): Xi = Z_sys^-1 F for every (system, bin).  One wavefront per
 // (system, bin), NBIN (1, 2 or 4: what fits LDS) consecutive bins per workgroup so that the loads of one matrix entry
@@ -4687,6 +4689,135 @@ extern "C" int raftx_mean_pose(raftx_ctx *c, int nDesign, int nLine, const doubl
     if (sc.begin()) return -2;
     if (int rc = expand_lines(c, c->stream, n, nLine, L)) return rc;   // (inside the timed window, as raftx_mooring_expand)
     launch_mean_pose(c->stream, A, nDesign, nLine, depth, tolT, tolR, max_iter);
+    return sc.finish();
+}
+
+// ---- arrays of units with shared lines (include/raftx_array_mooring.h, raftx_array_mooring.h)
+// The records of an entry point `who`: the record errors of check_lines, then the unit fields of every row.  A value that is
+// not an integer (a NaN too) is refused here, so the kernels may index with it.
+static int check_array_lines(raftx_ctx *c, const char *who, size_t nArray, int nUnit, int nLine, const double *lines, int *chains) {
+    if (nUnit < 1 || nUnit > RAFTX_ARRAY_MAX_UNIT) FAIL(c, "%s: nUnit must be 1 to %d (got %d)", who, RAFTX_ARRAY_MAX_UNIT, nUnit);
+    if (int rc = check_lines(c, who, nArray, nLine, lines, chains)) return rc;
+    for (size_t a = 0; a < nArray; a++) {
+        const double *row = lines + a * (size_t)nLine * RAFTX_ML_N;
+        double headB = 0.0;
+        bool headShared = false;
+        for (int l = 0; l < nLine; l++, row += RAFTX_ML_N) {
+            const double ub = row[RAFTX_ML_UNIT_B], ua = row[RAFTX_ML_UNIT_A];
+            if (!(ub == std::floor(ub)) || !(ub >= 0.0) || !(ub < (double)nUnit))
+                FAIL(c, "%s: row %d of array %zu has unit B = %g: an integer 0 to %d is required", who, l, a, ub, nUnit - 1);
+            if (!(ua == std::floor(ua)) || !(ua >= 0.0) || !(ua <= (double)nUnit))
+                FAIL(c, "%s: row %d of array %zu has unit A = %g: 0 (an anchor) or 1 + a unit index, at most %d, is required", who, l, a, ua, nUnit);
+            if (row[RAFTX_ML_CONT] != 0.0 || row[RAFTX_ML_LEG] != 0.0) {
+                if (headShared)
+                    FAIL(c, "%s: row %d of array %zu continues a shared row: a shared row is one suspended line without a continuation or leg row", who, l, a);
+                if (ua != 0.0 || ub != headB)
+                    FAIL(c, "%s: row %d of array %zu is a continuation or leg row with unit fields (%g, %g): it inherits its head row's unit %g (and 0)",
+                         who, l, a, ub, ua, headB);
+                continue;
+            }
+            headB = ub;
+            headShared = ua != 0.0;
+            if (!headShared) continue;
+            if (ua - 1.0 == ub) FAIL(c, "%s: shared row %d of array %zu has both ends on unit %g: unit A and unit B must differ", who, l, a, ub);
+            if (row[RAFTX_ML_WJOINT] != 0.0 || row[13] != 0.0 || !(row[9] == 0.0))
+                FAIL(c, "%s: shared row %d of array %zu has a joint weight, CB or field 13 set: a shared row is one plain suspended line", who, l, a);
+        }
+    }
+    return 0;
+}
+static void launch_array_moor(hipStream_t st, const ArrayMoorArgs &A) {
+    const dim3 gl(moor_grid((long long)A.nArray * A.nLine)), gd(moor_grid((long long)A.nArray * A.nUnit * A.nUnit));
+    if (A.chains == 2) hipLaunchKernelGGL((k_array_moor_line<true, true>), gl, dim3(MOOR_THREADS), 0, st, A);
+    else if (A.chains) hipLaunchKernelGGL((k_array_moor_line<true, false>), gl, dim3(MOOR_THREADS), 0, st, A);
+    else hipLaunchKernelGGL((k_array_moor_line<false, false>), gl, dim3(MOOR_THREADS), 0, st, A);
+    if (A.chains == 2) hipLaunchKernelGGL(k_array_moor_design<true>, gd, dim3(MOOR_THREADS), 0, st, A);
+    else hipLaunchKernelGGL(k_array_moor_design<false>, gd, dim3(MOOR_THREADS), 0, st, A);
+}
+
+extern "C" int raftx_array_mooring_lines(raftx_ctx *c, int nArray, int nUnit, int nLine, const double *lines, const double *pose,
+                                         double depth, double *C, double *F, double *T, double *J, double *line_out, int32_t *flags) {
+    if (!c) return -1;
+    if (nLine < 1) FAIL(c, "array_mooring_lines: nLine must be positive (got %d)", nLine);
+    if (nArray < 0) FAIL(c, "array_mooring_lines: nArray must not be negative (got %d)", nArray);
+    if (!lines || !pose || !flags) FAIL(c, "array_mooring_lines: bad arguments (lines, pose and flags are required)");
+    if (int rc = check_depth(c, "array_mooring_lines", depth)) return rc;
+    int chains = 0;
+    if (int rc = check_array_lines(c, "array_mooring_lines", (size_t)nArray, nUnit, nLine, lines, &chains)) return rc;
+    if (nArray == 0) return 0;
+    HIPCHK(c, hipSetDevice(c->device));
+    Scratch sc(c);
+    const size_t na = (size_t)nArray, nl = na * nLine, n = (size_t)6 * nUnit;
+    StagedLines L;
+    if (stage_lines(c, c->stream, sc.bag, na, nLine, lines, nullptr, L)) return -2;
+    ArrayMoorArgs A;
+    memset(&A, 0, sizeof(A));
+    A.nArray = nArray; A.nUnit = nUnit; A.nLine = nLine; A.depth = depth;
+    A.lines = L.lines;
+    A.pose = sc.in<double>(pose, na * n);
+    A.lw = sc.tmp<double>(nl * MOOR_LW_N);
+    A.sw = sc.tmp<double>(nl * ARR_SW_N);
+    if (chains == 2) A.bw = sc.tmp<double>(nl * MOOR_BW_N);
+    A.C = sc.out<double>(C, na * n * n);
+    A.F = sc.out<double>(F, na * n);
+    A.T = sc.out<double>(T, nl * 2);
+    A.J = sc.out<double>(J, nl * 2 * n);
+    A.line_out = sc.out<double>(line_out, nl * MOOR_LO_N);
+    A.flags = sc.out<int>(flags, na);
+    if (int rc = sc.upload("array_mooring_lines")) return rc;
+    if (sc.begin()) return -2;
+    A.chains = chains;
+    launch_array_moor(c->stream, A);
+    return sc.finish();
+}
+
+extern "C" int raftx_array_mean_pose(raftx_ctx *c, int nArray, int nUnit, int nLine, const double *lines, double depth,
+                                     const double *K_hs, const double *F0, const double *F_env, const double *x_ref, const double tol[2],
+                                     int max_iter, double *pose, double *C, double *F, double *T, double *J, double *F_res,
+                                     int32_t *iterations, int32_t *flags) {
+    if (!c) return -1;
+    if (nLine < 1) FAIL(c, "array_mean_pose: nLine must be positive (got %d)", nLine);
+    if (nArray < 0) FAIL(c, "array_mean_pose: nArray must not be negative (got %d)", nArray);
+    if (!lines || !K_hs || !F0 || !x_ref || !flags)
+        FAIL(c, "array_mean_pose: bad arguments (lines, K_hs, F0, x_ref and flags are required)");
+    if (int rc = check_depth(c, "array_mean_pose", depth)) return rc;
+    double tolT, tolR;
+    if (int rc = mean_pose_tol(c, "array_mean_pose", tol, &tolT, &tolR)) return rc;
+    int chains = 0;
+    if (int rc = check_array_lines(c, "array_mean_pose", (size_t)nArray, nUnit, nLine, lines, &chains)) return rc;
+    if (nArray == 0) return 0;
+    HIPCHK(c, hipSetDevice(c->device));
+    Scratch sc(c);
+    const size_t na = (size_t)nArray, nl = na * nLine, n = (size_t)6 * nUnit;
+    StagedLines L;
+    if (stage_lines(c, c->stream, sc.bag, na, nLine, lines, nullptr, L)) return -2;
+    ArrayPoseArgs A;
+    memset(&A, 0, sizeof(A));
+    A.nArray = nArray; A.nUnit = nUnit; A.nLine = nLine; A.maxIter = max_iter > 0 ? max_iter : MP_MAX_IT;
+    A.depth = depth; A.tolT = tolT; A.tolR = tolR;
+    A.lines = L.lines;
+    A.chains = chains;
+    A.K_hs = sc.in<double>(K_hs, na * nUnit * 36);
+    A.F0 = sc.in<double>(F0, na * n);
+    A.F_env = sc.in<double>(F_env, na * n);
+    A.x_ref = sc.in<double>(x_ref, na * n);
+    A.lw = sc.tmp<double>(nl * MOOR_LW_N);
+    A.sw = sc.tmp<double>(nl * ARR_SW_N);
+    if (chains == 2) A.bw = sc.tmp<double>(nl * MOOR_BW_N);
+    A.pose = sc.out<double>(pose, na * n);
+    A.C = C ? sc.out<double>(C, na * n * n) : sc.tmp<double>(na * n * n);      // the iteration itself passes C and F through memory
+    A.F = F ? sc.out<double>(F, na * n) : sc.tmp<double>(na * n);
+    A.T = sc.out<double>(T, nl * 2);
+    A.J = sc.out<double>(J, nl * 2 * n);
+    A.Fres = sc.out<double>(F_res, na * n);
+    A.iterations = sc.out<int>(iterations, na);
+    A.flags = sc.out<int>(flags, na);
+    if (int rc = sc.upload("array_mean_pose")) return rc;
+    if (sc.begin()) return -2;
+    const dim3 grid((unsigned)nArray);
+    if (chains == 2) hipLaunchKernelGGL((k_array_mean_pose<true, true>), grid, dim3(ARR_THREADS), 0, c->stream, A);
+    else if (chains) hipLaunchKernelGGL((k_array_mean_pose<true, false>), grid, dim3(ARR_THREADS), 0, c->stream, A);
+    else hipLaunchKernelGGL((k_array_mean_pose<false, false>), grid, dim3(ARR_THREADS), 0, c->stream, A);
     return sc.finish();
 }
 

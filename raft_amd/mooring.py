@@ -274,6 +274,63 @@ def bridles_from_design(design, rho=1025.0, g=9.81):
     return np.ascontiguousarray(recs), depth, names
 
 
+ML_UNIT_B, ML_UNIT_A = 11, 12  # array rows (include/raftx_array_mooring.h): the unit of end B; 0 or 1 + the unit of end A
+ARRAY_MAX_UNIT = 6
+
+
+def array_lines(unit_lines, locations, headings=None, shared=()):
+    """Array rows [nRow,16] (include/raftx_array_mooring.h) of a farm: the records of every unit -- ``unit_lines`` [nUnit] of
+    [nRow_i,16] from ``lines_from_design``, ``chains_from_design`` or ``bridles_from_design``, laid out about the origin --
+    turned about the vertical by ``headings`` [nUnit] (degrees, counter-clockwise: heading_adjust of the deck's ``array:``
+    table; anchors and fairleads turn together, the unit's pose stays unrotated as in the reference), their anchors shifted to
+    ``locations`` [nUnit,2] (x_location, y_location) and stamped with the unit; then one shared row per entry of ``shared``:
+    dicts unitA, rA, unitB, rB (unit indices and body-frame attachment points), L, EA, w.  The units' reference poses are
+    (x_location, y_location, 0, 0, 0, 0)."""
+    n_unit = len(unit_lines)
+    if not 1 <= n_unit <= ARRAY_MAX_UNIT:
+        raise ValueError("an array has 1 to %d units (got %d)" % (ARRAY_MAX_UNIT, n_unit))
+    locations = np.asarray(locations, dtype=float).reshape(n_unit, 2)
+    headings = np.zeros(n_unit) if headings is None else np.asarray(headings, dtype=float).reshape(n_unit)
+    rows = []
+    for u, recs in enumerate(unit_lines):
+        recs = np.array(recs, dtype=float).reshape(-1, ML_N)
+        if np.any(recs[:, ML_UNIT_B] != 0) or np.any(recs[:, ML_UNIT_A] != 0):
+            raise ValueError("unit %d: the records carry unit fields already (fields 11-12 must be zero)" % u)
+        c, s = np.cos(np.deg2rad(headings[u])), np.sin(np.deg2rad(headings[u]))
+        if headings[u] % 90.0 == 0.0:                            # exact quarter turns
+            c, s = np.round(c), np.round(s)
+        for lo in (ML_ANCHOR, ML_FAIRLEAD):
+            x, y = recs[:, lo].copy(), recs[:, lo + 1].copy()
+            recs[:, lo], recs[:, lo + 1] = c * x - s * y, s * x + c * y
+        head = (recs[:, ML_CONT] == 0) & (recs[:, ML_LEG] == 0)
+        recs[head, ML_ANCHOR] += locations[u, 0]
+        recs[head, ML_ANCHOR + 1] += locations[u, 1]
+        recs[:, ML_UNIT_B] = u
+        rows.append(recs)
+    for k, sh in enumerate(shared):
+        missing = [f for f in ("unitA", "rA", "unitB", "rB", "L", "EA", "w") if f not in sh]
+        if missing:
+            raise ValueError("shared line %d lacks %s" % (k, missing))
+        ua, ub = sh["unitA"], sh["unitB"]
+        for nm, v in (("unitA", ua), ("unitB", ub)):
+            if int(v) != v or not 0 <= int(v) < n_unit:
+                raise ValueError("shared line %d: %s = %r is no unit index 0 .. %d" % (k, nm, v, n_unit - 1))
+        if int(ua) == int(ub):
+            raise ValueError("shared line %d has both ends on unit %d" % (k, int(ua)))
+        L, EA, w = float(sh["L"]), float(sh["EA"]), float(sh["w"])
+        if not (L > 0 and EA > 0 and w > 0):
+            raise ValueError("shared line %d: L, EA and w must be positive (got %g, %g, %g)" % (k, L, EA, w))
+        rec = np.zeros(ML_N)
+        rec[ML_ANCHOR:ML_ANCHOR + 3] = np.asarray(sh["rA"], dtype=float).reshape(3)
+        rec[ML_FAIRLEAD:ML_FAIRLEAD + 3] = np.asarray(sh["rB"], dtype=float).reshape(3)
+        rec[ML_L], rec[ML_EA], rec[ML_W] = L, EA, w
+        rec[ML_UNIT_B], rec[ML_UNIT_A] = int(ub), int(ua) + 1
+        rows.append(rec[None])
+    if not rows or not sum(len(r) for r in rows):
+        raise ValueError("the array has no rows")
+    return np.ascontiguousarray(np.concatenate(rows))
+
+
 def tension_names(n):
     """Names of the 2 n tension channels in the order of T / J: ends A of all lines, then ends B (getTensions)."""
     return ["Tmoor_A%d" % (i + 1) for i in range(n)] + ["Tmoor_B%d" % (i + 1) for i in range(n)]

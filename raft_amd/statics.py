@@ -68,3 +68,40 @@ def mean_pose(ctx, K_hs, F0, lines=None, depth=None, program=None, params=None, 
     elif params is not None or program is not None:
         raise ValueError("mean_pose: lines and a mooring program exclude each other")
     return MeanPose(ctx.mean_pose(K_hs, F0, depth, lines=lines, params=params, F_env=F_env, x_ref=x_ref, tol=tol, max_iter=max_iter))
+
+
+class ArrayMeanPose:
+    """Result of ``array_mean_pose``: pose [nA,nUnit,6], C [nA,6 nUnit,6 nUnit] (the layout of Cc of solve_system), F
+    [nA,6 nUnit], T [nA,2 nLine], J [nA,2 nLine,6 nUnit], F_res [nA,6 nUnit], iterations [nA], flags [nA].  A flagged
+    array's rows are NaN."""
+
+    def __init__(self, res):
+        self.pose, self.C, self.F = res["pose"], res["C"], res["F"]
+        self.T, self.J, self.F_res = res["T"], res["J"], res["F_res"]
+        self.iterations, self.flags = res["iterations"], res["flags"]
+
+    @property
+    def ok(self):
+        """[nA] bool: the array converged and none of its rows was flagged."""
+        return self.flags == 0
+
+    def describe_flags(self, a):
+        names = dict(FLAG_NAMES)
+        names[mooring.FLAG_GROUNDED] = "line on or below the seabed"
+        return [name for bit, name in names.items() if int(self.flags[a]) & bit]
+
+
+def array_mean_pose(ctx, K_hs, F0, lines, locations, depth, F_env=None, tol=None, max_iter=0):
+    """Newton's iteration over the 6 nUnit DOFs of every array in one launch (include/raftx_array_mooring.h; Model.solveStatics
+    of a farm, raft_model.py:678-885, staticsMod 0 / forcingMod 0).  ``K_hs`` [nA,nUnit,6,6], ``F0`` [nA,nUnit,6], ``lines``
+    [nA,nRow,16] array rows (raft_amd.mooring.array_lines), ``locations`` [nUnit,2] or [nA,nUnit,2] (x_location, y_location) or
+    full reference poses [nA,nUnit,6], ``F_env`` [nA,nUnit,6] or None."""
+    K_hs = np.asarray(K_hs, dtype=float)
+    nA, nU = K_hs.shape[:2]
+    loc = np.asarray(locations, dtype=float)
+    if loc.shape[-1] == 2:
+        x_ref = np.zeros((nA, nU, 6))
+        x_ref[..., :2] = np.broadcast_to(loc, (nA, nU, 2))
+    else:
+        x_ref = np.broadcast_to(loc, (nA, nU, 6))
+    return ArrayMeanPose(ctx.array_mean_pose(K_hs, F0, np.ascontiguousarray(x_ref), depth, lines, F_env=F_env, tol=tol, max_iter=max_iter))

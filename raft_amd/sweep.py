@@ -199,11 +199,22 @@ class Sweep:
         r = ctx.fetch_results(want_Xi=False)
         return {"std": std, "psd": psd, "niter": r["niter"], "flags": r["flags"]}
 
-    def run_farm(self, ctx, n_unit, Cc=None, Mc=None, Bc=None):
+    def run_farm(self, ctx, n_unit, Cc=None, Mc=None, Bc=None, array_mooring=None):
         """Arrays: consecutive groups of ``n_unit`` designs are the units of one farm (raft_model.py:1164-1236).
         Two launches: the per-unit fixed points, then the coupled 6N x 6N solves fed from the resident Z / F_wave.
-        Returns Xi [nGroup,nCase,nHead,6*n_unit,nw] plus per-unit niter/flags."""
+        Returns Xi [nGroup,nCase,nHead,6*n_unit,nw] plus per-unit niter/flags.
+        ``array_mooring`` = dict(lines=[nGroup,nRow,16] array rows (raft_amd.mooring.array_lines), pose=[nGroup,n_unit,6] global,
+        depth=): the farms' own mooring systems, shared lines included, on the device (raftx_array_mooring_lines).  Their coupled
+        stiffness IS the coupling matrix of the solve -- a caller's ``Cc`` is added to it -- and the result also holds C_moor
+        [nGroup,6N,6N], T_mean [nGroup,2 nRow], T_std [nGroup,nCase,2 nRow] = the standard deviations of J Xi
+        (raft_model.py:383-386, 413-415; raftx_response_stats with nDof = 6N) and moor_flags [nGroup]: a flagged farm is NaN."""
         from ._abi import WANT_FWAVE, WANT_Z, WANT_BDRAG
+        moor = None
+        if array_mooring is not None:
+            moor = ctx.array_mooring_lines(array_mooring["lines"], array_mooring["pose"], array_mooring["depth"], want=("C", "T", "J"))
+            if moor["C"].shape[1] != 6 * n_unit:
+                raise ValueError("array_mooring has poses of %d units, the farm %d" % (moor["C"].shape[1] // 6, n_unit))
+            Cc = moor["C"] if Cc is None else np.ascontiguousarray(np.asarray(Cc, dtype=float) + moor["C"])
         self.upload(ctx)
         # units with constant M, B, C: the coupled solve assembles their 6 x 6 impedances itself from the matrices + the
         # exported B_drag, so the fixed points run as the LEAN kernel with the excitation export and no Z leaves them;
@@ -213,7 +224,18 @@ class Sweep:
         t_units = ctx.last_kernel_ms()
         Xi = ctx.solve_system_resident(n_unit, Mc, Bc, Cc)
         r = ctx.fetch_results(want_Xi=False)
-        return {"Xi": Xi, "niter": r["niter"], "flags": r["flags"], "kernel_ms": (t_units, ctx.last_kernel_ms())}
+        out = {"Xi": Xi, "niter": r["niter"], "flags": r["flags"], "kernel_ms": (t_units, ctx.last_kernel_ms())}
+        if moor is not None:
+            nG, nT = moor["T"].shape
+            dw = float(self.w[1] - self.w[0]) if self.nw > 1 else float(self.w[0])
+            T_std = np.empty((nG, Xi.shape[1], nT))
+            L = np.zeros((nT, 3, 6 * n_unit))
+            for g in range(nG):
+                L[:, 0, :] = moor["J"][g]
+                for c in range(Xi.shape[1]):
+                    T_std[g, c] = ctx.response_stats(self.w, L, Xi[g, c], dw)[0]
+            out.update(C_moor=moor["C"], T_mean=moor["T"], T_std=T_std, moor_flags=moor["flags"])
+        return out
 
     def run_second_order(self, ctx, qtf_tables, Mstruc, w2, k2, S0, rho_water=1025.0, kay=None):
         """potSecOrder == 1 for a whole batch (single wave heading): first-order fixed point, slender-body QTFs from the

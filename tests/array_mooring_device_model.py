@@ -1,0 +1,257 @@
+"""fp64 NumPy restatement of the array kernels (raft_amd/csrc/raftx_array_mooring.h): the same expressions in the same order,
+one array at a time, on the single-line records of tests/mooring_device_model.py (``line``) and a restatement of
+moor_shared_record.  It is what the gates of tests/array_mooring_reference.py are measured with on the CPU and -- through
+``seed`` -- the carrier of the deliberate errors the gates must reject (tests/test_array_mooring.py).  The kernels contract
+multiply-adds and use the device's library functions, so the model agrees with them to rounding, not to the bit.
+"""
+import numpy as np
+
+from . import mooring_device_model as dm
+
+CAPS = (30.0, 30.0, 5.0, 0.1, 0.1, 0.1)
+TOL = (1e-9, 1e-10)
+MAX_ITER = 40
+FLAG_POSE_CAP, FLAG_SINGULAR, FLAG_GROUNDED = 16, 32, 64
+SEEDS = ("no_cross", "cross_sign", "arm_wrong_unit", "va_zero")
+
+
+def shared(rec, pa, pb, depth, seed=None):
+    """(flag, dict) of one shared row: the records moor_shared_record writes."""
+    rec, pa, pb = (np.asarray(a, dtype=np.float64) for a in (rec, pa, pb))
+    L, EA, w = rec[6], rec[7], rec[8]
+    if not (np.all(np.isfinite(rec[:10])) and np.all(np.isfinite(pa)) and np.all(np.isfinite(pb))) or not (L > 0 and EA > 0 and w > 0):
+        return 1, None
+    rA, rB = dm._arm(rec[0:3], pa[3:]), dm._arm(rec[3:6], pb[3:])
+    dx, dy = (pb[0] + rB[0]) - (pa[0] + rA[0]), (pb[1] + rB[1]) - (pa[1] + rA[1])
+    XF = np.sqrt(dx * dx + dy * dy)
+    zA, zB = pa[2] + rA[2], pb[2] + rB[2]
+    ZF = zB - zA
+    if XF <= 1e-9 * L:
+        return 2, None
+    ux, uy = dx / XF, dy / XF
+    lam = 0.2 if L * L <= XF * XF + ZF * ZF else np.sqrt(3.0 * ((L * L - ZF * ZF) / (XF * XF) - 1.0))
+    H, V = abs(w * XF / (2.0 * lam)), 0.5 * w * (ZF / np.tanh(lam) + L)
+    X, Z, a11, a12, a22, _ = dm._eval(H, V, L, EA, w, False, None)
+    eX, eZ = X - XF, Z - ZF
+    res, a, it = max(abs(eX), abs(eZ)) / L, 1.0, 0
+    conv = res == 0.0
+    while not conv and it < dm.MAX_IT:
+        it += 1
+        det = a11 * a22 - a12 * a12
+        dH, dV = -(a22 * eX - a12 * eZ) / det, -(a11 * eZ - a12 * eX) / det
+        s = a
+        if H + s * dH <= 0.0:
+            s = -0.5 * H / dH
+        Ht, Vt = H + s * dH, V + s * dV
+        nx = dm._eval(Ht, Vt, L, EA, w, False, None)
+        nX, nZ = nx[0] - XF, nx[1] - ZF
+        rn = max(abs(nX), abs(nZ)) / L
+        if rn < res:
+            H, V, eX, eZ, res, a = Ht, Vt, nX, nZ, rn, 1.0
+            X, Z, a11, a12, a22, _ = nx
+            conv = res == 0.0
+        elif res <= dm.TIGHT:
+            conv = True
+        else:
+            a *= 0.5
+            if a < 2.0 ** -40:
+                break
+    if not conv:
+        return 8, None
+    VA = V - w * L
+    zlow = min(zA, zB)
+    if VA < 0.0 and V > 0.0:
+        vb = VA / H
+        sb = np.sqrt(1.0 + vb * vb)
+        zlow = zA - ((H / w) * (vb * vb / (sb + 1.0)) + VA * VA / (2.0 * EA * w))
+    if zlow < -depth - 1e-6 * depth:
+        return FLAG_GROUNDED, None
+    det = a11 * a22 - a12 * a12
+    k11, k12, k22 = a22 / det, -a12 / det, a11 / det
+    TB, TA = np.sqrt(H * H + V * V), np.sqrt(H * H + VA * VA)
+    th = H / XF
+    K = np.array([[k11 * ux * ux + th * (1.0 - ux * ux), k11 * ux * uy - th * (ux * uy), k12 * ux],
+                  [k11 * ux * uy - th * (ux * uy), k11 * uy * uy + th * (1.0 - uy * uy), k12 * uy],
+                  [k12 * ux, k12 * uy, k22]])
+    gAX, gAZ = (H * k11 + VA * k12) / TA, (H * k12 + VA * k22) / TA
+    gBX, gBZ = (H * k11 + V * k12) / TB, (H * k12 + V * k22) / TB
+    return 0, dict(f=np.array([-H * ux, -H * uy, -V]), r=rB, K=K, gA=np.array([gAX * ux, gAX * uy, gAZ]),
+                   gB=np.array([gBX * ux, gBX * uy, gBZ]), TA=TA, TB=TB, rA=rA,
+                   fA=np.array([H * ux, H * uy, 0.0 if seed == "va_zero" else VA]),
+                   lo=np.array([H, V, H, VA, 0.0, it, 0.0, 0.0]), low=zlow)
+
+
+def _cross(r, g):
+    return np.array([r[1] * g[2] - r[2] * g[1], r[2] * g[0] - r[0] * g[2], r[0] * g[1] - r[1] * g[0]])
+
+
+def moor(lines, x, depth, seed=None):
+    """(flag, C [n,n], F [n], T [2 nL], J [2 nL,n]) of one array at the poses x [nUnit,6]: the blocks of arr_block in row order."""
+    lines = np.asarray(lines, dtype=np.float64)
+    x = np.asarray(x, dtype=np.float64)
+    nL, nU = len(lines), len(x)
+    n = 6 * nU
+    recs = []
+    for l in range(nL):
+        ub, ua = int(lines[l, 11]), int(lines[l, 12]) - 1
+        recs.append(shared(lines[l], x[ua], x[ub], depth, seed) if ua >= 0 else dm.line(lines[l], x[ub], depth))
+    flag = 0
+    for fl, _ in recs:
+        flag |= fl
+    C, F, Tn, J = np.zeros((n, n)), np.zeros(n), np.zeros(2 * nL), np.zeros((2 * nL, n))
+    if flag:
+        return flag, C, F, Tn, J
+    for l, (_, q) in enumerate(recs):
+        ub, ua = int(lines[l, 11]), int(lines[l, 12]) - 1
+        ends = [(ub, q["r"], q["f"], True)]
+        if ua >= 0:
+            ends.append((ua, q["rA"], q["fA"], False))
+        for ui, ri, fi, iB in ends:
+            for uj, rj, _, jB in ends:
+                diag = iB == jB
+                if not diag and seed == "no_cross":
+                    continue
+                sg = 1.0 if (diag or seed == "cross_sign") else -1.0
+                K = sg * q["K"]
+                RI, RJ, FX = dm._skew(ri), dm._skew(rj), dm._skew(fi)
+                KR, RK = K @ RJ, RI @ K
+                bi, bj = 6 * ui, 6 * uj
+                C[bi:bi + 3, bj:bj + 3] += K
+                C[bi:bi + 3, bj + 3:bj + 6] += -KR
+                C[bi + 3:bi + 6, bj:bj + 3] += RK
+                turn = diag
+                if seed == "arm_wrong_unit" and ua >= 0:        # the arm-turning term of end A put on unit B's diagonal block, and back
+                    turn = False
+                C[bi + 3:bi + 6, bj + 3:bj + 6] += (-(RI @ KR) - FX @ RI) if turn else -(RI @ KR)
+                if seed == "arm_wrong_unit" and ua >= 0 and diag:
+                    uo, ro, fo, _ = ends[1] if iB else ends[0]
+                    C[bi + 3:bi + 6, bj + 3:bj + 6] += -(dm._skew(fo) @ dm._skew(ro))
+            F[6 * ui:6 * ui + 3] += fi
+            F[6 * ui + 3:6 * ui + 6] += _cross(ri, fi)
+            sg = 1.0 if iB else -1.0
+            for e, g in ((0, q["gA"]), (1, q["gB"])):
+                J[e * nL + l, 6 * ui:6 * ui + 3] = sg * g
+                J[e * nL + l, 6 * ui + 3:6 * ui + 6] = _cross(ri, sg * g)
+        Tn[l], Tn[nL + l] = q["TA"], q["TB"]
+    return 0, C, F, Tn, J
+
+
+def evaluate(lines, pose, depth, seed=None):
+    """dict C, F, T, J, flags of ONE array as raftx_array_mooring_lines gives them (NaN when flagged)."""
+    assert seed is None or seed in SEEDS
+    flag, C, F, Tn, J = moor(lines, pose, depth, seed)
+    if flag:
+        C, F, Tn, J = (np.full_like(a, np.nan) for a in (C, F, Tn, J))
+    return dict(C=C, F=F, T=Tn, J=J, flags=flag)
+
+
+def lu_solve(K, Y):
+    """(dX, singular): Gaussian elimination of [K | Y] with partial pivoting, the first row of the largest |a| as pivot (arr_solve)."""
+    n = len(Y)
+    A = np.concatenate([np.array(K, dtype=np.float64), np.asarray(Y, dtype=np.float64)[:, None]], axis=1)
+    sing = False
+    for k in range(n):
+        p, best = k, abs(A[k, k])
+        for i in range(k + 1, n):
+            if abs(A[i, k]) > best:
+                p, best = i, abs(A[i, k])
+        if p != k:
+            A[[k, p]] = A[[p, k]]
+        if not (best > 0.0) or not np.isfinite(best):
+            sing = True
+        with np.errstate(all="ignore"):
+            for i in range(k + 1, n):
+                m = A[i, k] / A[k, k]
+                A[i, k + 1:] = A[i, k + 1:] - m * A[k, k + 1:]
+    x = np.zeros(n)
+    with np.errstate(all="ignore"):
+        for i in range(n - 1, -1, -1):
+            s = A[i, n]
+            for j in range(i + 1, n):
+                s = s - A[i, j] * x[j]
+            x[i] = s / A[i, i]
+    return x, sing or not np.all(np.isfinite(x))
+
+
+def step(K, Y, log=None):
+    """(dX, singular) of one iteration over the whole 6 nUnit vector: the repaired diagonal, the solve, the diagonal growth
+    while dX.Y < 0, ONE scale factor against the caps repeated per unit."""
+    K = np.array(K, dtype=np.float64)
+    n = len(Y)
+    kmean = 0.0
+    for i in range(n):
+        kmean = kmean + K[i, i]
+    kmean = kmean / float(n)
+    for i in range(n):
+        if K[i, i] == 0.0:
+            K[i, i] = kmean
+            if log is not None:
+                log.append(("zero_diagonal", i))
+    dX, sing = lu_solve(K, Y)
+    for _ in range(10):
+        dot = 0.0
+        for i in range(n):
+            dot = dot + dX[i] * Y[i]
+        if sing or not (dot < 0.0):
+            break
+        for i in range(n):
+            K[i, i] = K[i, i] + 0.1 * abs(K[i, i])
+        if log is not None:
+            log.append(("enlarged", None))
+        dX, sing = lu_solve(K, Y)
+    if sing:
+        return dX, True
+    s = 1.0
+    for i in range(n):
+        if abs(dX[i]) * s > CAPS[i % 6]:
+            s = CAPS[i % 6] / abs(dX[i])
+    if s < 1.0 and log is not None:
+        log.append(("capped", s))
+    return dX * s, False
+
+
+def solve(lines, depth, K_hs, F0, F_env, x_ref, tol=None, max_iter=0, seed=None, log=None):
+    """dict pose [nUnit,6], C, F, T, J, F_res [n], iterations, flags as raftx_array_mean_pose gives them for ONE array."""
+    assert seed is None or seed in SEEDS
+    lines = np.asarray(lines, dtype=np.float64)
+    K_hs = np.asarray(K_hs, dtype=np.float64)
+    nU, nL = len(K_hs), len(lines)
+    n = 6 * nU
+    F0 = np.asarray(F0, dtype=np.float64).reshape(n)
+    F_env = np.zeros(n) if F_env is None else np.asarray(F_env, dtype=np.float64).reshape(n)
+    xr = np.asarray(x_ref, dtype=np.float64).reshape(n)
+    tol = TOL if tol is None else tol
+    max_iter = MAX_ITER if max_iter <= 0 else max_iter
+    x, it, flag, final = xr.copy(), 0, 0, False
+    nan = dict(pose=np.full((nU, 6), np.nan), C=np.full((n, n), np.nan), F=np.full(n, np.nan), T=np.full(2 * nL, np.nan),
+               J=np.full((2 * nL, n), np.nan), F_res=np.full(n, np.nan))
+    while True:
+        fl, C, Fm, Tn, J = moor(lines, x.reshape(nU, 6), depth, seed)
+        if fl:
+            flag |= fl
+            break
+        Y = np.zeros(n)
+        for r in range(n):
+            u, acc = r // 6, 0.0
+            for j in range(6):
+                acc = acc + K_hs[u, r % 6, j] * (x[6 * u + j] - xr[6 * u + j])
+            Y[r] = ((F0[r] + F_env[r]) - acc) + Fm[r]
+        if final:
+            return dict(pose=x.reshape(nU, 6), C=C, F=Fm, T=Tn, J=J, F_res=Y, iterations=it, flags=0)
+        K = C.copy()
+        for u in range(nU):
+            K[6 * u:6 * u + 6, 6 * u:6 * u + 6] = K_hs[u] + C[6 * u:6 * u + 6, 6 * u:6 * u + 6]
+        dX, sing = step(K, Y, log)
+        if sing:
+            flag |= FLAG_SINGULAR
+            break
+        conv = all(abs(dX[i]) <= tol[0 if i % 6 < 3 else 1] for i in range(n))
+        x = x + dX
+        it += 1
+        if conv:
+            final = True
+        elif it >= max_iter:
+            flag |= FLAG_POSE_CAP
+            break
+    nan.update(iterations=it, flags=flag)
+    return nan
