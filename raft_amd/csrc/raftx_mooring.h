@@ -25,6 +25,12 @@
 // (force, arm, 3 x 3 stiffness at the fairlead, the gradients of both end tensions); k_moor_design, one lane per design,
 // adds the lines' shares of C_moor / F_moor in line order and writes T and J.  No atomics, no LDS: a design's bits
 // depend on its own lines and pose only -- not on the batch or the grid.
+//
+// Shared steps: moor_chain_load / moor_chain_grounded (a chain, a bridle's stem), moor_end_set / moor_end_grad / moor_lo_write (a
+// chain, a stem, a leg), moor_design_walk (k_moor_design, k_mean_pose).  NOT shared, on purpose: the Newton loops of the single row
+// and of the chain stay beside moor_shoot, and the single row keeps its own record writer -- through the helpers the compiler fuses
+// the other product of K3's k11 u u + th (1 - u u) and C_moor moves in the last bit (profiles/mooring_one_solve_ab.txt) --, and the
+// shared rows of an array (raftx_array_mooring.h) keep their copy under a lexical `fp contract(off)` that a helper here would escape.
 #pragma once
 
 #define MOOR_THREADS 256
@@ -122,179 +128,7 @@ __device__ __forceinline__ void moor_chain_eval(const double H, const double V, 
     }
 }
 
-// A chain at the pose ps: the head row `line` and the nc continuation rows after it.  The records lw of all its rows and, where
-// lo_out is not null and the chain is not flagged, their line_out rows.  NOT inlined, and every argument a scalar or a pointer
-// to global memory: k_moor_line and k_mean_pose call one body, so the records of a chain are the same bits from both (for a
-// single line the two kernels' inlined copies of one source have always agreed; nothing promises that of a second, larger body).
-struct MoorPose { double v[6]; };
-__device__ __noinline__ void moor_chain_record(const double *__restrict__ line, const int nc, const MoorPose pose, const double depth,
-                                               double *__restrict__ lw, double *__restrict__ lo_out) {
-    double rec[RAFTX_ML_N], ps[6];
-#pragma unroll
-    for (int i = 0; i < RAFTX_ML_N; i++) rec[i] = line[i];
-#pragma unroll
-    for (int i = 0; i < 6; i++) ps[i] = pose.v[i];
-    MoorChain c;
-    c.n = nc + 1;
-    c.L[0] = rec[6]; c.EA[0] = rec[7]; c.w[0] = rec[8]; c.Wj[0] = 0.0;
-    bool fin = true;
-    for (int i = 0; i < 10; i++) fin = fin && isfinite(rec[i]);
-    for (int i = 0; i < 6; i++) fin = fin && isfinite(ps[i]);
-    bool pos = c.L[0] > 0.0 && c.EA[0] > 0.0 && c.w[0] > 0.0;
-    double Lt = c.L[0], Wt = c.w[0] * c.L[0];
-#pragma unroll
-    for (int i = 1; i < RAFTX_MOOR_MAX_SEG; i++) {
-        c.L[i] = 1.0; c.EA[i] = 1.0; c.w[i] = 1.0; c.Wj[i] = 0.0;
-        if (i >= c.n) continue;
-        const double *p = line + (size_t)i * RAFTX_ML_N;
-        c.L[i] = p[6]; c.EA[i] = p[7]; c.w[i] = p[8]; c.Wj[i] = p[RAFTX_ML_WJOINT];
-        fin = fin && isfinite(c.L[i]) && isfinite(c.EA[i]) && isfinite(c.w[i]) && isfinite(p[9]) && isfinite(c.Wj[i]);
-        pos = pos && c.L[i] > 0.0 && c.EA[i] > 0.0 && c.w[i] > 0.0;
-        Lt += c.L[i];
-        Wt += c.w[i] * c.L[i] + c.Wj[i];
-    }
-    const double az = rec[2];
-    int flag = 0;
-    double r[3] = {0, 0, 0}, XF = 0.0, ZF = 0.0, ux = 0.0, uy = 0.0;
-    if (!fin || !pos || !(Wt > 0.0) || az < -depth - 1e-6 * depth) flag = RAFTX_MOOR_BAD_LINE;
-    if (!flag) {
-        moor_arm(rec, ps, r);
-        const double dx = (ps[0] + r[0]) - rec[0], dy = (ps[1] + r[1]) - rec[1];
-        XF = sqrt(dx * dx + dy * dy);
-        ZF = (ps[2] + r[2]) - az;
-        ux = dx / XF;
-        uy = dy / XF;
-        if (!(ZF > 0.0)) flag = RAFTX_MOOR_BAD_LINE;
-        else if (XF <= 1e-9 * Lt) flag = RAFTX_MOOR_VERTICAL;
-        else if (Lt >= XF + ZF) flag = RAFTX_MOOR_SLACK;
-    }
-    double H = 0.0, V = 0.0, Vtop[RAFTX_MOOR_MAX_SEG] = {0, 0, 0, 0};
-    MoorEval e;
-    int it = 0;
-    if (!flag) {
-        const bool seabed = fabs(az + depth) <= 1e-6 * depth;
-        const double we = Wt / Lt;                                // the effective weight per length of the guess
-        const double lam = (Lt * Lt <= XF * XF + ZF * ZF) ? 0.2 : sqrt(3.0 * ((Lt * Lt - ZF * ZF) / (XF * XF) - 1.0));
-        H = fabs(we * XF / (2.0 * lam));
-        V = 0.5 * we * (ZF / tanh(lam) + Lt);
-        moor_chain_eval(H, V, c, seabed, e, Vtop);
-        double eX = e.X - XF, eZ = e.Z - ZF, res = fmax(fabs(eX), fabs(eZ)) / Lt, a = 1.0;
-        bool conv = res == 0.0;
-        while (!conv && it < MOOR_MAX_IT) {
-            it++;
-            const double det = e.a11 * e.a22 - e.a12 * e.a12;
-            const double dH = -(e.a22 * eX - e.a12 * eZ) / det, dV = -(e.a11 * eZ - e.a12 * eX) / det;
-            double s = a;
-            if (H + s * dH <= 0.0) s = -0.5 * H / dH;
-            const double Ht = H + s * dH, Vt = V + s * dV;
-            MoorEval n;
-            double Vn[RAFTX_MOOR_MAX_SEG] = {0, 0, 0, 0};
-            moor_chain_eval(Ht, Vt, c, seabed, n, Vn);
-            const double nX = n.X - XF, nZ = n.Z - ZF, rn = fmax(fabs(nX), fabs(nZ)) / Lt;
-            if (rn < res) {
-                H = Ht; V = Vt; e = n; eX = nX; eZ = nZ; res = rn; a = 1.0;
-#pragma unroll
-                for (int i = 0; i < RAFTX_MOOR_MAX_SEG; i++) Vtop[i] = Vn[i];
-                conv = res == 0.0;
-            } else if (res <= MOOR_TIGHT) {
-                conv = true;
-            } else {
-                a *= 0.5;
-                if (a < 0x1p-40) break;
-            }
-        }
-        if (!conv) flag = RAFTX_MOOR_NO_CONVERGENCE;
-        else if (seabed && Vtop[0] <= 0.0) flag = RAFTX_MOOR_GROUNDED;      // the anchor-side segment rests wholly: so would its upper joint
-        else {
-            // the joints and the sags (where V changes sign inside a segment) against the seabed, from the anchor up
-            const double floor = -depth - 1e-6 * depth;
-            double z = az;
-#pragma unroll
-            for (int i = 0; i < RAFTX_MOOR_MAX_SEG; i++) {
-                if (i >= c.n) continue;
-                const double Vb = Vtop[i] - c.w[i] * c.L[i];
-                if (!(i == 0 && e.contact) && Vb < 0.0 && Vtop[i] > 0.0) {
-                    const double vb = Vb / H, sb = sqrt(1.0 + vb * vb);
-                    const double drop = (H / c.w[i]) * (vb * vb / (sb + 1.0)) + Vb * Vb / (2.0 * c.EA[i] * c.w[i]);
-                    if (z - drop < floor) flag = RAFTX_MOOR_GROUNDED;
-                }
-                MoorEval s;
-                moor_eval(H, Vtop[i], c.L[i], c.EA[i], c.w[i], seabed && i == 0, s);
-                z += s.Z;
-                if (i + 1 < c.n && z < floor) flag = RAFTX_MOOR_GROUNDED;
-            }
-        }
-    }
-    if (!flag) {
-        const double det = e.a11 * e.a22 - e.a12 * e.a12;
-        const double k11 = e.a22 / det, k12 = -e.a12 / det, k22 = e.a11 / det;
-        const double th = H / XF;
-#pragma unroll
-        for (int i = 0; i < RAFTX_MOOR_MAX_SEG; i++) {
-            if (i >= c.n) continue;
-            double *q = lw + (size_t)i * MOOR_LW_N;
-            const bool ct = i == 0 && e.contact;
-            const double VB = Vtop[i], VA = ct ? 0.0 : VB - c.w[i] * c.L[i];
-            const double TB = sqrt(H * H + VB * VB), TA = sqrt(H * H + VA * VA);
-            if (i == 0) {
-                q[0] = -H * ux; q[1] = -H * uy; q[2] = -V;
-                q[6] = k11 * ux * ux + th * (1.0 - ux * ux);
-                q[7] = k11 * ux * uy - th * (ux * uy);
-                q[8] = k12 * ux;
-                q[9] = q[7];
-                q[10] = k11 * uy * uy + th * (1.0 - uy * uy);
-                q[11] = k12 * uy;
-                q[12] = q[8];
-                q[13] = q[11];
-                q[14] = k22;
-            } else {
-                q[0] = 0.0; q[1] = 0.0; q[2] = 0.0;
-                for (int k = 6; k < 15; k++) q[k] = 0.0;
-            }
-            q[3] = r[0]; q[4] = r[1]; q[5] = r[2];
-            const double gAX = (H * k11 + VA * k12) / TA, gAZ = (H * k12 + VA * k22) / TA;
-            const double gBX = (H * k11 + VB * k12) / TB, gBZ = (H * k12 + VB * k22) / TB;
-            q[15] = gAX * ux; q[16] = gAX * uy; q[17] = gAZ;
-            q[18] = gBX * ux; q[19] = gBX * uy; q[20] = gBZ;
-            q[21] = TA;
-            q[22] = TB;
-            double *o = lo_out ? lo_out + (size_t)i * MOOR_LO_N : nullptr;
-            if (o) {
-                o[0] = H; o[1] = VB; o[2] = H; o[3] = VA;
-                o[4] = ct ? c.L[0] - VB / c.w[0] : 0.0;
-                o[5] = (double)it;
-                o[6] = ct ? 1.0 : 0.0;
-                o[7] = 0.0;
-            }
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < RAFTX_MOOR_MAX_SEG; i++)
-        if (i < c.n) lw[(size_t)i * MOOR_LW_N + 23] = (double)flag;
-}
-
-// ---- bridles (include/raftx_mooring.h: stem rows anchor -> junction, then 2 .. RAFTX_MOOR_MAX_LEG leg rows junction ->
-// fairlead).  The unknown is the junction P; at every P the stem is shot in the vertical plane through the anchor and P
-// (moor_chain_eval) and every leg, a suspended catenary, in its own plane (moor_eval without a seabed), and
-//     R(P) = f_stem + sum f_leg,lower end - (0, 0, W_junction) = 0,       dR/dP = -K_PP = -(K_stem + sum K_leg)
-// with the 3 x 3 end stiffness K = [k11 u u' + HF/XF (I_h - u u'), k12 u; k12 u', k22] of an element, (k) the inverse of its
-// catenary Jacobian.  At the solution the fairleads see K_ij = K_i d_ij - K_i K_PP^-1 K_j, and dP/dx6 = K_PP^-1 sum K_j [I, -[r_j x]].
-// The legs of the rows after a head row `line` and its nc continuation rows (0: no bridle), within the nAfter rows that follow
-__device__ __forceinline__ int moor_bridle_legs(const double *__restrict__ line, const int nAfter, const int nc) {
-    int n = 0;
-    while (nc + n < nAfter && n < RAFTX_MOOR_MAX_LEG && line[(size_t)(nc + n + 1) * RAFTX_ML_N + RAFTX_ML_LEG] != 0.0) n++;
-    return n;
-}
-// The rows of the bridle whose head row is `line` (0: `line` is no head row of a bridle)
-__device__ __forceinline__ int moor_bridle_rows(const double *__restrict__ line, const int nAfter) {
-    if (line[RAFTX_ML_CONT] != 0.0 || line[RAFTX_ML_LEG] != 0.0) return 0;
-    int nc = 0;
-    while (nc < nAfter && nc < RAFTX_MOOR_MAX_SEG - 1 && line[(size_t)(nc + 1) * RAFTX_ML_N + RAFTX_ML_CONT] != 0.0) nc++;
-    const int nleg = moor_bridle_legs(line, nAfter, nc);
-    return nleg ? nc + 1 + nleg : 0;
-}
-
-// One element between its ends, XF apart horizontally and ZF vertically: the Newton iteration of moor_line_record /
+// ---- one element between its ends, XF apart horizontally and ZF vertically: the Newton iteration of moor_line_record /
 // moor_chain_record, cold start.  KIND 0: the chain c; 1: one suspended segment (c.L[0], c.EA[0], c.w[0]; no seabed); 2: the
 // chain c with the suspended segment top = (L, EA, w, weight of the point at its lower end) above it -- (H, V) at the top of
 // that segment, Vtop the chain's own.
@@ -348,7 +182,8 @@ __device__ __forceinline__ bool moor_shoot(const MoorChain &c, const bool seabed
     return conv;
 }
 
-// A solved element at one junction position: its end force pieces and the 3 x 3 end stiffness K (xx xy xz yy yz zz)
+// A solved element: its end force pieces, (k) the inverse of its catenary Jacobian and the 3 x 3 end stiffness
+// K = [k11 u u' + HF/XF (I_h - u u'), k12 u; k12 u', k22] (xx xy xz yy yz zz): a chain, a bridle's stem and its legs.
 struct MoorEnd {
     double H, V, ux, uy, k11, k12, k22, K[6];
 };
@@ -365,6 +200,200 @@ __device__ __forceinline__ void moor_end_set(MoorEnd &m, const double H, const d
     m.K[4] = m.k12 * uy;
     m.K[5] = m.k22;
 }
+// The gradient g3 of the tension Tx = |(H, Vx)| at a point of the element where the vertical force is Vx, for a displacement
+// of its upper end
+__device__ __forceinline__ void moor_end_grad(const MoorEnd &m, const double Vx, const double Tx, double g3[3]) {
+    const double gX = (m.H * m.k11 + Vx * m.k12) / Tx, gZ = (m.H * m.k12 + Vx * m.k22) / Tx;
+    g3[0] = gX * m.ux; g3[1] = gX * m.uy; g3[2] = gZ;
+}
+// The record q [0:23] of one row of the solved element m, between VA at its lower and VB at its upper end, with the arm r.
+// head: the row that carries the element's force and K3 (the anchor-side row of a chain); the others have zeros.
+__device__ __forceinline__ void moor_row_write(double *__restrict__ q, const MoorEnd &m, const double r[3], const bool head, const double VA,
+                                               const double VB) {
+    const double TB = sqrt(m.H * m.H + VB * VB), TA = sqrt(m.H * m.H + VA * VA);
+    if (head) {
+        q[0] = -m.H * m.ux; q[1] = -m.H * m.uy; q[2] = -m.V;
+        q[6] = m.K[0]; q[7] = m.K[1]; q[8] = m.K[2];
+        q[9] = m.K[1]; q[10] = m.K[3]; q[11] = m.K[4];
+        q[12] = m.K[2]; q[13] = m.K[4]; q[14] = m.K[5];
+    } else {
+        q[0] = 0.0; q[1] = 0.0; q[2] = 0.0;
+        for (int k = 6; k < 15; k++) q[k] = 0.0;
+    }
+    q[3] = r[0]; q[4] = r[1]; q[5] = r[2];
+    double gA[3], gB[3];
+    moor_end_grad(m, VA, TA, gA);
+    moor_end_grad(m, VB, TB, gB);
+    q[15] = gA[0]; q[16] = gA[1]; q[17] = gA[2];
+    q[18] = gB[0]; q[19] = gB[1]; q[20] = gB[2];
+    q[21] = TA;
+    q[22] = TB;
+}
+// A line_out row: LB the length on the seabed (ct: the row rests there in part), it the steps of the row's iteration
+__device__ __forceinline__ void moor_lo_write(double *o, const double H, const double VB, const double VA, const double LB, const int it,
+                                              const bool ct) {
+    o[0] = H; o[1] = VB; o[2] = H; o[3] = VA; o[4] = LB;
+    o[5] = (double)it; o[6] = ct ? 1.0 : 0.0; o[7] = 0.0;
+}
+// How far a segment (EA, w) sags below its lower end, where the vertical force is Vb < 0 (V changes sign inside the segment)
+__device__ __forceinline__ double moor_sag_drop(const double H, const double Vb, const double EA, const double w) {
+    const double vb = Vb / H, sb = sqrt(1.0 + vb * vb);
+    return (H / w) * (vb * vb / (sb + 1.0)) + Vb * Vb / (2.0 * EA * w);
+}
+// The head row `line` (into rec) and its nc continuation rows as the chain c, with the pose (into ps).  fin: every number read is
+// finite; pos: every L, EA, w is positive; Lt, Wt: the sums of the lengths and of the weights (segments and joints).
+struct MoorPose { double v[6]; };
+__device__ __forceinline__ void moor_chain_load(const double *__restrict__ line, const int nc, const MoorPose &pose, double rec[RAFTX_ML_N],
+                                                double ps[6], MoorChain &c, bool &fin, bool &pos, double &Lt, double &Wt) {
+#pragma unroll
+    for (int i = 0; i < RAFTX_ML_N; i++) rec[i] = line[i];
+#pragma unroll
+    for (int i = 0; i < 6; i++) ps[i] = pose.v[i];
+    c.n = nc + 1;
+    c.L[0] = rec[6]; c.EA[0] = rec[7]; c.w[0] = rec[8]; c.Wj[0] = 0.0;
+    fin = true;
+    for (int i = 0; i < 10; i++) fin = fin && isfinite(rec[i]);
+    for (int i = 0; i < 6; i++) fin = fin && isfinite(ps[i]);
+    pos = c.L[0] > 0.0 && c.EA[0] > 0.0 && c.w[0] > 0.0;
+    Lt = c.L[0];
+    Wt = c.w[0] * c.L[0];
+#pragma unroll
+    for (int i = 1; i < RAFTX_MOOR_MAX_SEG; i++) {
+        c.L[i] = 1.0; c.EA[i] = 1.0; c.w[i] = 1.0; c.Wj[i] = 0.0;
+        if (i >= c.n) continue;
+        const double *p = line + (size_t)i * RAFTX_ML_N;
+        c.L[i] = p[6]; c.EA[i] = p[7]; c.w[i] = p[8]; c.Wj[i] = p[RAFTX_ML_WJOINT];
+        fin = fin && isfinite(c.L[i]) && isfinite(c.EA[i]) && isfinite(c.w[i]) && isfinite(p[9]) && isfinite(c.Wj[i]);
+        pos = pos && c.L[i] > 0.0 && c.EA[i] > 0.0 && c.w[i] > 0.0;
+        Lt += c.L[i];
+        Wt += c.w[i] * c.L[i] + c.Wj[i];
+    }
+}
+// The solved chain c (H, its segments' Vtop, the anchor-side segment's contact) against the seabed, anchor at az: true where the
+// anchor-side segment rests wholly (so would its upper joint), or a joint or a sag lies below the floor
+__device__ __forceinline__ bool moor_chain_grounded(const MoorChain &c, const double H, const double Vtop[RAFTX_MOOR_MAX_SEG], const int contact,
+                                                    const bool seabed, const double az, const double depth) {
+    if (seabed && Vtop[0] <= 0.0) return true;
+    // the joints and the sags (where V changes sign inside a segment) against the seabed, from the anchor up
+    const double floor = -depth - 1e-6 * depth;
+    bool grounded = false;
+    double z = az;
+#pragma unroll
+    for (int i = 0; i < RAFTX_MOOR_MAX_SEG; i++) {
+        if (i >= c.n) continue;
+        const double Vb = Vtop[i] - c.w[i] * c.L[i];
+        if (!(i == 0 && contact) && Vb < 0.0 && Vtop[i] > 0.0) {
+            const double drop = moor_sag_drop(H, Vb, c.EA[i], c.w[i]);
+            if (z - drop < floor) grounded = true;
+        }
+        MoorEval s;
+        moor_eval(H, Vtop[i], c.L[i], c.EA[i], c.w[i], seabed && i == 0, s);
+        z += s.Z;
+        if (i + 1 < c.n && z < floor) grounded = true;
+    }
+    return grounded;
+}
+// A chain at the pose ps: the head row `line` and the nc continuation rows after it.  The records lw of all its rows and, where
+// lo_out is not null and the chain is not flagged, their line_out rows.  NOT inlined, and every argument a scalar or a pointer
+// to global memory: k_moor_line and k_mean_pose call one body, so the records of a chain are the same bits from both (for a
+// single line the two kernels' inlined copies of one source have always agreed; nothing promises that of a second, larger body).
+__device__ __noinline__ void moor_chain_record(const double *__restrict__ line, const int nc, const MoorPose pose, const double depth,
+                                               double *__restrict__ lw, double *__restrict__ lo_out) {
+    double rec[RAFTX_ML_N], ps[6], Lt, Wt;
+    MoorChain c;
+    bool fin, pos;
+    moor_chain_load(line, nc, pose, rec, ps, c, fin, pos, Lt, Wt);
+    const double az = rec[2];
+    int flag = 0;
+    double r[3] = {0, 0, 0}, XF = 0.0, ZF = 0.0, ux = 0.0, uy = 0.0;
+    if (!fin || !pos || !(Wt > 0.0) || az < -depth - 1e-6 * depth) flag = RAFTX_MOOR_BAD_LINE;
+    if (!flag) {
+        moor_arm(rec, ps, r);
+        const double dx = (ps[0] + r[0]) - rec[0], dy = (ps[1] + r[1]) - rec[1];
+        XF = sqrt(dx * dx + dy * dy);
+        ZF = (ps[2] + r[2]) - az;
+        ux = dx / XF;
+        uy = dy / XF;
+        if (!(ZF > 0.0)) flag = RAFTX_MOOR_BAD_LINE;
+        else if (XF <= 1e-9 * Lt) flag = RAFTX_MOOR_VERTICAL;
+        else if (Lt >= XF + ZF) flag = RAFTX_MOOR_SLACK;
+    }
+    double H = 0.0, V = 0.0, Vtop[RAFTX_MOOR_MAX_SEG] = {0, 0, 0, 0};
+    MoorEval e;
+    int it = 0;
+    if (!flag) {
+        const bool seabed = fabs(az + depth) <= 1e-6 * depth;
+        const double we = Wt / Lt;                                // the effective weight per length of the guess
+        const double lam = (Lt * Lt <= XF * XF + ZF * ZF) ? 0.2 : sqrt(3.0 * ((Lt * Lt - ZF * ZF) / (XF * XF) - 1.0));
+        H = fabs(we * XF / (2.0 * lam));
+        V = 0.5 * we * (ZF / tanh(lam) + Lt);
+        moor_chain_eval(H, V, c, seabed, e, Vtop);
+        double eX = e.X - XF, eZ = e.Z - ZF, res = fmax(fabs(eX), fabs(eZ)) / Lt, a = 1.0;
+        bool conv = res == 0.0;
+        while (!conv && it < MOOR_MAX_IT) {
+            it++;
+            const double det = e.a11 * e.a22 - e.a12 * e.a12;
+            const double dH = -(e.a22 * eX - e.a12 * eZ) / det, dV = -(e.a11 * eZ - e.a12 * eX) / det;
+            double s = a;
+            if (H + s * dH <= 0.0) s = -0.5 * H / dH;
+            const double Ht = H + s * dH, Vt = V + s * dV;
+            MoorEval n;
+            double Vn[RAFTX_MOOR_MAX_SEG] = {0, 0, 0, 0};
+            moor_chain_eval(Ht, Vt, c, seabed, n, Vn);
+            const double nX = n.X - XF, nZ = n.Z - ZF, rn = fmax(fabs(nX), fabs(nZ)) / Lt;
+            if (rn < res) {
+                H = Ht; V = Vt; e = n; eX = nX; eZ = nZ; res = rn; a = 1.0;
+#pragma unroll
+                for (int i = 0; i < RAFTX_MOOR_MAX_SEG; i++) Vtop[i] = Vn[i];
+                conv = res == 0.0;
+            } else if (res <= MOOR_TIGHT) {
+                conv = true;
+            } else {
+                a *= 0.5;
+                if (a < 0x1p-40) break;
+            }
+        }
+        if (!conv) flag = RAFTX_MOOR_NO_CONVERGENCE;
+        else if (moor_chain_grounded(c, H, Vtop, e.contact, seabed, az, depth)) flag = RAFTX_MOOR_GROUNDED;
+    }
+    if (!flag) {
+        MoorEnd m;
+        moor_end_set(m, H, V, e, ux, uy, XF);
+#pragma unroll
+        for (int i = 0; i < RAFTX_MOOR_MAX_SEG; i++) {
+            if (i >= c.n) continue;
+            const bool ct = i == 0 && e.contact;
+            const double VB = Vtop[i], VA = ct ? 0.0 : VB - c.w[i] * c.L[i];
+            moor_row_write(lw + (size_t)i * MOOR_LW_N, m, r, i == 0, VA, VB);
+            if (lo_out) moor_lo_write(lo_out + (size_t)i * MOOR_LO_N, H, VB, VA, ct ? c.L[0] - VB / c.w[0] : 0.0, it, ct);
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < RAFTX_MOOR_MAX_SEG; i++)
+        if (i < c.n) lw[(size_t)i * MOOR_LW_N + 23] = (double)flag;
+}
+
+// ---- bridles (include/raftx_mooring.h: stem rows anchor -> junction, then 2 .. RAFTX_MOOR_MAX_LEG leg rows junction ->
+// fairlead).  The unknown is the junction P; at every P the stem is shot in the vertical plane through the anchor and P
+// (moor_chain_eval) and every leg, a suspended catenary, in its own plane (moor_eval without a seabed), and
+//     R(P) = f_stem + sum f_leg,lower end - (0, 0, W_junction) = 0,       dR/dP = -K_PP = -(K_stem + sum K_leg)
+// with the 3 x 3 end stiffness K = [k11 u u' + HF/XF (I_h - u u'), k12 u; k12 u', k22] of an element, (k) the inverse of its
+// catenary Jacobian.  At the solution the fairleads see K_ij = K_i d_ij - K_i K_PP^-1 K_j, and dP/dx6 = K_PP^-1 sum K_j [I, -[r_j x]].
+// The legs of the rows after a head row `line` and its nc continuation rows (0: no bridle), within the nAfter rows that follow
+__device__ __forceinline__ int moor_bridle_legs(const double *__restrict__ line, const int nAfter, const int nc) {
+    int n = 0;
+    while (nc + n < nAfter && n < RAFTX_MOOR_MAX_LEG && line[(size_t)(nc + n + 1) * RAFTX_ML_N + RAFTX_ML_LEG] != 0.0) n++;
+    return n;
+}
+// The rows of the bridle whose head row is `line` (0: `line` is no head row of a bridle)
+__device__ __forceinline__ int moor_bridle_rows(const double *__restrict__ line, const int nAfter) {
+    if (line[RAFTX_ML_CONT] != 0.0 || line[RAFTX_ML_LEG] != 0.0) return 0;
+    int nc = 0;
+    while (nc < nAfter && nc < RAFTX_MOOR_MAX_SEG - 1 && line[(size_t)(nc + 1) * RAFTX_ML_N + RAFTX_ML_CONT] != 0.0) nc++;
+    const int nleg = moor_bridle_legs(line, nAfter, nc);
+    return nleg ? nc + 1 + nleg : 0;
+}
+
 // y = S x with S symmetric (xx xy xz yy yz zz)
 __device__ __forceinline__ void moor_sym_mul(const double S[6], const double x[3], double y[3]) {
     y[0] = S[0] * x[0] + S[1] * x[1] + S[2] * x[2];
@@ -383,30 +412,10 @@ __device__ __noinline__ void moor_bridle_record(const double *__restrict__ line,
                                                 const double depth, double *__restrict__ lw, double *__restrict__ bw,
                                                 double *__restrict__ lo_out) {
     const int nrow = nc + 1 + nleg;
-    double rec[RAFTX_ML_N], ps[6];
-#pragma unroll
-    for (int i = 0; i < RAFTX_ML_N; i++) rec[i] = line[i];
-#pragma unroll
-    for (int i = 0; i < 6; i++) ps[i] = pose.v[i];
+    double rec[RAFTX_ML_N], ps[6], Ls, Ws;
     MoorChain c;                                                 // the stem
-    c.n = nc + 1;
-    c.L[0] = rec[6]; c.EA[0] = rec[7]; c.w[0] = rec[8]; c.Wj[0] = 0.0;
-    bool fin = true;
-    for (int i = 0; i < 10; i++) fin = fin && isfinite(rec[i]);
-    for (int i = 0; i < 6; i++) fin = fin && isfinite(ps[i]);
-    bool pos = c.L[0] > 0.0 && c.EA[0] > 0.0 && c.w[0] > 0.0;
-    double Ls = c.L[0], Ws = c.w[0] * c.L[0];
-#pragma unroll
-    for (int i = 1; i < RAFTX_MOOR_MAX_SEG; i++) {
-        c.L[i] = 1.0; c.EA[i] = 1.0; c.w[i] = 1.0; c.Wj[i] = 0.0;
-        if (i >= c.n) continue;
-        const double *p = line + (size_t)i * RAFTX_ML_N;
-        c.L[i] = p[6]; c.EA[i] = p[7]; c.w[i] = p[8]; c.Wj[i] = p[RAFTX_ML_WJOINT];
-        fin = fin && isfinite(c.L[i]) && isfinite(c.EA[i]) && isfinite(c.w[i]) && isfinite(p[9]) && isfinite(c.Wj[i]);
-        pos = pos && c.L[i] > 0.0 && c.EA[i] > 0.0 && c.w[i] > 0.0;
-        Ls += c.L[i];
-        Ws += c.w[i] * c.L[i] + c.Wj[i];
-    }
+    bool fin, pos;
+    moor_chain_load(line, nc, pose, rec, ps, c, fin, pos, Ls, Ws);
     MoorChain g[RAFTX_MOOR_MAX_LEG];                             // the legs, one segment each
     double rl[RAFTX_MOOR_MAX_LEG][3], pf[RAFTX_MOOR_MAX_LEG][3];  // arms R r_f and fairlead positions
     double Wj = 0.0, Wl = 0.0;
@@ -574,30 +583,14 @@ __device__ __noinline__ void moor_bridle_record(const double *__restrict__ line,
     if (!flag) {
         // the seabed: the stem by the chain's rule, then the junction and the sags of the legs
         const double floor = -depth - 1e-6 * depth;
-        if (seabed && Vtop[0] <= 0.0) flag = RAFTX_MOOR_GROUNDED;
-        double z = az;
-#pragma unroll
-        for (int i = 0; i < RAFTX_MOOR_MAX_SEG; i++) {
-            if (i >= c.n) continue;
-            const double Vb = Vtop[i] - c.w[i] * c.L[i];
-            if (!(i == 0 && es.contact) && Vb < 0.0 && Vtop[i] > 0.0) {
-                const double vb = Vb / S.H, sb = sqrt(1.0 + vb * vb);
-                const double drop = (S.H / c.w[i]) * (vb * vb / (sb + 1.0)) + Vb * Vb / (2.0 * c.EA[i] * c.w[i]);
-                if (z - drop < floor) flag = RAFTX_MOOR_GROUNDED;
-            }
-            MoorEval s;
-            moor_eval(S.H, Vtop[i], c.L[i], c.EA[i], c.w[i], seabed && i == 0, s);
-            z += s.Z;
-            if (i + 1 < c.n && z < floor) flag = RAFTX_MOOR_GROUNDED;
-        }
+        if (moor_chain_grounded(c, S.H, Vtop, es.contact, seabed, az, depth)) flag = RAFTX_MOOR_GROUNDED;
         if (P[2] < floor) flag = RAFTX_MOOR_GROUNDED;
 #pragma unroll
         for (int i = 0; i < RAFTX_MOOR_MAX_LEG; i++) {
             if (i >= nleg) continue;
             const double Vb = G[i].V - g[i].w[0] * g[i].L[0];
             if (Vb < 0.0 && G[i].V > 0.0) {
-                const double vb = Vb / G[i].H, sb = sqrt(1.0 + vb * vb);
-                const double drop = (G[i].H / g[i].w[0]) * (vb * vb / (sb + 1.0)) + Vb * Vb / (2.0 * g[i].EA[0] * g[i].w[0]);
+                const double drop = moor_sag_drop(G[i].H, Vb, g[i].EA[0], g[i].w[0]);
                 if (P[2] - drop < floor) flag = RAFTX_MOOR_GROUNDED;
             }
         }
@@ -697,20 +690,12 @@ __device__ __noinline__ void moor_bridle_record(const double *__restrict__ line,
             b[42] = TA; b[43] = TB;
 #pragma unroll
             for (int e = 0; e < 2; e++) {
-                const double Vx = e ? VB : VA, Tx = e ? TB : TA;
-                const double gX = (S.H * S.k11 + Vx * S.k12) / Tx, gZ = (S.H * S.k12 + Vx * S.k22) / Tx;
-                const double g3[3] = {gX * S.ux, gX * S.uy, gZ};
+                double g3[3];
+                moor_end_grad(S, e ? VB : VA, e ? TB : TA, g3);
 #pragma unroll
                 for (int k = 0; k < 6; k++) b[44 + 6 * e + k] = g3[0] * DP[0][k] + g3[1] * DP[1][k] + g3[2] * DP[2][k];
             }
-            double *o = lo_out ? lo_out + (size_t)i * MOOR_LO_N : nullptr;
-            if (o) {
-                o[0] = S.H; o[1] = VB; o[2] = S.H; o[3] = VA;
-                o[4] = ct ? c.L[0] - VB / c.w[0] : 0.0;
-                o[5] = (double)it;
-                o[6] = ct ? 1.0 : 0.0;
-                o[7] = 0.0;
-            }
+            if (lo_out) moor_lo_write(lo_out + (size_t)i * MOOR_LO_N, S.H, VB, VA, ct ? c.L[0] - VB / c.w[0] : 0.0, it, ct);
         }
         // the legs' rows: the relative displacement of their ends is [I, -[r_i x]] - dP/dx6
 #pragma unroll
@@ -724,9 +709,8 @@ __device__ __noinline__ void moor_bridle_record(const double *__restrict__ line,
             b[42] = TA; b[43] = TB;
 #pragma unroll
             for (int e = 0; e < 2; e++) {
-                const double Vx = e ? VB : VA, Tx = e ? TB : TA;
-                const double gX = (H * G[i].k11 + Vx * G[i].k12) / Tx, gZ = (H * G[i].k12 + Vx * G[i].k22) / Tx;
-                const double g3[3] = {gX * G[i].ux, gX * G[i].uy, gZ};
+                double g3[3];
+                moor_end_grad(G[i], e ? VB : VA, e ? TB : TA, g3);
 #pragma unroll
                 for (int k = 0; k < 3; k++) {
                     b[44 + 6 * e + k] = (g3[k] - g3[0] * DP[0][k]) - g3[1] * DP[1][k] - g3[2] * DP[2][k];
@@ -734,10 +718,7 @@ __device__ __noinline__ void moor_bridle_record(const double *__restrict__ line,
                     b[44 + 6 * e + 3 + k] = (gr - g3[0] * DP[0][3 + k]) - g3[1] * DP[1][3 + k] - g3[2] * DP[2][3 + k];
                 }
             }
-            double *o = lo_out ? lo_out + (size_t)(c.n + i) * MOOR_LO_N : nullptr;
-            if (o) {
-                o[0] = H; o[1] = VB; o[2] = H; o[3] = VA; o[4] = 0.0; o[5] = (double)it; o[6] = 0.0; o[7] = 0.0;
-            }
+            if (lo_out) moor_lo_write(lo_out + (size_t)(c.n + i) * MOOR_LO_N, H, VB, VA, 0.0, it, false);
         }
     }
     for (int i = 0; i < nrow; i++) {
@@ -747,7 +728,8 @@ __device__ __noinline__ void moor_bridle_record(const double *__restrict__ line,
     }
 }
 
-// The share of a bridle (the bw record of its head row) in C_moor and F_moor, and a row's T and J: k_moor_design's part
+// The share of a bridle (the bw record of its head row) in C_moor and F_moor, and a row's T, J and Lr (J as rows of
+// k_sweep_channels: plane 0 = J, the other two zero), each or null: k_moor_design's part
 __device__ __forceinline__ void moor_bridle_share(const double *__restrict__ b, double C[36], double F[6]) {
 #pragma unroll
     for (int i = 0; i < 36; i++) C[i] += b[i];
@@ -755,13 +737,18 @@ __device__ __forceinline__ void moor_bridle_share(const double *__restrict__ b, 
     for (int i = 0; i < 6; i++) F[i] += b[36 + i];
 }
 __device__ __forceinline__ void moor_bridle_TJ(const double *__restrict__ b, const int l, const int nL, double *__restrict__ T,
-                                               double *__restrict__ J) {
+                                               double *__restrict__ J, double *__restrict__ Lr = nullptr) {
     if (T) { T[l] = b[42]; T[nL + l] = b[43]; }
     if (J)
 #pragma unroll
         for (int e = 0; e < 2; e++)
 #pragma unroll
             for (int k = 0; k < 6; k++) J[(size_t)(e * nL + l) * 6 + k] = b[44 + 6 * e + k];
+    if (Lr)
+#pragma unroll
+        for (int e = 0; e < 2; e++)
+#pragma unroll
+            for (int i = 0; i < 18; i++) Lr[(size_t)(e * nL + l) * 18 + i] = i < 6 ? b[44 + 6 * e + i] : 0.0;
 }
 
 // One line at the pose ps: the record lw [MOOR_LW_N] (in global memory) and lo [MOOR_LO_N].  The body of k_moor_line, shared
@@ -943,20 +930,70 @@ __device__ __forceinline__ void moor_line_share(const double *__restrict__ q, do
     F[4] += r[2] * f[0] - r[0] * f[2];
     F[5] += r[0] * f[1] - r[1] * f[0];
 }
-__device__ __forceinline__ void moor_line_TJ(const double *__restrict__ q, const int l, const int nL, double *__restrict__ T,
-                                             double *__restrict__ J) {
+// The six J values of end e (0: A, 1: B) of a row from its record q: (g, r x g)
+__device__ __forceinline__ void moor_row_J(const double *__restrict__ q, const int e, double *o) {
     const double r[3] = {q[3], q[4], q[5]};
+    const double *g = q + 15 + 3 * e;
+    o[0] = g[0]; o[1] = g[1]; o[2] = g[2];
+    o[3] = r[1] * g[2] - r[2] * g[1];
+    o[4] = r[2] * g[0] - r[0] * g[2];
+    o[5] = r[0] * g[1] - r[1] * g[0];
+}
+__device__ __forceinline__ void moor_line_TJ(const double *__restrict__ q, const int l, const int nL, double *__restrict__ T,
+                                             double *__restrict__ J, double *__restrict__ Lr = nullptr) {
     if (T) { T[l] = q[21]; T[nL + l] = q[22]; }
     if (J)
 #pragma unroll
+        for (int e = 0; e < 2; e++) moor_row_J(q, e, J + (size_t)(e * nL + l) * 6);
+    if (Lr)
+#pragma unroll
         for (int e = 0; e < 2; e++) {
-            const double *g = q + 15 + 3 * e;
-            double *o = J + (size_t)(e * nL + l) * 6;
-            o[0] = g[0]; o[1] = g[1]; o[2] = g[2];
-            o[3] = r[1] * g[2] - r[2] * g[1];
-            o[4] = r[2] * g[0] - r[0] * g[2];
-            o[5] = r[0] * g[1] - r[1] * g[0];
+            double *o = Lr + (size_t)(e * nL + l) * 18;
+            moor_row_J(q, e, o);
+#pragma unroll
+            for (int i = 6; i < 18; i++) o[i] = 0.0;
         }
+}
+
+// The walk over the nL rows of ONE design (its lines, its records lw and, with BRIDLES, bw): a bridle from its head row once,
+// else the line's own.  SUMS: the shares in C_moor [36] and F_moor [6], added in row order from zero; ROWS: T [2 nL],
+// J [2 nL,6] and Lr [2 nL,3,6] (each or null) of every row.  k_moor_design does both in one pass; k_mean_pose
+// (raftx_statics.h) the sums at every step and the rows once, through the two functions below.
+template <bool BRIDLES, bool SUMS, bool ROWS>
+__device__ __forceinline__ void moor_design_walk(const double *__restrict__ lines, const double *lw, const double *bw, const int nL,
+                                                 double *C, double *F, double *__restrict__ T, double *__restrict__ J,
+                                                 double *__restrict__ Lr) {
+    if (SUMS) {
+#pragma unroll
+        for (int i = 0; i < 36; i++) C[i] = 0.0;
+#pragma unroll
+        for (int i = 0; i < 6; i++) F[i] = 0.0;
+    }
+    for (int l = 0; l < nL; l++) {
+        if (BRIDLES) {
+            const int nb = moor_bridle_rows(lines + (size_t)l * RAFTX_ML_N, nL - 1 - l);
+            if (nb) {                                            // a bridle, from its head row: the share once, T and J of all its rows
+                const double *b = bw + (size_t)l * MOOR_BW_N;
+                if (SUMS) moor_bridle_share(b, C, F);
+                if (ROWS)
+                    for (int k = 0; k < nb; k++) moor_bridle_TJ(b + (size_t)k * MOOR_BW_N, l + k, nL, T, J, Lr);
+                l += nb - 1;
+                continue;
+            }
+        }
+        if (SUMS) moor_line_share(lw + (size_t)l * MOOR_LW_N, C, F);
+        if (ROWS) moor_line_TJ(lw + (size_t)l * MOOR_LW_N, l, nL, T, J, Lr);
+    }
+}
+template <bool BRIDLES>
+__device__ __forceinline__ void moor_design_sums(const double *__restrict__ lines, const double *lw, const double *bw, const int nL,
+                                                 double C[36], double F[6]) {
+    moor_design_walk<BRIDLES, true, false>(lines, lw, bw, nL, C, F, nullptr, nullptr, nullptr);
+}
+template <bool BRIDLES>
+__device__ __forceinline__ void moor_design_TJ(const double *__restrict__ lines, const double *lw, const double *bw, const int nL,
+                                               double *__restrict__ T, double *__restrict__ J) {
+    moor_design_walk<BRIDLES, false, true>(lines, lw, bw, nL, nullptr, nullptr, T, J, nullptr);
 }
 
 template <bool BRIDLES>
@@ -979,48 +1016,10 @@ __global__ void __launch_bounds__(MOOR_THREADS) k_moor_design(MoorArgs A) {
         if (A.Lr) for (int i = 0; i < 36 * nL; i++) A.Lr[(size_t)d * 36 * nL + i] = (i % 18) < 6 ? nan : 0.0;
         return;
     }
+    const double *lines = A.lines + (size_t)d * nL * RAFTX_ML_N, *bw0 = BRIDLES ? A.bw + (size_t)d * nL * MOOR_BW_N : nullptr;
     double C[36], F[6];
-#pragma unroll
-    for (int i = 0; i < 36; i++) C[i] = 0.0;
-#pragma unroll
-    for (int i = 0; i < 6; i++) F[i] = 0.0;
-    for (int l = 0; l < nL; l++) {
-        const double *q = lw0 + (size_t)l * MOOR_LW_N;
-        if (BRIDLES) {
-            const int nb = moor_bridle_rows(A.lines + ((size_t)d * nL + l) * RAFTX_ML_N, nL - 1 - l);
-            if (nb) {                                            // a bridle, from its head row: the share once, T and J of all its rows
-                const double *b = A.bw + ((size_t)d * nL + l) * MOOR_BW_N;
-                moor_bridle_share(b, C, F);
-                for (int k = 0; k < nb; k++) {
-                    moor_bridle_TJ(b + (size_t)k * MOOR_BW_N, l + k, nL, T, J);
-                    if (A.Lr)
-#pragma unroll
-                        for (int e = 0; e < 2; e++) {
-                            double *o = A.Lr + ((size_t)d * 2 * nL + (e * nL + l + k)) * 18;
-#pragma unroll
-                            for (int i = 0; i < 18; i++) o[i] = i < 6 ? b[(size_t)k * MOOR_BW_N + 44 + 6 * e + i] : 0.0;
-                        }
-                }
-                l += nb - 1;
-                continue;
-            }
-        }
-        moor_line_share(q, C, F);
-        const double r[3] = {q[3], q[4], q[5]};
-        moor_line_TJ(q, l, nL, T, J);
-        if (A.Lr)
-#pragma unroll
-            for (int e = 0; e < 2; e++) {
-                const double *g = q + 15 + 3 * e;
-                double *o = A.Lr + ((size_t)d * 2 * nL + (e * nL + l)) * 18;
-                o[0] = g[0]; o[1] = g[1]; o[2] = g[2];
-                o[3] = r[1] * g[2] - r[2] * g[1];
-                o[4] = r[2] * g[0] - r[0] * g[2];
-                o[5] = r[0] * g[1] - r[1] * g[0];
-#pragma unroll
-                for (int i = 6; i < 18; i++) o[i] = 0.0;
-            }
-    }
+    moor_design_walk<BRIDLES, true, true>(A.lines + (size_t)d * nL * RAFTX_ML_N, lw0, BRIDLES ? A.bw + (size_t)d * nL * MOOR_BW_N : nullptr, nL,
+                                          C, F, T, J, A.Lr ? A.Lr + (size_t)d * 36 * nL : nullptr);
     if (A.C)
 #pragma unroll
         for (int i = 0; i < 36; i++) A.C[(size_t)d * 36 + i] = C[i];

@@ -9,8 +9,8 @@
 // Work decomposition: k_mean_pose is ONE launch for the whole iteration of the whole batch.  A design has a group of G lanes
 // (G = the power of two at or above nLine, at most 64; a workgroup is one wavefront of 64 / G designs).  Per step the lanes of
 // a group solve the design's lines in parallel -- moor_line_record, the body of k_moor_line, cold start -- into the records lw
-// in global memory; after a workgroup barrier EVERY lane of the group gathers the records in line order (moor_line_share, the
-// sums of k_moor_design: the same bits), forms Y and K and takes the step, so the group needs no broadcast: its lanes hold the
+// in global memory; after a workgroup barrier EVERY lane of the group gathers the records in line order (moor_design_sums, the
+// walk and the sums of k_moor_design: the same bits), forms Y and K and takes the step, so the group needs no broadcast: its lanes hold the
 // same x, bit for bit.  The records cross the barrier through memory, as between k_moor_line and k_moor_design, so no
 // multiply-add is contracted across the two halves that those kernels could not contract either: C_moor, F_moor, T, J are what
 // raftx_mooring_lines returns at the returned pose.  The loop is uniform over the workgroup (__syncthreads_or): a finished
@@ -98,6 +98,7 @@ __global__ void __launch_bounds__(MP_THREADS) k_mean_pose(MeanPoseArgs A) {
 #pragma unroll
     for (int i = 0; i < 6; i++) x[i] = xr[i] = (live && A.x_ref) ? A.x_ref[dd * 6 + i] : 0.0;
     double *lw0 = A.lw + dd * nL * MOOR_LW_N;
+    const double *lines = A.lines + dd * nL * RAFTX_ML_N, *bw0 = BRIDLES ? A.bw + dd * nL * MOOR_BW_N : nullptr;
     int it = 0, flag = 0;
     int phase = live ? 0 : 2;                                    // 0 iterating, 1 converged: the outputs at x are due, 2 finished
     for (;;) {
@@ -116,21 +117,7 @@ __global__ void __launch_bounds__(MP_THREADS) k_mean_pose(MeanPoseArgs A) {
                 phase = 2;
             } else {
                 double C[36], F[6], Y[6];
-#pragma unroll
-                for (int i = 0; i < 36; i++) C[i] = 0.0;
-#pragma unroll
-                for (int i = 0; i < 6; i++) F[i] = 0.0;
-                for (int l = 0; l < nL; l++) {
-                    if (BRIDLES) {                                // a bridle from its head row, once (k_moor_design's order)
-                        const int nb = moor_bridle_rows(A.lines + (dd * nL + l) * RAFTX_ML_N, nL - 1 - l);
-                        if (nb) {
-                            moor_bridle_share(A.bw + (dd * nL + l) * MOOR_BW_N, C, F);
-                            l += nb - 1;
-                            continue;
-                        }
-                    }
-                    moor_line_share(lw0 + (size_t)l * MOOR_LW_N, C, F);
-                }
+                moor_design_sums<BRIDLES>(lines, lw0, bw0, nL, C, F);       // k_moor_design's walk: a bridle from its head row, once
                 const double *Kh = A.K_hs + dd * 36;
 #pragma unroll
                 for (int i = 0; i < 6; i++) {
@@ -152,18 +139,7 @@ __global__ void __launch_bounds__(MP_THREADS) k_mean_pose(MeanPoseArgs A) {
 #pragma unroll
                             for (int i = 0; i < 36; i++) A.C[dd * 36 + i] = C[i];
                         if (A.T || A.J)
-                            for (int l = 0; l < nL; l++) {
-                                double *Td = A.T ? A.T + dd * 2 * nL : nullptr, *Jd = A.J ? A.J + dd * 12 * nL : nullptr;
-                                if (BRIDLES) {
-                                    const int nb = moor_bridle_rows(A.lines + (dd * nL + l) * RAFTX_ML_N, nL - 1 - l);
-                                    if (nb) {
-                                        for (int k = 0; k < nb; k++) moor_bridle_TJ(A.bw + (dd * nL + l + k) * MOOR_BW_N, l + k, nL, Td, Jd);
-                                        l += nb - 1;
-                                        continue;
-                                    }
-                                }
-                                moor_line_TJ(lw0 + (size_t)l * MOOR_LW_N, l, nL, Td, Jd);
-                            }
+                            moor_design_TJ<BRIDLES>(lines, lw0, bw0, nL, A.T ? A.T + dd * 2 * nL : nullptr, A.J ? A.J + dd * 12 * nL : nullptr);
                     }
                     phase = 2;
                 } else {

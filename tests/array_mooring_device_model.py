@@ -29,33 +29,7 @@ def shared(rec, pa, pb, depth, seed=None):
     if XF <= 1e-9 * L:
         return 2, None
     ux, uy = dx / XF, dy / XF
-    lam = 0.2 if L * L <= XF * XF + ZF * ZF else np.sqrt(3.0 * ((L * L - ZF * ZF) / (XF * XF) - 1.0))
-    H, V = abs(w * XF / (2.0 * lam)), 0.5 * w * (ZF / np.tanh(lam) + L)
-    X, Z, a11, a12, a22, _ = dm._eval(H, V, L, EA, w, False, None)
-    eX, eZ = X - XF, Z - ZF
-    res, a, it = max(abs(eX), abs(eZ)) / L, 1.0, 0
-    conv = res == 0.0
-    while not conv and it < dm.MAX_IT:
-        it += 1
-        det = a11 * a22 - a12 * a12
-        dH, dV = -(a22 * eX - a12 * eZ) / det, -(a11 * eZ - a12 * eX) / det
-        s = a
-        if H + s * dH <= 0.0:
-            s = -0.5 * H / dH
-        Ht, Vt = H + s * dH, V + s * dV
-        nx = dm._eval(Ht, Vt, L, EA, w, False, None)
-        nX, nZ = nx[0] - XF, nx[1] - ZF
-        rn = max(abs(nX), abs(nZ)) / L
-        if rn < res:
-            H, V, eX, eZ, res, a = Ht, Vt, nX, nZ, rn, 1.0
-            X, Z, a11, a12, a22, _ = nx
-            conv = res == 0.0
-        elif res <= dm.TIGHT:
-            conv = True
-        else:
-            a *= 0.5
-            if a < 2.0 ** -40:
-                break
+    conv, H, V, it, (_, _, a11, a12, a22, _) = dm.newton(lambda H, V: dm._eval(H, V, L, EA, w, False, None), L, w, XF, ZF)
     if not conv:
         return 8, None
     VA = V - w * L
@@ -66,17 +40,9 @@ def shared(rec, pa, pb, depth, seed=None):
         zlow = zA - ((H / w) * (vb * vb / (sb + 1.0)) + VA * VA / (2.0 * EA * w))
     if zlow < -depth - 1e-6 * depth:
         return FLAG_GROUNDED, None
-    det = a11 * a22 - a12 * a12
-    k11, k12, k22 = a22 / det, -a12 / det, a11 / det
+    m = dm.end(H, V, a11, a12, a22, ux, uy, XF)                  # (the device keeps a copy of this arithmetic: moor_shared_body)
     TB, TA = np.sqrt(H * H + V * V), np.sqrt(H * H + VA * VA)
-    th = H / XF
-    K = np.array([[k11 * ux * ux + th * (1.0 - ux * ux), k11 * ux * uy - th * (ux * uy), k12 * ux],
-                  [k11 * ux * uy - th * (ux * uy), k11 * uy * uy + th * (1.0 - uy * uy), k12 * uy],
-                  [k12 * ux, k12 * uy, k22]])
-    gAX, gAZ = (H * k11 + VA * k12) / TA, (H * k12 + VA * k22) / TA
-    gBX, gBZ = (H * k11 + V * k12) / TB, (H * k12 + V * k22) / TB
-    return 0, dict(f=np.array([-H * ux, -H * uy, -V]), r=rB, K=K, gA=np.array([gAX * ux, gAX * uy, gAZ]),
-                   gB=np.array([gBX * ux, gBX * uy, gBZ]), TA=TA, TB=TB, rA=rA,
+    return 0, dict(f=np.array([-H * ux, -H * uy, -V]), r=rB, K=m["K"], gA=dm.end_grad(m, VA, TA), gB=dm.end_grad(m, V, TB), TA=TA, TB=TB, rA=rA,
                    fA=np.array([H * ux, H * uy, 0.0 if seed == "va_zero" else VA]),
                    lo=np.array([H, V, H, VA, 0.0, it, 0.0, 0.0]), low=zlow)
 

@@ -31,44 +31,8 @@ def _shoot(kind, L, EA, w, Wj, seabed, Lt, we, XF, ZF, top=None):
             return (t[0] + c[0], t[1] + c[1], t[2] + c[2], t[3] + c[3], t[4] + c[4], c[5], c[6])
         return cdm._chain_eval(H, V, L, EA, w, Wj, seabed, None)
 
-    lam = 0.2 if Lt * Lt <= XF * XF + ZF * ZF else np.sqrt(3.0 * ((Lt * Lt - ZF * ZF) / (XF * XF) - 1.0))
-    H, V = abs(we * XF / (2.0 * lam)), 0.5 * we * (ZF / np.tanh(lam) + Lt)
-    cur = ev(H, V)
-    eX, eZ = cur[0] - XF, cur[1] - ZF
-    res, a, it = max(abs(eX), abs(eZ)) / Lt, 1.0, 0
-    conv = res == 0.0
-    while not conv and it < MAX_IT:
-        it += 1
-        a11, a12, a22 = cur[2:5]
-        det = a11 * a22 - a12 * a12
-        dH, dV = -(a22 * eX - a12 * eZ) / det, -(a11 * eZ - a12 * eX) / det
-        s = a
-        if H + s * dH <= 0.0:
-            s = -0.5 * H / dH
-        Ht, Vt = H + s * dH, V + s * dV
-        nx = ev(Ht, Vt)
-        nX, nZ = nx[0] - XF, nx[1] - ZF
-        rn = max(abs(nX), abs(nZ)) / Lt
-        if rn < res:
-            H, V, eX, eZ, res, a, cur = Ht, Vt, nX, nZ, rn, 1.0, nx
-            conv = res == 0.0
-        elif res <= TIGHT:
-            conv = True
-        else:
-            a *= 0.5
-            if a < 2.0 ** -40:
-                break
+    conv, H, V, _, cur = dm.newton(ev, Lt, we, XF, ZF)
     return (conv, H, V) + tuple(cur[2:])
-
-
-def _end(H, V, a11, a12, a22, ux, uy, XF):
-    det = a11 * a22 - a12 * a12
-    k11, k12, k22 = a22 / det, -a12 / det, a11 / det
-    th = H / XF
-    K = np.array([[k11 * ux * ux + th * (1.0 - ux * ux), k11 * ux * uy - th * (ux * uy), k12 * ux],
-                  [k11 * ux * uy - th * (ux * uy), k11 * uy * uy + th * (1.0 - uy * uy), k12 * uy],
-                  [k12 * ux, k12 * uy, k22]])
-    return dict(H=H, V=V, ux=ux, uy=uy, k11=k11, k12=k12, k22=k22, K=K)
 
 
 def bridle(rows, ns, ps, depth, seed=None):
@@ -119,7 +83,7 @@ def bridle(rows, ns, ps, depth, seed=None):
         s = _shoot(0, L, EA, w, Wjs, seabed, Ls, wes, XF, ZF)
         if not s[0]:
             return None
-        S = _end(s[1], s[2], s[3], s[4], s[5], dx / XF, dy / XF, XF)
+        S = dm.end(s[1], s[2], s[3], s[4], s[5], dx / XF, dy / XF, XF)
         S["contact"], S["Vtop"] = s[6], s[7]
         R = np.array([-S["H"] * S["ux"], -S["H"] * S["uy"], -S["V"] - Wj])
         K = S["K"].copy()
@@ -132,7 +96,7 @@ def bridle(rows, ns, ps, depth, seed=None):
             s = _shoot(1, [legs[i, 6]], [legs[i, 7]], [legs[i, 8]], [0.0], False, legs[i, 6], legs[i, 8], XF, ZF)
             if not s[0]:
                 return None
-            g = _end(s[1], s[2], s[3], s[4], s[5], dx / XF, dy / XF, XF)
+            g = dm.end(s[1], s[2], s[3], s[4], s[5], dx / XF, dy / XF, XF)
             R = R + np.array([g["H"] * g["ux"], g["H"] * g["uy"], g["V"] - legs[i, 8] * legs[i, 6]])
             if not (seed == "leg_missing_from_kpp" and i == nleg - 1):
                 K = K + g["K"]
@@ -198,28 +162,12 @@ def bridle(rows, ns, ps, depth, seed=None):
         return 8, None
     floor = -depth - 1e-6 * depth
     flag = 0
-    if seabed and S["Vtop"][0] <= 0.0:
-        flag = GROUNDED
-    z = az
-    for i in range(ns):
-        Vb = S["Vtop"][i] - w[i] * L[i]
-        if not (i == 0 and S["contact"]) and Vb < 0.0 and S["Vtop"][i] > 0.0:
-            vb = Vb / S["H"]
-            sb = np.sqrt(1.0 + vb * vb)
-            if z - ((S["H"] / w[i]) * (vb * vb / (sb + 1.0)) + Vb * Vb / (2.0 * EA[i] * w[i])) < floor:
-                flag = GROUNDED
-        z += dm._eval(S["H"], S["Vtop"][i], L[i], EA[i], w[i], seabed and i == 0, None)[1]
-        if i + 1 < ns and z < floor:
-            flag = GROUNDED
-    if P[2] < floor:
+    if cdm.grounded(S["H"], S["Vtop"], S["contact"], L, EA, w, seabed, az, depth) or P[2] < floor:
         flag = GROUNDED
     for i in range(nleg):
         Vb = G[i]["V"] - legs[i, 8] * legs[i, 6]
-        if Vb < 0.0 and G[i]["V"] > 0.0:
-            vb = Vb / G[i]["H"]
-            sb = np.sqrt(1.0 + vb * vb)
-            if P[2] - ((G[i]["H"] / legs[i, 8]) * (vb * vb / (sb + 1.0)) + Vb * Vb / (2.0 * legs[i, 7] * legs[i, 8])) < floor:
-                flag = GROUNDED
+        if Vb < 0.0 and G[i]["V"] > 0.0 and P[2] - cdm.sag_drop(G[i]["H"], Vb, legs[i, 7], legs[i, 8]) < floor:
+            flag = GROUNDED
     if flag:
         return flag, dict(P=P)                             # (the junction, for who wants to look: the records are not written)
     D = [Ki @ G[j]["K"] for j in range(nleg)]
@@ -253,9 +201,8 @@ def bridle(rows, ns, ps, depth, seed=None):
         VA = 0.0 if ct else VB - w[i] * L[i]
         for e, Vx in ((0, VA), (1, VB)):
             Tx = np.sqrt(S["H"] ** 2 + Vx * Vx)
-            gX, gZ = (S["H"] * S["k11"] + Vx * S["k12"]) / Tx, (S["H"] * S["k12"] + Vx * S["k22"]) / Tx
             T[i, e] = Tx
-            J[i, e] = np.array([gX * S["ux"], gX * S["uy"], gZ]) @ DP
+            J[i, e] = dm.end_grad(S, Vx, Tx) @ DP
         lo[i] = [S["H"], VB, S["H"], VA, L[0] - VB / w[0] if ct else 0.0, it, 1.0 if ct else 0.0, 0.0]
     for i in range(nleg):
         g = G[i]
@@ -263,9 +210,8 @@ def bridle(rows, ns, ps, depth, seed=None):
         VA = VB - legs[i, 8] * legs[i, 6]
         for e, Vx in ((0, VA), (1, VB)):
             Tx = np.sqrt(g["H"] ** 2 + Vx * Vx)
-            gX, gZ = (g["H"] * g["k11"] + Vx * g["k12"]) / Tx, (g["H"] * g["k12"] + Vx * g["k22"]) / Tx
             T[ns + i, e] = Tx
-            J[ns + i, e] = np.array([gX * g["ux"], gX * g["uy"], gZ]) @ (B[i] - DP)
+            J[ns + i, e] = dm.end_grad(g, Vx, Tx) @ (B[i] - DP)
         lo[ns + i] = [g["H"], VB, g["H"], VA, 0.0, it, 0.0, 0.0]
     return 0, dict(C=C, F=F, T=T, J=J, lo=lo, P=P)
 

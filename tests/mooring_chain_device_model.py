@@ -33,6 +33,29 @@ def _chain_eval(H, V, L, EA, w, Wj, seabed, seed):
     return X, Z, a11, a12, a22, contact, Vtop
 
 
+def sag_drop(H, Vb, EA, w):
+    """How far a segment sags below its lower end, where the vertical force is Vb < 0 (moor_sag_drop)."""
+    vb = Vb / H
+    sb = np.sqrt(1.0 + vb * vb)
+    return (H / w) * (vb * vb / (sb + 1.0)) + Vb * Vb / (2.0 * EA * w)
+
+
+def grounded(H, Vtop, ct, L, EA, w, seabed, az, depth):
+    """The solved chain against the seabed (moor_chain_grounded): the anchor-side segment rests wholly, or a joint or a sag
+    (where V changes sign inside a segment) lies below the floor, from the anchor up."""
+    if seabed and Vtop[0] <= 0.0:
+        return True
+    floor, z, n = -depth - 1e-6 * depth, az, len(L)
+    for i in range(n):
+        Vb = Vtop[i] - w[i] * L[i]
+        if not (i == 0 and ct) and Vb < 0.0 and Vtop[i] > 0.0 and z - sag_drop(H, Vb, EA[i], w[i]) < floor:
+            return True
+        z += dm._eval(H, Vtop[i], L[i], EA[i], w[i], seabed and i == 0, None)[1]
+        if i + 1 < n and z < floor:
+            return True
+    return False
+
+
 def chain(rows, ps, depth, seed=None):
     """(flag, [record per row]) of one composite line: what the head row's lane writes."""
     rows = np.asarray(rows, dtype=np.float64)
@@ -61,54 +84,12 @@ def chain(rows, ps, depth, seed=None):
     ux, uy = dx / XF, dy / XF
     seabed = abs(az + depth) <= 1e-6 * depth
     we = Wt / Lt
-    lam = 0.2 if Lt * Lt <= XF * XF + ZF * ZF else np.sqrt(3.0 * ((Lt * Lt - ZF * ZF) / (XF * XF) - 1.0))
-    H, V = abs(we * XF / (2.0 * lam)), 0.5 * we * (ZF / np.tanh(lam) + Lt)
-    X, Z, a11, a12, a22, ct, Vtop = _chain_eval(H, V, L, EA, w, Wj, seabed, seed)
-    eX, eZ = X - XF, Z - ZF
-    res, a, it = max(abs(eX), abs(eZ)) / Lt, 1.0, 0
-    conv = res == 0.0
-    while not conv and it < MAX_IT:
-        it += 1
-        det = a11 * a22 - a12 * a12
-        dH, dV = -(a22 * eX - a12 * eZ) / det, -(a11 * eZ - a12 * eX) / det
-        s = a
-        if H + s * dH <= 0.0:
-            s = -0.5 * H / dH
-        Ht, Vt = H + s * dH, V + s * dV
-        nx = _chain_eval(Ht, Vt, L, EA, w, Wj, seabed, seed)
-        nX, nZ = nx[0] - XF, nx[1] - ZF
-        rn = max(abs(nX), abs(nZ)) / Lt
-        if rn < res:
-            H, V, eX, eZ, res, a = Ht, Vt, nX, nZ, rn, 1.0
-            X, Z, a11, a12, a22, ct, Vtop = nx
-            conv = res == 0.0
-        elif res <= TIGHT:
-            conv = True
-        else:
-            a *= 0.5
-            if a < 2.0 ** -40:
-                break
+    conv, H, V, it, (_, _, a11, a12, a22, ct, Vtop) = dm.newton(lambda H, V: _chain_eval(H, V, L, EA, w, Wj, seabed, seed), Lt, we, XF, ZF)
     if not conv:
         return 8, None
-    if seabed and Vtop[0] <= 0.0:
+    if grounded(H, Vtop, ct, L, EA, w, seabed, az, depth):
         return GROUNDED, None
-    floor, z = -depth - 1e-6 * depth, az
-    for i in range(n):
-        Vb = Vtop[i] - w[i] * L[i]
-        if not (i == 0 and ct) and Vb < 0.0 and Vtop[i] > 0.0:
-            vb = Vb / H
-            sb = np.sqrt(1.0 + vb * vb)
-            if z - ((H / w[i]) * (vb * vb / (sb + 1.0)) + Vb * Vb / (2.0 * EA[i] * w[i])) < floor:
-                return GROUNDED, None
-        z += dm._eval(H, Vtop[i], L[i], EA[i], w[i], seabed and i == 0, None)[1]
-        if i + 1 < n and z < floor:
-            return GROUNDED, None
-    det = a11 * a22 - a12 * a12
-    k11, k12, k22 = a22 / det, -a12 / det, a11 / det
-    th = H / XF
-    K = np.array([[k11 * ux * ux + th * (1.0 - ux * ux), k11 * ux * uy - th * (ux * uy), k12 * ux],
-                  [k11 * ux * uy - th * (ux * uy), k11 * uy * uy + th * (1.0 - uy * uy), k12 * uy],
-                  [k12 * ux, k12 * uy, k22]])
+    m = dm.end(H, V, a11, a12, a22, ux, uy, XF)
     out = []
     for i in range(n):
         c = i == 0 and ct
@@ -116,10 +97,8 @@ def chain(rows, ps, depth, seed=None):
         VA = 0.0 if c else VB - w[i] * L[i]
         TB, TA = np.sqrt(H * H + VB * VB), np.sqrt(H * H + VA * VA)
         VgA = VB if seed == "gradient_wrong_end" else VA
-        gAX, gAZ = (H * k11 + VgA * k12) / TA, (H * k12 + VgA * k22) / TA
-        gBX, gBZ = (H * k11 + VB * k12) / TB, (H * k12 + VB * k22) / TB
-        out.append(dict(f=np.array([-H * ux, -H * uy, -V]) if i == 0 else np.zeros(3), r=r, K=K if i == 0 else np.zeros((3, 3)),
-                        gA=np.array([gAX * ux, gAX * uy, gAZ]), gB=np.array([gBX * ux, gBX * uy, gBZ]), TA=TA, TB=TB,
+        out.append(dict(f=np.array([-H * ux, -H * uy, -V]) if i == 0 else np.zeros(3), r=r, K=m["K"] if i == 0 else np.zeros((3, 3)),
+                        gA=dm.end_grad(m, VgA, TA), gB=dm.end_grad(m, VB, TB), TA=TA, TB=TB,
                         lo=np.array([H, VB, H, VA, L[0] - VB / w[0] if c else 0.0, it, 1.0 if c else 0.0, 0.0])))
     return 0, out
 

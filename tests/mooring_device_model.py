@@ -52,6 +52,56 @@ def _arm(rf, ang):
     return r
 
 
+def newton(ev, Lt, we, XF, ZF):
+    """(conv, H, V, it, last evaluation) of one element between ends XF, ZF apart: moor_shoot, THE damped Newton iteration on
+    (H, V), cold start.  ev(H, V) -> (X, Z, a11, a12, a22, ...); Lt, we: the length and weight per length of the guess."""
+    lam = 0.2 if Lt * Lt <= XF * XF + ZF * ZF else np.sqrt(3.0 * ((Lt * Lt - ZF * ZF) / (XF * XF) - 1.0))
+    H, V = abs(we * XF / (2.0 * lam)), 0.5 * we * (ZF / np.tanh(lam) + Lt)
+    cur = ev(H, V)
+    eX, eZ = cur[0] - XF, cur[1] - ZF
+    res, a, it = max(abs(eX), abs(eZ)) / Lt, 1.0, 0
+    conv = res == 0.0
+    while not conv and it < MAX_IT:
+        it += 1
+        a11, a12, a22 = cur[2:5]
+        det = a11 * a22 - a12 * a12
+        dH, dV = -(a22 * eX - a12 * eZ) / det, -(a11 * eZ - a12 * eX) / det
+        s = a
+        if H + s * dH <= 0.0:
+            s = -0.5 * H / dH
+        Ht, Vt = H + s * dH, V + s * dV
+        nx = ev(Ht, Vt)
+        nX, nZ = nx[0] - XF, nx[1] - ZF
+        rn = max(abs(nX), abs(nZ)) / Lt
+        if rn < res:
+            H, V, eX, eZ, res, a, cur = Ht, Vt, nX, nZ, rn, 1.0, nx
+            conv = res == 0.0
+        elif res <= TIGHT:
+            conv = True
+        else:
+            a *= 0.5
+            if a < 2.0 ** -40:
+                break
+    return conv, H, V, it, cur
+
+
+def end(H, V, a11, a12, a22, ux, uy, XF):
+    """A solved element (MoorEnd / moor_end_set): (k) the inverse of its catenary Jacobian and the 3 x 3 end stiffness K."""
+    det = a11 * a22 - a12 * a12
+    k11, k12, k22 = a22 / det, -a12 / det, a11 / det
+    th = H / XF
+    K = np.array([[k11 * ux * ux + th * (1.0 - ux * ux), k11 * ux * uy - th * (ux * uy), k12 * ux],
+                  [k11 * ux * uy - th * (ux * uy), k11 * uy * uy + th * (1.0 - uy * uy), k12 * uy],
+                  [k12 * ux, k12 * uy, k22]])
+    return dict(H=H, V=V, ux=ux, uy=uy, k11=k11, k12=k12, k22=k22, K=K)
+
+
+def end_grad(m, Vx, Tx):
+    """The gradient of the tension Tx where the element's vertical force is Vx (moor_end_grad)."""
+    gX, gZ = (m["H"] * m["k11"] + Vx * m["k12"]) / Tx, (m["H"] * m["k12"] + Vx * m["k22"]) / Tx
+    return np.array([gX * m["ux"], gX * m["uy"], gZ])
+
+
 def line(rec, ps, depth, seed=None):
     """(flag, dict) of one line: the record k_moor_line writes."""
     rec = np.asarray(rec, dtype=np.float64)
@@ -71,47 +121,13 @@ def line(rec, ps, depth, seed=None):
         return 4, None
     ux, uy = dx / XF, dy / XF
     seabed = abs(az + depth) <= 1e-6 * depth
-    lam = 0.2 if L * L <= XF * XF + ZF * ZF else np.sqrt(3.0 * ((L * L - ZF * ZF) / (XF * XF) - 1.0))
-    H, V = abs(w * XF / (2.0 * lam)), 0.5 * w * (ZF / np.tanh(lam) + L)
-    X, Z, a11, a12, a22, ct = _eval(H, V, L, EA, w, seabed, seed)
-    eX, eZ = X - XF, Z - ZF
-    res, a, it = max(abs(eX), abs(eZ)) / L, 1.0, 0
-    conv = res == 0.0
-    while not conv and it < MAX_IT:
-        it += 1
-        det = a11 * a22 - a12 * a12
-        dH, dV = -(a22 * eX - a12 * eZ) / det, -(a11 * eZ - a12 * eX) / det
-        s = a
-        if H + s * dH <= 0.0:
-            s = -0.5 * H / dH
-        Ht, Vt = H + s * dH, V + s * dV
-        nx = _eval(Ht, Vt, L, EA, w, seabed, seed)
-        nX, nZ = nx[0] - XF, nx[1] - ZF
-        rn = max(abs(nX), abs(nZ)) / L
-        if rn < res:
-            H, V, eX, eZ, res, a = Ht, Vt, nX, nZ, rn, 1.0
-            X, Z, a11, a12, a22, ct = nx
-            conv = res == 0.0
-        elif res <= TIGHT:
-            conv = True
-        else:
-            a *= 0.5
-            if a < 2.0 ** -40:
-                break
+    conv, H, V, it, (_, _, a11, a12, a22, ct) = newton(lambda H, V: _eval(H, V, L, EA, w, seabed, seed), L, w, XF, ZF)
     if not conv:
         return 8, None
-    det = a11 * a22 - a12 * a12
-    k11, k12, k22 = a22 / det, -a12 / det, a11 / det
+    m = end(H, V, a11, a12, a22, ux, uy, XF)
     VA = 0.0 if ct else V - w * L
     TB, TA = np.sqrt(H * H + V * V), np.sqrt(H * H + VA * VA)
-    th = H / XF
-    K = np.array([[k11 * ux * ux + th * (1.0 - ux * ux), k11 * ux * uy - th * (ux * uy), k12 * ux],
-                  [k11 * ux * uy - th * (ux * uy), k11 * uy * uy + th * (1.0 - uy * uy), k12 * uy],
-                  [k12 * ux, k12 * uy, k22]])
-    gAX, gAZ = (H * k11 + VA * k12) / TA, (H * k12 + VA * k22) / TA
-    gBX, gBZ = (H * k11 + V * k12) / TB, (H * k12 + V * k22) / TB
-    return 0, dict(f=np.array([-H * ux, -H * uy, -V]), r=r, K=K, gA=np.array([gAX * ux, gAX * uy, gAZ]),
-                   gB=np.array([gBX * ux, gBX * uy, gBZ]), TA=TA, TB=TB,
+    return 0, dict(f=np.array([-H * ux, -H * uy, -V]), r=r, K=m["K"], gA=end_grad(m, VA, TA), gB=end_grad(m, V, TB), TA=TA, TB=TB,
                    lo=np.array([H, V, H, VA, L - V / w if ct else 0.0, it, ct, 0.0]))
 
 
