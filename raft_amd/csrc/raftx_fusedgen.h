@@ -64,4 +64,4 @@ __device__ __forceinline__ void fusedgen_publish() {
         solve_pair<NB, FLAGS, MAXT, true>(PG.P.T, PG.P.A, idx, PG.P.xl_base + blockIdx.x);                              \
         RAFTX_KP_REENTER(NAME);                                                                                         \
     }
-RAFTX_KPG_DEFINE(raftx_kpg_f0, 2, 0, 128, RAFTX_KP_MINB)
+RAFTX_KPG_DEFINE(raftx_kpg_f0, 2, 0, 128, MINB_2X128)

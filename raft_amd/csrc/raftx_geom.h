@@ -1362,9 +1362,7 @@ __device__ unsigned long long geom_phase_cycles[10];
 #define GEOM_PHASE(i)
 #define GEOM_PHASE_BEGIN
 #endif
-#ifndef GD_T
 #define GD_T 128            // threads per design: two wavefronts share the candidate strips and the output loops
-#endif
 static_assert(GD_T % 64 == 0 && GD_T % DS_N == 0 && GD_T <= 256, "k_geom_design: whole wavefronts, a lane keeps its record field");
 // The tables of design d, by the GD_T threads of the calling workgroup: the body of k_geom_design, and the prologue of the
 // fused fixed point's generating form (raftx_fusedgen.h), where the workgroup that has claimed a pair builds its design's

@@ -231,10 +231,8 @@ __global__ void __launch_bounds__(256) k_solve_system(int nSys, int nUnit, int n
 // per unit instead of 36 x nw complex per pair: the fixed points then need not export Z at all (a farm sweep of 200 000
 // pairs writes and re-reads 23 GB of it) and run as the LEAN kernel with the excitation export (KF_OUTF).
 template <int NU, int NR, bool RESIDENT, bool ASM = false>          // NR: right-hand sides compiled in (nRhs <= NR; the rest are zero columns)
-#ifndef RAFTX_SYSROWS_WAVES
-#define RAFTX_SYSROWS_WAVES 2     // waves per SIMD the register allocation aims at (tuning builds: 3, 4)
-#endif
-__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(RAFTX_SYSROWS_WAVES, RAFTX_SYSROWS_WAVES))) k_solve_system_rows(int nSys, int nRhs, int nw, int nCase, const double *__restrict__ w,
+// amdgpu_waves_per_eu(2, 2): the waves per SIMD the register allocation aims at
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) k_solve_system_rows(int nSys, int nRhs, int nw, int nCase, const double *__restrict__ w,
                                                           const cplx *__restrict__ Zblk, const double *__restrict__ Mc,
                                                           const double *__restrict__ Bc, const double *__restrict__ Cc,
                                                           const cplx *__restrict__ F, cplx *__restrict__ Xi,
@@ -326,10 +324,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(RAFTX_S
         const int p = 31 - (int)((half ? l1 : l0) & 31u);
         const bool mine = todo && r == p;
         const bool upd = todo && r != p;
-#ifndef RAFTX_SYSROWS_EXP
-#define RAFTX_SYSROWS_EXP 0       // timing experiments (wrong results): 1 = no pivot-row stores, 2 = neither stores nor loads
-#endif
-        if (mine && RAFTX_SYSROWS_EXP == 0) {
+        if (mine) {
 #pragma unroll
             for (int c = k; c < N; c++) rowbuf[c] = a[c];
 #pragma unroll
@@ -337,12 +332,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(RAFTX_S
                 rowbuf[N + j] = bR[j];
         }
         wave_lds_fence();
-#if RAFTX_SYSROWS_EXP == 2
-#define ROWBUF_(c) (cplx{a[(c) < N ? (c) : 0].im + 1.0, a[(c) < N ? (c) : 0].re})
-#else
-#define ROWBUF_(c) rowbuf[c]
-#endif
-        const cplx pv = ROWBUF_(k);
+        const cplx pv = rowbuf[k];
         // 1 / |pivot|^2: v_rcp_f64 + two Newton steps (5 instructions; the IEEE division sequence is ~15).  A zero pivot still
         // ends in NaN.
         const double pp = pv.re * pv.re + pv.im * pv.im;
@@ -355,16 +345,15 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(RAFTX_S
         const cplx l = {upd ? lk.re : 0.0, upd ? lk.im : 0.0};
 #pragma unroll
         for (int c = k + 1; c < N; c++) {
-            const cplx u = ROWBUF_(c);
+            const cplx u = rowbuf[c];
             a[c] = cfnma(a[c], l, u);                     // four FMAs (as a difference of a product: six instructions)
         }
 #pragma unroll
         for (int j = 0; j < NR; j++)
         {
-            const cplx u = ROWBUF_(N + j);
+            const cplx u = rowbuf[N + j];
             bR[j] = cfnma(bR[j], l, u);
         }
-#undef ROWBUF_
         if (mine) {
             todo = false;
             mystep = k;
@@ -400,8 +389,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(RAFTX_S
     }
 }
 static bool solve_system_rows_ok(int nUnit, int nRhs) {
-    static const char *off = getenv("RAFTX_SYSTEM_LDS");                 // tuning / tests: keep the LDS-resident kernel
-    return !(off && atoi(off)) && nUnit >= 2 && nUnit <= 5 && nRhs >= 1 && nRhs <= SYSROWS_MAXRHS;
+    return nUnit >= 2 && nUnit <= 5 && nRhs >= 1 && nRhs <= SYSROWS_MAXRHS;
 }
 // launches the register-resident kernel; returns false if this shape has none
 template <bool RESIDENT, bool ASM = false>
@@ -1250,9 +1238,7 @@ static int check_source(raftx_ctx *c, const BuildSource &B, int nDesign, const c
     return 0;
 }
 static void launch_scan(hipStream_t st, const GeomArgs &A) {
-    static const int scan_t = getenv("RAFTX_SCAN_T") ? atoi(getenv("RAFTX_SCAN_T")) : 1024;     // tuning: 256 | 1024 threads
-    if (scan_t == 256) hipLaunchKernelGGL(k_geom_scan_t<256>, dim3(1), dim3(256), 0, st, A);
-    else hipLaunchKernelGGL(k_geom_scan_t<1024>, dim3(1), dim3(1024), 0, st, A);
+    hipLaunchKernelGGL(k_geom_scan_t<1024>, dim3(1), dim3(1024), 0, st, A);
 }
 // Designs [lo, lo + nDesign) of a source: their members [m0, m1), stations [s0, s1) and caps [c0, c1) in the batch's arrays.
 struct Slice { int lo; int64_t m0, m1, s0, s1, c0, c1; };
@@ -1726,10 +1712,7 @@ extern "C" int raftx_upload_cases(raftx_ctx *c, int nCase, int nHead, int nw, co
 struct Shape {
     int nb, threads;
 };
-#ifndef RAFTX_MINB128
-#define RAFTX_MINB128 2          // waves per SIMD the default 200-bin shape is compiled for (tuning builds override)
-#endif
-#define SHAPES(X) X(1, 64, 1) X(2, 64, 1) X(4, 64, 1) X(2, 128, RAFTX_MINB128) X(1, 256, 2) X(2, 256, 2) X(2, 512, 1) X(3, 512, 1) X(4, 512, 1)
+#define SHAPES(X) X(1, 64, 1) X(2, 64, 1) X(4, 64, 1) X(2, 128, MINB_2X128) X(1, 256, 2) X(2, 256, 2) X(2, 512, 1) X(3, 512, 1) X(4, 512, 1)
 // (NB, MAXT, MINB) of every instantiated kernel: MAXT is the shape's threads, MINB the waves per SIMD it is compiled for
 static bool shape_ok(Shape sh, int nw) {
 #define X(NB_, MT_, MB_) if (sh.nb == NB_ && sh.threads == MT_) return (long)NB_ * MT_ >= nw;
@@ -2002,14 +1985,10 @@ __global__ void k_iota(int n, int *__restrict__ out) {
 // ---- persistent fused launches (raftx_kernels.h: raftx_kp_f<FLAGS>)
 typedef void (*kp_fn)(PersistArgs);
 static kp_fn kp_kernel(int flags) {
-#ifdef RAFTX_KP_ONLY
-    return flags == 0 ? raftx_kp_f0 : nullptr;
-#else
 #define X(F) if (flags == F) return raftx_kp_f##F;
     RAFTX_PERSIST128(X)
 #undef X
     return nullptr;
-#endif
 }
 #define KP_RING 64
 #define KP_MAX_GRID 2048                 // workgroups of a persistent grid at most (8 per CU x 256 CUs)
@@ -2062,10 +2041,10 @@ static bool solve_kernel(Shape sh, int flags, SolveKernel *out) {
 #define ENTRY_(NB_, FL_, MT_, MB_)                                                                                      \
     {                                                                                                                   \
         *out = {k_solve_dynamics<NB_, FL_, MT_, MB_>, MB_,                                                              \
-                (NB_ == 2 && MT_ == 128 && MB_ == RAFTX_KP_MINB) ? kp_kernel(FL_) : nullptr};                           \
+                (NB_ == 2 && MT_ == 128 && MB_ == MINB_2X128) ? kp_kernel(FL_) : nullptr};                              \
         return true;                                                                                                    \
     }
-#define LEAN_(F) if (flags == (F)) ENTRY_(2, (F), 128, RAFTX_MINB128)
+#define LEAN_(F) if (flags == (F)) ENTRY_(2, (F), 128, MINB_2X128)
 #define X(NB_, MT_, MB_)                                                                                                \
     if (sh.nb == NB_ && sh.threads == MT_) {                                                                            \
         if (flags == KF_ALL) ENTRY_(NB_, KF_ALL, MT_, 1)                                                                \
@@ -2099,8 +2078,7 @@ struct LaunchPlan {
     // the run-start cache (raftx_kernels.h Kin): as many 16-byte-per-bin slots as fit without costing a resident pair.
     int rc_slots(int S) const {
         if (!rc_shape) return 0;
-        static const char *env = getenv("RAFTX_RC_SLOTS");                 // tuning: cap (0 = no cache)
-        const int cap = env ? atoi(env) : 24;
+        const int cap = 24;
         const size_t base = lds(S, 0);
         const size_t budget = LDS_LIMIT / (size_t)wg_per_cu - (persist ? KP_STASH * sizeof(double) : 0);
         if (budget <= base) return 0;
@@ -2136,12 +2114,11 @@ static int make_plan(raftx_ctx *c, SolveArgs *A, LaunchPlan *lp) {
     if (!solve_kernel(sh, lean >= 0 ? lean : KF_ALL, &lp->k)) NO_KERNEL(c, sh);
     c->last_flags = lean >= 0 ? lean : KF_ALL;
     c->last_minb = lp->k.minb;
-    static const int wgcu_env = getenv("RAFTX_WG_PER_CU") ? atoi(getenv("RAFTX_WG_PER_CU")) : 0;     // tuning: pairs per CU the LDS is budgeted for
-    lp->wg_per_cu = wgcu_env > 0 ? wgcu_env : std::max(1, lp->k.minb * 4 / (sh.threads / 64));
+    lp->wg_per_cu = std::max(1, lp->k.minb * 4 / (sh.threads / 64));
     // the persistent form (raftx_kernels.h k_solve_dynamics_p / raftx_kp_f*): lean 200-bin launches of one LDS class that
     // are not cut into slabs; RAFTX_PERSIST=0 keeps the one-workgroup-per-pair launches (A/B, tuning)
     static const bool persist_env = !(getenv("RAFTX_PERSIST") && !atoi(getenv("RAFTX_PERSIST")));
-    lp->persist = persist_env && lp->rc_shape && lean >= 0 && (lp->xlg || RAFTX_XL_LDS);
+    lp->persist = persist_env && lp->rc_shape && lean >= 0 && lp->xlg;
     if (!lp->persist) lp->k.kp = nullptr;
     A->rc_n = c->last_rc = lp->rc_slots(c->maxS);
     return 0;
@@ -2151,11 +2128,7 @@ static int make_plan(raftx_ctx *c, SolveArgs *A, LaunchPlan *lp) {
 // bits are cleared once -- every workgroup returns its slot
 static int ensure_xl_scratch(raftx_ctx *c, const LaunchPlan &lp) {
     if (!lp.xlg) return 0;
-#ifdef RAFTX_XL_PER_PAIR
-    const size_t xl_regions = std::max<size_t>(XL_SLOTS, c->r_npair);
-#else
     const size_t xl_regions = XL_SLOTS + KP_MAX_GRID;      // the slot pool + one region per workgroup of a persistent grid
-#endif
     const size_t want = xl_regions * 12 * (size_t)lp.nw;
     // (the whole device: fused kernels of the other streams may hold slots of the old slab)
     if (grow_device(c, c->rXl, want, DRAIN_DEVICE)) return -2;
@@ -2570,8 +2543,7 @@ extern "C" int raftx_solve_system(raftx_ctx *c, int nSys, int nUnit, int nRhs, i
 // launch of the dense solves of nSys systems x nw bins on device arrays: the register-resident kernel where the augmented
 // matrix fits its grid (the flexible deck: 150 + 1), the L2-workspace kernel otherwise.  Matrix set of system s: s / mdiv.
 static bool dense_reg_shape(int n, int nRhs) {
-    static const bool dense_l2 = getenv("RAFTX_DENSE_L2") && atoi(getenv("RAFTX_DENSE_L2"));     // tuning / tests: the L2-workspace kernel
-    return !dense_l2 && n + nRhs <= 160;
+    return n + nRhs <= 160;
 }
 // size of the L2-workspace kernel's block A, in elements: 0 where the register kernel takes the shape
 static size_t dense_workspace(int nSys, int n, int nRhs, int nw) {
@@ -2996,8 +2968,7 @@ static int qtf_slender_impl(raftx_ctx *c, int nSet, int nw2, const double *w2, c
         hipLaunchKernelGGL(k_qtf_tables, dim3((unsigned)(nStrip + nMem + nSet)), dim3(nw2 > 128 ? 256 : 128), 0, c->stream, A,
                            (int)nStrip, (int)nMem);
         if (A.nrow) {
-            static const int blk_env = getenv("RAFTX_QTF_BLOCK") ? atoi(getenv("RAFTX_QTF_BLOCK")) : 0;      // tuning: 64 | 128
-            const int blk = (blk_env == 64 || blk_env == 128) ? blk_env : (nw2 > 64 ? 128 : 64);
+            const int blk = nw2 > 64 ? 128 : 64;
             const size_t per_xcd = ((size_t)nSet * A.nrow + 7) / 8;                 // see k_qtf_pairs: a slab of the (set, row) list per XCD
             hipLaunchKernelGGL(k_qtf_pairs, dim3((unsigned)(per_xcd * 8)), dim3(blk), 0, c->stream, A);
         }
@@ -3095,31 +3066,17 @@ static int block_ctx(raftx_ctx *c, int slot, size_t i, raftx_ctx **out) {
     *out = W[i];
     return 0;
 }
-// block sizes: RAFTX_SWEEP_SPLIT="f0,f1,..." (fractions, tuning) | nChunk equal blocks | default: ONE block when the other slot
+// block sizes: nChunk equal blocks | default: ONE block when the other slot
 // has a crossing in flight (streamed batches: that crossing's kernels hide this one's upload), otherwise a small first block
 // whose kernels hide the descriptor upload of the rest (every further block costs a partial last residency round of the
 // fused kernel plus the fixed latencies of the generation kernels: two blocks measured best, also for a crossing that
 // downloads its responses -- profiles/MEASUREMENT_HISTORY.md, "Closed scheduling experiments of the crossing")
 static std::vector<int> sweep_bounds(int nDesign, long pairs, int nChunk, bool pipelined) {
     std::vector<double> fr;
-    static const char *env = getenv("RAFTX_SWEEP_SPLIT");
-    if (env && nChunk <= 0) {
-        const char *p = env;
-        while (*p) {
-            char *e = nullptr;
-            const double v = strtod(p, &e);
-            if (e == p) break;
-            if (v > 0) fr.push_back(v);
-            p = (*e == ',') ? e + 1 : e;
-            if (*e != ',') break;
-        }
-    }
-    if (fr.empty()) {
-        if (nChunk > 0) fr.assign((size_t)nChunk, 1.0);
-        else if (pipelined) fr = {1.0};              // the crossing in the other slot hides this one's upload: one launch, no extra tail
-        else if (pairs >= 3072) fr = {0.2, 0.8};     // measured on MI355X at 10 k pairs (profiles/r02_crossing_splits.txt)
-        else fr = {1.0};
-    }
+    if (nChunk > 0) fr.assign((size_t)nChunk, 1.0);
+    else if (pipelined) fr = {1.0};              // the crossing in the other slot hides this one's upload: one launch, no extra tail
+    else if (pairs >= 3072) fr = {0.2, 0.8};     // measured on MI355X at 10 k pairs (profiles/r02_crossing_splits.txt)
+    else fr = {1.0};
     double tot = 0;
     for (double v : fr) tot += v;
     std::vector<int> b{0};

@@ -186,13 +186,10 @@ __device__ __forceinline__ int pair_of_block(int b, int npair) {
 static inline unsigned grid_for_pairs(size_t npair) { return (unsigned)(((npair + 7) / 8) * 8); }
 
 // ------------------------------------------------------------------ LDS layout
-#ifndef RAFTX_RUN_LOOPS
-#define RAFTX_RUN_LOOPS 1    // sweeps iterate over runs with run-type-specialised inner loops (0: one flag-switched loop over strips)
-#endif
-// ... for the shapes with up to two bins per lane; the larger ones (more than 1024 bins) keep the single loop, whose
-// register footprint is smaller there
+// Sweeps iterate over runs with run-type-specialised inner loops for the shapes with up to two bins per lane; the larger
+// ones (more than 1024 bins) keep the single flag-switched loop over strips, whose register footprint is smaller there
 template <int NB>
-constexpr bool RUN_LOOPS = RAFTX_RUN_LOOPS && NB <= 2;
+constexpr bool RUN_LOOPS = NB <= 2;
 #define RA_N 18              // doubles per staged record: arm, q, p1, p2 (pass A) + x, y, z, unit step (run starts)
 #define TR_ROWS 6            // rows of a reduction tile (pass A: 2 strips x 3 sums per batch)
 #define TR_STRIDE 72         // doubles per row (8 segments of 9: conflict-free)
@@ -273,10 +270,7 @@ __device__ __forceinline__ ldptr vsq_of(const Lds &l, int wv, int nwv, int S, in
 // shapes that keep XiLast in global scratch (SolveArgs::Xl, a region per RUNNING workgroup: xl_slot_acquire) instead of LDS: the largest ones (no room), and the
 // two-waves-per-SIMD 200-bin shape, whose LDS goes to the run-start cache instead (XiLast is touched twice per
 // iteration, the run starts fourteen times)
-#ifndef RAFTX_XL_LDS
-#define RAFTX_XL_LDS 0       // tuning build (profiles/r06_xilast_ab.json): 1 = the 200-bin shape keeps XiLast in LDS too (three pairs per CU)
-#endif
-static __host__ __device__ constexpr bool xl_global(int nb, int maxt) { return (maxt == 512 && nb >= 3) || (!RAFTX_XL_LDS && maxt == 128 && nb == 2); }
+static __host__ __device__ constexpr bool xl_global(int nb, int maxt) { return (maxt == 512 && nb >= 3) || (maxt == 128 && nb == 2); }
 
 // LDS traffic between lanes of ONE wave needs no s_barrier (a wave's LDS instructions
 // execute in order); it only needs the compiler to keep the order.
@@ -367,21 +361,15 @@ __device__ __forceinline__ void set_heading_amp(const DevTables &T, Bins<NB> &b,
 // (helpers.py:211-218): 2 = k == 0, 1 = deep water (k h > 89.4), 0 = finite depth
 __device__ __forceinline__ int depth_mode(double k, double depth) { return k == 0.0 ? 2 : (k * depth > 89.4 ? 1 : 0); }
 
-// RAFTX_UNIT_ROTORS: keep the rotors of ONE unit step only and apply them twice for a two-unit step -- no more
+// The rotors of ONE unit step only are kept and applied twice for a two-unit step -- no more
 // instructions than choosing between two rotor sets per step with selects, and 16 VGPRs less at two bins per lane
-#ifndef RAFTX_UNIT_ROTORS
-#define RAFTX_UNIT_ROTORS 1
-#endif
 // ------------------------------------------------------------------ wave kinematics along a run
 // State per bin: a = amp * e^{-i k xi_s};  P = e^{k z_s};  Q = e^{-k (z_s + 2h)}  (Q = 0 in the
-// deep-water branch, helpers.py:215-218, unless KEEPQ);  rotors of one and of two unit steps.
+// deep-water branch, helpers.py:215-218, unless KEEPQ);  rotors of one unit step.
 template <int NB>
 struct Kin {
     double ar[NB], ai[NB], P[NB], Q[NB];
     double r1r[NB], r1i[NB], r1p[NB], r1q[NB];
-#if !RAFTX_UNIT_ROTORS
-    double r2r[NB], r2i[NB], r2p[NB], r2q[NB];
-#endif
     // memo of the previous run start (wave-uniform keys, per-bin values): members that start at
     // the same depth share P, Q; members with the same step vector share the rotors
     double P0[NB], Q0[NB];
@@ -537,12 +525,6 @@ __device__ __forceinline__ void kin_start(Kin<NB> &K, const RunStart rs, const B
             K.r1i[j] = s[j];
             K.r1p[j] = pp[j];
             K.r1q[j] = qq[j];
-#if !RAFTX_UNIT_ROTORS
-            K.r2r[j] = c[j] * c[j] - s[j] * s[j];
-            K.r2i[j] = 2.0 * c[j] * s[j];
-            K.r2p[j] = pp[j] * pp[j];
-            K.r2q[j] = qq[j] * qq[j];
-#endif
         }
     }
 }
@@ -561,19 +543,8 @@ __device__ __forceinline__ void kin_step1(Kin<NB> &K) {
 }
 template <int NB>
 __device__ __forceinline__ void kin_step2(Kin<NB> &K) {
-#if RAFTX_UNIT_ROTORS
     kin_step1(K);
     kin_step1(K);
-#else
-#pragma unroll
-    for (int j = 0; j < NB; j++) {
-        const double t = K.ar[j] * K.r2r[j] - K.ai[j] * K.r2i[j];
-        K.ai[j] = K.ar[j] * K.r2i[j] + K.ai[j] * K.r2r[j];
-        K.ar[j] = t;
-        K.P[j] *= K.r2p[j];
-        K.Q[j] *= K.r2q[j];
-    }
-#endif
 }
 // advance to the strip described by (fl, rec) -- wave-uniform control flow; rec is either the
 // global device record (scalar loads) or the staged LDS record
@@ -596,10 +567,6 @@ __device__ __forceinline__ void kin_reset(Kin<NB> &K) {
         K.ar[j] = 0.0; K.ai[j] = 0.0; K.P[j] = 1.0; K.Q[j] = 0.0;
         K.r1r[j] = K.r1p[j] = K.r1q[j] = 1.0;
         K.r1i[j] = 0.0;
-#if !RAFTX_UNIT_ROTORS
-        K.r2r[j] = K.r2p[j] = K.r2q[j] = 1.0;
-        K.r2i[j] = 0.0;
-#endif
         K.P0[j] = 1.0;
         K.Q0[j] = 0.0;
     }
@@ -754,14 +721,8 @@ __device__ __forceinline__ void inertial_excitation(const DevTables &T, cdptr ds
 //                  run-start fields keep coming through scalar loads, whose latency the kinematics update covers.
 //                  Four pairs per CU leave no LDS for more.
 //   0              larger shapes: scalar loads only
-#ifndef RAFTX_STAGE256
-#define RAFTX_STAGE256 0
-#endif
-#ifndef RAFTX_STAGE128
-#define RAFTX_STAGE128 6     // (0, all through scalar loads, measured at the round-3 kernel: 3.63 ms against 3.33)
-#endif
 static __host__ __device__ constexpr int stage_policy(int nb, int maxt) {
-    return maxt == 64 ? RA_N : (maxt == 128 ? RAFTX_STAGE128 : ((RAFTX_STAGE256 && maxt == 256 && nb == 1) ? RA_N : 0));
+    return maxt == 64 ? RA_N : (maxt == 128 ? 6 : 0);
 }
 
 // Hot per-strip constants of pass A.  Two sources (template STAGE):
@@ -1021,17 +982,6 @@ __device__ __forceinline__ void kin_decay1(Kin<NB> &K) {
         mul_inplace(K.Q[j], K.r1q[j]);
     }
 }
-#if RAFTX_UNIT_ROTORS
-template <int NB>
-__device__ __forceinline__ void kin_rotate2(Kin<NB> &K) {
-    kin_rotate1(K);
-    kin_rotate1(K);
-}
-template <int NB>
-__device__ __forceinline__ void kin_decay2(Kin<NB> &K) {
-    kin_decay1(K);
-    kin_decay1(K);
-}
 // m = 1 or 2 (wave-uniform): the second application sits in a branch; the tied operands keep the state where it is
 template <int NB>
 __device__ __forceinline__ void kin_rotate(Kin<NB> &K, int m) {
@@ -1043,31 +993,6 @@ __device__ __forceinline__ void kin_decay(Kin<NB> &K, int m) {
     kin_decay1(K);
     if (m == 2) kin_decay1(K);
 }
-#else
-template <int NB>
-__device__ __forceinline__ void kin_rotate2(Kin<NB> &K) {
-#pragma unroll
-    for (int j = 0; j < NB; j++) rot_inplace(K.ar[j], K.ai[j], K.r2r[j], K.r2i[j]);
-}
-template <int NB>
-__device__ __forceinline__ void kin_decay2(Kin<NB> &K) {
-#pragma unroll
-    for (int j = 0; j < NB; j++) {
-        mul_inplace(K.P[j], K.r2p[j]);
-        mul_inplace(K.Q[j], K.r2q[j]);
-    }
-}
-template <int NB>
-__device__ __forceinline__ void kin_rotate(Kin<NB> &K, int m) {
-    if (m == 1) kin_rotate1(K);
-    else kin_rotate2(K);
-}
-template <int NB>
-__device__ __forceinline__ void kin_decay(Kin<NB> &K, int m) {
-    if (m == 1) kin_decay1(K);
-    else kin_decay2(K);
-}
-#endif
 template <int NB, int RT>
 __device__ __forceinline__ void kin_step_rt(Kin<NB> &K, int m) {      // RT 3 = RT 2 with an upright cross-section
     if (RT != 1 && RT != 4) kin_rotate(K, m);
@@ -1633,38 +1558,16 @@ __device__ __forceinline__ void drag_excitation(cdptr ds, ciptr dsi, int S, cons
     // compiler keeps the stepped state in temporaries beside the live one and copies it back on every trip).
     int s = 0;
     int fl = src.flags(min(1, S - 1));              // flags of strip 0; strip 1's are on their way
-    // The interior of a member steps by two units, its end strips by one: the two-unit steps get a loop of their own, so that
-    // no trip chooses between rotor sets (as selects, or as two arms whose results the compiler then copies together).
-#ifndef RAFTX_SPLIT_MASK
-#define RAFTX_SPLIT_MASK 0      // which pass-B run loops get the separate two-unit loop: 1 vertical, 2 upright pontoon, 4 horizontal, 8 inclined
-#endif
-#define RUN_LOOP(WHICH, STEP1, STEP2, STEPM, PRE)      \
+    // The interior of a member steps by two units, its end strips by one: STEPM takes the step count m_ of the trip.
+#define RUN_LOOP(STEPM, PRE)                           \
     do {                                               \
         body();                                        \
         int m_ = next_step();                          \
-        if constexpr ((RAFTX_SPLIT_MASK & (WHICH)) != 0) { \
-        _Pragma("unroll 1") while (m_ != 0) {          \
-            if (m_ == 2) {                             \
-                _Pragma("unroll 1") do {               \
-                    PRE;                               \
-                    STEP2;                             \
-                    body();                            \
-                    m_ = next_step();                  \
-                } while (m_ == 2);                     \
-            } else {                                   \
-                PRE;                                   \
-                STEP1;                                 \
-                body();                                \
-                m_ = next_step();                      \
-            }                                          \
-        }                                              \
-        } else {                                       \
         _Pragma("unroll 1") while (m_ != 0) {          \
             PRE;                                       \
             STEPM;                                     \
             body();                                    \
             m_ = next_step();                          \
-        }                                              \
         }                                              \
     } while (0)
     // As in pass A: the flags of the strips after s come as one vector load per run (lane i: strip s + 1 + i), a ballot gives
@@ -2004,7 +1907,7 @@ __device__ __forceinline__ void inertial_excitation_uv(const DevTables &T, cdptr
             kin_start<NB, true, RC ? 1 : 0>(K, run_start_of(rec0), b, one, cb, sb);
             if (MCF && rec0[DS_MCF] >= 0.0) {                       // a run is one member: MacCamy-Fuchs or not as a whole
                 auto body = [&]() { mcf_strip(s); };
-                RUN_LOOP(8, (kin_rotate1(K), kin_decay1(K)), (kin_rotate2(K), kin_decay2(K)), (kin_rotate(K, m_), kin_decay(K, m_)), );
+                RUN_LOOP((kin_rotate(K, m_), kin_decay(K, m_)), );
             } else if (!K.rot && (fl & DSI_VAX)) {
                 double G0[NB], G1[NB], G3[NB], G4[NB], Z2[NB];
 #pragma unroll
@@ -2028,7 +1931,7 @@ __device__ __forceinline__ void inertial_excitation_uv(const DevTables &T, cdptr
                     }
                 };
                 const Dec2<NB> D2 = dec2_of(K);
-                RUN_LOOP(1, kin_decay1(K), kin_decay2(K), kin_decay_m(K, D2, m_), );
+                RUN_LOOP(kin_decay_m(K, D2, m_), );
 #pragma unroll
                 for (int j = 0; j < NB; j++) {
                     const double ar = K.ar[j], ai = K.ai[j];
@@ -2074,7 +1977,7 @@ __device__ __forceinline__ void inertial_excitation_uv(const DevTables &T, cdptr
                     }
                 };
                 const Rot2<NB> R2 = rot2_of(K);
-                RUN_LOOP(2, kin_rotate1(K), kin_rotate2(K), kin_rotate_m(K, R2, m_), );
+                RUN_LOOP(kin_rotate_m(K, R2, m_), );
                 const double c3q = -az * qy, c3p = -az * p2y, c4q = az * qx, c4p = az * p2x;
 #pragma unroll
                 for (int j = 0; j < NB; j++) {
@@ -2103,7 +2006,7 @@ __device__ __forceinline__ void inertial_excitation_uv(const DevTables &T, cdptr
                 }
             } else {
                 auto body = [&]() { general_strip(s); };
-                RUN_LOOP(8, (kin_rotate1(K), kin_decay1(K)), (kin_rotate2(K), kin_decay2(K)), (kin_rotate(K, m_), kin_decay(K, m_)), );
+                RUN_LOOP((kin_rotate(K, m_), kin_decay(K, m_)), );
             }
         }
     }
@@ -2212,10 +2115,7 @@ __device__ __forceinline__ void solve6(Lu6 &A, cplx x[6]) {
 #define KF_XLIO 64   // linearisation point given (restart) / exported (raft_model.py:1108-1131 re-entry)
 #define KF_ALL 127
 
-#ifndef RAFTX_EQ_ORDER
-#define RAFTX_EQ_ORDER 4, 3, 2, 1, 0, 5
-#endif
-__device__ constexpr int EQ_ORDER[6] = {RAFTX_EQ_ORDER};
+__device__ constexpr int EQ_ORDER[6] = {4, 3, 2, 1, 0, 5};
 
 // Assemble and solve one bin's 6x6 system: x <- Z^-1 x  (raft_model.py:1086-1089)
 // Frequency-dependent added mass / damping of a design, [2][36][nw] doubles, as a raw buffer: entry e of bin iw is one
@@ -2678,16 +2578,12 @@ __device__ __forceinline__ void solve_pair(const DevTables &T, const SolveArgs &
     constexpr int STAGE = stage_policy(NB, MAXT);
     constexpr bool XLG = xl_global(NB, MAXT);
     constexpr int PARK = park_policy(NB, MAXT);
-    constexpr bool RC = PARK != 0 && (XLG || RAFTX_XL_LDS);   // the shape whose spare LDS is a run-start cache (A.rc_n slots)
+    constexpr bool RC = PARK != 0 && XLG;                     // the shape whose spare LDS is a run-start cache (A.rc_n slots)
     Lds l = carve(smem + (PERSIST ? KP_STASH : 0), S, XLG ? 0 : nw, blockDim.x >> 6, STAGE, PARK, RC ? A.rc_n : 0, RC ? nw : 0);
     XlStore<XLG> xl;
     if constexpr (XLG) {
-#ifdef RAFTX_XL_PER_PAIR                                   // tuning build: round 1-4's form, a region per pair
-        xl.p = A.Xl + (size_t)pair * 12 * nw;
-#else
         if constexpr (PERSIST) xl.p = A.Xl + (size_t)xslot * 12 * nw;
         else xl.p = A.Xl + (size_t)xl_slot_acquire(A.slots, smem) * 12 * nw;  // before anything is staged in LDS
-#endif
         xl.n = nw;
     }
     if (STAGE) stage_recA(p.ds, p.dsi, S, l, STAGE);
@@ -2752,7 +2648,7 @@ __device__ __forceinline__ void solve_pair(const DevTables &T, const SolveArgs &
     // follow the second solve -- one round trip to the slab per iteration, its 24 loads in flight together while
     // the registers of the 6x6 systems are dead -- and w * XiLast of the next linearisation stays in registers (Xc)
     // instead of being fetched again at the top of the loop.
-    constexpr bool DEFER = PARK != 0 && (XLG || RAFTX_XL_LDS);
+    constexpr bool DEFER = PARK != 0 && XLG;
     cplx Xc[DEFER ? NB : 1][6];
     if constexpr (DEFER) {
 #pragma unroll
@@ -2942,9 +2838,7 @@ __device__ __forceinline__ void solve_pair(const DevTables &T, const SolveArgs &
         iiter++;
         wg_sync(multi);
     }
-#ifndef RAFTX_XL_PER_PAIR
     if constexpr (XLG && !PERSIST) xl_slot_release(A.slots, (unsigned)((size_t)(xl.p - A.Xl) / ((size_t)12 * nw)));    // XiLast is dead from here on
-#endif
 
     // remaining headings: same impedance, same linearised coefficients (:1200-1236)
     if constexpr (MULTI) {
@@ -3138,13 +3032,9 @@ __device__ __forceinline__ int claim_pair(unsigned *ctr, int nl, LDS_AS int *mai
         solve_pair<NB, FLAGS, MAXT, true>(P.T, P.A, idx, P.xl_base + blockIdx.x);                                       \
         RAFTX_KP_REENTER(NAME);                                                                                         \
     }
-#ifndef RAFTX_KP_MINB
-#define RAFTX_KP_MINB 2
-#endif
-#define X(F) RAFTX_KP_DEFINE(raftx_kp_f##F, 2, F, 128, RAFTX_KP_MINB)
-#ifdef RAFTX_KP_ONLY          // screening builds: one specialisation
-X(0)
-#else
+// Waves per SIMD the 200-bin shape (2 x 128) is compiled for: the per-pair kernel and its persistent twins alike -- a
+// twin stands in for the per-pair kernel it pairs with, so both must be compiled for the same occupancy.
+#define MINB_2X128 2
+#define X(F) RAFTX_KP_DEFINE(raftx_kp_f##F, 2, F, 128, MINB_2X128)
 RAFTX_PERSIST128(X)
-#endif
 #undef X

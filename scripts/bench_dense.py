@@ -17,4 +17,4 @@ for n, nw in ((150, 40), (150, 200), (60, 40)):
         ks.append(ctx.last_kernel_ms())
     Z = -(w[None, None, :] ** 2) * M[:, :, None] + 1j * w[None, None, :] * B[:, :, None] + C[:, :, None]
     res = max(np.abs(Z[:, :, i] @ X[0, :, i] - F[0, :, i]).max() / np.abs(F[0, :, i]).max() for i in range(nw))
-    print("n=%d nw=%d kernel ms %s  residual %.1e  (RAFTX_DENSE_L2=%s)" % (n, nw, ["%.3f" % k for k in ks[2:]], res, os.environ.get("RAFTX_DENSE_L2", "0")))
+    print("n=%d nw=%d kernel ms %s  residual %.1e" % (n, nw, ["%.3f" % k for k in ks[2:]], res))

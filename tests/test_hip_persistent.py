@@ -51,7 +51,7 @@ def child(kind, setting, tmp_path_factory, fused_gen=None):
     if _DEAD:
         pytest.fail("no further child process: " + _DEAD[0])
     env = dict(os.environ)
-    for name in ("RAFTX_KP_GRID", "RAFTX_PERSIST", "RAFTX_FUSED_GEN", "RAFTX_FORCE_ALL", "RAFTX_WG_PER_CU", "RAFTX_RC_SLOTS", "RAFTX_SHAPE"):
+    for name in ("RAFTX_KP_GRID", "RAFTX_PERSIST", "RAFTX_FUSED_GEN", "RAFTX_FORCE_ALL", "RAFTX_SHAPE"):
         env.pop(name, None)
     env.update(SETTINGS[setting])
     if fused_gen is not None:
