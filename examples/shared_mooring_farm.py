@@ -7,8 +7,10 @@ Two units 1600 m apart, each with the deck's three chains (unit 1's turned by 18
 the facing columns.  Per candidate length, all on the device: the farm's mean pose over its 12 DOFs (raftx_array_mean_pose,
 every farm of the sweep in one launch), the coupled 12 x 12 mooring stiffness, the mean tensions and their Jacobian at that pose
 (raftx_array_mooring_lines), and the coupled response of the two units with that stiffness as the farm's coupling matrix
-(Sweep.run_farm(array_mooring=...): the units' hydrodynamics stay linearised at their reference poses).  Printed: the mean
-offsets of both units, the worst line tension as mean + 3 sigma, and the surge-surge coupling C[0,6].
+(Sweep.run_farm(array_mooring=...): the units' hydrodynamics stay linearised at their reference poses), and the natural periods
+of the moored farm over its 12 DOFs at the solved pose (statics.array_modes, include/raftx_array_modal.h).  Printed: the mean
+offsets of both units, the worst line tension as mean + 3 sigma, the surge-surge coupling C[0,6], and the two coupled surge
+periods: the units moving in phase (the shared line rides along) and out of phase (it is stretched).
 
 Runs on the committed fixtures (no reference tree needed)."""
 import json
@@ -66,9 +68,23 @@ def main():
     pose = np.where(ok[:, None, None], res.pose, np.array([[x, y, 0, 0, 0, 0] for x, y in loc])[None])
     out = sweep.run_farm(ctx, 2, array_mooring=dict(lines=lines, pose=np.ascontiguousarray(pose), depth=depth))
     worst = (out["T_mean"][:, None, :] + 3.0 * out["T_std"]).max(axis=(1, 2))
-    print("   L [m]   unit 0 surge  unit 1 surge   worst T (mean + 3 sigma) [N]   C[0,6] [N/m]")
-    for g in np.flatnonzero(ok)[:: max(1, int(ok.sum()) // 8)]:
-        print("%8.1f %12.2f %13.2f %22.4g %21.4g" % (lengths[g], res.pose[g, 0, 0], res.pose[g, 1, 0] - SPACING, worst[g], out["C_moor"][g, 0, 6]))
+    # the coupled surge periods at the solved pose: unit masses = structure + rotor-nacelle assembly + strip-theory added mass
+    st = ctx.fetch_statics()
+    M_unit = (st["M_struc"] + M_rna + st["A_morison"]).reshape(n, 2, 6, 6)
+    t0 = time.perf_counter()
+    modes = statics.array_modes(ctx, M_unit, K_hs.reshape(n, 2, 6, 6), lines, np.ascontiguousarray(pose), depth)
+    t_modes, k_modes = time.perf_counter() - t0, ctx.last_kernel_ms()
+    print("%d farms: 12-DOF eigen analysis at the pose in %.2f ms (kernels %.3f ms), %d flagged"
+          % (n, 1e3 * t_modes, k_modes, (~modes.ok).sum()))
+    T = modes.periods
+    surge = modes.modes[:, [0, 6]][:, :, [0, 6]]                       # surge of both units in the two modes that claimed surge
+    in_phase = surge[:, 0, :] * surge[:, 1, :] > 0                       # [n,2]: per mode, do the units move together?
+    T_in = np.where(in_phase[:, 0], T[:, 0], T[:, 6])
+    T_out = np.where(in_phase[:, 0], T[:, 6], T[:, 0])
+    print("   L [m]   unit 0 surge  unit 1 surge   worst T (mean + 3 sigma) [N]   C[0,6] [N/m]   surge T in phase [s]  out of phase [s]")
+    for g in np.flatnonzero(ok & modes.ok)[:: max(1, int((ok & modes.ok).sum()) // 8)]:
+        print("%8.1f %12.2f %13.2f %22.4g %21.4g %18.2f %17.2f" % (lengths[g], res.pose[g, 0, 0], res.pose[g, 1, 0] - SPACING, worst[g],
+                                                                    out["C_moor"][g, 0, 6], T_in[g], T_out[g]))
 
 
 if __name__ == "__main__":

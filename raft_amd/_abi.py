@@ -60,6 +60,9 @@ ML_LEG, MOOR_MAX_LEG = 14, 3   # leg rows of a bridle: the mark and how many at 
 STATICS_EXPORTS = ("raftx_mean_pose", "raftx_sweep_mean_pose")
 # include/raftx_array_mooring.h: arrays of units with shared lines, the device library only
 ARRAY_MOORING_EXPORTS = ("raftx_array_mooring_lines", "raftx_array_mean_pose")
+# include/raftx_array_modal.h: eigen analysis of moored arrays over all 6 nUnit DOFs, the device library only
+ARRAY_MODAL_EXPORTS = ("raftx_array_modal_batch", "raftx_array_modal_moored")
+ARRAY_MAX_UNIT = 6
 ML_UNIT_B, ML_UNIT_A, ARRAY_MAX_UNIT = 11, 12, 6   # RAFTX_ML_UNIT_B, RAFTX_ML_UNIT_A, RAFTX_ARRAY_MAX_UNIT
 MOOR_BAD_LINE, MOOR_VERTICAL, MOOR_SLACK, MOOR_NO_CONVERGENCE = 1, 2, 4, 8
 MOOR_GROUNDED = 64
@@ -190,6 +193,12 @@ class RaftxLib:
             L.raftx_array_mean_pose.argtypes = [_vp, C.c_int, C.c_int, C.c_int, _vp, C.c_double, _vp, _vp, _vp, _vp, _vp, C.c_int,
                                                 _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]
             L.raftx_array_mean_pose.restype = C.c_int
+        self.has_array_modal = all(hasattr(L, s) for s in ARRAY_MODAL_EXPORTS)
+        if self.has_array_modal:
+            L.raftx_array_modal_batch.argtypes = [_vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp]
+            L.raftx_array_modal_batch.restype = C.c_int
+            L.raftx_array_modal_moored.argtypes = [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_double, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]
+            L.raftx_array_modal_moored.restype = C.c_int
         self.has_current = all(hasattr(L, s) for s in CURRENT_EXPORTS)
         if self.has_current:
             L.raftx_current_loads.argtypes = [_vp, C.c_int, _vp, _vp, _vp, C.c_double, C.c_double, _vp]
@@ -896,6 +905,51 @@ class Context:
                                             _ptr(out["T"]), _ptr(out["J"]), _ptr(out["F_res"]), _ptr(out["iterations"]),
                                             _ptr(out["flags"])), "raftx_array_mean_pose")
         return {k: v for k, v in out.items() if v is not None}
+
+    # ------------------------------------------------------------- eigen analysis of moored arrays (include/raftx_array_modal.h)
+    def _array_modal_lib(self, what):
+        if not self.rlib.has_array_modal:
+            raise RaftxError("%s: %s does not implement include/raftx_array_modal.h (the device library does)" % (what, self.rlib.path))
+        return self.rlib.lib
+
+    def array_modal_batch(self, M, C_):
+        """Natural frequencies [Hz] and modes of arrays of rigid units over all n = 6 nUnit DOFs (raftx_array_modal_batch):
+        M, C [nA,n,n] summed M_tot / C_tot in (unit-major DOFs); dict(fn [nA,n], modes [nA,n,n] (column j: mode of fn[j]),
+        flags [nA] (MODAL_*))."""
+        L = self._array_modal_lib("array_modal_batch")
+        M, C_ = _f64(M), _f64(C_)
+        if M.ndim != 3 or M.shape[1] != M.shape[2] or M.shape[1] % 6 or M.shape[1] == 0 or C_.shape != M.shape:
+            raise ValueError("M, C have shapes %s, %s, expected [nArray,6 nUnit,6 nUnit]" % (M.shape, C_.shape))
+        nA, n = M.shape[:2]
+        out = dict(fn=np.empty((nA, n)), modes=np.empty((nA, n, n)), flags=np.zeros(nA, dtype=np.int32))
+        self._check(L.raftx_array_modal_batch(self._h, nA, n // 6, _ptr(M), _ptr(C_), _ptr(out["fn"]), _ptr(out["modes"]),
+                                              _ptr(out["flags"])), "raftx_array_modal_batch")
+        return out
+
+    def array_modal_moored(self, M_unit, K_unit, lines, pose, depth, dC=None):
+        """The same on the moored array at the units' poses, composed on the device (raftx_array_modal_moored):
+        C_tot = blockdiag(K_unit) + the array stiffness of ``array_mooring_lines`` (+ dC), M_tot = blockdiag(M_unit).
+        ``M_unit``, ``K_unit`` [nA,nUnit,6,6], ``lines`` [nA,nLine,16] array rows, ``pose`` [nA,nUnit,6], ``dC`` [nA,n,n] or None.
+        dict(fn, modes, flags as ``array_modal_batch``, C [nA,n,n] = C_tot, moor_flags [nA]: an array with a mooring flag is
+        NaN and carries flags = 0)."""
+        L = self._array_modal_lib("array_modal_moored")
+        M_unit = _f64(M_unit)
+        if M_unit.ndim != 4 or M_unit.shape[2:] != (6, 6):
+            raise ValueError("M_unit has shape %s, expected [nArray,nUnit,6,6]" % (M_unit.shape,))
+        nA, nU = M_unit.shape[:2]
+        n = 6 * nU
+        K_unit = _f64(K_unit, (nA, nU, 6, 6), "K_unit")
+        pose = _f64(pose, (nA, nU, 6), "pose")
+        dC = None if dC is None else _f64(dC, (nA, n, n), "dC")
+        lines = self._array_lines(lines)
+        if lines.shape[0] != nA:
+            raise ValueError("lines has shape %s, expected [%d,nLine,%d]" % (lines.shape, nA, ML_N))
+        out = dict(fn=np.empty((nA, n)), modes=np.empty((nA, n, n)), C=np.empty((nA, n, n)), flags=np.zeros(nA, dtype=np.int32),
+                   moor_flags=np.zeros(nA, dtype=np.int32))
+        self._check(L.raftx_array_modal_moored(self._h, nA, nU, lines.shape[1], _ptr(lines), _ptr(pose), float(depth), _ptr(M_unit),
+                                               _ptr(K_unit), _ptr(dC), _ptr(out["fn"]), _ptr(out["modes"]), _ptr(out["C"]),
+                                               _ptr(out["flags"]), _ptr(out["moor_flags"])), "raftx_array_modal_moored")
+        return out
 
     def sweep_mean_pose(self, handle, lines=None, C_extra=None, F_extra=None, F_env=None, tol=None, max_iter=0):
         """Ask for a PREPARED, not yet launched crossing to run at every design's mean pose (raftx_sweep_mean_pose):

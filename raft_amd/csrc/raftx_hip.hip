@@ -49,6 +49,7 @@
 #include "../../include/raftx_mooring.h"
 #include "../../include/raftx_statics.h"
 #include "../../include/raftx_array_mooring.h"
+#include "../../include/raftx_array_modal.h"
 #include "../../include/raftx_launch.h"
 
 // roctx ranges around the phases of the host side: named spans for `rocprofv3 --marker-trace`.
@@ -96,6 +97,7 @@ struct RangeScope {
 #include "raftx_mooring.h"
 #include "raftx_statics.h"
 #include "raftx_array_mooring.h"
+#include "raftx_array_modal.h"
 
 // Coupled array solve (raft_model.py:1164-1236): Xi = Z_sys^-1 F for every (system, bin).  One wavefront per
 // (system, bin), NBIN (1, 2 or 4: what fits LDS) consecutive bins per workgroup so that the loads of one matrix entry
@@ -4775,6 +4777,97 @@ extern "C" int raftx_array_mean_pose(raftx_ctx *c, int nArray, int nUnit, int nL
     if (chains == 2) hipLaunchKernelGGL((k_array_mean_pose<true, true>), grid, dim3(ARR_THREADS), 0, c->stream, A);
     else if (chains) hipLaunchKernelGGL((k_array_mean_pose<true, false>), grid, dim3(ARR_THREADS), 0, c->stream, A);
     else hipLaunchKernelGGL((k_array_mean_pose<false, false>), grid, dim3(ARR_THREADS), 0, c->stream, A);
+    return sc.finish();
+}
+
+// ---- eigen analysis of moored arrays (include/raftx_array_modal.h, raftx_array_modal.h)
+static void launch_array_modal(hipStream_t st, int nUnit, const ArrayModalArgs &A) {
+    const dim3 grid((unsigned)A.n), block(64);
+    switch (nUnit) {
+    case 1: hipLaunchKernelGGL(k_array_modal<6>, grid, block, 0, st, A); break;
+    case 2: hipLaunchKernelGGL(k_array_modal<12>, grid, block, 0, st, A); break;
+    case 3: hipLaunchKernelGGL(k_array_modal<18>, grid, block, 0, st, A); break;
+    case 4: hipLaunchKernelGGL(k_array_modal<24>, grid, block, 0, st, A); break;
+    case 5: hipLaunchKernelGGL(k_array_modal<30>, grid, block, 0, st, A); break;
+    default: hipLaunchKernelGGL(k_array_modal<36>, grid, block, 0, st, A); break;
+    }
+}
+static_assert(RAFTX_ARRAY_MAX_UNIT == 6, "launch_array_modal instantiates k_array_modal for 1 .. 6 units");
+
+extern "C" int raftx_array_modal_batch(raftx_ctx *c, int nArray, int nUnit, const double *M, const double *C, double *fn,
+                                       double *modes, int32_t *flags) {
+    if (!c) return -1;
+    if (nUnit < 1 || nUnit > RAFTX_ARRAY_MAX_UNIT) FAIL(c, "array_modal_batch: nUnit must be 1 to %d (got %d)", RAFTX_ARRAY_MAX_UNIT, nUnit);
+    if (nArray < 0) FAIL(c, "array_modal_batch: nArray must not be negative (got %d)", nArray);
+    if (nArray > 0 && (!M || !C || !fn || !modes || !flags)) FAIL(c, "array_modal_batch: bad arguments");
+    if (nArray == 0) return 0;
+    HIPCHK(c, hipSetDevice(c->device));
+    Scratch sc(c);
+    const size_t na = (size_t)nArray, n = (size_t)6 * nUnit;
+    ArrayModalArgs A;
+    memset(&A, 0, sizeof(A));
+    A.n = nArray;
+    A.M = sc.in<double>(M, na * n * n);
+    A.C = sc.in<double>(C, na * n * n);
+    A.fn = sc.out<double>(fn, na * n);
+    A.modes = sc.out<double>(modes, na * n * n);
+    A.flags = sc.out<int32_t>(flags, na);
+    if (int rc = sc.upload("array_modal_batch")) return rc;
+    if (sc.begin()) return -2;
+    launch_array_modal(c->stream, nUnit, A);
+    return sc.finish();
+}
+
+extern "C" int raftx_array_modal_moored(raftx_ctx *c, int nArray, int nUnit, int nLine, const double *lines, const double *pose,
+                                        double depth, const double *M_unit, const double *K_unit, const double *dC, double *fn,
+                                        double *modes, double *C_out, int32_t *flags, int32_t *moor_flags) {
+    if (!c) return -1;
+    if (nLine < 1) FAIL(c, "array_modal_moored: nLine must be positive (got %d)", nLine);
+    if (nArray < 0) FAIL(c, "array_modal_moored: nArray must not be negative (got %d)", nArray);
+    if (!lines || !pose || !M_unit || !K_unit || !fn || !modes || !flags || !moor_flags)
+        FAIL(c, "array_modal_moored: bad arguments (lines, pose, M_unit, K_unit, fn, modes, flags and moor_flags are required)");
+    if (int rc = check_depth(c, "array_modal_moored", depth)) return rc;
+    int chains = 0;
+    if (int rc = check_array_lines(c, "array_modal_moored", (size_t)nArray, nUnit, nLine, lines, &chains)) return rc;
+    if (nArray == 0) return 0;
+    HIPCHK(c, hipSetDevice(c->device));
+    Scratch sc(c);
+    const size_t na = (size_t)nArray, nl = na * nLine, n = (size_t)6 * nUnit;
+    StagedLines L;
+    if (stage_lines(c, c->stream, sc.bag, na, nLine, lines, nullptr, L)) return -2;
+    ArrayMoorArgs A;                                     // the line kernels of raftx_array_mooring_lines, C alone asked for
+    memset(&A, 0, sizeof(A));
+    A.nArray = nArray; A.nUnit = nUnit; A.nLine = nLine; A.depth = depth;
+    A.lines = L.lines;
+    A.pose = sc.in<double>(pose, na * n);
+    A.lw = sc.tmp<double>(nl * MOOR_LW_N);
+    A.sw = sc.tmp<double>(nl * ARR_SW_N);
+    if (chains == 2) A.bw = sc.tmp<double>(nl * MOOR_BW_N);
+    A.C = sc.tmp<double>(na * n * n);
+    A.flags = sc.out<int>(moor_flags, na);
+    ArrayModalAssembleArgs B;
+    memset(&B, 0, sizeof(B));
+    B.nArray = nArray; B.nUnit = nUnit;
+    B.M_unit = sc.in<double>(M_unit, na * nUnit * 36);
+    B.K_unit = sc.in<double>(K_unit, na * nUnit * 36);
+    B.dC = sc.in<double>(dC, na * n * n);
+    B.C_moor = A.C;
+    B.M = sc.tmp<double>(na * n * n);
+    B.C = C_out ? sc.out<double>(C_out, na * n * n) : sc.tmp<double>(na * n * n);
+    ArrayModalArgs E;
+    memset(&E, 0, sizeof(E));
+    E.n = nArray;
+    E.M = B.M; E.C = B.C;
+    E.fn = sc.out<double>(fn, na * n);
+    E.modes = sc.out<double>(modes, na * n * n);
+    E.flags = sc.out<int32_t>(flags, na);
+    E.moor_flags = A.flags;
+    if (int rc = sc.upload("array_modal_moored")) return rc;
+    if (sc.begin()) return -2;
+    A.chains = chains;
+    launch_array_moor(c->stream, A);
+    hipLaunchKernelGGL(k_array_modal_assemble, dim3((unsigned)((na * n * n + 255) / 256)), dim3(256), 0, c->stream, B);
+    launch_array_modal(c->stream, nUnit, E);
     return sc.finish();
 }
 

@@ -8,10 +8,14 @@
 //   balance A                       exact power-of-two row / column scaling (EISPACK balanc, dgebal's scaling step)
 //   Hessenberg                      Householder reduction with the transformations accumulated (orthes + ortran)
 //   Schur form + eigenvectors       Francis double-shift QR, back-substitution of the real quasi-triangular form
-//                                   (hqr2); at most 30*6 QR steps in all, then NO_CONVERGENCE
+//                                   (hqr2); at most 30 N QR steps in all, then NO_CONVERGENCE
 //   undo the balancing, unit 2-norm columns, sign: largest |component| positive (first index on ties)
-//   DOF order                       rows 5 .. 0 each claim the unclaimed column of largest |v| (first on ties); the
+//   DOF order                       rows N-1 .. 0 each claim the unclaimed column of largest |v| (first on ties); the
 //                                   list reversed: output column i is the column row i claimed
+//
+// modal_core_n<N> is this method for any N <= 36 as serial code: N = 6 is the rigid unit (modal_core, k_modal below); the
+// larger sizes are the arrays of 6 nUnit DOFs, which raftx_array_modal.h runs with one wavefront per system and checks
+// against this text on the host (tests/csrc/array_modal_driver.cpp).
 //
 // Data layout: one system per lane.  Everything indexed at run time (H, Z and the small vectors: the deflation
 // window and the pivot rows have run-time bounds) lives in LDS as [entry][lane] -- 8-byte words of consecutive lanes
@@ -31,12 +35,18 @@
 #define MODAL_NV 24
 #define MODAL_NE (2 * 36 + MODAL_NV)   // LDS words per lane: H, Z (M before the solve), the vectors
 
+// The claim mask of the DOF order: 32 bits up to 32 DOFs (the rigid unit's instance stays what it was), 64 above.
+template <bool WIDE> struct ModalMask { typedef unsigned type; };
+template <> struct ModalMask<true> { typedef unsigned long long type; };
+
 // S: H(i, j), Z(i, j), V(k) -- references into the system's storage.  On entry Z holds M_tot and H holds C_tot.
-// fn [6], modes [36] (row-major, column i = DOF i's mode).  Returns the RAFTX_MODAL_* flags.
-template <class S>
-RAFTX_MODAL_HD inline int modal_core(S &s, double *fn, double *modes) {
+// N DOFs (6 for one rigid unit, 6 nUnit <= 36 for an array: V holds 4 N words, d | e | scale | ort, at MODAL_V_* scaled
+// by N / 6).  fn [N], modes [N*N] (row-major, column i = DOF i's mode).  Returns the RAFTX_MODAL_* flags.
+template <int N, class S>
+RAFTX_MODAL_HD inline int modal_core_n(S &s, double *fn, double *modes) {
 #pragma clang fp contract(off)
-    const int n = MODAL_N;
+    const int n = N;
+    const int VD = 0, VE = N, VSC = 2 * N, VORT = 3 * N;      // d, e, scale, ort in V (MODAL_V_* at N = 6)
     const double eps = 2.220446049250313e-16;            // 2^-52
     int flags = 0;
     for (int i = 0; i < n; i++)
@@ -72,7 +82,7 @@ RAFTX_MODAL_HD inline int modal_core(S &s, double *fn, double *modes) {
                 s.H(i, j) = t / s.Z(i, i);
             }
         // ---- balancing: powers of two only, so the scaled matrix is exactly similar
-        for (int i = 0; i < n; i++) s.V(MODAL_V_SC + i) = 1.0;
+        for (int i = 0; i < n; i++) s.V(VSC + i) = 1.0;
         for (int sweep = 0; sweep < 64; sweep++) {
             bool noconv = false;
             for (int i = 0; i < n; i++) {
@@ -87,7 +97,7 @@ RAFTX_MODAL_HD inline int modal_core(S &s, double *fn, double *modes) {
                 while (c >= g) { f = f / 2.0; c = c / 4.0; }
                 if ((c + r) / f < 0.95 * tot) {
                     const double gi = 1.0 / f;
-                    s.V(MODAL_V_SC + i) = s.V(MODAL_V_SC + i) * f;
+                    s.V(VSC + i) = s.V(VSC + i) * f;
                     noconv = true;
                     for (int j = 0; j < n; j++) s.H(i, j) = s.H(i, j) * gi;
                     for (int j = 0; j < n; j++) s.H(j, i) = s.H(j, i) * f;
@@ -103,26 +113,26 @@ RAFTX_MODAL_HD inline int modal_core(S &s, double *fn, double *modes) {
                 double h = 0.0;
                 for (int i = n - 1; i >= m; i--) {
                     const double o = s.H(i, m - 1) / scale;
-                    s.V(MODAL_V_ORT + i) = o;
+                    s.V(VORT + i) = o;
                     h = h + o * o;
                 }
                 double g = sqrt(h);
-                if (s.V(MODAL_V_ORT + m) > 0) g = -g;
-                h = h - s.V(MODAL_V_ORT + m) * g;
-                s.V(MODAL_V_ORT + m) = s.V(MODAL_V_ORT + m) - g;
+                if (s.V(VORT + m) > 0) g = -g;
+                h = h - s.V(VORT + m) * g;
+                s.V(VORT + m) = s.V(VORT + m) - g;
                 for (int j = m; j < n; j++) {
                     double f = 0.0;
-                    for (int i = n - 1; i >= m; i--) f = f + s.V(MODAL_V_ORT + i) * s.H(i, j);
+                    for (int i = n - 1; i >= m; i--) f = f + s.V(VORT + i) * s.H(i, j);
                     f = f / h;
-                    for (int i = m; i < n; i++) s.H(i, j) = s.H(i, j) - f * s.V(MODAL_V_ORT + i);
+                    for (int i = m; i < n; i++) s.H(i, j) = s.H(i, j) - f * s.V(VORT + i);
                 }
                 for (int i = 0; i < n; i++) {
                     double f = 0.0;
-                    for (int j = n - 1; j >= m; j--) f = f + s.V(MODAL_V_ORT + j) * s.H(i, j);
+                    for (int j = n - 1; j >= m; j--) f = f + s.V(VORT + j) * s.H(i, j);
                     f = f / h;
-                    for (int j = m; j < n; j++) s.H(i, j) = s.H(i, j) - f * s.V(MODAL_V_ORT + j);
+                    for (int j = m; j < n; j++) s.H(i, j) = s.H(i, j) - f * s.V(VORT + j);
                 }
-                s.V(MODAL_V_ORT + m) = scale * s.V(MODAL_V_ORT + m);
+                s.V(VORT + m) = scale * s.V(VORT + m);
                 s.H(m, m - 1) = scale * g;
             }
         }
@@ -130,12 +140,12 @@ RAFTX_MODAL_HD inline int modal_core(S &s, double *fn, double *modes) {
             for (int j = 0; j < n; j++) s.Z(i, j) = (i == j) ? 1.0 : 0.0;
         for (int m = n - 2; m >= 1; m--) {
             if (s.H(m, m - 1) != 0.0) {
-                for (int i = m + 1; i < n; i++) s.V(MODAL_V_ORT + i) = s.H(i, m - 1);
+                for (int i = m + 1; i < n; i++) s.V(VORT + i) = s.H(i, m - 1);
                 for (int j = m; j < n; j++) {
                     double g = 0.0;
-                    for (int i = m; i < n; i++) g = g + s.V(MODAL_V_ORT + i) * s.Z(i, j);
-                    g = (g / s.V(MODAL_V_ORT + m)) / s.H(m, m - 1);
-                    for (int i = m; i < n; i++) s.Z(i, j) = s.Z(i, j) + g * s.V(MODAL_V_ORT + i);
+                    for (int i = m; i < n; i++) g = g + s.V(VORT + i) * s.Z(i, j);
+                    g = (g / s.V(VORT + m)) / s.H(m, m - 1);
+                    for (int i = m; i < n; i++) s.Z(i, j) = s.Z(i, j) + g * s.V(VORT + i);
                 }
             }
         }
@@ -158,8 +168,8 @@ RAFTX_MODAL_HD inline int modal_core(S &s, double *fn, double *modes) {
             }
             if (l == nn) {                                // one root
                 s.H(nn, nn) = s.H(nn, nn) + exshift;
-                s.V(MODAL_V_D + nn) = s.H(nn, nn);
-                s.V(MODAL_V_E + nn) = 0.0;
+                s.V(VD + nn) = s.H(nn, nn);
+                s.V(VE + nn) = 0.0;
                 nn--;
                 iter = 0;
             } else if (l == nn - 1) {                     // two roots
@@ -172,11 +182,11 @@ RAFTX_MODAL_HD inline int modal_core(S &s, double *fn, double *modes) {
                 x = s.H(nn, nn);
                 if (q >= 0) {                             // a real pair: rotate it to triangular form
                     z = (p >= 0) ? p + z : p - z;
-                    s.V(MODAL_V_D + nn - 1) = x + z;
-                    s.V(MODAL_V_D + nn) = s.V(MODAL_V_D + nn - 1);
-                    if (z != 0.0) s.V(MODAL_V_D + nn) = x - w / z;
-                    s.V(MODAL_V_E + nn - 1) = 0.0;
-                    s.V(MODAL_V_E + nn) = 0.0;
+                    s.V(VD + nn - 1) = x + z;
+                    s.V(VD + nn) = s.V(VD + nn - 1);
+                    if (z != 0.0) s.V(VD + nn) = x - w / z;
+                    s.V(VE + nn - 1) = 0.0;
+                    s.V(VE + nn) = 0.0;
                     x = s.H(nn, nn - 1);
                     sv = fabs(x) + fabs(z);
                     p = x / sv;
@@ -200,10 +210,10 @@ RAFTX_MODAL_HD inline int modal_core(S &s, double *fn, double *modes) {
                         s.Z(i, nn) = q * s.Z(i, nn) - p * z;
                     }
                 } else {                                  // a complex pair
-                    s.V(MODAL_V_D + nn - 1) = x + p;
-                    s.V(MODAL_V_D + nn) = x + p;
-                    s.V(MODAL_V_E + nn - 1) = z;
-                    s.V(MODAL_V_E + nn) = -z;
+                    s.V(VD + nn - 1) = x + p;
+                    s.V(VD + nn) = x + p;
+                    s.V(VE + nn - 1) = z;
+                    s.V(VE + nn) = -z;
                     flags |= RAFTX_MODAL_COMPLEX;
                 }
                 nn -= 2;
@@ -318,7 +328,7 @@ RAFTX_MODAL_HD inline int modal_core(S &s, double *fn, double *modes) {
             // ---- eigenvectors of the (now real upper triangular) Schur form, then back to A's basis
             if (norm != 0.0) {
                 for (int k = n - 1; k >= 0; k--) {
-                    const double lam = s.V(MODAL_V_D + k);
+                    const double lam = s.V(VD + k);
                     s.H(k, k) = 1.0;
                     for (int i = k - 1; i >= 0; i--) {
                         const double wd = s.H(i, i) - lam;
@@ -339,7 +349,7 @@ RAFTX_MODAL_HD inline int modal_core(S &s, double *fn, double *modes) {
                     }
             }
             for (int i = 0; i < n; i++) {             // the balancing undone, unit 2-norm, the sign convention
-                const double sc = s.V(MODAL_V_SC + i);
+                const double sc = s.V(VSC + i);
                 for (int j = 0; j < n; j++) s.Z(i, j) = s.Z(i, j) * sc;
             }
             for (int j = 0; j < n; j++) {
@@ -355,7 +365,7 @@ RAFTX_MODAL_HD inline int modal_core(S &s, double *fn, double *modes) {
                 for (int i = 0; i < n; i++) s.Z(i, j) = s.Z(i, j) * f;
             }
             for (int j = 0; j < n; j++)
-                if (!(s.V(MODAL_V_D + j) > 0.0)) flags |= RAFTX_MODAL_NONPOSITIVE;
+                if (!(s.V(VD + j) > 0.0)) flags |= RAFTX_MODAL_NONPOSITIVE;
         }
     }
     if (flags & ~RAFTX_MODAL_SMALL_DIAG) {
@@ -364,22 +374,27 @@ RAFTX_MODAL_HD inline int modal_core(S &s, double *fn, double *modes) {
         for (int i = 0; i < n * n; i++) modes[i] = nan;
         return flags;
     }
-    // ---- the reference's DOF order: row i (5 .. 0) claims the unclaimed column of largest |v[i, :]|
-    unsigned claimed = 0;
+    // ---- the reference's DOF order: row i (N-1 .. 0) claims the unclaimed column of largest |v[i, :]|
+    typename ModalMask<(N > 32)>::type claimed = 0;
+    const typename ModalMask<(N > 32)>::type one = 1;
     for (int i = n - 1; i >= 0; i--) {
         int best = -1;
         double bv = -1.0;
         for (int j = 0; j < n; j++) {
-            if (claimed & (1u << j)) continue;
+            if (claimed & (one << j)) continue;
             const double a = fabs(s.Z(i, j));
             if (a > bv) { bv = a; best = j; }
         }
-        claimed |= 1u << best;
-        fn[i] = sqrt(s.V(MODAL_V_D + best)) / 2.0 / 3.141592653589793;
+        claimed |= one << best;
+        fn[i] = sqrt(s.V(VD + best)) / 2.0 / 3.141592653589793;
         for (int r2 = 0; r2 < n; r2++) modes[r2 * n + i] = s.Z(r2, best);
     }
     return flags;
 }
+
+// The rigid unit's instance, what k_modal runs.
+template <class S>
+RAFTX_MODAL_HD inline int modal_core(S &s, double *fn, double *modes) { return modal_core_n<MODAL_N>(s, fn, modes); }
 
 #ifdef __HIPCC__
 // Storage of one lane's system in the block's LDS: word e of lane t at sm[e * BS + t].

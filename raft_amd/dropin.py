@@ -125,7 +125,7 @@ class Engine:
         """raft_fowt.py:1664-1729 / raft_model.py:472-540 after the assembly: viability message, one raftx_modal_batch
         call, the reference's errors, outPath / display."""
         message = ''
-        for i in range(6):
+        for i in range(len(M_tot)):
             if M_tot[i, i] < 1.0:
                 message += f'Diagonal entry {i} of system mass matrix is less than 1 ({M_tot[i,i]}). '
             if C_tot[i, i] < 1.0:
@@ -133,7 +133,10 @@ class Engine:
         if len(message) > 0:
             raise RuntimeError('System matrices computed by RAFT have one or more small or negative diagonals: ' + message)
         from ._abi import MODAL_NONPOSITIVE, MODAL_COMPLEX, MODAL_SINGULAR_M, MODAL_NO_CONVERGENCE
-        r = self.ctx.modal_batch(M_tot[None], C_tot[None])
+        if len(M_tot) == 6:
+            r = self.ctx.modal_batch(M_tot[None], C_tot[None])
+        else:                                                # an array: all 6 nUnit DOFs (include/raftx_array_modal.h)
+            r = self.ctx.array_modal_batch(M_tot[None], C_tot[None])
         fl = int(r["flags"][0])
         if fl & (MODAL_COMPLEX | MODAL_SINGULAR_M | MODAL_NO_CONVERGENCE):
             raise UnsupportedFOWT("solveEigen: the eigen problem has %s (device flags %d)" % (
@@ -169,10 +172,45 @@ class Engine:
         return self._eigen(np.asarray(M_tot, dtype=float), C_tot, display, outPath, getattr(fowt, "write_modes_json", None),
                            "Mode        1         2         3         4         5         6")
 
-    def solveEigen(self, model, display=0, outPath=None):
-        """Model.solveEigen (raft_model.py:436-547) for one rigid unit without an array mooring system; sets
-        model.results['eigen'].  Arrays and units with more than 6 DOFs raise UnsupportedFOWT."""
+    def _solveEigen_array(self, model, display, outPath):
+        """Model.solveEigen for an array of rigid units (raft_model.py:450-547): the block-diagonal unit matrices plus the
+        array mooring system's ms.getCoupledStiffnessA(lines_only=True) over all 6 nFOWT DOFs, one raftx_array_modal_batch
+        call.  moorMod 2 (the dynamic line matrices) and units with more than 6 DOFs raise UnsupportedFOWT."""
+        from ._abi import ARRAY_MAX_UNIT
         fowts = list(model.fowtList)
+        for fowt in fowts:
+            self._eigen_unit(fowt, "Model.solveEigen")
+        if not 1 <= len(fowts) <= ARRAY_MAX_UNIT:
+            raise UnsupportedFOWT("Model.solveEigen: arrays of 1 to %d units are covered (got %d)" % (ARRAY_MAX_UNIT, len(fowts)))
+        ms = getattr(model, "ms", None)
+        if ms and int(getattr(model, "moorMod", 0)) == 2:
+            raise UnsupportedFOWT("Model.solveEigen: an array mooring system with moorMod 2 (dynamic line matrices) is not covered")
+        n = 6 * len(fowts)
+        M_tot = np.zeros([n, n])
+        C_tot = np.zeros([n, n])
+        for i, fowt in enumerate(fowts):
+            i1, i2 = 6 * i, 6 * (i + 1)
+            M_tot[i1:i2, i1:i2] += fowt.M_struc + fowt.A_hydro_morison + fowt.A_BEM[:, :, 0]
+            C_tot[i1:i2, i1:i2] += fowt.C_struc + fowt.C_hydro + fowt.C_moor + fowt.C_elast
+            C_tot[i1 + 5, i1 + 5] += fowt.yawstiff
+        if ms:
+            C_tot += ms.getCoupledStiffnessA(lines_only=True)
+        return self._eigen(M_tot, C_tot, display, outPath, getattr(model, "write_modes_json", None),
+                           "Mode   " + "".join([f"{i+10:3d}" for i in range(6)]))
+
+    def solveEigen(self, model, display=0, outPath=None, arrays=False):
+        """Model.solveEigen (raft_model.py:436-547); sets model.results['eigen'].  By default one rigid unit without an array
+        mooring system: arrays raise UnsupportedFOWT.  ``arrays=True`` also covers arrays of rigid units with an array mooring
+        system of moorMod 0 or 1, over all 6 nFOWT DOFs.  Units with more than 6 DOFs raise UnsupportedFOWT either way."""
+        fowts = list(model.fowtList)
+        if arrays and (len(fowts) != 1 or getattr(model, "ms", None)):
+            fns, modes = self._solveEigen_array(model, display, outPath)
+            if not hasattr(model, "results") or model.results is None:
+                model.results = {}
+            model.results['eigen'] = {}
+            model.results['eigen']['frequencies'] = fns
+            model.results['eigen']['modes'] = modes
+            return fns, modes
         if len(fowts) != 1 or getattr(model, "ms", None):
             raise UnsupportedFOWT("Model.solveEigen: arrays (%d units%s) are not covered" % (
                 len(fowts), ", array mooring system" if getattr(model, "ms", None) else ""))
@@ -1522,8 +1560,8 @@ def solveDynamics(model, case, tol=0.01, conv_plot=0, RAO_plot=0, display=0):
                                          RAO_plot=RAO_plot, display=display)
 
 
-def solveEigen(model, display=0, outPath=None):
-    return _default_engine.solveEigen(model, display=display, outPath=outPath)
+def solveEigen(model, display=0, outPath=None, arrays=False):
+    return _default_engine.solveEigen(model, display=display, outPath=outPath, arrays=arrays)
 
 
 def fowt_solveEigen(fowt, display=0, outPath=None):

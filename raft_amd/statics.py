@@ -105,3 +105,42 @@ def array_mean_pose(ctx, K_hs, F0, lines, locations, depth, F_env=None, tol=None
     else:
         x_ref = np.broadcast_to(loc, (nA, nU, 6))
     return ArrayMeanPose(ctx.array_mean_pose(K_hs, F0, np.ascontiguousarray(x_ref), depth, lines, F_env=F_env, tol=tol, max_iter=max_iter))
+
+
+MODAL_FLAG_NAMES = {1: "small diagonal", 2: "eigenvalue <= 0", 4: "complex eigenvalues", 8: "singular mass matrix",
+                    16: "QR iteration not converged"}
+
+
+class ArrayModes:
+    """Result of ``array_modes``: fn [nA,n] (Hz) and periods [nA,n] (s) in DOF order (n = 6 nUnit, unit-major), modes [nA,n,n]
+    (column j: the unit-norm mode of fn[j]), C [nA,n,n] (the stiffness the modes belong to: blockdiag(K_hs) + the array
+    mooring stiffness at the pose), flags [nA] (the eigen solver's), moor_flags [nA] (the lines').  An array with a mooring
+    flag, or an eigen flag other than "small diagonal", is NaN."""
+
+    def __init__(self, res):
+        self.fn, self.modes, self.C = res["fn"], res["modes"], res["C"]
+        self.flags, self.moor_flags = res["flags"], res["moor_flags"]
+
+    @property
+    def periods(self):
+        return 1.0 / self.fn
+
+    @property
+    def ok(self):
+        """[nA] bool: no line was flagged and the eigen analysis returned numbers."""
+        return (self.moor_flags == 0) & ((self.flags & ~1) == 0)
+
+    def describe_flags(self, a):
+        names = dict(FLAG_NAMES)
+        names[mooring.FLAG_GROUNDED] = "line on or below the seabed"
+        return ([name for bit, name in names.items() if int(self.moor_flags[a]) & bit] +
+                [name for bit, name in MODAL_FLAG_NAMES.items() if int(self.flags[a]) & bit])
+
+
+def array_modes(ctx, M_unit, K_hs, lines, pose, depth, dC=None):
+    """Natural frequencies and modes of every moored array over all 6 nUnit DOFs at the given poses, composed on the device
+    (include/raftx_array_modal.h; Model.solveEigen of a farm, raft_model.py:436-547).  ``M_unit`` [nA,nUnit,6,6] (structure +
+    added mass per unit), ``K_hs`` [nA,nUnit,6,6] (each unit's own stiffness), ``lines`` [nA,nRow,16] array rows
+    (raft_amd.mooring.array_lines), ``pose`` [nA,nUnit,6] (``array_mean_pose(...).pose`` when it is not known), ``dC``
+    [nA,n,n] or None: further stiffness over all DOFs."""
+    return ArrayModes(ctx.array_modal_moored(M_unit, K_hs, lines, pose, depth, dC=dC))
