@@ -5,7 +5,8 @@
  * numpy.linalg.eig, and the DOF claim over rows n-1 .. 0.  The method, the flags, the unit 2-norm modes and their sign
  * convention are those of raftx_modal.h; SMALL_DIAG looks at all n diagonals and the QR step cap is 30 n.  With nUnit == 1 the
  * results are those of raftx_modal_batch, bit for bit.  A system's bits do not depend on its place in the batch, on the batch
- * size or on the other systems.  Flexible units (nDOF != 6) are not covered.
+ * size or on the other systems.  Flexible units (nDOF != 6) are not covered
+ * here: a single unit with flexible members is raftx_flex_modal.h.
  *
  * Kept out of raftx.h as raftx_modal.h and raftx_array_mooring.h are: the CPU oracle has no eigen solver.
  */

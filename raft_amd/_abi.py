@@ -63,6 +63,9 @@ ARRAY_MOORING_EXPORTS = ("raftx_array_mooring_lines", "raftx_array_mean_pose")
 # include/raftx_array_modal.h: eigen analysis of moored arrays over all 6 nUnit DOFs, the device library only
 ARRAY_MODAL_EXPORTS = ("raftx_array_modal_batch", "raftx_array_modal_moored")
 ARRAY_MAX_UNIT = 6
+# include/raftx_flex_modal.h: eigen analysis of units with flexible members (any n up to FLEX_MODAL_MAX_N), the device library only
+FLEX_MODAL_EXPORTS = ("raftx_flex_modal_batch",)
+FLEX_MODAL_MAX_N = 256   # RAFTX_FLEX_MODAL_MAX_N
 ML_UNIT_B, ML_UNIT_A, ARRAY_MAX_UNIT = 11, 12, 6   # RAFTX_ML_UNIT_B, RAFTX_ML_UNIT_A, RAFTX_ARRAY_MAX_UNIT
 MOOR_BAD_LINE, MOOR_VERTICAL, MOOR_SLACK, MOOR_NO_CONVERGENCE = 1, 2, 4, 8
 MOOR_GROUNDED = 64
@@ -199,6 +202,10 @@ class RaftxLib:
             L.raftx_array_modal_batch.restype = C.c_int
             L.raftx_array_modal_moored.argtypes = [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_double, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]
             L.raftx_array_modal_moored.restype = C.c_int
+        self.has_flex_modal = all(hasattr(L, s) for s in FLEX_MODAL_EXPORTS)
+        if self.has_flex_modal:
+            L.raftx_flex_modal_batch.argtypes = [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp]
+            L.raftx_flex_modal_batch.restype = C.c_int
         self.has_current = all(hasattr(L, s) for s in CURRENT_EXPORTS)
         if self.has_current:
             L.raftx_current_loads.argtypes = [_vp, C.c_int, _vp, _vp, _vp, C.c_double, C.c_double, _vp]
@@ -949,6 +956,24 @@ class Context:
         self._check(L.raftx_array_modal_moored(self._h, nA, nU, lines.shape[1], _ptr(lines), _ptr(pose), float(depth), _ptr(M_unit),
                                                _ptr(K_unit), _ptr(dC), _ptr(out["fn"]), _ptr(out["modes"]), _ptr(out["C"]),
                                                _ptr(out["flags"]), _ptr(out["moor_flags"])), "raftx_array_modal_moored")
+        return out
+
+    # ------------------------------------------------------------- eigen analysis of flexible units (include/raftx_flex_modal.h)
+    def flex_modal_batch(self, M, C_, n_modes=None):
+        """Natural frequencies [Hz] and modes of systems of any n DOFs, 6 <= n <= FLEX_MODAL_MAX_N (raftx_flex_modal_batch):
+        M, C [nSys,n,n] summed M_tot / C_tot; dict(fn [nSys,n] ascending, modes [nSys,n,n_modes] (column j: mode of fn[j], the
+        n_modes lowest; None: all n), flags [nSys] (MODAL_*))."""
+        if not self.rlib.has_flex_modal:
+            raise RaftxError("flex_modal_batch: %s does not implement include/raftx_flex_modal.h (the device library does)" % self.rlib.path)
+        M, C_ = _f64(M), _f64(C_)
+        if M.ndim != 3 or M.shape[1] != M.shape[2] or C_.shape != M.shape:
+            raise ValueError("M, C have shapes %s, %s, expected [nSys,n,n]" % (M.shape, C_.shape))
+        nS, n = M.shape[:2]
+        m = n if n_modes is None else int(n_modes)
+        out = dict(fn=np.empty((nS, n)), modes=np.empty((nS, n, max(m, 0))), flags=np.zeros(nS, dtype=np.int32))
+        self._check(self.rlib.lib.raftx_flex_modal_batch(self._h, nS, n, m, _ptr(M), _ptr(C_), _ptr(out["fn"]),
+                                                         _ptr(out["modes"]) if m > 0 else None, _ptr(out["flags"])),
+                    "raftx_flex_modal_batch")
         return out
 
     def sweep_mean_pose(self, handle, lines=None, C_extra=None, F_extra=None, F_env=None, tol=None, max_iter=0):

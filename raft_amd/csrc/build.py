@@ -24,6 +24,7 @@ def build(force=False, verbose=False, extra=()):
             os.path.join(HERE, "..", "..", "include", "raftx_statics.h"),
             os.path.join(HERE, "..", "..", "include", "raftx_array_mooring.h"),
             os.path.join(HERE, "..", "..", "include", "raftx_array_modal.h"),
+            os.path.join(HERE, "..", "..", "include", "raftx_flex_modal.h"),
             os.path.join(HERE, "..", "..", "include", "raftx_launch.h"), os.path.abspath(__file__)]
     deps += [os.path.join(HERE, f) for f in os.listdir(HERE) if f.endswith(".h")]
     if (not force) and os.path.exists(OUT) and all(os.path.getmtime(OUT) >= os.path.getmtime(d) for d in deps):

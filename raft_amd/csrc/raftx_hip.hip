@@ -50,6 +50,7 @@
 #include "../../include/raftx_statics.h"
 #include "../../include/raftx_array_mooring.h"
 #include "../../include/raftx_array_modal.h"
+#include "../../include/raftx_flex_modal.h"
 #include "../../include/raftx_launch.h"
 
 // roctx ranges around the phases of the host side: named spans for `rocprofv3 --marker-trace`.
@@ -98,6 +99,7 @@ struct RangeScope {
 #include "raftx_statics.h"
 #include "raftx_array_mooring.h"
 #include "raftx_array_modal.h"
+#include "raftx_flex_modal.h"
 
 // Coupled array solve (raft_model.py:1164-1236): Xi = Z_sys^-1 F for every (system, bin).  One wavefront per
 // (system, bin), NBIN (1, 2 or 4: what fits LDS) consecutive bins per workgroup so that the loads of one matrix entry
@@ -4868,6 +4870,46 @@ extern "C" int raftx_array_modal_moored(raftx_ctx *c, int nArray, int nUnit, int
     launch_array_moor(c->stream, A);
     hipLaunchKernelGGL(k_array_modal_assemble, dim3((unsigned)((na * n * n + 255) / 256)), dim3(256), 0, c->stream, B);
     launch_array_modal(c->stream, nUnit, E);
+    return sc.finish();
+}
+
+// ---- eigen analysis of units with flexible members (include/raftx_flex_modal.h, raftx_flex_modal.h)
+extern "C" int raftx_flex_modal_batch(raftx_ctx *c, int nSys, int n, int nModes, const double *M, const double *C, double *fn,
+                                      double *modes, int32_t *flags) {
+    if (!c) return -1;
+    if (n < 6 || n > RAFTX_FLEX_MODAL_MAX_N) FAIL(c, "flex_modal_batch: n must be 6 to %d (got %d)", RAFTX_FLEX_MODAL_MAX_N, n);
+    if (nModes < 0 || nModes > n) FAIL(c, "flex_modal_batch: nModes must be 0 to n = %d (got %d)", n, nModes);
+    if (nSys < 0) FAIL(c, "flex_modal_batch: nSys must not be negative (got %d)", nSys);
+    if (nSys > 0 && (!M || !C || !fn || !flags || (nModes > 0 && !modes))) FAIL(c, "flex_modal_batch: bad arguments");
+    if (nSys == 0) return 0;
+    HIPCHK(c, hipSetDevice(c->device));
+    // the workgroups of the call: a few per CU, each with its own H | X | Z workspace; RAFTX_FLEX_MODAL_GRID (tests) overrides
+    if (!c->nCU) {
+        hipDeviceProp_t pr;
+        HIPCHK(c, hipGetDeviceProperties(&pr, c->device));
+        c->nCU = pr.multiProcessorCount > 0 ? pr.multiProcessorCount : 256;
+    }
+    long grid = (long)FLEX_MODAL_WG_PER_CU * c->nCU;
+    if (const char *env = getenv("RAFTX_FLEX_MODAL_GRID"))
+        if (atol(env) > 0) grid = std::min(atol(env), 65535L);
+    grid = std::min<long>(grid, nSys);
+    Scratch sc(c);
+    const size_t ns = (size_t)nSys, nn = (size_t)n * n;
+    FlexModalArgs A;
+    memset(&A, 0, sizeof(A));
+    A.nSys = nSys;
+    A.n = n;
+    A.nModes = nModes;
+    A.pitch = flex_modal_pitch(n);
+    A.M = sc.in<double>(M, ns * nn);
+    A.C = sc.in<double>(C, ns * nn);
+    A.fn = sc.out<double>(fn, ns * n);
+    A.modes = nModes ? sc.out<double>(modes, ns * n * nModes) : nullptr;
+    A.flags = sc.out<int32_t>(flags, ns);
+    A.work = sc.tmp<double>((size_t)grid * 3 * n * A.pitch);
+    if (int rc = sc.upload("flex_modal_batch")) return rc;
+    if (sc.begin()) return -2;
+    hipLaunchKernelGGL(k_flex_modal, dim3((unsigned)grid), dim3(FLEX_MODAL_THREADS), 0, c->stream, A);
     return sc.finish();
 }
 

@@ -117,13 +117,22 @@ class Engine:
 
     # ------------------------------------------------------------------ eigen analysis (include/raftx_modal.h)
     @staticmethod
-    def _eigen_unit(fowt, what):
-        if int(getattr(fowt, "nDOF", 6)) != 6:
+    def _eigen_unit(fowt, what, flexible=False):
+        """Refuses a unit the eigen analysis does not cover; True for a unit with flexible members under ``flexible=True``."""
+        n = int(getattr(fowt, "nDOF", 6))
+        if n == 6:
+            return False
+        if not flexible:
             raise UnsupportedFOWT("%s: units with %d reduced DOFs are not covered (rigid 6-DOF units only)" % (what, fowt.nDOF))
+        from ._abi import FLEX_MODAL_MAX_N
+        if not 6 < n <= FLEX_MODAL_MAX_N:
+            raise UnsupportedFOWT("%s: units with 7 to %d reduced DOFs are covered (got %d)" % (what, FLEX_MODAL_MAX_N, n))
+        return True
 
-    def _eigen(self, M_tot, C_tot, display, outPath, writer, mode_header):
+    def _eigen(self, M_tot, C_tot, display, outPath, writer, mode_header, flexible=False):
         """raft_fowt.py:1664-1729 / raft_model.py:472-540 after the assembly: viability message, one raftx_modal_batch
-        call, the reference's errors, outPath / display."""
+        call (raftx_flex_modal_batch with all n modes for a unit with flexible members: ascending, no DOF claim), the
+        reference's errors, outPath / display."""
         message = ''
         for i in range(len(M_tot)):
             if M_tot[i, i] < 1.0:
@@ -133,7 +142,9 @@ class Engine:
         if len(message) > 0:
             raise RuntimeError('System matrices computed by RAFT have one or more small or negative diagonals: ' + message)
         from ._abi import MODAL_NONPOSITIVE, MODAL_COMPLEX, MODAL_SINGULAR_M, MODAL_NO_CONVERGENCE
-        if len(M_tot) == 6:
+        if flexible:                                         # nDOF != 6 (include/raftx_flex_modal.h)
+            r = self.ctx.flex_modal_batch(M_tot[None], C_tot[None])
+        elif len(M_tot) == 6:
             r = self.ctx.modal_batch(M_tot[None], C_tot[None])
         else:                                                # an array: all 6 nUnit DOFs (include/raftx_array_modal.h)
             r = self.ctx.array_modal_batch(M_tot[None], C_tot[None])
@@ -158,10 +169,12 @@ class Engine:
             print("-----------------------------------------------------------")
         return fns, modes
 
-    def fowt_solveEigen(self, fowt, display=0, outPath=None):
+    def fowt_solveEigen(self, fowt, display=0, outPath=None, flexible=False):
         """FOWT.solveEigen (raft_fowt.py:1646-1729, with getStiffness :1627-1644): natural frequencies [Hz] and modes of
-        one rigid unit.  Modes have unit 2-norm with their largest component positive (the reference's sign is LAPACK's)."""
-        self._eigen_unit(fowt, "FOWT.solveEigen")
+        one rigid unit.  Modes have unit 2-norm with their largest component positive (the reference's sign is LAPACK's).
+        ``flexible=True`` also covers a unit with more than 6 reduced DOFs (raft_fowt.py:1705-1714: all nDOF frequencies
+        ascending, the modes as columns in that order); by default such a unit raises UnsupportedFOWT."""
+        flex = self._eigen_unit(fowt, "FOWT.solveEigen", flexible)
         M_tot = fowt.M_struc + fowt.A_hydro_morison + fowt.A_BEM[:, :, 0]
         C_tot = np.zeros([fowt.nDOF, fowt.nDOF])
         C_tot += fowt.C_moor
@@ -170,7 +183,7 @@ class Engine:
             C_tot += fowt.body.getStiffness()
         C_tot += fowt.C_struc + fowt.C_hydro + fowt.C_elast
         return self._eigen(np.asarray(M_tot, dtype=float), C_tot, display, outPath, getattr(fowt, "write_modes_json", None),
-                           "Mode        1         2         3         4         5         6")
+                           "Mode        1         2         3         4         5         6", flexible=flex)
 
     def _solveEigen_array(self, model, display, outPath):
         """Model.solveEigen for an array of rigid units (raft_model.py:450-547): the block-diagonal unit matrices plus the
@@ -198,10 +211,12 @@ class Engine:
         return self._eigen(M_tot, C_tot, display, outPath, getattr(model, "write_modes_json", None),
                            "Mode   " + "".join([f"{i+10:3d}" for i in range(6)]))
 
-    def solveEigen(self, model, display=0, outPath=None, arrays=False):
+    def solveEigen(self, model, display=0, outPath=None, arrays=False, flexible=False):
         """Model.solveEigen (raft_model.py:436-547); sets model.results['eigen'].  By default one rigid unit without an array
         mooring system: arrays raise UnsupportedFOWT.  ``arrays=True`` also covers arrays of rigid units with an array mooring
-        system of moorMod 0 or 1, over all 6 nFOWT DOFs.  Units with more than 6 DOFs raise UnsupportedFOWT either way."""
+        system of moorMod 0 or 1, over all 6 nFOWT DOFs.  Units with more than 6 DOFs raise UnsupportedFOWT by default;
+        ``flexible=True`` covers a SINGLE such unit without an array mooring system (raft_model.py:518-527: all nDOF
+        frequencies ascending).  Arrays of units with flexible members stay refused (the reference raises there too)."""
         fowts = list(model.fowtList)
         if arrays and (len(fowts) != 1 or getattr(model, "ms", None)):
             fns, modes = self._solveEigen_array(model, display, outPath)
@@ -215,14 +230,15 @@ class Engine:
             raise UnsupportedFOWT("Model.solveEigen: arrays (%d units%s) are not covered" % (
                 len(fowts), ", array mooring system" if getattr(model, "ms", None) else ""))
         fowt = fowts[0]
-        self._eigen_unit(fowt, "Model.solveEigen")
-        M_tot = np.zeros([6, 6])
-        C_tot = np.zeros([6, 6])
-        M_tot[0:6, 0:6] += fowt.M_struc + fowt.A_hydro_morison + fowt.A_BEM[:, :, 0]
-        C_tot[0:6, 0:6] += fowt.C_struc + fowt.C_hydro + fowt.C_moor + fowt.C_elast
+        flex = self._eigen_unit(fowt, "Model.solveEigen", flexible)
+        n = int(fowt.nDOF) if flex else 6
+        M_tot = np.zeros([n, n])
+        C_tot = np.zeros([n, n])
+        M_tot[0:n, 0:n] += fowt.M_struc + fowt.A_hydro_morison + fowt.A_BEM[:, :, 0]
+        C_tot[0:n, 0:n] += fowt.C_struc + fowt.C_hydro + fowt.C_moor + fowt.C_elast
         C_tot[5, 5] += fowt.yawstiff
         fns, modes = self._eigen(M_tot, C_tot, display, outPath, getattr(model, "write_modes_json", None),
-                                 "Mode   " + "".join([f"{i+10:3d}" for i in range(6)]))
+                                 "Mode   " + "".join([f"{i+10:3d}" for i in range(6)]), flexible=flex)
         if not hasattr(model, "results") or model.results is None:
             model.results = {}
         model.results['eigen'] = {}
@@ -1560,12 +1576,12 @@ def solveDynamics(model, case, tol=0.01, conv_plot=0, RAO_plot=0, display=0):
                                          RAO_plot=RAO_plot, display=display)
 
 
-def solveEigen(model, display=0, outPath=None, arrays=False):
-    return _default_engine.solveEigen(model, display=display, outPath=outPath, arrays=arrays)
+def solveEigen(model, display=0, outPath=None, arrays=False, flexible=False):
+    return _default_engine.solveEigen(model, display=display, outPath=outPath, arrays=arrays, flexible=flexible)
 
 
-def fowt_solveEigen(fowt, display=0, outPath=None):
-    return _default_engine.fowt_solveEigen(fowt, display=display, outPath=outPath)
+def fowt_solveEigen(fowt, display=0, outPath=None, flexible=False):
+    return _default_engine.fowt_solveEigen(fowt, display=display, outPath=outPath, flexible=flexible)
 
 
 def calcCurrentLoads(fowt, case):

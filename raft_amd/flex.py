@@ -144,6 +144,24 @@ class FlexSweep:
             except (ValueError, AttributeError):
                 pass
 
+    def natural_modes(self, ctx, n_modes=12, dM=None, dC=None):
+        """Natural frequencies and the lowest modes of every unit in one call (raftx_flex_modal_batch; raft_fowt.py:1705-1714
+        per unit): the eigen problem of u.M + dM and u.C + dC.  ``dM``, ``dC``: [nDOF,nDOF] for all units or [nUnit,nDOF,nDOF],
+        or None -- dM is where a caller adds A_BEM[:,:,0] in the first six DOFs (the units carry M_struc + A_hydro_morison).
+        {"fn": [nUnit,nDOF] Hz ascending, "modes": [nUnit,nDOF,n_modes] (column j: mode of fn[j]; None: all), "flags": [nUnit]
+        (raft_amd._abi.MODAL_*: a unit with any bit but SMALL_DIAG is NaN)}."""
+        nD, n = len(self.units), self.n
+        M = np.array([u.M for u in self.units])
+        C = np.array([u.C for u in self.units])
+        for base, add, name in ((M, dM, "dM"), (C, dC, "dC")):
+            if add is None:
+                continue
+            add = np.asarray(add, dtype=np.float64)
+            if add.shape not in ((n, n), (nD, n, n)):
+                raise ValueError("%s has shape %s, expected [%d,%d] or [%d,%d,%d]" % (name, add.shape, n, n, nD, n, n))
+            base += add
+        return ctx.flex_modal_batch(M, C, n_modes=n_modes)
+
     def run(self, ctx, want_Z=False, copy=True):
         """{"Xi": [nUnit,nCase,nHead,nDOF,nw], "niter", "flags" [nUnit,nCase] (1 = converged), "B_drag" [nUnit,nCase,nDOF,nDOF],
         "kernel_ms": (inertial excitation sweep, the fixed point's span on the device)}.  copy=False: Xi, B_drag (and Z) are
