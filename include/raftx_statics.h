@@ -19,7 +19,12 @@
  * crossing at the solved pose, per design and on the device (the reference's order: solveStatics, setPosition,
  * solveDynamics at the offset).
  *
- * Not covered: staticsMod / forcingMod 1 (hydrostatics and loads re-evaluated at the pose), flexible units (arrays with shared
+ * raftx_mean_pose_nonlinear (raftx_statics_nl.h, included at the end of this file) is the solve for staticsMod == 1
+ * (raft_model.py:705-712, :797-800): buoyancy and weight are re-evaluated from the member descriptors at every iterate instead
+ * of being linearised once at the reference pose.
+ *
+ * Not covered: forcingMod 1 (loads re-evaluated at the pose: it needs the rotor model), staticsMod 1 inside a sweep crossing
+ * (raftx_sweep_mean_pose is staticsMod 0; solve with raftx_mean_pose_nonlinear and prepare the crossing with that pose), flexible units (arrays with shared
  * lines have an entry of their own: raftx_array_mean_pose, include/raftx_array_mooring.h); in a crossing also the design's own current load as F_env (its strip tables do not exist before the
  * solve) and second-order tables at the solved pose.
  */
@@ -31,7 +36,8 @@
 /* flags [nDesign]: the RAFTX_MOOR_* bits of the iterate that raised them (raftx_mooring.h: 1, 2, 4, 8 and 64, a composite
  * line grounded at that iterate), and */
 #define RAFTX_STATICS_POSE_CAP   16   /* max_iter steps were taken and the last one was not within tol */
-#define RAFTX_STATICS_SINGULAR   32   /* a zero or non-finite pivot, or a non-finite step */
+#define RAFTX_STATICS_SINGULAR   32   /* a zero or non-finite pivot, or a non-finite step or iterate */
+#define RAFTX_STATICS_BAD_MEMBER 128  /* raftx_mean_pose_nonlinear: a member the geometry pass refuses at an iterate */
 
 #ifdef __cplusplus
 extern "C" {
@@ -89,5 +95,7 @@ int raftx_sweep_mean_pose(raftx_ctx *ctx, int slot, int nLine, const double *lin
 #ifdef __cplusplus
 }
 #endif
+
+#include "raftx_statics_nl.h"   /* raftx_mean_pose_nonlinear, raftx_mean_pose_nonlinear_variants: staticsMod == 1 */
 
 #endif /* RAFTX_STATICS_H */

@@ -58,6 +58,8 @@ MOOR_MAX_SEG = 4   # rows of one composite line, at most (RAFTX_MOOR_MAX_SEG)
 ML_LEG, MOOR_MAX_LEG = 14, 3   # leg rows of a bridle: the mark and how many at most (RAFTX_ML_LEG, RAFTX_MOOR_MAX_LEG)
 # include/raftx_statics.h: the mean equilibrium pose, the device library only
 STATICS_EXPORTS = ("raftx_mean_pose", "raftx_sweep_mean_pose")
+# include/raftx_statics_nl.h (included by raftx_statics.h): staticsMod 1, hydrostatics at every iterate; the device library only
+STATICS_NL_EXPORTS = ("raftx_mean_pose_nonlinear", "raftx_mean_pose_nonlinear_variants")
 # include/raftx_array_mooring.h: arrays of units with shared lines, the device library only
 ARRAY_MOORING_EXPORTS = ("raftx_array_mooring_lines", "raftx_array_mean_pose")
 # include/raftx_array_modal.h: eigen analysis of moored arrays over all 6 nUnit DOFs, the device library only
@@ -189,6 +191,13 @@ class RaftxLib:
             L.raftx_mean_pose.restype = C.c_int
             L.raftx_sweep_mean_pose.argtypes = [_vp, C.c_int, C.c_int, _vp, C.c_int, _vp, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp]
             L.raftx_sweep_mean_pose.restype = C.c_int
+        self.has_statics_nl = all(hasattr(L, s) for s in STATICS_NL_EXPORTS)
+        if self.has_statics_nl:
+            tail = [C.c_double, C.c_double, _vp, C.c_int, _vp, C.c_double, C.c_int, C.c_int] + [_vp] * 6 + [C.c_int] + [_vp] * 10
+            L.raftx_mean_pose_nonlinear.argtypes = [_vp, C.c_int] + [_vp] * 6 + tail
+            L.raftx_mean_pose_nonlinear.restype = C.c_int
+            L.raftx_mean_pose_nonlinear_variants.argtypes = [_vp, C.c_int, _vp] + tail
+            L.raftx_mean_pose_nonlinear_variants.restype = C.c_int
         self.has_array_mooring = all(hasattr(L, s) for s in ARRAY_MOORING_EXPORTS)
         if self.has_array_mooring:
             L.raftx_array_mooring_lines.argtypes = [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_double, _vp, _vp, _vp, _vp, _vp, _vp]
@@ -847,6 +856,90 @@ class Context:
                                       _ptr(x_ref), _ptr(tol), int(max_iter), _ptr(out["pose"]), _ptr(out["C"]), _ptr(out["F"]),
                                       _ptr(out["T"]), _ptr(out["J"]), _ptr(out["F_res"]), _ptr(out["iterations"]), _ptr(out["flags"])),
                     "raftx_mean_pose")
+        return {k: v for k, v in out.items() if v is not None}
+
+    def mean_pose_nonlinear(self, depth, tables=None, params=None, lines=None, rho=1025.0, g=9.81, drho=None, point_masses=None,
+                            C_extra=None, F_extra=None, F_env=None, x_ref=None, tol=None, max_iter=0,
+                            want=("pose", "K_hs", "F0", "C", "F", "T", "J", "F_res", "iterations")):
+        """The mean pose of every design with the hydrostatics re-evaluated at every iterate (raftx_mean_pose_nonlinear /
+        _variants; Model.solveStatics, staticsMod 1 / forcingMod 0).  The designs are ``tables`` (member_off, members,
+        station_off, stations, cap_off, caps: a raft_amd.geometry batch) or the variants ``params`` [nD,nParam] of the
+        installed variant program; ``lines`` [nD,nLine,16], or None with ``params``: the installed mooring program.
+        ``drho`` [nD] or None; ``point_masses`` [nPM,4] or [nD,nPM,4] (mass, x, y, z); ``C_extra`` [6,6] or [nD,6,6],
+        ``F_extra`` [6] or [nD,6] -- shared or per design, all alike.  Returns the dict of ``mean_pose`` with K_hs
+        [nD,6,6] and F0 [nD,6] at the returned pose."""
+        if not self.rlib.has_statics_nl:
+            raise RaftxError("mean_pose_nonlinear: %s does not implement raftx_mean_pose_nonlinear (the device library does)"
+                             % self.rlib.path)
+        if (tables is None) == (params is None):
+            raise ValueError("mean_pose_nonlinear: give tables, or the params of the installed variant program")
+        L = self.rlib.lib
+        if params is not None:
+            if getattr(self, "_vprog", None) is None:
+                raise RaftxError("mean_pose_nonlinear: no program installed (variant_program first)")
+            params = _f64(params)
+            nD = params.shape[0]
+            params = _f64(params, (nD, self._vprog[3]), "params")
+        else:
+            member_off = np.ascontiguousarray(tables.member_off, dtype=np.int64)
+            station_off = np.ascontiguousarray(tables.station_off, dtype=np.int64)
+            nD = len(member_off) - 1
+            members = _f64(tables.members, (member_off[-1], 16), "members")
+            if len(station_off) != member_off[-1] + 1:
+                raise ValueError("station_off has %d entries, expected %d" % (len(station_off), member_off[-1] + 1))
+            stations = _f64(tables.stations, (station_off[-1], 16), "stations")
+            cap_off = caps = None
+            if getattr(tables, "cap_off", None) is not None:
+                cap_off = np.ascontiguousarray(tables.cap_off, dtype=np.int64)
+                if len(cap_off) != member_off[-1] + 1:
+                    raise ValueError("cap_off has %d entries, expected %d" % (len(cap_off), member_off[-1] + 1))
+                caps = _f64(tables.caps, (cap_off[-1], 4), "caps")
+                if caps.size == 0:
+                    caps = np.zeros((1, 4))
+        if lines is None:
+            if params is None or getattr(self, "_mprog", None) is None:
+                raise RaftxError("mean_pose_nonlinear: no lines given (and no params with an installed mooring program)")
+            nL = self._mprog[0]
+        else:
+            lines = _f64(lines)
+            if lines.ndim != 3 or lines.shape[0] != nD or lines.shape[2] != ML_N:
+                raise ValueError("lines has shape %s, expected [%d,nLine,%d]" % (lines.shape, nD, ML_N))
+            nL = lines.shape[1]
+        # the extras: shared (nX = 1) or one set per design (nX = nD), all of them alike
+        extras = dict(pm=point_masses, C=C_extra, F=F_extra)
+        base = dict(pm=2, C=2, F=1)
+        given = {k: np.asarray(v, dtype=np.float64) for k, v in extras.items() if v is not None}
+        nX = 0
+        if given:
+            per_design = any(a.ndim == base[k] + 1 for k, a in given.items())
+            nX = nD if per_design else 1
+            for k, a in given.items():
+                if a.ndim == base[k]:
+                    a = np.broadcast_to(a, (nX,) + a.shape)
+                given[k] = np.ascontiguousarray(a)
+        pm, Cx, Fx = given.get("pm"), given.get("C"), given.get("F")
+        nPM = 0 if pm is None else pm.shape[1]
+        pm = None if pm is None or nPM == 0 else _f64(pm, (nX, nPM, 4), "point_masses")
+        Cx = None if Cx is None else _f64(Cx, (nX, 6, 6), "C_extra")
+        Fx = None if Fx is None else _f64(Fx, (nX, 6), "F_extra")
+        drho = None if drho is None else _f64(drho, (nD,), "drho")
+        F_env = None if F_env is None else _f64(F_env, (nD, 6), "F_env")
+        x_ref = None if x_ref is None else _f64(x_ref, (nD, 6), "x_ref")
+        tol = None if tol is None else _f64(tol, (2,), "tol")
+        shapes = dict(pose=(nD, 6), K_hs=(nD, 6, 6), F0=(nD, 6), C=(nD, 6, 6), F=(nD, 6), T=(nD, 2 * nL), J=(nD, 2 * nL, 6),
+                      F_res=(nD, 6))
+        out = {k: (np.empty(shapes[k]) if k in want else None) for k in shapes}
+        out["iterations"] = np.zeros(nD, dtype=np.int32) if "iterations" in want else None
+        out["flags"] = np.zeros(nD, dtype=np.int32)
+        tail = (float(rho), float(g), _ptr(drho), int(nL), _ptr(lines), float(depth), int(nPM), int(nX), _ptr(pm), _ptr(Cx), _ptr(Fx),
+                _ptr(F_env), _ptr(x_ref), _ptr(tol), int(max_iter), _ptr(out["pose"]), _ptr(out["K_hs"]), _ptr(out["F0"]),
+                _ptr(out["C"]), _ptr(out["F"]), _ptr(out["T"]), _ptr(out["J"]), _ptr(out["F_res"]), _ptr(out["iterations"]),
+                _ptr(out["flags"]))
+        if params is not None:
+            self._check(L.raftx_mean_pose_nonlinear_variants(self._h, nD, _ptr(params), *tail), "raftx_mean_pose_nonlinear_variants")
+        else:
+            self._check(L.raftx_mean_pose_nonlinear(self._h, nD, _ptr(member_off), _ptr(members), _ptr(station_off), _ptr(stations),
+                                                    _ptr(cap_off), _ptr(caps), *tail), "raftx_mean_pose_nonlinear")
         return {k: v for k, v in out.items() if v is not None}
 
     # ------------------------------------------------------------- arrays with shared lines (include/raftx_array_mooring.h)

@@ -22,6 +22,7 @@ def build(force=False, verbose=False, extra=()):
             os.path.join(HERE, "..", "..", "include", "raftx_qtfgen.h"),
             os.path.join(HERE, "..", "..", "include", "raftx_mooring.h"),
             os.path.join(HERE, "..", "..", "include", "raftx_statics.h"),
+            os.path.join(HERE, "..", "..", "include", "raftx_statics_nl.h"),
             os.path.join(HERE, "..", "..", "include", "raftx_array_mooring.h"),
             os.path.join(HERE, "..", "..", "include", "raftx_array_modal.h"),
             os.path.join(HERE, "..", "..", "include", "raftx_flex_modal.h"),

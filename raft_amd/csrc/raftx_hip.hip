@@ -4653,6 +4653,174 @@ extern "C" int raftx_mean_pose(raftx_ctx *c, int nDesign, int nLine, const doubl
     return sc.finish();
 }
 
+// ---- staticsMod 1 (raftx_mean_pose_nonlinear / _variants; k_mean_pose_nl, raftx_statics.h)
+// what the two entries share besides the geometry: the checks that do not concern it ...
+struct NlCommon {
+    double rho, g;
+    const double *drho;
+    int nLine;
+    const double *lines;
+    double depth;
+    int nPM, nX;
+    const double *pm, *C_extra, *F_extra, *F_env, *x_ref, *tol;
+    int max_iter;
+    double *pose, *K_hs, *F0, *C_moor, *F_moor, *T, *J, *F_res;
+    int32_t *iterations, *flags;
+};
+static int nl_check(raftx_ctx *c, const char *who, int nDesign, const NlCommon &U, double *tolT, double *tolR) {
+    if (U.nLine < 1) FAIL(c, "%s: nLine must be positive (got %d)", who, U.nLine);
+    if (nDesign < 0) FAIL(c, "%s: nDesign must not be negative (got %d)", who, nDesign);
+    if (!U.flags) FAIL(c, "%s: bad arguments (flags is required)", who);
+    if (int rc = check_depth(c, who, U.depth)) return rc;
+    if (int rc = mean_pose_tol(c, who, U.tol, tolT, tolR)) return rc;
+    if (!std::isfinite(U.rho) || !std::isfinite(U.g) || !(U.rho > 0.0) || !(U.g > 0.0))
+        FAIL(c, "%s: rho and g must be positive and finite (got %g, %g)", who, U.rho, U.g);
+    if (U.nX != 0 && U.nX != 1 && U.nX != nDesign) FAIL(c, "%s: nX must be 0, 1 or nDesign (got %d)", who, U.nX);
+    if (U.nPM < 0) FAIL(c, "%s: nPM must not be negative (got %d)", who, U.nPM);
+    if (U.nX && U.nPM && !U.pm) FAIL(c, "%s: nPM=%d point masses and pm is NULL", who, U.nPM);
+    return 0;
+}
+// ... and the staging, the launch and the results, once the geometry fields of N are set.  maxMember: members of the largest design.
+template <class Rows>
+static void launch_mean_pose_nl(hipStream_t st, const MeanPoseNlArgs &N, dim3 grid) {
+    if (N.P.chains == 2) hipLaunchKernelGGL((k_mean_pose_nl<Rows, true, true>), grid, dim3(MP_THREADS), 0, st, N);
+    else if (N.P.chains) hipLaunchKernelGGL((k_mean_pose_nl<Rows, true, false>), grid, dim3(MP_THREADS), 0, st, N);
+    else hipLaunchKernelGGL((k_mean_pose_nl<Rows, false, false>), grid, dim3(MP_THREADS), 0, st, N);
+}
+static int nl_run(raftx_ctx *c, const char *who, Scratch &sc, MeanPoseNlArgs &N, int nDesign, size_t nMember, int maxMember,
+                  const NlCommon &U, const double *params, int chains, double tolT, double tolR) {
+    const size_t n = (size_t)nDesign, nl = n * U.nLine, nx = (size_t)U.nX;
+    StagedLines L;
+    if (stage_lines(c, c->stream, sc.bag, n, U.nLine, U.lines, U.lines ? nullptr : params, L)) return -2;
+    MeanPoseArgs &A = N.P;
+    A.lines = L.lines;
+    A.chains = chains;
+    A.F_env = sc.in<double>(U.F_env, n * 6);
+    A.x_ref = sc.in<double>(U.x_ref, n * 6);
+    A.lw = sc.tmp<double>(nl * MOOR_LW_N);
+    if (chains == 2) A.bw = sc.tmp<double>(nl * MOOR_BW_N);
+    A.pose = sc.out<double>(U.pose, n * 6);
+    A.C = sc.out<double>(U.C_moor, n * 36);
+    A.F = sc.out<double>(U.F_moor, n * 6);
+    A.T = sc.out<double>(U.T, nl * 2);
+    A.J = sc.out<double>(U.J, nl * 12);
+    A.Fres = sc.out<double>(U.F_res, n * 6);
+    A.iterations = sc.out<int>(U.iterations, n);
+    A.flags = sc.out<int>(U.flags, n);
+    N.rho = U.rho; N.g = U.g;
+    N.drho = sc.in<double>(U.drho, n);
+    N.nPM = U.nPM; N.nX = U.nX;
+    N.pm = sc.in<double>(U.pm, nx * 4 * (size_t)U.nPM);
+    N.Cx = sc.in<double>(U.C_extra, nx * 36);
+    N.Fx = sc.in<double>(U.F_extra, nx * 6);
+    N.mw = sc.tmp<double>(std::max<size_t>(nMember, 1) * FR_N);
+    N.mflag = sc.tmp<int>(std::max<size_t>(nMember, 1));
+    N.red = sc.tmp<double>(n * NL_RED_N);
+    N.K_out = sc.out<double>(U.K_hs, n * 36);
+    N.F0_out = sc.out<double>(U.F0, n * 6);
+    if (int rc = sc.upload(who)) return rc;
+    if (sc.begin()) return -2;
+    if (int rc = expand_lines(c, c->stream, n, U.nLine, L)) return rc;
+    A.nDesign = nDesign; A.nLine = U.nLine; A.G = mean_pose_nl_group(maxMember, U.nLine);
+    A.maxIter = U.max_iter > 0 ? U.max_iter : MP_MAX_IT;
+    A.depth = U.depth; A.tolT = tolT; A.tolR = tolR;
+    const int perBlock = MP_THREADS / A.G;
+    const dim3 grid((unsigned)((nDesign + perBlock - 1) / perBlock));
+    if (N.prog.params) launch_mean_pose_nl<GeomRowsProg>(c->stream, N, grid);
+    else launch_mean_pose_nl<GeomRowsPlain>(c->stream, N, grid);
+    return sc.finish();
+}
+extern "C" int raftx_mean_pose_nonlinear(raftx_ctx *c, int nDesign, const int64_t *memberOff, const double *members,
+                                         const int64_t *stationOff, const double *stations, const int64_t *capOff, const double *caps,
+                                         double rho, double g, const double *drho, int nLine, const double *lines, double depth, int nPM,
+                                         int nX, const double *pm, const double *C_extra, const double *F_extra, const double *F_env,
+                                         const double *x_ref, const double tol[2], int max_iter, double *pose, double *K_hs, double *F0,
+                                         double *C_moor, double *F_moor, double *T, double *J, double *F_res, int32_t *iterations,
+                                         int32_t *flags) {
+    if (!c) return -1;
+    const char *who = "mean_pose_nonlinear";
+    const NlCommon U{rho, g, drho, nLine, lines, depth, nPM, nX, pm, C_extra, F_extra, F_env, x_ref, tol, max_iter,
+                     pose, K_hs, F0, C_moor, F_moor, T, J, F_res, iterations, flags};
+    double tolT, tolR;
+    if (int rc = nl_check(c, who, nDesign, U, &tolT, &tolR)) return rc;
+    if (!lines) FAIL(c, "%s: lines is NULL (the mooring program belongs to raftx_mean_pose_nonlinear_variants)", who);
+    if (!memberOff || !stationOff) FAIL(c, "%s: bad arguments (memberOff and stationOff are required)", who);
+    int maxMember = 0;
+    for (int d = 0; d < nDesign; d++) {
+        if (memberOff[d + 1] < memberOff[d]) FAIL(c, "%s: member offsets not monotone at design %d", who, d);
+        maxMember = (int)std::min<int64_t>(std::max<int64_t>(maxMember, memberOff[d + 1] - memberOff[d]), 1 << 30);
+    }
+    const int64_t m0 = memberOff[0], nMember = memberOff[nDesign] - m0;
+    if (m0 < 0) FAIL(c, "%s: member offsets not monotone at design 0", who);
+    if (nMember >= ((int64_t)1 << 31)) FAIL(c, "%s: %lld members in one batch", who, (long long)nMember);
+    for (int64_t m = 0; m < nMember; m++) {
+        if (stationOff[m0 + m + 1] < stationOff[m0 + m]) FAIL(c, "%s: station offsets not monotone at member %lld", who, (long long)(m0 + m));
+        if (capOff && capOff[m0 + m + 1] < capOff[m0 + m]) FAIL(c, "%s: cap offsets not monotone at member %lld", who, (long long)(m0 + m));
+    }
+    const int64_t s0 = stationOff[m0], nSta = stationOff[m0 + nMember] - s0, c0 = capOff ? capOff[m0] : 0,
+                  nCap = capOff ? capOff[m0 + nMember] - c0 : 0;
+    if (s0 < 0 || c0 < 0) FAIL(c, "%s: station or cap offsets not monotone at member %lld", who, (long long)m0);
+    if ((nMember && !members) || (nSta && !stations) || (nCap && !caps)) FAIL(c, "%s: bad arguments (rows are NULL)", who);
+    int chains = 0;
+    if (int rc = check_lines(c, who, (size_t)nDesign, nLine, lines, &chains)) return rc;
+    if (nDesign == 0) return 0;
+    HIPCHK(c, hipSetDevice(c->device));
+    std::vector<int64_t> mo((size_t)nDesign + 1), so((size_t)nMember + 1), co(capOff ? (size_t)nMember + 1 : 0);
+    for (int d = 0; d <= nDesign; d++) mo[(size_t)d] = memberOff[d] - m0;
+    for (int64_t m = 0; m <= nMember; m++) {
+        so[(size_t)m] = stationOff[m0 + m] - s0;
+        if (capOff) co[(size_t)m] = capOff[m0 + m] - c0;
+    }
+    Scratch sc(c);
+    MeanPoseNlArgs N;
+    memset(&N, 0, sizeof(N));
+    N.memberOff = sc.in<int64_t>(mo.data(), mo.size());
+    N.stationOff = sc.in<int64_t>(so.data(), so.size());
+    N.capOff = capOff ? sc.in<int64_t>(co.data(), co.size()) : nullptr;
+    N.gm = sc.in<double>(members ? members + (size_t)m0 * RAFTX_GM_N : nullptr, (size_t)nMember * RAFTX_GM_N);
+    N.gs = sc.in<double>(stations ? stations + (size_t)s0 * RAFTX_GS_N : nullptr, (size_t)nSta * RAFTX_GS_N);
+    N.gc = sc.in<double>(caps ? caps + (size_t)c0 * RAFTX_GC_N : nullptr, (size_t)std::max<int64_t>(nCap, 1) * RAFTX_GC_N);
+    if (capOff && !N.gc) N.gc = sc.tmp<double>(RAFTX_GC_N);      // (no cap in the batch: a block nobody reads)
+    return nl_run(c, who, sc, N, nDesign, (size_t)nMember, maxMember, U, nullptr, chains, tolT, tolR);
+}
+extern "C" int raftx_mean_pose_nonlinear_variants(raftx_ctx *c, int nDesign, const double *params, double rho, double g,
+                                                  const double *drho, int nLine, const double *lines, double depth, int nPM, int nX,
+                                                  const double *pm, const double *C_extra, const double *F_extra, const double *F_env,
+                                                  const double *x_ref, const double tol[2], int max_iter, double *pose, double *K_hs,
+                                                  double *F0, double *C_moor, double *F_moor, double *T, double *J, double *F_res,
+                                                  int32_t *iterations, int32_t *flags) {
+    if (!c) return -1;
+    const char *who = "mean_pose_nonlinear_variants";
+    const VariantProg &P = c->vprog;
+    if (!P.nM) FAIL(c, "%s: no program (raftx_variant_program first)", who);
+    const NlCommon U{rho, g, drho, nLine, lines, depth, nPM, nX, pm, C_extra, F_extra, F_env, x_ref, tol, max_iter,
+                     pose, K_hs, F0, C_moor, F_moor, T, J, F_res, iterations, flags};
+    double tolT, tolR;
+    if (int rc = nl_check(c, who, nDesign, U, &tolT, &tolR)) return rc;
+    if (!params && nDesign && P.nP) FAIL(c, "%s: bad arguments (params [nDesign,%d] is required)", who, P.nP);
+    if (params && !all_finite(params, (size_t)nDesign * P.nP)) FAIL(c, "%s: a parameter value is not finite", who);
+    int chains = 0;
+    if (!lines) {
+        if (!c->mprog.nLine) FAIL(c, "%s: lines == NULL without a mooring program (raftx_mooring_program first)", who);
+        if (int rc = check_line_program(c, who, nLine, P.nP, true)) return rc;
+        chains = c->mprog.chains;
+    } else if (int rc = check_lines(c, who, (size_t)nDesign, nLine, lines, &chains))
+        return rc;
+    if (nDesign == 0) return 0;
+    if ((int64_t)nDesign * P.nM >= ((int64_t)1 << 31)) FAIL(c, "%s: %lld members in one batch", who, (long long)nDesign * P.nM);
+    HIPCHK(c, hipSetDevice(c->device));
+    Scratch sc(c);
+    MeanPoseNlArgs N;
+    memset(&N, 0, sizeof(N));
+    N.nM = P.nM;
+    N.stationOff = sc.in<int64_t>(P.hS.data(), P.hS.size());
+    N.capOff = P.has_caps ? sc.in<int64_t>(P.hC.data(), P.hC.size()) : nullptr;
+    variant_view(P, N.prog);
+    static const double no_param = 0.0;                          // (a program without parameters still marks "rows of the program")
+    N.prog.params = sc.in<double>(P.nP ? params : &no_param, P.nP ? (size_t)nDesign * P.nP : 1);
+    return nl_run(c, who, sc, N, nDesign, (size_t)nDesign * P.nM, P.nM, U, params, chains, tolT, tolR);
+}
+
 // ---- arrays of units with shared lines (include/raftx_array_mooring.h, raftx_array_mooring.h)
 // The records of an entry point `who`: the record errors of check_lines, then the unit fields of every row.  A value that is
 // not an integer (a NaN too) is refused here, so the kernels may index with it.

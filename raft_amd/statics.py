@@ -1,5 +1,5 @@
-"""The mean equilibrium pose of every design on the device (include/raftx_statics.h): Model.solveStatics for staticsMod 0 /
-forcingMod 0, rigid 6-DOF units with mooring lines of their own.
+"""The mean equilibrium pose of every design on the device (include/raftx_statics.h): Model.solveStatics for staticsMod 0
+and 1 / forcingMod 0, rigid 6-DOF units with mooring lines of their own.
 
 ``hydrostatics(ctx, ...)`` assembles K_hs and F0 of the resident design set from raftx_fetch_statics and the caller's
 terms that do not come from the geometry; ``mean_pose(ctx, ...)`` runs the one-launch Newton solve and returns a
@@ -9,20 +9,22 @@ import numpy as np
 
 from . import mooring
 
-FLAG_POSE_CAP, FLAG_SINGULAR = 16, 32
+FLAG_POSE_CAP, FLAG_SINGULAR, FLAG_BAD_MEMBER = 16, 32, 128
 FLAG_NAMES = {mooring.FLAG_BAD_LINE: "bad line", mooring.FLAG_VERTICAL: "vertical line", mooring.FLAG_SLACK: "slack line",
-              mooring.FLAG_NO_CONVERGENCE: "line not converged", FLAG_POSE_CAP: "pose iteration cap", FLAG_SINGULAR: "singular system"}
+              mooring.FLAG_NO_CONVERGENCE: "line not converged", FLAG_POSE_CAP: "pose iteration cap", FLAG_SINGULAR: "singular system",
+              FLAG_BAD_MEMBER: "member refused at an iterate"}
 
 
 class MeanPose:
     """Result of ``mean_pose``: pose [nD,6] (m, rad), C_moor [nD,6,6], F_moor [nD,6], T [nD,2 nLine] (ends A, then ends
     B), J [nD,2 nLine,6], F_res [nD,6] (the residual at the pose), iterations [nD], flags [nD].  A flagged design's rows
-    are NaN."""
+    are NaN.  With ``statics_mod=1`` also K_hs [nD,6,6] and F0 [nD,6], the hydrostatics at the pose (else None)."""
 
     def __init__(self, res):
         self.pose, self.C_moor, self.F_moor = res["pose"], res["C"], res["F"]
         self.T, self.J, self.F_res = res["T"], res["J"], res["F_res"]
         self.iterations, self.flags = res["iterations"], res["flags"]
+        self.K_hs, self.F0 = res.get("K_hs"), res.get("F0")
 
     @property
     def ok(self):
@@ -54,12 +56,45 @@ def hydrostatics(ctx, C_extra=None, F_extra=None, current=None):
     return np.ascontiguousarray(K_hs), np.ascontiguousarray(F0), F_env
 
 
-def mean_pose(ctx, K_hs, F0, lines=None, depth=None, program=None, params=None, F_env=None, x_ref=None, tol=None, max_iter=0):
-    """Newton's iteration on F0 + F_env - K_hs (x - x_ref) + F_moor(x) = 0 for every design in one launch.  Give either
-    ``lines`` [nD,nLine,16] (raft_amd.mooring.lines_from_design), or ``program`` (a MooringProgram, installed here unless it already is;
-    None keeps the installed one) with ``params`` [nD,nParam].  ``tol`` = (m, rad), None: 1e-9, 1e-10."""
+def mean_pose(ctx, K_hs=None, F0=None, lines=None, depth=None, program=None, params=None, F_env=None, x_ref=None, tol=None, max_iter=0,
+              statics_mod=0, designs=None, point_masses=None, drho=None, C_extra=None, F_extra=None, rho=1025.0, g=9.81):
+    """Newton's iteration on the mean equilibrium of every design in one launch.  Give either ``lines`` [nD,nLine,16]
+    (raft_amd.mooring.lines_from_design), or ``program`` (a MooringProgram, installed here unless it already is; None keeps
+    the installed one) with ``params`` [nD,nParam].  ``tol`` = (m, rad), None: 1e-9, 1e-10.
+
+    ``statics_mod=0``: F0 + F_env - K_hs (x - x_ref) + F_moor(x) = 0 with the hydrostatics ``K_hs``, ``F0`` linearised at
+    ``x_ref`` (``hydrostatics``).
+
+    ``statics_mod=1``: buoyancy and weight are re-evaluated from the geometry at every iterate.  ``designs`` is a
+    raft_amd.geometry batch (member_off, members, station_off, stations, cap_off, caps), or the variant parameters
+    [nD,nParam] of the variant program installed on ``ctx`` (they also feed the mooring program when ``lines`` is None).
+    ``K_hs`` / ``F0`` are not given; ``C_extra`` / ``F_extra`` are the CONSTANT terms ([6,6] / [6] or per design: C_elast,
+    f0_additional), ``point_masses`` [nPM,4] or [nD,nPM,4] (mass, x, y, z about the PRP), ``drho`` [nD] the ballast-density correction of a
+    trim made at ``x_ref``.  The result carries K_hs and F0 at the returned pose."""
     if depth is None:
         raise ValueError("mean_pose: the water depth is required")
+    if statics_mod not in (0, 1):
+        raise ValueError("mean_pose: statics_mod must be 0 or 1 (got %r)" % (statics_mod,))
+    if statics_mod == 1:
+        if K_hs is not None or F0 is not None:
+            raise ValueError("mean_pose: statics_mod=1 evaluates K_hs and F0 itself (constant terms: C_extra, F_extra)")
+        if designs is None:
+            raise ValueError("mean_pose: statics_mod=1 needs designs (a MemberTable batch, or variant parameters)")
+        variants = not hasattr(designs, "member_off")
+        if lines is None:
+            if not variants:
+                raise ValueError("mean_pose: statics_mod=1 on a MemberTable batch needs lines")
+            if params is not None and not np.array_equal(np.asarray(params, dtype=float), np.asarray(designs, dtype=float)):
+                raise ValueError("mean_pose: statics_mod=1 feeds the mooring program the variant parameters: params must be None or designs")
+            if program is not None and getattr(ctx, "_mprog_owner", None) is not program:
+                ctx.mooring_program(program)
+        elif params is not None or program is not None:
+            raise ValueError("mean_pose: lines and a mooring program exclude each other")
+        kw = dict(params=designs) if variants else dict(tables=designs)
+        return MeanPose(ctx.mean_pose_nonlinear(depth, lines=lines, rho=rho, g=g, drho=drho, point_masses=point_masses, C_extra=C_extra,
+                                                F_extra=F_extra, F_env=F_env, x_ref=x_ref, tol=tol, max_iter=max_iter, **kw))
+    if any(a is not None for a in (designs, point_masses, drho, C_extra, F_extra)):
+        raise ValueError("mean_pose: designs, point_masses, drho, C_extra and F_extra belong to statics_mod=1")
     if lines is None:
         if params is None:
             raise ValueError("mean_pose: give lines, or a mooring program's params")
